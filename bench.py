@@ -23,6 +23,11 @@ second (FLOPs are linear in the frame count; frames that two windows both comput
 achieved = their algorithmic FLOPs / their summed launch time, against the dense fp16 MFMA peak.
 Weights are synthetic (diffusers-shaped, seeded); inputs are synthetic noise/text embeddings.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes work of its own: the box
+probes before the warm-up and behind the timed steps, the shader-clock sampler, the same steps again with the CFG-shared
+prefix off (`ms_per_step_full_duplicate`) and the bounded CPU-oracle sample (`cpu_baseline`, with `rel_l2_vs_hip`).
+`--dump-outputs DIR` writes the latents the last timed step returned, as float32 `.npy` files (see `dump_outputs`).
 """
 import argparse
 import json
@@ -229,6 +234,24 @@ def copy_activity_of_a_step(step, i, lats):
         return {"step_copy_activity_error": f"{type(e).__name__}: {e}"[:200]}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, lats, rank, world):
+    """The latents the last timed step returned (what a caller of `step` receives), one float32 file per window:
+    `latents_rank{rank}_window{k}.npy`.  The ranks share DUMP_BUDGET_BYTES; a window that would exceed its share is
+    written as a fixed, seeded sample of its elements (flattened; the same indices in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (4 * world * max(len(lats), 1))
+    for k, lat in enumerate(lats):
+        a = lat.detach().float().cpu()
+        if a.numel() > cap:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(k))[:cap].sort().values
+            a = a.flatten()[idx]
+        np.save(os.path.join(out_dir, f"latents_rank{rank}_window{k}.npy"), a.numpy())
+
+
 def self_launch_command(argv, n, port):
     """The command a bare `python bench.py --gpus N` (N > 1, no launcher) re-runs itself under: one rank per GPU through
     torch.distributed.run on 127.0.0.1 — exactly what the driver's own multi-GPU command is."""
@@ -263,6 +286,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also take the box probes and the shader clock, time the steps again with the CFG-shared prefix off, "
+                         "and run the bounded CPU-oracle sample (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the latents of the last one to DIR/*.npy (float32)")
     ap.add_argument("--frames", type=int, default=0, help="override the total frame count of the configuration (dev aid)")
     ap.add_argument("--config", default=None, choices=["cfg2", "cfg3", "cfg4", "cfg5"],
                     help="BASELINE configuration to run (default: the one of the world size)")
@@ -270,7 +298,7 @@ def main():
                     help="with --rehearse-dist on one GPU: plan as if the job had this many ranks ...")
     ap.add_argument("--as-rank", type=int, default=0, help="... and run the windows of this rank")
     ap.add_argument("--cpu-frames", type=int, default=2,
-                    help="frames of the bounded CPU-baseline sample (0 = skip); 2 frames = ~13 s on 16 cores")
+                    help="with --full: frames of the bounded CPU-baseline sample (0 = skip); 2 frames = ~13 s on 16 cores")
     ap.add_argument("--shapes", type=int, default=0, help="also list the top-N GEMM shapes by time (dev aid)")
     ap.add_argument("--rehearse-dist", action="store_true",
                     help="N=1 only: run the multi-GPU code path (RCCL init, sharded weights, collectives) with world 1")
@@ -295,7 +323,7 @@ def main():
     ap.add_argument("--no-shared-prefix", action="store_true",
                     help="diagnostic (needs --rehearsal): every block computes both CFG items, as a forward on torch.cat([lat]*2) does")
     ap.add_argument("--no-duplicate-leg", action="store_true",
-                    help="skip the second timing of the same steps with the CFG-shared prefix off (`ms_per_step_full_duplicate`)")
+                    help="with --full: skip the second timing of the same steps with the CFG-shared prefix off (`ms_per_step_full_duplicate`)")
     ap.add_argument("--rehearse-copies", action="store_true",
                     help="with --rehearse-dist --as-world N on one GPU: issue every parameter gather as N copies (the host call count of a node)")
     ap.add_argument("--hog", type=int, default=0,
@@ -430,11 +458,11 @@ def main():
             out.append(sched.step_cfg(noise, t, lat, 7.5))
         return out
 
-    box = box_probe(dev) if rank == 0 else {}
+    box = box_probe(dev) if rank == 0 and args.full else {}
     for i in range(args.warmup):
         lats = step(i, lats)
     torch.cuda.reset_peak_memory_stats()
-    sclk = SclkSampler(local) if rank == 0 else None
+    sclk = SclkSampler(local) if rank == 0 and args.full else None
 
     def fence():
         torch.cuda.synchronize()
@@ -459,7 +487,7 @@ def main():
     dt = time.perf_counter() - t0
     if sclk is not None:
         box.update(sclk.stop())
-    if rank == 0:
+    if rank == 0 and args.full:
         # The probe once more right behind the timed steps, REPORTED ONLY: round 6 measured it on five boxes — it reads 1 453 to
         # 1 751 TFLOP/s (a sustained dense-MFMA stream runs into each part's power limit, 1.39-1.67 GHz) while the step differs by
         # 4.5 %, so it does not predict the step.  The reading BEFORE the warm-up (a short burst on a part that has just synthesised
@@ -471,12 +499,14 @@ def main():
     finite = all(bool(torch.isfinite(lat.float()).all()) for lat in lats)
     peak_gb = torch.cuda.max_memory_allocated() / 2 ** 30
     free_b, total_b = torch.cuda.mem_get_info(dev)            # device-wide (the reference's pynvml `used`, :41-45,262)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lats, rank, world)
     # The same K steps once more with the CFG-shared prefix OFF (every block computes both batch items, as a forward on
     # `torch.cat([lat]*2)` does): the line carries both times, so a reader sees what the product's default saves and that
     # the headline is not a step with work dropped — only a duplicate (same output bits, tests/test_unet_gpu.py).
     shared_on = bool(getattr(unet, "last_forward_shared_prefix", False))
     dt_dup = 0.0
-    if shared_on and not args.no_duplicate_leg:
+    if shared_on and args.full and not args.no_duplicate_leg:
         unet.share_cfg_prefix = False
         lats_d = step(args.warmup + args.steps, lats)           # warm the shapes of the duplicated form
         fence()
@@ -520,8 +550,9 @@ def main():
             # (profiles/monolithic_peaks.json, measured by tools/mem_profile.py --frames T); north star: <= 0.15 at N = 8
             "peak_hbm_frac_of_monolithic": round(peak_gb / mono, 4) if mono else None,
             "output_finite": finite,
-            "box": box,
         }
+        if args.full:
+            out["box"] = box
         # EXECUTED FLOPs: the shared prefix computes its blocks for one item, not two.  `path_tflops_per_gpu` / `path_mfma_frac`
         # — the fields tracked since round 1 — carry the EXECUTED work since round 6 (on the reference-equivalent
         # count a removed duplicate read as a utilisation gain); the reference-equivalent figures keep their own names.
@@ -631,7 +662,7 @@ def main():
             ach = tf_step * args.steps / dt
             out["roofline"] = {"bound": "mfma", "achieved": round(ach, 2), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
                                "frac": round(ach / PEAK_MFMA_TFLOPS, 4), "traffic": None, "kernel": "whole step"}
-        if world == 1 and args.cpu_frames > 0 and not args.rehearse_dist and cname == "cfg2":
+        if args.full and world == 1 and args.cpu_frames > 0 and not args.rehearse_dist and cname == "cfg2":
             hip_y = sd_cpu = None
             if not args.peaked:
                 # the HIP forward the oracle sample is compared with: this process's UNet on the sample's inputs

@@ -62,6 +62,27 @@ def test_bench_selects_the_baseline_configuration_of_the_world_size():
     assert plan(96, 8, 0, 4).ranges[-2:] == ((72, 88), (84, 96)) and len(plan(96, 8, 0, 4).ranges) == 8
 
 
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one float32 .npy per window, exact where it fits its share of the budget, a fixed
+    seeded sample of its elements where it does not (the same indices in every run)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 << 10)
+    g = torch.Generator().manual_seed(0)
+    lats = [torch.randn(1, 4, 2, 8, 16, generator=g).half(), torch.randn(1, 4, 16, 32, 32, generator=g).half()]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), lats, 0, 1)
+    small = np.load(tmp_path / "a" / "latents_rank0_window0.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, lats[0].float().numpy())
+    big = np.load(tmp_path / "a" / "latents_rank0_window1.npy")
+    assert big.dtype == np.float32 and big.shape == ((64 << 10) // 8,)
+    assert np.array_equal(big, np.load(tmp_path / "b" / "latents_rank0_window1.npy"))
+    assert np.isin(big, lats[1].float().numpy()).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < (64 << 10) + 1024
+
+
 def test_perf_guard_flags_a_slower_dominant_kernel(tmp_path):
     """tools/perf_guard.py: a guarded kernel whose average launch is > 4 % slower than the committed profile fails the run."""
     import subprocess

@@ -29,6 +29,16 @@ class GemmArgs(C.Structure):
     ]
 
 
+class ClipPreprocessArgs(C.Structure):
+    """Mirror of `vdx_clip_preprocess_args` (include/vdx.h)."""
+    _fields_ = [
+        ("frames", C.c_void_p), ("x_bounds", C.c_void_p), ("x_coeffs", C.c_void_p), ("y_bounds", C.c_void_p),
+        ("y_coeffs", C.c_void_p), ("out", C.c_void_p), ("out_u8", C.c_void_p),
+        ("frame_pitch", C.c_size_t), ("row_pitch", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("kx", C.c_int32), ("ky", C.c_int32), ("band", C.c_int32), ("span", C.c_int32), ("ldo", C.c_int32),
+    ]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/vdx.h declares
@@ -97,6 +107,10 @@ SIGNATURES = {
     "vdx_ddim_step_f16": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _sz, _vp]),
     "vdx_blend_accumulate_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vdx_blend_finalize_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vdx_clip_preprocess_u8": (_i, [C.POINTER(ClipPreprocessArgs), _vp]),
+    "vdx_clip_vision_embed_f16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vdx_quick_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
+    "vdx_clip_cosine_score_f16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -42,6 +42,7 @@ class CLIPTextConfig:
     num_attention_heads: int = 16
     max_position_embeddings: int = 77
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "gelu"           # "gelu": SD-2's OpenCLIP ViT-H (erf GELU); "quick_gelu": CLIP ViT-B/32 (vdx/clip_score.py)
 
     @staticmethod
     def sd2() -> "CLIPTextConfig":
@@ -66,6 +67,8 @@ class CLIPTextModel(nn.Module):
             raise VdxError("CLIPTextModel: the attention kernel needs 64-wide heads (hidden = 64 * heads)")
         if c.hidden_size % 64 or c.intermediate_size % 64 or c.max_position_embeddings > SEQ_PAD:
             raise VdxError("CLIPTextModel: widths must be multiples of 64 and positions <= 128")
+        if c.hidden_act not in ("gelu", "quick_gelu"):
+            raise VdxError(f"CLIPTextModel: hidden_act {c.hidden_act!r} is not built (gelu, quick_gelu)")
         self.W: Dict[str, torch.Tensor] = {}
         self._device = torch.device("cpu")
 
@@ -152,7 +155,10 @@ class CLIPTextModel(nn.Module):
             x = ops.gemm(o, W[a + ".out.weight"], M=M, bias=W[a + ".out.bias"], residual=x)
             ln = ops.layernorm(x, W[p + ".layer_norm2.weight"], W[p + ".layer_norm2.bias"], M=M, eps=c.layer_norm_eps)
             hid = ops.gemm(ln, W[p + ".mlp.fc1.weight"], M=M, bias=W[p + ".mlp.fc1.bias"])
-            ops.gelu(hid, out=hid)
+            if c.hidden_act == "quick_gelu":
+                ops.quick_gelu(hid, out=hid)
+            else:
+                ops.gelu(hid, out=hid)
             x = ops.gemm(hid, W[p + ".mlp.fc2.weight"], M=M, bias=W[p + ".mlp.fc2.bias"], residual=x)
         y = ops.layernorm(x, W["final_layer_norm.weight"], W["final_layer_norm.bias"], M=M, eps=c.layer_norm_eps)
         return TextEncoderOutput((y.view(B, SEQ_PAD, D)[:, :S].contiguous(),))

@@ -311,6 +311,142 @@ def gelu(x, out=None):
     return out
 
 
+def quick_gelu(x, out=None):
+    """x * sigmoid(1.702 x): CLIP ViT-B/32's MLP activation (vdx_quick_gelu_f16)."""
+    lib = _lib.load()
+    if not x.is_contiguous():
+        raise VdxError("quick_gelu: x must be contiguous")
+    if out is None:
+        out = torch.empty_like(x)
+    if out.shape != x.shape or not out.is_contiguous():
+        raise VdxError("quick_gelu: out must be contiguous and shaped like x")
+    _lib.check(lib.vdx_quick_gelu_f16(_p(x, "x"), _p(out, "out"), x.numel(), _stream()), "vdx_quick_gelu_f16")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
+# CLIP score front end (InferNet/template/validator/scoring.py:81-85, :121-122; include/vdx.h vdx_clip_preprocess_u8)
+CLIP_IMAGE = 224
+CLIP_BAND = 8                 # output rows per block of vdx_clip_preprocess_u8
+CLIP_LDS_MAX = 65536
+
+
+def clip_resize_coeffs(in_size: int, out_size: int = CLIP_IMAGE):
+    """Pillow's bilinear windows and 22-bit weights for one axis (ImagingResample's precompute_coeffs +
+    normalize_coeffs_8bpc), in float64 on the host -> (bounds int32 [out][2] = (first input index, count),
+    coeffs int32 [out][ksize]).  The filter's support is max(in/out, 1); a weight w becomes int(w * 2^22 +- 0.5)."""
+    import math
+    import numpy as np
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = fs                                   # bilinear support 1.0, widened when reducing
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((out_size, 2), np.int32)
+    coeffs = np.zeros((out_size, ksize), np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) / fs)) for x in range(n)]
+        ww = sum(w)
+        for x, v in enumerate(w):
+            v = v / ww if ww != 0.0 else v
+            coeffs[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
+        bounds[xx] = (xmin, n)
+    return bounds, coeffs
+
+
+def clip_band_span(y_bounds, band: int) -> int:
+    """Input rows the widest band of `band` output rows reads (its LDS rows in vdx_clip_preprocess_u8)."""
+    out = len(y_bounds)
+    return max(int(y_bounds[min(b + band, out) - 1].sum() - y_bounds[b, 0]) for b in range(0, out, band))
+
+
+_CLIP_TABLES: dict = {}   # (in_size, device) -> (bounds, coeffs) int32 device tensors, host-computed once per size
+
+
+def _clip_table(in_size: int, device):
+    key = (in_size, str(device))
+    t = _CLIP_TABLES.get(key)
+    if t is None:
+        b, k = clip_resize_coeffs(in_size)
+        t = _CLIP_TABLES[key] = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), b)
+    return t
+
+
+def clip_preprocess(frames, out=None, return_u8=False):
+    """uint8 RGB frames (F, H, W, 3) on the GPU (rows and frames may be pitched; pixels packed) -> the patch-GEMM rows
+    fp16 [F*49][3072] of Resize((224, 224)) + ToTensor + Normalize(ImageNet).  `return_u8`: also the resized uint8
+    (F, 224, 224, 3) image -> (rows, u8)."""
+    lib = _lib.load()
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise VdxError(f"clip_preprocess: expected uint8 (F, H, W, 3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)}")
+    F, H, W, _ = frames.shape
+    if F == 0 or H == 0 or W == 0:
+        raise VdxError("clip_preprocess: empty frames")
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) < 3 * W or frames.stride(0) < frames.stride(1) * H:
+        raise VdxError("clip_preprocess: pixels must be packed RGB with non-overlapping rows and frames")
+    dev = frames.device
+    xb, xk, _ = _clip_table(W, dev)
+    yb, yk, yb_host = _clip_table(H, dev)
+    band = CLIP_BAND
+    while band > 1 and clip_band_span(yb_host, band) * CLIP_IMAGE * 3 > CLIP_LDS_MAX:
+        band //= 2
+    span = clip_band_span(yb_host, band)
+    if span * CLIP_IMAGE * 3 > CLIP_LDS_MAX:
+        raise VdxError(f"clip_preprocess: H={H} needs {span} input rows per output row (more than LDS holds)")
+    if out is None:
+        out = torch.empty((F * 49, 3072), dtype=torch.float16, device=dev)
+    orow, ocol, ldo = _rows(out, "out")
+    if orow < F * 49 or ocol < 3072:
+        raise VdxError(f"clip_preprocess: out {tuple(out.shape)} smaller than [{F * 49}][3072]")
+    u8 = torch.empty((F, CLIP_IMAGE, CLIP_IMAGE, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+    a = _lib.ClipPreprocessArgs()
+    a.frames, a.out, a.out_u8 = frames.data_ptr(), _p(out, "out"), (u8.data_ptr() if u8 is not None else None)
+    a.x_bounds, a.x_coeffs, a.y_bounds, a.y_coeffs = xb.data_ptr(), xk.data_ptr(), yb.data_ptr(), yk.data_ptr()
+    a.frame_pitch, a.row_pitch, a.F, a.H, a.W = frames.stride(0), frames.stride(1), F, H, W
+    a.kx, a.ky, a.band, a.span, a.ldo = xk.shape[1], yk.shape[1], band, span, ldo
+    _lib.check(lib.vdx_clip_preprocess_u8(C.byref(a), _stream()), "vdx_clip_preprocess_u8")
+    return (out, u8) if return_u8 else out
+
+
+def clip_vision_embed(patch, class_emb, pos_emb, gamma, beta, *, F, seq_pad, eps=1e-5, out=None):
+    """CLIPVisionEmbeddings + pre_layrnorm: patch-GEMM rows [F*P][D] -> rows [F*seq_pad][D] (class token, P patches,
+    zero rows up to seq_pad), P = pos_emb rows - 1."""
+    lib = _lib.load()
+    r, D, ldp = _rows(patch, "patch")
+    P = pos_emb.shape[0] - 1
+    if r < F * P or pos_emb.shape[1] != D or class_emb.numel() != D or gamma.numel() != D or beta.numel() != D:
+        raise VdxError(f"clip_vision_embed: patch [{r}][{D}], pos {tuple(pos_emb.shape)}: shapes do not match F={F}")
+    if seq_pad <= P or not pos_emb.is_contiguous():
+        raise VdxError(f"clip_vision_embed: seq_pad={seq_pad} must exceed {P} patches; pos_emb contiguous")
+    if out is None:
+        out = torch.empty((F * seq_pad, D), dtype=torch.float16, device=patch.device)
+    orow, ocol, ldo = _rows(out, "out")
+    if orow < F * seq_pad or ocol < D:
+        raise VdxError("clip_vision_embed: out too small")
+    _lib.check(lib.vdx_clip_vision_embed_f16(_p(patch, "patch"), ldp, _p(class_emb, "class_emb"), _p(pos_emb, "pos_emb"),
+                                             _p(gamma, "gamma"), _p(beta, "beta"), float(eps), F, P, seq_pad, D,
+                                             _p(out, "out"), ldo, _stream()), "vdx_clip_vision_embed_f16")
+    return out
+
+
+def clip_cosine_score(img, txt):
+    """F.normalize(img[f]) . F.normalize(txt) for F image embeddings fp16 [F][D] and one text embedding fp16 [D]
+    -> (mean fp32 [1], per_frame fp32 [F]) on the device, in a fixed reduction order."""
+    lib = _lib.load()
+    F, D, ldi = _rows(img, "img")
+    if txt.numel() != D or not txt.is_contiguous():
+        raise VdxError(f"clip_cosine_score: text embedding has {txt.numel()} values, images {D}")
+    if F == 0:
+        raise VdxError("clip_cosine_score: no frames")
+    per = torch.empty(F, dtype=torch.float32, device=img.device)
+    mean = torch.empty(1, dtype=torch.float32, device=img.device)
+    _lib.check(lib.vdx_clip_cosine_score_f16(_p(img, "img"), ldi, _p(txt, "txt"), F, D, _p(per, "per_frame", torch.float32),
+                                             _p(mean, "mean", torch.float32), _stream()), "vdx_clip_cosine_score_f16")
+    return mean, per
+
+
 # --------------------------------------------------------------------------------------------
 _gn_ws: dict = {}
 

@@ -442,7 +442,10 @@ class DistributedVideoDiffuser:
 def build_arg_parser():
     """The reference's argparse, flag for flag and default for default (`fsdp_chunked_coherent.py:281-300`) — the sweep script
     `Distribution/full_experiments_ZeroscopeXL.sh` drives the job through these.  Two additions, both off by default:
-    `--exchange` (allgather | halo, the module docstring) and `--noise_device` (parity runs generate the seeded noise on the CPU)."""
+    `--exchange` (allgather | halo, the module docstring) and `--noise_device` (parity runs generate the seeded noise on the CPU).
+    Two more, also off by default: `--clip_json` scores the decoded frames with the validator's CLIP quality score
+    (vdx/clip_score.py) on rank 0 and writes it there; `--clip_model` names the scorer's weights (a local directory in
+    transformers layout; without it, seeded synthetic ViT-B/32 weights, recorded as such)."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -465,6 +468,8 @@ def build_arg_parser():
     p.add_argument("--exchange", choices=["allgather", "halo"], default="allgather")
     p.add_argument("--noise_device", default=None)
     p.add_argument("--out_video", default="out.mp4")
+    p.add_argument("--clip_json", default=None, help="write the CLIP quality score of the decoded frames here (rank 0)")
+    p.add_argument("--clip_model", default=None, help="local CLIP ViT-B/32 directory (transformers layout) for --clip_json")
     return p
 
 
@@ -475,7 +480,23 @@ def config_from_args(a) -> DiffuserConfig:
                           out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms)
 
 
-def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None) -> dict:
+def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
+    """The validator's quality score (InferNet/template/validator/scoring.py:87-147) of the decoded frames, as `--clip_json`
+    writes it.  Weights: `clip_model` (a local transformers-layout directory) or seeded synthetic ViT-B/32 weights.  Tokenizer:
+    the one in `clip_model` when it has tokenizer files, else the pipeline's."""
+    from .clip_score import CLIPScorer
+    scorer = CLIPScorer.from_local(clip_model, device=device) if clip_model else CLIPScorer.synthetic(seed=0, device=device)
+    if scorer.tokenizer is not None:
+        tok, tok_src = scorer.tokenizer, "clip_model"
+    else:
+        tok, tok_src = pipe_tokenizer, "pipeline"
+    score, per = scorer.score(frames, prompt, tokenizer=tok)
+    return {"clip_score": score, "per_frame": per.tolist(), "synthetic_weights": scorer.synthetic_weights,
+            "tokenizer": f"{tok_src}:{type(tok).__name__}", "n_frames": len(frames)}
+
+
+def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
+            clip_inputs: Optional[dict] = None) -> dict:
     """The reference's `DistributedVideoDiffuser(cfg)()` (:47-276) end to end -> its result dict (:263-275): pipeline
     components (`model_id` = a local checkpoint directory in diffusers layout, else seeded synthetic weights: nothing can be
     downloaded here), text embeddings (:96-103), chunked denoising + exchange + blend, per-frame VAE decode (:219-225),
@@ -531,6 +552,9 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     peak_mb, reduce_s = metrics.peak_vram_mb(dev)
     pynvml_shim.nvmlInit()
     end_mb = pynvml_shim.nvmlDeviceGetMemoryInfo(pynvml_shim.nvmlDeviceGetHandleByIndex(dev.index or 0)).used // 1024 ** 2
+    if d.rank == 0 and clip_inputs is not None:
+        # what `clip_score_record` needs, handed to the caller: the score runs outside the job (and outside main()'s timing)
+        clip_inputs.update(frames=frames, tokenizer=tok, device=dev)
     return {"world_size": d.world, "chunk_size": info["chunk_size"], "overlap": info["overlap"], "num_frames": cfg.num_frames,
             "peak_vram_mb": peak_mb, "end_vram_mb": int(end_mb), "network_bytes": int(info["payload_bytes"]),
             "net_gather_s": info["net_gather_s"], "net_reduce_s": reduce_s, "temp_instab": temp_instab, "flow_err": flow_err,
@@ -547,12 +571,19 @@ def main(argv=None) -> int:
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
+    clip_inputs = {} if a.clip_json else None
     t0 = time.time()
-    res = run_job(cfg, exchange=a.exchange, out_video=a.out_video)
+    res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs)
     if res["rank"] == 0:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
+        if a.clip_json:
+            # scored after the row took its latency and memory readings: the row is that of a run without --clip_json
+            import json
+            rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
+            with open(a.clip_json, "w") as f:
+                json.dump(rec, f, indent=1)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
     return 0

@@ -356,6 +356,51 @@ int vdx_persistent_grid_cus(void);
 int vdx_probe_mfma_f16(float* out, size_t out_floats, int iters, double* flops, vdx_stream_t stream);
 int vdx_probe_occupancy_hog(int blocks, int lds_bytes, int micros, vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CLIP prompt-fidelity score of a generated video: the validator's quality score
+ *   InferNet/neurons/validator.py:277,898   compute_quality_score_clip(video, prompt)
+ *   InferNet/template/validator/scoring.py:87-147   CLIPScorer.compute_quality_score
+ *   Q = 1/F * sum_i cos(E_text, E_frame_i) under CLIP ViT-B/32 (csrc/clip.hip; the towers: vdx/clip_vision.py,
+ *   vdx/clip_text.py, vdx/clip_score.py).  Frames come as decoded uint8 RGB, not re-read from the mp4 (:110-121).
+ * ---------------------------------------------------------------------------------------- */
+/* transforms.Resize((224, 224)) + ToTensor + Normalize(ImageNet mean/std) (scoring.py:81-85, :121-122) of F uint8 RGB frames.
+ * The resize is Pillow's bilinear filter with antialiasing, bit for bit: a horizontal pass, then a vertical pass, each
+ * out = clip8((2^21 + sum px * k) >> 22) with 22-bit weights (uint8 intermediate).  Normalization is
+ * ((u / 255) - mean) / std in fp32 with correctly rounded division, then fp16.  The rows are the patch GEMM's operand:
+ * row f*49 + py*7 + px, column c*1024 + ky*32 + kx (patch_embedding.weight.reshape(768, 3072)).                        */
+typedef struct vdx_clip_preprocess_args {
+    const void* frames;         /* uint8: frame f, row y, pixel x, channel c at f*frame_pitch + y*row_pitch + x*3 + c     */
+    const int32_t* x_bounds;    /* [224][2] (first input column, count) of each output column's window                 */
+    const int32_t* x_coeffs;    /* [224][kx] 22-bit fixed-point weights of those windows                               */
+    const int32_t* y_bounds;    /* [224][2] the same for output rows                                                    */
+    const int32_t* y_coeffs;    /* [224][ky]                                                                            */
+    void* out;                  /* fp16 [F*49][ldo], 3072 columns written                                               */
+    void* out_u8;               /* optional uint8 (F, 224, 224, 3): the resized image (tests); NULL in production         */
+    size_t frame_pitch;         /* bytes                                                                                 */
+    int32_t row_pitch;          /* bytes, >= 3*W                                                                         */
+    int32_t F, H, W;
+    int32_t kx, ky;             /* row lengths of x_coeffs / y_coeffs                                                    */
+    int32_t band;               /* output rows per block                                                                 */
+    int32_t span;               /* input rows the widest band's vertical windows cover (LDS: span*224*3 bytes <= 64 KiB)  */
+    int32_t ldo;                /* >= 3072, a multiple of 8                                                              */
+} vdx_clip_preprocess_args;
+int vdx_clip_preprocess_u8(const vdx_clip_preprocess_args* a, vdx_stream_t stream);
+
+/* CLIPVisionEmbeddings + pre_layrnorm (transformers CLIPVisionTransformer; scoring.py:123 get_image_features): patch GEMM
+ * rows [F*patches][ldp] -> out rows [F*seq_pad][ldo]: row f*seq_pad + 0 = class_emb + pos[0], row f*seq_pad + t =
+ * patch[f*patches + t-1] + pos[t] (t = 1..patches), each LayerNorm'd with fp32 statistics; rows patches+1..seq_pad-1 zero
+ * (the attention kernel's key padding).  D <= 1024.                                                                   */
+int vdx_clip_vision_embed_f16(const void* patch, int ldp, const void* class_emb, const void* pos_emb, const void* gamma,
+                              const void* beta, float eps, int F, int patches, int seq_pad, int D, void* out, int ldo,
+                              vdx_stream_t stream);
+/* y = x * sigmoid(1.702 x): the `quick_gelu` activation of CLIP ViT-B/32's MLPs (both towers).  y may alias x.         */
+int vdx_quick_gelu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
+/* scoring.py:106-107, :123-124, :137-140: per_frame[f] = F.normalize(img[f]) . F.normalize(txt) (eps 1e-12), *mean = their
+ * mean over the F frames.  img fp16 [F][ldi], txt fp16 [D]; per_frame / mean fp32 device memory.  A fixed reduction
+ * order: the same bits on every run.                                                                                    */
+int vdx_clip_cosine_score_f16(const void* img, int ldi, const void* txt, int F, int D, float* per_frame, float* mean,
+                              vdx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ class GemmArgs(C.Structure):
         ("rows_per_bias2", C.c_int32), ("ldb2", C.c_int32), ("epilogue", C.c_int32),
         ("row_begin", C.c_int32), ("row_end", C.c_int32),
         ("ksplit", C.c_int32), ("wset_rows", C.c_int32), ("workspace", C.c_void_p), ("wset_bias", C.c_void_p),
-        ("workspace_bytes", C.c_size_t),
+        ("workspace_bytes", C.c_size_t), ("pad_mode", C.c_int32),
     ]
 
 
@@ -111,6 +111,11 @@ SIGNATURES = {
     "vdx_clip_vision_embed_f16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _i, _vp]),
     "vdx_quick_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
     "vdx_clip_cosine_score_f16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "vdx_resample_h_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _i, _vp]),
+    "vdx_resample_v_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _i, _vp]),
+    "vdx_frames_to_conv_in_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "vdx_vae_posterior_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _vp, _sz, _sz, _vp]),
+    "vdx_add_noise_f16": (_i, [_vp, _vp, _vp, _f, _f, _sz, _vp]),
 }
 
 _lib = None

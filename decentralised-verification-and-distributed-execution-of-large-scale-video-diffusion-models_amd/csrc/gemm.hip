@@ -4,7 +4,8 @@
 //
 // One kernel template serves every contraction of the 3D-UNet:
 //   MODE 0  plain rows (Linear, 1x1 shortcut conv; optional 2-source channel concat)
-//   MODE 1  3x3 conv, pad 1, stride 1|2, optional nearest-x2 upsample folded into the gather
+//   MODE 1  3x3 conv, pad 1 (or (0,1,0,1) at stride 2: Downsample2D(padding=0)), stride 1|2, optional nearest-x2
+//           upsample folded into the gather
 //   MODE 2  temporal 3-tap conv (Conv3d (3,1,1)), zero padded at the chunk's first/last frame
 // Data layout: activations channels-last rows [pixels][C] so a K-slice of 64 channels of one
 // row is one 128-byte line; weights [N][K] with K = tap*C + c.
@@ -74,7 +75,7 @@ struct Stager {
                 const int n = mm / per, rem = mm - n * per;
                 const int yo = rem / p.w_out, xo = rem - yo * p.w_out;
                 d0[i] = n * p.h_in * p.w_in;
-                d1[i] = ((yo * p.stride) << 16) | (xo * p.stride);
+                d1[i] = ((yo * p.stride + p.pad_shift) << 16) | (xo * p.stride + p.pad_shift);
             } else {
                 d0[i] = mm;
                 d1[i] = (mm / p.hw) % p.frames;
@@ -544,7 +545,7 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& forc
     p.M = a->row_end ? a->row_end : a->M; p.m_begin = a->row_begin; p.N = a->N; p.K = a->K; p.c1 = a->c1; p.c2 = a->c2;
     p.lda = a->lda; p.lda2 = a->lda2; p.ldo = a->ldo; p.ldr = a->ldr;
     p.h_in = a->h_in; p.w_in = a->w_in; p.h_out = a->h_out; p.w_out = a->w_out;
-    p.stride = a->stride; p.ups = a->upsample;     // (the gathers shift by ups: 0 | 1; ups == 2 runs the VAR = 2 kernels)
+    p.stride = a->stride; p.pad_shift = a->pad_mode; p.ups = a->upsample;     // (the gathers shift by ups: 0 | 1; ups == 2 runs the VAR = 2 kernels)
     p.h_up = a->upsample == 1 ? 2 * a->h_in : a->upsample == 2 ? a->h_out : a->h_in;
     p.w_up = a->upsample == 1 ? 2 * a->w_in : a->upsample == 2 ? a->w_out : a->w_in;
     p.usy = a->h_in > 0 && p.h_up > 0 ? (float)a->h_in / (float)p.h_up : 1.0f;
@@ -580,6 +581,7 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& forc
     }
     switch (a->mode) {
         case VDX_GEMM_PLAIN:
+            VDX_CHECK(a->pad_mode == 0, "gemm: pad_mode is a conv3x3 setting");
             break;
         case VDX_GEMM_CONV3X3:
             VDX_CHECK(!geglu, "gemm: GEGLU epilogue is plain-mode only");
@@ -590,12 +592,20 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& forc
             {
                 VDX_CHECK(a->upsample >= 0 && a->upsample <= 2 && (a->upsample == 0 || a->stride == 1), "gemm: upsample %d with stride %d", a->upsample, a->stride);
                 VDX_CHECK(a->upsample != 2 || (a->h_out >= a->h_in && a->w_out >= a->w_in), "gemm: upsample-to-size target smaller than the source");
+                VDX_CHECK(a->pad_mode == 0 || a->pad_mode == 1, "gemm: pad_mode %d", a->pad_mode);
+                VDX_CHECK(a->pad_mode == 0 || (a->stride == 2 && a->upsample == 0),
+                          "gemm: pad_mode 1 (pad (0,1,0,1)) needs stride 2 and no upsample (stride %d, upsample %d)", a->stride, a->upsample);
                 const int he = p.h_up, we = p.w_up;
-                VDX_CHECK(a->h_out == (he + 2 - 3) / a->stride + 1 && a->w_out == (we + 2 - 3) / a->stride + 1,
-                          "gemm: conv output %dx%d inconsistent with input %dx%d stride %d", a->h_out, a->w_out, he, we, a->stride);
+                if (a->pad_mode == 1)       // F.pad(x, (0,1,0,1)) + conv3x3 stride 2: (h + 1 - 3) / 2 + 1 = h / 2
+                    VDX_CHECK(a->h_out == he / 2 && a->w_out == we / 2 && a->h_out > 0 && a->w_out > 0,
+                              "gemm: conv output %dx%d inconsistent with input %dx%d, pad (0,1,0,1) stride 2", a->h_out, a->w_out, he, we);
+                else
+                    VDX_CHECK(a->h_out == (he + 2 - 3) / a->stride + 1 && a->w_out == (we + 2 - 3) / a->stride + 1,
+                              "gemm: conv output %dx%d inconsistent with input %dx%d stride %d", a->h_out, a->w_out, he, we, a->stride);
             }
             break;
         case VDX_GEMM_TCONV3:
+            VDX_CHECK(a->pad_mode == 0, "gemm: pad_mode is a conv3x3 setting");
             VDX_CHECK(!geglu, "gemm: GEGLU epilogue is plain-mode only");
             VDX_CHECK(a->c2 == 0, "gemm: tconv3 takes one source");
             VDX_CHECK(a->frames > 0 && a->hw > 0 && a->M % (a->frames * a->hw) == 0, "gemm: tconv geometry M=%d F=%d HW=%d", a->M, a->frames, a->hw);
@@ -625,6 +635,7 @@ extern "C" int vdx_gemm_f16(const vdx_gemm_args* a, vdx_stream_t stream) {
                   a->ksplit, (int)KSPLIT_SLAB_BYTES);
         // the split-K kernels are VAR = 1: their gather shifts by p.ups (0 | 1) and has no nearest-to-size source map
         VDX_CHECK(a->upsample != 2, "gemm: split-K does not take the upsample-to-size gather (upsample = 2)");
+        VDX_CHECK(a->pad_mode == 0, "gemm: split-K does not take the (0,1,0,1) padding (pad_mode = 1)");
         switch (a->mode) {
             case VDX_GEMM_PLAIN: return launch_ksplit<0>(p, a->ksplit, (float*)a->workspace, st);
             case VDX_GEMM_CONV3X3: return launch_ksplit<1>(p, a->ksplit, (float*)a->workspace, st);
@@ -667,6 +678,7 @@ extern "C" int vdx_gemm_plan_ksplit(const vdx_gemm_args* a, int32_t* split_row, 
     if (const int rc = gemm_prepare(a, p, geglu, force, ws_family)) return rc;
     *split_row = 0; *ksplit = 0; *workspace_bytes = 0;
     if (ws_family || geglu || force || p.m_begin != 0 || p.M != a->M) return 0;
+    if (a->pad_mode != 0) return 0;     // vdx_gemm_f16 refuses split-K with pad_mode = 1
     if (a->upsample == 2) return 0;     // no split-K instantiation carries the nearest-to-size gather (vdx_gemm_f16 refuses it)
     const long long rows = p.M;
     const int nt320 = (p.N + 319) / 320, nk = p.K >> 6;

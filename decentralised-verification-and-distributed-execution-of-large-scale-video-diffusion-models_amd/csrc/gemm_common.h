@@ -8,6 +8,7 @@ struct GemmP {
     int M, N, K, c1, c2;
     int lda, lda2, ldo, ldr;
     int h_in, w_in, h_out, w_out, stride;
+    int pad_shift;    // conv3x3: 0 = pad 1 on every side; 1 = pad (0,1,0,1) (vdx_gemm_args.pad_mode): taps start at row 2yo
     int ups;          // conv3x3 source: 0 as is, 1 nearest x2, 2 nearest to (h_up, w_up) (torch's rule: floor(dst * in / out) in fp32)
     int h_up, w_up;   // extent of the (virtually) upsampled source
     float usy, usx;   // ups == 2: in / out as fp32

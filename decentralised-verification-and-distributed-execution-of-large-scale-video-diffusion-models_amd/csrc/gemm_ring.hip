@@ -70,8 +70,8 @@ __global__ __launch_bounds__(WMB * 128) void gemm_ring_kernel(const GemmP p) {
             const int per = p.h_out * p.w_out;
             const int n = mm / per, rem = mm - n * per;
             const int yo = rem / p.w_out, xo = rem - yo * p.w_out;
-            a_y[i] = yo * p.stride - 1;
-            a_x[i] = xo * p.stride - 1;
+            a_y[i] = yo * p.stride - 1 + p.pad_shift;     // first tap row: pad 1, or 0 with pad (0,1,0,1)
+            a_x[i] = xo * p.stride - 1 + p.pad_shift;
             a_off[i] = (size_t)n * p.h_in * p.w_in;
             a_off2[i] = 0;
         } else {

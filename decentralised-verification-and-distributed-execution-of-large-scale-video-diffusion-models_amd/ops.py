@@ -94,8 +94,9 @@ def groupnorm_linear(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sam
 
 def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=0, residual=None,
          out=None, geglu=False, conv=None, tconv=None, variant=0, row_begin=0, row_end=0, allow_ksplit=False, ksplit=0,
-         wset_rows=0, wset_bias=None):
+         wset_rows=0, wset_bias=None, pad_mode=0):
     """out[M][N] = epi(gather(a|a2)[M][K] @ w[N][K]^T).  See include/vdx.h `vdx_gemm_args`.
+    `pad_mode=1` (conv3x3, stride 2): zero padding (0,1,0,1) — diffusers Downsample2D(padding=0); h_out = h_in // 2.
     `allow_ksplit`: the tail of the product (less than half a round of big tiles) may run as K slices + a fixed-order
     reduction (vdx_gemm_plan_ksplit) — faster on the 16-frame windows, not bit-identical to the unsplit order (the
     callers that rely on row-split bit-identity do not pass it).  `ksplit`: pin it for rows [row_begin, row_end).
@@ -159,6 +160,7 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     g.bias, g.bias2, g.residual, g.out = _p(bias, "bias"), _p(bias2, "bias2"), _p(residual, "residual"), _p(out, "out")
     g.M, g.N, g.K, g.mode, g.c1, g.c2 = M, N, K, mode, c1, c2
     g.lda, g.ldo = lda, ldo
+    g.pad_mode = int(pad_mode)
     g.epilogue = (EPI_GEGLU if geglu else 0) | ((variant & 15) << 8)   # variant: kernel override (tests/tuning)
     if wset_rows:
         g.wset_rows, g.wset_bias = wset_rows, wset_bias.data_ptr()
@@ -167,6 +169,8 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     spans = [(row_begin, row_end, ksplit)]
     if variant == 0 and row_begin == 0 and row_end == 0 and ksplit == 0 and not wset_rows:
         key = (M, N, K, mode, geglu, a2 is not None, bias2 is not None, allow_ksplit, int(g.upsample))      # everything the plan depends on
+        if pad_mode:
+            key += (int(pad_mode),)
         plan_ = _PLAN_CACHE.get(key)
         if plan_ is None:
             v_, split_, ks_, wsb_ = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_size_t(0)
@@ -331,23 +335,47 @@ CLIP_BAND = 8                 # output rows per block of vdx_clip_preprocess_u8
 CLIP_LDS_MAX = 65536
 
 
-def clip_resize_coeffs(in_size: int, out_size: int = CLIP_IMAGE):
-    """Pillow's bilinear windows and 22-bit weights for one axis (ImagingResample's precompute_coeffs +
-    normalize_coeffs_8bpc), in float64 on the host -> (bounds int32 [out][2] = (first input index, count),
-    coeffs int32 [out][ksize]).  The filter's support is max(in/out, 1); a weight w becomes int(w * 2^22 +- 0.5)."""
+def _bilinear_filter(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic_filter(x: float) -> float:          # Pillow's bicubic_filter, a = -0.5
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+RESIZE_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "bicubic": (_bicubic_filter, 2.0)}   # name -> (filter, support)
+
+
+def clip_resize_coeffs(in_size: int, out_size: int = CLIP_IMAGE, filter: str = "bilinear"):
+    """Pillow's windows and 22-bit weights for one axis (ImagingResample's precompute_coeffs + normalize_coeffs_8bpc), in
+    float64 on the host -> (bounds int32 [out][2] = (first input index, count), coeffs int32 [out][ksize]).  `filter`:
+    "bilinear" (support 1, the CLIP front end) or "bicubic" (a = -0.5, support 2: Image.resize's default); the support is
+    widened by max(in/out, 1) when reducing; a weight w becomes int(w * 2^22 +- 0.5)."""
     import math
     import numpy as np
+    filt, base_support = RESIZE_FILTERS[filter]
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = fs                                   # bilinear support 1.0, widened when reducing
+    support = base_support * fs
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     coeffs = np.zeros((out_size, ksize), np.int32)
+    ss = 1.0 / fs
     for xx in range(out_size):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         n = min(int(center + support + 0.5), in_size) - xmin
-        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) / fs)) for x in range(n)]
+        if filter == "bilinear":                   # (kept as the CLIP front end has always computed it)
+            w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) / fs)) for x in range(n)]
+        else:
+            w = [filt((x + xmin - center + 0.5) * ss) for x in range(n)]
         ww = sum(w)
         for x, v in enumerate(w):
             v = v / ww if ww != 0.0 else v
@@ -987,3 +1015,129 @@ def occupancy_hog(blocks: int, lds_bytes: int, micros: int, stream=None) -> None
     for the CUs a collective's channel kernels hold (one-GPU rehearsal of the distributed path, bench.py --hog)."""
     st = stream.cuda_stream if stream is not None else _stream()
     _lib.check(_lib.load().vdx_probe_occupancy_hog(int(blocks), int(lds_bytes), int(micros), st), "vdx_probe_occupancy_hog")
+
+
+# --------------------------------------------------------------------------------------------
+# Video-to-video refinement (include/vdx.h, last section): resize, frames -> conv_in rows, posterior, add_noise
+_RESIZE_TABLES: dict = {}   # (in_size, out_size, filter, device) -> (bounds, coeffs) int32 device tensors
+
+
+def _resize_table(in_size: int, out_size: int, filter: str, device):
+    key = (in_size, out_size, filter, str(device))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        b, k = clip_resize_coeffs(in_size, out_size, filter)
+        t = _RESIZE_TABLES[key] = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device))
+    return t
+
+
+def _check_u8_frames(frames, what):
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise VdxError(f"{what}: expected uint8 (F, H, W, 3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)}")
+    F, H, W, _ = frames.shape
+    if F == 0 or H == 0 or W == 0:
+        raise VdxError(f"{what}: empty frames")
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) < 3 * W or frames.stride(0) < frames.stride(1) * H:
+        raise VdxError(f"{what}: pixels must be packed RGB with non-overlapping rows and frames")
+    return F, H, W
+
+
+def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
+    """uint8 RGB (F, Hi, Wi, 3) on the GPU -> (F, height, width, 3): `PIL.Image.resize((width, height))` bit for bit
+    (default filter BICUBIC; 22-bit weights, horizontal pass then vertical, uint8 intermediate).  As in Pillow, a pass whose
+    size does not change is skipped (both unchanged: a copy)."""
+    lib = _lib.load()
+    F, Hi, Wi = _check_u8_frames(frames, "resize_u8")
+    if height <= 0 or width <= 0:
+        raise VdxError(f"resize_u8: target {height}x{width}")
+    dev = frames.device
+    out = torch.empty((F, height, width, 3), dtype=torch.uint8, device=dev)
+    if Hi == height and Wi == width:
+        return out.copy_(frames)
+    src = frames
+    if Wi != width:
+        mid = out if Hi == height else torch.empty((F, Hi, width, 3), dtype=torch.uint8, device=dev)
+        b, k = _resize_table(Wi, width, filter, dev)
+        _lib.check(lib.vdx_resample_h_u8(src.data_ptr(), src.stride(0), src.stride(1), F, Hi, Wi, b.data_ptr(), k.data_ptr(),
+                                         k.shape[1], width, mid.data_ptr(), mid.stride(0), mid.stride(1), _stream()),
+                   "vdx_resample_h_u8")
+        src = mid
+    if Hi != height:
+        b, k = _resize_table(Hi, height, filter, dev)
+        _lib.check(lib.vdx_resample_v_u8(src.data_ptr(), src.stride(0), src.stride(1), F, Hi, width, b.data_ptr(), k.data_ptr(),
+                                         k.shape[1], height, out.data_ptr(), out.stride(0), out.stride(1), _stream()),
+                   "vdx_resample_v_u8")
+    return out
+
+
+_U8_MAP: dict = {}      # device -> fp16 [256]
+
+
+def u8_to_unit_lut():
+    """The diffusers video preprocessing of one uint8 value, cast to the VAE dtype: fp16(float32(u) / 255 * 2 - 1)
+    (numpy float32, every op rounded, as VideoProcessor's pil_to_numpy + normalize evaluate it)."""
+    import numpy as np
+    u = np.arange(256, dtype=np.float32)
+    x = u / np.float32(255.0)
+    x = np.float32(2.0) * x
+    x = x - np.float32(1.0)
+    return torch.from_numpy(x.astype(np.float16))
+
+
+def frames_to_conv_in(frames, out=None):
+    """uint8 (F, H, W, 3) on the GPU -> fp16 rows [F*H*W][64]: the im2col operand of the encoder's conv_in (K = tap*3 + c,
+    columns 27..63 zero) of the mapped frames (`u8_to_unit_lut`), zero outside the image — the same rows `conv_in` builds
+    from the mapped (F, 3, 1, H, W) tensor."""
+    lib = _lib.load()
+    F, H, W = _check_u8_frames(frames, "frames_to_conv_in")
+    dev = frames.device
+    lut = _U8_MAP.get(str(dev))
+    if lut is None:
+        lut = _U8_MAP[str(dev)] = u8_to_unit_lut().to(dev)
+    if out is None:
+        out = torch.empty((F * H * W, 64), dtype=torch.float16, device=dev)
+    r, c, ldo = _rows(out, "out")
+    if r < F * H * W or c < 64:
+        raise VdxError(f"frames_to_conv_in: out {tuple(out.shape)} smaller than [{F * H * W}][64]")
+    _lib.check(lib.vdx_frames_to_conv_in_u8(frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, lut.data_ptr(),
+                                            _p(out, "out"), ldo, _stream()), "vdx_frames_to_conv_in_u8")
+    return out
+
+
+def vae_posterior(moments, n: int, hw: int, eps=None, scale: float = 1.0, out=None, out_offset: int = 0, out_strides=None):
+    """DiagonalGaussianDistribution over the encoder's moment rows [n*hw][ld] (mean columns 0..3, logvar 4..7):
+    scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps), or scale * mean without `eps` (mode), fp16 after every op.
+    Default output (n, 4, h*w); a contiguous `out` + `out_offset` (elements) + `out_strides` = (channel, image) element strides
+    write elsewhere, e.g. frames f0.. of a (1, 4, T, h, w) latent: offset f0*hw, strides (T*hw, hw)."""
+    lib = _lib.load()
+    r, c, ld = _rows(moments, "moments")
+    if r < n * hw or c < 8:
+        raise VdxError(f"vae_posterior: moments {tuple(moments.shape)} smaller than [{n * hw}][8]")
+    if eps is not None and (eps.dtype != torch.float16 or not eps.is_contiguous() or eps.numel() != n * 4 * hw
+                            or eps.device != moments.device):
+        raise VdxError("vae_posterior: eps must be contiguous fp16 (n, 4, h, w) on the moments' device")
+    if out is None:
+        out = torch.empty((n, 4, hw), dtype=torch.float16, device=moments.device)
+        out_strides = (hw, 4 * hw)
+    elif out_strides is None or out.dtype != torch.float16 or not out.is_contiguous() or out.device != moments.device:
+        raise VdxError("vae_posterior: an explicit `out` must be contiguous fp16 on the moments' device, with out_strides")
+    cs, fs = out_strides
+    if out_offset < 0 or out_offset + 3 * cs + (n - 1) * fs + hw > out.numel():
+        raise VdxError("vae_posterior: out too small for its offset and strides")
+    _lib.check(lib.vdx_vae_posterior_f16(_p(moments, "moments"), ld, n, hw, eps.data_ptr() if eps is not None else None,
+                                         int(eps is None), float(scale), out.data_ptr() + 2 * out_offset, cs, fs, _stream()),
+               "vdx_vae_posterior_f16")
+    return out
+
+
+def add_noise(x0, noise, sqrt_ab: float, sqrt_1mab: float, out=None):
+    """DDIMScheduler.add_noise with fp16 coefficients: fp16(fp16(sqrt_ab * x0) + fp16(sqrt_1mab * noise))."""
+    lib = _lib.load()
+    if x0.shape != noise.shape or x0.dtype != torch.float16 or noise.dtype != torch.float16 \
+            or not (x0.is_contiguous() and noise.is_contiguous()):
+        raise VdxError("add_noise: x0 and noise must be contiguous fp16 tensors of one shape")
+    if out is None:
+        out = torch.empty_like(x0)
+    _lib.check(lib.vdx_add_noise_f16(_p(x0, "x0"), _p(noise, "noise"), _p(out, "out"), float(sqrt_ab), float(sqrt_1mab),
+                                     x0.numel(), _stream()), "vdx_add_noise_f16")
+    return out

@@ -58,6 +58,11 @@ class DiffuserConfig:
     emu_bw_mbps: float = 0.0               # throttle: payload_bytes / (Mbps * 1e6 / 8) seconds before the gather (0 = off)
     emu_rtt_ms: float = 0.0                # one-way latency: gauss(rtt, jitter) ms before the gather, rtt ms before the reduction
     emu_jitter_ms: float = 0.0
+    # video-to-video refinement (diffusers VideoToVideoSDPipeline; unpinned): start from an encoded clip noised to the first
+    # timestep of the schedule truncated by `strength`, instead of pure noise.  None = text-to-video, as the reference runs
+    init_video: Optional[str] = None       # .npy uint8 (T,H,W,3) or a directory of image files (sorted by name)
+    strength: float = 0.6
+    posterior: str = "sample"              # "sample" | "mode" of the encoder's diagonal Gaussian
 
     @property
     def use_fsdp(self):
@@ -104,6 +109,43 @@ def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
     base = torch.randn(*shape, device=nd, dtype=dtype)
     base *= sigma
     return base.to(device)
+
+
+def vid2vid_timesteps(scheduler, steps: int, strength: float) -> List[int]:
+    """diffusers VideoToVideoSDPipeline.get_timesteps: init = min(int(steps*strength), steps), t_start = max(steps - init, 0),
+    the tail `timesteps[t_start:]` of a schedule set for `steps` (the DDIM step's prev_t keeps the full `steps` spacing).
+    `scheduler` must have had set_timesteps(steps)."""
+    if steps <= 0:
+        raise ValueError(f"vid2vid_timesteps: steps must be positive, got {steps}")
+    if not (0.0 < strength <= 1.0):
+        raise ValueError(f"vid2vid_timesteps: strength must be in (0, 1], got {strength}")
+    if scheduler.num_inference_steps != steps:
+        raise ValueError(f"vid2vid_timesteps: the scheduler is set for {scheduler.num_inference_steps} steps, not {steps}")
+    init = min(int(steps * strength), steps)
+    t_start = max(steps - init, 0)
+    return list(scheduler._host_timesteps[t_start:])
+
+
+def load_init_video(path: str):
+    """--init_video: a .npy uint8 (T,H,W,3) array, or a directory of image files sorted by name (needs Pillow) -> numpy uint8."""
+    import os
+
+    import numpy as np
+    if os.path.isdir(path):
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError(f"--init_video {path}: a directory of images needs Pillow, which is not installed "
+                               "(pass a .npy uint8 (T,H,W,3) array instead)") from e
+        names = sorted(n for n in os.listdir(path) if not n.startswith("."))
+        if not names:
+            raise ValueError(f"--init_video {path}: no image files")
+        arr = np.stack([np.asarray(Image.open(os.path.join(path, n)).convert("RGB")) for n in names])
+    else:
+        arr = np.load(path)
+    if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
+        raise ValueError(f"--init_video {path}: expected uint8 (T,H,W,3), got {arr.dtype} {arr.shape}")
+    return np.ascontiguousarray(arr)
 
 
 def ramp_weights(length: int, ov: int) -> torch.Tensor:
@@ -321,7 +363,11 @@ def blend_owned(mine: List[torch.Tensor], hp: HaloPlan, got: dict, done, like: t
 
 
 class DistributedVideoDiffuser:
-    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb):
+    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None):
+        """`init_latents` (video-to-video): the scaled clean latent (1,C,T,h,w) fp16 of the whole clip (every rank encodes the
+        whole clip: identical bits on every rank, no collective).  The denoise then runs `vid2vid_timesteps(cfg.strength)`
+        from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
+        frame-mean of that start latent.  None: text-to-video, unchanged."""
         self.cfg = cfg
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
@@ -331,7 +377,20 @@ class DistributedVideoDiffuser:
             unet.shard_(self.rank, self.world)
         scheduler.set_timesteps(cfg.steps, device=cfg.device)
         self.ctx = None
-        if cfg.use_ctx:                                               # reference :105-127
+        self.init_latents = init_latents
+        self.timesteps = None                                         # video-to-video only: the truncated schedule
+        self._start = None
+        if init_latents is not None:
+            C = unet.config.in_channels
+            shape = (1, C, cfg.num_frames, cfg.height // 8, cfg.width // 8)
+            if tuple(init_latents.shape) != shape:
+                raise ValueError(f"init_latents {tuple(init_latents.shape)} != {shape}")
+            self.timesteps = vid2vid_timesteps(scheduler, cfg.steps, cfg.strength)
+            base = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+            self._start = scheduler.add_noise(init_latents.to(cfg.device, torch.float16).contiguous(), base, self.timesteps[0])
+            if cfg.use_ctx:                                           # the frame-mean of the whole clip's start latent
+                self.ctx = self._start.mean(dim=2, keepdim=True).contiguous()
+        elif cfg.use_ctx:                                             # reference :105-127
             C = unet.config.in_channels
             shape = (1, C, cfg.num_frames, cfg.height // 8, cfg.width // 8)
             if self.rank == 0:
@@ -348,7 +407,7 @@ class DistributedVideoDiffuser:
         cfg, sched = self.cfg, self.scheduler
         emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0)
         lat = lat.contiguous()
-        for t in sched._host_timesteps:
+        for t in (sched._host_timesteps if self.timesteps is None else self.timesteps):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb).sample
             lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale)
@@ -396,15 +455,19 @@ class DistributedVideoDiffuser:
         T, H, W = cfg.num_frames, cfg.height // 8, cfg.width // 8
         cp = self.plan()
         C = self.unet.config.in_channels
-        base = seeded_noise((1, C, T, H, W), self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+        if self._start is None:
+            start = seeded_noise((1, C, T, H, W), self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+        else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
+            start = self._start
         t0 = time.time()
-        mine = [self.denoise(base[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
+        mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
         if self.world > 1:
             dist.barrier()
         self._sync()
         denoise_s = time.time() - t0
         info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": list(cp.ranges), "world_size": self.world,
-                "num_frames": T, "denoise_s": denoise_s, "exchange": exchange}
+                "num_frames": T, "denoise_s": denoise_s, "exchange": exchange,
+                "steps_run": len(self.scheduler._host_timesteps if self.timesteps is None else self.timesteps)}
         payload_ref = sum(t.shape[2] * C * 2 for t in mine)                 # the reference's `payload_bytes` (:194)
         delay = emu_gather_delay_s(payload_ref, cfg)                        # :195-199, outside the timed gather like there
         if delay > 0:
@@ -418,12 +481,12 @@ class DistributedVideoDiffuser:
             info["network_bytes"] = (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2    # received per rank
             info["payload_bytes"] = sum(t.shape[2] * C * 2 for t in mine)          # the reference's formula (:194), see below
             info["payload_bytes_actual"] = sum(t.numel() * 2 for t in mine)
-            return self.blend(chunks, base, cp.overlap), info
+            return self.blend(chunks, start, cp.overlap), info
         if exchange != "halo":
             raise ValueError(f"unknown exchange {exchange!r}")
         hp = HaloPlan(cp, T)
         got, done = exchange_halos(mine, hp, self.rank, comm=comm) if self.world > 1 else ({}, None)
-        owned = self.blend_owned(mine, hp, got, done, base)
+        owned = self.blend_owned(mine, hp, got, done, start)
         self._sync()
         info["net_gather_s"] = time.time() - t0
         info["network_bytes"] = sum(t.numel() * 2 for t in got.values())
@@ -470,6 +533,10 @@ def build_arg_parser():
     p.add_argument("--out_video", default="out.mp4")
     p.add_argument("--clip_json", default=None, help="write the CLIP quality score of the decoded frames here (rank 0)")
     p.add_argument("--clip_model", default=None, help="local CLIP ViT-B/32 directory (transformers layout) for --clip_json")
+    p.add_argument("--init_video", default=None,
+                   help="video-to-video: refine this clip (.npy uint8 (T,H,W,3) or a directory of images) instead of starting from noise")
+    p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
+    p.add_argument("--posterior", choices=["sample", "mode"], default="sample", help="video-to-video: encoder posterior")
     return p
 
 
@@ -477,7 +544,8 @@ def config_from_args(a) -> DiffuserConfig:
     return DiffuserConfig(num_frames=a.num_frames, steps=a.steps, guidance_scale=a.guidance_scale, chunk_size=a.chunk_size,
                           overlap=a.overlap, height=a.height, width=a.width, mode=a.mode, context_weight=a.context_weight,
                           device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
-                          out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms)
+                          out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
+                          init_video=a.init_video, strength=a.strength, posterior=a.posterior)
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -493,6 +561,44 @@ def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_token
     score, per = scorer.score(frames, prompt, tokenizer=tok)
     return {"clip_score": score, "per_frame": per.tolist(), "synthetic_weights": scorer.synthetic_weights,
             "tokenizer": f"{tok_src}:{type(tok).__name__}", "n_frames": len(frames)}
+
+
+def encode_init_video(cfg: DiffuserConfig, vae, dev):
+    """--init_video -> the scaled clean latent (1,4,T,h,w) fp16 on `dev`, seconds: the clip is loaded, resized on the GPU to
+    (height, width) when its size differs (Image.resize, BICUBIC), and encoded (posterior noise: (T,4,h,w) fp16 from a
+    torch.Generator seeded 1 on the noise device).  Encoder weights: `vae/` of a local checkpoint, else seeded synthetic ones."""
+    import os
+
+    from . import weights as _weights
+    from .compat.diffusers_shim import _load_file
+    clip = load_init_video(cfg.init_video)
+    if clip.shape[0] != cfg.num_frames:
+        raise ValueError(f"--init_video has {clip.shape[0]} frames, --num_frames is {cfg.num_frames}")
+    if cfg.posterior not in ("sample", "mode"):
+        raise ValueError(f"posterior must be 'sample' or 'mode', got {cfg.posterior!r}")
+    d = str(cfg.model_id)
+    sd = None
+    if os.path.isdir(d):
+        sd = _load_file([f"{d}/vae/diffusion_pytorch_model.safetensors", f"{d}/vae/diffusion_pytorch_model.bin"])
+    if sd is None:
+        sd = _weights.synthetic_vae_encoder_state_dict(vae.cfg, 8, "cpu")
+    vae.load_diffusers_encoder_state_dict(sd, device=dev)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    t0 = time.time()
+    frames = torch.from_numpy(clip).to(dev)
+    if frames.shape[1:3] != (cfg.height, cfg.width):
+        frames = ops.resize_u8(frames, cfg.height, cfg.width)
+    noise = None
+    if cfg.posterior == "sample":
+        nd = torch.device(cfg.noise_device) if cfg.noise_device is not None else dev
+        g = torch.Generator(device=nd).manual_seed(1)
+        noise = torch.randn((cfg.num_frames, 4, cfg.height // 8, cfg.width // 8), generator=g, device=nd,
+                            dtype=torch.float16).to(dev)
+    lat = vae.encode_frames_u8(frames, posterior=cfg.posterior, noise=noise)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    return lat, time.time() - t0
 
 
 def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
@@ -527,7 +633,10 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     with torch.no_grad():
         emb = pipe.text_encoder(ids.to(dev))[0]
     cond, uncond = emb[:1].contiguous(), emb[1:].contiguous()
-    d = DistributedVideoDiffuser(cfg, unet, pipe.scheduler, uncond, cond)
+    init_latents, encode_s = None, 0.0
+    if cfg.init_video is not None:
+        init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
+    d = DistributedVideoDiffuser(cfg, unet, pipe.scheduler, uncond, cond, init_latents=init_latents)
     out, info = d(exchange=exchange)
     ranges = info["ranges"]
     if exchange == "allgather":
@@ -559,7 +668,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "peak_vram_mb": peak_mb, "end_vram_mb": int(end_mb), "network_bytes": int(info["payload_bytes"]),
             "net_gather_s": info["net_gather_s"], "net_reduce_s": reduce_s, "temp_instab": temp_instab, "flow_err": flow_err,
             "denoise_s": info["denoise_s"], "exchange": exchange, "rank": d.rank, "synthetic_weights": pipe.synthetic_weights,
-            "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay}
+            "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
+            "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s}
 
 
 def main(argv=None) -> int:

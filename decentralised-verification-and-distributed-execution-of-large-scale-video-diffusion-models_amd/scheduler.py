@@ -89,6 +89,17 @@ class DDIMScheduler:
                              self.coefficients(self._host_timestep(timestep)))
         return SimpleNamespace(prev_sample=prev)
 
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
+        then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers
+        does), then x_t = sqrt(a_t)*x0 + sqrt(1-a_t)*noise in the HIP kernel with fp16 rounding after each op.  Unpinned
+        boundary (diffusers is not installed: DESIGN §2)."""
+        t = self._host_timestep(timesteps) if torch.is_tensor(timesteps) else int(timesteps)
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        sa = float(ac[t] ** 0.5)
+        s1 = float((1 - ac[t]) ** 0.5)
+        return ops.add_noise(original_samples.contiguous(), noise.contiguous(), sa, s1)
+
     def step_cfg(self, noise2, timestep, sample, guidance_scale: float):
         """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel."""
         return ops.cfg_ddim_step(noise2, sample, guidance_scale, self.coefficients(self._host_timestep(timestep)))

@@ -174,6 +174,51 @@ def synthetic_vae_state_dict(cfg=None, seed: int = 7, device="cpu", dtype=torch.
     return sd
 
 
+def synthetic_vae_encoder_state_dict(cfg=None, seed: int = 8, device="cpu", dtype=torch.float16):
+    """diffusers-shaped AutoencoderKL ENCODER table (+ quant_conv) with seeded values: what `vdx.vae.AutoencoderKL.
+    load_diffusers_encoder_state_dict` ingests for video-to-video runs without a checkpoint (its own seed: the decoder's
+    seeded values of `synthetic_vae_state_dict` stay as they are)."""
+    from .vae import VaeConfig
+    cfg = cfg or VaeConfig.sd()
+    dev = torch.device(device)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    ch = tuple(cfg.block_out_channels)
+    sd = {}
+
+    def conv(name, co, ci, k):
+        sd[name + ".weight"] = (torch.randn(co, ci, k, k, generator=g, device=dev) / (ci * k * k) ** 0.5).to(dtype)
+        sd[name + ".bias"] = (0.02 * torch.randn(co, generator=g, device=dev)).to(dtype)
+
+    def norm(name, c):
+        sd[name + ".weight"] = (1 + 0.05 * torch.randn(c, generator=g, device=dev)).to(dtype)
+        sd[name + ".bias"] = (0.02 * torch.randn(c, generator=g, device=dev)).to(dtype)
+
+    def resnet(p, ci, co):
+        norm(p + ".norm1", ci); conv(p + ".conv1", co, ci, 3); norm(p + ".norm2", co); conv(p + ".conv2", co, co, 3)
+        if ci != co:
+            conv(p + ".conv_shortcut", co, ci, 1)
+
+    conv("encoder.conv_in", ch[0], cfg.out_channels, 3)
+    prev = ch[0]
+    for i, c in enumerate(ch):
+        for j in range(cfg.layers_per_block):
+            resnet(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else c, c)
+        if i != len(ch) - 1:
+            conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", c, c, 3)
+        prev = c
+    resnet("encoder.mid_block.resnets.0", ch[-1], ch[-1])
+    a = "encoder.mid_block.attentions.0"
+    norm(a + ".group_norm", ch[-1])
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        sd[f"{a}.{n}.weight"] = (torch.randn(ch[-1], ch[-1], generator=g, device=dev) / ch[-1] ** 0.5).to(dtype)
+        sd[f"{a}.{n}.bias"] = (0.02 * torch.randn(ch[-1], generator=g, device=dev)).to(dtype)
+    resnet("encoder.mid_block.resnets.1", ch[-1], ch[-1])
+    norm("encoder.conv_norm_out", ch[-1])
+    conv("encoder.conv_out", 2 * cfg.latent_channels, ch[-1], 3)
+    conv("quant_conv", 2 * cfg.latent_channels, 2 * cfg.latent_channels, 1)
+    return sd
+
+
 def synthetic_clip_state_dict(cfg=None, seed: int = 11, device="cpu", dtype=torch.float16):
     """`transformers.CLIPTextModel`-shaped table (keys without the `text_model.` prefix) with seeded values."""
     from .clip_text import CLIPTextConfig

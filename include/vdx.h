@@ -62,7 +62,7 @@ typedef struct vdx_gemm_args {
     int32_t lda, lda2, ldo, ldr;
     int32_t h_in, w_in;   /* conv3x3: source image size (rows of `a` = n*h_in*w_in)              */
     int32_t h_out, w_out; /* conv3x3: output image size (M = n*h_out*w_out)                      */
-    int32_t stride;       /* conv3x3: 1 or 2 (pad 1)                                             */
+    int32_t stride;       /* conv3x3: 1 or 2 (pad 1, or pad_mode below)                          */
     int32_t upsample;     /* conv3x3: 1 = source is nearest-x2 upsampled on the fly; 2 = nearest-upsampled to
                            * (h_out, w_out) — diffusers' `upsample_size` path for latents not divisible by 8 */
     int32_t frames, hw;   /* tconv3: M = b*frames*hw, taps step `hw` rows, zero pad in time      */
@@ -83,6 +83,10 @@ typedef struct vdx_gemm_args {
     void* workspace;      /* ksplit > 1: >= tiles * ksplit * 327 680 bytes (vdx_gemm_plan_ksplit), 16-byte aligned    */
     const float* wset_bias; /* wset_rows > 0: fp32 [M / wset_rows][N], the initial accumulators                          */
     size_t workspace_bytes; /* ksplit > 1: the size of `workspace`; the call is refused when the slabs would not fit        */
+    int32_t pad_mode;     /* conv3x3 zero padding: 0 = 1 on every side (Conv2d(padding=1)); 1 = (0, 1, 0, 1), stride 2 only:
+                             diffusers Downsample2D(padding=0) = conv3x3_s2(F.pad(x, (0,1,0,1))) — output pixel yo reads
+                             rows 2yo .. 2yo+2, row h_in is zero, h_out = h_in / 2.  Refused with upsample and split-K;
+                             the fused GroupNorm conv (vdx_conv3x3_gn_f16) has no such mode                           */
 } vdx_gemm_args;
 
 int vdx_gemm_f16(const vdx_gemm_args* a, vdx_stream_t stream);
@@ -400,6 +404,41 @@ int vdx_quick_gelu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
  * order: the same bits on every run.                                                                                    */
 int vdx_clip_cosine_score_f16(const void* img, int ldi, const void* txt, int F, int D, float* per_frame, float* mean,
                               vdx_stream_t stream);
+
+
+/* ------------------------------------------------------------------------------------------
+ * Video-to-video refinement (Zeroscope v2 XL's second stage): diffusers VideoToVideoSDPipeline + AutoencoderKL.encode
+ * (unpinned: diffusers is not part of the parity set).  The first-stage clip is resized to the target size
+ * (Image.resize, BICUBIC), mapped to [-1, 1], encoded (vdx/vae.py: encoder on the GEMM / GroupNorm / attention kernels),
+ * sampled from the diagonal Gaussian posterior, scaled, and noised to the first timestep of the truncated schedule.
+ * ---------------------------------------------------------------------------------------- */
+/* One pass of Pillow's ImagingResample on 8-bit RGB (any filter; windows + 22-bit weights from the host,
+ * vdx/ops.py `clip_resize_coeffs(.., filter=)`): out = clip8((2^21 + sum px * k) >> 22).  Horizontal: (F, H, Wi, 3) -> (F, H, Wo, 3);
+ * vertical: (F, Hi, W, 3) -> (F, Ho, W, 3).  bounds [out][2] = (first input index, count), coeffs [out][ksize].
+ * Pitches in bytes; pixels packed RGB.  Window indices are clamped to the input.                                */
+int vdx_resample_h_u8(const void* in, size_t in_frame_pitch, int in_row_pitch, int F, int H, int Wi, const int32_t* bounds,
+                      const int32_t* coeffs, int ksize, int Wo, void* out, size_t out_frame_pitch, int out_row_pitch,
+                      vdx_stream_t stream);
+int vdx_resample_v_u8(const void* in, size_t in_frame_pitch, int in_row_pitch, int F, int Hi, int W, const int32_t* bounds,
+                      const int32_t* coeffs, int ksize, int Ho, void* out, size_t out_frame_pitch, int out_row_pitch,
+                      vdx_stream_t stream);
+/* uint8 RGB frames (F, H, W, 3) -> the im2col rows of the encoder's conv_in: row f*H*W + y*W + x, column
+ * K = (ky*3+kx)*3 + ci holds map(u[f, y+ky-1, x+kx-1, ci]) (0.0 outside the image: the conv pads the NORMALISED image),
+ * columns 27..63 zero.  map = lut (256 fp16 on the device, fp16(float32(u)/255*2-1) built on the host).  ldo >= 64, % 8;
+ * out_rows 16-byte aligned (16-byte stores).                                                                       */
+int vdx_frames_to_conv_in_u8(const void* frames, size_t frame_pitch, int row_pitch, int F, int H, int W, const void* lut_f16,
+                             void* out_rows, int ldo, vdx_stream_t stream);
+/* DiagonalGaussianDistribution(moments) -> scaled latent.  moments: the encoder's rows [n*h*w][ld] (mean = columns 0..3,
+ * logvar = 4..7).  Per element, fp16 after every op like torch: lv = clamp(lv, -30, 20); std = exp(0.5*lv) (expf);
+ * x = mean + std*eps (mode_only: x = mean); out = scale*x.  eps fp16 (n,4,h,w) (unused with mode_only).
+ * out[c*out_c_stride + i*out_f_stride + p] for image i, channel c, pixel p: (1,4,T,h,w) at frame f0 is
+ * out + f0*h*w with strides (T*h*w, h*w); (n,4,h,w) is strides (h*w, 4*h*w).                                   */
+int vdx_vae_posterior_f16(const void* moments, int ld, int n, int hw, const void* eps, int mode_only, float scale, void* out,
+                          size_t out_c_stride, size_t out_f_stride, vdx_stream_t stream);
+/* DDIMScheduler.add_noise: out = sqrt_ab*x0 + sqrt_1mab*noise with fp16 rounding after each op; the two coefficients are
+ * fp16 values (alphas_cumprod cast to the sample dtype first, then ** 0.5 — the host evaluates them like diffusers).  */
+int vdx_add_noise_f16(const void* x0, const void* noise, void* out, float sqrt_ab, float sqrt_1mab, size_t n,
+                      vdx_stream_t stream);
 
 #ifdef __cplusplus
 }

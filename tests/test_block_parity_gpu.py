@@ -1,0 +1,626 @@
+"""-m gpu: a shadow check of the HIP UNet at the shapes the project is measured on.  Every block of a real forward —
+ResNets, temporal convolutions, spatial and temporal transformers, down / up samplers and the in / out steps — is compared,
+at its production shape, with the fp32 oracle module of the same name (`oracle/unet3d_ref.py`) run on the block's OWN HIP
+input.  Errors do not compound from block to block, so each bound is tight, and a failure names the block, the CFG item,
+the frame and the worst row.
+
+The whole-network oracle comparison (`tests/test_full_extent_gpu.py`) runs at 2 and 3 frames, where other kernels are taken:
+K3 needs F % 8 == 0, K7b / K1 are picked per F, and every GEMM's plan (family, split row, split-K tail) depends on M.  Here
+the headline input (2, 4, 24, 72, 128) with the CFG-shared prefix and the 16-frame window of cfg4 / cfg5 run the kernels
+the benchmark times, and the kernels launched by the headline forward are pinned (`HEADLINE_DISPATCH`).
+
+Per block, four checks (the compared quantity is the residual branch `out - x` where the block has an identity residual,
+else the whole output):
+  * rel-L2 over the block;
+  * worst rel-L2 over one (item, frame) image;
+  * worst rel-L2 over one 256-row tile of an image (the GEMM's row tile: one bad tile of a 442 368-row activation is
+    diluted to nothing in the first two);
+  * the per-op element bound |err| <= tol * max|ref| + tol * |ref|.
+The constants (`BOUNDS`) were calibrated at F = 2 (72x128) and are used unchanged at 16 and 24 frames.
+
+The reference runs on the GPU in fp32: TF32 off, MIOpen off (torch's own im2col + fp32 GEMM convolutions: no run-time
+kernel compilation), the math SDPA backend.  `test_gpu_reference_matches_cpu_oracle` shows it agrees with the same modules on
+the CPU."""
+import copy
+import math
+import os
+import time
+from contextlib import contextmanager
+
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+pytestmark = pytest.mark.gpu
+
+H, W = 72, 128
+T = 981
+TILE = 256              # rows of the GEMM's big tile
+CHUNK_ROWS = 18432      # images per oracle call: at most this many rows (two level-0 images: 2 x 1.7 GB of fp32 scores)
+REL_CAP, ELEM_CAP = 4e-3, 1e-2      # no bound is looser than these
+
+# (block rel-L2, worst (item, frame) rel-L2, worst 256-row tile rel-L2, element tol) per block class: no more than 2x the
+# worst value measured at F = 2 over both weight tables (the `f2-*` configurations below), and never above REL_CAP / ELEM_CAP.
+# The 16- and 24-frame configurations use them unchanged.
+BOUNDS = {                  # measured at F = 2, worst over the class (block, frame, tile, element):
+    "time":      (7.7e-4, 7.7e-4, 7.7e-4, 6.0e-4),      # 3.885e-4 3.885e-4 3.885e-4 3.032e-4
+    "conv_in":   (4.1e-4, 4.1e-4, 4.1e-4, 3.9e-4),      # 2.077e-4 2.078e-4 2.095e-4 1.960e-4
+    "resnet":    (3.8e-3, 3.8e-3, 3.8e-3, 5.6e-3),      # 1.917e-3 1.931e-3 1.931e-3 2.837e-3
+    "temp_conv": (REL_CAP, REL_CAP, REL_CAP, 6.3e-3),   # 2.296e-3 2.316e-3 2.483e-3 3.188e-3
+    "spatial":   (2.2e-3, 2.2e-3, 2.2e-3, 3.3e-3),      # 1.129e-3 1.135e-3 1.136e-3 1.687e-3
+    "temporal":  (2.1e-3, 2.1e-3, 2.1e-3, 3.1e-3),      # 1.052e-3 1.055e-3 1.062e-3 1.581e-3
+    "sampler":   (4.1e-4, 4.1e-4, 4.1e-4, 4.6e-4),      # 2.079e-4 2.082e-4 2.093e-4 2.318e-4
+    "conv_out":  (5.8e-4, 5.8e-4, 6.2e-4, 4.8e-4),      # 2.912e-4 2.930e-4 3.114e-4 2.446e-4
+}
+
+# name -> (weight table, frames, context term, headline)
+CONFIGS = {
+    "f2-synthetic": ("synthetic", 2, False, False),
+    "headline-24f": ("synthetic", 24, False, True),
+    "window-16f-ctx": ("synthetic", 16, True, False),
+    "f2-hard": ("hard", 2, True, False),
+    "window-16f-hard": ("hard", 16, True, False),
+}
+
+# Kernels the headline forward launches (GEMM instantiations as ops.gemm_kernel_name names them, after vdx_gemm_plan's split)
+HEADLINE_DISPATCH = {
+    # fused blocks and attention kernels (K1 conv3x3+GN, K3 temporal conv+GN, K5 cross-attention, K7 / K7b temporal
+    # attention, K8 feed-forward with proj_out)
+    'K1 conv3x3_gn', 'K3 tconv_gn<12>', 'K5 cross_attn_block<320>',
+    'K7 temporal_attn_block<512>', 'K7b temporal_attn_block2<320>', 'K8 ff_block<320, proj_out>',
+    'flash_attn<v_rows>', 'flash_attn<vt>', 'temporal_attn',
+    # GEMM families
+    'gemm_kernel<128, 128, 4, 2, 0, false, false, 0>',
+    'gemm_kernel<128, 128, 4, 2, 0, true, false, 0>',
+    'gemm_kernel<128, 128, 4, 2, 1, false, false, 0>',
+    'gemm_kernel<128, 128, 4, 2, 2, false, false, 0>',
+    'gemm_kernel<256, 320, 4, 2, 0, false, false, 0>',
+    'gemm_kernel<256, 320, 4, 2, 0, true, false, 0>',
+    'gemm_kernel<256, 320, 4, 2, 1, false, true, 0>',
+    'gemm_kernel<256, 320, 4, 2, 2, false, true, 0>',
+    'gemm_kernel<256, 64, 4, 1, 1, false, false, 0>',
+    'gemm_ring_kernel<4, 32, 4, 0, false>',
+    'gemm_ring_kernel<4, 32, 4, 1, false>',
+    'gemm_ring_kernel<4, 32, 4, 2, false>',
+    'gemm_ws_kernel<320, 10, 64, false, false, false, false>',
+    'gemm_ws_kernel<320, 10, 64, false, false, false, true>',
+    'gemm_ws_kernel<320, 10, 64, false, true, false, false>',
+    'gemm_ws_kernel<320, 8, 64, false, false, true, true>',
+    'gemm_ws_kernel<512, 8, 32, true, false, true, false>',
+    'gemm_ws_kernel<640, 8, 32, false, false, true, false>',
+    'gemm_ws_kernel<640, 8, 32, false, false, true, true>',
+    'gemm_ws_kernel<640, 8, 32, false, true, true, false>',
+    'gemm_ws_kernel<640, 8, 32, true, false, true, false>',
+}
+
+# Mutation canaries on the headline forward: block -> (what is corrupted, item, frame).  The comparator must reject each
+# corrupted copy and name that block, item and frame.
+CANARIES = {
+    "up_blocks.3.resnets.1": ("tile", 1, 5),               # level 0, up path: one 256-row tile x 1.01
+    "down_blocks.3.resnets.1": ("swap", 0, 7),             # level 3: two adjacent 16-row groups swapped
+    "down_blocks.0.temp_attentions.0": ("last=first", 1, 23),   # an item's last frame replaced by its first
+}
+
+
+def _vdx():
+    import vdx  # noqa: F401
+    from vdx import ops, packing
+    return ops, packing
+
+
+@contextmanager
+def _fp32_reference():
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    saved = (torch.backends.cuda.matmul.allow_tf32, torch.backends.cudnn.allow_tf32, torch.backends.cudnn.enabled)
+    torch.backends.cuda.matmul.allow_tf32 = False
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cudnn.enabled = False
+    try:
+        with sdpa_kernel(SDPBackend.MATH), torch.no_grad():
+            yield
+    finally:
+        (torch.backends.cuda.matmul.allow_tf32, torch.backends.cudnn.allow_tf32, torch.backends.cudnn.enabled) = saved
+
+
+def _to_rows(y):
+    """(n, C, h, w) -> rows [n*h*w][C]"""
+    return y.permute(0, 2, 3, 1).reshape(-1, y.shape[1])
+
+
+def _chunks(n_items, F, S):
+    """(item, first frame, end frame) of the oracle calls: whole images of one item, at most CHUNK_ROWS rows."""
+    k = max(1, min(F, CHUNK_ROWS // S))
+    for b in range(n_items):
+        for f0 in range(0, F, k):
+            yield b, f0, min(f0 + k, F)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the comparator
+# ---------------------------------------------------------------------------------------------------------------
+class Report:
+    def __init__(self, name, cls, F, S):
+        self.name, self.cls, self.F, self.S = name, cls, F, S
+        self.kernels = []
+        self.fails = []
+
+    def where(self, row):
+        img = row // self.S
+        return img // self.F, img % self.F
+
+    def line(self):
+        b = BOUNDS[self.cls]
+        (fv, fi, ff), (tv, ti, tf, tr), (ev, ei, ef, er, ec) = self.frame, self.tile, self.elem
+        ks = " ".join(sorted(set(self.kernels)))
+        return (f"{self.name:34s} rel {self.rel:.2e}/{b[0]:.1e}  frame {fv:.2e}/{b[1]:.1e} (item {fi} f{ff})  "
+                f"tile {tv:.2e}/{b[2]:.1e} (item {ti} f{tf} row {tr})  elem {ev:.2e}/{b[3]:.1e} (item {ei} f{ef} row {er})"
+                + (f"  [{ks}]" if ks else "") + ("  FAIL " + "; ".join(self.fails) if self.fails else ""))
+
+
+def compare(name, cls, out, ref, base, F, S):
+    """out: the HIP rows [R][C] (fp16); ref: the oracle's rows (fp32); base: the block's identity-residual input rows or
+    None.  R = n_img * S, image i = (item i // F, frame i % F)."""
+    rep = Report(name, cls, F, S)
+    R, C = ref.shape
+    assert tuple(out.shape) == (R, C), (name, tuple(out.shape), (R, C))
+    assert R % S == 0, (name, R, S)
+    n_img = R // S
+    err = out.float() - ref
+    cmp = ref if base is None else ref - base.float()
+    assert torch.isfinite(err).all(), f"{name}: non-finite HIP output"
+    e2 = err.square().sum(1, dtype=torch.float64)
+    c2 = cmp.square().sum(1, dtype=torch.float64)
+    rep.rel = math.sqrt(float(e2.sum()) / max(float(c2.sum()), 1e-300))
+    fr = (e2.view(n_img, S).sum(1) / c2.view(n_img, S).sum(1).clamp_min(1e-300)).sqrt()
+    i = int(fr.argmax())
+    rep.frame = (float(fr[i]), i // F, i % F)
+    nt = -(-S // TILE)
+    pe = torch.zeros(n_img, nt * TILE, dtype=torch.float64, device=e2.device)
+    pc = torch.zeros_like(pe)
+    pe[:, :S], pc[:, :S] = e2.view(n_img, S), c2.view(n_img, S)
+    tr = (pe.view(n_img, nt, TILE).sum(2) / pc.view(n_img, nt, TILE).sum(2).clamp_min(1e-300)).sqrt()
+    j = int(tr.argmax())
+    img, t = j // nt, j % nt
+    rep.tile = (float(tr.view(-1)[j]), img // F, img % F, img * S + t * TILE)
+    scale = float(cmp.abs().max())
+    ratio = err.abs_().div_(cmp.abs().add_(scale))
+    k = int(ratio.argmax())
+    row, col = k // C, k % C
+    rep.elem = (float(ratio.view(-1)[k]), *rep.where(row), row, col)
+    del err, cmp, ratio
+    b = BOUNDS[cls]
+    if rep.rel > b[0]:
+        rep.fails.append(f"block rel-L2 {rep.rel:.3e} > {b[0]:.1e}")
+    if rep.frame[0] > b[1]:
+        rep.fails.append(f"rel-L2 {rep.frame[0]:.3e} > {b[1]:.1e} at item {rep.frame[1]} frame {rep.frame[2]}")
+    if rep.tile[0] > b[2]:
+        rep.fails.append(f"tile rel-L2 {rep.tile[0]:.3e} > {b[2]:.1e} at item {rep.tile[1]} frame {rep.tile[2]} rows "
+                         f"{rep.tile[3]}..{rep.tile[3] + TILE - 1}")
+    if rep.elem[0] > b[3]:
+        rep.fails.append(f"element ratio {rep.elem[0]:.3e} > {b[3]:.1e} at item {rep.elem[1]} frame {rep.elem[2]} row "
+                         f"{rep.elem[3]} column {rep.elem[4]}")
+    return rep
+
+
+def _corrupt(out, kind, item, frame, F, S):
+    """A corrupted copy of the block output `out` (rows [B*F*S][C])."""
+    bad = out.clone()
+    r0 = (item * F + frame) * S
+    if kind == "tile":
+        t = (S // TILE) // 2 * TILE
+        bad[r0 + t:r0 + t + TILE] *= 1.01
+    elif kind == "swap":
+        a, b = r0 + 16, r0 + 32
+        bad[a:a + 16], bad[b:b + 16] = out[b:b + 16], out[a:a + 16]
+    elif kind == "last=first":
+        first = (item * F) * S
+        bad[r0:r0 + S] = out[first:first + S]
+    return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the shadow: wrapped block methods and inline ops
+# ---------------------------------------------------------------------------------------------------------------
+FAMILY_OPS = ("conv3x3_gn", "tconv_gn", "cross_attn_block", "temporal_attn_block", "temporal_attn_block2", "ff_block",
+              "flash_attn", "temporal_attn")
+
+
+def _family(name, args, kw):
+    """The kernel family a vdx.ops call launches (the non-GEMM ones; GEMMs come from ops.PROFILE)."""
+    if name == "conv3x3_gn":
+        return "K1 conv3x3_gn"
+    if name == "tconv_gn":
+        F = kw["F"]
+        return f"K3 tconv_gn<{16 if F % 16 == 0 else 12 if F % 12 == 0 else 8}>"
+    if name == "cross_attn_block":
+        return f"K5 cross_attn_block<{args[0].shape[1]}>"
+    if name == "temporal_attn_block":
+        return f"K7 temporal_attn_block<{args[0].shape[1]}>"
+    if name == "temporal_attn_block2":
+        return f"K7b temporal_attn_block2<{args[0].shape[1]}>"
+    if name == "ff_block":
+        return f"K8 ff_block<{args[0].shape[1]}{', proj_out' if kw.get('proj') is not None else ''}>"
+    if name == "flash_attn":
+        return f"flash_attn<{'v_rows' if kw.get('v_rows') else 'vt'}>"
+    return name
+
+
+class Shadow:
+    """Wraps the four block methods of one model instance and the vdx.ops calls `forward` makes inline; every wrapped call
+    is compared with the oracle as it returns, and its copies are dropped."""
+
+    def __init__(self, m, ref, ehs, t, F, canaries=None):
+        self.m, self.ref, self.t, self.F = m, ref, t, F
+        self.ehs = ehs.float()
+        self.canaries = canaries or {}
+        self.reports = {}
+        self.canary_reports = {}
+        self.dispatch = set()
+        self.block_kernels = None
+        self.temb = self.e = self.gn_in = None
+        self.oracle_s = 0.0
+        W = m.W
+        # the GEMMs forward launches inline, by the identity of their weight tensor -> the name they are compared under
+        key = {"time_embedding.linear_1.weight": "time_proj", "time_embedding.linear_2.weight": "time_embedding",
+               "time_emb_proj_all.weight": "time_emb_proj_all", "conv_out.weight": "conv_out"}
+        for n in W:
+            if n.endswith((".downsamplers.0.conv.weight", ".upsamplers.0.conv.weight")):
+                key[n] = n[:-len(".conv.weight")]
+        self.by_weight = {id(W[n]): v for n, v in key.items()}
+        self.conv_in_w, self.norm_out_w = W["conv_in.weight"], W["conv_norm_out.weight"]
+
+    # -- plumbing ---------------------------------------------------------------------------------------------
+    def __enter__(self):
+        ops, _ = _vdx()
+        self.ops = ops
+        self.saved_ops = {n: getattr(ops, n) for n in FAMILY_OPS + ("gemm", "conv_in", "groupnorm")}
+        self.saved_profile = (ops.PROFILE, ops.PROFILE_ONLY)
+        ops.PROFILE, ops.PROFILE_ONLY = [], ("gemm",)         # GEMM launches by instantiation name (after the plan's split)
+        for n in FAMILY_OPS:
+            setattr(ops, n, self._family_wrapper(n, self.saved_ops[n]))
+        ops.gemm, ops.conv_in, ops.groupnorm = self._gemm, self._conv_in, self._groupnorm
+        m = self.m
+        self.orig = {n: getattr(m, n) for n in ("_resnet", "_temp_conv", "_spatial_transformer", "_temporal_transformer")}
+        m._resnet, m._temp_conv = self._resnet, self._temp_conv
+        m._spatial_transformer, m._temporal_transformer = self._spatial, self._temporal
+        return self
+
+    def __exit__(self, *exc):
+        ops = self.ops
+        for n, f in self.saved_ops.items():
+            setattr(ops, n, f)
+        self.drain_profile()
+        ops.PROFILE, ops.PROFILE_ONLY = self.saved_profile
+        for n in self.orig:
+            self.m.__dict__.pop(n, None)
+        return False
+
+    def drain_profile(self):
+        """GEMM launches recorded since the last call -> the dispatch set; returns how many there were."""
+        n = len(self.ops.PROFILE)
+        self.dispatch.update(rec[0] for rec in self.ops.PROFILE)
+        self.ops.PROFILE.clear()
+        return n
+
+    def _family_wrapper(self, name, fn):
+        def wrapped(*args, **kw):
+            fam = _family(name, args, kw)
+            self.dispatch.add(fam)
+            if self.block_kernels is not None:
+                self.block_kernels.append(fam.split(" ")[0] if fam.startswith("K") else fam.split("<")[0])
+            return fn(*args, **kw)
+        return wrapped
+
+    def _oracle(self, fn):
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        self.oracle_s += time.perf_counter() - t0
+        return r
+
+    def _check(self, name, cls, out, ref, base, F, S, kernels=()):
+        rep = compare(name, cls, out, ref, base, F, S)
+        rep.kernels += list(kernels)
+        assert name not in self.reports, f"{name} compared twice"
+        self.reports[name] = rep
+        if name in self.canaries:
+            kind, item, frame = self.canaries[name]
+            self.canary_reports[name] = compare(name, cls, _corrupt(out, kind, item, frame, F, S), ref, base, F, S)
+        return rep
+
+    def _block(self, call):
+        """Runs one HIP block; returns its output and the kernel families it launched."""
+        self.drain_profile()
+        self.block_kernels = []
+        try:
+            out = call()
+        finally:
+            kernels, self.block_kernels = self.block_kernels, None
+        return out, kernels + (["gemm"] if self.drain_profile() else [])
+
+    # -- the blocks ---------------------------------------------------------------------------------------------
+    def _resnet(self, p, x, x2, temb_all, n_img, F, hh, ww, part=0, ksplit_ok=True):
+        # (the owned-input protocol: the model clears a list it is handed — keep our own references first)
+        xs = list(x) if isinstance(x, list) else [x] + ([x2] if x2 is not None else [])
+        out, ks = self._block(lambda: self.orig["_resnet"](p, x, x2, temb_all, n_img, F, hh, ww, part=part, ksplit_ok=ksplit_ok))
+        _, packing = _vdx()
+        mod = self.ref.get_submodule(p)
+        S = hh * ww
+        ref = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+
+        def run():
+            for b, f0, f1 in _chunks(n_img // F, F, S):
+                r0, r1 = (b * F + f0) * S, (b * F + f1) * S
+                xi = torch.cat([packing.rows_to_nchw(t[r0:r1], f1 - f0, hh, ww) for t in xs], 1).float()
+                ref[r0:r1] = _to_rows(mod(xi, self.e[b:b + 1].expand(f1 - f0, -1)))
+        self._oracle(run)
+        self._check(p, "resnet", out, ref, xs[0] if mod.conv_shortcut is None else None, F, S, ks)
+        return out
+
+    def _temporal_rows(self, mod, x, B, F, S, out):
+        """TemporalConvLayer / TransformerTemporalModel per CFG item: statistics over the item's frames and pixels.  The
+        pixels of a frame stand as an (S, 1) image: both modules act on each pixel's frame sequence."""
+        _, packing = _vdx()
+        ref = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+
+        def run():
+            for b in range(B):
+                r0, r1 = b * F * S, (b + 1) * F * S
+                y = mod(packing.rows_to_nchw(x[r0:r1], F, S, 1).float(), F)
+                ref[r0:r1] = _to_rows(y)
+        self._oracle(run)
+        return ref
+
+    def _temp_conv(self, p, x, B, F, S, part=0, ksplit_ok=True):
+        out, ks = self._block(lambda: self.orig["_temp_conv"](p, x, B, F, S, part=part, ksplit_ok=ksplit_ok))
+        ref = self._temporal_rows(self.ref.get_submodule(p), x, B, F, S, out)
+        self._check(p, "temp_conv", out, ref, x, F, S, ks)
+        return out
+
+    def _temporal(self, p, x, B, F, S, heads, part=0, ksplit_ok=True):
+        out, ks = self._block(lambda: self.orig["_temporal_transformer"](p, x, B, F, S, heads, part=part, ksplit_ok=ksplit_ok))
+        ref = self._temporal_rows(self.ref.get_submodule(p), x, B, F, S, out)
+        self._check(p, "temporal", out, ref, x, F, S, ks)
+        return out
+
+    def _spatial(self, p, x, ehs_pad, n_img, F, hh, ww, dup=False):
+        """`dup`: x holds ONE item's rows (the CFG-shared prefix); the output holds both items."""
+        out, ks = self._block(lambda: self.orig["_spatial_transformer"](p, x, ehs_pad, n_img, F, hh, ww, dup=dup))
+        _, packing = _vdx()
+        mod = self.ref.get_submodule(p)
+        S = hh * ww
+        ref = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+
+        def run():
+            for b, f0, f1 in _chunks(n_img // F, F, S):
+                s0 = f0 if dup else b * F + f0
+                xi = packing.rows_to_nchw(x[s0 * S:(s0 + f1 - f0) * S], f1 - f0, hh, ww).float()
+                y = mod(xi, self.ehs[b:b + 1].expand(f1 - f0, -1, -1))
+                ref[(b * F + f0) * S:(b * F + f1) * S] = _to_rows(y)
+        self._oracle(run)
+        self._check(p, "spatial", out, ref, torch.cat([x, x]) if dup else x, F, S, ks)
+        return out
+
+    # -- the inline steps of forward ------------------------------------------------------------------------------
+    def _conv_in(self, x, w, bias, out=None):
+        y = self.saved_ops["conv_in"](x, w, bias, out=out)
+        if w is not self.conv_in_w:
+            return y
+        self.drain_profile()
+        B1, _, F, hh, ww = x.shape
+        S = hh * ww
+        ref = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+
+        def run():
+            for b, f0, f1 in _chunks(B1, F, S):
+                ref[(b * F + f0) * S:(b * F + f1) * S] = _to_rows(self.ref.conv_in(x[b, :, f0:f1].permute(1, 0, 2, 3).float()))
+        self._oracle(run)
+        self._check("conv_in", "conv_in", y, ref, None, F, S, ["gemm"])
+        return y
+
+    def _groupnorm(self, x, gamma, beta, **kw):
+        if gamma is self.norm_out_w:
+            self.gn_in = (x, kw["n_samples"], kw["rows_per_sample"])
+        return self.saved_ops["groupnorm"](x, gamma, beta, **kw)
+
+    def _gemm(self, a, w, **kw):
+        y = self.saved_ops["gemm"](a, w, **kw)
+        name = self.by_weight.get(id(w))
+        if name is None:
+            return y
+        self.drain_profile()
+        from oracle.unet3d_ref import timestep_embedding
+        ref_m, F = self.ref, self.F
+        if name == "time_proj":               # a = the sinusoidal embedding, y = linear_1
+            self.temb = a
+            want = timestep_embedding(torch.full((a.shape[0],), float(self.t), device=a.device), a.shape[1])
+            self._check("time_proj", "time", a, want, None, 1, 1)
+        elif name == "time_embedding":        # y = linear_2(SiLU(linear_1(temb)))
+            want = self._oracle(lambda: ref_m.time_embedding(self.temb.float()))
+            self._check("time_embedding", "time", y, want, None, 1, 1, ["gemm"])
+            self.e = y.float()
+        elif name == "time_emb_proj_all":
+            se = Fn.silu(self.e)
+            want = self._oracle(lambda: torch.cat([ref_m.get_submodule(n).time_emb_proj(se) for n in self.m._resnet_names()], 1))
+            self._check("time_emb_proj_all", "time", y, want, None, 1, 1, ["gemm"])
+        elif name == "conv_out":              # conv_out(SiLU(conv_norm_out(x))), the kernel's N padded to 64
+            x, n_img, S = self.gn_in
+            self.gn_in = None
+            _, packing = _vdx()
+            _, hh, ww = kw["conv"][:3]
+            co = ref_m.conv_out.out_channels
+            ref = torch.empty((n_img * S, co), dtype=torch.float32, device=y.device)
+
+            def run():
+                for b, f0, f1 in _chunks(n_img // F, F, S):
+                    r0, r1 = (b * F + f0) * S, (b * F + f1) * S
+                    xi = packing.rows_to_nchw(x[r0:r1], f1 - f0, hh, ww).float()
+                    ref[r0:r1] = _to_rows(ref_m.conv_out(Fn.silu(ref_m.conv_norm_out(xi))))
+            self._oracle(run)
+            self._check("conv_out", "conv_out", y[:, :co], ref, None, F, S, ["gemm"])
+        else:                                 # a sampler: (n_img, h_in, w_in, h_out, w_out, stride, upsample)
+            _, packing = _vdx()
+            n_img, hi, wi, ho, wo, stride, up = kw["conv"]
+            mod = ref_m.get_submodule(name)
+            Si, So = hi * wi, ho * wo
+            ref = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+
+            def run():
+                for b, f0, f1 in _chunks(n_img // F, F, Si):
+                    i0, i1 = b * F + f0, b * F + f1
+                    xi = packing.rows_to_nchw(a[i0 * Si:i1 * Si], i1 - i0, hi, wi).float()
+                    yi = mod(xi) if stride == 2 else mod(xi, None if up == 1 else (ho, wo))
+                    ref[i0 * So:i1 * So] = _to_rows(yi)
+            self._oracle(run)
+            self._check(name, "sampler", y, ref, None, F, So, ["gemm"])
+        return y
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# models
+# ---------------------------------------------------------------------------------------------------------------
+def _table(gpu, kind):
+    """The fp16 table both models load.  `hard`: spatial self-attention q and k x2 (bench.py --peaked) and every
+    GroupNorm / LayerNorm gamma ~ N(1, 0.3), beta ~ N(0, 0.3) — synthetic N(0, 0.02)-scale weights with gamma ~ 1 are the
+    kernels' easy case."""
+    from vdx.unet3d import UNet3DConfig
+    from vdx.weights import synthetic_state_dict
+    from oracle.unet3d_ref import UNet3DConditionModelRef, UNet3DConfig as RefCfg
+    sd = synthetic_state_dict(UNet3DConfig.zeroscope(), 1234, gpu)
+    if kind == "hard":
+        g = torch.Generator(device=gpu).manual_seed(4321)
+        with torch.device("meta"):
+            shape = UNet3DConditionModelRef(RefCfg.zeroscope())
+        for n, mod in shape.named_modules():
+            if isinstance(mod, (torch.nn.GroupNorm, torch.nn.LayerNorm)):
+                c = mod.weight.shape
+                sd[n + ".weight"] = (1 + 0.3 * torch.randn(c, generator=g, device=gpu)).half()
+                sd[n + ".bias"] = (0.3 * torch.randn(c, generator=g, device=gpu)).half()
+        for n in sd:
+            if ".attentions." in n and n.endswith((".attn1.to_q.weight", ".attn1.to_k.weight")):
+                sd[n] = sd[n] * 2
+    return sd
+
+
+@pytest.fixture(scope="module")
+def xl_pairs(gpu):
+    """kind -> (HIP UNet, fp32 oracle UNet on the GPU), both from one fp16 table; one pair alive at a time."""
+    _vdx()
+    from vdx.unet3d import UNet3DConditionModel, UNet3DConfig
+    from oracle.unet3d_ref import UNet3DConditionModelRef, UNet3DConfig as RefCfg
+    cache = {}
+
+    def get(kind):
+        if kind not in cache:
+            cache.clear()
+            torch.cuda.empty_cache()
+            sd = _table(gpu, kind)
+            m = UNet3DConditionModel(UNet3DConfig.zeroscope()).load_diffusers_state_dict(sd, device=gpu)
+            with torch.device("meta"):
+                ref = UNet3DConditionModelRef(RefCfg.zeroscope())
+            ref = ref.to_empty(device=gpu).eval()
+            ref.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
+            del sd
+            cache[kind] = (m, ref)
+        return cache[kind]
+    yield get
+    cache.clear()
+    torch.cuda.empty_cache()
+
+
+def _expected_blocks(ref):
+    from oracle import unet3d_ref as o
+    kinds = {o.ResnetBlock2D: "resnet", o.TemporalConvLayer: "temp_conv", o.Transformer2DModel: "spatial",
+             o.TransformerTemporalModel: "temporal", o.Downsample2D: "sampler", o.Upsample2D: "sampler"}
+    names = {n: kinds[type(mod)] for n, mod in ref.named_modules() if type(mod) in kinds}
+    names.update(time_proj="time", time_embedding="time", time_emb_proj_all="time", conv_in="conv_in", conv_out="conv_out")
+    return names
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# tests
+# ---------------------------------------------------------------------------------------------------------------
+def test_gpu_reference_matches_cpu_oracle(gpu, xl_pairs):
+    """The reference itself: the GPU-fp32 evaluation (settings of `_fp32_reference`) of a level-0 ResNet and a level-0 spatial
+    transformer agrees with the same oracle modules on the CPU at F = 2 (72x128), rel-L2 <= 1e-5."""
+    _, ref = xl_pairs("synthetic")
+    torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
+    g = torch.Generator().manual_seed(2)
+    x = (torch.randn(2, 320, H, W, generator=g) * 1.3 + 0.2).half().float()
+    emb = torch.randn(1, 1280, generator=g).expand(2, -1)
+    ehs = torch.randn(1, 77, 1024, generator=g).half().float().expand(2, -1, -1)
+    for p, args in (("down_blocks.0.resnets.0", (x, emb)), ("down_blocks.0.attentions.0", (x, ehs))):
+        mod = ref.get_submodule(p)
+        with _fp32_reference():
+            got = mod(*(a.to(gpu) for a in args)).cpu()
+        with torch.no_grad():
+            want = copy.deepcopy(mod).cpu()(*args)
+        err = float((got.double() - want.double()).norm() / want.double().norm())
+        print(f"{p}: GPU fp32 vs CPU fp32 rel-L2 {err:.2e}")
+        assert err <= 1e-5, f"{p}: the GPU reference differs from the CPU oracle (rel-L2 {err:.2e})"
+
+
+@pytest.mark.parametrize("config", list(CONFIGS))
+def test_every_block_matches_oracle(gpu, xl_pairs, config):
+    """One CFG forward (ops.cfg_input: the shared prefix), t = 981, shadowed block by block; plus the guards: the shadowed
+    forward has the plain forward's bits, every oracle block was compared, the headline dispatch is the pinned one, and
+    the canaries are rejected where they were planted."""
+    ops, _ = _vdx()
+    kind, F, with_ctx, headline = CONFIGS[config]
+    m, ref = xl_pairs(kind)
+    g = torch.Generator(device=gpu).manual_seed(100 + F + (7 if kind == "hard" else 0))
+    lat = torch.randn(1, 4, F, H, W, generator=g, device=gpu).half()
+    ctx = torch.randn(1, 4, 1, H, W, generator=g, device=gpu).half() if with_ctx else None
+    ehs = torch.randn(2, 77, 1024, generator=g, device=gpu).half()
+    x = ops.cfg_input(lat, ctx, 0.35 if with_ctx else 0.0)
+    t0 = time.perf_counter()
+    plain = m(x, T, encoder_hidden_states=ehs).sample
+    assert m.last_forward_shared_prefix, "a cfg_input batch did not take the shared prefix"
+    torch.cuda.reset_peak_memory_stats()
+    with _fp32_reference(), Shadow(m, ref, ehs, T, F, canaries=CANARIES if headline else None) as sh:
+        shadowed = m(x, T, encoder_hidden_states=ehs).sample
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    reps = list(sh.reports.values())
+    print(f"\n== {config}: (2, 4, {F}, {H}, {W}), {kind} weights, ctx {'on' if with_ctx else 'off'}: {len(reps)} blocks, "
+          f"output std {float(plain.float().std()):.3f}; {wall:.1f} s ({sh.oracle_s:.1f} s in the oracle), "
+          f"peak {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    for r in reps:
+        print(r.line())
+    for cls in BOUNDS:
+        rs = [r for r in reps if r.cls == cls]
+        if rs:
+            print(f"  class {cls:9s} worst: block {max(r.rel for r in rs):.3e}  frame {max(r.frame[0] for r in rs):.3e}  "
+                  f"tile {max(r.tile[0] for r in rs):.3e}  elem {max(r.elem[0] for r in rs):.3e}")
+    print(f"  dispatch: {sorted(sh.dispatch)}")
+
+    problems = []
+    # wrapping changes nothing
+    if not torch.equal(plain, shadowed):
+        problems.append("the shadowed forward's output differs from the plain forward's")
+    # every block compared, nothing silently skipped
+    want = _expected_blocks(ref)
+    if set(sh.reports) != set(want):
+        problems.append(f"compared blocks != the oracle's: missing {sorted(set(want) - set(sh.reports))}, "
+                        f"extra {sorted(set(sh.reports) - set(want))}")
+    problems += [f"{r.name}: class {r.cls}, oracle class {want[r.name]}" for r in reps if r.name in want and want[r.name] != r.cls]
+    # dispatch coverage of the headline forward is pinned
+    if headline and sh.dispatch != HEADLINE_DISPATCH:
+        problems.append(f"headline dispatch changed: new {sorted(sh.dispatch - HEADLINE_DISPATCH)}, "
+                        f"gone {sorted(HEADLINE_DISPATCH - sh.dispatch)}")
+    # mutation canaries: each corrupted copy is rejected, and the report names its block, item and frame
+    if headline:
+        for name, (kind_, item, frame) in CANARIES.items():
+            c = sh.canary_reports.get(name)
+            if c is None:
+                problems.append(f"canary {name}: block not reached")
+                continue
+            print(f"  canary {kind_:10s} -> {c.line()}")
+            located = [loc for loc, v, b in ((c.frame[1:3], c.frame[0], BOUNDS[c.cls][1]), (c.tile[1:3], c.tile[0], BOUNDS[c.cls][2]),
+                                             (c.elem[1:3], c.elem[0], BOUNDS[c.cls][3])) if v > b]
+            if not c.fails:
+                problems.append(f"canary {name} ({kind_}, item {item} frame {frame}): the comparator accepted it")
+            elif not located or any(tuple(loc) != (item, frame) for loc in located):
+                problems.append(f"canary {name} ({kind_}): rejected at {located}, corrupted item {item} frame {frame}")
+    problems += [f"{r.name}: " + "; ".join(r.fails) for r in reps if r.fails]
+    assert not problems, f"{config}:\n  " + "\n  ".join(problems)

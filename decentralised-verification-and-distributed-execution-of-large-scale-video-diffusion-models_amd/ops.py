@@ -7,6 +7,7 @@ activations are channels-last row matrices [pixels][channels].
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -47,16 +48,62 @@ def round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+def _launch(symbol: str, *args) -> None:
+    """Enqueue `symbol`(*args) on torch's current stream; a failure raises VdxError labelled with `symbol`."""
+    _lib.check(getattr(_lib.load(), symbol)(*args, _stream()), symbol)
+
+
+@contextlib.contextmanager
+def _timed(name: Optional[str], flops: float, shape: tuple):
+    """bench.py instrumentation around one launch: with PROFILE set and `name` profiled, HIP events on the launch stream
+    just before and after the body, appended to PROFILE as (name, algorithmic FLOPs, start, end, shape)."""
+    if PROFILE is None or not _profiled(name):
+        yield
+        return
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    PROFILE.append((name, flops, ev0, ev1, shape))
+
+
+def _covers(t, rows: int, cols: int, what: str, name: str, rows_per_row: int = 1) -> int:
+    """Row stride of the optional row matrix `t` (0 without one), which must cover [rows][cols] of the product when each
+    of its rows serves `rows_per_row` product rows (bias2: one time-embedding row per sample)."""
+    if t is None:
+        return 0
+    r, c, ld = _rows(t, name)
+    if rows_per_row <= 0 or r * rows_per_row < rows or c < cols:
+        raise VdxError(f"{what}: {name} {tuple(t.shape)} does not cover [{rows}][{cols}]")
+    return ld
+
+
+def _out(out, rows: int, cols: int, like: torch.Tensor, what: str):
+    """-> (out, ldo): `out`, or a new fp16 [rows][cols] on `like`'s device; a given `out` must cover [rows][cols]."""
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.float16, device=like.device)
+    return out, _covers(out, rows, cols, what, "out")
+
+
+def _packed(blob, nbytes: int, what: str, packer: str) -> None:
+    """A fused block's weight blob must be contiguous fp16 of exactly the kernel's `nbytes` (the layout `packer` builds)."""
+    if blob.dtype != torch.float16 or blob.numel() * 2 != nbytes or not blob.is_contiguous():
+        raise VdxError(f"{what} does not match the kernel's layout ({packer})")
+
+
 # --------------------------------------------------------------------------------------------
-_KSPLIT_WS = {}     # (device, stream) -> fp32 workspace of the split-K tails (grown on demand; the slice kernel and its
-                    # reduction are ordered by ONE stream, so two streams must not share slabs)
+_KSPLIT_WS: dict = {}   # fp32 partial slabs of the split-K tails
+_GN_WS: dict = {}       # GroupNorm statistics (vdx_groupnorm_workspace_part)
 
 
-def _ksplit_workspace(device, nbytes):
+def _scratch(pool: dict, device, nbytes: int, dtype: torch.dtype, minimum: int = 0) -> torch.Tensor:
+    """A workspace of at least `nbytes` from `pool`: one buffer per (device, stream), grown on demand to
+    max(nbytes, minimum) bytes.  A kernel and the launch that reads what it left there are ordered by ONE stream, so two
+    streams must not share a buffer."""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _KSPLIT_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _KSPLIT_WS[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    ws = pool.get(key)
+    if ws is None or ws.numel() * ws.element_size() < nbytes:
+        ws = pool[key] = torch.empty(-(-max(nbytes, minimum) // dtype.itemsize), dtype=dtype, device=device)
     return ws
 
 
@@ -69,7 +116,6 @@ def groupnorm_linear(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sam
     """Linear(GroupNorm(x)) without the normalised tensor (`norm` -> `proj_in` of the transformer blocks): the statistics
     pass, then one weight matrix + fp32 bias per sample (`vdx_groupnorm_fold_linear_f16`), then the weights-stationary GEMM
     on the raw rows with `wset_rows = rows_per_sample`."""
-    lib = _lib.load()
     r, Cc, ldx = _rows(x, "x")
     M = n_samples * rows_per_sample
     N, K = w.shape
@@ -77,18 +123,13 @@ def groupnorm_linear(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sam
         raise VdxError(f"groupnorm_linear: x [{r}][{Cc}], w [{N}][{K}], gamma {gamma.numel()}: shapes do not match")
     if not groupnorm_linear_supported(Cc, N, rows_per_sample) or not w.is_contiguous():
         raise VdxError(f"groupnorm_linear: C={Cc}, N={N}, rows_per_sample={rows_per_sample} not supported")
-    need = lib.vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
-    key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-        _gn_ws[key] = ws
+    need = _lib.load().vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
+    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
     w_s = torch.empty((n_samples * N, K), dtype=torch.float16, device=x.device)
     b_s = torch.empty((n_samples, N), dtype=torch.float32, device=x.device)
-    _lib.check(lib.vdx_groupnorm_fold_linear_f16(_p(x, "x"), Cc, ldx, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups,
-                                                 n_samples, rows_per_sample, ws.data_ptr(), partition_samples, _p(w, "w"),
-                                                 _p(bias, "bias"), N, w_s.data_ptr(), b_s.data_ptr(), _stream()),
-               "vdx_groupnorm_fold_linear_f16")
+    _launch("vdx_groupnorm_fold_linear_f16", _p(x, "x"), Cc, ldx, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups,
+            n_samples, rows_per_sample, ws.data_ptr(), partition_samples, _p(w, "w"), _p(bias, "bias"), N, w_s.data_ptr(),
+            b_s.data_ptr())
     return gemm(x, w_s, M=M, wset_rows=rows_per_sample, wset_bias=b_s, out=out)
 
 
@@ -102,7 +143,6 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     callers that rely on row-split bit-identity do not pass it).  `ksplit`: pin it for rows [row_begin, row_end).
     `wset_rows` / `wset_bias`: one weight set per `wset_rows` rows, w = [M / wset_rows][N][K] and an fp32 bias per set
     (a GroupNorm folded into the Linear: `groupnorm_linear`)."""
-    lib = _lib.load()
     ar, c1, lda = _rows(a, "a")
     N, K = w.shape
     if wset_rows:
@@ -139,23 +179,12 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
         g.frames, g.hw = frames, hw
     if ar < need_rows or (a2 is not None and a2r < need_rows):
         raise VdxError(f"gemm: source has {ar} rows, kernel would read {need_rows}")
-    if out is None:
-        out = torch.empty((M, n_out), dtype=torch.float16, device=a.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < n_out:
-        raise VdxError(f"gemm: out {tuple(out.shape)} smaller than [{M}][{n_out}]")
+    out, ldo = _out(out, M, n_out, a, "gemm")
     if bias is not None and bias.numel() != N:
         raise VdxError(f"gemm: bias has {bias.numel()} elements, N={N}")
-    if bias2 is not None:
-        b2r, b2c, ldb2 = _rows(bias2, "bias2")
-        if rows_per_bias2 <= 0 or b2r * rows_per_bias2 < M or b2c < N:
-            raise VdxError("gemm: bias2 does not cover M rows / N columns")
-        g.rows_per_bias2, g.ldb2 = rows_per_bias2, ldb2
-    if residual is not None:
-        rr, rc, ldr = _rows(residual, "residual")
-        if rr < M or rc < N:
-            raise VdxError(f"gemm: residual {tuple(residual.shape)} smaller than [{M}][{N}]")
-        g.ldr = ldr
+    g.ldb2 = _covers(bias2, M, N, "gemm", "bias2", rows_per_bias2)
+    g.rows_per_bias2 = rows_per_bias2 if bias2 is not None else 0
+    g.ldr = _covers(residual, M, N, "gemm", "residual")
     g.a, g.a2, g.w = _p(a, "a"), _p(a2, "a2"), _p(w, "w")
     g.bias, g.bias2, g.residual, g.out = _p(bias, "bias"), _p(bias2, "bias2"), _p(residual, "residual"), _p(out, "out")
     g.M, g.N, g.K, g.mode, g.c1, g.c2 = M, N, K, mode, c1, c2
@@ -174,6 +203,7 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
         plan_ = _PLAN_CACHE.get(key)
         if plan_ is None:
             v_, split_, ks_, wsb_ = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_size_t(0)
+            lib = _lib.load()           # host-only queries: no stream
             if allow_ksplit:
                 _lib.check(lib.vdx_gemm_plan_ksplit(C.byref(g), C.byref(split_), C.byref(ks_), C.byref(wsb_)), "vdx_gemm_plan_ksplit")
             if ks_.value == 0:
@@ -188,23 +218,17 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     for rb, re_, ks in spans:
         g.row_begin, g.row_end, g.ksplit, g.workspace, g.workspace_bytes = rb, re_, ks, None, 0
         if ks > 1:
-            ws_ = _ksplit_workspace(out.device, wsb)
+            ws_ = _scratch(_KSPLIT_WS, out.device, wsb, torch.float32)
             g.workspace, g.workspace_bytes = ws_.data_ptr(), ws_.numel() * 4
+        rows = (re_ or M) - rb
+        name = None                     # only named when bench.py profiles (gemm_kernel_name is not free on the host)
         if PROFILE is not None:
-            rows = (re_ or M) - rb
             name = gemm_kernel_name(rows, N, K, mode, geglu, 7 if wset_rows else variant, single_source=a2 is None and bias2 is None,
                                     residual=residual is not None, whole=(rb == 0 and re_ in (0, M)), wset=bool(wset_rows))
             if ks > 1:
                 name = f"gemm_kernel<256, 320, 4, 2, {mode}, false, {'true' if mode else 'false'}, 1> split-K + reduce"
-        if PROFILE is None or not _profiled(name):
-            _lib.check(lib.vdx_gemm_f16(C.byref(g), _stream()), "vdx_gemm_f16")
-            continue
-        # bench.py instrumentation: HIP events on the launch stream around this one kernel
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        _lib.check(lib.vdx_gemm_f16(C.byref(g), _stream()), "vdx_gemm_f16")
-        ev1.record()
-        PROFILE.append((name, 2.0 * rows * N * K, ev0, ev1, (rows, N, K)))
+        with _timed(name, 2.0 * rows * N * K, (rows, N, K)):
+            _launch("vdx_gemm_f16", C.byref(g))
     return out
 
 
@@ -255,7 +279,6 @@ def gemm_kernel_name(M: int, N: int, K: int, mode: int, geglu: bool, variant: in
 def conv_in(x, w, bias, out=None):
     """x (B,Cin,F,H,W) fp16 -> rows [B*F*H*W][Cout]; w [Cout][Kpad] = pack_conv3x3 zero-padded in K
     to a multiple of 64.  im2col gather (HBM-light: Cin = 4) + the MFMA GEMM."""
-    lib = _lib.load()
     B, Cin, F, H, W = x.shape
     if not x.is_contiguous():
         raise VdxError("conv_in: x must be contiguous (B,C,F,H,W)")
@@ -264,13 +287,11 @@ def conv_in(x, w, bias, out=None):
         raise VdxError("conv_in: w must be contiguous [Cout][Kpad], Kpad a multiple of 64 >= 9*Cin")
     M = B * F * H * W
     cols = torch.empty((M, Kpad), dtype=torch.float16, device=x.device)
-    _lib.check(lib.vdx_im2col_in_f16(_p(x, "x"), _p(cols, "cols"), B, Cin, F, H, W, Kpad, _stream()),
-               "vdx_im2col_in_f16")
+    _launch("vdx_im2col_in_f16", _p(x, "x"), _p(cols, "cols"), B, Cin, F, H, W, Kpad)
     return gemm(cols, w, M=M, bias=bias, out=out)
 
 
 def rows_to_ncfhw(rows, B, C, F, H, W, out=None):
-    lib = _lib.load()
     r, c, ld = _rows(rows, "rows")
     if r < B * F * H * W or c < C:
         raise VdxError("rows_to_ncfhw: rows too small")
@@ -278,53 +299,47 @@ def rows_to_ncfhw(rows, B, C, F, H, W, out=None):
         out = torch.empty((B, C, F, H, W), dtype=torch.float16, device=rows.device)
     if tuple(out.shape) != (B, C, F, H, W) or not out.is_contiguous():
         raise VdxError("rows_to_ncfhw: bad out")
-    _lib.check(lib.vdx_rows_to_ncfhw_f16(_p(rows, "rows"), ld, _p(out, "out"), B, C, F, H, W, _stream()),
-               "vdx_rows_to_ncfhw_f16")
+    _launch("vdx_rows_to_ncfhw_f16", _p(rows, "rows"), ld, _p(out, "out"), B, C, F, H, W)
     return out
 
 
 def silu(x, out=None):
-    lib = _lib.load()
     if not x.is_contiguous():
         raise VdxError("silu: x must be contiguous")
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(lib.vdx_silu_f16(_p(x, "x"), _p(out, "out"), x.numel(), _stream()), "vdx_silu_f16")
+    _launch("vdx_silu_f16", _p(x, "x"), _p(out, "out"), x.numel())
     return out
 
 
 def timestep_embedding(t_dev, B, dim, out=None):
     """Sinusoidal embedding of ONE fp32 timestep held in device memory -> fp16 [B][dim] (include/vdx.h)."""
-    lib = _lib.load()
     if t_dev.dtype != torch.float32 or t_dev.numel() != 1:
         raise VdxError("timestep_embedding: t must be one fp32 value on the GPU")
     if out is None:
         out = torch.empty((B, dim), dtype=torch.float16, device=t_dev.device)
-    _lib.check(lib.vdx_timestep_embedding_f16(_p(t_dev, "t", torch.float32), _p(out, "out"), B, dim, _stream()),
-               "vdx_timestep_embedding_f16")
+    _launch("vdx_timestep_embedding_f16", _p(t_dev, "t", torch.float32), _p(out, "out"), B, dim)
     return out
 
 
 def gelu(x, out=None):
-    lib = _lib.load()
     if not x.is_contiguous():
         raise VdxError("gelu: x must be contiguous")
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(lib.vdx_gelu_f16(_p(x, "x"), _p(out, "out"), x.numel(), _stream()), "vdx_gelu_f16")
+    _launch("vdx_gelu_f16", _p(x, "x"), _p(out, "out"), x.numel())
     return out
 
 
 def quick_gelu(x, out=None):
     """x * sigmoid(1.702 x): CLIP ViT-B/32's MLP activation (vdx_quick_gelu_f16)."""
-    lib = _lib.load()
     if not x.is_contiguous():
         raise VdxError("quick_gelu: x must be contiguous")
     if out is None:
         out = torch.empty_like(x)
     if out.shape != x.shape or not out.is_contiguous():
         raise VdxError("quick_gelu: out must be contiguous and shaped like x")
-    _lib.check(lib.vdx_quick_gelu_f16(_p(x, "x"), _p(out, "out"), x.numel(), _stream()), "vdx_quick_gelu_f16")
+    _launch("vdx_quick_gelu_f16", _p(x, "x"), _p(out, "out"), x.numel())
     return out
 
 
@@ -406,14 +421,7 @@ def clip_preprocess(frames, out=None, return_u8=False):
     """uint8 RGB frames (F, H, W, 3) on the GPU (rows and frames may be pitched; pixels packed) -> the patch-GEMM rows
     fp16 [F*49][3072] of Resize((224, 224)) + ToTensor + Normalize(ImageNet).  `return_u8`: also the resized uint8
     (F, 224, 224, 3) image -> (rows, u8)."""
-    lib = _lib.load()
-    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise VdxError(f"clip_preprocess: expected uint8 (F, H, W, 3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)}")
-    F, H, W, _ = frames.shape
-    if F == 0 or H == 0 or W == 0:
-        raise VdxError("clip_preprocess: empty frames")
-    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) < 3 * W or frames.stride(0) < frames.stride(1) * H:
-        raise VdxError("clip_preprocess: pixels must be packed RGB with non-overlapping rows and frames")
+    F, H, W = _check_u8_frames(frames, "clip_preprocess")
     dev = frames.device
     xb, xk, _ = _clip_table(W, dev)
     yb, yk, yb_host = _clip_table(H, dev)
@@ -423,46 +431,35 @@ def clip_preprocess(frames, out=None, return_u8=False):
     span = clip_band_span(yb_host, band)
     if span * CLIP_IMAGE * 3 > CLIP_LDS_MAX:
         raise VdxError(f"clip_preprocess: H={H} needs {span} input rows per output row (more than LDS holds)")
-    if out is None:
-        out = torch.empty((F * 49, 3072), dtype=torch.float16, device=dev)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < F * 49 or ocol < 3072:
-        raise VdxError(f"clip_preprocess: out {tuple(out.shape)} smaller than [{F * 49}][3072]")
+    out, ldo = _out(out, F * 49, 3072, frames, "clip_preprocess")
     u8 = torch.empty((F, CLIP_IMAGE, CLIP_IMAGE, 3), dtype=torch.uint8, device=dev) if return_u8 else None
     a = _lib.ClipPreprocessArgs()
     a.frames, a.out, a.out_u8 = frames.data_ptr(), _p(out, "out"), (u8.data_ptr() if u8 is not None else None)
     a.x_bounds, a.x_coeffs, a.y_bounds, a.y_coeffs = xb.data_ptr(), xk.data_ptr(), yb.data_ptr(), yk.data_ptr()
     a.frame_pitch, a.row_pitch, a.F, a.H, a.W = frames.stride(0), frames.stride(1), F, H, W
     a.kx, a.ky, a.band, a.span, a.ldo = xk.shape[1], yk.shape[1], band, span, ldo
-    _lib.check(lib.vdx_clip_preprocess_u8(C.byref(a), _stream()), "vdx_clip_preprocess_u8")
+    _launch("vdx_clip_preprocess_u8", C.byref(a))
     return (out, u8) if return_u8 else out
 
 
 def clip_vision_embed(patch, class_emb, pos_emb, gamma, beta, *, F, seq_pad, eps=1e-5, out=None):
     """CLIPVisionEmbeddings + pre_layrnorm: patch-GEMM rows [F*P][D] -> rows [F*seq_pad][D] (class token, P patches,
     zero rows up to seq_pad), P = pos_emb rows - 1."""
-    lib = _lib.load()
     r, D, ldp = _rows(patch, "patch")
     P = pos_emb.shape[0] - 1
     if r < F * P or pos_emb.shape[1] != D or class_emb.numel() != D or gamma.numel() != D or beta.numel() != D:
         raise VdxError(f"clip_vision_embed: patch [{r}][{D}], pos {tuple(pos_emb.shape)}: shapes do not match F={F}")
     if seq_pad <= P or not pos_emb.is_contiguous():
         raise VdxError(f"clip_vision_embed: seq_pad={seq_pad} must exceed {P} patches; pos_emb contiguous")
-    if out is None:
-        out = torch.empty((F * seq_pad, D), dtype=torch.float16, device=patch.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < F * seq_pad or ocol < D:
-        raise VdxError("clip_vision_embed: out too small")
-    _lib.check(lib.vdx_clip_vision_embed_f16(_p(patch, "patch"), ldp, _p(class_emb, "class_emb"), _p(pos_emb, "pos_emb"),
-                                             _p(gamma, "gamma"), _p(beta, "beta"), float(eps), F, P, seq_pad, D,
-                                             _p(out, "out"), ldo, _stream()), "vdx_clip_vision_embed_f16")
+    out, ldo = _out(out, F * seq_pad, D, patch, "clip_vision_embed")
+    _launch("vdx_clip_vision_embed_f16", _p(patch, "patch"), ldp, _p(class_emb, "class_emb"), _p(pos_emb, "pos_emb"),
+            _p(gamma, "gamma"), _p(beta, "beta"), float(eps), F, P, seq_pad, D, _p(out, "out"), ldo)
     return out
 
 
 def clip_cosine_score(img, txt):
     """F.normalize(img[f]) . F.normalize(txt) for F image embeddings fp16 [F][D] and one text embedding fp16 [D]
     -> (mean fp32 [1], per_frame fp32 [F]) on the device, in a fixed reduction order."""
-    lib = _lib.load()
     F, D, ldi = _rows(img, "img")
     if txt.numel() != D or not txt.is_contiguous():
         raise VdxError(f"clip_cosine_score: text embedding has {txt.numel()} values, images {D}")
@@ -470,20 +467,16 @@ def clip_cosine_score(img, txt):
         raise VdxError("clip_cosine_score: no frames")
     per = torch.empty(F, dtype=torch.float32, device=img.device)
     mean = torch.empty(1, dtype=torch.float32, device=img.device)
-    _lib.check(lib.vdx_clip_cosine_score_f16(_p(img, "img"), ldi, _p(txt, "txt"), F, D, _p(per, "per_frame", torch.float32),
-                                             _p(mean, "mean", torch.float32), _stream()), "vdx_clip_cosine_score_f16")
+    _launch("vdx_clip_cosine_score_f16", _p(img, "img"), ldi, _p(txt, "txt"), F, D, _p(per, "per_frame", torch.float32),
+            _p(mean, "mean", torch.float32))
     return mean, per
 
 
 # --------------------------------------------------------------------------------------------
-_gn_ws: dict = {}
-
-
 def groupnorm(x, gamma, beta, *, groups, n_samples, rows_per_sample, eps, silu_act, x2=None, out=None, partition_samples=0):
     """GroupNorm (+SiLU) over rows [n_samples*rows_per_sample][C]; x2 = second concat source.
     partition_samples: reduce the statistics with the slab partition of a batch of that many samples (bit-stable
     results for a sample whatever batch it is normalised in; include/vdx.h)."""
-    lib = _lib.load()
     r, c1, ldx = _rows(x, "x")
     c2, ldx2 = 0, 0
     M = n_samples * rows_per_sample
@@ -496,21 +489,12 @@ def groupnorm(x, gamma, beta, *, groups, n_samples, rows_per_sample, eps, silu_a
     Cc = c1 + c2
     if gamma.numel() != Cc or beta.numel() != Cc:
         raise VdxError(f"groupnorm: gamma/beta size {gamma.numel()} != C={Cc}")
-    if out is None:
-        out = torch.empty((M, Cc), dtype=torch.float16, device=x.device)
-    orow, ocol, ldy = _rows(out, "out")
-    if orow < M or ocol < Cc:
-        raise VdxError("groupnorm: out too small")
-    need = lib.vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
-    key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-        _gn_ws[key] = ws
-    _lib.check(lib.vdx_groupnorm_part_f16(_p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"),
-                                          _p(beta, "beta"), float(eps), groups, n_samples, rows_per_sample,
-                                          int(bool(silu_act)), _p(out, "out"), ldy, ws.data_ptr(), partition_samples,
-                                          _stream()), "vdx_groupnorm_f16")
+    out, ldy = _out(out, M, Cc, x, "groupnorm")
+    need = _lib.load().vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
+    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
+    _launch("vdx_groupnorm_part_f16", _p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"), _p(beta, "beta"),
+            float(eps), groups, n_samples, rows_per_sample, int(bool(silu_act)), _p(out, "out"), ldy, ws.data_ptr(),
+            partition_samples)
     return out
 
 
@@ -529,7 +513,6 @@ def conv3x3_gn(x, gamma, beta, w, *, x2=None, bias=None, bias2=None, rows_per_bi
     normalised tensor: the statistics pass (`vdx_groupnorm_stats_f16`, one sample per image) leaves a scale / shift pair per
     (image, channel); K1 (`vdx_conv3x3_gn_f16`, csrc/conv_fused.hip) applies them, and the SiLU, to its staged image patch
     in LDS.  x (and x2: the skip tensor of the up blocks): raw rows [n_img*h*wd][c]; w: packed weights [N][9*(c1+c2)]."""
-    lib = _lib.load()
     r, c1, ldx = _rows(x, "x")
     S = h * wd
     M = n_img * S
@@ -546,42 +529,18 @@ def conv3x3_gn(x, gamma, beta, w, *, x2=None, bias=None, bias2=None, rows_per_bi
         raise VdxError(f"conv3x3_gn: c1={c1}, c2={c2}, N={N} not supported")
     if bias is not None and bias.numel() != N:
         raise VdxError(f"conv3x3_gn: bias has {bias.numel()} elements, N={N}")
-    ldb2 = 0
-    if bias2 is not None:
-        b2r, b2c, ldb2 = _rows(bias2, "bias2")
-        if rows_per_bias2 <= 0 or b2r * rows_per_bias2 < M or b2c < N:
-            raise VdxError("conv3x3_gn: bias2 does not cover M rows / N columns")
-    ldr = 0
-    if residual is not None:
-        rr, rc, ldr = _rows(residual, "residual")
-        if rr < M or rc < N:
-            raise VdxError(f"conv3x3_gn: residual {tuple(residual.shape)} smaller than [{M}][{N}]")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < N:
-        raise VdxError("conv3x3_gn: out too small")
-    need = lib.vdx_groupnorm_workspace_part(n_img, S, Cc, groups, partition_samples)
-    key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-        _gn_ws[key] = ws
+    ldb2 = _covers(bias2, M, N, "conv3x3_gn", "bias2", rows_per_bias2)
+    ldr = _covers(residual, M, N, "conv3x3_gn", "residual")
+    out, ldo = _out(out, M, N, x, "conv3x3_gn")
+    need = _lib.load().vdx_groupnorm_workspace_part(n_img, S, Cc, groups, partition_samples)
+    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
     off = C.c_size_t(0)
-    _lib.check(lib.vdx_groupnorm_stats_f16(_p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"), _p(beta, "beta"), float(eps),
-                                           groups, n_img, S, ws.data_ptr(), partition_samples, C.byref(off), _stream()),
-               "vdx_groupnorm_stats_f16")
-    name = "conv3x3_gn_kernel"
-    timed = PROFILE is not None and _profiled(name)       # bench.py --profile-all: HIP events around this launch
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.vdx_conv3x3_gn_f16(_p(x, "x"), ldx, _p(x2, "x2"), ldx2, c1, c2, ws.data_ptr() + off.value, _p(w, "w"), _p(bias, "bias"),
-                                      _p(bias2, "bias2"), rows_per_bias2, ldb2, _p(residual, "residual"), ldr, _p(out, "out"), ldo,
-                                      n_img, h, wd, N, _stream()), "vdx_conv3x3_gn_f16")
-    if timed:
-        ev1.record()
-        PROFILE.append((name, 2.0 * M * N * K, ev0, ev1, (M, N, K)))
+    _launch("vdx_groupnorm_stats_f16", _p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"), _p(beta, "beta"),
+            float(eps), groups, n_img, S, ws.data_ptr(), partition_samples, C.byref(off))
+    with _timed("conv3x3_gn_kernel", 2.0 * M * N * K, (M, N, K)):
+        _launch("vdx_conv3x3_gn_f16", _p(x, "x"), ldx, _p(x2, "x2"), ldx2, c1, c2, ws.data_ptr() + off.value, _p(w, "w"),
+                _p(bias, "bias"), _p(bias2, "bias2"), rows_per_bias2, ldb2, _p(residual, "residual"), ldr, _p(out, "out"), ldo,
+                n_img, h, wd, N)
     return out
 
 
@@ -600,7 +559,6 @@ def tconv_gn(x, gamma, beta, w, *, bias=None, residual=None, groups, B, F, S, ep
     the statistics pass (`vdx_groupnorm_stats_f16`, n_samples = B, rows_per_sample = F*S) leaves a scale / shift pair per
     (sample, channel); K3 (`vdx_tconv_gn_f16`) applies them, and the SiLU, to its staged image in LDS.  x: raw rows
     [B*F*S][C]; w: packed temporal weights [N][3*C] (packing.pack_tconv)."""
-    lib = _lib.load()
     r, Cc, ldx = _rows(x, "x")
     M = B * F * S
     N, K = w.shape
@@ -610,74 +568,46 @@ def tconv_gn(x, gamma, beta, w, *, bias=None, residual=None, groups, B, F, S, ep
         raise VdxError(f"tconv_gn: C={Cc}, N={N}, F={F} not supported")
     if bias is not None and bias.numel() != N:
         raise VdxError(f"tconv_gn: bias has {bias.numel()} elements, N={N}")
-    ldr = 0
-    if residual is not None:
-        rr, rc, ldr = _rows(residual, "residual")
-        if rr < M or rc < N:
-            raise VdxError(f"tconv_gn: residual {tuple(residual.shape)} smaller than [{M}][{N}]")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < N:
-        raise VdxError("tconv_gn: out too small")
-    need = lib.vdx_groupnorm_workspace_part(B, F * S, Cc, groups, partition_samples)
-    key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-        _gn_ws[key] = ws
+    ldr = _covers(residual, M, N, "tconv_gn", "residual")
+    out, ldo = _out(out, M, N, x, "tconv_gn")
+    need = _lib.load().vdx_groupnorm_workspace_part(B, F * S, Cc, groups, partition_samples)
+    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
     off = C.c_size_t(0)
-    _lib.check(lib.vdx_groupnorm_stats_f16(_p(x, "x"), Cc, ldx, None, 0, 0, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups, B,
-                                           F * S, ws.data_ptr(), partition_samples, C.byref(off), _stream()), "vdx_groupnorm_stats_f16")
-    name = f"tconv_gn_kernel<{16 if F % 16 == 0 else 12 if F % 12 == 0 else 8}>"
-    timed = PROFILE is not None and _profiled(name)       # bench.py --profile-all: HIP events around this launch
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.vdx_tconv_gn_f16(_p(x, "x"), ldx, ws.data_ptr() + off.value, _p(w, "w"), _p(bias, "bias"), _p(residual, "residual"),
-                                    ldr, _p(out, "out"), ldo, B, F, S, Cc, N, _stream()), "vdx_tconv_gn_f16")
-    if timed:
-        ev1.record()
-        PROFILE.append((name, 2.0 * M * N * K, ev0, ev1, (M, N, K)))
+    _launch("vdx_groupnorm_stats_f16", _p(x, "x"), Cc, ldx, None, 0, 0, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups, B,
+            F * S, ws.data_ptr(), partition_samples, C.byref(off))
+    with _timed(f"tconv_gn_kernel<{16 if F % 16 == 0 else 12 if F % 12 == 0 else 8}>", 2.0 * M * N * K, (M, N, K)):
+        _launch("vdx_tconv_gn_f16", _p(x, "x"), ldx, ws.data_ptr() + off.value, _p(w, "w"), _p(bias, "bias"),
+                _p(residual, "residual"), ldr, _p(out, "out"), ldo, B, F, S, Cc, N)
     return out
 
 
 def layernorm(x, gamma, beta, *, M, eps=1e-5, out=None):
-    lib = _lib.load()
     r, Cc, ldx = _rows(x, "x")
     if r < M:
         raise VdxError("layernorm: x too small")
     if gamma.numel() != Cc or beta.numel() != Cc:
         raise VdxError("layernorm: gamma/beta size")
-    if out is None:
-        out = torch.empty((M, Cc), dtype=torch.float16, device=x.device)
-    orow, ocol, ldy = _rows(out, "out")
-    if orow < M or ocol < Cc:
-        raise VdxError("layernorm: out too small")
-    _lib.check(lib.vdx_layernorm_f16(_p(x, "x"), ldx, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), M, Cc,
-                                     _p(out, "out"), ldy, _stream()), "vdx_layernorm_f16")
+    out, ldy = _out(out, M, Cc, x, "layernorm")
+    _launch("vdx_layernorm_f16", _p(x, "x"), ldx, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), M, Cc, _p(out, "out"), ldy)
     return out
 
 
 def softmax_rows(x, *, rows, cols, scale):
     """In-place softmax(scale * x[r, :cols]) per row (fp32 inside): AutoencoderKL mid-block attention."""
-    lib = _lib.load()
     r, c, ld = _rows(x, "x")
     if r < rows or c < cols:
         raise VdxError("softmax_rows: x too small")
-    _lib.check(lib.vdx_softmax_rows_f16(_p(x, "x"), ld, rows, cols, float(scale), _stream()), "vdx_softmax_rows_f16")
+    _launch("vdx_softmax_rows_f16", _p(x, "x"), ld, rows, cols, float(scale))
     return x
 
 
 def rows_to_u8_frames(rows, n, H, W):
     """Decoder output rows [n*H*W][ld] (RGB first) -> uint8 (n,H,W,3): fsdp_chunked_coherent.py:224-225."""
-    lib = _lib.load()
     r, c, ld = _rows(rows, "rows")
     if r < n * H * W or c < 3:
         raise VdxError("rows_to_u8_frames: rows too small")
     out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=rows.device)
-    _lib.check(lib.vdx_rows_to_u8_frames(_p(rows, "rows"), ld, n * H * W, out.data_ptr(), _stream()),
-               "vdx_rows_to_u8_frames")
+    _launch("vdx_rows_to_u8_frames", _p(rows, "rows"), ld, n * H * W, out.data_ptr())
     return out
 
 
@@ -685,7 +615,6 @@ def rows_to_u8_frames(rows, n, H, W):
 def flash_attn(q, k, vt, *, n_seq, sq, skv, skv_pad, heads, seq_per_kv, scale, out=None, causal=False, v_rows=False):
     """q rows [n_seq*sq][>=heads*64]; k rows [n_kv*skv_pad][>=heads*64]; vt [heads*64][>= n_kv*skv_pad] — or, with
     `v_rows`, V as rows like k (the third column block of a q|k|v projection: `vdx_flash_attn_rows_f16`)."""
-    lib = _lib.load()
     qr, qc, ldq = _rows(q, "q")
     kr, kc, ldk = _rows(k, "k")
     vr, vc, ldvt = _rows(vt, "v" if v_rows else "vt")
@@ -699,44 +628,23 @@ def flash_attn(q, k, vt, *, n_seq, sq, skv, skv_pad, heads, seq_per_kv, scale, o
         raise VdxError("flash_attn: v too small")
     if not v_rows and (vr < inner or vc < n_kv * skv_pad):
         raise VdxError("flash_attn: vt too small")
-    if out is None:
-        out = torch.empty((n_seq * sq, inner), dtype=torch.float16, device=q.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < n_seq * sq or ocol < inner:
-        raise VdxError("flash_attn: out too small")
-    rec = False
-    if PROFILE is not None:        # bench.py instrumentation (as in gemm): HIP events on the launch stream
-        two = sq >= 512 and skv >= 256                      # flash.hip: 64 queries per wave
-        name = f"flash_attn_kernel<{2 if two else 1}, {'true' if causal else 'false'}, {'true' if v_rows else 'false'}>"
-        rec = _profiled(name)
-    if rec:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    fn = lib.vdx_flash_attn_rows_f16 if v_rows else lib.vdx_flash_attn_f16
-    _lib.check(fn(_p(q, "q"), ldq, _p(k, "k"), ldk, _p(vt, "vt"), ldvt, _p(out, "out"), ldo,
-                  n_seq, sq, skv, skv_pad, heads, seq_per_kv, float(scale), int(bool(causal)), _stream()),
-               "vdx_flash_attn_rows_f16" if v_rows else "vdx_flash_attn_f16")
-    if rec:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        PROFILE.append((name, 4.0 * n_seq * heads * sq * skv * 64, ev0, ev1, (n_seq * sq, skv, heads * 64)))
+    out, ldo = _out(out, n_seq * sq, inner, q, "flash_attn")
+    two = sq >= 512 and skv >= 256                      # flash.hip: 64 queries per wave
+    name = f"flash_attn_kernel<{2 if two else 1}, {'true' if causal else 'false'}, {'true' if v_rows else 'false'}>"
+    with _timed(name, 4.0 * n_seq * heads * sq * skv * 64, (n_seq * sq, skv, heads * 64)):
+        _launch("vdx_flash_attn_rows_f16" if v_rows else "vdx_flash_attn_f16", _p(q, "q"), ldq, _p(k, "k"), ldk, _p(vt, "vt"),
+                ldvt, _p(out, "out"), ldo, n_seq, sq, skv, skv_pad, heads, seq_per_kv, float(scale), int(bool(causal)))
     return out
 
 
 def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
-    lib = _lib.load()
     r, c, ld = _rows(qkv, "qkv")
     inner = heads * 64
     M = B * F * HW
     if r < M or c < 3 * inner:
         raise VdxError("temporal_attn: qkv too small")
-    if out is None:
-        out = torch.empty((M, inner), dtype=torch.float16, device=qkv.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < inner:
-        raise VdxError("temporal_attn: out too small")
-    _lib.check(lib.vdx_temporal_attn_f16(_p(qkv, "qkv"), ld, _p(out, "out"), ldo, B, F, HW, heads, float(scale),
-                                         _stream()), "vdx_temporal_attn_f16")
+    out, ldo = _out(out, M, inner, qkv, "temporal_attn")
+    _launch("vdx_temporal_attn_f16", _p(qkv, "qkv"), ld, _p(out, "out"), ldo, B, F, HW, heads, float(scale))
     return out
 
 
@@ -747,25 +655,17 @@ def temporal_attn_block2_supported(inner: int, F: int) -> bool:
 def temporal_attn_block2(t, packed, *, B, F, HW, eps=1e-5, out=None):
     """K7, second design (csrc/tattn2.hip): t + to_out(attention_over_frames(LayerNorm(t))) in one kernel; LayerNorm's
     affine, the softmax scale and the biases are inside `packed` (packing.pack_k7b)."""
-    lib = _lib.load()
     r, inner, ldt = _rows(t, "t")
     M = B * F * HW
     if r < M:
         raise VdxError(f"temporal_attn_block2: t has {r} rows, need {M}")
-    if not lib.vdx_temporal_attn_block2_supported(inner, F):
+    if not temporal_attn_block2_supported(inner, F):
         raise VdxError(f"temporal_attn_block2: inner={inner}, F={F} not supported by the fused kernel")
-    if packed.dtype != torch.float16 or packed.numel() * 2 != lib.vdx_temporal_attn_block2_pack_bytes(inner) \
-            or not packed.is_contiguous():
-        raise VdxError("temporal_attn_block2: packed blob does not match the kernel's layout (packing.pack_k7b)")
-    if out is None:
-        out = torch.empty((M, inner), dtype=torch.float16, device=t.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < inner:
-        raise VdxError("temporal_attn_block2: out too small")
+    _packed(packed, _lib.load().vdx_temporal_attn_block2_pack_bytes(inner), "temporal_attn_block2: packed blob", "packing.pack_k7b")
+    out, ldo = _out(out, M, inner, t, "temporal_attn_block2")
     if out.data_ptr() == t.data_ptr():
         raise VdxError("temporal_attn_block2: out may not alias t")
-    _lib.check(lib.vdx_temporal_attn_block2_f16(_p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(out, "out"), ldo,
-                                                B, F, HW, inner, _stream()), "vdx_temporal_attn_block2_f16")
+    _launch("vdx_temporal_attn_block2_f16", _p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(out, "out"), ldo, B, F, HW, inner)
     return out
 
 
@@ -778,44 +678,30 @@ def ff_block(t, packed, *, M, eps=1e-5, out=None, proj=None):
     LayerNorm's affine and the biases are inside `packed` (packing.pack_k8).
     `proj` = (tail blob of packing.pack_k8_proj, x, xrows): the transformer's proj_out and its residual run behind the
     feed-forward in the same kernel — out[r] = x[r % xrows] + W_p . (t[r] + ff(LayerNorm(t[r]))) + b_p, xrows = M or M / 2."""
-    lib = _lib.load()
     r, inner, ldt = _rows(t, "t")
     if r < M:
         raise VdxError(f"ff_block: t has {r} rows, need {M}")
-    if not lib.vdx_ff_block_supported(inner):
+    if not ff_block_supported(inner):
         raise VdxError(f"ff_block: inner={inner} not supported by the fused kernel")
-    if packed.dtype != torch.float16 or packed.numel() * 2 != lib.vdx_ff_block_pack_bytes(inner) or not packed.is_contiguous():
-        raise VdxError("ff_block: packed blob does not match the kernel's layout (packing.pack_k8)")
-    if out is None:
-        out = torch.empty((M, inner), dtype=torch.float16, device=t.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < inner:
-        raise VdxError("ff_block: out too small")
+    _packed(packed, _lib.load().vdx_ff_block_pack_bytes(inner), "ff_block: packed blob", "packing.pack_k8")
+    out, ldo = _out(out, M, inner, t, "ff_block")
     if out.data_ptr() == t.data_ptr():
         raise VdxError("ff_block: out may not alias t")
-    name = f"ff_fused_kernel<{inner}, {'true' if proj is not None else 'false'}>"
-    rec = PROFILE is not None and _profiled(name)
-    if rec:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
     if proj is None:
-        _lib.check(lib.vdx_ff_block_f16(_p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(out, "out"), ldo, M, inner, _stream()),
-                   "vdx_ff_block_f16")
+        args = ("vdx_ff_block_f16", _p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(out, "out"), ldo, M, inner)
     else:
         blob, x, xrows = proj
         xr, xc, ldx = _rows(x, "x")
         if xc < inner or xr < xrows or xrows not in (M, M // 2) or (xrows != M and 2 * xrows != M):
             raise VdxError(f"ff_block: x {tuple(x.shape)} / xrows {xrows} do not pair with M = {M} rows")
-        if blob.dtype != torch.float16 or blob.numel() * 2 != lib.vdx_ff_block_proj_pack_bytes(inner) or not blob.is_contiguous():
-            raise VdxError("ff_block: proj blob does not match the kernel's layout (packing.pack_k8_proj)")
+        _packed(blob, _lib.load().vdx_ff_block_proj_pack_bytes(inner), "ff_block: proj blob", "packing.pack_k8_proj")
         if out.data_ptr() == x.data_ptr():
             raise VdxError("ff_block: out may not alias x")
-        _lib.check(lib.vdx_ff_block_proj_f16(_p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(x, "x"), ldx, int(xrows), _p(blob, "proj"),
-                                             _p(out, "out"), ldo, M, inner, _stream()), "vdx_ff_block_proj_f16")
-    if rec:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        PROFILE.append((name, 2.0 * M * inner * (12 + (1 if proj is not None else 0)) * inner, ev0, ev1, (M, inner, 12 * inner)))
+        args = ("vdx_ff_block_proj_f16", _p(t, "t"), ldt, _p(packed, "packed"), float(eps), _p(x, "x"), ldx, int(xrows),
+                _p(blob, "proj"), _p(out, "out"), ldo, M, inner)
+    with _timed(f"ff_fused_kernel<{inner}, {'true' if proj is not None else 'false'}>",
+                2.0 * M * inner * (12 + (1 if proj is not None else 0)) * inner, (M, inner, 12 * inner)):
+        _launch(*args)
     return out
 
 
@@ -827,35 +713,21 @@ def cross_attn_block(t, packed, kv_packed, *, kv_len, n_items, rows_per_item, ep
     """K5 (csrc/xattn.hip): t + to_out(softmax(q K^T) V), q = LayerNorm(t).W_q^T — the cross-attention sub-block of a spatial
     transformer — in one kernel.  `packed`: packing.pack_k5 (LayerNorm's affine, the scale, the biases inside);
     `kv_packed`: packing.pack_k5_kv of the text keys / values, [n_items][heads][3 units]; rows [n_items*rows_per_item][inner]."""
-    lib = _lib.load()
     r, inner, ldt = _rows(t, "t")
     M = n_items * rows_per_item
     if r < M:
         raise VdxError(f"cross_attn_block: t has {r} rows, need {M}")
-    if not lib.vdx_cross_attn_block_supported(inner, kv_len):
+    if not cross_attn_block_supported(inner, kv_len):
         raise VdxError(f"cross_attn_block: inner={inner}, kv_len={kv_len} not supported by the fused kernel")
-    if packed.dtype != torch.float16 or packed.numel() * 2 != lib.vdx_cross_attn_block_pack_bytes(inner) or not packed.is_contiguous():
-        raise VdxError("cross_attn_block: packed blob does not match the kernel's layout (packing.pack_k5)")
-    if kv_packed.dtype != torch.float16 or kv_packed.numel() * 2 != n_items * lib.vdx_cross_attn_block_kv_bytes(inner) \
-            or not kv_packed.is_contiguous():
-        raise VdxError("cross_attn_block: key / value blob does not match the kernel's layout (packing.pack_k5_kv)")
-    if out is None:
-        out = torch.empty((M, inner), dtype=torch.float16, device=t.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < inner:
-        raise VdxError("cross_attn_block: out too small")
+    lib = _lib.load()
+    _packed(packed, lib.vdx_cross_attn_block_pack_bytes(inner), "cross_attn_block: packed blob", "packing.pack_k5")
+    _packed(kv_packed, n_items * lib.vdx_cross_attn_block_kv_bytes(inner), "cross_attn_block: key / value blob", "packing.pack_k5_kv")
+    out, ldo = _out(out, M, inner, t, "cross_attn_block")
     if out.data_ptr() == t.data_ptr():
         raise VdxError("cross_attn_block: out may not alias t")
-    rec = PROFILE is not None and _profiled(f"xattn_kernel<{inner}>")
-    if rec:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.vdx_cross_attn_block_f16(_p(t, "t"), ldt, _p(packed, "packed"), _p(kv_packed, "kv_packed"), int(kv_len), float(eps),
-                                            _p(out, "out"), ldo, n_items, rows_per_item, inner, _stream()), "vdx_cross_attn_block_f16")
-    if rec:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        PROFILE.append((f"xattn_kernel<{inner}>", 2.0 * M * (2 * inner * inner + 2 * kv_len * inner), ev0, ev1, (M, inner, 2 * inner + 2 * kv_len)))
+    with _timed(f"xattn_kernel<{inner}>", 2.0 * M * (2 * inner * inner + 2 * kv_len * inner), (M, inner, 2 * inner + 2 * kv_len)):
+        _launch("vdx_cross_attn_block_f16", _p(t, "t"), ldt, _p(packed, "packed"), _p(kv_packed, "kv_packed"), int(kv_len),
+                float(eps), _p(out, "out"), ldo, n_items, rows_per_item, inner)
     return out
 
 
@@ -865,31 +737,22 @@ def temporal_attn_block_supported(inner: int, F: int) -> bool:
 
 def temporal_attn_block(t, gamma, beta, wqkv_packed, wo_packed, bo, *, B, F, HW, scale, eps=1e-5, out=None):
     """K7: t + to_out(attention_over_frames(LayerNorm(t))) in one kernel (include/vdx.h)."""
-    lib = _lib.load()
     r, inner, ldt = _rows(t, "t")
     M = B * F * HW
     if r < M:
         raise VdxError(f"temporal_attn_block: t has {r} rows, need {M}")
-    if not lib.vdx_temporal_attn_block_supported(inner, F):
+    if not temporal_attn_block_supported(inner, F):
         raise VdxError(f"temporal_attn_block: inner={inner}, F={F} not supported by the fused kernel")
     if gamma.numel() != inner or beta.numel() != inner or bo.numel() != inner:
         raise VdxError("temporal_attn_block: gamma/beta/bias size")
-    if wqkv_packed.numel() * 2 != lib.vdx_temporal_attn_block_wqkv_bytes(inner) or \
-            wo_packed.numel() * 2 != lib.vdx_temporal_attn_block_wo_bytes(inner):
-        raise VdxError("temporal_attn_block: packed weight size does not match the kernel's stage layout")
-    if not (wqkv_packed.is_contiguous() and wo_packed.is_contiguous()):
-        raise VdxError("temporal_attn_block: packed weights must be contiguous")
-    if out is None:
-        out = torch.empty((M, inner), dtype=torch.float16, device=t.device)
-    orow, ocol, ldo = _rows(out, "out")
-    if orow < M or ocol < inner:
-        raise VdxError("temporal_attn_block: out too small")
+    lib = _lib.load()
+    _packed(wqkv_packed, lib.vdx_temporal_attn_block_wqkv_bytes(inner), "temporal_attn_block: wqkv blob", "packing.pack_k7_qkv")
+    _packed(wo_packed, lib.vdx_temporal_attn_block_wo_bytes(inner), "temporal_attn_block: wo blob", "packing.pack_k7_out")
+    out, ldo = _out(out, M, inner, t, "temporal_attn_block")
     if out.data_ptr() == t.data_ptr():
         raise VdxError("temporal_attn_block: out may not alias t")
-    _lib.check(lib.vdx_temporal_attn_block_f16(_p(t, "t"), ldt, _p(gamma, "gamma"), _p(beta, "beta"), float(eps),
-                                               _p(wqkv_packed, "wqkv"), _p(wo_packed, "wo"), _p(bo, "bo"),
-                                               _p(out, "out"), ldo, B, F, HW, inner, float(scale), _stream()),
-               "vdx_temporal_attn_block_f16")
+    _launch("vdx_temporal_attn_block_f16", _p(t, "t"), ldt, _p(gamma, "gamma"), _p(beta, "beta"), float(eps),
+            _p(wqkv_packed, "wqkv"), _p(wo_packed, "wo"), _p(bo, "bo"), _p(out, "out"), ldo, B, F, HW, inner, float(scale))
     return out
 
 
@@ -899,7 +762,6 @@ def cfg_input(lat, ctx, weight, out=None):
     The result is TAGGED as a known duplicate (`is_cfg_duplicate`): the UNet then computes its text-independent blocks once.
     The tag is tied to torch's version counter, which torch operations bump and this library's kernels do NOT: never hand the
     result to a vdx op as its `out=` (nothing in this package does)."""
-    lib = _lib.load()
     b, Cc, F, H, W = lat.shape
     if b != 1 or not lat.is_contiguous():
         raise VdxError("cfg_input: lat must be contiguous (1,C,F,H,W)")
@@ -907,8 +769,7 @@ def cfg_input(lat, ctx, weight, out=None):
         raise VdxError("cfg_input: ctx must be contiguous (1,C,1,H,W)")
     if out is None:
         out = torch.empty((2, Cc, F, H, W), dtype=torch.float16, device=lat.device)
-    _lib.check(lib.vdx_cfg_input_f16(_p(lat, "lat"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, F, H * W,
-                                     _stream()), "vdx_cfg_input_f16")
+    _launch("vdx_cfg_input_f16", _p(lat, "lat"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, F, H * W)
     out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
     return out
 
@@ -925,7 +786,6 @@ def is_cfg_duplicate(x) -> bool:
 
 def cfg_ddim_step(eps2, lat, guidance, coeffs, out=None):
     """fsdp_chunked_coherent.py:141-142.  coeffs = (sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev))."""
-    lib = _lib.load()
     if eps2.shape[0] != 2 or tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1:
         raise VdxError("cfg_ddim_step: eps2 must be (2,...) matching lat (1,...)")
     if not (eps2.is_contiguous() and lat.is_contiguous()):
@@ -933,43 +793,37 @@ def cfg_ddim_step(eps2, lat, guidance, coeffs, out=None):
     if out is None:
         out = torch.empty_like(lat)
     s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _lib.check(lib.vdx_cfg_ddim_step_f16(_p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), float(guidance),
-                                         s1, sa, sp, s1p, lat.numel(), _stream()), "vdx_cfg_ddim_step_f16")
+    _launch("vdx_cfg_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), float(guidance), s1, sa, sp, s1p,
+            lat.numel())
     return out
 
 
 def ddim_step(eps, lat, coeffs, out=None):
     """`scheduler.step(eps, t, lat).prev_sample` (fsdp_chunked_coherent.py:142) without the CFG combine."""
-    lib = _lib.load()
     if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
         raise VdxError("ddim_step: eps and lat must be contiguous and of equal shape")
     if out is None:
         out = torch.empty_like(lat)
     s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _lib.check(lib.vdx_ddim_step_f16(_p(eps, "eps"), _p(lat, "lat"), _p(out, "out"), s1, sa, sp, s1p,
-                                     lat.numel(), _stream()), "vdx_ddim_step_f16")
+    _launch("vdx_ddim_step_f16", _p(eps, "eps"), _p(lat, "lat"), _p(out, "out"), s1, sa, sp, s1p, lat.numel())
     return out
 
 
 def blend_accumulate(full, weight, chunk, w, s, e):
-    lib = _lib.load()
     _, Cc, T, H, W = full.shape
     if tuple(chunk.shape) != (1, Cc, e - s, H, W) or not (chunk.is_contiguous() and full.is_contiguous()):
         raise VdxError("blend_accumulate: chunk shape does not match range")
     if weight.numel() != T or w.numel() != e - s:
         raise VdxError("blend_accumulate: weight vectors")
-    _lib.check(lib.vdx_blend_accumulate_f16(_p(full, "full"), _p(weight, "weight", torch.float32),
-                                            _p(chunk, "chunk"), _p(w, "w", torch.float32), Cc, T, H * W, s, e,
-                                            _stream()), "vdx_blend_accumulate_f16")
+    _launch("vdx_blend_accumulate_f16", _p(full, "full"), _p(weight, "weight", torch.float32), _p(chunk, "chunk"),
+            _p(w, "w", torch.float32), Cc, T, H * W, s, e)
 
 
 def blend_finalize(full, weight):
-    lib = _lib.load()
     _, Cc, T, H, W = full.shape
     out = torch.empty(full.shape, dtype=torch.float32, device=full.device)
-    _lib.check(lib.vdx_blend_finalize_f32(_p(full, "full"), _p(weight, "weight", torch.float32),
-                                          _p(out, "out", torch.float32), Cc, T, H * W, _stream()),
-               "vdx_blend_finalize_f32")
+    _launch("vdx_blend_finalize_f32", _p(full, "full"), _p(weight, "weight", torch.float32), _p(out, "out", torch.float32),
+            Cc, T, H * W)
     return out
 
 
@@ -993,7 +847,6 @@ def probe_mfma(device, iters: int = 4000, repeats: int = 3) -> float:
     """Sustained TFLOP/s of a FIXED dense fp16 MFMA stream on this part, in this process (`vdx_probe_mfma_f16`): what the
     box gives the instruction every matrix kernel of the library is made of.  Median of `repeats` timed launches after one
     warm-up launch (~20 ms each at the default `iters`)."""
-    lib = _lib.load()
     n = 2 * torch.cuda.get_device_properties(device).multi_processor_count * 256
     scratch = torch.empty(n, dtype=torch.float32, device=device)
     flops = C.c_double(0.0)
@@ -1001,7 +854,7 @@ def probe_mfma(device, iters: int = 4000, repeats: int = 3) -> float:
     for r in range(repeats + 1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.check(lib.vdx_probe_mfma_f16(_p(scratch, "scratch", torch.float32), n, iters, C.byref(flops), _stream()), "vdx_probe_mfma_f16")
+        _launch("vdx_probe_mfma_f16", _p(scratch, "scratch", torch.float32), n, iters, C.byref(flops))
         e1.record()
         e1.synchronize()
         if r:
@@ -1046,7 +899,6 @@ def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     """uint8 RGB (F, Hi, Wi, 3) on the GPU -> (F, height, width, 3): `PIL.Image.resize((width, height))` bit for bit
     (default filter BICUBIC; 22-bit weights, horizontal pass then vertical, uint8 intermediate).  As in Pillow, a pass whose
     size does not change is skipped (both unchanged: a copy)."""
-    lib = _lib.load()
     F, Hi, Wi = _check_u8_frames(frames, "resize_u8")
     if height <= 0 or width <= 0:
         raise VdxError(f"resize_u8: target {height}x{width}")
@@ -1058,15 +910,13 @@ def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     if Wi != width:
         mid = out if Hi == height else torch.empty((F, Hi, width, 3), dtype=torch.uint8, device=dev)
         b, k = _resize_table(Wi, width, filter, dev)
-        _lib.check(lib.vdx_resample_h_u8(src.data_ptr(), src.stride(0), src.stride(1), F, Hi, Wi, b.data_ptr(), k.data_ptr(),
-                                         k.shape[1], width, mid.data_ptr(), mid.stride(0), mid.stride(1), _stream()),
-                   "vdx_resample_h_u8")
+        _launch("vdx_resample_h_u8", src.data_ptr(), src.stride(0), src.stride(1), F, Hi, Wi, b.data_ptr(), k.data_ptr(),
+                k.shape[1], width, mid.data_ptr(), mid.stride(0), mid.stride(1))
         src = mid
     if Hi != height:
         b, k = _resize_table(Hi, height, filter, dev)
-        _lib.check(lib.vdx_resample_v_u8(src.data_ptr(), src.stride(0), src.stride(1), F, Hi, width, b.data_ptr(), k.data_ptr(),
-                                         k.shape[1], height, out.data_ptr(), out.stride(0), out.stride(1), _stream()),
-                   "vdx_resample_v_u8")
+        _launch("vdx_resample_v_u8", src.data_ptr(), src.stride(0), src.stride(1), F, Hi, width, b.data_ptr(), k.data_ptr(),
+                k.shape[1], height, out.data_ptr(), out.stride(0), out.stride(1))
     return out
 
 
@@ -1088,19 +938,14 @@ def frames_to_conv_in(frames, out=None):
     """uint8 (F, H, W, 3) on the GPU -> fp16 rows [F*H*W][64]: the im2col operand of the encoder's conv_in (K = tap*3 + c,
     columns 27..63 zero) of the mapped frames (`u8_to_unit_lut`), zero outside the image — the same rows `conv_in` builds
     from the mapped (F, 3, 1, H, W) tensor."""
-    lib = _lib.load()
     F, H, W = _check_u8_frames(frames, "frames_to_conv_in")
     dev = frames.device
     lut = _U8_MAP.get(str(dev))
     if lut is None:
         lut = _U8_MAP[str(dev)] = u8_to_unit_lut().to(dev)
-    if out is None:
-        out = torch.empty((F * H * W, 64), dtype=torch.float16, device=dev)
-    r, c, ldo = _rows(out, "out")
-    if r < F * H * W or c < 64:
-        raise VdxError(f"frames_to_conv_in: out {tuple(out.shape)} smaller than [{F * H * W}][64]")
-    _lib.check(lib.vdx_frames_to_conv_in_u8(frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, lut.data_ptr(),
-                                            _p(out, "out"), ldo, _stream()), "vdx_frames_to_conv_in_u8")
+    out, ldo = _out(out, F * H * W, 64, frames, "frames_to_conv_in")
+    _launch("vdx_frames_to_conv_in_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, lut.data_ptr(),
+            _p(out, "out"), ldo)
     return out
 
 
@@ -1109,7 +954,6 @@ def vae_posterior(moments, n: int, hw: int, eps=None, scale: float = 1.0, out=No
     scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps), or scale * mean without `eps` (mode), fp16 after every op.
     Default output (n, 4, h*w); a contiguous `out` + `out_offset` (elements) + `out_strides` = (channel, image) element strides
     write elsewhere, e.g. frames f0.. of a (1, 4, T, h, w) latent: offset f0*hw, strides (T*hw, hw)."""
-    lib = _lib.load()
     r, c, ld = _rows(moments, "moments")
     if r < n * hw or c < 8:
         raise VdxError(f"vae_posterior: moments {tuple(moments.shape)} smaller than [{n * hw}][8]")
@@ -1124,20 +968,17 @@ def vae_posterior(moments, n: int, hw: int, eps=None, scale: float = 1.0, out=No
     cs, fs = out_strides
     if out_offset < 0 or out_offset + 3 * cs + (n - 1) * fs + hw > out.numel():
         raise VdxError("vae_posterior: out too small for its offset and strides")
-    _lib.check(lib.vdx_vae_posterior_f16(_p(moments, "moments"), ld, n, hw, eps.data_ptr() if eps is not None else None,
-                                         int(eps is None), float(scale), out.data_ptr() + 2 * out_offset, cs, fs, _stream()),
-               "vdx_vae_posterior_f16")
+    _launch("vdx_vae_posterior_f16", _p(moments, "moments"), ld, n, hw, eps.data_ptr() if eps is not None else None,
+            int(eps is None), float(scale), out.data_ptr() + 2 * out_offset, cs, fs)
     return out
 
 
 def add_noise(x0, noise, sqrt_ab: float, sqrt_1mab: float, out=None):
     """DDIMScheduler.add_noise with fp16 coefficients: fp16(fp16(sqrt_ab * x0) + fp16(sqrt_1mab * noise))."""
-    lib = _lib.load()
     if x0.shape != noise.shape or x0.dtype != torch.float16 or noise.dtype != torch.float16 \
             or not (x0.is_contiguous() and noise.is_contiguous()):
         raise VdxError("add_noise: x0 and noise must be contiguous fp16 tensors of one shape")
     if out is None:
         out = torch.empty_like(x0)
-    _lib.check(lib.vdx_add_noise_f16(_p(x0, "x0"), _p(noise, "noise"), _p(out, "out"), float(sqrt_ab), float(sqrt_1mab),
-                                     x0.numel(), _stream()), "vdx_add_noise_f16")
+    _launch("vdx_add_noise_f16", _p(x0, "x0"), _p(noise, "noise"), _p(out, "out"), float(sqrt_ab), float(sqrt_1mab), x0.numel())
     return out

@@ -42,7 +42,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, packing
+from . import ops, packing
 from ._lib import VdxError
 
 
@@ -356,9 +356,8 @@ class AutoencoderKL(nn.Module):
         n, _, H, Wd = x.shape
         self._check_encode_size(H, Wd)
         cols = torch.empty((n * H * Wd, 64), dtype=torch.float16, device=x.device)
-        lib = _lib.load()
         x5 = x.to(torch.float16).unsqueeze(2).contiguous()
-        _lib.check(lib.vdx_im2col_in_f16(x5.data_ptr(), cols.data_ptr(), n, 3, 1, H, Wd, 64, ops._stream()), "vdx_im2col_in_f16")
+        ops._launch("vdx_im2col_in_f16", x5.data_ptr(), cols.data_ptr(), n, 3, 1, H, Wd, 64)
         m, hh, ww = self._encode_rows(cols, n, H, Wd)
         dist_ = DiagonalGaussianDistribution(m, n, hh, ww)
         return SimpleNamespace(latent_dist=dist_) if return_dict else (dist_,)

@@ -45,6 +45,95 @@ def test_gemm_args_struct_matches_header_field_order():
     assert names == [f[0] for f in _lib.GemmArgs._fields_]
 
 
+def _header_declarations():
+    """include/vdx.h -> {name: (return type, [parameter declarations])} for every `ret vdx_name(params);`."""
+    src = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "vdx.h")).read(), flags=re.S)
+    src = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", src).splitlines() if not ln.lstrip().startswith("#"))
+    decls = {}
+    for chunk in re.split(r"[;{}]", src):
+        m = re.fullmatch(r"\s*(.+?)\b(vdx_[a-z0-9_]+)\s*\((.*)\)\s*", chunk, re.S)
+        if m:
+            params = [" ".join(p.split()) for p in m.group(3).split(",")]
+            decls[m.group(2)] = (" ".join(m.group(1).split()), [] if params == ["void"] else params)
+    return decls
+
+
+def _c_abi_class(decl: str) -> str:
+    """ABI class of a C type or parameter declaration: pointers of any pointee (the stream handle is one) or a scalar."""
+    if "*" in decl or re.match(r"(const\s+)?vdx_stream_t\b", decl):
+        return "pointer"
+    base = re.sub(r"\bconst\b", "", decl).split()[0]
+    return {"int": "int32", "int32_t": "int32", "size_t": "size_t", "float": "float", "double": "double", "void": "void"}.get(
+        base, f"unknown C type {decl!r}")
+
+
+def _ctypes_abi_class(t) -> str:
+    """The same classes for a ctypes type: device pointers bound as c_void_p and host out-parameters as POINTER(...) alike."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int32: "int32", ctypes.c_size_t: "size_t", ctypes.c_float: "float", ctypes.c_double: "double"}.get(
+        t, f"unknown ctypes type {t.__name__}")
+
+
+def _abi_mismatches(signatures, decls):
+    """Names whose ctypes row differs from the header declaration in return class, argument count or an argument's class."""
+    bad = []
+    for name, (ret, params) in sorted(decls.items()):
+        res, args = signatures[name]
+        if _c_abi_class(ret) != _ctypes_abi_class(res) or [_c_abi_class(p) for p in params] != [_ctypes_abi_class(a) for a in args]:
+            bad.append(name)
+    return bad
+
+
+def test_ctypes_rows_match_header_abi_classes():
+    """Every SIGNATURES row has its declaration's argument count, and each argument and the result its ABI class: a row that
+    lost or swapped an argument would hand the library corrupt arguments without any error."""
+    decls = _header_declarations()
+    assert set(decls) == set(_lib.SIGNATURES), set(decls) ^ set(_lib.SIGNATURES)
+    assert _abi_mismatches(_lib.SIGNATURES, decls) == []
+
+
+@pytest.mark.parametrize("doctor", ["drop an argument", "int -> size_t"])
+def test_abi_check_reports_a_doctored_row(doctor):
+    decls = _header_declarations()
+    sigs = dict(_lib.SIGNATURES)
+    name = "vdx_softmax_rows_f16"                 # (const void* x, int ld, int rows, int cols, float scale, stream)
+    res, args = sigs[name]
+    sigs[name] = (res, args[:-1] if doctor == "drop an argument" else [args[0], ctypes.c_size_t] + args[2:])
+    assert _abi_mismatches(sigs, decls) == [name]
+
+
+def test_struct_layouts_match_the_compiled_header(tmp_path):
+    """sizeof and every field's offsetof of the two argument structs, as a C compiler lays them out from include/vdx.h,
+    equal ctypes' layout of GemmArgs / ClipPreprocessArgs."""
+    import shutil
+    rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")
+    cc = shutil.which("cc") or shutil.which("gcc") or (rocm_clang if os.path.exists(rocm_clang) else None)
+    if cc is None:
+        pytest.skip("no C compiler here")
+    structs = {"vdx_gemm_args": _lib.GemmArgs, "vdx_clip_preprocess_args": _lib.ClipPreprocessArgs}
+    lines = []
+    for cname, py in structs.items():
+        lines.append(f'    printf("{cname} sizeof %zu\\n", sizeof({cname}));')
+        lines += [f'    printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));' for f, _ in py._fields_]
+    prog = tmp_path / "layout.c"
+    prog.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vdx.h"\nint main(void) {\n' + "\n".join(lines)
+                    + "\n    return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-std=c11", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True, timeout=120)
+    got = {}
+    for ln in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        s, f, v = ln.split()
+        got[(s, f)] = int(v)
+    want = {}
+    for cname, py in structs.items():
+        want[(cname, "sizeof")] = ctypes.sizeof(py)
+        want.update({(cname, f): getattr(py, f).offset for f, _ in py._fields_})
+    assert got == want
+
+
 @pytest.mark.parametrize("rule", ["coherent", "third"])
 def test_planner_matches_oracle_sweep(rule):
     n = 0

@@ -48,6 +48,7 @@ SIGNATURES = {
     "vdx_build_flags": (_i, []),
     "vdx_gemm_f16": (_i, [C.POINTER(GemmArgs), _vp]),
     "vdx_gemm_plan": (_i, [C.POINTER(GemmArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vdx_gemm_kernel_name": (_i, [C.POINTER(GemmArgs), C.c_char_p, _sz]),
     "vdx_gemm_plan_ksplit": (_i, [C.POINTER(GemmArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     "vdx_softmax_rows_f16": (_i, [_vp, _i, _i, _i, _f, _vp]),
     "vdx_rows_to_u8_frames": (_i, [_vp, _i, _sz, _vp, _vp]),

@@ -21,6 +21,7 @@
 // 8 consecutive output channels of one row -> 16-byte epilogue stores.
 #include "gemm_common.h"
 #include <stdlib.h>
+#include <string.h>
 
 #ifdef VDX_STAMPS   // diagnostic build only (make stamps): per-block phase clocks, never in the product library
 #define STAMP_MAX 32768
@@ -377,7 +378,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmP p) {
 
 // ---- host side ------------------------------------------------------------------------------
 template <int BM, int BN, int WM, int WN, int MODE, bool GEGLU, bool SPLIT = false, int VAR = 0>
-static int launch(const GemmP& p, hipStream_t st) {
+static int launch(const GemmP& p, const GemmSink& to) {
+    if (to.name)
+        return snprintf(to.name, GEMM_NAME_MAX, "gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", BM, BN, WM, WN, MODE, tf(GEGLU), tf(SPLIT), VAR), 0;
     constexpr int lds = 2 * (BM + BN) * 128 + (GEGLU ? GELU_TAB_BYTES : 0);
     auto kern = gemm_kernel<BM, BN, WM, WN, MODE, GEGLU, SPLIT, VAR>;
     // one-time LDS opt-in; a function-local static is initialised exactly once even under concurrent callers
@@ -387,7 +390,7 @@ static int launch(const GemmP& p, hipStream_t st) {
     q.ntn = (p.N + BN - 1) / BN;
     const int ntm = (p.M - p.m_begin + BM - 1) / BM;
     q.ntm = ntm;
-    hipLaunchKernelGGL(kern, dim3(ntm * q.ntn), dim3(WM * WN * 64), lds, st, q);
+    hipLaunchKernelGGL(kern, dim3(ntm * q.ntn), dim3(WM * WN * 64), lds, to.st, q);
     return vdx_launch_status("vdx_gemm_f16");
 }
 
@@ -428,20 +431,21 @@ __global__ __launch_bounds__(64) void gemm_reduce_kernel(const GemmP p) {
 static constexpr size_t KSPLIT_SLAB_BYTES = 256 * 320 * 4;     // fp32 accumulators of one 256x320 tile
 
 template <int MODE>
-static int launch_ksplit(const GemmP& p, int ksplit, float* ws, hipStream_t st) {
-    constexpr int BM = 256, BN = 320, WM = 4, WN = 2;
+static int launch_ksplit(const GemmP& p, const GemmSink& to) {     // (p.ksplit slices per tile, slabs in p.partial: gemm_prepare)
+    constexpr int BM = 256, BN = 320, WM = 4, WN = 2, VAR = 1;
+    constexpr bool GEGLU = false, SPLIT = MODE != 0;
+    if (to.name)
+        return snprintf(to.name, GEMM_NAME_MAX, "gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d> split-K + reduce", BM, BN, WM, WN, MODE, tf(GEGLU), tf(SPLIT), VAR), 0;
     constexpr int lds = 2 * (BM + BN) * 128;
-    auto kern = gemm_kernel<BM, BN, WM, WN, MODE, false, MODE != 0, 1>;
+    auto kern = gemm_kernel<BM, BN, WM, WN, MODE, GEGLU, SPLIT, VAR>;
     static const hipError_t attr_rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (attr_rc != hipSuccess) return vdx_fail("gemm: cannot reserve %d bytes of LDS", lds);
     GemmP q = p;
     q.ntn = (p.N + BN - 1) / BN;
     q.ntm = (p.M - p.m_begin + BM - 1) / BM;
-    q.ksplit = ksplit;
-    q.partial = ws;
     const int tiles = q.ntm * q.ntn;
-    hipLaunchKernelGGL(kern, dim3(tiles * ksplit), dim3(WM * WN * 64), lds, st, q);
-    hipLaunchKernelGGL((gemm_reduce_kernel<BM, BN, WM, WN>), dim3(tiles * WM * WN), dim3(64), 0, st, q);
+    hipLaunchKernelGGL(kern, dim3(tiles * q.ksplit), dim3(WM * WN * 64), lds, to.st, q);
+    hipLaunchKernelGGL((gemm_reduce_kernel<BM, BN, WM, WN>), dim3(tiles * WM * WN), dim3(64), 0, to.st, q);
     return vdx_launch_status("vdx_gemm_f16 (split-K tail)");
 }
 
@@ -449,8 +453,8 @@ static int launch_ksplit(const GemmP& p, int ksplit, float* ws, hipStream_t st) 
 // variant: 1 = 128x128 two-stage (eight waves; 9 = four waves), 2 = 256x320 two-stage (K-step 64), 3 = 256x320 four-stage ring
 // (K-step 32), 4 = 128x320 two-stage ring with two blocks per CU, 8 = 128x320 four-stage ring with eight
 // 32x160 waves, 5 = 256x64, 6 = variant 2 without the
-// split staging roles (every wave issues its share of both operands at the top of the K tile); 7 (handled in
-// vdx_gemm_f16) = the weights-stationary short-K kernels of gemm_ws.hip.
+// split staging roles (every wave issues its share of both operands at the top of the K tile); 7 = the
+// weights-stationary short-K kernels of gemm_ws.hip.
 //
 // Channel widths of this UNet are multiples of 320: the 320-wide tiles (64x160 per wave) halve LDS/L2 bytes per MFMA
 // against 128x128.  Widths that are not multiples of 320 (transformer_in: 512/1536/4096) still take the 320-wide tile
@@ -465,12 +469,15 @@ struct TileChoice {
     int v;            // variant
     long long cost;   // in tenths of a 256x320 tile time
 };
+static int nt320_of(int N) { return (N + 319) / 320; }
+// N fills 320-wide tiles: the masked tail wastes < 25 % of the last column of tiles
+static bool fills320(int N) { return nt320_of(N) * 320 * 4 <= N * 5; }
+static bool fits320(long long rows, int N) { return fills320(N) && rows >= 1024; }   // (swapped V^T products have M = C)
 static TileChoice choose_tile(long long rows, int N) {
-    const int nt320 = (N + 319) / 320;
-    const bool fits = nt320 * 320 * 4 <= N * 5 && rows >= 1024;   // (swapped V^T products have M = C)
+    const int nt320 = nt320_of(N);
     const long long t1 = ((rows + 127) / 128) * ((N + 127) / 128);
     const long long c1 = 3 * ((t1 + 255) / 256);
-    if (!fits) return TileChoice{N > 64 ? 1 : 5, c1};
+    if (!fits320(rows, N)) return TileChoice{N > 64 ? 1 : 5, c1};
     const long long t256 = ((rows + 255) / 256) * nt320, t128 = ((rows + 127) / 128) * nt320;
     const long long c2 = 10 * ((t256 + 255) / 256), c8 = 8 * ((t128 + 255) / 256);
     if (c2 <= c8 && c2 <= c1) return TileChoice{2, c2};
@@ -481,10 +488,10 @@ static TileChoice choose_tile(long long rows, int N) {
 static int choose_split(int begin, int end, int N) {
     const long long rows = end - begin;
     const TileChoice whole = choose_tile(rows, N);
-    const int nt320 = (N + 319) / 320;
+    const int nt320 = nt320_of(N);
     // (also when the WHOLE product prefers small tiles — 18 432 rows x 1280: 288 big tiles = two rounds for 1.125 — whole
     // rounds of big tiles + a small-tile tail can still win: one round at 1.2 PFLOP/s + 160 small tiles)
-    if (whole.v != 2 && !(nt320 * 320 * 4 <= N * 5 && rows >= 1024)) return 0;
+    if (whole.v != 2 && !fits320(rows, N)) return 0;
     const long long t256 = ((rows + 255) / 256) * nt320;
     const long long full = t256 / 256;
     // The main launch is EXACT-FIT: `full` rounds of one tile per CU.  Beside a collective whose channel kernels hold a few CUs
@@ -503,28 +510,97 @@ static int choose_split(int begin, int end, int N) {
     return cost * 100 <= whole.cost * 94 ? split : 0;      // (measured in the step at 24 / 16 / 12 frames: 94 >= 100 >= 104 > 110)
 }
 
-template <int MODE, bool GEGLU>
-static int pick_tile(const GemmP& p, int force, hipStream_t st) {
-    const int v = force ? force : choose_tile(p.M - p.m_begin, p.N).v;
-    if constexpr (MODE == 1 && !GEGLU) {
-        if (p.ups == 2)     // nearest-to-size gather: two instantiations of its own (latents not divisible by 8 only)
-            return v == 1 ? launch<128, 128, 2, 2, 1, false, false, 2>(p, st) : launch<256, 320, 4, 2, 1, false, true, 2>(p, st);
+// The ROUTE of a call: everything that selects the template instantiation it runs.  gemm_route decides it once, from the
+// prepared arguments; vdx_gemm_f16 launches from it, vdx_gemm_kernel_name names from it, vdx_gemm_plan reports it and
+// vdx_gemm_plan_ksplit asks it (gemm_run below: the one switch from a route to its instantiation).
+struct GemmRoute {
+    int v;          // kernel variant as listed above: 1 2 5 6 9 gemm_kernel, 3 4 8 gemm_ring_kernel, 7 gemm_ws_kernel
+    int ws;         // v == 7: the weights-stationary shape family (its residual / weight-set flags come from p.res / p.wset_rows)
+    int mode;       // MODE (a GEGLU product is plain)
+    bool geglu;     // GEGLU
+    int var;        // VAR: 0 | 1 split-K slices + reduction (p.ksplit > 1; v == 2) | 2 the upsample-to-size gather
+    bool forced;    // the caller pinned the variant
+    bool whole;     // the call covers the whole product (row_begin / row_end unset or [0, M))
+};
+static int gemm_route(const vdx_gemm_args* a, const GemmP& p, GemmRoute& r) {
+    const int force = (a->epilogue >> 8) & 15;   // kernel variant override (0 = automatic)
+    r = GemmRoute{};
+    r.geglu = (a->epilogue & VDX_EPI_GEGLU) != 0;
+    r.mode = a->mode;
+    r.forced = force != 0;
+    r.whole = a->row_begin == 0 && (a->row_end == 0 || a->row_end == a->M);
+    r.var = p.ksplit > 1 ? 1 : (a->mode == VDX_GEMM_CONV3X3 && a->upsample == 2) ? 2 : 0;
+    // short-K Linear layers on many rows (levels 0/1, transformer_in): weights-stationary streaming kernels
+    // (variant 7 pins them); they walk whole products only
+    if (r.whole && (force == 7 || (force == 0 && a->M >= 16384))) {
+        r.ws = vdx_gemm_ws_family(p, a->mode, r.geglu);
+        VDX_CHECK(r.ws || force != 7, "gemm: variant 7 (weights-stationary) needs plain single-source rows, K in {320, 512, 640}, N %% 32 == 0, M %% 64 == 0");
+    } else {
+        VDX_CHECK(force != 7, "gemm: variant 7 (weights-stationary) computes whole products (row_begin / row_end unset)");
     }
-    switch (v) {
-        case 1: return launch<128, 128, 4, 2, MODE, GEGLU>(p, st);     // EIGHT waves of 32x64: two waves per SIMD (3-10 % over four 64x64 waves on the tails, same bits)
-        case 2: return launch<256, 320, 4, 2, MODE, GEGLU, MODE != 0>(p, st);   // split roles pay on the gathers only
-        case 6: return launch<256, 320, 4, 2, MODE, GEGLU, false>(p, st);
-        case 3: return vdx_gemm_ring_launch(p, MODE, GEGLU, 0, st);
-        case 4: return vdx_gemm_ring_launch(p, MODE, GEGLU, 1, st);
-        case 8: return vdx_gemm_ring_launch(p, MODE, GEGLU, 2, st);
-        case 5: return launch<256, 64, 4, 1, MODE, GEGLU>(p, st);
-        case 9: return launch<128, 128, 2, 2, MODE, GEGLU>(p, st);     // the four-wave form (64x64 per wave), kept for comparison
+    if (a->wset_rows != 0) {        // a weight set per row range (GroupNorm folded into the Linear): weights-stationary kernels only
+        VDX_CHECK(a->wset_rows > 0 && a->wset_bias && a->M % a->wset_rows == 0, "gemm: wset_rows=%d needs wset_bias and M %% wset_rows == 0", a->wset_rows);
+        VDX_CHECK(!a->bias && !a->bias2 && !a->residual && !r.geglu && a->mode == VDX_GEMM_PLAIN && a->ksplit <= 1,
+                  "gemm: weight sets take no bias / bias2 / residual / GEGLU / split-K (fold them into wset_bias)");
+        if (!r.ws && r.whole) r.ws = vdx_gemm_ws_family(p, a->mode, r.geglu);      // (also below the automatic row threshold)
+        VDX_CHECK(r.ws == 1 || r.ws == 2 || r.ws == 4, "gemm: weight sets run on the weights-stationary kernels (K = 320 / 640, whole products)");
+        VDX_CHECK(a->wset_rows % 64 == 0, "gemm: wset_rows must be a multiple of 64");
     }
-    return vdx_fail("gemm: unknown kernel variant %d", v);
+    if (r.var == 1) {               // a pinned split-K call: the 256x320 tile, whatever else the shape would take
+        VDX_CHECK(!r.geglu && (force == 0 || force == 2), "gemm: split-K runs the 256x320 tile without GEGLU");
+        VDX_CHECK(a->ksplit <= 16 && (p.K >> 6) / a->ksplit >= 2, "gemm: ksplit %d leaves fewer than two K tiles per slice (K = %d)", a->ksplit, p.K);
+        VDX_CHECK(fills320(p.N), "gemm: split-K needs N = %d to fill 320-wide tiles", p.N);
+        // the split-K kernels are VAR = 1: their gather shifts by p.ups (0 | 1) and has no nearest-to-size source map
+        VDX_CHECK(a->upsample != 2, "gemm: split-K does not take the upsample-to-size gather (upsample = 2)");
+        VDX_CHECK(a->pad_mode == 0, "gemm: split-K does not take the (0,1,0,1) padding (pad_mode = 1)");
+        r.ws = 0;
+        r.v = 2;
+    } else if (r.ws) {
+        r.v = 7;
+    } else {
+        r.v = force ? force : choose_tile(p.M - p.m_begin, p.N).v;
+    }
+    return 0;
 }
 
-// validation + the kernel-side parameter block, shared by the launch and by vdx_gemm_plan
-static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& force, int& ws_family) {
+template <int MODE, bool GEGLU>
+static int pick_tile(const GemmP& p, const GemmRoute& r, const GemmSink& to) {
+    if constexpr (MODE == 1 && !GEGLU) {
+        if (r.var == 2)     // nearest-to-size gather: two instantiations of its own (latents not divisible by 8 only)
+            return r.v == 1 ? launch<128, 128, 2, 2, 1, false, false, 2>(p, to) : launch<256, 320, 4, 2, 1, false, true, 2>(p, to);
+    }
+    switch (r.v) {
+        case 1: return launch<128, 128, 4, 2, MODE, GEGLU>(p, to);     // EIGHT waves of 32x64: two waves per SIMD (3-10 % over four 64x64 waves on the tails, same bits)
+        case 2: return launch<256, 320, 4, 2, MODE, GEGLU, MODE != 0>(p, to);   // split roles pay on the gathers only
+        case 6: return launch<256, 320, 4, 2, MODE, GEGLU, false>(p, to);
+        case 3: return vdx_gemm_ring_launch(p, MODE, GEGLU, 0, to);
+        case 4: return vdx_gemm_ring_launch(p, MODE, GEGLU, 1, to);
+        case 8: return vdx_gemm_ring_launch(p, MODE, GEGLU, 2, to);
+        case 5: return launch<256, 64, 4, 1, MODE, GEGLU>(p, to);
+        case 9: return launch<128, 128, 2, 2, MODE, GEGLU>(p, to);     // the four-wave form (64x64 per wave), kept for comparison
+    }
+    return vdx_fail("gemm: unknown kernel variant %d", r.v);
+}
+// route -> its instantiation: launched on to.st, or (to.name) only named, by the launch template itself
+static int gemm_run(const GemmP& p, const GemmRoute& r, const GemmSink& to) {
+    if (r.var == 1) {
+        switch (r.mode) {
+            case VDX_GEMM_PLAIN: return launch_ksplit<0>(p, to);
+            case VDX_GEMM_CONV3X3: return launch_ksplit<1>(p, to);
+            default: return launch_ksplit<2>(p, to);
+        }
+    }
+    if (r.v == 7) return vdx_gemm_ws_launch(p, r.ws, r.geglu, to);
+    if (r.geglu) return pick_tile<0, true>(p, r, to);
+    switch (r.mode) {
+        case VDX_GEMM_PLAIN: return pick_tile<0, false>(p, r, to);
+        case VDX_GEMM_CONV3X3: return pick_tile<1, false>(p, r, to);
+        default: return pick_tile<2, false>(p, r, to);
+    }
+}
+
+// validation + the kernel-side parameter block + the route, shared by the launch, the name and the plans
+static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, GemmRoute& r) {
     VDX_CHECK(a && a->a && a->w && a->out, "gemm: null pointer");
     VDX_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "gemm: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
     VDX_CHECK(a->N % 64 == 0 && a->K % 64 == 0, "gemm: N=%d and K=%d must be multiples of 64", a->N, a->K);
@@ -553,31 +629,13 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& forc
     p.frames = a->frames; p.hw = a->hw; p.rpb2 = a->rows_per_bias2 > 0 ? a->rows_per_bias2 : 1;
     p.ldb2 = a->ldb2 > 0 ? a->ldb2 : a->N;
     VDX_CHECK(p.ldb2 % 8 == 0, "gemm: ldb2 must be a multiple of 8");
-    p.ntn = 0; p.ntm = 0; p.ksplit = 0; p.partial = nullptr;
+    p.ntn = 0; p.ntm = 0;
+    p.ksplit = a->ksplit > 1 ? a->ksplit : 0; p.partial = a->ksplit > 1 ? (float*)a->workspace : nullptr;
     p.wset_rows = a->wset_rows; p.wset_bias = a->wset_bias;
-    geglu = (a->epilogue & VDX_EPI_GEGLU) != 0;
-    force = (a->epilogue >> 8) & 15;   // kernel variant override (0 = automatic)
+    const bool geglu = (a->epilogue & VDX_EPI_GEGLU) != 0;
     if (geglu) {
         VDX_CHECK(a->mode == VDX_GEMM_PLAIN && !a->bias2 && !a->residual, "gemm: GEGLU epilogue is plain-mode only");
         VDX_CHECK(a->ldo % 4 == 0, "gemm: GEGLU ldo must be a multiple of 4");
-    }
-    // short-K Linear layers on many rows (levels 0/1, transformer_in): weights-stationary streaming kernels
-    // (variant 7 pins them); they walk whole products only
-    const bool whole = a->row_begin == 0 && (a->row_end == 0 || a->row_end == a->M);
-    ws_family = 0;
-    if (whole && (force == 7 || (force == 0 && a->M >= 16384))) {
-        ws_family = vdx_gemm_ws_family(p, a->mode, geglu);
-        VDX_CHECK(ws_family || force != 7, "gemm: variant 7 (weights-stationary) needs plain single-source rows, K in {320, 512, 640}, N %% 32 == 0, M %% 64 == 0");
-    } else {
-        VDX_CHECK(force != 7, "gemm: variant 7 (weights-stationary) computes whole products (row_begin / row_end unset)");
-    }
-    if (a->wset_rows != 0) {        // a weight set per row range (GroupNorm folded into the Linear): weights-stationary kernels only
-        VDX_CHECK(a->wset_rows > 0 && a->wset_bias && a->M % a->wset_rows == 0, "gemm: wset_rows=%d needs wset_bias and M %% wset_rows == 0", a->wset_rows);
-        VDX_CHECK(!a->bias && !a->bias2 && !a->residual && !geglu && a->mode == VDX_GEMM_PLAIN && a->ksplit <= 1,
-                  "gemm: weight sets take no bias / bias2 / residual / GEGLU / split-K (fold them into wset_bias)");
-        if (!ws_family && whole) ws_family = vdx_gemm_ws_family(p, a->mode, geglu);      // (also below the automatic row threshold)
-        VDX_CHECK(ws_family == 1 || ws_family == 2 || ws_family == 4, "gemm: weight sets run on the weights-stationary kernels (K = 320 / 640, whole products)");
-        VDX_CHECK(a->wset_rows % 64 == 0, "gemm: wset_rows must be a multiple of 64");
     }
     switch (a->mode) {
         case VDX_GEMM_PLAIN:
@@ -613,57 +671,46 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, bool& geglu, int& forc
         default:
             return vdx_fail("gemm: unknown mode %d", a->mode);
     }
-    return 0;
+    return gemm_route(a, p, r);
 }
 
 extern "C" int vdx_gemm_f16(const vdx_gemm_args* a, vdx_stream_t stream) {
     GemmP p;
-    bool geglu;
-    int force, ws_family;
-    if (const int rc = gemm_prepare(a, p, geglu, force, ws_family)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (a->ksplit > 1) {
-        const int nt320 = (p.N + 319) / 320;
-        const long long tiles = (long long)((p.M - p.m_begin + 255) / 256) * nt320;
-        VDX_CHECK(!geglu && (force == 0 || force == 2), "gemm: split-K runs the 256x320 tile without GEGLU");
-        VDX_CHECK(a->ksplit <= 16 && (p.K >> 6) / a->ksplit >= 2, "gemm: ksplit %d leaves fewer than two K tiles per slice (K = %d)", a->ksplit, p.K);
-        VDX_CHECK(nt320 * 320 * 4 <= p.N * 5, "gemm: split-K needs N = %d to fill 320-wide tiles", p.N);
+    GemmRoute r;
+    if (const int rc = gemm_prepare(a, p, r)) return rc;
+    if (r.var == 1) {
+        const long long tiles = (long long)((p.M - p.m_begin + 255) / 256) * nt320_of(p.N);
         VDX_CHECK(a->workspace && (uintptr_t)a->workspace % 16 == 0, "gemm: split-K needs a 16-byte aligned workspace");
         VDX_CHECK(tiles * a->ksplit <= (1 << 20), "gemm: split-K grid too large");
         VDX_CHECK(a->workspace_bytes >= (size_t)tiles * a->ksplit * KSPLIT_SLAB_BYTES,
                   "gemm: split-K workspace of %zu bytes is smaller than %lld tiles x %d slices x %d bytes", a->workspace_bytes, tiles,
                   a->ksplit, (int)KSPLIT_SLAB_BYTES);
-        // the split-K kernels are VAR = 1: their gather shifts by p.ups (0 | 1) and has no nearest-to-size source map
-        VDX_CHECK(a->upsample != 2, "gemm: split-K does not take the upsample-to-size gather (upsample = 2)");
-        VDX_CHECK(a->pad_mode == 0, "gemm: split-K does not take the (0,1,0,1) padding (pad_mode = 1)");
-        switch (a->mode) {
-            case VDX_GEMM_PLAIN: return launch_ksplit<0>(p, a->ksplit, (float*)a->workspace, st);
-            case VDX_GEMM_CONV3X3: return launch_ksplit<1>(p, a->ksplit, (float*)a->workspace, st);
-            default: return launch_ksplit<2>(p, a->ksplit, (float*)a->workspace, st);
-        }
     }
-    if (ws_family) return vdx_gemm_ws_launch(p, ws_family, geglu, st);
-    if (geglu) return pick_tile<0, true>(p, force, st);
-    switch (a->mode) {
-        case VDX_GEMM_PLAIN: return pick_tile<0, false>(p, force, st);
-        case VDX_GEMM_CONV3X3: return pick_tile<1, false>(p, force, st);
-        default: return pick_tile<2, false>(p, force, st);
-    }
+    return gemm_run(p, r, GemmSink{(hipStream_t)stream, nullptr});
+}
+
+// Host-only, no GPU needed.  Runs ALL of vdx_gemm_f16's validation of shape, flags and geometry (gemm_prepare: a call it
+// refuses has no name) except the split-K workspace's alignment and size, which select nothing; pointers are only tested
+// for null.
+extern "C" int vdx_gemm_kernel_name(const vdx_gemm_args* a, char* buf, size_t n) {
+    VDX_CHECK(buf, "gemm_kernel_name: null buffer");
+    GemmP p;
+    GemmRoute r;
+    if (const int rc = gemm_prepare(a, p, r)) return rc;
+    char name[GEMM_NAME_MAX];
+    if (const int rc = gemm_run(p, r, GemmSink{nullptr, name})) return rc;
+    VDX_CHECK(strlen(name) < n, "gemm_kernel_name: \"%s\" does not fit a buffer of %zu bytes", name, n);
+    memcpy(buf, name, strlen(name) + 1);
+    return 0;
 }
 
 extern "C" int vdx_gemm_plan(const vdx_gemm_args* a, int32_t* variant, int32_t* split_row) {
     VDX_CHECK(variant && split_row, "gemm_plan: null pointer");
     GemmP p;
-    bool geglu;
-    int force, ws_family;
-    if (const int rc = gemm_prepare(a, p, geglu, force, ws_family)) return rc;
-    *split_row = 0;
-    if (ws_family) {
-        *variant = 7;
-        return 0;
-    }
-    *variant = force ? force : choose_tile(p.M - p.m_begin, p.N).v;
-    if (!force) *split_row = choose_split(p.m_begin, p.M, p.N);
+    GemmRoute r;
+    if (const int rc = gemm_prepare(a, p, r)) return rc;
+    *variant = r.v;
+    *split_row = r.forced || r.v == 7 || r.var == 1 ? 0 : choose_split(p.m_begin, p.M, p.N);
     return 0;
 }
 
@@ -673,19 +720,18 @@ extern "C" int vdx_gemm_plan(const vdx_gemm_args* a, int32_t* variant, int32_t* 
 extern "C" int vdx_gemm_plan_ksplit(const vdx_gemm_args* a, int32_t* split_row, int32_t* ksplit, size_t* workspace_bytes) {
     VDX_CHECK(split_row && ksplit && workspace_bytes, "gemm_plan_ksplit: null pointer");
     GemmP p;
-    bool geglu;
-    int force, ws_family;
-    if (const int rc = gemm_prepare(a, p, geglu, force, ws_family)) return rc;
+    GemmRoute r;
+    if (const int rc = gemm_prepare(a, p, r)) return rc;
     *split_row = 0; *ksplit = 0; *workspace_bytes = 0;
-    if (ws_family || geglu || force || p.m_begin != 0 || p.M != a->M) return 0;
-    if (a->pad_mode != 0) return 0;     // vdx_gemm_f16 refuses split-K with pad_mode = 1
-    if (a->upsample == 2) return 0;     // no split-K instantiation carries the nearest-to-size gather (vdx_gemm_f16 refuses it)
+    if (r.v == 7 || r.geglu || r.forced || !r.whole) return 0;
+    if (a->pad_mode != 0) return 0;     // gemm_route refuses split-K with pad_mode = 1
+    if (a->upsample == 2) return 0;     // no split-K instantiation carries the nearest-to-size gather (gemm_route refuses it)
     const long long rows = p.M;
-    const int nt320 = (p.N + 319) / 320, nk = p.K >> 6;
-    if (!(nt320 * 320 * 4 <= p.N * 5 && rows >= 1024)) return 0;        // (choose_tile's `fits`: N fills 320-wide tiles)
+    const int nt320 = nt320_of(p.N), nk = p.K >> 6;
+    if (!fits320(rows, p.N)) return 0;
     const long long t256 = ((rows + 255) / 256) * nt320, full = t256 / 256;
     if (full == 0 || t256 % 256 == 0) return 0;
-    const long long mt_main = full * 256 / nt320;
+    const long long mt_main = full * 256 / nt320;                      // (on all 256 CUs: unlike choose_split, a reserve — vdx_grid_cus() — does not shrink this main launch)
     const long long split = mt_main * 256;
     if (split >= rows) return 0;
     const long long t = ((rows - split + 255) / 256) * nt320;          // tiles of the tail

@@ -21,6 +21,16 @@ struct GemmP {
     const float* wset_bias;
 };
 
+// Where a routed call ends.  name == nullptr: the kernel is launched on `st`.  Otherwise nothing is launched and no GPU is
+// needed: the host launch template the route reaches formats ITS OWN template arguments into name[GEMM_NAME_MAX], spelled as
+// rocprofv3 prints the instantiation (vdx_gemm_kernel_name), so a name cannot drift from what is instantiated.
+struct GemmSink {
+    hipStream_t st;
+    char* name;
+};
+constexpr int GEMM_NAME_MAX = 96;
+static inline const char* tf(bool b) { return b ? "true" : "false"; }
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -99,7 +109,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TM][T
 
 // K-step-32 LDS-ring kernels (gemm_ring.hip); mode = VDX_GEMM_*; variant 0 = 256x320 tile with a
 // four-stage ring (one block per CU), variant 1 = 128x320 tile, two stages, two blocks per CU.
-int vdx_gemm_ring_launch(const GemmP& p, int mode, bool geglu, int variant, hipStream_t st);
+int vdx_gemm_ring_launch(const GemmP& p, int mode, bool geglu, int variant, const GemmSink& to);
 
 // Logical tile id -> (m tile, n tile).  Up to 4 column tiles: n fastest (the tiles of a row block share its
 // activations).  More (N >= 1600: the level-2/3 GEGLU and q|k|v layers): column PANELS of 4 n tiles, m-major inside
@@ -121,4 +131,4 @@ __device__ __forceinline__ void gemm_tile_of(int bid, int ntm, int ntn, int& mt,
 
 // Weights-stationary streaming kernels for short-K Linear layers (gemm_ws.hip): family 0 = shape not covered.
 int vdx_gemm_ws_family(const GemmP& p, int mode, bool geglu);
-int vdx_gemm_ws_launch(const GemmP& p, int family, bool geglu, hipStream_t st);
+int vdx_gemm_ws_launch(const GemmP& p, int family, bool geglu, const GemmSink& to);

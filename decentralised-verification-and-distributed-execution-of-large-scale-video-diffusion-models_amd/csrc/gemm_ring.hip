@@ -199,7 +199,8 @@ __global__ __launch_bounds__(WMB * 128) void gemm_ring_kernel(const GemmP p) {
 }
 
 template <int WMB, int RPW, int NS, int MODE, bool GEGLU>
-int launch_ring(const GemmP& p, hipStream_t st) {
+int launch_ring(const GemmP& p, const GemmSink& to) {
+    if (to.name) return snprintf(to.name, GEMM_NAME_MAX, "gemm_ring_kernel<%d, %d, %d, %d, %s>", WMB, RPW, NS, MODE, tf(GEGLU)), 0;
     constexpr int BM = WMB * RPW;
     constexpr int lds = NS * (BM + BN) * 64 + (GEGLU ? GELU_TAB_BYTES : 0);
     auto kern = gemm_ring_kernel<WMB, RPW, NS, MODE, GEGLU>;
@@ -210,24 +211,24 @@ int launch_ring(const GemmP& p, hipStream_t st) {
     q.ntn = (p.N + BN - 1) / BN;
     const int ntm = (p.M - p.m_begin + BM - 1) / BM;
     q.ntm = ntm;
-    hipLaunchKernelGGL(kern, dim3(ntm * q.ntn), dim3(WMB * 128), lds, st, q);
+    hipLaunchKernelGGL(kern, dim3(ntm * q.ntn), dim3(WMB * 128), lds, to.st, q);
     return vdx_launch_status("vdx_gemm_f16");
 }
 
 }  // namespace
 
 template <int WMB, int RPW, int NS>
-static int dispatch(const GemmP& p, int mode, bool geglu, hipStream_t st) {
-    if (geglu) return launch_ring<WMB, RPW, NS, 0, true>(p, st);
+static int dispatch(const GemmP& p, int mode, bool geglu, const GemmSink& to) {
+    if (geglu) return launch_ring<WMB, RPW, NS, 0, true>(p, to);
     switch (mode) {
-        case VDX_GEMM_PLAIN: return launch_ring<WMB, RPW, NS, 0, false>(p, st);
-        case VDX_GEMM_CONV3X3: return launch_ring<WMB, RPW, NS, 1, false>(p, st);
-        default: return launch_ring<WMB, RPW, NS, 2, false>(p, st);
+        case VDX_GEMM_PLAIN: return launch_ring<WMB, RPW, NS, 0, false>(p, to);
+        case VDX_GEMM_CONV3X3: return launch_ring<WMB, RPW, NS, 1, false>(p, to);
+        default: return launch_ring<WMB, RPW, NS, 2, false>(p, to);
     }
 }
 
-int vdx_gemm_ring_launch(const GemmP& p, int mode, bool geglu, int variant, hipStream_t st) {
-    if (variant == 0) return dispatch<4, 64, 4>(p, mode, geglu, st);
-    if (variant == 1) return dispatch<2, 64, 2>(p, mode, geglu, st);
-    return dispatch<4, 32, 4>(p, mode, geglu, st);
+int vdx_gemm_ring_launch(const GemmP& p, int mode, bool geglu, int variant, const GemmSink& to) {
+    if (variant == 0) return dispatch<4, 64, 4>(p, mode, geglu, to);
+    if (variant == 1) return dispatch<2, 64, 2>(p, mode, geglu, to);
+    return dispatch<4, 32, 4>(p, mode, geglu, to);
 }

@@ -342,7 +342,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_ws_kernel(const WsP q) {
 }
 
 template <int K, int NW, int ROWS, bool GEGLU, bool RES, bool PIPE, bool WSET = false>
-int launch_ws(const GemmP& p, hipStream_t st) {
+int launch_ws(const GemmP& p, const GemmSink& to) {
+    if (to.name)
+        return snprintf(to.name, GEMM_NAME_MAX, "gemm_ws_kernel<%d, %d, %d, %s, %s, %s, %s>", K, NW, ROWS, tf(GEGLU), tf(RES), tf(PIPE), tf(WSET)), 0;
     typedef Ws<K, NW, ROWS, GEGLU, RES, PIPE, WSET> W;
     static_assert(!(WSET && GEGLU), "weight sets run the plain epilogue");
     constexpr int lds = W::NS * W::STAGE + (GEGLU ? GELU_TAB_BYTES : 0) + (WSET ? NW * 64 * 32 : 0);
@@ -358,14 +360,14 @@ int launch_ws(const GemmP& p, hipStream_t st) {
     q.groups = grid / q.nt;
     q.nch = p.M / ROWS;
     q.per_xcd = grid / 8;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, q);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, to.st, q);
     return vdx_launch_status("vdx_gemm_f16 (weights-stationary)");
 }
 
 template <int K, int NW, int ROWS, bool PIPE>
-int launch_ws_epi(const GemmP& p, bool geglu, hipStream_t st) {
-    if (geglu) return launch_ws<K, NW, ROWS, true, false, PIPE>(p, st);
-    return p.res ? launch_ws<K, NW, ROWS, false, true, PIPE>(p, st) : launch_ws<K, NW, ROWS, false, false, PIPE>(p, st);
+int launch_ws_epi(const GemmP& p, bool geglu, const GemmSink& to) {
+    if (geglu) return launch_ws<K, NW, ROWS, true, false, PIPE>(p, to);
+    return p.res ? launch_ws<K, NW, ROWS, false, true, PIPE>(p, to) : launch_ws<K, NW, ROWS, false, false, PIPE>(p, to);
 }
 
 }  // namespace
@@ -383,20 +385,20 @@ int vdx_gemm_ws_family(const GemmP& p, int mode, bool geglu) {
     return 0;
 }
 
-int vdx_gemm_ws_launch(const GemmP& p, int family, bool geglu, hipStream_t st) {
+int vdx_gemm_ws_launch(const GemmP& p, int family, bool geglu, const GemmSink& to) {
     if (p.wset_rows > 0) {      // (gemm_prepare: plain epilogue, families 1 / 2 / 4)
         switch (family) {
-            case 1: return launch_ws<320, 10, 64, false, false, false, true>(p, st);
-            case 2: return launch_ws<320, 8, 64, false, false, true, true>(p, st);
-            case 4: return launch_ws<640, 8, 32, false, false, true, true>(p, st);
+            case 1: return launch_ws<320, 10, 64, false, false, false, true>(p, to);
+            case 2: return launch_ws<320, 8, 64, false, false, true, true>(p, to);
+            case 4: return launch_ws<640, 8, 32, false, false, true, true>(p, to);
         }
         return vdx_fail("gemm_ws: weight sets on family %d", family);
     }
     switch (family) {
-        case 1: return launch_ws_epi<320, 10, 64, false>(p, geglu, st);
-        case 2: return launch_ws_epi<320, 8, 64, true>(p, geglu, st);
-        case 3: return launch_ws_epi<512, 8, 32, true>(p, geglu, st);
-        case 4: return launch_ws_epi<640, 8, 32, true>(p, geglu, st);
+        case 1: return launch_ws_epi<320, 10, 64, false>(p, geglu, to);
+        case 2: return launch_ws_epi<320, 8, 64, true>(p, geglu, to);
+        case 3: return launch_ws_epi<512, 8, 32, true>(p, geglu, to);
+        case 4: return launch_ws_epi<640, 8, 32, true>(p, geglu, to);
     }
     return vdx_fail("gemm_ws: shape not supported");
 }

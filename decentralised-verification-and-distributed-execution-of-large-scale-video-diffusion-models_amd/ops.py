@@ -221,12 +221,7 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
             ws_ = _scratch(_KSPLIT_WS, out.device, wsb, torch.float32)
             g.workspace, g.workspace_bytes = ws_.data_ptr(), ws_.numel() * 4
         rows = (re_ or M) - rb
-        name = None                     # only named when bench.py profiles (gemm_kernel_name is not free on the host)
-        if PROFILE is not None:
-            name = gemm_kernel_name(rows, N, K, mode, geglu, 7 if wset_rows else variant, single_source=a2 is None and bias2 is None,
-                                    residual=residual is not None, whole=(rb == 0 and re_ in (0, M)), wset=bool(wset_rows))
-            if ks > 1:
-                name = f"gemm_kernel<256, 320, 4, 2, {mode}, false, {'true' if mode else 'false'}, 1> split-K + reduce"
+        name = _gemm_name(g) if PROFILE is not None else None     # only asked for when bench.py profiles
         with _timed(name, 2.0 * rows * N * K, (rows, N, K)):
             _launch("vdx_gemm_f16", C.byref(g))
     return out
@@ -241,39 +236,38 @@ def _profiled(name: str) -> bool:
     return PROFILE_ONLY is None or any(s_ in name for s_ in PROFILE_ONLY)
 
 
-WS_MIN_ROWS = 16384   # gemm.hip: smallest M the weights-stationary K=320 kernel is picked for
+def _gemm_name(g: GemmArgs) -> str:
+    """vdx_gemm_kernel_name: the instantiation vdx_gemm_f16(g) would launch, named by the library's own dispatch."""
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().vdx_gemm_kernel_name(C.byref(g), buf, len(buf)), "vdx_gemm_kernel_name")
+    return buf.value.decode()
 
 
 def gemm_kernel_name(M: int, N: int, K: int, mode: int, geglu: bool, variant: int = 0, single_source: bool = True,
                      residual: bool = False, whole: bool = True, wset: bool = False) -> str:
     """Name of the instantiation vdx_gemm_f16 launches (as rocprofv3 prints it) for M rows (`whole`: the call covers
-    the whole product — the weights-stationary kernels take no row ranges)."""
-    v = variant
-    if whole and single_source and mode == PLAIN and N % 32 == 0 and (v == 7 or (v == 0 and M >= WS_MIN_ROWS)):
-        fam = None   # mirrors vdx_gemm_ws_family (gemm_ws.hip): (K, waves, chunk rows, pipelined)
-        if K == 320 and M % 64 == 0:
-            fam = (320, 10, 64, False) if (N % 320 == 0 and not (geglu and N % 256 == 0)) else (320, 8, 64, True)
-        elif ((K == 512 and N % 256 == 0) or K == 640) and M % 32 == 0:
-            fam = (K, 8, 32, True)
-        if fam:
-            b = lambda x: "true" if x else "false"
-            return f"gemm_ws_kernel<{fam[0]}, {fam[1]}, {fam[2]}, {b(geglu)}, {b(residual and not geglu)}, {b(fam[3])}, {b(wset)}>"
-    if v == 0:
-        nt320 = (N + 319) // 320
-        fits = nt320 * 320 * 4 <= N * 5 and M >= 1024
-        if not fits:
-            v = 1 if N > 64 else 5
-        else:   # mirrors pick_tile (gemm.hip): rounds of 256 tiles x relative tile time
-            t256 = ((M + 255) // 256) * nt320
-            t128 = ((M + 127) // 128) * nt320
-            t1 = ((M + 127) // 128) * ((N + 127) // 128)
-            c2, c8, c1 = 10 * ((t256 + 255) // 256), 8 * ((t128 + 255) // 256), 3 * ((t1 + 255) // 256)
-            v = 2 if (c2 <= c8 and c2 <= c1) else (8 if c8 <= c1 else 1)
-    tail = f"{0 if geglu else mode}, {'true' if geglu else 'false'}"
-    split = {1: ", false, 0>", 9: ", false, 0>", 2: ", true, 0>" if (mode != PLAIN and not geglu) else ", false, 0>", 5: ", false, 0>",
-             6: ", false, 0>"}.get(v, ">")   # gemm_kernel's SPLIT flag and VAR (0: the product kernels)
-    return {1: "gemm_kernel<128, 128, 4, 2, ", 9: "gemm_kernel<128, 128, 2, 2, ", 2: "gemm_kernel<256, 320, 4, 2, ", 3: "gemm_ring_kernel<4, 64, 4, ",
-            4: "gemm_ring_kernel<2, 64, 2, ", 8: "gemm_ring_kernel<4, 32, 4, ", 5: "gemm_kernel<256, 64, 4, 1, ", 6: "gemm_kernel<256, 320, 4, 2, "}[v] + tail + split
+    the whole product — the weights-stationary kernels take no row ranges).  Host-only (no GPU): a call of this shape
+    with placeholder pointers, which the library tests for null and never reads, and the smallest geometry its
+    validation accepts (one M x 1 picture, one one-frame clip), which the choice does not depend on."""
+    g = GemmArgs()
+    g.a = g.w = g.out = 1 << 20
+    g.M, g.N, g.K, g.mode, g.ldo = M, N, K, mode, N
+    g.c1 = g.lda = K // {PLAIN: 1, CONV3X3: 9, TCONV3: 3}[mode]
+    g.epilogue = (EPI_GEGLU if geglu else 0) | ((variant & 15) << 8)
+    if mode == CONV3X3:
+        g.h_in, g.w_in, g.h_out, g.w_out, g.stride = M, 1, M, 1, 1
+    elif mode == TCONV3:
+        g.frames, g.hw = 1, M
+    elif not single_source:             # a second source: 64 channels of the concat
+        g.a2, g.c2, g.lda2, g.c1 = 1 << 20, 64, 64, K - 64
+    if residual:
+        g.residual, g.ldr = 1 << 20, N
+    if wset:
+        g.wset_rows, g.wset_bias = M, 1 << 20
+    if not whole:                       # rows [0, M) of a longer product
+        g.row_end = M
+        g.M = 2 * M
+    return _gemm_name(g)
 
 
 def conv_in(x, w, bias, out=None):

@@ -96,6 +96,14 @@ int vdx_gemm_f16(const vdx_gemm_args* a, vdx_stream_t stream);
  * which splitting the product into two calls ([row_begin, split_row) and [split_row, row_end)) is expected to be faster
  * (whole rounds of 256 big tiles + a tail of small ones instead of a mostly idle last round), or 0.                  */
 int vdx_gemm_plan(const vdx_gemm_args* a, int32_t* variant, int32_t* split_row);
+/* The name of the kernel instantiation vdx_gemm_f16(a) would launch for rows [row_begin, row_end) with a->ksplit, as
+ * rocprofv3 prints it without `void `, namespaces and the argument list ("gemm_kernel<256, 320, 4, 2, 1, false, true, 0>";
+ * a split-K call: its slice kernel + " split-K + reduce").  Host-only: launches nothing, needs no GPU, and formats the
+ * name where the template is instantiated, so it cannot differ from the launch.  It runs vdx_gemm_f16's whole validation
+ * of shapes, flags and geometry (a refused call has no name) but not that of the split-K workspace; pointers are tested
+ * for null (the weights-stationary route depends on `residual` and `bias2`), never dereferenced.  `n`: the size of `buf`;
+ * a name that does not fit (with its terminator) is an error, never truncated.                                      */
+int vdx_gemm_kernel_name(const vdx_gemm_args* a, char* buf, size_t n);
 /* The same question with a split-K tail allowed (whole products only): rows [0, *split_row) as one ordinary call, rows
  * [*split_row, M) as one call with ksplit = *ksplit and a workspace of *workspace_bytes; *ksplit = 0 when vdx_gemm_plan's
  * answer is at least as good.  Pays on the 16-frame windows of BASELINE cfg4 / cfg5, whose row counts leave 1/8 - 1/2 of a

@@ -62,7 +62,7 @@ CONFIGS = {
     "window-16f-hard": ("hard", 16, True, False),
 }
 
-# Kernels the headline forward launches (GEMM instantiations as ops.gemm_kernel_name names them, after vdx_gemm_plan's split)
+# Kernels the headline forward launches (GEMM instantiations as the library's own dispatch names them: vdx_gemm_kernel_name, after vdx_gemm_plan's split)
 HEADLINE_DISPATCH = {
     # fused blocks and attention kernels (K1 conv3x3+GN, K3 temporal conv+GN, K5 cross-attention, K7 / K7b temporal
     # attention, K8 feed-forward with proj_out)

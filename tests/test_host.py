@@ -320,6 +320,90 @@ def test_gemm_plan_is_host_only_and_splits_the_mostly_idle_last_round():
         assert lib.vdx_gemm_plan(C.byref(g), C.byref(v), C.byref(s)) != 0 and b"rows [" in lib.vdx_last_error(), bad
 
 
+def test_gemm_kernel_name_is_host_only_and_comes_from_the_dispatch():
+    """vdx_gemm_kernel_name names what vdx_gemm_f16 would launch, from the switch that instantiates it, without a GPU:
+    (1) every row of tests/golden/gemm_kernel_names.json — the names the Python restatement of the dispatch gave at the last
+    commit that had one (make_gemm_kernel_names.py) — byte for byte; (2) the two routes that restatement got wrong, against
+    the C code: the upsample-to-size gather runs the VAR = 2 instantiations, N > 65536 has no weights-stationary kernel;
+    (3) vdx_gemm_plan's variant and the name agree; (4) each of the 21 GEMM names rocprofv3 recorded on the hardware
+    (profiles/r07_kernel_stats.csv) is the library's answer for some row of the table: the spelling is the profiler's."""
+    import ctypes as C
+    import csv
+    import json
+    from vdx import _lib, ops
+    lib = _lib.load()
+
+    def args(M, N, K, mode=0, taps=1, **kw):
+        g = _lib.GemmArgs()
+        g.a = g.w = g.out = 1 << 20            # never dereferenced on the host
+        g.M, g.N, g.K, g.mode, g.c1 = M, N, K, mode, K // taps
+        g.lda, g.ldo = K // taps, N
+        for k, v in kw.items():
+            setattr(g, k, v)
+        return g
+
+    def name(g, n=128):
+        buf = C.create_string_buffer(b"?" * (n - 1), n)
+        assert lib.vdx_gemm_kernel_name(C.byref(g), buf, n) == 0, lib.vdx_last_error()
+        return buf.value.decode()
+
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_kernel_names.json")))
+    assert len(table) >= 1000
+    got = set()
+    for *call, want in table:
+        M, N, K, mode, geglu, variant, single, res, whole, wset = call
+        assert ops.gemm_kernel_name(M, N, K, mode, bool(geglu), variant, bool(single), bool(res), bool(whole), bool(wset)) == want, call
+        got.add(want)
+
+    # (2) pick_tile's VAR = 2 branch; vdx_gemm_ws_family's N <= 256 * 256
+    ups = dict(mode=1, taps=9, h_in=8, w_in=22, h_out=16, w_out=43, stride=1, upsample=2)
+    assert name(args(48 * 16 * 43, 640, 9 * 640, **ups)) == "gemm_kernel<128, 128, 2, 2, 1, false, false, 2>"  # 258 big tiles: the choice is variant 1
+    assert name(args(48 * 16 * 43, 640, 9 * 640, epilogue=2 << 8, **ups)) == "gemm_kernel<256, 320, 4, 2, 1, false, true, 2>"
+    assert name(args(372 * 16 * 43, 640, 9 * 640, **ups)) == "gemm_kernel<256, 320, 4, 2, 1, false, true, 2>"  # 7.8 rounds of big tiles: variant 2
+    assert name(args(372 * 16 * 43, 640, 9 * 640, **dict(ups, upsample=0, h_in=16, w_in=43))) == "gemm_kernel<256, 320, 4, 2, 1, false, true, 0>"
+    assert name(args(16384, 65536, 320)).startswith("gemm_ws_kernel<320, 8, 64,")
+    wide = name(args(16384, 65600, 320))
+    assert "gemm_ws_kernel" not in wide and wide == ops.gemm_kernel_name(16384, 65600, 320, ops.PLAIN, False)
+
+    # (3) the shapes of test_gemm_plan_is_host_only_and_splits_the_mostly_idle_last_round
+    family = {7: "gemm_ws_kernel", 2: "gemm_kernel<256, 320", 1: "gemm_kernel<128, 128, 4, 2", 8: "gemm_ring_kernel<4, 32, 4"}
+    t24, t16 = dict(mode=2, taps=3, frames=24, hw=2304), dict(mode=2, taps=3, frames=16, hw=2304)
+    seen = set()
+    for g in (args(110592, 640, 1920, **t24), args(73728, 640, 1920, **t16), args(73728, 640, 1920, row_begin=65536, **t16),
+              args(442368, 320, 960, mode=2, taps=3, frames=24, hw=9216), args(18432, 1280, 1280),
+              args(18432, 1280, 1280, row_begin=16384), args(6912, 1280, 1280), args(442368, 320, 320),
+              args(442368, 320, 320, row_end=1024)):
+        v, s_ = C.c_int32(-1), C.c_int32(-1)
+        assert lib.vdx_gemm_plan(C.byref(g), C.byref(v), C.byref(s_)) == 0, lib.vdx_last_error()
+        assert name(g).startswith(family[v.value]), (v.value, name(g))
+        seen.add(v.value)
+    assert seen == set(family)
+
+    # a pinned split-K call: the slice kernel of the 256x320 tile + the reduction; what the call would refuse has no name
+    assert name(args(2048, 1280, 11520, mode=1, taps=9, h_in=32, w_in=64, h_out=32, w_out=64, stride=1, ksplit=8)) == \
+        "gemm_kernel<256, 320, 4, 2, 1, false, true, 1> split-K + reduce"
+    assert name(args(2048, 1280, 1280, ksplit=4)) == "gemm_kernel<256, 320, 4, 2, 0, false, false, 1> split-K + reduce"
+    buf = C.create_string_buffer(128)
+    assert lib.vdx_gemm_kernel_name(C.byref(args(2048, 384, 1280, ksplit=4)), buf, 128) != 0 and b"320-wide" in lib.vdx_last_error()
+    assert lib.vdx_gemm_kernel_name(C.byref(_lib.GemmArgs()), buf, 128) != 0 and b"null" in lib.vdx_last_error()
+    # a buffer the name does not fit is an error and is left alone, never a truncated name
+    g = args(442368, 320, 320)
+    want = name(g)
+    small = C.create_string_buffer(b"?" * len(want), len(want))
+    assert lib.vdx_gemm_kernel_name(C.byref(g), small, len(want)) != 0 and b"does not fit" in lib.vdx_last_error()
+    assert small.raw == b"?" * len(want)
+    assert name(g, len(want) + 1) == want
+
+    # (4) rocprofv3's own spelling
+    traced = set()
+    for row in csv.reader(open(os.path.join(ROOT, "profiles", "r07_kernel_stats.csv"))):
+        m = re.fullmatch(r"void (?:\(anonymous namespace\)::)?(gemm(?:_ring|_ws)?_kernel<[^>]*>)\((?:\(anonymous namespace\)::)?(?:GemmP|WsP)\)", row[0])
+        if m:
+            traced.add(m.group(1))
+    assert len(traced) == 21
+    assert traced <= got, sorted(traced - got)
+
+
 def test_fused_conv_predicates_are_host_only_and_state_their_limits():
     """K1 / K3's `supported` / `preferred` entry points answer without a GPU (the UNet asks them per layer): widths in 64-channel
     slices, 320-column tiles, K1's per-picture scale / shift table bounded by the LDS left beside the tiles (C1 + C2 <= 1536),

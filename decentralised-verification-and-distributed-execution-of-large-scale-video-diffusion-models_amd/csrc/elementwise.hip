@@ -90,7 +90,12 @@ extern "C" int vdx_silu_f16(const void* x, void* y, size_t n, vdx_stream_t strea
 
 // ---- sinusoidal timestep embedding (diffusers `Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)`,
 // SURVEY.md Appendix A.2): emb[b] = [cos(t * f_0..f_{h-1}) | sin(t * f_0..f_{h-1})], f_j = exp(-ln(10000) * j / h),
-// h = dim / 2, computed in fp32 and stored fp16 like the reference's `t_emb.to(dtype)`.  The timestep is read from
+// h = dim / 2, computed in fp32 and stored fp16 like the reference's `t_emb.to(dtype)`: the exponent and the product t * f
+// are fp32 as diffusers forms them; f itself is the correctly rounded fp32 value of exp (evaluated in double: expf's last
+// bit moves the argument by 6e-5 at t ~ 1000, more than the fp32 product's own rounding;
+// tests/test_activations_gpu.py::test_timestep_embedding_all_timesteps).  This is a DEFINITION chosen so that the value can be
+// stated and tested, not a closer match to diffusers: torch's fp32 exp is within an ulp of it too, differently on the CPU
+// and on a GPU, and no kernel can follow either to the bit.  The timestep is read from
 // DEVICE memory, so a forward needs no host value of it (no sync on device-tensor timesteps, nothing to copy per step).
 __global__ void timestep_embedding_kernel(const float* t, f16* out, int B, int dim) {
     const int half = dim >> 1;
@@ -98,7 +103,7 @@ __global__ void timestep_embedding_kernel(const float* t, f16* out, int B, int d
     if (i >= B * dim) return;
     const int b = i / dim, c = i - b * dim;
     const int j = c < half ? c : c - half;
-    const float f = expf(-9.210340371976184f * (float)j / (float)half);
+    const float f = (float)exp((double)(-9.210340371976184f * (float)j / (float)half));
     const float a = t[0] * f;
     out[i] = (f16)(c < half ? cosf(a) : sinf(a));
 }

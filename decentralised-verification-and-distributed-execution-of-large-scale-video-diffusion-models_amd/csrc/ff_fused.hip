@@ -71,9 +71,18 @@ __device__ __forceinline__ float dpp_add8(float v) {
     return v;
 }
 
-// Phi(x) = 0.5 (1 + erf(x / sqrt 2)) as 0.5 + xc P(xc^2), xc = clamp(x, -4.5, 4.5), P of degree 8 (fitted; |error| <=
-// 2e-5 on the interval, the clamped tail 4.5 (1 - Phi(4.5)) = 1.5e-5 in the product): 12 full-rate instructions, no
-// transcendental — the chunk's 48 products per lane sit between two MFMA phases, so their issue time is exposed.
+// Phi(x) = 0.5 (1 + erf(x / sqrt 2)) as 0.5 + xc P(xc^2), xc = clamp(x, -4.5, 4.5), P of degree 8 (fitted): 12 full-rate
+// instructions, no transcendental — the chunk's 48 products per lane sit between two MFMA phases, so their issue time is
+// exposed.  Contract, enforced over fp16 and fp32 gates (the bias is fp32) by tests/test_activations_gpu.py::test_ff_block_gelu:
+//   * x in [-4.5, 4.5]: |Phi error| <= 2.1e-5, i.e. gelu within 2.1e-5 |x| (measured 2.01e-5 at the fp32 values just inside
+//     -4.5, 1.99e-5 at x = -4.25);
+//   * x > 4.5: Phi stays at the polynomial's Phi(4.5) = 1 - 1.8e-5: inside the same 2.1e-5 |x|;
+//   * x < -4.5: Phi stays at the polynomial's Phi(-4.5) <= Phi(-4.5) + 2.1e-5 = 2.44e-5 while the exact one goes to 0, so the
+//     result is up to 2.44e-5 |x| below 0 (measured 1.8e-5 |x| next to -4.5, 1.46e-5 |x| beyond: -2.3e-4 at x = -16, -0.96 at x = -65504) — a LINEAR tail, not
+//     a bounded one.  Gates of the real feed-forwards stay far inside it (|x| < 20: 5e-4, below the block bounds).
+//     Bounding it costs one instruction, `fmaxf(x, -4.5f)` as the outer factor, and that instruction shows: measured in one
+//     session, alternating, at the headline shape, the 30 launches of a step took 33.83 / 33.85 ms without it and 34.41 /
+//     34.40 ms with it (+1.7 %, run-to-run spread 0.02 ms; the kernel alone 1.201 against 1.234 ms).  So the tail stays.
 #define K8_C0 3.988662064e-01f
 #define K8_C1 -6.624013931e-02f
 #define K8_C2 9.729332291e-03f

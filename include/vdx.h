@@ -120,7 +120,8 @@ int vdx_im2col_in_f16(const void* x_ncfhw, void* out_rows, int B, int Cin, int F
 int vdx_rows_to_ncfhw_f16(const void* rows, int ld, void* out, int B, int C, int F, int H, int W,
                           vdx_stream_t stream);
 
-/* y = x * sigmoid(x), n elements (TimestepEmbedding act / ResnetBlock2D.nonlinearity(temb)) */
+/* y = x * sigmoid(x), n elements (TimestepEmbedding act / ResnetBlock2D.nonlinearity(temb)).  The correctly rounded
+ * function to 0.51 fp16 ulp for every finite fp16 x; +inf -> +inf, -inf and NaN -> NaN, as torch. */
 int vdx_silu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
 
 /* Sinusoidal timestep embedding of UNet3DConditionModel (`Timesteps(320, flip_sin_to_cos=True, shift 0)`):
@@ -128,7 +129,9 @@ int vdx_silu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
  * `t_device` points at ONE fp32 timestep in device memory (all B batch items share it, fsdp_chunked_coherent.py:140). */
 int vdx_timestep_embedding_f16(const float* t_device, void* out, int B, int dim, vdx_stream_t stream);
 
-/* y = gelu(x) (exact, erf), n elements: CLIPMLP's activation between fc1 and fc2 (hidden_act "gelu") */
+/* y = gelu(x) (exact, erf), n elements: CLIPMLP's activation between fc1 and fc2 (hidden_act "gelu").  Within 0.75e-7 |x|
+ * (+ rounding) of x Phi(x) for every finite fp16 x; +inf -> +inf, -inf and NaN -> NaN (torch's CPU fp32 gelu gives NaN for
+ * +inf too). */
 int vdx_gelu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -229,7 +232,10 @@ int vdx_flash_attn_rows_f16(const void* q, int ldq, const void* k, int ldk, cons
 /* K8 — the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
  * erf GELU, both in Transformer2DModel and TransformerTemporalModel) as ONE kernel: LayerNorm -> [val | gate] projection ->
  * val * gelu(gate) -> output projection (+bias) + residual; the [rows][4*inner] intermediate never leaves the CU
- * (csrc/ff_fused.hip).  Built for inner 320 (level 0).
+ * (csrc/ff_fused.hip).  Built for inner 320 (level 0).  Its GELU is a polynomial in clamp(gate, -4.5, 4.5): within
+ * 2.1e-5 |gate| of gate Phi(gate) for gate >= -4.5; for gate < -4.5 the result is up to 2.44e-5 |gate| below the exact -0
+ * (a linear left tail: -4e-4 at gate = -16).  The GEGLU epilogue of vdx_gemm_f16 (a table of Phi on [-5, 5)) is within
+ * 3.1e-6 |gate| everywhere and gives exactly -0 for gate < -5.
  *   t, out : fp16 rows [M][ld], `inner` columns used; out may not alias t
  *   packed : vdx/packing.py pack_k8 (LayerNorm's affine folded into the first projection), vdx_ff_block_pack_bytes bytes */
 int vdx_ff_block_supported(int inner);
@@ -405,7 +411,8 @@ int vdx_clip_preprocess_u8(const vdx_clip_preprocess_args* a, vdx_stream_t strea
 int vdx_clip_vision_embed_f16(const void* patch, int ldp, const void* class_emb, const void* pos_emb, const void* gamma,
                               const void* beta, float eps, int F, int patches, int seq_pad, int D, void* out, int ldo,
                               vdx_stream_t stream);
-/* y = x * sigmoid(1.702 x): the `quick_gelu` activation of CLIP ViT-B/32's MLPs (both towers).  y may alias x.         */
+/* y = x * sigmoid(1.702 x): the `quick_gelu` activation of CLIP ViT-B/32's MLPs (both towers).  y may alias x.  The
+ * correctly rounded function to 0.51 fp16 ulp for every finite fp16 x; +inf -> +inf, -inf and NaN -> NaN, as torch.    */
 int vdx_quick_gelu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
 /* scoring.py:106-107, :123-124, :137-140: per_frame[f] = F.normalize(img[f]) . F.normalize(txt) (eps 1e-12), *mean = their
  * mean over the F frames.  img fp16 [F][ldi], txt fp16 [D]; per_frame / mean fp32 device memory.  A fixed reduction

@@ -6,7 +6,7 @@
 //
 // Un-fused this is LayerNorm, a GEGLU GEMM that writes the [rows][1280] intermediate (1.13 GB per call at level 0 of the
 // XL step) and a GEMM that reads it back: 1.39 ms for 1.09 TFLOP.  Here the intermediate never leaves the CU.  The
-// kernel is tattn2.hip's machinery (K7, second design) with the attention taken out:
+// kernel is rowtile_common.h's machinery (the one tattn2.hip, K7's second design, is built on) with the attention taken out:
 //   * a workgroup of 4 waves holds 192 rows (48 per wave, private to it) as the LayerNorm-ed fp16 MFMA-operand image in
 //     LDS (120 KB); LayerNorm's affine is folded into W1 / b1 on the host (packing.pack_k8);
 //   * the hidden width is walked in 20 chunks of 64: five K-64 steps compute val^T and gate^T of the chunk as [hidden][row]
@@ -18,33 +18,17 @@
 //     across chunks and tiles), exact-or-conservative counted vmcnt waits, one barrier per step;
 //   * persistent: a workgroup walks tiles blockIdx.x, + gridDim.x, ...
 // Built for inner 320 (level 0 of the UNet: 10 feed-forwards per forward).
-#include "vdx_common.h"
-#include <utility>
+#include "rowtile_common.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) char lchar;
-typedef __attribute__((address_space(3))) f16x8 lf16x8;
-typedef __attribute__((address_space(1))) f16 gf16;
-typedef __attribute__((address_space(1))) f16x8 gf16x8;
-typedef __attribute__((address_space(1))) f32x4 gf32x4;
-typedef __attribute__((address_space(1))) float gf32;
-
-__device__ __forceinline__ void wg_barrier() {
+__device__ __forceinline__ void k8_barrier() {
 #ifdef K8_ABL_NOBAR
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     return;
 #endif
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    wg_barrier();
 }
 
 struct K8P {
@@ -61,15 +45,6 @@ struct K8P {
     const float* bp;     // [320]
     int ldx, xrows;
 };
-
-static __device__ __attribute__((aligned(16))) u32x4 g_dump_page8[64 + 64];
-
-__device__ __forceinline__ float dpp_add8(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    return v;
-}
 
 // Phi(x) = 0.5 (1 + erf(x / sqrt 2)) as 0.5 + xc P(xc^2), xc = clamp(x, -4.5, 4.5), P of degree 8 (fitted): 12 full-rate
 // instructions, no transcendental — the chunk's 48 products per lane sit between two MFMA phases, so their issue time is
@@ -108,18 +83,17 @@ __device__ __forceinline__ float gelu_poly(float x) {
 }
 
 template <int INNER, bool PO = false>
-struct K8 {
+struct K8 : RowTile<INNER> {
+    typedef RowTile<INNER> RT;
+    using RT::XB, RT::UB, RT::NU, RT::NPS, RT::NCGF, RT::NCG, RT::ROWS, RT::nt_of, RT::opaque;
+    using RT::lds, RT::lane, RT::n16, RT::q4, RT::wave, RT::woffb, RT::xb, RT::set_lane_constants;
+    using typename RT::Frag;
     static constexpr int KS = INNER / 32, KM = KS / 2;    // MFMA k steps / K-64 steps over the model width
     static constexpr int HID = 4 * INNER, CHUNKS = HID / 64;
-    static constexpr int ROWS = 192, RB = INNER * 2, XB = ROWS * RB;
-    static constexpr int UB = 8192, NU = 5;
-    static constexpr int NCGF = INNER / 128, NCG = (INNER + 127) / 128;
     static constexpr int CSTEPS = KM + NCG;               // steps of one chunk: KM of val|gate, NCG of the output product
     static constexpr int UPC = 2 * KM + 2 * NCGF + (NCG - NCGF);    // units of one chunk
-    static constexpr int NCB = INNER / 64, RBB = NCB * 1024, NPS = 6;
     static constexpr int NT = INNER / 16;                 // 16-column tiles of the output
     static_assert(INNER == 320, "geometry: written for inner 320");
-    static_assert(XB + NU * UB <= 160 * 1024, "LDS budget");
     static_assert(UPC % NU == 0, "the ring position of a unit must not depend on the chunk");
 
     // ---- the static schedule of a chunk (the stream runs on into the next chunk: s >= CSTEPS)
@@ -127,7 +101,6 @@ struct K8 {
     static constexpr int ubl(int r) { return r <= KM ? 2 * r : 2 * KM + (r - KM <= NCGF ? 2 * (r - KM) : 2 * NCGF + (r - KM - NCGF)); }
     static constexpr int ub(int s) { return UPC * (s / CSTEPS) + ubl(s % CSTEPS); }
     static constexpr int hm(int s) { return s < 0 ? NU : ub(s + 1) + NU; }
-    static constexpr int nt_of(int g) { return g < NCGF ? 8 : 4; }
     // vector-memory instructions other than weight pieces, issued at the top of step s: the next chunk's bias (8 loads;
     // tools/k8_check_waits.py compares these counts and every wait with the emitted ISA)
     static constexpr int n_b1(int s) { return s % CSTEPS == KM ? 8 : 0; }
@@ -135,7 +108,8 @@ struct K8 {
 
     // ---- PO: the tail of a tile — 15 steps of tattn2's output-projection schedule (3 column groups x 5 K-64 steps, 25 units of
     // W_p), contracted over y = t + ff(t) held in registers as B operands; the next tile's rows are fetched and normalised
-    // behind it (tattn2's row-prefetch schedule with RS0 = TRS0), so the tile seam of the plain kernel is gone.  The unit
+    // behind it (rowtile_common.h's schedule: column groups of KM steps from tail step 0), so the tile seam of the plain kernel is
+    // gone.  The unit
     // stream runs on from the last chunk into the tail and from the tail into the next tile's chunk 0.
     static constexpr int TSTEPS = NCG * KM, TUNITS = 2 * KM * NCGF + KM * (NCG - NCGF), TRS0 = KM;
     static_assert(!PO || TUNITS % NU == 0, "the ring position of the next tile's first unit must not depend on the tail");
@@ -145,31 +119,17 @@ struct K8 {
         return c < NCGF ? 2 * KM * c + 2 * m : 2 * KM * NCGF + (t - NCGF * KM);
     }
     static constexpr int thm(int t) { return t < 0 ? NU : tub(t + 1) + NU; }
-    static constexpr int txp(int t) { return t == TRS0 || t == TRS0 + 1 ? 3 * (INNER / 64) : 0; }          // row pieces issued in tail step t
-    static constexpr int tp0_mask(int t) {
-        return t == TRS0 + 3 ? 0x03 : t == TRS0 + 5 ? 0x04 : t == TRS0 + 6 ? 0x08 : t == TRS0 + 7 ? 0x10 : t == TRS0 + 8 ? 0x20 : 0;
-    }
-    static constexpr int tfirst(int c) { return c * KM; }
-    static constexpr int tn_bias(int t) {
-        for (int c = 1; c < NCG; ++c) if (t == tfirst(c) - 1) return nt_of(c);        // (group 0's bias is loaded before the tail)
-        return 0;
-    }
-    static constexpr int tn_res(int t) {
-        for (int c = 0; c < NCG; ++c) if (t == tfirst(c) + 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
-    static constexpr int tn_st(int t) {
-        for (int c = 0; c < NCG; ++c) if (t == tfirst(c) + KM - 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
+    static constexpr int txp(int t) { return RT::op_xp(t, 0, KM); }                // row pieces issued in tail step t
+    static constexpr int tp0_mask(int t) { return RT::op_p0_mask(t, 0, KM); }
+    // (group 0's bias is loaded before the tail: t = -1 is never asked)
+    static constexpr int tn_bias(int t) { return RT::op_bias(t, 0, KM); }
+    static constexpr int tn_res(int t) { return RT::op_res(t, 0, KM); }
+    static constexpr int tn_st(int t) { return RT::op_st(t, 0, KM); }
     // vector-memory instructions younger than the last unit piece tail step t needs (tattn2.hip `younger`); at t = 0 the loads
     // issued before the tail are left out: counting fewer only waits for more
     static constexpr int tyounger(int t) { return t == 0 ? 0 : txp(t - 1) + tn_st(t - 1) + tn_bias(t) + tn_res(t); }
     static constexpr int tinflight(int t) { return 2 * (thm(t - 1) - tub(t + 2)) + tyounger(t); }
 
-    struct Frag {
-        f16x8 w[8], x[3];
-    };
     struct State {
         Frag fa, fb;
         f32x4 av[3][4], ag[3][4];        // val^T, gate^T of the chunk: [hidden][row]
@@ -187,57 +147,34 @@ struct K8 {
     };
 
     const K8P& p;
-    char* smem;
-    lchar* lds;
-    int lane, n16, q4, wave;
-    int woffb, xb[2];
     const char* wc0;                     // weights of the current chunk / the next chunk
     const char* wc1;
     const gf32* b1n;                     // bias of the next chunk
 
-    __device__ __forceinline__ K8(const K8P& p_, char* s) : p(p_), smem(s), lds((lchar*)s) {}
-
-    __device__ static __forceinline__ int opaque(int v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    }
+    __device__ __forceinline__ K8(const K8P& p_, char* s) : RT(s), p(p_) {}
 
     // ---- weight stream: unit U of the running chunk (U >= UPC: of the next chunk)
-    template <int U>
-    __device__ __forceinline__ void issue_unit() {
+    template <int U0, int U1>
+    __device__ __forceinline__ void issue_range() {
 #ifdef K8_ABL_NOWDMA       /* diagnostic builds (timing only, wrong results): what each part of the tile costs */
         return;
 #endif
-        const char* src = (U >= UPC ? wc1 + (size_t)(U - UPC) * UB : wc0 + (size_t)U * UB) + (2 * wave) * 1024 + lane * 16;
-        char* dst = smem + XB + (U % NU) * UB + (2 * wave) * 1024;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024), (lptr_t)(dst + 1024), 16, 0, 0);
-    }
-    template <int U0, int U1>
-    __device__ __forceinline__ void issue_range() {
-        if constexpr (U0 < U1) {
-            issue_unit<U0>();
-            issue_range<U0 + 1, U1>();
-        }
+        RT::template issue_range<U0, U1>([this](auto u) {
+            constexpr int U = decltype(u)::value;
+            return U >= UPC ? wc1 + (size_t)(U - UPC) * UB : wc0 + (size_t)U * UB;
+        });
     }
     // tail unit U (U >= TUNITS: unit U - TUNITS of chunk 0 — of the next tile; the weights are the same for every tile)
-    template <int U>
-    __device__ __forceinline__ void issue_tunit() {
-        const char* src = (U >= TUNITS ? p.w + (size_t)(U - TUNITS) * UB : p.wp + (size_t)U * UB) + (2 * wave) * 1024 + lane * 16;
-        char* dst = smem + XB + (U % NU) * UB + (2 * wave) * 1024;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024), (lptr_t)(dst + 1024), 16, 0, 0);
-    }
     template <int U0, int U1>
     __device__ __forceinline__ void issue_trange() {
-        if constexpr (U0 < U1) {
-            issue_tunit<U0>();
-            issue_trange<U0 + 1, U1>();
-        }
+        RT::template issue_range<U0, U1>([this](auto u) {
+            constexpr int U = decltype(u)::value;
+            return U >= TUNITS ? p.w + (size_t)(U - TUNITS) * UB : p.wp + (size_t)U * UB;
+        });
     }
 
-    // ---- the row image (tattn2.hip's layout: [row block of 8][column block of 64 channels][8 rows][128 B], chunk c of a
-    // row at position c ^ (row & 7)); rows past M read the zero page
+    // ---- the row image (rowtile_common.h); rows past M read the zero page.  The gather is RowTile::issue_rows written
+    // out: called through it, this kernel alone got another register allocation (profiles/rowtile_refactor.md)
     template <int PS>
     __device__ __forceinline__ void issue_rows(int tile) {
         const long long gr = (long long)tile * ROWS + wave * 48 + 8 * PS + (lane >> 3);
@@ -245,48 +182,10 @@ struct K8 {
         const char* rowp = (const char*)(p.t + (ok ? gr : 0ll) * p.ldt) + (((lane & 7) ^ (lane >> 3)) << 4);
         const char* src = ok ? rowp : (const char*)g_zero_page;
         const int cstep = ok ? 128 : 0;
-        char* dst = smem + (wave * 6 + PS) * RBB;
+        char* dst = RT::smem + (wave * 6 + PS) * RT::RBB;
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
+        for (int cb = 0; cb < RT::NCB; ++cb)
             __builtin_amdgcn_global_load_lds((gptr_t)(src + cb * cstep), (lptr_t)(dst + cb * 1024), 16, 0, 0);
-    }
-    // centre and scale the 8 rows of pass PS in place (tattn2.hip p0_pass: fp32 statistics, fp16-exact differences)
-    template <int PS>
-    __device__ __forceinline__ void p0_pass() {
-        lchar* base = lds + (wave * 6 + PS) * RBB + lane * 16;
-        f16x8 v[NCB];
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) v[j] = *(const lf16x8*)(base + 1024 * j);
-        const f16x2 ones = (f16x2){(f16)1.f, (f16)1.f};
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum = __builtin_amdgcn_fdot2((f16x2){v[j][2 * e], v[j][2 * e + 1]}, ones, sum, false);
-        sum = dpp_add8(sum);
-        const float mean = sum * (1.0f / INNER);
-        const f16 mh = (f16)mean;
-        const float dm = mean - (float)mh;
-        const f16x2 nm = (f16x2){(f16)-mh, (f16)-mh};
-        float ss = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const f16x2 d = (f16x2){v[j][2 * e], v[j][2 * e + 1]} + nm;
-                ss = __builtin_amdgcn_fdot2(d, d, ss, false);
-            }
-        ss = dpp_add8(ss);
-        const float var = fmaxf(ss * (1.0f / INNER) - dm * dm, 0.f);
-        const float rstd = rsqrtf(var + p.eps);
-        const float nmr = -mean * rstd;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) {
-            f16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf((float)v[j][e], rstd, nmr);
-            *(lf16x8*)(base + 1024 * j) = o;
-        }
     }
 
     __device__ __forceinline__ f16x8 xfrag(int i, int ks) const {
@@ -296,7 +195,7 @@ struct K8 {
         asm volatile("" : "+v"(v));
         return v;
 #endif
-        return *(const lf16x8*)(lds + xb[ks & 1] + (2 * i * RBB + 1024 * (ks >> 1)));
+        return RT::xfrag(i, ks);
     }
     __device__ __forceinline__ f16x8 wfrag(int unit, int tile) const {
 #ifdef K8_ABL_NOLDSW      /* timing only: weight fragments from a register pattern instead of LDS */
@@ -305,7 +204,11 @@ struct K8 {
         asm volatile("" : "+v"(v));
         return v;
 #endif
-        return *(const lf16x8*)(lds + woffb + ((unit % NU) * UB + tile * 1024));
+        return RT::wfrag(unit, tile);
+    }
+    template <int C, int KK>
+    __device__ __forceinline__ void read_out_half(Frag& f, int u0) const {      // (through this kernel's wfrag: K8_ABL_NOLDSW)
+        RT::template read_out_half<C, KK>(f, u0, [this](int unit, int tile) { return wfrag(unit, tile); });
     }
 
     // fragments of half KK (one MFMA k step) of step S (S may be CSTEPS: step 0 of the next chunk)
@@ -322,14 +225,7 @@ struct K8 {
 #pragma unroll
             for (int i = 0; i < 3; ++i) f.x[i] = xfrag(i, 2 * S + KK);
         } else {
-            constexpr int g = S - KM;
-            if constexpr (g < NCGF) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f.w[j] = wfrag(u0 + KK, j);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) f.w[j] = wfrag(u0, 4 * KK + j);
-            }
+            read_out_half<S - KM, KK>(f, u0);
         }
     }
 
@@ -352,16 +248,7 @@ struct K8 {
                 for (int i = 0; i < 3; ++i)
                     st.acc[i][8 * g + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[j], st.hh[i][KK], st.acc[i][8 * g + j], 0, 0, 0);
         }
-#pragma unroll
-        for (int g = 0; g < NVM; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < NDS; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
+        RT::template pin_after_mfma<NVM, NDS>();
     }
     static constexpr int nds(int s_) {
         const int s = s_ % CSTEPS;
@@ -415,97 +302,44 @@ struct K8 {
 #pragma unroll
         for (int a = 0; a < NT / 2; ++a)
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = (f16)st.acc[i][2 * a][e];
-                    o[4 + e] = (f16)st.acc[i][2 * a + 1][e];
-                }
-                st.yb[i][a] = o + rv[i][a];
-            }
+            for (int i = 0; i < 3; ++i)
+                st.yb[i][a] = RT::round_add_residual(st.acc[i][2 * a], st.acc[i][2 * a + 1], rv[i][a]);
     }
+    // bias / residual rows (x) / epilogue of the tail's column group C (rowtile_common.h)
     template <int C>
-    __device__ __forceinline__ void load_bias2(State& st) {
-        const int o = opaque(C * 128 + 8 * q4);
-#pragma unroll
-        for (int j = 0; j < nt_of(C); ++j) st.bv[j] = *(const gf32x4*)((const gf32*)p.bp + o + 32 * (j / 2) + 4 * (j % 2));
-    }
+    __device__ __forceinline__ void load_bias2(State& st) { RT::template load_bias<C>(st.bv, p.bp); }
     template <int C>
-    __device__ __forceinline__ void load_residual2(State& st) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const gf16* src = st.xpr[i] + opaque(0);
-#pragma unroll
-            for (int a = 0; a < nt_of(C) / 2; ++a) st.rv2[i][a] = *(const gf16x8*)(src + C * 128 + 32 * a);
-        }
-    }
-    // column group C: the projection (bias included) rounded to fp16, the residual added in fp16 (the reference's order)
+    __device__ __forceinline__ void load_residual2(State& st) { RT::template load_residual<C>(st.rv2, st.xpr); }
     template <int C>
-    __device__ __forceinline__ void epilogue2(State& st) {
-#pragma unroll
-        for (int a = 0; a < nt_of(C) / 2; ++a)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = (f16)st.acc2[i][2 * a][e];
-                    o[4 + e] = (f16)st.acc2[i][2 * a + 1][e];
-                }
-                o = o + st.rv2[i][a];
-                *(gf16x8*)(st.outp[i] + C * 128 + 32 * a) = o;
-            }
-    }
+    __device__ __forceinline__ void epilogue2(State& st) { RT::template epilogue<C>(st.acc2, st.rv2, st.outp); }
     // weight fragments of half KK of tail step T (T >= TSTEPS: the next tile's chunk step T - TSTEPS)
     template <int T, int KK>
     __device__ __forceinline__ void read_thalf(Frag& f) const {
         if constexpr (T >= TSTEPS) {
             read_half<T - TSTEPS, KK>(f);              // (its unit indices are chunk-relative: the ring position is the same)
         } else {
-            constexpr int c = T / KM, u0 = tub(T);
-            if constexpr (c < NCGF) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f.w[j] = wfrag(u0 + KK, j);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) f.w[j] = wfrag(u0, 4 * KK + j);
-            }
+            read_out_half<T / KM, KK>(f, tub(T));
         }
     }
     static constexpr int tnds(int t) { return t >= TSTEPS ? nds(t - TSTEPS) : nt_of(t / KM); }
     template <int T, int KK, int NDS, int NVM>
     __device__ __forceinline__ void tmma_half(State& st, const Frag& f) {
         constexpr int c = T / KM, m = T % KM;
-        constexpr bool Z = m == 0 && KK == 0;
-#pragma unroll
-        for (int j = 0; j < nt_of(c); ++j)
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                st.acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[j], st.yb[i][2 * m + KK], Z ? st.bv[j] : st.acc2[i][j], 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < NVM; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < NDS; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
+        RT::template mma_out<c, m == 0 && KK == 0>(st.acc2, f, st.yb[0][2 * m + KK], st.yb[1][2 * m + KK], st.yb[2][2 * m + KK], st.bv);
+        RT::template pin_after_mfma<NVM, NDS>();
     }
     template <int T>
     __device__ __forceinline__ void tstep(State& st, int next_tile) {
         if constexpr (tn_bias(T) > 0) load_bias2<(T + 1) / KM>(st);
         if constexpr (tn_res(T) > 0) load_residual2<T / KM>(st);
-        tp0_passes<tp0_mask(T)>(std::make_integer_sequence<int, NPS>{});
+        RT::template p0_passes<tp0_mask(T)>(p.eps);
         read_thalf<T, 1>(st.fb);
         tmma_half<T, 0, tnds(T), 0>(st, st.fa);
         __builtin_amdgcn_sched_barrier(0);
         wait_vm<tinflight(T)>();
         __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
         asm volatile("" ::: "memory");
-        wg_barrier();
+        k8_barrier();
         issue_trange<thm(T - 1), thm(T)>();
         if constexpr (txp(T) > 0) {
             issue_rows<3 * (T - TRS0)>(next_tile);
@@ -521,11 +355,6 @@ struct K8 {
     __device__ __forceinline__ void tsteps(State& st, int next_tile, std::integer_sequence<int, T...>) {
         (tstep<T>(st, next_tile), ...);
     }
-    template <int MASK, int... PS>
-    __device__ __forceinline__ void tp0_passes(std::integer_sequence<int, PS...>) {
-        ((MASK >> PS & 1 ? p0_pass<PS>() : void()), ...);
-    }
-
     template <int S>
     __device__ __forceinline__ void step(State& st) {
         if constexpr (n_b1(S) > 0) load_b1(st, b1n);
@@ -535,7 +364,7 @@ struct K8 {
         wait_vm<inflight(S)>();
         __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
         asm volatile("" ::: "memory");
-        wg_barrier();
+        k8_barrier();
         issue_range<hm(S - 1), hm(S)>();
         read_half<S + 1, 0>(st.fa);
         mma_half<S, 1, nds(S + 1), 2 * (hm(S) - hm(S - 1))>(st, st.fb);
@@ -550,21 +379,6 @@ struct K8 {
     __device__ __forceinline__ void rows_in(int tile, std::integer_sequence<int, PS...>) {
         (issue_rows<PS>(tile), ...);
     }
-    template <int... PS>
-    __device__ __forceinline__ void rows_norm(std::integer_sequence<int, PS...>) {
-        (p0_pass<PS>(), ...);
-    }
-
-    __device__ __forceinline__ void set_lane_constants() {
-        n16 = lane & 15;
-        q4 = lane >> 4;
-        const int g = (0x1320 >> (4 * (n16 >> 2))) & 3;
-        woffb = XB + n16 * 64 + ((q4 ^ g) << 4);
-        const int rr = n16 & 7, xrow = (wave * 6 + (n16 >> 3)) * RBB + rr * 128;
-        xb[0] = xrow + ((q4 ^ rr) << 4);
-        xb[1] = xrow + (((4 + q4) ^ rr) << 4);
-    }
-
     // output bias = the initial value of the output accumulators (tile 2a + jj, register e: column 32a + 8*q4 + 4*jj + e)
     __device__ __forceinline__ void init_acc(State& st) {
         const int o = opaque(8 * q4);
@@ -581,7 +395,7 @@ struct K8 {
         for (int i = 0; i < 3; ++i) {
             const long long gr = (long long)tile * ROWS + wave * 48 + 16 * i + n16;
             const bool ok = gr < p.M;
-            gf16* dump = (gf16*)g_dump_page8 + lane * 8;
+            gf16* dump = (gf16*)g_dump_page + lane * 8;
             st.resp[i] = ok ? (const gf16*)p.t + gr * p.ldt + 8 * q4 : dump;
             st.outp[i] = ok ? (gf16*)p.out + gr * p.ldo + 8 * q4 : dump;
             if constexpr (PO) {
@@ -590,8 +404,7 @@ struct K8 {
             }
         }
     }
-    // tile pair (2a, 2a+1) gives this lane 8 consecutive columns 32a + 8*q4 .. +7 of row n16 (+16i); the projection (bias
-    // included) is rounded to fp16 and the residual added in fp16 — the reference's order
+    // y = t + ff(t), all columns at once: rounded and added as the output projection's epilogue does (rowtile_common.h)
     __device__ __forceinline__ void epilogue(State& st) {
         f16x8 rv[3][NT / 2];
 #pragma unroll
@@ -601,16 +414,8 @@ struct K8 {
 #pragma unroll
         for (int a = 0; a < NT / 2; ++a)
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = (f16)st.acc[i][2 * a][e];
-                    o[4 + e] = (f16)st.acc[i][2 * a + 1][e];
-                }
-                o = o + rv[i][a];
-                *(gf16x8*)(st.outp[i] + 32 * a) = o;
-            }
+            for (int i = 0; i < 3; ++i)
+                *(gf16x8*)(st.outp[i] + 32 * a) = RT::round_add_residual(st.acc[i][2 * a], st.acc[i][2 * a + 1], rv[i][a]);
     }
 
     __device__ __forceinline__ void run() {
@@ -633,9 +438,9 @@ struct K8 {
             init_acc(st);
             if (!PO || tile == (int)blockIdx.x) {          // (PO: a later tile's rows were fetched and normalised behind the previous
                 wait_vm<0>();                              //  tile's tail, whose last step also read the first fragments)
-                rows_norm(std::make_integer_sequence<int, NPS>{});
+                RT::template p0_passes<(1 << NPS) - 1>(p.eps);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wg_barrier();                        // (first tile: the first units have landed for everyone)
+                k8_barrier();                        // (first tile: the first units have landed for everyone)
                 read_half<0, 0>(st.fa);
             }
             for (int c = 0; c < CHUNKS; ++c) {
@@ -706,17 +511,11 @@ static int ff_block_launch(const void* t, int ldt, const void* packed, float eps
     p.x = (const f16*)x; p.ldx = ldx; p.xrows = xrows;
     p.wp = (const char*)proj_packed;
     p.bp = (const float*)(p.wp + (size_t)T::TUNITS * T::UB);
-    constexpr int lds = T::XB + T::NU * T::UB;
+    constexpr int lds = T::LDS_BYTES;
     auto kern = proj_packed ? ff_fused_kernel<320, true> : ff_fused_kernel<320, false>;
-    static const hipError_t attr_rc = [] {
-        const hipError_t a = hipFuncSetAttribute((const void*)ff_fused_kernel<320, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        const hipError_t b = hipFuncSetAttribute((const void*)ff_fused_kernel<320, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        return a != hipSuccess ? a : b;
-    }();
+    static const hipError_t attr_rc = vdx_reserve_lds(lds, ff_fused_kernel<320, false>, ff_fused_kernel<320, true>);
     if (attr_rc != hipSuccess) return vdx_fail("ff_block: cannot reserve %d bytes of LDS", lds);
-    const int ncu = vdx_grid_cus();
-    const int rounds = (p.ntiles + ncu - 1) / ncu;
-    const int grid = (p.ntiles + rounds - 1) / rounds;
+    const int grid = vdx_persistent_grid(p.ntiles);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
     return vdx_launch_status(proj_packed ? "vdx_ff_block_proj_f16" : "vdx_ff_block_f16");
 }

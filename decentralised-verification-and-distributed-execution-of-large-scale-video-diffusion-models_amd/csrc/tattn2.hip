@@ -24,29 +24,12 @@
 //
 // Geometry (inner 320): 4 waves, one per SIMD, each owning a row group of 48 rows = G pixels x F frames (G = 48 / F)
 // for the whole tile; nothing a wave reads of the row image is written by another wave (so the image needs no barrier).
-#include "vdx_common.h"
-#include <utility>
+//
+// The row image, the weight ring and the output projection are shared with K5 (xattn.hip) and K8 (ff_fused.hip), which
+// were built on this kernel: they live in rowtile_common.h.  Here: the step schedule, the wait model, the attention.
+#include "rowtile_common.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) char lchar;                 // LDS addresses as 32-bit arithmetic: a constant
-typedef __attribute__((address_space(3))) f16x8 lf16x8;               // term then folds into the DS offset field
-typedef __attribute__((address_space(1))) f16 gf16;                   // explicit global pointers: a pointer the optimiser
-typedef __attribute__((address_space(1))) f16x8 gf16x8;               // cannot trace becomes a FLAT access (counts on both
-typedef __attribute__((address_space(1))) f32x4 gf32x4;               // counters, completes out of order)
-
-// workgroup barrier the COMPILER also treats as a memory barrier (LLVM models s_barrier as touching no memory)
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 struct K7BP {
     const f16* t;        // [M][ldt] rows, row = (b*F + f)*S + p
@@ -65,44 +48,12 @@ struct K7BP {
     float eps;
 };
 
-// stores of rows that do not exist (last tile) go here, so that every epilogue issues the same number of stores and the
-// counted s_waitcnt of the next step stays exact
-static __device__ __attribute__((aligned(16))) u32x4 g_dump_page[64 + 64];     // lane * 16 bytes + up to 2 * INNER bytes of column offset
-
-__device__ __forceinline__ float dpp_add8(float v) {        // sum over the 8 lanes that share a row (lane & ~7)
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    return v;
-}
-// value of lanes l, l^16, l^32, l^48 combined (the four lane quads that hold one query's keys): two VALU swaps, no LDS
-#ifdef K7B_SHFL
-__device__ __forceinline__ float quad_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
-__device__ __forceinline__ float quad_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
+#ifdef K7B_SHFL     // lab build: the quad reductions by ds_bpermute instead of the permlane swaps (rowtile_common.h)
+__device__ __forceinline__ float k7b_quad_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
+__device__ __forceinline__ float k7b_quad_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 #else
-// v_permlane16_swap exchanges the odd 16-lane rows of its first operand with the even rows of its second;
-// v_permlane32_swap the upper half of the first with the lower half of the second.  Fed the same value twice, the two
-// results together hold the value of both partners in every lane.  Inline asm, not the builtins: hipcc (ROCm 7.2) folds
-// `r[0] op r[1]` of the builtin to `r[0] op r[0]` (seen in the ISA as v_add_f32 v, a0, a0 — the reduction is then a
-// no-op).  The s_nop covers the VALU-write -> permlane-read hazard (2 wait states), which nothing pads inside asm.
-__device__ __forceinline__ void swap16(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void swap32(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ float quad_max(float v) {
-    float a = v, b = v;
-    swap16(a, b);
-    a = fmaxf(a, b);
-    b = a;
-    swap32(a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    float a = v, b = v;
-    swap16(a, b);
-    a = a + b;
-    b = a;
-    swap32(a, b);
-    return a + b;
-}
+__device__ __forceinline__ float k7b_quad_max(float v) { return quad_max(v); }
+__device__ __forceinline__ float k7b_quad_sum(float v) { return quad_sum(v); }
 #endif
 
 #ifdef K7B_STAMPS   // diagnostic build only: cycle totals per (step kind, segment) of wave 0; never in the product library
@@ -136,7 +87,11 @@ extern "C" int vdx_debug_read_k7b_stamps(void* dst) {
 // 16*kt + 4*q4 + e) then belong to ONE pixel, so the block-diagonal mask needs one compare per key tile instead of four
 // (F = 8, 4, 48).  1: any F | 48.
 template <int INNER, int FS>
-struct K7B {
+struct K7B : RowTile<INNER> {
+    typedef RowTile<INNER> RT;
+    using RT::XB, RT::UB, RT::NU, RT::NPS, RT::NCGF, RT::NCG, RT::nt_of, RT::opaque;
+    using RT::lane, RT::n16, RT::q4, RT::wave, RT::wfrag, RT::xfrag;
+    using typename RT::Frag;
     static constexpr bool F4 = FS != 1;
     // tile relations at a compile-time F (16-row tiles a, b of the 48-row group): do they share a pixel / lie in ONE pixel
     static constexpr bool tiles_meet(int a, int b) {
@@ -152,26 +107,11 @@ struct K7B {
     static constexpr int KS = INNER / 32;                 // MFMA k steps over the model width
     static constexpr int HEADS = INNER / 64;
     static constexpr int KM = KS / 2;                     // K-64 steps over the model width
-    static constexpr int ROWS = 192;
-    static constexpr int RB = INNER * 2;                  // bytes of one row of the image
-    static constexpr int XB = ROWS * RB;
-    static constexpr int UB = 8192, NU = 5;               // ring: NU units of UB bytes
     static constexpr int HSTEPS = 2 * KM;                 // steps of one head: KM of q|k, KM of v
     static constexpr int P1S = HEADS * HSTEPS;
-    static constexpr int NCGF = INNER / 128;              // full 128-column groups of the output projection
-    static constexpr int NCG = (INNER + 127) / 128;
     static constexpr int NSTEP = P1S + NCG * HEADS;       // the output projection contracts head by head (K = 64)
     static constexpr int UPH = 3 * KM;                    // units of one head in the q|k|v stream
-    static constexpr int CPL = INNER / 64;                // 16-byte chunks per lane in P0 (8 lanes per row)
-    static constexpr int CPR = INNER / 8;                 // 16-byte chunks per row
-    static constexpr int NPS = 6;                         // P0 passes of 8 rows
-    static constexpr int PPP = 8 * RB / 1024;             // DMA pieces per pass
-    static_assert(KS % 2 == 0 && (INNER % 128 == 0 || INNER % 128 == 64), "geometry");
-    static_assert(XB + NU * UB <= 160 * 1024, "LDS budget");
-    static constexpr int NCB = INNER / 64;                // column blocks of 64 channels (= PPP: one DMA piece each)
-    static constexpr int RBB = NCB * 1024;                // bytes of one row block (8 rows)
-    static_assert(PPP == NCB && XB == 24 * RBB, "a DMA piece is one (row block, column block): 8 rows x 128 bytes");
-    static_assert(NCG == 3 && NPS == 6 && HEADS == 5, "the row prefetch schedule below is written for three column groups of five steps");
+    static_assert(KS % 2 == 0, "geometry");
 
     // ---- the static schedule of a tile: step s consumes units [ub(s), ub(s+1)) of the weight stream; the stream runs
     // on into the next tile (s >= NSTEP: the same schedule again)
@@ -195,41 +135,21 @@ struct K7B {
     // issue point come, in this order: the row pieces of the next tile issued there, the stores of a column group's
     // epilogue (end of step s-1), and the loads at the top of step s (q bias of the next head, output bias of the next
     // column group, residual rows).  All of them are unconditional and opaque to the optimiser (see opaque()).
-    // The next tile's rows are requested right AFTER the first column group's epilogue and have landed before the
-    // second one's: an epilogue consumes plain loads, in front of which hipcc waits vmcnt(0) — every DMA in flight at
-    // that point, HBM-latency row pieces included, would be waited for.  Passes 0-2 in step RS0, passes 3-5 in RS0 + 1.
-    static constexpr int RS0 = P1S + HEADS;
-    static constexpr int xp(int s) { return s == RS0 || s == RS0 + 1 ? 3 * PPP : 0; }               // row pieces issued in step s
-    // P0 passes normalised in the first half of step s: bit ps of the result.  Each at least two step waits after its
-    // pieces were issued (the waits retire every older DMA), none in the last step of the second column group.
-    static constexpr int p0_mask_of(int s) {
-        return s == RS0 + 3 ? 0x03 : s == RS0 + 5 ? 0x04 : s == RS0 + 6 ? 0x08 : s == RS0 + 7 ? 0x10 : s == RS0 + 8 ? 0x20 : 0;
-    }
-    static constexpr int nt_of(int c) { return c < NCGF ? 8 : 4; }
-    static constexpr int first_of(int c) { return P1S + c * HEADS; }
+    // The output projection's part of this — column groups of HEADS steps from step P1S, the next tile's rows behind
+    // them — is rowtile_common.h's.
+    static constexpr int RS0 = P1S + HEADS;                                                         // first step that issues row pieces
+    static constexpr int xp(int s) { return RT::op_xp(s, P1S, HEADS); }                             // row pieces issued in step s
+    static constexpr int p0_mask_of(int s) { return RT::op_p0_mask(s, P1S, HEADS); }                // P0 passes normalised in step s
     static constexpr int n_bq(int s) { return kind(s) == 1 && s % HSTEPS == HSTEPS - 1 && s + 1 < P1S ? 4 : (s == NSTEP - 1 ? 4 : 0); }
-    static constexpr int n_bias(int s) {      // bias of column group c: one step before the group starts
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) - 1) return nt_of(c);
-        return 0;
-    }
-    static constexpr int n_res(int s) {       // residual rows of column group c: at the top of its second step
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) + 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
-    static constexpr int n_st(int s) {        // stores of the epilogue that ran at the end of step s
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) + HEADS - 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
+    static constexpr int n_bias(int s) { return RT::op_bias(s, P1S, HEADS); }
+    static constexpr int n_res(int s) { return RT::op_res(s, P1S, HEADS); }
+    static constexpr int n_st(int s) { return RT::op_st(s, P1S, HEADS); }
     static constexpr int prev(int s) { return s == 0 ? NSTEP - 1 : s - 1; }
     static constexpr int younger(int s) { return xp(prev(s)) + n_st(prev(s)) + n_bq(s) + n_bias(s) + n_res(s); }
     // DMA pieces (two per wave and unit) + other instructions that may still be in flight when step s waits for the
     // units of step s+1
     static constexpr int inflight(int s) { return 2 * (hm(s - 1) - ub(s + 2)) + younger(s); }
 
-
-    struct Frag {
-        f16x8 w[8], x[3];
-    };
     struct State {
         Frag fa, fb;
         f32x4 aq[3][4], ak[3][4], av[3][4];      // q^T, k^T: [d][row]; v: [row][d]
@@ -245,30 +165,19 @@ struct K7B {
     };
 
     const K7BP& p;
-    char* smem;
-    lchar* lds;                                  // the same, as an LDS pointer
-    int lane, n16, q4, wave;
     // order in which this tile / the next tile walks the heads: rotated by the tile's position INSIDE its batch item.
     // Why rotate at all: see tattn_fused.hip (workgroups that share an XCD would otherwise ask for the same weight lines at
     // the same time and then not again for a whole tile).  Why by that position: the output projection sums the heads in
     // walking order, so the order must be a function of the data alone — a sample's result then has the same bits
     // wherever it sits in the batch, whatever the grid (tests/test_unet_gpu.py: batch independence).
     int rot, rotn;
-    int woffb, xb[2];                            // LDS byte addresses: weight fragment base, row-image fragment bases (k step parity)
     int tb, tg, tbn, tgn;                        // this wave's (batch item, row group inside it) in this tile / the next tile
     int qpix[3], kpix[3][F4 ? 1 : 4];
 #ifdef K7B_STAMPS
     unsigned long long tsum[16], tlast;
 #endif
 
-    __device__ __forceinline__ K7B(const K7BP& p_, char* s) : p(p_), smem(s), lds((lchar*)s) {}
-
-    // a value the optimiser cannot see through: loads addressed with it are neither hoisted out of the tile loop nor
-    // merged — every source-level load below is exactly one instruction per tile (the wait counts rely on it)
-    __device__ static __forceinline__ int opaque(int v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    }
+    __device__ __forceinline__ K7B(const K7BP& p_, char* s) : RT(s), p(p_) {}
 
     // ---- weight stream
     template <int U>
@@ -295,22 +204,12 @@ struct K7B {
             }
         }
     }
-    template <int U>
-    __device__ __forceinline__ void issue_unit() {
+    template <int U0, int U1>
+    __device__ __forceinline__ void issue_range() {
 #ifdef K7B_ABL_NOWDMA      /* diagnostic builds (timing only, wrong results): what each part of the tile costs */
         return;
 #endif
-        const char* src = unit_src<U>() + (2 * wave) * 1024 + lane * 16;
-        char* dst = smem + XB + (U % NU) * UB + (2 * wave) * 1024;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024), (lptr_t)(dst + 1024), 16, 0, 0);
-    }
-    template <int U0, int U1>
-    __device__ __forceinline__ void issue_range() {
-        if constexpr (U0 < U1) {
-            issue_unit<U0>();
-            issue_range<U0 + 1, U1>();
-        }
+        RT::template issue_range<U0, U1>([this](auto u) { return unit_src<decltype(u)::value>(); });
     }
 
     // global row index of local row r (0..47) of row group g4 of batch item b (clamped to row 0 when it does not exist)
@@ -323,85 +222,22 @@ struct K7B {
         return ok;
     }
 
-    // ---- The row image.  LDS layout: [row block of 8 rows][column block of 64 channels][8 rows][128 bytes]; inside the
-    // 128 bytes of a row the 16-byte chunk c sits at position c ^ (row & 7).  A (row block, column block) is 1 KB = one
-    // LDS-DMA piece whose lane L carries row L >> 3, position L & 7: the per-lane SOURCE address does the row gather (a
-    // row's frames are S rows apart) and the XOR; the column block is an immediate offset.  For the MFMA fragment reads
-    // (16 rows x 16 bytes per lane quad) the XOR makes every ds_read_b128 lane group hit 16 distinct slots of the
-    // 256-byte bank row; the in-place normalisation reads and writes whole pieces.
-    //
-    // rows of row group g4, pass PS (its 8 rows) -> the wave's part of the image, by LDS-DMA.  Rows that do not exist
-    // read the zero page (their values must stay finite: a masked key still multiplies a zero probability).
+    // ---- the row image (rowtile_common.h): rows of row group g4, pass PS -> the wave's part of the image; P0 in place
     template <int PS>
     __device__ __forceinline__ void issue_rows(int b, int g4) {
 #ifdef K7B_ABL_NOROWS
         return;
 #endif
-        const int r = 8 * PS + (lane >> 3);
         long long gr;
-        const bool ok = grow_of(b, g4, r, gr);
-        const char* rowp = (const char*)(p.t + gr * p.ldt) + (((lane & 7) ^ (lane >> 3)) << 4);
-        const char* zp = (const char*)g_zero_page;
-        const char* src = ok ? rowp : zp;
-        const int cstep = ok ? 128 : 0;
-        char* dst = smem + (wave * 6 + PS) * RBB;
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + cb * cstep), (lptr_t)(dst + cb * 1024), 16, 0, 0);
+        const bool ok = grow_of(b, g4, 8 * PS + (lane >> 3), gr);
+        RT::template issue_rows<PS>((const char*)(p.t + gr * p.ldt), ok);
     }
-    // P0 of pass PS, in place: centre and scale the 8 rows (8 lanes per row, one chunk of every column block per lane).
-    // fp32 statistics: the mean from the row sum, the variance from the squares of (x - mean_h) with mean_h the mean
-    // rounded to fp16 (the differences are then exact to fp16 relative precision, whatever the mean) corrected by
-    // (mean - mean_h)^2; the result x * rstd - mean * rstd is formed in fp32 and rounded once.  gamma / beta live in
-    // the weights.
-    template <int PS>
-    __device__ __forceinline__ void p0_pass() {
+    template <int MASK>
+    __device__ __forceinline__ void p0_passes() {
 #ifdef K7B_ABL_NOROWS
         return;
 #endif
-        lchar* base = lds + (wave * 6 + PS) * RBB + lane * 16;
-        f16x8 v[NCB];
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) v[j] = *(const lf16x8*)(base + 1024 * j);
-        const f16x2 ones = (f16x2){(f16)1.f, (f16)1.f};
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum = __builtin_amdgcn_fdot2((f16x2){v[j][2 * e], v[j][2 * e + 1]}, ones, sum, false);
-        sum = dpp_add8(sum);
-        const float mean = sum * (1.0f / INNER);
-        const f16 mh = (f16)mean;
-        const float dm = mean - (float)mh;
-        const f16x2 nm = (f16x2){(f16)-mh, (f16)-mh};
-        float ss = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const f16x2 d = (f16x2){v[j][2 * e], v[j][2 * e + 1]} + nm;
-                ss = __builtin_amdgcn_fdot2(d, d, ss, false);
-            }
-        ss = dpp_add8(ss);
-        const float var = fmaxf(ss * (1.0f / INNER) - dm * dm, 0.f);
-        const float rstd = rsqrtf(var + p.eps);
-        const float nmr = -mean * rstd;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) {
-            f16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf((float)v[j][e], rstd, nmr);
-            *(lf16x8*)(base + 1024 * j) = o;
-        }
-    }
-
-    // row-image fragment: row 16*i + n16 of the wave's group, chunk 4*ks + q4: row block 2i + (n16 >> 3), column block
-    // ks >> 1, position (4*(ks & 1) + q4) ^ (n16 & 7): xb[ks & 1] + a constant
-    __device__ __forceinline__ f16x8 xfrag(int i, int ks) const {
-        return *(const lf16x8*)(lds + xb[ks & 1] + (2 * i * RBB + 1024 * (ks >> 1)));
-    }
-    __device__ __forceinline__ f16x8 wfrag(int unit, int tile) const {
-        return *(const lf16x8*)(lds + woffb + ((unit % NU) * UB + tile * 1024));
+        RT::template p0_passes<MASK>(p.eps);
     }
 
     // fragments of half KK (one MFMA k step) of step S (S may be NSTEP: step 0 of the next tile)
@@ -425,14 +261,7 @@ struct K7B {
 #pragma unroll
             for (int i = 0; i < 3; ++i) f.x[i] = xfrag(i, 2 * m + KK);
         } else {
-            constexpr int c = (S - P1S) / HEADS;
-            if constexpr (c < NCGF) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f.w[j] = wfrag(u0 + KK, j);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) f.w[j] = wfrag(u0, 4 * KK + j);
-            }
+            RT::template read_out_half<(S - P1S) / HEADS, KK>(f, u0);
         }
     }
 
@@ -459,25 +288,9 @@ struct K7B {
                     st.av[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.x[i], f.w[j], Z ? zero4 : st.av[i][j], 0, 0, 0);
         } else {
             constexpr int v = S - P1S, c = v / HEADS, hs = v % HEADS;
-            constexpr bool Z = hs == 0 && KK == 0;
-            constexpr int NT = nt_of(c);
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    st.acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[j], st.oh[hs][i][KK], Z ? st.bv[j] : st.acc[i][j], 0, 0, 0);
+            RT::template mma_out<c, hs == 0 && KK == 0>(st.acc, f, st.oh[hs][0][KK], st.oh[hs][1][KK], st.oh[hs][2][KK], st.bv);
         }
-        // issue order (a compile-time directive): one memory instruction after every MFMA until they are used up
-#pragma unroll
-        for (int g = 0; g < NVM; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < NDS; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
+        RT::template pin_after_mfma<NVM, NDS>();
     }
 
     static constexpr int nds(int s_) {
@@ -528,7 +341,7 @@ struct K7B {
                 mx = fmaxf(mx, sc[kt][e]);
             }
         }
-        mx = quad_max(mx);
+        mx = k7b_quad_max(mx);
         float rs = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 3; ++kt) {
@@ -539,7 +352,7 @@ struct K7B {
                 rs += sc[kt][e];
             }
         }
-        rs = quad_sum(rs);
+        rs = k7b_quad_sum(rs);
         const float inv = 1.0f / rs;
 #pragma unroll
         for (int kt = 0; kt < 3; ++kt) {
@@ -593,50 +406,24 @@ struct K7B {
 #pragma unroll
         for (int j = 0; j < 4; ++j) st.bqv[j] = *(const gf32x4*)((const __attribute__((address_space(1))) float*)p.bq + o + 16 * j);
     }
-    // output bias of column group C: the initial accumulator of the projection (tile 2a + jj, register e: column
-    // 32a + 8*q4 + 4*jj + e of the group)
+    // output bias / residual rows / epilogue of column group C (rowtile_common.h)
     template <int C>
-    __device__ __forceinline__ void load_bias(State& st) {
-        const int o = opaque(C * 128 + 8 * q4);
-#pragma unroll
-        for (int j = 0; j < nt_of(C); ++j) st.bv[j] = *(const gf32x4*)((const __attribute__((address_space(1))) float*)p.bo2 + o + 32 * (j / 2) + 4 * (j % 2));
-    }
-    // residual rows of column group C: requested at the top of the group's second K step (HBM latency), consumed after it
+    __device__ __forceinline__ void load_bias(State& st) { RT::template load_bias<C>(st.bv, p.bo2); }
     template <int C>
     __device__ __forceinline__ void load_residual(State& st) {
 #ifdef K7B_ABL_NOEPI
         for (int i = 0; i < 3; ++i) for (int a = 0; a < 4; ++a) st.rv[i][a] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
         return;
 #endif
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const gf16* src = st.resp[i] + opaque(0);
-#pragma unroll
-            for (int a = 0; a < nt_of(C) / 2; ++a) st.rv[i][a] = *(const gf16x8*)(src + C * 128 + 32 * a);
-        }
+        RT::template load_residual<C>(st.rv, st.resp);
     }
-    // tile pair (2a, 2a+1) gives this lane 8 consecutive columns 32a + 8*q4 .. +7 of row n16 (+16i).  The projection
-    // (bias included: it was the initial accumulator) is rounded to fp16 and the residual added in fp16 — the
-    // reference's order (to_out returns fp16, `attn_output + hidden_states` is an fp16 add).
     template <int C>
     __device__ __forceinline__ void epilogue(State& st) {
 #ifdef K7B_ABL_NOEPI
         for (int a = 0; a < nt_of(C); ++a) for (int i = 0; i < 3; ++i) asm volatile("" ::"v"(st.acc[i][a]));
         return;
 #endif
-#pragma unroll
-        for (int a = 0; a < nt_of(C) / 2; ++a)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = (f16)st.acc[i][2 * a][e];
-                    o[4 + e] = (f16)st.acc[i][2 * a + 1][e];
-                }
-                o = o + st.rv[i][a];
-                *(gf16x8*)(st.outp[i] + C * 128 + 32 * a) = o;
-            }
+        RT::template epilogue<C>(st.acc, st.rv, st.outp);
     }
 
     // ---- one step of the tile.  At its top the fragments of its first half are in registers (st.fa).
@@ -649,7 +436,7 @@ struct K7B {
         if constexpr (n_res(S) > 0) load_residual<(S - P1S) / HEADS>(st);
         // vector work that rides on this step's MFMAs: the scores of the head (v steps 0..2), the next tile's rows
         if constexpr (kd == 1 && S % HSTEPS - KM < 3) attn_scores<S % HSTEPS - KM>(st);
-        p0_passes<p0_mask_of(S)>(std::make_integer_sequence<int, NPS>{});
+        p0_passes<p0_mask_of(S)>();
         // second half's fragments behind the first half's MFMAs
         read_half<S, 1>(st.fb);
         mma_half<S, 0, nds(S), 0>(st, st.fa);
@@ -682,25 +469,15 @@ struct K7B {
     __device__ __forceinline__ void steps(State& st, std::integer_sequence<int, S...>) {
         (step<S>(st), ...);
     }
-    template <int MASK, int... PS>
-    __device__ __forceinline__ void p0_passes(std::integer_sequence<int, PS...>) {
-        ((MASK >> PS & 1 ? p0_pass<PS>() : void()), ...);
-    }
     template <int... PS>
     __device__ __forceinline__ void first_rows(std::integer_sequence<int, PS...>) {
         (issue_rows<PS>(tb, tg), ...);
         wait_vm<0>();
-        (p0_pass<PS>(), ...);
+        p0_passes<(1 << NPS) - 1>();
     }
 
     __device__ __forceinline__ void set_lane_constants() {
-        n16 = lane & 15;
-        q4 = lane >> 4;
-        const int g = (0x1320 >> (4 * (n16 >> 2))) & 3;          // g = [0, 2, 3, 1][n >> 2]
-        woffb = XB + n16 * 64 + ((q4 ^ g) << 4);
-        const int rr = n16 & 7, xrow = (wave * 6 + (n16 >> 3)) * RBB + rr * 128;
-        xb[0] = xrow + ((q4 ^ rr) << 4);
-        xb[1] = xrow + (((4 + q4) ^ rr) << 4);
+        RT::set_lane_constants();
         // pixel of my query rows / key rows inside the 48-row group (for the block-diagonal mask)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -818,22 +595,13 @@ extern "C" int vdx_temporal_attn_block2_f16(const void* t, int ldt, const void* 
     p.ntiles = B * p.tps;
     p.fmagic = (65536 + F - 1) / F;
     p.eps = eps;
-    constexpr int lds = T::XB + T::NU * T::UB;
+    constexpr int lds = T::LDS_BYTES;
     void (*kern)(const K7BP) = F == 24 ? tattn2_kernel<320, 24> : F == 16 ? tattn2_kernel<320, 16> : F == 12 ? tattn2_kernel<320, 12>
                                : F % 4 == 0 ? tattn2_kernel<320, 4> : tattn2_kernel<320, 1>;
-    static const hipError_t attr_rc = [] {
-        hipError_t e = hipSuccess;
-        for (auto k : {tattn2_kernel<320, 24>, tattn2_kernel<320, 16>, tattn2_kernel<320, 12>, tattn2_kernel<320, 4>, tattn2_kernel<320, 1>}) {
-            const hipError_t r = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (r != hipSuccess) e = r;
-        }
-        return e;
-    }();
+    static const hipError_t attr_rc = vdx_reserve_lds(lds, tattn2_kernel<320, 24>, tattn2_kernel<320, 16>, tattn2_kernel<320, 12>,
+                                                      tattn2_kernel<320, 4>, tattn2_kernel<320, 1>);
     if (attr_rc != hipSuccess) return vdx_fail("temporal_attn_block2: cannot reserve %d bytes of LDS", lds);
-    // persistent grid: every workgroup walks the same number of tiles (+-1), one workgroup per CU at most
-    const int ncu = vdx_grid_cus();
-    const int rounds = (p.ntiles + ncu - 1) / ncu;
-    const int grid = (p.ntiles + rounds - 1) / rounds;
+    const int grid = vdx_persistent_grid(p.ntiles);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
     return vdx_launch_status("vdx_temporal_attn_block2_f16");
 }

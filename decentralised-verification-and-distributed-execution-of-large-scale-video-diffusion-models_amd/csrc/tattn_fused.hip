@@ -25,7 +25,7 @@
 //   inner 320 (levels 0): NRG 4, NCH 1 — 192 rows per block, 12 KB stages, 3-deep ring
 //   inner 512 (transformer_in): NRG 2, NCH 2 — 96 rows per block, 24 KB stages, 2-deep ring
 // F must divide 48 (the BASELINE chunks: 24, 16, 12; also 8, 6, 4, 3, 2, 1); other shapes take the un-fused kernels.
-#include "vdx_common.h"
+#include "rowtile_common.h"
 
 #ifdef VDX_STAMPS   // diagnostic build only (make stamps): per-block phase cycle totals of one wave; never in the product library
 static __device__ unsigned long long g_k7_stamps[4096 * 8];
@@ -59,27 +59,14 @@ extern "C" int vdx_debug_read_k7_stamps(void* dst) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     /* DS read */                    \
     }
 #ifdef K7_DBG_XBAR
-#define K7_DBG_STEP_END { __builtin_amdgcn_s_waitcnt(0xC07F); k7_barrier(); }
+#define K7_DBG_STEP_END { __builtin_amdgcn_s_waitcnt(0xC07F); wg_barrier(); }
 #else
 #define K7_DBG_STEP_END
 #endif
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// workgroup barrier that the COMPILER also treats as a memory barrier: LLVM models the s_barrier builtin as touching no
-// memory, so LDS reads of a stage could be scheduled above the barrier that publishes it (seen: corrupted rows).
-__device__ __forceinline__ void k7_barrier() {
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// (address-space typedefs, wg_barrier and wait_vm: rowtile_common.h)
 
 struct K7P {
     const f16* t;        // [M][ldt] rows, row = (b*F + f)*S + p
@@ -159,12 +146,12 @@ struct K7 {
         // above the previous step's register-only MFMAs, i.e. the wave waited for its fragment reads before multiplying)
         __builtin_amdgcn_sched_barrier(0);
 #ifdef K7_DBG_VM0
-        wait_vmcnt<0>();
+        wait_vm<0>();
 #else
         if (NS == 3) {
-            if (s + 2 < NST) wait_vmcnt<PPW>(); else wait_vmcnt<0>();     // (stage s+2 may still be in flight)
+            if (s + 2 < NST) wait_vm<PPW>(); else wait_vm<0>();     // (stage s+2 may still be in flight)
         } else {
-            wait_vmcnt<0>();
+            wait_vm<0>();
         }
 #endif
         // my LDS accesses are done before I signal.  The BUILTIN form: the compiler's wait-count pass sees it and knows
@@ -175,7 +162,7 @@ struct K7 {
 #ifdef VDX_STAMPS
         const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
 #endif
-        k7_barrier();
+        wg_barrier();
 #ifdef VDX_STAMPS
         const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -340,9 +327,9 @@ struct K7 {
             }
         need = __builtin_amdgcn_readfirstlane(need);
         // stage 0 has landed for everyone (and X is complete): its fragments open the pipeline
-        if (NS == 3) wait_vmcnt<2 * PPW>(); else wait_vmcnt<PPW>();
+        if (NS == 3) wait_vm<2 * PPW>(); else wait_vm<PPW>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        k7_barrier();
+        wg_barrier();
         const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
         Frags fa, fb;
         read_w<12>(fa, 0);
@@ -461,7 +448,7 @@ struct K7 {
         }
 
         // ---- P2: the heads' outputs replace X (same image: row-major, swizzled 16-byte chunks)
-        k7_barrier();            // every wave is past its last read of X
+        wg_barrier();            // every wave is past its last read of X
 #pragma unroll
         for (int hg = 0; hg < NHG; ++hg) {
             const int head = ((hg + rot) % NHG) * NCH + ch;      // (ohead is indexed by time; the head it holds is rotated)
@@ -478,7 +465,7 @@ struct K7 {
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        k7_barrier();            // O is complete in LDS
+        wg_barrier();            // O is complete in LDS
         read_x(fa, 0);                           // (fa already holds the weight fragments of the first P3 stage)
         K7_T(4)
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
 #include "../../include/vdx.h"
 
 typedef _Float16 f16;
@@ -53,6 +54,23 @@ extern int g_vdx_reserved_cus;
 static inline int vdx_grid_cus() {
     int n = (vdx_num_cus() - g_vdx_reserved_cus) & ~7;
     return n < 8 ? 8 : n;
+}
+// blocks of a persistent grid over ntiles tiles: every workgroup walks the same number of tiles ±1, at most one per CU of
+// `vdx_grid_cus()`
+static inline int vdx_persistent_grid(int ntiles) {
+    const int ncu = vdx_grid_cus();
+    const int rounds = (ntiles + ncu - 1) / ncu;
+    return (ntiles + rounds - 1) / rounds;
+}
+// dynamic LDS above the default limit, for every instantiation a launcher may pick; meant for a function-local static (once)
+template <class... K>
+static inline hipError_t vdx_reserve_lds(int lds, K... kernels) {
+    hipError_t e = hipSuccess;
+    for (const void* k : {(const void*)kernels...}) {
+        const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (r != hipSuccess) e = r;
+    }
+    return e;
 }
 
 // ---- device helpers ---------------------------------------------------------------------

@@ -4,8 +4,8 @@
 //     t' = t + to_out( softmax( q K^T / 8 ) V ),   q = LayerNorm(t) . W_q^T,   K, V = the sample's text keys / values (77 x inner)
 //
 // Un-fused this is LayerNorm, a q GEMM, the flash kernel on 77 keys and an output GEMM + residual: four round trips of a
-// [442 368][320] tensor per block.  Here a row is read once and written once.  The kernel is tattn2.hip's machinery (K7,
-// second design) with the roles changed:
+// [442 368][320] tensor per block.  Here a row is read once and written once.  The kernel is rowtile_common.h's machinery
+// — the one tattn2.hip (K7, second design) is built on — with the roles changed:
 //   * rows: 192 consecutive rows per tile (4 waves x 48), never straddling two batch items; centred / scaled in LDS,
 //     LayerNorm's affine and the softmax scale folded into W_q on the host (packing.pack_k5);
 //   * per head: five K-64 steps project q (24 MFMAs each), then ONE attention step: the head's text keys and values — 80
@@ -13,32 +13,12 @@
 //     the same weight ring; the scores S^T = K q^T (key on the registers, query on the lane), the softmax over the 80 slots
 //     (slots >= kv_len masked) and O^T = V^T P^T run in registers; O^T is the B operand of the output projection as it
 //     stands (tattn2's permuted W_o);
-//   * the output projection, bias, residual, epilogue, the prefetch of the next tile's rows behind the projection, the
-//     5-unit weight ring and the counted s_waitcnt scheme are tattn2's (see the comments there).
+//   * the output projection, bias, residual, epilogue, the prefetch of the next tile's rows behind the projection and the
+//     5-unit weight ring are rowtile_common.h's; the counted s_waitcnt scheme is tattn2's (see the comments there).
 // Built for inner 320 (level 0: 5 cross-attentions per forward).
-#include "vdx_common.h"
-#include <utility>
+#include "rowtile_common.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) char lchar;
-typedef __attribute__((address_space(3))) f16x8 lf16x8;
-typedef __attribute__((address_space(3))) f16x4 lf16x4;
-typedef __attribute__((address_space(1))) f16 gf16;
-typedef __attribute__((address_space(1))) f16x8 gf16x8;
-typedef __attribute__((address_space(1))) f32x4 gf32x4;
-
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 struct K5P {
     const f16* t;        // [M][ldt] rows
@@ -56,59 +36,22 @@ struct K5P {
     float eps;
 };
 
-static __device__ __attribute__((aligned(16))) u32x4 g_dump_page5[64 + 64];
-
-__device__ __forceinline__ float dpp_add8(float v) {        // sum over the 8 lanes that share a row (lane & ~7)
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    return v;
-}
-// value of lanes l, l^16, l^32, l^48 combined (the four lane quads that hold one query's keys): see tattn2.hip
-__device__ __forceinline__ void swap16(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void swap32(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ float quad_max(float v) {
-    float a = v, b = v;
-    swap16(a, b);
-    a = fmaxf(a, b);
-    b = a;
-    swap32(a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    float a = v, b = v;
-    swap16(a, b);
-    a = a + b;
-    b = a;
-    swap32(a, b);
-    return a + b;
-}
-
 template <int INNER>
-struct K5 {
+struct K5 : RowTile<INNER> {
+    typedef RowTile<INNER> RT;
+    using RT::XB, RT::UB, RT::NU, RT::NPS, RT::NCGF, RT::NCG, RT::ROWS, RT::nt_of, RT::opaque;
+    using RT::lds, RT::lane, RT::n16, RT::q4, RT::wave, RT::wfrag, RT::xfrag;
+    using typename RT::Frag;
     static constexpr int KS = INNER / 32;                 // MFMA k steps over the model width
     static constexpr int HEADS = INNER / 64;
     static constexpr int KM = KS / 2;                     // K-64 steps over the model width
-    static constexpr int ROWS = 192;
-    static constexpr int RB = INNER * 2;                  // bytes of one row of the image
-    static constexpr int XB = ROWS * RB;
-    static constexpr int UB = 8192, NU = 5;               // ring: NU units of UB bytes
     static constexpr int KVU = 3;                         // units of one head's keys + values
     static constexpr int KT = 5;                          // key tiles of 16 slots
     static constexpr int HSTEPS = KM + 1;                 // steps of one head: KM of q, one of attention
     static constexpr int P1S = HEADS * HSTEPS;
-    static constexpr int NCGF = INNER / 128;              // full 128-column groups of the output projection
-    static constexpr int NCG = (INNER + 127) / 128;
     static constexpr int NSTEP = P1S + NCG * HEADS;       // the output projection contracts head by head (K = 64)
     static constexpr int UPH = KM + KVU;                  // units of one head in the stream
-    static constexpr int NPS = 6;                         // P0 passes of 8 rows
-    static constexpr int PPP = 8 * RB / 1024;             // DMA pieces per pass
-    static_assert(KS % 2 == 0 && (INNER % 128 == 0 || INNER % 128 == 64), "geometry");
-    static_assert(XB + NU * UB <= 160 * 1024, "LDS budget");
-    static constexpr int NCB = INNER / 64;                // column blocks of 64 channels (= PPP: one DMA piece each)
-    static constexpr int RBB = NCB * 1024;                // bytes of one row block (8 rows)
-    static_assert(PPP == NCB && XB == 24 * RBB, "a DMA piece is one (row block, column block): 8 rows x 128 bytes");
-    static_assert(NCG == 3 && NPS == 6 && HEADS == 5, "the row prefetch schedule below is written for three column groups of five steps");
+    static_assert(KS % 2 == 0, "geometry");
     static_assert(KVU <= NU && 2 * KT * 4 * 512 <= KVU * UB, "a head's keys and values must fit its units and the ring");
 
     // ---- the static schedule of a tile (tattn2.hip): step s consumes units [ub(s), ub(s+1)) of the weight stream
@@ -125,34 +68,19 @@ struct K5 {
     static_assert(ub1(HSTEPS) == UPH && ub1(KM + 1) - ub1(KM) == KVU, "the attention step owns the head's KVU units");
 
     // ---- every vector-memory instruction a wave issues, in order (tattn2.hip): the step's s_waitcnt vmcnt(N) is exact
+    // (the output projection and the row prefetch behind it: rowtile_common.h, groups of HEADS steps from step P1S)
     static constexpr int RS0 = P1S + HEADS;
-    static constexpr int xp(int s) { return s == RS0 || s == RS0 + 1 ? 3 * PPP : 0; }               // row pieces issued in step s
-    static constexpr int p0_mask_of(int s) {
-        return s == RS0 + 3 ? 0x03 : s == RS0 + 5 ? 0x04 : s == RS0 + 6 ? 0x08 : s == RS0 + 7 ? 0x10 : s == RS0 + 8 ? 0x20 : 0;
-    }
-    static constexpr int nt_of(int c) { return c < NCGF ? 8 : 4; }
-    static constexpr int first_of(int c) { return P1S + c * HEADS; }
+    static constexpr int xp(int s) { return RT::op_xp(s, P1S, HEADS); }
+    static constexpr int p0_mask_of(int s) { return RT::op_p0_mask(s, P1S, HEADS); }
     // q bias of the next head: loaded at the top of the head's attention step (its q accumulators are dead by then)
     static constexpr int n_bq(int s) { return kind(s) == 1 && s + 1 < P1S ? 4 : (s == NSTEP - 1 ? 4 : 0); }
-    static constexpr int n_bias(int s) {
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) - 1) return nt_of(c);
-        return 0;
-    }
-    static constexpr int n_res(int s) {
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) + 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
-    static constexpr int n_st(int s) {
-        for (int c = 0; c < NCG; ++c) if (s == first_of(c) + HEADS - 1) return 3 * nt_of(c) / 2;
-        return 0;
-    }
+    static constexpr int n_bias(int s) { return RT::op_bias(s, P1S, HEADS); }
+    static constexpr int n_res(int s) { return RT::op_res(s, P1S, HEADS); }
+    static constexpr int n_st(int s) { return RT::op_st(s, P1S, HEADS); }
     static constexpr int prev(int s) { return s == 0 ? NSTEP - 1 : s - 1; }
     static constexpr int younger(int s) { return xp(prev(s)) + n_st(prev(s)) + n_bq(s) + n_bias(s) + n_res(s); }
     static constexpr int inflight(int s) { return 2 * (hm(s - 1) - ub(s + 2)) + younger(s); }
 
-    struct Frag {
-        f16x8 w[8], x[3];
-    };
     struct State {
         Frag fa, fb;
         f32x4 aq[3][4];                          // q^T: [d][row]
@@ -169,20 +97,11 @@ struct K5 {
     };
 
     const K5P& p;
-    char* smem;
-    lchar* lds;
-    int lane, n16, q4, wave;
     int rot, rotn;                               // head walking order of this / the next tile (tattn2.hip: a function of the tile's position in its item)
-    int woffb, xb[2];
     int kvoff;                                   // LDS byte offset of this lane inside a fragment block: lane * 8
     int tb, tg, tbn, tgn;                        // this wave's (batch item, 48-row group inside it) in this tile / the next tile
 
-    __device__ __forceinline__ K5(const K5P& p_, char* s) : p(p_), smem(s), lds((lchar*)s) {}
-
-    __device__ static __forceinline__ int opaque(int v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    }
+    __device__ __forceinline__ K5(const K5P& p_, char* s) : RT(s), p(p_) {}
 
     // ---- weight stream
     template <int U>
@@ -215,19 +134,9 @@ struct K5 {
             }
         }
     }
-    template <int U>
-    __device__ __forceinline__ void issue_unit() {
-        const char* src = unit_src<U>() + (2 * wave) * 1024 + lane * 16;
-        char* dst = smem + XB + (U % NU) * UB + (2 * wave) * 1024;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024), (lptr_t)(dst + 1024), 16, 0, 0);
-    }
     template <int U0, int U1>
     __device__ __forceinline__ void issue_range() {
-        if constexpr (U0 < U1) {
-            issue_unit<U0>();
-            issue_range<U0 + 1, U1>();
-        }
+        RT::template issue_range<U0, U1>([this](auto u) { return unit_src<decltype(u)::value>(); });
     }
 
     // global row index of local row r (0..47) of row group g4 of batch item b and whether it exists
@@ -238,64 +147,12 @@ struct K5 {
         return ok;
     }
 
-    // ---- the row image (tattn2.hip's layout)
+    // ---- the row image (rowtile_common.h)
     template <int PS>
     __device__ __forceinline__ void issue_rows(int b, int g4) {
-        const int r = 8 * PS + (lane >> 3);
         long long gr;
-        const bool ok = grow_of(b, g4, r, gr);
-        const char* rowp = (const char*)(p.t + gr * p.ldt) + (((lane & 7) ^ (lane >> 3)) << 4);
-        const char* zp = (const char*)g_zero_page;
-        const char* src = ok ? rowp : zp;
-        const int cstep = ok ? 128 : 0;
-        char* dst = smem + (wave * 6 + PS) * RBB;
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + cb * cstep), (lptr_t)(dst + cb * 1024), 16, 0, 0);
-    }
-    template <int PS>
-    __device__ __forceinline__ void p0_pass() {
-        lchar* base = lds + (wave * 6 + PS) * RBB + lane * 16;
-        f16x8 v[NCB];
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) v[j] = *(const lf16x8*)(base + 1024 * j);
-        const f16x2 ones = (f16x2){(f16)1.f, (f16)1.f};
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum = __builtin_amdgcn_fdot2((f16x2){v[j][2 * e], v[j][2 * e + 1]}, ones, sum, false);
-        sum = dpp_add8(sum);
-        const float mean = sum * (1.0f / INNER);
-        const f16 mh = (f16)mean;
-        const float dm = mean - (float)mh;
-        const f16x2 nm = (f16x2){(f16)-mh, (f16)-mh};
-        float ss = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const f16x2 d = (f16x2){v[j][2 * e], v[j][2 * e + 1]} + nm;
-                ss = __builtin_amdgcn_fdot2(d, d, ss, false);
-            }
-        ss = dpp_add8(ss);
-        const float var = fmaxf(ss * (1.0f / INNER) - dm * dm, 0.f);
-        const float rstd = rsqrtf(var + p.eps);
-        const float nmr = -mean * rstd;
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) {
-            f16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf((float)v[j][e], rstd, nmr);
-            *(lf16x8*)(base + 1024 * j) = o;
-        }
-    }
-
-    __device__ __forceinline__ f16x8 xfrag(int i, int ks) const {
-        return *(const lf16x8*)(lds + xb[ks & 1] + (2 * i * RBB + 1024 * (ks >> 1)));
-    }
-    __device__ __forceinline__ f16x8 wfrag(int unit, int tile) const {
-        return *(const lf16x8*)(lds + woffb + ((unit % NU) * UB + tile * 1024));
+        const bool ok = grow_of(b, g4, 8 * PS + (lane >> 3), gr);
+        RT::template issue_rows<PS>((const char*)(p.t + gr * p.ldt), ok);
     }
     // fragment block BLK (512 bytes: 64 lanes x 8) of the head whose first K|V unit is U0: byte BLK * 512 of the head's stream
     template <int U0, int BLK>
@@ -316,14 +173,7 @@ struct K5 {
 #pragma unroll
             for (int i = 0; i < 3; ++i) f.x[i] = xfrag(i, 2 * m + KK);
         } else if constexpr (kd == 2) {
-            constexpr int c = (S - P1S) / HEADS;
-            if constexpr (c < NCGF) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f.w[j] = wfrag(u0 + KK, j);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) f.w[j] = wfrag(u0, 4 * KK + j);
-            }
+            RT::template read_out_half<(S - P1S) / HEADS, KK>(f, u0);
         }
     }
 
@@ -340,26 +190,9 @@ struct K5 {
                     st.aq[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[j], f.x[i], Z ? st.bqv[j] : st.aq[i][j], 0, 0, 0);
         } else if constexpr (kd == 2) {
             constexpr int v = S - P1S, c = v / HEADS, hs = v % HEADS;
-            constexpr bool Z = hs == 0 && KK == 0;
-            constexpr int NT = nt_of(c);
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    st.acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[j], st.oh[hs][i][KK], Z ? st.bv[j] : st.acc[i][j], 0, 0, 0);
+            RT::template mma_out<c, hs == 0 && KK == 0>(st.acc, f, st.oh[hs][0][KK], st.oh[hs][1][KK], st.oh[hs][2][KK], st.bv);
         }
-        if constexpr (kd != 1) {
-#pragma unroll
-            for (int g = 0; g < NVM; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-#pragma unroll
-            for (int g = 0; g < NDS; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-        }
+        if constexpr (kd != 1) RT::template pin_after_mfma<NVM, NDS>();
     }
     static constexpr int nds(int s_) {
         const int s = s_ % NSTEP;
@@ -463,36 +296,11 @@ struct K5 {
         for (int j = 0; j < 4; ++j) st.bqv[j] = *(const gf32x4*)((const __attribute__((address_space(1))) float*)p.bq + o + 16 * j);
     }
     template <int C>
-    __device__ __forceinline__ void load_bias(State& st) {
-        const int o = opaque(C * 128 + 8 * q4);
-#pragma unroll
-        for (int j = 0; j < nt_of(C); ++j) st.bv[j] = *(const gf32x4*)((const __attribute__((address_space(1))) float*)p.bo2 + o + 32 * (j / 2) + 4 * (j % 2));
-    }
+    __device__ __forceinline__ void load_bias(State& st) { RT::template load_bias<C>(st.bv, p.bo2); }
     template <int C>
-    __device__ __forceinline__ void load_residual(State& st) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const gf16* src = st.resp[i] + opaque(0);
-#pragma unroll
-            for (int a = 0; a < nt_of(C) / 2; ++a) st.rv[i][a] = *(const gf16x8*)(src + C * 128 + 32 * a);
-        }
-    }
+    __device__ __forceinline__ void load_residual(State& st) { RT::template load_residual<C>(st.rv, st.resp); }
     template <int C>
-    __device__ __forceinline__ void epilogue(State& st) {
-#pragma unroll
-        for (int a = 0; a < nt_of(C) / 2; ++a)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = (f16)st.acc[i][2 * a][e];
-                    o[4 + e] = (f16)st.acc[i][2 * a + 1][e];
-                }
-                o = o + st.rv[i][a];
-                *(gf16x8*)(st.outp[i] + C * 128 + 32 * a) = o;
-            }
-    }
+    __device__ __forceinline__ void epilogue(State& st) { RT::template epilogue<C>(st.acc, st.rv, st.outp); }
 
     // ---- one step of the tile.  At its top the fragments of its first half are in registers (st.fa).
     template <int S>
@@ -501,7 +309,7 @@ struct K5 {
         if constexpr (n_bq(S) > 0) load_bq<(S == NSTEP - 1 ? 0 : S / HSTEPS + 1), S == NSTEP - 1>(st);
         if constexpr (n_bias(S) > 0) load_bias<(S + 1 - P1S) / HEADS>(st);
         if constexpr (n_res(S) > 0) load_residual<(S - P1S) / HEADS>(st);
-        p0_passes<p0_mask_of(S)>(std::make_integer_sequence<int, NPS>{});
+        RT::template p0_passes<p0_mask_of(S)>(p.eps);
         if constexpr (kd == 1) {
             attn_first<S>(st);
         } else {
@@ -533,25 +341,15 @@ struct K5 {
     __device__ __forceinline__ void steps(State& st, std::integer_sequence<int, S...>) {
         (step<S>(st), ...);
     }
-    template <int MASK, int... PS>
-    __device__ __forceinline__ void p0_passes(std::integer_sequence<int, PS...>) {
-        ((MASK >> PS & 1 ? p0_pass<PS>() : void()), ...);
-    }
     template <int... PS>
     __device__ __forceinline__ void first_rows(std::integer_sequence<int, PS...>) {
         (issue_rows<PS>(tb, tg), ...);
         wait_vm<0>();
-        (p0_pass<PS>(), ...);
+        RT::template p0_passes<(1 << NPS) - 1>(p.eps);
     }
 
     __device__ __forceinline__ void set_lane_constants() {
-        n16 = lane & 15;
-        q4 = lane >> 4;
-        const int g = (0x1320 >> (4 * (n16 >> 2))) & 3;          // g = [0, 2, 3, 1][n >> 2]
-        woffb = XB + n16 * 64 + ((q4 ^ g) << 4);
-        const int rr = n16 & 7, xrow = (wave * 6 + (n16 >> 3)) * RBB + rr * 128;
-        xb[0] = xrow + ((q4 ^ rr) << 4);
-        xb[1] = xrow + (((4 + q4) ^ rr) << 4);
+        RT::set_lane_constants();
         kvoff = lane * 8;
     }
 
@@ -591,7 +389,7 @@ struct K5 {
             for (int i = 0; i < 3; ++i) {
                 long long gr;
                 const bool ok = grow_of(tb, tg, 16 * i + n16, gr);
-                gf16* dump = (gf16*)g_dump_page5 + lane * 8;
+                gf16* dump = (gf16*)g_dump_page + lane * 8;
                 const gf16* rp = (const gf16*)p.t + gr * p.ldt + 8 * q4;
                 gf16* op = (gf16*)p.out + gr * p.ldo + 8 * q4;
                 st.resp[i] = ok ? rp : dump;
@@ -655,12 +453,10 @@ extern "C" int vdx_cross_attn_block_f16(const void* t, int ldt, const void* pack
     p.ntiles = n_items * p.tps;
     p.kv_len = kv_len;
     p.eps = eps;
-    constexpr int lds = T::XB + T::NU * T::UB;
-    static const hipError_t attr_rc = hipFuncSetAttribute((const void*)xattn_kernel<320>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    constexpr int lds = T::LDS_BYTES;
+    static const hipError_t attr_rc = vdx_reserve_lds(lds, xattn_kernel<320>);
     if (attr_rc != hipSuccess) return vdx_fail("cross_attn_block: cannot reserve %d bytes of LDS", lds);
-    const int ncu = vdx_grid_cus();
-    const int rounds = (p.ntiles + ncu - 1) / ncu;
-    const int grid = (p.ntiles + rounds - 1) / rounds;
+    const int grid = vdx_persistent_grid(p.ntiles);
     hipLaunchKernelGGL(xattn_kernel<320>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
     return vdx_launch_status("vdx_cross_attn_block_f16");
 }

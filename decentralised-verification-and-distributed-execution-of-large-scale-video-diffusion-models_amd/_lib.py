@@ -117,6 +117,12 @@ SIGNATURES = {
     "vdx_frames_to_conv_in_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "vdx_vae_posterior_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _vp, _sz, _sz, _vp]),
     "vdx_add_noise_f16": (_i, [_vp, _vp, _vp, _f, _f, _sz, _vp]),
+    "vdx_lpips_stem_u8": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
+    "vdx_relu_f16": (_i, [_vp, _vp, _sz, _vp]),
+    "vdx_relu_maxpool_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vdx_im2col_f16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vdx_lpips_distance_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "vdx_frame_stats_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -976,3 +976,87 @@ def add_noise(x0, noise, sqrt_ab: float, sqrt_1mab: float, out=None):
         out = torch.empty_like(x0)
     _launch("vdx_add_noise_f16", _p(x0, "x0"), _p(noise, "noise"), _p(out, "out"), float(sqrt_ab), float(sqrt_1mab), x0.numel())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# MD-VQS: LPIPS-AlexNet and the authenticity gate's frame statistics (InferNet/template/validator/scoring.py:13-67, :269-309;
+# include/vdx.h "MD-VQS"; csrc/mdvqs.hip)
+LPIPS_STEM_OUT, LPIPS_STEM_K, LPIPS_STEM_KPAD = 55, 363, 384
+
+
+def lpips_stem(u8, lut, out=None):
+    """Resized uint8 frames (F, 224, 224, 3), contiguous on the GPU, -> conv1's im2col rows fp16 [F*3025][384] through the
+    fp16 [3][256] table of both affine maps (`vdx.lpips.stem_lut`); see vdx_lpips_stem_u8."""
+    F, H, W = _check_u8_frames(u8, "lpips_stem")
+    if (H, W) != (CLIP_IMAGE, CLIP_IMAGE) or not u8.is_contiguous():
+        raise VdxError(f"lpips_stem: expected contiguous (F, 224, 224, 3) frames, got {tuple(u8.shape)}")
+    if lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != u8.device:
+        raise VdxError("lpips_stem: lut must be contiguous fp16 [3][256] on the frames' device")
+    out, ldo = _out(out, F * LPIPS_STEM_OUT * LPIPS_STEM_OUT, LPIPS_STEM_KPAD, u8, "lpips_stem")
+    _launch("vdx_lpips_stem_u8", u8.data_ptr(), F, _p(lut, "lut"), _p(out, "out"), ldo)
+    return out
+
+
+def relu(x, out=None):
+    """max(x, 0) like torch.relu (vdx_relu_f16); `out=x` runs in place."""
+    if not x.is_contiguous():
+        raise VdxError("relu: x must be contiguous")
+    if out is None:
+        out = torch.empty_like(x)
+    if out.shape != x.shape or not out.is_contiguous():
+        raise VdxError("relu: out must be contiguous and shaped like x")
+    _launch("vdx_relu_f16", _p(x, "x"), _p(out, "out"), x.numel())
+    return out
+
+
+def relu_maxpool(x, *, n_img, H, W, out=None):
+    """Rows x [n_img*H*W][C] are ReLU'd in place; -> rows [n_img*Ho*Wo][C] of MaxPool2d(3, stride 2) over them,
+    Ho = (H - 3) // 2 + 1 (vdx_relu_maxpool_f16)."""
+    r, Cc, ldx = _rows(x, "x")
+    if r < n_img * H * W or H < 3 or W < 3 or Cc % 8:
+        raise VdxError(f"relu_maxpool: x {tuple(x.shape)} does not hold {n_img} images of {H}x{W} (C % 8 == 0, H, W >= 3)")
+    Ho, Wo = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+    out, ldo = _out(out, n_img * Ho * Wo, Cc, x, "relu_maxpool")
+    _launch("vdx_relu_maxpool_f16", _p(x, "x"), ldx, n_img, H, W, Cc, _p(out, "out"), ldo)
+    return out
+
+
+def im2col(x, *, n_img, H, W, k, pad, out=None):
+    """Channels-last rows x [n_img*H*W][C] (C % 64 == 0) -> stride-1 im2col rows [n_img*Ho*Wo][k*k*C], column
+    (ky*k + kx)*C + c, zero outside the image (vdx_im2col_f16)."""
+    r, Cc, ldx = _rows(x, "x")
+    if r < n_img * H * W or Cc % 64 or not (1 <= k <= 11) or not (0 <= pad < k) or H + 2 * pad < k or W + 2 * pad < k:
+        raise VdxError(f"im2col: x {tuple(x.shape)}, {n_img} images of {H}x{W}, k={k}, pad={pad}: not supported")
+    Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
+    out, ldo = _out(out, n_img * Ho * Wo, k * k * Cc, x, "im2col")
+    _launch("vdx_im2col_f16", _p(x, "x"), ldx, n_img, H, W, Cc, k, pad, _p(out, "out"), ldo)
+    return out
+
+
+def lpips_distance(x, lin, *, F, HW, out=None):
+    """One LPIPS tap over the F-1 consecutive pairs of tap rows x fp16 [F*HW][C] with fp32 `lin` [C] -> fp32 [F-1]; a given
+    `out` is added to (the sum over taps).  vdx_lpips_distance_f16."""
+    r, Cc, ldx = _rows(x, "x")
+    if F < 2 or r < F * HW or Cc > 512 or lin.numel() != Cc or not lin.is_contiguous():
+        raise VdxError(f"lpips_distance: x {tuple(x.shape)}, lin {tuple(lin.shape)}, F={F}, HW={HW}: shapes do not match (C <= 512)")
+    acc = out is not None
+    if out is None:
+        out = torch.empty(F - 1, dtype=torch.float32, device=x.device)
+    if out.numel() != F - 1 or not out.is_contiguous():
+        raise VdxError("lpips_distance: out must be contiguous fp32 [F-1]")
+    _launch("vdx_lpips_distance_f16", _p(x, "x"), ldx, F, HW, Cc, _p(lin, "lin", torch.float32), _p(out, "out", torch.float32), int(acc))
+    return out
+
+
+def frame_stats(frames):
+    """uint8 RGB frames (F, H, W, 3) on the GPU (rows and frames may be pitched) -> (grey histograms int32 [F][256] holding
+    the uint32 counts, absolute-difference sums int64 [F-1] holding the uint64 sums); vdx_frame_stats_u8.  torch has no
+    arithmetic on unsigned 32 / 64-bit tensors: the counts (< 2^31 for H*W < 2^31) and sums (< 2^63) are read as signed."""
+    F, H, W = _check_u8_frames(frames, "frame_stats")
+    if H * W >= 1 << 31:
+        raise VdxError("frame_stats: H*W must stay below 2^31")
+    hist = torch.empty((F, 256), dtype=torch.int32, device=frames.device)
+    diff = torch.empty((max(F - 1, 1),), dtype=torch.int64, device=frames.device)
+    _launch("vdx_frame_stats_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, hist.data_ptr(),
+            diff.data_ptr() if F > 1 else None)
+    return hist, diff[:F - 1]

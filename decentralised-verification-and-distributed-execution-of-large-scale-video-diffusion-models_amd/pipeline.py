@@ -508,7 +508,9 @@ def build_arg_parser():
     `--exchange` (allgather | halo, the module docstring) and `--noise_device` (parity runs generate the seeded noise on the CPU).
     Two more, also off by default: `--clip_json` scores the decoded frames with the validator's CLIP quality score
     (vdx/clip_score.py) on rank 0 and writes it there; `--clip_model` names the scorer's weights (a local directory in
-    transformers layout; without it, seeded synthetic ViT-B/32 weights, recorded as such)."""
+    transformers layout; without it, seeded synthetic ViT-B/32 weights, recorded as such).  `--mdvqs_json` does the same with
+    the validator's MD-VQS record (vdx/mdvqs.py: PF, VQ, TC, the weighted total and the authenticity gate); `--lpips_model`
+    names the LPIPS weights (a local file in the `lpips` state-dict layout; without it, seeded synthetic ones)."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -533,6 +535,8 @@ def build_arg_parser():
     p.add_argument("--out_video", default="out.mp4")
     p.add_argument("--clip_json", default=None, help="write the CLIP quality score of the decoded frames here (rank 0)")
     p.add_argument("--clip_model", default=None, help="local CLIP ViT-B/32 directory (transformers layout) for --clip_json")
+    p.add_argument("--mdvqs_json", default=None, help="write the MD-VQS record of the decoded frames here (rank 0)")
+    p.add_argument("--lpips_model", default=None, help="local LPIPS-AlexNet state dict (lpips layout) for --mdvqs_json")
     p.add_argument("--init_video", default=None,
                    help="video-to-video: refine this clip (.npy uint8 (T,H,W,3) or a directory of images) instead of starting from noise")
     p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
@@ -561,6 +565,26 @@ def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_token
     score, per = scorer.score(frames, prompt, tokenizer=tok)
     return {"clip_score": score, "per_frame": per.tolist(), "synthetic_weights": scorer.synthetic_weights,
             "tokenizer": f"{tok_src}:{type(tok).__name__}", "n_frames": len(frames)}
+
+
+def mdvqs_record(frames, prompt: str, lpips_model: Optional[str], clip_model: Optional[str], pipe_tokenizer, device) -> dict:
+    """The validator's MD-VQS record (InferNet/template/validator/scoring.py:13-67, :154-343) of the decoded frames, as
+    `--mdvqs_json` writes it.  Weights: `clip_model` / `lpips_model` (local), else seeded synthetic ones, recorded as such.
+    Tokenizer: as for `clip_score_record`."""
+    from .clip_score import CLIPScorer
+    from .lpips import LPIPSAlex
+    from .mdvqs import MDVQS, verify_video_authenticity
+    clip = CLIPScorer.from_local(clip_model, device=device) if clip_model else CLIPScorer.synthetic(seed=0, device=device)
+    lp = LPIPSAlex.from_local(lpips_model, device=device) if lpips_model else LPIPSAlex.synthetic(seed=0, device=device)
+    m = MDVQS(clip, lp)
+    tok = clip.tokenizer if clip.tokenizer is not None else pipe_tokenizer
+    pf = m.compute_prompt_fidelity(frames, prompt, tokenizer=tok)
+    vq, per = m.compute_video_quality(frames)
+    tc = m.compute_temporal_consistency(frames)
+    ok, stats = verify_video_authenticity(frames, device=device)
+    return {"pf": pf, "vq": vq, "tc": tc, "total": m.alpha * pf + m.beta * vq + m.gamma * tc,
+            "weights": {"alpha": m.alpha, "beta": m.beta, "gamma": m.gamma}, "lpips_per_pair": per.tolist(),
+            "authentic": ok, "authenticity": stats, "synthetic_weights": m.synthetic_weights, "n_frames": len(frames)}
 
 
 def encode_init_video(cfg: DiffuserConfig, vae, dev):
@@ -681,7 +705,7 @@ def main(argv=None) -> int:
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
-    clip_inputs = {} if a.clip_json else None
+    clip_inputs = {} if a.clip_json or a.mdvqs_json else None
     t0 = time.time()
     res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs)
     if res["rank"] == 0:
@@ -693,6 +717,13 @@ def main(argv=None) -> int:
             import json
             rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
             with open(a.clip_json, "w") as f:
+                json.dump(rec, f, indent=1)
+        if a.mdvqs_json:
+            # likewise after the row: MD-VQS (its optical flow runs on the CPU) never shows in `latency_s`
+            import json
+            rec = mdvqs_record(clip_inputs["frames"], cfg.prompt, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
+                               clip_inputs["device"])
+            with open(a.mdvqs_json, "w") as f:
                 json.dump(rec, f, indent=1)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -455,6 +455,48 @@ int vdx_vae_posterior_f16(const void* moments, int ld, int n, int hw, const void
 int vdx_add_noise_f16(const void* x0, const void* noise, void* out, float sqrt_ab, float sqrt_1mab, size_t n,
                       vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MD-VQS: the validator's video-quality term and its authenticity gate
+ *   InferNet/neurons/validator.py:120,1295   self.quality_scorer = MDVQS(); compute_quality_score = 0.4 PF + 0.3 VQ + 0.3 TC
+ *   InferNet/neurons/validator.py:259,872    verify_video_authenticity
+ *   InferNet/template/validator/scoring.py:269-309   VQ = max(0, 1 - mean LPIPS-AlexNet(frame_i, frame_i-1))
+ *   InferNet/template/validator/scoring.py:13-67     grey-level entropy and frame differences
+ * (csrc/mdvqs.hip; vdx/lpips.py, vdx/mdvqs.py).  The `lpips` package is not part of the parity set: LPIPS is restated from
+ * its published definition (unpinned).  The five AlexNet convolutions run on vdx_gemm_f16.
+ * ---------------------------------------------------------------------------------------- */
+/* conv1's operand from the RESIZED uint8 frames (F, 224, 224, 3) (scoring.py:171-175 Resize((224, 224)): vdx_resample_*_u8 /
+ * vdx_clip_preprocess_u8's out_u8): row f*3025 + oy*55 + ox, column (ky*11 + kx)*3 + c = lut[c][u8[f][4oy-2+ky][4ox-2+kx][c]],
+ * 0.0 outside the image (Conv2d(3, 64, 11, stride 4, padding 2) pads its input, i.e. after the scaling layer), columns
+ * 363..383 zero.  lut_f16: fp16 [3][256] on the device = fp16(((u/255 - mean_c)/std_c - shift_c)/scale_c), both affine maps
+ * (ToTensor + Normalize, :171-175; LPIPS' ScalingLayer, reached with normalize=False, :288) in fp32 on the host.
+ * ldo >= 384, % 8; out_rows 16-byte aligned.                                                                          */
+int vdx_lpips_stem_u8(const void* u8_frames, int F, const void* lut_f16, void* out_rows, int ldo, vdx_stream_t stream);
+/* y = max(x, 0) as torch.relu (NaN -> NaN), n elements: AlexNet's ReLU behind conv3..conv5 (:288).  y may alias x.        */
+int vdx_relu_f16(const void* x, void* y, size_t n, vdx_stream_t stream);
+/* AlexNet's ReLU + MaxPool2d(3, stride 2) behind conv1 and conv2 (:288): rows x [n_img*H*W][ldx] (C columns) are ReLU'd IN
+ * PLACE (the LPIPS tap) and out rows [n_img*Ho*Wo][ldo] get the window maxima of the ReLU'd rows, Ho = (H-3)/2 + 1 (no
+ * padding; 55 -> 27, 27 -> 13).  C % 8 == 0; out may not alias x.                                                       */
+int vdx_relu_maxpool_f16(void* x, int ldx, int n_img, int H, int W, int C, void* out, int ldo, vdx_stream_t stream);
+/* Stride-1 im2col of channels-last rows x [n_img*H*W][ldx] (C % 64 == 0): out row n*Ho*Wo + oy*Wo + ox, column
+ * (ky*k + kx)*C + c = x[n][oy-pad+ky][ox-pad+kx][c], 0 outside the image, Ho = H + 2 pad - k + 1.  With vdx_gemm_f16 (plain)
+ * and w.permute(0, 2, 3, 1).reshape(N, k*k*C): Conv2d(C, N, k, padding=pad) — AlexNet's conv2 (k 5, pad 2; :288).          */
+int vdx_im2col_f16(const void* x, int ldx, int n_img, int H, int W, int C, int k, int pad, void* out, int ldo,
+                   vdx_stream_t stream);
+/* One tap of LPIPS (:288, lpips.LPIPS.forward with lpips=True, spatial=False) for the F-1 consecutive frame pairs: with
+ * n(v) = v / (sqrt(sum_c v^2) + 1e-10) per pixel, out[p] (+)= mean_pix sum_c lin[c] (n(x_p) - n(x_p+1))^2.  x: tap rows fp16
+ * [F*HW][ldx], C <= 512 columns; lin: fp32 [C] (the non-negative 1x1 `lin` layer; Dropout is the identity in eval mode);
+ * out: fp32 [F-1], overwritten (accumulate = 0) or added to (the sum over taps).  fp32 norms, a fixed reduction order without
+ * atomics: the same bits on every run; identical frames give exactly 0.                                                */
+int vdx_lpips_distance_f16(const void* x, int ldx, int F, int HW, int C, const float* lin, float* out, int accumulate,
+                           vdx_stream_t stream);
+/* The integer half of verify_video_authenticity_common (:27-36) over F uint8 RGB frames (pitches in bytes as in
+ * vdx_clip_preprocess_args): hist[f][g] = pixels of frame f with grey level g = (4899 R + 9617 G + 1868 B + 8192) >> 14
+ * (cv2.cvtColor's 8-bit weights; cv2.calcHist's counts), absdiff[f] = sum over all bytes of |frame f+1 - frame f|
+ * (cv2.absdiff; F-1 sums, may be NULL for F = 1).  Both are zeroed on the stream, then filled with integer atomics: exact.
+ * The host finishes (normalise, entropy, means) in numpy with the reference's dtypes (vdx/mdvqs.py).                      */
+int vdx_frame_stats_u8(const void* frames, size_t frame_pitch, int row_pitch, int F, int H, int W, uint32_t* hist,
+                       uint64_t* absdiff, vdx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

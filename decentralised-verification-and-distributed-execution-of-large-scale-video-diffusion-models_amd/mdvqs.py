@@ -13,8 +13,12 @@ What it computes, term by term (the same as the reference unless stated):
     (vdx/lpips.py: restated from the published definition, parity with the `lpips` package unpinned); fewer than two
     frames score 0.0 (:295-297).  The mean is numpy's, over the fp32 per-pair distances as float64 (`.item()` values, :288-301);
   * TC, temporal consistency (:311-339): the mean over consecutive pairs of mean(|Farneback flow|) with the reference's
-    parameters (0.5, 3, 15, 3, 5, 1.2, 0), on the CPU through `metrics._cv2()` — OpenCV when installed, else the project's
-    own Farneback (vdx/compat/cv2_shim.py: parity with OpenCV unpinned); no pairs score 0.0 (:336-337).
+    parameters (0.5, 3, 15, 3, 5, 1.2, 0); no pairs score 0.0 (:336-337).  By default (`flow="cpu"`) on the CPU through
+    `metrics._cv2()` — OpenCV when installed, else the project's own Farneback (vdx/compat/cv2_shim.py: parity with OpenCV
+    unpinned).  `MDVQS(..., flow="gpu")` computes the same flow in HIP kernels, batched over all pairs (vdx/flow.py,
+    csrc/flow.hip): pinned against the shim (tests/test_flow_gpu.py), the shim against OpenCV still is not.  Measured on one
+    MI355X box (profiles/flow_bench.json, 24 frames at 576x1024): the 23 flows take 3.4 ms, TC as a whole 3.5 ms, i.e. 0.15 ms
+    per pair where the shim takes 0.70 s for one pair on the same box — 4 700 times the GPU's per-pair time.
     DEVIATION: the reference hands Farneback the 3-channel BGR frames as read (:319-327).  OpenCV's Farneback takes
     single-channel 8-bit images and is believed to reject those, in which case the reference's own TC is its exception
     value 0.0 (:341-343); nobody could run `cv2` where this was written to confirm.  Here the flow is computed on the
@@ -84,8 +88,10 @@ class MDVQS:
     `LPIPSAlex` (each term raises `VdxError` without its model)."""
 
     def __init__(self, clip: Optional[CLIPScorer] = None, lpips: Optional[LPIPSAlex] = None, alpha: float = 0.4,
-                 beta: float = 0.3, gamma: float = 0.3):
-        self.clip, self.lpips = clip, lpips
+                 beta: float = 0.3, gamma: float = 0.3, flow: str = "cpu"):
+        if flow not in ("cpu", "gpu"):
+            raise VdxError(f"MDVQS: flow must be 'cpu' or 'gpu', got {flow!r}")
+        self.clip, self.lpips, self.flow = clip, lpips, flow
         self.alpha, self.beta, self.gamma = alpha, beta, gamma
 
     @classmethod
@@ -113,7 +119,15 @@ class MDVQS:
         return max(0.0, 1.0 - avg), per
 
     def compute_temporal_consistency(self, frames) -> float:
-        """:311-339 on the CPU, on grey frames (the module docstring's deviation); no pairs -> 0.0."""
+        """:311-339 on grey frames (the module docstring's deviation), on the CPU or with `flow="gpu"` on the device of the
+        frames (host frames: of the models, else "cuda"); no pairs -> 0.0."""
+        if self.flow == "gpu":
+            from . import flow as _flow
+            if len(frames) == 0:
+                return 0.0
+            model = self.lpips if self.lpips is not None else self.clip
+            on_gpu = isinstance(frames, torch.Tensor) and frames.is_cuda
+            return _flow.temporal_consistency(frames, device=None if on_gpu or model is None else model.device)
         from .metrics import _cv2
         cv2 = _cv2()
         fr = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else [np.asarray(f) for f in frames]

@@ -3,7 +3,7 @@ reduction and the CSV contract that `Distribution/plot_helpers/plot.py:7-13` rea
 
 `temp_instab` (mean absolute difference of the two frames either side of every chunk boundary) is restated
 exactly (:227-247, host numpy on the decoded uint8 frames, as the reference computes it).  `flow_err` (:236-245) is
-the same loop with OpenCV's Farneback flow + remap; `cv2` is taken from the environment when it is installed and
+the same loop with OpenCV's Farneback flow + remap (on the GPU when `flow_warp_error` is given a device); `cv2` is taken from the environment when it is installed and
 from `vdx.compat.cv2_shim` (an own implementation of the published algorithm) otherwise — with the shim the number
 is not pinned against OpenCV's ("parity unpinned", see the shim's docstring).  `write_video` is :250-253.
 """
@@ -44,9 +44,13 @@ def _cv2():
         return cv2_shim
 
 
-def flow_warp_error(frames: Sequence[np.ndarray], ranges: Sequence[Tuple[int, int]]) -> Optional[float]:
+def flow_warp_error(frames: Sequence[np.ndarray], ranges: Sequence[Tuple[int, int]], device=None) -> Optional[float]:
     """:229-246 — at every chunk boundary: Farneback flow prev -> next (pyr 0.5, 3 levels, window 15, 3 iterations,
-    poly 5 / 1.2), warp prev by it (remap, bilinear) and take the mean absolute difference to next."""
+    poly 5 / 1.2), warp prev by it (remap, bilinear) and take the mean absolute difference to next.  With a `device` the
+    same runs in HIP kernels there (vdx/flow.py; pinned against the shim, not against OpenCV); the default is the host path."""
+    if device is not None:
+        from . import flow
+        return flow.flow_warp_error(frames, ranges, device=device)
     cv2 = _cv2()
     if len(frames) <= 1:
         return None

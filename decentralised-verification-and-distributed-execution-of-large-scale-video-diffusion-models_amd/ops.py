@@ -1060,3 +1060,109 @@ def frame_stats(frames):
     _launch("vdx_frame_stats_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, hist.data_ptr(),
             diff.data_ptr() if F > 1 else None)
     return hist, diff[:F - 1]
+
+
+# --------------------------------------------------------------------------------------------
+# Farneback optical flow (cv2_shim.py:99-182; scoring.py:311-339, fsdp_chunked_coherent.py:236-246; include/vdx.h
+# "Farneback"; csrc/flow.hip).  vdx/flow.py drives these; images are packed fp32 [n][H][W], flows fp32 [P][H][W][2].
+def _f32(t, shape, what, name):
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise VdxError(f"{what}: {name} must be contiguous fp32 {tuple(shape)} on the GPU, got {t.dtype} {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def flow_grey(frames, bgr: bool = False):
+    """uint8 RGB frames (F, H, W, 3) on the GPU -> fp32 grey (F, H, W) with OpenCV's 8-bit weights; `bgr`: COLOR_BGR2GRAY
+    applied to the same bytes (vdx_flow_grey_u8)."""
+    F, H, W = _check_u8_frames(frames, "flow_grey")
+    out = torch.empty((F, H, W), dtype=torch.float32, device=frames.device)
+    _launch("vdx_flow_grey_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, int(bool(bgr)), out.data_ptr())
+    return out
+
+
+def flow_corr1d(img, taps, axis: int):
+    """correlate1d(img, taps, axis, mode="mirror") of fp32 images (n, H, W); taps fp32 [2r + 1] on the GPU (vdx_flow_corr1d_f32)."""
+    if img.dim() != 3 or axis not in (0, 1):
+        raise VdxError(f"flow_corr1d: expected images (n, H, W) and axis 0 or 1, got {tuple(img.shape)}, axis {axis}")
+    n, H, W = img.shape
+    if taps.dim() != 1 or taps.numel() % 2 != 1 or taps.device != img.device:
+        raise VdxError("flow_corr1d: taps must be an odd-length vector on the images' device")
+    out = torch.empty_like(img)
+    _launch("vdx_flow_corr1d_f32", _f32(img, (n, H, W), "flow_corr1d", "img"), out.data_ptr(), n, H, W,
+            _f32(taps, taps.shape, "flow_corr1d", "taps"), taps.numel() // 2, axis)
+    return out
+
+
+def flow_resize(x, height: int, width: int, mul: float = 1.0):
+    """`_resize_linear` of fp32 images (n, H, W) or flows (n, H, W, 2) to (height, width), times `mul` (vdx_flow_resize_f32)."""
+    if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[3] != 2) or height <= 0 or width <= 0:
+        raise VdxError(f"flow_resize: expected (n, H, W) or (n, H, W, 2) and a positive size, got {tuple(x.shape)} -> {height}x{width}")
+    n, H, W = x.shape[:3]
+    Cc = 1 if x.dim() == 3 else 2
+    out = torch.empty((n, height, width) + tuple(x.shape[3:]), dtype=torch.float32, device=x.device)
+    _launch("vdx_flow_resize_f32", _f32(x, x.shape, "flow_resize", "x"), n, H, W, Cc, out.data_ptr(), height, width, float(mul))
+    return out
+
+
+def flow_polyexp(img, taps, inv_g):
+    """`_poly_exp` (poly_n 5) of fp32 images (n, H, W) -> (n, 5, H, W) = bx, by, axx, ayy, axy.  `taps` (3, 11) and `inv_g` (5, 6):
+    host arrays (`vdx.flow.poly_tables`), passed as kernel arguments (vdx_flow_polyexp_f32)."""
+    import numpy as np
+    if img.dim() != 3:
+        raise VdxError(f"flow_polyexp: expected images (n, H, W), got {tuple(img.shape)}")
+    n, H, W = img.shape
+    k, g = np.ascontiguousarray(taps, np.float32), np.ascontiguousarray(inv_g, np.float32)
+    if k.shape != (3, 11) or g.shape != (5, 6):
+        raise VdxError(f"flow_polyexp: taps {k.shape} / inv_g {g.shape}: expected (3, 11) and (5, 6)")
+    out = torch.empty((n, 5, H, W), dtype=torch.float32, device=img.device)
+    fp = C.POINTER(C.c_float)
+    _launch("vdx_flow_polyexp_f32", _f32(img, (n, H, W), "flow_polyexp", "img"), n, H, W, k.ctypes.data_as(fp), g.ctypes.data_as(fp),
+            out.data_ptr())
+    return out
+
+
+def flow_update(R, flow, step: int = 1, out=None):
+    """One `_update_flow` iteration for every pair: R (n, 5, H, W) expansions, flow (P, H, W, 2); pair p uses images p*step and
+    p*step + 1 -> the new flow (P, H, W, 2) (`out`, which may not be `flow`).  vdx_flow_update_f32."""
+    if R.dim() != 4 or R.shape[1] != 5 or flow.dim() != 4 or flow.shape[3] != 2:
+        raise VdxError(f"flow_update: expected R (n, 5, H, W) and flow (P, H, W, 2), got {tuple(R.shape)}, {tuple(flow.shape)}")
+    n, _, H, W = R.shape
+    P = flow.shape[0]
+    if step not in (1, 2) or P < 1 or (P - 1) * step + 2 > n or tuple(flow.shape[1:3]) != (H, W) or flow.device != R.device:
+        raise VdxError(f"flow_update: {P} pairs of step {step} at {tuple(flow.shape[1:3])} do not fit {n} expansions at {(H, W)}")
+    if out is None:
+        out = torch.empty_like(flow)
+    if out.data_ptr() == flow.data_ptr():
+        raise VdxError("flow_update: out may not be the input flow")
+    _launch("vdx_flow_update_f32", _f32(R, R.shape, "flow_update", "R"), _f32(flow, flow.shape, "flow_update", "flow"),
+            _f32(out, flow.shape, "flow_update", "out"), P, step, H, W)
+    return out
+
+
+def flow_abs_sum(flow):
+    """fp32 flows (P, H, W, 2) -> fp32 [P], the sum of |flow| of each pair in a fixed order (vdx_flow_abs_sum_f32)."""
+    if flow.dim() != 4 or flow.shape[0] < 1:
+        raise VdxError(f"flow_abs_sum: expected flows (P, H, W, 2), got {tuple(flow.shape)}")
+    P = flow.shape[0]
+    ws = torch.empty((P, 64), dtype=torch.float32, device=flow.device)
+    out = torch.empty((P,), dtype=torch.float32, device=flow.device)
+    _launch("vdx_flow_abs_sum_f32", _f32(flow, flow.shape, "flow_abs_sum", "flow"), P, flow[0].numel(), ws.data_ptr(), out.data_ptr())
+    return out
+
+
+def flow_remap_absdiff(frames, flow, step: int = 1, want_warped: bool = False):
+    """uint8 RGB frames (F, H, W, 3) and flows (P, H, W, 2): pair p warps frame p*step by its flow (`cv2.remap`, bilinear,
+    constant-0 border) and compares it with frame p*step + 1 -> (int64 [P] sums of |warp - next| over all bytes, the warped
+    frames uint8 (P, H, W, 3) or None).  vdx_flow_remap_absdiff_u8."""
+    F, H, W = _check_u8_frames(frames, "flow_remap_absdiff")
+    if flow.dim() != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (H, W, 2) or flow.device != frames.device:
+        raise VdxError(f"flow_remap_absdiff: flow {tuple(flow.shape)} does not match frames {(H, W)}")
+    P = flow.shape[0]
+    if step not in (1, 2) or (P - 1) * step + 2 > F:
+        raise VdxError(f"flow_remap_absdiff: {P} pairs of step {step} need more than {F} frames")
+    diff = torch.empty((P,), dtype=torch.int64, device=frames.device)
+    warped = torch.empty((P, H, W, 3), dtype=torch.uint8, device=frames.device) if want_warped else None
+    _launch("vdx_flow_remap_absdiff_u8", frames.data_ptr(), frames.stride(0), frames.stride(1),
+            _f32(flow, flow.shape, "flow_remap_absdiff", "flow"), P, step, H, W, diff.data_ptr(),
+            warped.data_ptr() if want_warped else None)
+    return diff, warped

@@ -63,6 +63,7 @@ class DiffuserConfig:
     init_video: Optional[str] = None       # .npy uint8 (T,H,W,3) or a directory of image files (sorted by name)
     strength: float = 0.6
     posterior: str = "sample"              # "sample" | "mode" of the encoder's diagonal Gaussian
+    gpu_flow: bool = False                 # flow_err (and MD-VQS' TC) from the HIP Farneback kernels instead of the host path
 
     @property
     def use_fsdp(self):
@@ -510,7 +511,9 @@ def build_arg_parser():
     (vdx/clip_score.py) on rank 0 and writes it there; `--clip_model` names the scorer's weights (a local directory in
     transformers layout; without it, seeded synthetic ViT-B/32 weights, recorded as such).  `--mdvqs_json` does the same with
     the validator's MD-VQS record (vdx/mdvqs.py: PF, VQ, TC, the weighted total and the authenticity gate); `--lpips_model`
-    names the LPIPS weights (a local file in the `lpips` state-dict layout; without it, seeded synthetic ones)."""
+    names the LPIPS weights (a local file in the `lpips` state-dict layout; without it, seeded synthetic ones).  `--gpu_flow`
+    computes the Farneback flow behind `flow_err` and behind MD-VQS' TC in HIP kernels (vdx/flow.py) instead of on the host;
+    the MD-VQS record then carries `"flow": "gpu"`."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -537,6 +540,7 @@ def build_arg_parser():
     p.add_argument("--clip_model", default=None, help="local CLIP ViT-B/32 directory (transformers layout) for --clip_json")
     p.add_argument("--mdvqs_json", default=None, help="write the MD-VQS record of the decoded frames here (rank 0)")
     p.add_argument("--lpips_model", default=None, help="local LPIPS-AlexNet state dict (lpips layout) for --mdvqs_json")
+    p.add_argument("--gpu_flow", action="store_true", help="Farneback flow of flow_err and of MD-VQS' TC on the GPU (vdx/flow.py)")
     p.add_argument("--init_video", default=None,
                    help="video-to-video: refine this clip (.npy uint8 (T,H,W,3) or a directory of images) instead of starting from noise")
     p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
@@ -549,7 +553,7 @@ def config_from_args(a) -> DiffuserConfig:
                           overlap=a.overlap, height=a.height, width=a.width, mode=a.mode, context_weight=a.context_weight,
                           device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
                           out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
-                          init_video=a.init_video, strength=a.strength, posterior=a.posterior)
+                          init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow)
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -567,24 +571,29 @@ def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_token
             "tokenizer": f"{tok_src}:{type(tok).__name__}", "n_frames": len(frames)}
 
 
-def mdvqs_record(frames, prompt: str, lpips_model: Optional[str], clip_model: Optional[str], pipe_tokenizer, device) -> dict:
+def mdvqs_record(frames, prompt: str, lpips_model: Optional[str], clip_model: Optional[str], pipe_tokenizer, device,
+                 flow: str = "cpu") -> dict:
     """The validator's MD-VQS record (InferNet/template/validator/scoring.py:13-67, :154-343) of the decoded frames, as
     `--mdvqs_json` writes it.  Weights: `clip_model` / `lpips_model` (local), else seeded synthetic ones, recorded as such.
-    Tokenizer: as for `clip_score_record`."""
+    Tokenizer: as for `clip_score_record`.  `flow="gpu"` (`--gpu_flow`): TC from the HIP Farneback kernels; the record then
+    has one more key, "flow": "gpu"."""
     from .clip_score import CLIPScorer
     from .lpips import LPIPSAlex
     from .mdvqs import MDVQS, verify_video_authenticity
     clip = CLIPScorer.from_local(clip_model, device=device) if clip_model else CLIPScorer.synthetic(seed=0, device=device)
     lp = LPIPSAlex.from_local(lpips_model, device=device) if lpips_model else LPIPSAlex.synthetic(seed=0, device=device)
-    m = MDVQS(clip, lp)
+    m = MDVQS(clip, lp, flow=flow)
     tok = clip.tokenizer if clip.tokenizer is not None else pipe_tokenizer
     pf = m.compute_prompt_fidelity(frames, prompt, tokenizer=tok)
     vq, per = m.compute_video_quality(frames)
     tc = m.compute_temporal_consistency(frames)
     ok, stats = verify_video_authenticity(frames, device=device)
-    return {"pf": pf, "vq": vq, "tc": tc, "total": m.alpha * pf + m.beta * vq + m.gamma * tc,
-            "weights": {"alpha": m.alpha, "beta": m.beta, "gamma": m.gamma}, "lpips_per_pair": per.tolist(),
-            "authentic": ok, "authenticity": stats, "synthetic_weights": m.synthetic_weights, "n_frames": len(frames)}
+    rec = {"pf": pf, "vq": vq, "tc": tc, "total": m.alpha * pf + m.beta * vq + m.gamma * tc,
+           "weights": {"alpha": m.alpha, "beta": m.beta, "gamma": m.gamma}, "lpips_per_pair": per.tolist(),
+           "authentic": ok, "authenticity": stats, "synthetic_weights": m.synthetic_weights, "n_frames": len(frames)}
+    if flow != "cpu":
+        rec["flow"] = flow
+    return rec
 
 
 def encode_init_video(cfg: DiffuserConfig, vae, dev):
@@ -676,7 +685,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     temp_instab = flow_err = None
     if d.rank == 0 and len(frames) > 1 and not cfg.no_chunking:
         temp_instab = metrics.boundary_l1(frames, ranges)
-        flow_err = metrics.flow_warp_error(frames, ranges)
+        flow_err = metrics.flow_warp_error(frames, ranges, device=dev) if cfg.gpu_flow else metrics.flow_warp_error(frames, ranges)
     if d.rank == 0 and out_video:
         metrics.write_video(frames, out_video, cfg.fps)
     delay = emu_reduce_delay_s(cfg)             # :257-258
@@ -719,10 +728,10 @@ def main(argv=None) -> int:
             with open(a.clip_json, "w") as f:
                 json.dump(rec, f, indent=1)
         if a.mdvqs_json:
-            # likewise after the row: MD-VQS (its optical flow runs on the CPU) never shows in `latency_s`
+            # likewise after the row: MD-VQS (its optical flow runs on the CPU unless --gpu_flow) never shows in `latency_s`
             import json
             rec = mdvqs_record(clip_inputs["frames"], cfg.prompt, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
-                               clip_inputs["device"])
+                               clip_inputs["device"], **({"flow": "gpu"} if a.gpu_flow else {}))
             with open(a.mdvqs_json, "w") as f:
                 json.dump(rec, f, indent=1)
     if dist.is_available() and dist.is_initialized():

@@ -497,6 +497,50 @@ int vdx_lpips_distance_f16(const void* x, int ldx, int F, int HW, int C, const f
 int vdx_frame_stats_u8(const void* frames, size_t frame_pitch, int row_pitch, int F, int H, int W, uint32_t* hist,
                        uint64_t* absdiff, vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Farneback dense optical flow, batched over the frame pairs of a clip, and the two numbers built on it
+ *   InferNet/template/validator/scoring.py:311-339            TC = mean over consecutive pairs of mean |Farneback flow|
+ *   Distribution/strategies/fsdp_chunked_coherent.py:236-246  flow_err = mean |remap(prev, flow) - next| at chunk boundaries
+ * (csrc/flow.hip; vdx/flow.py).  The algorithm is vdx/compat/cv2_shim.py's calcOpticalFlowFarneback stage by stage
+ * (cv2_shim.py:99-182; parameters 0.5, levels, 15, iterations, 5, 1.2, 0), which stands in for cv2's where OpenCV is not
+ * installed: the GPU path is pinned against that shim, the shim against OpenCV is not.  fp32 throughout, fixed summation
+ * orders, no floating-point atomics: the same bits on every run and for every batch size.  Images are fp32 [n][H][W],
+ * flows fp32 [P][H][W][2] (x, y), both packed.
+ * ---------------------------------------------------------------------------------------- */
+/* cv2.cvtColor(frame, COLOR_RGB2GRAY) (scoring.py:319-327 as vdx/mdvqs.py states it; bgr = 0) or COLOR_BGR2GRAY applied to
+ * the same bytes (fsdp_chunked_coherent.py:238-239 / vdx/metrics.py:59; bgr = 1: channel 0 takes the blue weight) of F uint8
+ * frames (pitches in bytes), as fp32: (4899 R + 9617 G + 1868 B + 8192) >> 14.                                        */
+int vdx_flow_grey_u8(const void* frames, size_t frame_pitch, int row_pitch, int F, int H, int W, int bgr, float* out,
+                     vdx_stream_t stream);
+/* scipy.ndimage.correlate1d(.., mode="mirror") along axis 0 (rows) or 1 (columns) of n_img images: one pass of the pyramid's
+ * gaussian_filter (cv2_shim.py:170-172).  taps: fp32 [2 radius + 1] on the device (vdx/flow.py gaussian_taps).           */
+int vdx_flow_corr1d_f32(const float* in, float* out, int n_img, int H, int W, const float* taps, int radius, int axis,
+                        vdx_stream_t stream);
+/* _resize_linear (cv2_shim.py:55-67): bilinear, src = (dst + 0.5) Hi / Ho - 0.5 clipped to the image, evaluated in exact
+ * integer arithmetic; in [n][Hi][Wi][C] -> out [n][Ho][Wo][C], C = 1 (pyramid level, :171-172) or 2 (the flow carried to the
+ * next level, :178), times mul (1, or 1 / pyr_scale = 2 for the flow).                                                 */
+int vdx_flow_resize_f32(const float* in, int n_img, int Hi, int Wi, int C, float* out, int Ho, int Wo, float mul,
+                        vdx_stream_t stream);
+/* _poly_exp (cv2_shim.py:99-118) with poly_n = 5 of n_img images -> out [n][5][H][W] = bx, by, axx, ayy, axy.  taps_host:
+ * fp32 [3][11] HOST memory, g, g x, g x^2; inv_g_host: fp32 [5][6] HOST memory, rows 1..5 of inv(G) (both from
+ * vdx/flow.py poly_tables, evaluated in float64); they travel as kernel arguments.                                     */
+int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, const float* taps_host, const float* inv_g_host, float* out,
+                         vdx_stream_t stream);
+/* _update_flow (cv2_shim.py:132-153), box window of 15, for P pairs in one launch: pair p reads the expansions of images
+ * p*step and p*step + 1 of R ([..][5][H][W]; step 1: consecutive frames, each expansion serving two pairs; step 2: disjoint
+ * pairs) and flow_in[p], and writes flow_out[p] (may not alias flow_in).  The five window products stay in LDS.           */
+int vdx_flow_update_f32(const float* R, const float* flow_in, float* flow_out, int P, int step, int H, int W,
+                        vdx_stream_t stream);
+/* scoring.py:329-331: out[p] = sum of |flow[p]| over its n = H*W*2 values (the host divides).  workspace: fp32 [P][64].
+ * Two stages of fixed order.                                                                                          */
+int vdx_flow_abs_sum_f32(const float* flow, int P, size_t n, float* workspace, float* out, vdx_stream_t stream);
+/* fsdp_chunked_coherent.py:241-246 / vdx/metrics.py:61-65 for P pairs: prev = frame p*step, next = frame p*step + 1 of
+ * `frames` (uint8 RGB, pitches in bytes); warp = cv2.remap(prev, x + flow_x, y + flow_y, INTER_LINEAR) (cv2_shim.py:70-93:
+ * constant-0 border, round half to even, clip), absdiff[p] = sum over all bytes of |warp - next| (zeroed on the stream,
+ * integer atomics: exact).  warped: NULL, or uint8 [P][H][W][3] that receives the warped frames.                         */
+int vdx_flow_remap_absdiff_u8(const void* frames, size_t frame_pitch, int row_pitch, const float* flow, int P, int step, int H,
+                              int W, uint64_t* absdiff, void* warped, vdx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

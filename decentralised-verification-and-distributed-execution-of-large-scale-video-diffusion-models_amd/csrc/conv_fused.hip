@@ -23,6 +23,7 @@
 // Diagnostic switches (tools/k1_abl.sh builds them into csrc/build/abl/libk1_<tag>.so; the product defines none):
 //   K1_ABL_NONORM  timing-only, WRONG RESULTS: later slices are not normalised;   K1_ABL_NOPIN  hipcc's own instruction order.
 #include "gemm_common.h"
+#include "lab.h"
 
 struct C1P {
     const f16 *a, *a2, *w, *bias, *bias2, *res;
@@ -372,13 +373,5 @@ extern "C" int vdx_conv3x3_gn_f16(const void* a, int lda, const void* a2, int ld
     return vdx_launch_status("vdx_conv3x3_gn_f16");
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_conv_fused(void) {
-#if defined(K1_ABL_NOPIN) || defined(K1_ABL_NONORM)
-    return 64;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_conv_fused(void) { return VDX_LAB_CONV_FUSED; }

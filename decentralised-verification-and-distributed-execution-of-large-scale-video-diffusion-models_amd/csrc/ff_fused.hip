@@ -19,6 +19,7 @@
 //   * persistent: a workgroup walks tiles blockIdx.x, + gridDim.x, ...
 // Built for inner 320 (level 0 of the UNet: 10 feed-forwards per forward).
 #include "rowtile_common.h"
+#include "lab.h"
 
 namespace {
 
@@ -540,13 +541,5 @@ extern "C" int vdx_ff_block_proj_f16(const void* t, int ldt, const void* packed,
     return ff_block_launch(t, ldt, packed, eps, out, ldo, M, inner, x, ldx, xrows, proj_packed, stream);
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_ff_fused(void) {
-#if defined(K8_ABL_NOWDMA) || defined(K8_ABL_NOLDSX) || defined(K8_ABL_NOLDSW) || defined(K8_ABL_NOGEGLU) || defined(K8_ABL_NOBAR)
-    return 32;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_ff_fused(void) { return VDX_LAB_FF_FUSED; }

@@ -24,6 +24,7 @@
 // "flash: ping-pong kernel experiment") is not faster: beside a wave that streams MFMAs, the softmax's vector mix is all
 // but starved, whichever wave is older or has the priority.
 #include "attn_common.h"
+#include "lab.h"
 
 // Diagnostic switches (tools/flash_abl.sh builds them into csrc/build/abl/libflash_<tag>.so; the product defines none):
 //   FL_ABL_NOEXP / NOSUM / NOMAX / NODMA / NOKREAD / NOVREAD / NOBAR   timing-only builds with one part of the tile
@@ -52,14 +53,13 @@ __device__ __forceinline__ f32x16 fl_mfma(const f16x8 a, const f16x8 b, const f3
 }
 #endif
 #ifdef FL_STAMPS
-static __device__ unsigned long long g_fl_stamps[8 * 32768];     // [block * waves + wave][8]: four phase sums, total, tiles
-#define FL_T(i)                                                     \
-    do {                                                            \
-        __builtin_amdgcn_sched_barrier(0);                          \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        fl_sum[i] += now_ - fl_last;                                \
-        fl_last = now_;                                             \
-        __builtin_amdgcn_sched_barrier(0);                          \
+// [block * waves + wave][8] x u64: four phase sums, total, tiles of the last launch; the reader copies the first `bytes`
+VDX_STAMP_BUFFER_AS(g_fl_stamps, 8 * 32768, vdx_flash_stamps_read(void* dst, size_t bytes), bytes)
+#define FL_T(i)                                 \
+    do {                                        \
+        __builtin_amdgcn_sched_barrier(0);      \
+        VDX_STAMP_ACC(fl_sum[i], fl_last)       \
+        __builtin_amdgcn_sched_barrier(0);      \
     } while (0)
 #else
 #define FL_T(i)
@@ -509,22 +509,5 @@ extern "C" int vdx_flash_attn_rows_f16(const void* q, int ldq, const void* k, in
     return flash_launch<true>(q, ldq, k, ldk, v, ldv, out, ldo, n_seq, sq, skv, skv_pad, heads, seq_per_kv, scale, causal, stream);
 }
 
-#ifdef FL_STAMPS
-// diagnostic builds only: the per-wave phase sums of the last launch ([block * waves + wave][8] x u64)
-extern "C" int vdx_flash_stamps_read(void* host, size_t bytes) {
-    VDX_CHECK(host && bytes <= sizeof(g_fl_stamps), "flash_stamps_read: bad buffer");
-    const hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fl_stamps), bytes, 0, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? 0 : vdx_fail("flash_stamps_read: %s", hipGetErrorString(e));
-}
-#endif
-
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_flash(void) {
-#if defined(FL_STAMPS) || defined(FL_ABL_NOEXP) || defined(FL_ABL_MFMA16) || defined(FL_ABL_NOVREAD) || defined(FL_ABL_NOSUM) || defined(FL_ABL_NOMAX) || defined(FL_ABL_NOKREAD) || defined(FL_ABL_NODMA) || defined(FL_ABL_NOBAR)
-    return 16;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_flash(void) { return VDX_LAB_FLASH; }

@@ -20,15 +20,13 @@
 // MFMAs.  The MFMA is issued with the weight fragment as the A operand, so a lane ends up holding
 // 8 consecutive output channels of one row -> 16-byte epilogue stores.
 #include "gemm_common.h"
+#include "lab.h"
 #include <stdlib.h>
 #include <string.h>
 
 #ifdef VDX_STAMPS   // diagnostic build only (make stamps): per-block phase clocks, never in the product library
 #define STAMP_MAX 32768
-static __device__ unsigned long long g_stamps[STAMP_MAX * 8];
-extern "C" int vdx_debug_read_stamps(void* dst, int nblocks) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), (size_t)nblocks * 64) == hipSuccess ? 0 : -1;
-}
+VDX_STAMP_BUFFER_AS(g_stamps, STAMP_MAX * 8, vdx_debug_read_stamps(void* dst, int nblocks), (size_t)nblocks * 64)
 #define STAMP(i) st_[i] = __builtin_amdgcn_s_memtime()
 #else
 #define STAMP(i)
@@ -224,18 +222,18 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmP p) {
     for (int kt = KS ? kt_lo : 0; kt < (KS ? kt_hi : nk); ++kt) {
         const int cur = KS ? (kt - kt_lo) & 1 : kt & 1;
         const bool more = kt + 1 < (KS ? kt_hi : nk);
-#if !(defined(VDX_STAMPS) && VDX_ABL == 2)   // diagnostic ablation 2: no DMA inside the K loop
+#if !VDX_ABL_IS(2)   // diagnostic ablation 2: no DMA inside the K loop
         // buffer cur^1 was last read before the previous barrier
-#if !(defined(VDX_STAMPS) && VDX_ABL == 5)    // ablation 5: no activation DMA in the loop
+#if !VDX_ABL_IS(5)    // ablation 5: no activation DMA in the loop
         if (more && does_a) sg.issue_a(p, smem, cur ^ 1);
 #endif
-#if !(defined(VDX_STAMPS) && VDX_ABL == 6)    // ablation 6: no weight DMA in the loop
+#if !VDX_ABL_IS(6)    // ablation 6: no weight DMA in the loop
         if (more && !SPLIT) sg.issue_w(p, smem, cur ^ 1);
 #endif
 #endif
         const char* As = smem + cur * STAGE;
         const char* Bs = As + BM * 128;
-#if !defined(VDX_STAMPS) || VDX_ABL == 7       // (the stamped builds keep the plain loop below unless ablation 7 asks for this one)
+#if !defined(VDX_STAMPS) || VDX_ABL_IS(7)       // (the stamped builds keep the plain loop below unless ablation 7 asks for this one)
         if constexpr (TM == 4 && TN == 10 && !defined_gemm_plain_loop) {
             // ---- the 64x160 wave tile: ROLLING fragment prefetch.  A K half is two groups of 20 MFMAs (column tiles 0-4, 5-9)
             // walked column-major, so a weight fragment is dead after four MFMAs and the read of the fragment that takes its
@@ -312,12 +310,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmP p) {
             __builtin_amdgcn_sched_group_barrier(0x008, 20, 0);
         } else
 #endif
-#if defined(VDX_STAMPS) && VDX_ABL == 1         // diagnostic ablation 1: DMA only, no LDS reads / MFMA
+#if VDX_ABL_IS(1)         // diagnostic ablation 1: DMA only, no LDS reads / MFMA
         if (false)
 #endif
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-#if !(defined(VDX_STAMPS) && (VDX_ABL == 2 || VDX_ABL == 6))
+#if !(VDX_ABL_IS(2) || VDX_ABL_IS(6))
             if (SPLIT && ks == 1 && more && does_w) sg.issue_w(p, smem, cur ^ 1);
 #endif
             f16x8 af[TM];
@@ -755,13 +753,5 @@ extern "C" int vdx_gemm_plan_ksplit(const vdx_gemm_args* a, int32_t* split_row, 
     return 0;
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_gemm(void) {
-#if defined(VDX_STAMPS) || (defined(VDX_ABL) && VDX_ABL) || defined(VDX_GEMM_PLAIN_LOOP)
-    return 1;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_gemm(void) { return VDX_LAB_GEMM; }

@@ -24,12 +24,10 @@
 // LDS traffic per MFMA is the same as in the tiled kernel; L2 -> LDS traffic drops from (A + W) per tile to
 // A only, and there is no per-tile prologue/epilogue bubble.
 #include "gemm_common.h"
+#include "lab.h"
 
 #ifdef VDX_STAMPS   // diagnostic build only: per-block cycle totals of wave 0 (wait+barrier, DMA issue, compute+epilogue)
-static __device__ unsigned long long g_ws_stamps[256 * 4];
-extern "C" int vdx_debug_read_ws_stamps(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_ws_stamps), sizeof(unsigned long long) * 256 * 4) == hipSuccess ? 0 : -1;
-}
+VDX_STAMP_BUFFER(g_ws_stamps, vdx_debug_read_ws_stamps, 256 * 4)
 #define WS_T() __builtin_amdgcn_s_memtime()
 #endif
 
@@ -403,13 +401,5 @@ int vdx_gemm_ws_launch(const GemmP& p, int family, bool geglu, const GemmSink& t
     return vdx_fail("gemm_ws: shape not supported");
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_gemm_ws(void) {
-#if defined(VDX_STAMPS) || defined(VDX_WS_NS3)
-    return 2;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_gemm_ws(void) { return VDX_LAB_GEMM_WS; }

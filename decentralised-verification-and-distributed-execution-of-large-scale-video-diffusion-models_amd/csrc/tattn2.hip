@@ -28,6 +28,7 @@
 // The row image, the weight ring and the output projection are shared with K5 (xattn.hip) and K8 (ff_fused.hip), which
 // were built on this kernel: they live in rowtile_common.h.  Here: the step schedule, the wait model, the attention.
 #include "rowtile_common.h"
+#include "lab.h"
 
 namespace {
 
@@ -57,10 +58,7 @@ __device__ __forceinline__ float k7b_quad_sum(float v) { return quad_sum(v); }
 #endif
 
 #ifdef K7B_STAMPS   // diagnostic build only: cycle totals per (step kind, segment) of wave 0; never in the product library
-static __device__ unsigned long long g_k7b_stamps[1024 * 16];
-extern "C" int vdx_debug_read_k7b_stamps(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_k7b_stamps), sizeof(g_k7b_stamps)) == hipSuccess ? 0 : -1;
-}
+VDX_STAMP_BUFFER(g_k7b_stamps, vdx_debug_read_k7b_stamps, 1024 * 16)
 #ifndef K7B_SS
 #define K7B_SS 0
 #define K7B_SE 1000
@@ -606,13 +604,5 @@ extern "C" int vdx_temporal_attn_block2_f16(const void* t, int ldt, const void* 
     return vdx_launch_status("vdx_temporal_attn_block2_f16");
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_tattn2(void) {
-#if defined(K7B_STAMPS) || defined(K7B_ABL_NOROWS) || defined(K7B_ABL_NOEPI) || defined(K7B_ABL_NOATT) || defined(K7B_ABL_NOWDMA)
-    return 8;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_tattn2(void) { return VDX_LAB_TATTN2; }

@@ -26,13 +26,11 @@
 //   inner 512 (transformer_in): NRG 2, NCH 2 — 96 rows per block, 24 KB stages, 2-deep ring
 // F must divide 48 (the BASELINE chunks: 24, 16, 12; also 8, 6, 4, 3, 2, 1); other shapes take the un-fused kernels.
 #include "rowtile_common.h"
+#include "lab.h"
 
 #ifdef VDX_STAMPS   // diagnostic build only (make stamps): per-block phase cycle totals of one wave; never in the product library
-static __device__ unsigned long long g_k7_stamps[4096 * 8];
-extern "C" int vdx_debug_read_k7_stamps(void* dst) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_k7_stamps), sizeof(unsigned long long) * 4096 * 8) == hipSuccess ? 0 : -1;
-}
-#define K7_T(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_[i] += now_ - last_; last_ = now_; }
+VDX_STAMP_BUFFER(g_k7_stamps, vdx_debug_read_k7_stamps, 4096 * 8)
+#define K7_T(i) VDX_STAMP_ACC(st_[i], last_)
 #define K7_STAMP_ACC(i, a, b, c) { asm volatile("" ::"v"(a), "v"(b), "v"(c)); K7_T(i) }
 #else
 #define K7_T(i)
@@ -58,11 +56,6 @@ extern "C" int vdx_debug_read_k7_stamps(void* dst) {
         __builtin_amdgcn_sched_group_barrier(0x008, (NMFMA) >= 36 ? 2 : 1, 0);                 \
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     /* DS read */                    \
     }
-#ifdef K7_DBG_XBAR
-#define K7_DBG_STEP_END { __builtin_amdgcn_s_waitcnt(0xC07F); wg_barrier(); }
-#else
-#define K7_DBG_STEP_END
-#endif
 
 namespace {
 
@@ -145,15 +138,11 @@ struct K7 {
         // (asm statements only order MEMORY operations: without this the waits and the barrier below were scheduled
         // above the previous step's register-only MFMAs, i.e. the wave waited for its fragment reads before multiplying)
         __builtin_amdgcn_sched_barrier(0);
-#ifdef K7_DBG_VM0
-        wait_vm<0>();
-#else
         if (NS == 3) {
             if (s + 2 < NST) wait_vm<PPW>(); else wait_vm<0>();     // (stage s+2 may still be in flight)
         } else {
             wait_vm<0>();
         }
-#endif
         // my LDS accesses are done before I signal.  The BUILTIN form: the compiler's wait-count pass sees it and knows
         // the fragment registers read last step are valid (behind an asm wait it re-waited lgkmcnt(0) after issuing
         // this step's reads, which put their latency in front of the MFMAs)
@@ -256,11 +245,7 @@ struct K7 {
 #else
 #pragma unroll
                 for (int j = 0; j < CPL; ++j)
-#ifdef K7_EXP_NT
-                    v[ps][j] = __builtin_nontemporal_load((const f16x8*)(src + j * step));
-#else
                     v[ps][j] = *(const f16x8*)(src + j * step);
-#endif
 #endif
             }
 #pragma unroll
@@ -355,7 +340,6 @@ struct K7 {
             ++s_idx;                                                                                          \
             slot = ns_;                                                                                       \
             K7_STAMP_ACC(2, aq[0][0], ak[2][3], av[2][3])                                                     \
-            K7_DBG_STEP_END                                                                                   \
         }
 #pragma unroll
         for (int hg = 0; hg < NHG; ++hg) {                       // (unrolled: ohead must be indexed statically)
@@ -487,7 +471,6 @@ struct K7 {
             ++s_idx;                                                                                          \
             slot = ns_;                                                                                       \
             K7_STAMP_ACC(6, acc[0][0], acc[2][CG - 1], acc[1][0])                                             \
-            K7_DBG_STEP_END                                                                                   \
         }
 #pragma unroll 1
         for (int cg = 0; cg < NCG; ++cg) {
@@ -603,13 +586,5 @@ extern "C" int vdx_temporal_attn_block_f16(const void* t, int ldt, const void* g
     return launch_k7<512, 2, 2>(p, st);
 }
 
-// Lab variants of this translation unit (phase stamps, ablations: timing only, some give WRONG results) are compiled in only
-// under the macros below; a library that carries one says so through vdx_build_flags() and vdx/_lib.py refuses to load it
-// as the product.
-extern "C" int vdx_lab_tattn_fused(void) {
-#if defined(VDX_STAMPS) || defined(K7_ABL_NOP0) || defined(K7_ABL_NOMFMA) || defined(K7_ABL_NOEPI) || defined(K7_ABL_NODMA) || defined(K7_ABL_NOATT)
-    return 4;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_tattn_fused(void) { return VDX_LAB_TATTN_FUSED; }

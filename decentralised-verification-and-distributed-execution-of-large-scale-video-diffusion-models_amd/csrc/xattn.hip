@@ -17,6 +17,7 @@
 //     5-unit weight ring are rowtile_common.h's; the counted s_waitcnt scheme is tattn2's (see the comments there).
 // Built for inner 320 (level 0: 5 cross-attentions per forward).
 #include "rowtile_common.h"
+#include "lab.h"
 
 namespace {
 
@@ -461,11 +462,5 @@ extern "C" int vdx_cross_attn_block_f16(const void* t, int ldt, const void* pack
     return vdx_launch_status("vdx_cross_attn_block_f16");
 }
 
-// Lab variants (timing only, wrong results) are compiled in only under the macro below; vdx_build_flags() reports them.
-extern "C" int vdx_lab_xattn(void) {
-#if defined(K5_ABL_NOATT)
-    return 128;
-#else
-    return 0;
-#endif
-}
+// Lab variants of this translation unit are compiled in only under the switches that lab.h lists for it.
+extern "C" int vdx_lab_xattn(void) { return VDX_LAB_XATTN; }

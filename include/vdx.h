@@ -34,7 +34,7 @@ const char* vdx_last_error(void);
 int vdx_version(void);
 /* 0 for the product build.  Non-zero: some translation unit was compiled with a lab macro (phase stamps, ablations — timing
  * only, some variants compute wrong results); bit = unit (1 gemm, 2 gemm_ws, 4 tattn_fused, 8 tattn2, 16 flash, 32 ff_fused,
- * 64 conv_fused, 128 xattn).  The Python binding refuses such a library unless VDX_ALLOW_LAB_BUILD=1 (the lab tools set it). */
+ * 64 conv_fused, 128 xattn; csrc/lab.h lists every unit's switches).  The Python binding refuses such a library unless VDX_ALLOW_LAB_BUILD=1 (the lab tools set it). */
 int vdx_build_flags(void);
 
 /* ------------------------------------------------------------------------------------------

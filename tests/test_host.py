@@ -559,6 +559,82 @@ def test_k8_counted_waits_match_the_emitted_isa(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def _lab_lists(lab_h):
+    """{unit: (bit, switches)} from csrc/lab.h: the `#if` chain in front of every `#define VDX_LAB_<UNIT> <bit>`."""
+    text = lab_h.replace("\\\n", " ")
+    found = re.findall(r"^#if (.*)\n#define VDX_LAB_(\w+) (\d+)\n#else\n#define VDX_LAB_\2 0\n#endif$", text, re.M)
+    return {unit.lower(): (int(bit), set(re.findall(r"\bdefined\((\w+)\)", cond))) for cond, unit, bit in found}
+
+
+def _tested_macros(text, header):
+    """Every identifier that `text` tests with #if / #ifdef / #ifndef / #elif / defined(), but for a header's include guard."""
+    text = re.sub(r"/\*.*?\*/", " ", text.replace("\\\n", " "), flags=re.S)
+    text = re.sub(r"//.*", "", text)
+    names = set()
+    for rest in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, re.M):
+        names |= set(re.findall(r"\b[A-Za-z_]\w*", rest)) - {"defined"}
+    guard = re.search(r"\A\s*#[ \t]*ifndef[ \t]+(\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1[ \t]*\n", text)
+    if header and guard:
+        names.discard(guard.group(1))
+    # lab.h's VDX_ABL_IS(n) is a test of VDX_ABL
+    return {"VDX_ABL" if n == "VDX_ABL_IS" else n for n in names}
+
+
+def lab_switch_errors(csrc):
+    """What is wrong between the macros that the sources under `csrc` test and lab.h's lists (nothing: [])."""
+    read = lambda name: open(os.path.join(csrc, name)).read()  # noqa: E731
+    lists = _lab_lists(read("lab.h"))
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")) and f != "lab.h")
+    includes = {f: set(re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([\w.]+)"', read(f), re.M)) & set(files) for f in files}
+
+    def closure(f):
+        seen, todo = set(), [f]
+        while todo:
+            for g in includes[todo.pop()] - seen:
+                seen.add(g)
+                todo.append(g)
+        return seen
+
+    units = {f[:-4]: {f} | closure(f) for f in files if f.endswith(".hip")}     # a unit is a .hip file and what it includes
+    errors = []
+    for f in files:
+        for name in sorted(_tested_macros(read(f), f.endswith(".h"))):
+            for unit in sorted(u for u, members in units.items() if f in members):
+                if unit not in lists:
+                    errors.append(f"{f} tests {name}, and lab.h has no list for unit {unit}")
+                elif name not in lists[unit][1]:
+                    errors.append(f"{f} tests {name}, which lab.h's list for {unit} lacks")
+    for unit, (bit, switches) in sorted(lists.items()):
+        if unit not in units:
+            errors.append(f"lab.h lists a unit {unit} that has no {unit}.hip")
+            continue
+        text = "\n".join(read(f) for f in units[unit]).replace("VDX_ABL_IS", "VDX_ABL")
+        errors += [f"lab.h lists {s} for {unit}, which none of its files uses" for s in sorted(switches) if not re.search(r"\b%s\b" % s, text)]
+    return errors
+
+
+def test_lab_switches_are_all_listed_in_lab_h():
+    """The guard below only holds if vdx_lab_<unit>() knows every switch that changes its unit.  csrc/lab.h is that list
+    (one `#if` chain per unit in front of `#define VDX_LAB_<UNIT> <bit>`).  Plain text, no compiler: every macro that a
+    csrc/*.hip or csrc/*.h tests (#if, #ifdef, #ifndef, #elif, defined(); include guards apart) stands in the list of the
+    file's unit — for a header, of every unit that includes it — and lab.h lists nothing that its unit's files do not use.
+    The bits are the ones include/vdx.h documents, and every vdx_lab_<unit>() returns lab.h's macro and nothing else."""
+    csrc = os.path.join(ROOT, "decentralised-verification-and-distributed-execution-of-large-scale-video-diffusion-models_amd", "csrc")
+    lists = _lab_lists(open(os.path.join(csrc, "lab.h")).read())
+    assert {u: b for u, (b, _) in lists.items()} == {"gemm": 1, "gemm_ws": 2, "tattn_fused": 4, "tattn2": 8, "flash": 16,
+                                                     "ff_fused": 32, "conv_fused": 64, "xattn": 128}
+    doc = open(os.path.join(ROOT, "include", "vdx.h")).read()
+    assert all(f"{b} {u}" in doc for u, (b, _) in lists.items()), "include/vdx.h documents other bits"
+    errors = lab_switch_errors(csrc)
+    assert not errors, "\n".join(errors)
+    for unit in lists:
+        src = open(os.path.join(csrc, unit + ".hip")).read()
+        assert 'extern "C" int vdx_lab_%s(void) { return VDX_LAB_%s; }' % (unit, unit.upper()) in src, unit
+    # the scan itself: comments, a helper's alias, a defaulted value, and a header's include guard
+    assert _tested_macros("#if !defined(A_B) || VDX_ABL_IS(7)  // C\n#ifndef D /* E */\n#define D 0\n#elif F > 2\n", False) == {"A_B", "VDX_ABL", "D", "F"}
+    assert _tested_macros("#ifndef G_H\n#define G_H\n#ifdef I\n", True) == {"I"}
+
+
 def test_lab_build_is_refused_as_the_product(tmp_path):
     """`VDX_LIB_PATH` must not slip a stamps / ablation library (timing-only code paths, some with wrong
     results) into the product.  A library whose conv_fused unit is compiled with -DK1_ABL_NONORM reports it through

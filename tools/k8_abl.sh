@@ -1,6 +1,7 @@
 #!/bin/bash
 # Dev tool: timing-only builds of csrc/ff_fused.hip with parts of the tile removed (-DK8_ABL_*; wrong results), linked
 # against the product's other objects into csrc/build/abl/libvdx_hip_<tag>.so (git-ignored, travels to the GPU box).  Usage: tools/k8_abl.sh TAG "-DK8_ABL_X ..."
+# Time it with: VDX_LIB_PATH=<that library> tools/kernel_time.py k8
 set -e
 cd "$(dirname "$0")/.."
 CS=$(ls -d dec*/csrc)

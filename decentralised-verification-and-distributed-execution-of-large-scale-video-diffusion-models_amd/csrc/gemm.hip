@@ -5,7 +5,8 @@
 // One kernel template serves every contraction of the 3D-UNet:
 //   MODE 0  plain rows (Linear, 1x1 shortcut conv; optional 2-source channel concat)
 //   MODE 1  3x3 conv, pad 1 (or (0,1,0,1) at stride 2: Downsample2D(padding=0)), stride 1|2, optional nearest-x2
-//           upsample folded into the gather
+//           upsample folded into the gather; or its PHASE form (upsample = 3): four 2x2 convs on the source image, one
+//           per output parity, K = 4*C instead of 9*C (the Stager's setup below)
 //   MODE 2  temporal 3-tap conv (Conv3d (3,1,1)), zero padded at the chunk's first/last frame
 // Data layout: activations channels-last rows [pixels][C] so a K-slice of 64 channels of one
 // row is one 128-byte line; weights [N][K] with K = tap*C + c.
@@ -57,15 +58,33 @@ struct Stager {
     int d0[ACH], d1[ACH];   // MODE 0: source row | MODE 1: image base row, (y+1)<<16|(x+1) | MODE 2: row, frame
     int wrow0, csw, iwave;
     int tap, kc, kw;        // the NEXT K tile to be issued (kw = its first weight column)
+    int ky, kx, tw;         // MODE 1: its tap as (row, column) of the tw x tw window (tw = p.tapw) — wave-uniform counters
+    const f16* wb;          // weight table of this tile (MODE 1 phase form: the tile's phase)
 
     __device__ __forceinline__ void setup(const GemmP& p, int tid, int m0, int n0) {
         const int it = SPLIT ? (tid & (IT - 1)) : tid;
         const int prow = it >> 3;
         iwave = __builtin_amdgcn_readfirstlane(it >> 6);
         csw = ((it & 7) ^ (prow & 7)) * 8;    // element offset of the data chunk this slot fetches
+        // MODE 1 phase form (p.ph_pad > 0): nearest-x2 + conv3x3 = four 2x2 convs on the SOURCE image, one per output
+        // parity (a, b).  Rows are virtual and phase-major: v -> phase v / ph_pad, source pixel v % ph_pad (valid below
+        // ph_src; clamped for the gather, never stored).  ph_pad is a multiple of 256 and tiles start at multiples of
+        // their height, so a tile has ONE phase: its weight table is p.w + phase*N*K, and tap (ty, tx) of output
+        // (2i+a, 2j+b) reads source (i + a - 1 + ty, j + b - 1 + tx) — the (y+1, x+1) of d1 moved by (a, b).  The zero
+        // padding of the upsampled image is the zero padding of the source image.  (p.h_out, p.w_out are the source's.)
+        int ph_a = 0, ph_b = 0, ph_m0 = 0;
+        wb = p.w;
+        if (MODE == 1 && p.ph_pad) {
+            const int phase = m0 / p.ph_pad;
+            ph_a = phase >> 1;
+            ph_b = phase & 1;
+            ph_m0 = phase * p.ph_pad;
+            wb = p.w + (size_t)phase * p.N * p.K;
+        }
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
-            const int mm = min(m0 + prow + i * RPP, p.M - 1);
+            int mm = min(m0 + prow + i * RPP, p.M - 1);
+            if (MODE == 1 && p.ph_pad) mm = min(mm - ph_m0, p.ph_src - 1);
             if (MODE == 0) {
                 d0[i] = mm;
                 d1[i] = 0;
@@ -74,7 +93,7 @@ struct Stager {
                 const int n = mm / per, rem = mm - n * per;
                 const int yo = rem / p.w_out, xo = rem - yo * p.w_out;
                 d0[i] = n * p.h_in * p.w_in;
-                d1[i] = ((yo * p.stride + p.pad_shift) << 16) | (xo * p.stride + p.pad_shift);
+                d1[i] = ((yo * p.stride + p.pad_shift + ph_a) << 16) | (xo * p.stride + p.pad_shift + ph_b);
             } else {
                 d0[i] = mm;
                 d1[i] = (mm / p.hw) % p.frames;
@@ -84,6 +103,8 @@ struct Stager {
         // that after the MFMA a lane owns 8 consecutive output columns (RPP % 32 == 0: same for every i).
         wrow0 = n0 + ((((prow >> 2) & 3) << 3) | (((prow >> 4) & 1) << 2) | (prow & 3)) + (prow & ~31);
         tap = kc = kw = 0;
+        ky = kx = 0;
+        tw = p.tapw;
     }
     // weight rows of the next K tile -> stage buffer `buf`
     __device__ __forceinline__ void issue_w(const GemmP& p, char* smem, int buf) {
@@ -91,7 +112,7 @@ struct Stager {
 #pragma unroll
         for (int i = 0; i < BCH; ++i) {
             const int r = min(wrow0 + i * RPP, p.N - 1);
-            __builtin_amdgcn_global_load_lds((gptr_t)(p.w + (size_t)r * p.K + kw + csw), (lptr_t)(sb + i * RPP * 128), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)(wb + (size_t)r * p.K + kw + csw), (lptr_t)(sb + i * RPP * 128), 16, 0, 0);
         }
     }
     // (gathered) activation rows of the next K tile -> stage buffer `buf`
@@ -106,7 +127,6 @@ struct Stager {
             for (int i = 0; i < ACH; ++i)
                 __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)d0[i] * ld), (lptr_t)(sa + i * RPP * 128), 16, 0, 0);
         } else if (MODE == 1) {
-            const int ky = tap / 3, kx = tap - ky * 3;
             const int hlim = p.h_up, wlim = p.w_up;
 #pragma unroll
             for (int i = 0; i < ACH; ++i) {
@@ -138,20 +158,34 @@ struct Stager {
         if (MODE == 0) {
             kc = kw;
         } else {
-            constexpr int T = MODE == 1 ? 9 : 3;
+            constexpr int T = MODE == 1 ? 9 : 3;      // (split-K slices: never the phase form)
             const int slice = kt / T;
             tap = kt - slice * T;
             kc = slice * 64;
+            if (MODE == 1) {
+                ky = tap / 3;
+                kx = tap - ky * 3;
+            }
         }
     }
     __device__ __forceinline__ void advance() {
         // K order of the gathers is (64-channel slice, tap, channel): all taps of one channel slice are
         // consumed back to back, so the shifted re-reads of the same source pixels hit the XCD's L2
         // (tap-major order streamed ~0.5 MB per CU between re-uses and thrashed it: 7.5x re-fetch).
+        // MODE 1 walks a tw x tw window (3: the nine taps; 2: the phase form's four) with scalar counters: the
+        // window is run-time, the lanes never branch on it.
         kw += 64;
         if (MODE == 0) {
             kc += 64;
-        } else if (++tap == (MODE == 1 ? 9 : 3)) {
+        } else if (MODE == 1) {
+            if (++kx == tw) {
+                kx = 0;
+                if (++ky == tw) {
+                    ky = 0;
+                    kc += 64;
+                }
+            }
+        } else if (++tap == 3) {
             tap = 0;
             kc += 64;
         }
@@ -358,7 +392,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmP p) {
             for (int j = 0; j < TN; ++j) *(f32x4*)(dst + (i * TN + j) * NT * 4) = acc[i][j];
         return;
     }
-    gemm_epilogue<TM, TN, GEGLU>(p, acc, m0 + wm * WTM, n0 + wn * WTN, frow, fq, gelu);
+    gemm_epilogue<TM, TN, GEGLU, MODE == 1>(p, acc, m0 + wm * WTM, n0 + wn * WTN, frow, fq, gelu);
 #ifdef VDX_STAMPS
     __builtin_amdgcn_s_waitcnt(0);        // stores drained
     STAMP(3);
@@ -471,21 +505,22 @@ static int nt320_of(int N) { return (N + 319) / 320; }
 // N fills 320-wide tiles: the masked tail wastes < 25 % of the last column of tiles
 static bool fills320(int N) { return nt320_of(N) * 320 * 4 <= N * 5; }
 static bool fits320(long long rows, int N) { return fills320(N) && rows >= 1024; }   // (swapped V^T products have M = C)
-static TileChoice choose_tile(long long rows, int N) {
+// ring_ok = false (the phase-form gather, which only the tiled gemm_kernel families carry): variant 8 is not a candidate
+static TileChoice choose_tile(long long rows, int N, bool ring_ok = true) {
     const int nt320 = nt320_of(N);
     const long long t1 = ((rows + 127) / 128) * ((N + 127) / 128);
     const long long c1 = 3 * ((t1 + 255) / 256);
     if (!fits320(rows, N)) return TileChoice{N > 64 ? 1 : 5, c1};
     const long long t256 = ((rows + 255) / 256) * nt320, t128 = ((rows + 127) / 128) * nt320;
     const long long c2 = 10 * ((t256 + 255) / 256), c8 = 8 * ((t128 + 255) / 256);
-    if (c2 <= c8 && c2 <= c1) return TileChoice{2, c2};
-    return c8 <= c1 ? TileChoice{8, c8} : TileChoice{1, c1};
+    if (c2 <= c1 && (c2 <= c8 || !ring_ok)) return TileChoice{2, c2};
+    return c8 <= c1 && ring_ok ? TileChoice{8, c8} : TileChoice{1, c1};
 }
 // Row at which to split a product into [begin, split) on 256x320 tiles (whole rounds of 256) + [split, end) on whatever
 // suits the rest, or 0: the last round of a 256x320 launch is otherwise as slow as a full one however few tiles it has.
-static int choose_split(int begin, int end, int N) {
+static int choose_split(int begin, int end, int N, bool ring_ok = true) {
     const long long rows = end - begin;
-    const TileChoice whole = choose_tile(rows, N);
+    const TileChoice whole = choose_tile(rows, N, ring_ok);
     const int nt320 = nt320_of(N);
     // (also when the WHOLE product prefers small tiles — 18 432 rows x 1280: 288 big tiles = two rounds for 1.125 — whole
     // rounds of big tiles + a small-tile tail can still win: one round at 1.2 PFLOP/s + 160 small tiles)
@@ -503,7 +538,7 @@ static int choose_split(int begin, int end, int N) {
     if (mt_main == 0) return 0;
     const int split = begin + (int)(mt_main * 256);
     if (split >= end) return 0;
-    const TileChoice tail = choose_tile(end - split, N);
+    const TileChoice tail = choose_tile(end - split, N, ring_ok);
     const long long cost = 10 * ((mt_main * nt320 + 255) / 256) + tail.cost + 1;   // + 1: the second launch's ramp
     return cost * 100 <= whole.cost * 94 ? split : 0;      // (measured in the step at 24 / 16 / 12 frames: 94 >= 100 >= 104 > 110)
 }
@@ -517,16 +552,28 @@ struct GemmRoute {
     int mode;       // MODE (a GEGLU product is plain)
     bool geglu;     // GEGLU
     int var;        // VAR: 0 | 1 split-K slices + reduction (p.ksplit > 1; v == 2) | 2 the upsample-to-size gather
+    bool phase;     // the phase-form gather (upsample = 3): VAR 0 of the tiled gemm_kernel families only (v in 1 2 5 6 9)
     bool forced;    // the caller pinned the variant
     bool whole;     // the call covers the whole product (row_begin / row_end unset or [0, M))
 };
+// Rows the kernels walk, and the unit of row_begin / row_end.  The phase form (conv3x3, upsample = 3) walks 4 phases of the
+// source pixels padded to whole 256-row tiles; everything else walks the M output rows.
+static bool gemm_is_phase(const vdx_gemm_args* a) { return a->mode == VDX_GEMM_CONV3X3 && a->upsample == 3; }
+static int gemm_rows(const vdx_gemm_args* a) { return gemm_is_phase(a) ? 4 * ((a->M / 4 + 255) / 256 * 256) : a->M; }
+
 static int gemm_route(const vdx_gemm_args* a, const GemmP& p, GemmRoute& r) {
     const int force = (a->epilogue >> 8) & 15;   // kernel variant override (0 = automatic)
     r = GemmRoute{};
     r.geglu = (a->epilogue & VDX_EPI_GEGLU) != 0;
     r.mode = a->mode;
     r.forced = force != 0;
-    r.whole = a->row_begin == 0 && (a->row_end == 0 || a->row_end == a->M);
+    r.phase = p.ph_pad != 0;
+    r.whole = a->row_begin == 0 && (a->row_end == 0 || a->row_end == gemm_rows(a));
+    if (r.phase) {
+        VDX_CHECK(force == 0 || force == 1 || force == 2 || force == 5 || force == 6 || force == 9,
+                  "gemm: the phase-form gather (upsample = 3) runs on the tiled kernels only (variant %d)", force);
+        VDX_CHECK(a->ksplit <= 1, "gemm: the phase-form gather (upsample = 3) takes no split-K (ksplit = %d)", a->ksplit);
+    }
     r.var = p.ksplit > 1 ? 1 : (a->mode == VDX_GEMM_CONV3X3 && a->upsample == 2) ? 2 : 0;
     // short-K Linear layers on many rows (levels 0/1, transformer_in): weights-stationary streaming kernels
     // (variant 7 pins them); they walk whole products only
@@ -556,7 +603,7 @@ static int gemm_route(const vdx_gemm_args* a, const GemmP& p, GemmRoute& r) {
     } else if (r.ws) {
         r.v = 7;
     } else {
-        r.v = force ? force : choose_tile(p.M - p.m_begin, p.N).v;
+        r.v = force ? force : choose_tile(p.M - p.m_begin, p.N, !r.phase).v;
     }
     return 0;
 }
@@ -601,10 +648,12 @@ static int gemm_run(const GemmP& p, const GemmRoute& r, const GemmSink& to) {
 static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, GemmRoute& r) {
     VDX_CHECK(a && a->a && a->w && a->out, "gemm: null pointer");
     VDX_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "gemm: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
-    VDX_CHECK(a->N % 64 == 0 && a->K % 64 == 0, "gemm: N=%d and K=%d must be multiples of 64", a->N, a->K);
+    const bool phase = gemm_is_phase(a);
+    // (the phase form runs on the tiled kernels only, which mask columns in groups of 8)
+    VDX_CHECK(a->N % (phase ? 8 : 64) == 0 && a->K % 64 == 0, "gemm: N=%d must be a multiple of %d and K=%d of 64", a->N, phase ? 8 : 64, a->K);
     VDX_CHECK(a->c1 > 0 && a->c1 % 64 == 0 && a->c2 % 64 == 0, "gemm: c1=%d c2=%d must be multiples of 64", a->c1, a->c2);
     VDX_CHECK((a->c2 == 0) == (a->a2 == nullptr), "gemm: a2/c2 mismatch");
-    const int taps = a->mode == VDX_GEMM_CONV3X3 ? 9 : a->mode == VDX_GEMM_TCONV3 ? 3 : 1;
+    const int taps = phase ? 4 : a->mode == VDX_GEMM_CONV3X3 ? 9 : a->mode == VDX_GEMM_TCONV3 ? 3 : 1;
     VDX_CHECK(a->K == taps * (a->c1 + a->c2), "gemm: K=%d != taps*(c1+c2)=%d", a->K, taps * (a->c1 + a->c2));
     VDX_CHECK(a->lda % 8 == 0 && a->ldo % 8 == 0 && (a->a2 == nullptr || a->lda2 % 8 == 0) &&
                   (a->residual == nullptr || a->ldr % 8 == 0),
@@ -613,15 +662,22 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, GemmRoute& r) {
     p.a = (const f16*)a->a; p.a2 = (const f16*)a->a2; p.w = (const f16*)a->w;
     p.bias = (const f16*)a->bias; p.bias2 = (const f16*)a->bias2; p.res = (const f16*)a->residual;
     p.out = (f16*)a->out;
-    VDX_CHECK(a->row_begin >= 0 && (a->row_end == 0 || (a->row_end > a->row_begin && a->row_end <= a->M)) && a->row_begin < a->M,
-              "gemm: rows [%d, %d) of %d", a->row_begin, a->row_end, a->M);
+    const int rows = gemm_rows(a);
+    VDX_CHECK(a->row_begin >= 0 && (a->row_end == 0 || (a->row_end > a->row_begin && a->row_end <= rows)) && a->row_begin < rows,
+              "gemm: rows [%d, %d) of %d", a->row_begin, a->row_end, rows);
     // (kernels mask rows >= p.M: the end of the row range; geometry checks below use the whole product's a->M)
-    p.M = a->row_end ? a->row_end : a->M; p.m_begin = a->row_begin; p.N = a->N; p.K = a->K; p.c1 = a->c1; p.c2 = a->c2;
+    p.M = a->row_end ? a->row_end : rows; p.m_begin = a->row_begin; p.N = a->N; p.K = a->K; p.c1 = a->c1; p.c2 = a->c2;
     p.lda = a->lda; p.lda2 = a->lda2; p.ldo = a->ldo; p.ldr = a->ldr;
     p.h_in = a->h_in; p.w_in = a->w_in; p.h_out = a->h_out; p.w_out = a->w_out;
     p.stride = a->stride; p.pad_shift = a->pad_mode; p.ups = a->upsample;     // (the gathers shift by ups: 0 | 1; ups == 2 runs the VAR = 2 kernels)
     p.h_up = a->upsample == 1 ? 2 * a->h_in : a->upsample == 2 ? a->h_out : a->h_in;
     p.w_up = a->upsample == 1 ? 2 * a->w_in : a->upsample == 2 ? a->w_out : a->w_in;
+    p.tapw = 3; p.ph_src = 0; p.ph_pad = 0;
+    if (phase) {        // four 2x2 convs on the source image: no shift, the source's own limits, its own grid of pixels
+        p.ups = 0; p.tapw = 2;
+        p.h_out = a->h_in; p.w_out = a->w_in;
+        p.ph_src = a->M / 4; p.ph_pad = rows / 4;
+    }
     p.usy = a->h_in > 0 && p.h_up > 0 ? (float)a->h_in / (float)p.h_up : 1.0f;
     p.usx = a->w_in > 0 && p.w_up > 0 ? (float)a->w_in / (float)p.w_up : 1.0f;
     p.frames = a->frames; p.hw = a->hw; p.rpb2 = a->rows_per_bias2 > 0 ? a->rows_per_bias2 : 1;
@@ -645,7 +701,13 @@ static int gemm_prepare(const vdx_gemm_args* a, GemmP& p, GemmRoute& r) {
             VDX_CHECK(a->stride == 1 || a->stride == 2, "gemm: stride %d", a->stride);
             VDX_CHECK(a->h_in > 0 && a->w_in > 0 && a->h_out > 0 && a->w_out > 0, "gemm: conv geometry");
             VDX_CHECK(a->M % (a->h_out * a->w_out) == 0, "gemm: M=%d not a whole number of %dx%d images", a->M, a->h_out, a->w_out);
-            {
+            if (phase) {
+                VDX_CHECK(a->stride == 1 && a->pad_mode == 0, "gemm: the phase-form gather (upsample = 3) needs stride 1 and pad_mode 0 (stride %d, pad_mode %d)", a->stride, a->pad_mode);
+                VDX_CHECK(a->h_out == 2 * a->h_in && a->w_out == 2 * a->w_in, "gemm: the phase-form gather (upsample = 3) is an exact x2: %dx%d -> %dx%d", a->h_in, a->w_in, a->h_out, a->w_out);
+                VDX_CHECK(!a->bias2 && !a->residual && !a->a2, "gemm: the phase-form gather (upsample = 3) takes no bias2 / residual / second source");
+                VDX_CHECK(a->row_begin % 256 == 0, "gemm: the phase-form gather (upsample = 3) starts at whole 256-row tiles (row_begin %d)", a->row_begin);
+                VDX_CHECK(a->wset_rows == 0, "gemm: the phase-form gather (upsample = 3) takes no weight sets");
+            } else {
                 VDX_CHECK(a->upsample >= 0 && a->upsample <= 2 && (a->upsample == 0 || a->stride == 1), "gemm: upsample %d with stride %d", a->upsample, a->stride);
                 VDX_CHECK(a->upsample != 2 || (a->h_out >= a->h_in && a->w_out >= a->w_in), "gemm: upsample-to-size target smaller than the source");
                 VDX_CHECK(a->pad_mode == 0 || a->pad_mode == 1, "gemm: pad_mode %d", a->pad_mode);
@@ -708,7 +770,7 @@ extern "C" int vdx_gemm_plan(const vdx_gemm_args* a, int32_t* variant, int32_t* 
     GemmRoute r;
     if (const int rc = gemm_prepare(a, p, r)) return rc;
     *variant = r.v;
-    *split_row = r.forced || r.v == 7 || r.var == 1 ? 0 : choose_split(p.m_begin, p.M, p.N);
+    *split_row = r.forced || r.v == 7 || r.var == 1 ? 0 : choose_split(p.m_begin, p.M, p.N, !r.phase);
     return 0;
 }
 
@@ -723,7 +785,7 @@ extern "C" int vdx_gemm_plan_ksplit(const vdx_gemm_args* a, int32_t* split_row, 
     *split_row = 0; *ksplit = 0; *workspace_bytes = 0;
     if (r.v == 7 || r.geglu || r.forced || !r.whole) return 0;
     if (a->pad_mode != 0) return 0;     // gemm_route refuses split-K with pad_mode = 1
-    if (a->upsample == 2) return 0;     // no split-K instantiation carries the nearest-to-size gather (gemm_route refuses it)
+    if (a->upsample >= 2) return 0;     // no split-K instantiation carries the nearest-to-size gather or the phase form (gemm_route refuses them)
     const long long rows = p.M;
     const int nt320 = nt320_of(p.N), nk = p.K >> 6;
     if (!fits320(rows, p.N)) return 0;

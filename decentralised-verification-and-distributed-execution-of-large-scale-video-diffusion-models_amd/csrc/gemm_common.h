@@ -19,6 +19,9 @@ struct GemmP {
     float* partial;   //      fp32 accumulators in a slab of `partial`; vdx_gemm_reduce_kernel sums the slabs and runs the epilogue
     int wset_rows;    // > 0: one weight set (w + s*N*K, wset_bias + s*N) per `wset_rows` rows (weights-stationary kernels only)
     const float* wset_bias;
+    int tapw;         // conv3x3: width of the tap window the K loop walks — 3, or 2 in the phase form
+    int ph_src, ph_pad;   // conv3x3 phase form (vdx_gemm_args.upsample = 3; gemm.hip only), else 0: source pixels n*h_in*w_in and
+                          // that rounded up to 256.  M counts 4*ph_pad virtual rows, phase-major; h_out / w_out are the SOURCE's
 };
 
 // Where a routed call ends.  name == nullptr: the kernel is launched on `st`.  Otherwise nothing is launched and no GPU is
@@ -40,7 +43,9 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // waited for once: issued one by one next to their use, each load was a full serialized memory
 // round trip (20 per lane per tile), which is what the short-K layers' time went to.
 // GEGLU kernels pass the block's GELU table (GELU_TAB_BYTES of LDS, filled by gelu_tab_init before a barrier).
-template <int TM, int TN, bool GEGLU>
+// PHASE_OK (the 3x3 gathers of gemm.hip): the call may be in phase form (p.ph_pad > 0) — virtual row -> output row
+// n*4*h*w + (2i+a)*2*w + 2j+b, stored when its source pixel exists.  (The phase form takes no residual and no bias2.)
+template <int TM, int TN, bool GEGLU, bool PHASE_OK = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TM][TN], int mb, int nb, int frow, int fq,
                                               const float2* gelu = nullptr) {
     constexpr int NA = TN / 2;
@@ -61,7 +66,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TM][T
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = mb + i * 16 + frow;
-        const bool row_ok = m < p.M;
+        bool row_ok = m < p.M;
+        size_t orow = (size_t)m;
+        if (PHASE_OK && p.ph_pad) {
+            const int phase = mb / p.ph_pad, s = m - phase * p.ph_pad;
+            const int per = p.h_out * p.w_out;
+            const int n = s / per, rem = s - n * per;
+            const int yi = rem / p.w_out, xi = rem - yi * p.w_out;
+            row_ok = row_ok && s < p.ph_src;
+            orow = (size_t)n * 4 * per + (size_t)(2 * yi + (phase >> 1)) * 2 * p.w_out + 2 * xi + (phase & 1);
+        }
         f16x8 rv[NA], b2v[NA];
 #pragma unroll
         for (int a = 0; a < NA; ++a)
@@ -96,12 +110,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TM][T
                 f16x4 o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = (f16)(v[j] * gelu_tab(v[4 + j], gelu));
-                if (row_ok && n < p.N) *(f16x4*)(p.out + (size_t)m * p.ldo + (n >> 1)) = o;
+                if (row_ok && n < p.N) *(f16x4*)(p.out + orow * p.ldo + (n >> 1)) = o;
             } else {
                 f16x8 o;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = (f16)(v[j] + (float)b2v[a][j] + (float)rv[a][j]);
-                if (row_ok && n < p.N) *(f16x8*)(p.out + (size_t)m * p.ldo + n) = o;
+                if (row_ok && n < p.N) *(f16x8*)(p.out + orow * p.ldo + n) = o;
             }
         }
     }

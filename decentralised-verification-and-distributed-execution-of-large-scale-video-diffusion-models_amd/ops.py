@@ -142,9 +142,16 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     reduction (vdx_gemm_plan_ksplit) — faster on the 16-frame windows, not bit-identical to the unsplit order (the
     callers that rely on row-split bit-identity do not pass it).  `ksplit`: pin it for rows [row_begin, row_end).
     `wset_rows` / `wset_bias`: one weight set per `wset_rows` rows, w = [M / wset_rows][N][K] and an fp32 bias per set
-    (a GroupNorm folded into the Linear: `groupnorm_linear`)."""
+    (a GroupNorm folded into the Linear: `groupnorm_linear`).
+    `conv=(..., stride, upsample)` with upsample 3: nearest x2 in phase form — `w` is packing.pack_upconv_phase's
+    [4 * N][4 * c1] table; row ranges and the plan's split count its 4 * round_up(M / 4, 256) virtual rows (vdx.h)."""
     ar, c1, lda = _rows(a, "a")
     N, K = w.shape
+    phase = mode == CONV3X3 and int(conv[6]) == 3
+    if phase:
+        if N % 4:
+            raise VdxError("gemm: the phase form (upsample 3) takes a [4 * N][4 * c1] table")
+        N //= 4
     if wset_rows:
         if M % wset_rows or N % (M // wset_rows) or wset_bias is None or wset_bias.dtype != torch.float32:
             raise VdxError("gemm: wset_rows needs M % wset_rows == 0, w = [sets * N][K] and an fp32 wset_bias [sets][N]")
@@ -158,7 +165,7 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
     if a2 is not None:
         a2r, c2, lda2 = _rows(a2, "a2")
         g.lda2 = lda2
-    taps = {PLAIN: 1, CONV3X3: 9, TCONV3: 3}[mode]
+    taps = 4 if phase else {PLAIN: 1, CONV3X3: 9, TCONV3: 3}[mode]
     if K != taps * (c1 + c2):
         raise VdxError(f"gemm: K={K} != {taps}*(c1={c1}+c2={c2})")
     n_out = N // 2 if geglu else N
@@ -220,7 +227,7 @@ def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=
         if ks > 1:
             ws_ = _scratch(_KSPLIT_WS, out.device, wsb, torch.float32)
             g.workspace, g.workspace_bytes = ws_.data_ptr(), ws_.numel() * 4
-        rows = (re_ or M) - rb
+        rows = (re_ or (4 * round_up(M // 4, 256) if phase else M)) - rb
         name = _gemm_name(g) if PROFILE is not None else None     # only asked for when bench.py profiles
         with _timed(name, 2.0 * rows * N * K, (rows, N, K)):
             _launch("vdx_gemm_f16", C.byref(g))

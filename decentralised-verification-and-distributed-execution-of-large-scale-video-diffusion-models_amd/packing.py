@@ -38,6 +38,25 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     return _taps_slice_major(w.permute(0, 2, 3, 1).reshape(co, 9, ci))
 
 
+def pack_upconv_phase(w: torch.Tensor, dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """Conv2d weight [N][C][3][3] of a conv that follows a nearest-x2 upsample -> the PHASE table [4*N][4*C] (`dtype`).
+
+    Output pixel (2i+a, 2j+b) of conv3x3(nearest_x2(x)) sees only the 2x2 source pixels (i+a-1+ty, j+b-1+tx), ty, tx in
+    {0, 1} (zero outside the image: the padding of the upsampled image falls on the padding of the source), so the nine taps
+    collapse onto four whose weights are sums of the original ones:
+        a = 0: ty 0 <- ky 0, ty 1 <- ky 1 + ky 2        a = 1: ty 0 <- ky 0 + ky 1, ty 1 <- ky 2        (columns likewise)
+    Rows p*N .. p*N+N-1 are phase p = 2a + b; inside a row tap = 2*ty + tx in the K order of `_taps_slice_major`.
+    For the fp16 table the sums are formed in fp32 from the fp16-rounded weights and rounded once."""
+    n, c, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    acc = torch.float32 if dtype == torch.float16 else dtype
+    w = (w.to(torch.float16) if dtype == torch.float16 else w).to(acc)
+    # mix[a][ty][ky]: which original rows land on tap ty at parity a
+    mix = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=acc, device=w.device)
+    ph = torch.einsum("ayk,bxl,nckl->abnyxc", mix, mix, w)                      # [a][b][N][ty][tx][C]
+    return _taps_slice_major(ph.reshape(4 * n, 4, c)).to(dtype).contiguous()
+
+
 def pack_conv_in(w: torch.Tensor) -> torch.Tensor:
     """conv_in weight [Cout][Cin][3][3] -> [Cout][Kpad]: K = (ky*3+kx)*Cin + c zero-padded to a
     multiple of 64 (matches the im2col rows of vdx_im2col_in_f16)."""

@@ -222,7 +222,9 @@ class UNet3DConditionModel(nn.Module):
                     transformer(f"{p}.attentions.{j}", False)
                     transformer(f"{p}.temp_attentions.{j}", True)
             if i != len(c.block_out_channels) - 1:
-                put(f"{p}.upsamplers.0.conv.weight", packing.pack_conv3x3(get(f"{p}.upsamplers.0.conv.weight")))
+                # exact x2: the phase table (four 2x2 convs on the source, K = 4C); x-to-size (latents not divisible by 8): nine taps
+                put(f"{p}.upsamplers.0.conv.weight", packing.pack_upconv_phase(get(f"{p}.upsamplers.0.conv.weight")))
+                put(f"{p}.upsamplers.0.conv.weight_taps9", packing.pack_conv3x3(get(f"{p}.upsamplers.0.conv.weight")))
                 put(f"{p}.upsamplers.0.conv.bias", get(f"{p}.upsamplers.0.conv.bias"))
         norm("conv_norm_out")
         put("conv_out.weight", packing.pad_rows(packing.pack_conv3x3(get("conv_out.weight")), 64))
@@ -257,7 +259,8 @@ class UNet3DConditionModel(nn.Module):
         return out
 
     def num_parameters(self) -> int:
-        return sum(self.W[k].numel() for k in self.W.keys())
+        # (the upsamplers' phase tables are sums of the nine taps counted under `weight_taps9`, not parameters)
+        return sum(self.W[k].numel() for k in self.W.keys() if not k.endswith(".upsamplers.0.conv.weight"))
 
     # ------------------------------------------------------------------------------------------
     # parameter sharding (reference: FSDP wrap, fsdp_chunked_coherent.py:63-88)
@@ -739,13 +742,15 @@ class UNet3DConditionModel(nn.Module):
                     x = self._temporal_transformer(f"{p}.temp_attentions.{j}", x, B, F, hh * ww, x.shape[1] // 64)
             if i != nlev - 1:
                 th, tw = skips[-1][1], skips[-1][2]          # resolution of the next block's skip tensors
+                w_up = W[f"{p}.upsamplers.0.conv.weight"]
                 if (th, tw) == (2 * hh, 2 * ww):
-                    mode_up = 1                               # nearest x2, folded into the conv's gather
+                    mode_up = 3                               # nearest x2 in phase form: four 2x2 convs on the source image
                 elif hh <= th <= 2 * hh and ww <= tw <= 2 * ww:
-                    mode_up = 2                               # F.interpolate(size=skip resolution, mode="nearest"), folded likewise
+                    mode_up = 2                               # F.interpolate(size=skip resolution, mode="nearest"), folded into the nine-tap gather
+                    w_up = W[f"{p}.upsamplers.0.conv.weight_taps9"]
                 else:
                     raise VdxError(f"upsampler {p}: {hh}x{ww} -> {th}x{tw}")
-                x = ops.gemm(x, W[f"{p}.upsamplers.0.conv.weight"], M=n_img * th * tw, mode=ops.CONV3X3,
+                x = ops.gemm(x, w_up, M=n_img * th * tw, mode=ops.CONV3X3,
                              bias=W[f"{p}.upsamplers.0.conv.bias"], conv=(n_img, hh, ww, th, tw, 1, mode_up), allow_ksplit=True)
                 hh, ww = th, tw
         # out

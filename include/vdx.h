@@ -64,7 +64,15 @@ typedef struct vdx_gemm_args {
     int32_t h_out, w_out; /* conv3x3: output image size (M = n*h_out*w_out)                      */
     int32_t stride;       /* conv3x3: 1 or 2 (pad 1, or pad_mode below)                          */
     int32_t upsample;     /* conv3x3: 1 = source is nearest-x2 upsampled on the fly; 2 = nearest-upsampled to
-                           * (h_out, w_out) — diffusers' `upsample_size` path for latents not divisible by 8 */
+                           * (h_out, w_out) — diffusers' `upsample_size` path for latents not divisible by 8;
+                           * 3 = nearest x2 in PHASE form: the same result as 1 computed as four 2x2 convolutions on the
+                           * source image, one per output parity.  `w` is the phase table [4][N][4*c1] (phase p = 2a + b for
+                           * output (2i+a, 2j+b); tap 2*ty + tx reads source (i+a-1+ty, j+b-1+tx); weights = the sums of the
+                           * 3x3 taps that fall on that source pixel; K order as for 9 taps), K = 4*c1, M = n*h_out*w_out
+                           * as ever, N a multiple of 8, stride 1, h_out = 2*h_in, w_out = 2*w_in.  The kernels walk
+                           * 4 * round_up(M / 4, 256) VIRTUAL rows, phase-major: row_begin (a multiple of 256) / row_end
+                           * and vdx_gemm_plan's split_row count those.  Tiled kernels only (variants 1 2 5 6 9); refused
+                           * with bias2, residual, a2, GEGLU, pad_mode, stride 2, ksplit and weight sets          */
     int32_t frames, hw;   /* tconv3: M = b*frames*hw, taps step `hw` rows, zero pad in time      */
     int32_t rows_per_bias2, ldb2; /* bias2 row = m / rows_per_bias2, row stride ldb2 elements        */
     int32_t epilogue;     /* VDX_EPI_* flags                                                     */

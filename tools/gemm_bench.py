@@ -55,17 +55,21 @@ def main():
                 ("Tin ff2 2048->512 +res", dict(mode=ops.PLAIN, cin=2048, N=512, res=True)),
                 ("Tin proj_out 512->320 +res", dict(mode=ops.PLAIN, cin=512, N=320, res=True)),
             ]
+        if lvl > 0:    # up_blocks.{3 - lvl}.upsamplers.0: conv3x3 over nearest-x2, as the nine-tap gather and in phase form (K = 4C)
+            for form, tag in ((1, "nine taps"), (3, "phase form")):
+                cases.append((f"L{lvl}->L{lvl - 1} up x2 {C} {tag}", dict(mode=ops.CONV3X3, cin=C, N=C, rows=4 * M, src_rows=M, taps=9 if form == 1 else 4,
+                                                                   wrows=C if form == 1 else 4 * C, conv=(n_img, h, w, 2 * h, 2 * w, 1, form))))
         # the V projection of spatial self-attention, issued with swapped operands so that V arrives transposed for the
         # flash kernel: "rows" = the C output channels, "weights" = the M activation rows
         cases.append((f"L{lvl} v^T {C}x{M}", dict(mode=ops.PLAIN, cin=C, N=M, rows=C)))
         for name, c in cases:
             if only and only not in name:
                 continue
-            taps = {ops.PLAIN: 1, ops.CONV3X3: 9, ops.TCONV3: 3}[c["mode"]]
+            taps = c.get("taps", {ops.PLAIN: 1, ops.CONV3X3: 9, ops.TCONV3: 3}[c["mode"]])
             K = taps * c["cin"]
             M = c.get("rows", n_img * h * w)
-            a = rnd(M, c["cin"])
-            wgt = rnd(c["N"], K)
+            a = rnd(c.get("src_rows", M), c["cin"])
+            wgt = rnd(c.get("wrows", c["N"]), K)
             bias = rnd(c["N"])
             res = rnd(M, c["N"]) if c.get("res") else None
             n_out = c["N"] // 2 if c.get("geglu") else c["N"]
@@ -84,7 +88,7 @@ def main():
                     per.append(timeit(fn))
                 except Exception:   # variant not applicable to this shape
                     per.append(float("inf"))
-            auto = ops.gemm_kernel_name(M, c["N"], K, c["mode"], c.get("geglu", False))
+            auto = ops.gemm_kernel_name(M, c["N"], 9 * c["cin"] if "taps" in c else K, c["mode"], c.get("geglu", False))
             rows.append((name, M, c["N"], K, per, flops, byts, auto))
             del a, wgt, out, res
     names = ["128x128", "256x320", "ring4", "128x320", "ws", "128x320w8", "auto"]

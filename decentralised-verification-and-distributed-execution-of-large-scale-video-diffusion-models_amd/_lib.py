@@ -130,6 +130,11 @@ SIGNATURES = {
     "vdx_flow_update_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vdx_flow_abs_sum_f32": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:200-264 the writer)
+    "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
+    "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vdx_mjpeg_idct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_mjpeg_color": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -195,3 +195,10 @@ class CLIPScorer:
         txt = self.text_features(ids)
         mean, per = ops.clip_cosine_score(img, txt[0])
         return float(mean.item()), per.cpu()
+
+    def score_file(self, src, prompt_or_ids, tokenizer=None) -> Tuple[float, torch.Tensor]:
+        """`compute_quality_score(video_path, prompt)` (scoring.py:87-147) starting from the FILE like the reference
+        (`cv2.VideoCapture(video_path)`, :110): `src` (a path, the file's bytes, or a list of JPEG byte strings) is decoded on the
+        GPU (vdx/video.py `read_frames`, bit for bit Pillow's decode) and `score` takes the frames where they are."""
+        from .video import read_frames
+        return self.score(read_frames(src, device=self.device)[0], prompt_or_ids, tokenizer=tokenizer)

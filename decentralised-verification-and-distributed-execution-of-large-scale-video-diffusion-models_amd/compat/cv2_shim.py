@@ -4,6 +4,7 @@
     calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15, 3, 5, 1.2, 0)   dense flow (h, w, 2) float32
     remap(src, map_x, map_y, INTER_LINEAR)                             bilinear, constant-0 border
     VideoWriter(path, VideoWriter_fourcc(*"mp4v"), fps, (w, h)).write(bgr) / .release()
+    VideoCapture(path).isOpened() / .read() / .get(CAP_PROP_FRAME_COUNT | _WIDTH | _HEIGHT | _FPS) / .release()
 
 `calcOpticalFlowFarneback` is an independent implementation of the published algorithm (G. Farneback, "Two-frame
 motion estimation based on polynomial expansion", SCIA 2003) with OpenCV's parameterisation: Gaussian image pyramid,
@@ -14,7 +15,12 @@ tests pin the implementation on synthetic translations instead.
 
 `VideoWriter` writes Motion-JPEG samples (Pillow encodes them) into an ISO base-media (.mp4) file under the `mp4v`
 sample entry with object type 0x6C — the container and fourcc the reference asks for; an MPEG-4 part 2 encoder does
-not exist here.
+not exist here.  `VideoWriter(..., restart_rows=N)` (not OpenCV's; default 0 = today's bytes) makes Pillow emit a restart
+marker every N MCU rows, which lets the GPU decoder work on that many more segments per frame.
+
+`VideoCapture` reads exactly those files back (InferNet/template/validator/scoring.py:16-24, :110-118: `cap.read()` until it
+fails): `vdx.video.read_frames` decodes the whole clip on the GPU at the first `read()`, pinned bit for bit to Pillow's decode;
+frames come out BGR as OpenCV's do.  Any other codec leaves `isOpened()` false.
 """
 from __future__ import annotations
 
@@ -28,6 +34,7 @@ COLOR_BGR2GRAY, COLOR_RGB2GRAY, COLOR_RGB2BGR, COLOR_BGR2RGB = 6, 7, 4, 4
 COLOR_GRAY2BGR = 8
 INTER_NEAREST, INTER_LINEAR = 0, 1
 OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_FARNEBACK_GAUSSIAN = 4, 256
+CAP_PROP_FRAME_WIDTH, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FPS, CAP_PROP_FRAME_COUNT = 3, 4, 5, 7
 
 
 class error(Exception):
@@ -198,8 +205,9 @@ def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
 
 
 class VideoWriter:
-    def __init__(self, filename=None, fourcc=0, fps=0.0, frameSize=(0, 0), isColor=True):
+    def __init__(self, filename=None, fourcc=0, fps=0.0, frameSize=(0, 0), isColor=True, restart_rows=0):
         self._f = None
+        self._restart_rows = int(restart_rows)
         if filename is not None:
             self.open(filename, fourcc, fps, frameSize, isColor)
 
@@ -222,7 +230,8 @@ class VideoWriter:
             raise error(f"VideoWriter.write: frame {frame.shape[1]}x{frame.shape[0]} != {self._w}x{self._h}")
         rgb = frame[..., ::-1] if frame.ndim == 3 else frame       # OpenCV frames are BGR
         buf = io.BytesIO()
-        Image.fromarray(np.ascontiguousarray(rgb)).save(buf, format="JPEG", quality=92)
+        extra = {"restart_marker_rows": self._restart_rows} if self._restart_rows > 0 else {}
+        Image.fromarray(np.ascontiguousarray(rgb)).save(buf, format="JPEG", quality=92, **extra)
         data = buf.getvalue()
         self._f.write(data)
         self._sizes.append(len(data))
@@ -262,3 +271,51 @@ class VideoWriter:
         f.write(_box(b"moov", mvhd + trak))
         f.close()
         self._f = None
+
+
+# ---------------------------------------------------------------------------------------------
+# VideoCapture: the same files read back, decoded on the GPU (vdx/video.py, csrc/mjpeg.hip)
+# ---------------------------------------------------------------------------------------------
+class VideoCapture:
+    def __init__(self, filename=None, device="cuda"):
+        self._meta = self._jpegs = self._frames = None
+        self._device, self._next = device, 0
+        if filename is not None:
+            self.open(filename)
+
+    def open(self, filename):
+        from .. import video
+        from .._lib import VdxError
+        self.release()
+        try:
+            with open(filename, "rb") as f:
+                self._jpegs, meta = video.demux(f.read())
+            first = video.parse_jpeg(self._jpegs[0])
+        except (OSError, VdxError, IndexError, struct.error):
+            self._jpegs = None
+            return False
+        self._meta = {CAP_PROP_FRAME_COUNT: float(len(self._jpegs)), CAP_PROP_FRAME_WIDTH: float(first.width),
+                      CAP_PROP_FRAME_HEIGHT: float(first.height), CAP_PROP_FPS: float(meta["fps"])}
+        return True
+
+    def isOpened(self):
+        return self._jpegs is not None
+
+    def get(self, prop):
+        return self._meta.get(prop, 0.0) if self._meta else 0.0
+
+    def read(self):
+        if self._jpegs is None:
+            return False, None
+        if self._frames is None:                                   # the whole clip in one launch, at the first read
+            from .. import video
+            frames = video.read_frames(self._jpegs, device=self._device)[0].cpu().numpy()
+            self._frames = frames[..., ::-1] if frames.ndim == 4 else np.repeat(frames[..., None], 3, axis=3)
+        if self._next >= len(self._frames):
+            return False, None
+        self._next += 1
+        return True, np.ascontiguousarray(self._frames[self._next - 1])
+
+    def release(self):
+        self._meta = self._jpegs = self._frames = None
+        self._next = 0

@@ -7,7 +7,8 @@
 
 What it computes, term by term (the same as the reference unless stated):
   * frames: decoded uint8 RGB (F, H, W, 3), on the GPU or as host arrays.  DEVIATION: every term of the reference re-reads
-    the mp4 with OpenCV; here the frames the pipeline decoded are scored directly (vdx/clip_score.py's deviation);
+    the mp4 with OpenCV; here the frames the pipeline decoded are scored directly (vdx/clip_score.py's deviation).  The
+    `*_file` entry points start from the file instead: it is decoded once on the GPU (vdx/video.py) and scored from there;
   * PF, prompt fidelity (:213-267): the CLIP score, `CLIPScorer.score` (vdx/clip_score.py), unchanged;
   * VQ, video quality (:269-309): max(0, 1 - mean over consecutive pairs of LPIPS-AlexNet(frame_i, frame_i-1))
     (vdx/lpips.py: restated from the published definition, parity with the `lpips` package unpinned); fewer than two
@@ -83,6 +84,14 @@ def verify_video_authenticity(frames, device="cuda") -> Tuple[bool, Dict[str, Op
                                     t.shape[1] * t.shape[2] * 3)
 
 
+def verify_video_authenticity_file(src, device="cuda") -> Tuple[bool, Dict[str, Optional[float]]]:
+    """`verify_video_authenticity_common(video_path)` (scoring.py:13-67) of the FILE: `src` (a path, the file's bytes, or a list
+    of JPEG byte strings) is decoded on the GPU (vdx/video.py `read_frames`, bit for bit Pillow's decode) and the frames go,
+    still on the device, through `verify_video_authenticity`."""
+    from .video import read_frames
+    return verify_video_authenticity(read_frames(src, device=device)[0], device=device)
+
+
 class MDVQS:
     """`MDVQS` (scoring.py:154-343) on the HIP path; see the module docstring.  `clip` / `lpips`: a `CLIPScorer` and an
     `LPIPSAlex` (each term raises `VdxError` without its model)."""
@@ -148,6 +157,14 @@ class MDVQS:
         vq = self.compute_video_quality(frames)[0]
         tc = self.compute_temporal_consistency(frames)
         return pf, vq, tc, self.alpha * pf + self.beta * vq + self.gamma * tc
+
+    def compute_md_vqs_file(self, src, prompt, tokenizer=None, device=None) -> Tuple[float, float, float, float]:
+        """:190-207 starting from the file as the reference does (`cv2.VideoCapture(video_path)`, :230, :272, :314): `src` is
+        decoded once on the GPU (vdx/video.py `read_frames`) and `compute_md_vqs` scores those frames on the device."""
+        from .video import read_frames
+        model = self.clip if self.clip is not None else self.lpips
+        dev = device if device is not None else (model.device if model is not None else "cuda")
+        return self.compute_md_vqs(read_frames(src, device=dev)[0], prompt, tokenizer=tokenizer)
 
     def compute_quality_score(self, frames, prompt, tokenizer=None) -> float:
         """:177-188 — the total alone."""

@@ -70,11 +70,17 @@ def flow_warp_error(frames: Sequence[np.ndarray], ranges: Sequence[Tuple[int, in
     return float(np.mean(diffs)) if diffs else None
 
 
-def write_video(frames: Sequence[np.ndarray], path: str, fps: float) -> None:
-    """:250-253 — `cv2.VideoWriter(path, fourcc("mp4v"), fps, (W, H))`, frames RGB -> BGR, release."""
-    cv2 = _cv2()
+def write_video(frames: Sequence[np.ndarray], path: str, fps: float, restart_rows: int = 0) -> None:
+    """:250-253 — `cv2.VideoWriter(path, fourcc("mp4v"), fps, (W, H))`, frames RGB -> BGR, release.  `restart_rows` > 0 (not
+    the reference's): the project's own Motion-JPEG writer with a restart marker every that many MCU rows, for the GPU
+    decoder (vdx/video.py); 0 writes what it always wrote."""
     h, w = frames[0].shape[:2]
-    vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"mp4v"), fps, (w, h))
+    if restart_rows > 0:
+        from .compat import cv2_shim as cv2
+        vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"mp4v"), fps, (w, h), restart_rows=restart_rows)
+    else:
+        cv2 = _cv2()
+        vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"mp4v"), fps, (w, h))
     for f in frames:
         vw.write(cv2.cvtColor(f, cv2.COLOR_RGB2BGR))
     vw.release()

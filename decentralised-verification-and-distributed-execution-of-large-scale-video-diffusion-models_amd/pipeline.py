@@ -513,7 +513,10 @@ def build_arg_parser():
     the validator's MD-VQS record (vdx/mdvqs.py: PF, VQ, TC, the weighted total and the authenticity gate); `--lpips_model`
     names the LPIPS weights (a local file in the `lpips` state-dict layout; without it, seeded synthetic ones).  `--gpu_flow`
     computes the Farneback flow behind `flow_err` and behind MD-VQS' TC in HIP kernels (vdx/flow.py) instead of on the host;
-    the MD-VQS record then carries `"flow": "gpu"`."""
+    the MD-VQS record then carries `"flow": "gpu"`.  `--video_restart_rows N` writes the mp4's JPEG frames with a restart marker
+    every N MCU rows (vdx/compat/cv2_shim.py), and `--score_from_file` makes `--clip_json` / `--mdvqs_json` score the frames
+    decoded back from the written mp4 on the GPU (vdx/video.py: what a validator holding the file would score) instead of the
+    frames in memory; the records then carry `"source": "file"`."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -541,6 +544,10 @@ def build_arg_parser():
     p.add_argument("--mdvqs_json", default=None, help="write the MD-VQS record of the decoded frames here (rank 0)")
     p.add_argument("--lpips_model", default=None, help="local LPIPS-AlexNet state dict (lpips layout) for --mdvqs_json")
     p.add_argument("--gpu_flow", action="store_true", help="Farneback flow of flow_err and of MD-VQS' TC on the GPU (vdx/flow.py)")
+    p.add_argument("--video_restart_rows", type=int, default=0,
+                   help="restart marker every N MCU rows in the mp4's JPEG frames (0: none, the bytes written without this flag)")
+    p.add_argument("--score_from_file", action="store_true",
+                   help="--clip_json / --mdvqs_json score the frames decoded back from --out_video (vdx/video.py)")
     p.add_argument("--init_video", default=None,
                    help="video-to-video: refine this clip (.npy uint8 (T,H,W,3) or a directory of images) instead of starting from noise")
     p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
@@ -635,7 +642,7 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev):
 
 
 def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
-            clip_inputs: Optional[dict] = None) -> dict:
+            clip_inputs: Optional[dict] = None, video_restart_rows: int = 0) -> dict:
     """The reference's `DistributedVideoDiffuser(cfg)()` (:47-276) end to end -> its result dict (:263-275): pipeline
     components (`model_id` = a local checkpoint directory in diffusers layout, else seeded synthetic weights: nothing can be
     downloaded here), text embeddings (:96-103), chunked denoising + exchange + blend, per-frame VAE decode (:219-225),
@@ -687,7 +694,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
         temp_instab = metrics.boundary_l1(frames, ranges)
         flow_err = metrics.flow_warp_error(frames, ranges, device=dev) if cfg.gpu_flow else metrics.flow_warp_error(frames, ranges)
     if d.rank == 0 and out_video:
-        metrics.write_video(frames, out_video, cfg.fps)
+        metrics.write_video(frames, out_video, cfg.fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}))
     delay = emu_reduce_delay_s(cfg)             # :257-258
     if delay > 0:
         time.sleep(delay)
@@ -716,15 +723,25 @@ def main(argv=None) -> int:
         torch.cuda.reset_peak_memory_stats()
     clip_inputs = {} if a.clip_json or a.mdvqs_json else None
     t0 = time.time()
-    res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs)
+    if a.score_from_file and not a.out_video:
+        raise ValueError("--score_from_file needs --out_video")
+    res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs,
+                  **({"video_restart_rows": a.video_restart_rows} if a.video_restart_rows else {}))
     if res["rank"] == 0:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
+        source = {}
+        if clip_inputs is not None and a.score_from_file:
+            # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
+            from .video import read_frames
+            clip_inputs["frames"] = read_frames(a.out_video, device=clip_inputs["device"])[0]
+            source = {"source": "file"}
         if a.clip_json:
             # scored after the row took its latency and memory readings: the row is that of a run without --clip_json
             import json
             rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
+            rec.update(source)
             with open(a.clip_json, "w") as f:
                 json.dump(rec, f, indent=1)
         if a.mdvqs_json:
@@ -732,6 +749,7 @@ def main(argv=None) -> int:
             import json
             rec = mdvqs_record(clip_inputs["frames"], cfg.prompt, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
                                clip_inputs["device"], **({"flow": "gpu"} if a.gpu_flow else {}))
+            rec.update(source)
             with open(a.mdvqs_json, "w") as f:
                 json.dump(rec, f, indent=1)
     if dist.is_available() and dist.is_initialized():

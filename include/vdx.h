@@ -549,6 +549,38 @@ int vdx_flow_abs_sum_f32(const float* flow, int P, size_t n, float* workspace, f
 int vdx_flow_remap_absdiff_u8(const void* frames, size_t frame_pitch, int row_pitch, const float* flow, int P, int step, int H,
                               int W, uint64_t* absdiff, void* warped, vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
+ *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
+ *   vdx/compat/cv2_shim.py:200-264                                      the writer whose .mp4 this reads back
+ * (csrc/mjpeg.hip; vdx/video.py parses the container and the JPEG headers on the host).  Baseline sequential JPEG, 8 bit;
+ * `layout` 0: one component, 1: three components 1x1 (4:4:4), 2: 2x2, 1x1, 1x1 (4:2:0).  All frames of a call share W, H and
+ * layout.  Integers only and no atomics: the same bits on every run and for any number of frames per call, and bit for bit
+ * libjpeg's decode (slow-integer IDCT, h2v2 fancy upsampling, 16-bit fixed-point YCbCr -> RGB), i.e. Pillow's.
+ * The three stages share `workspace` (vdx_mjpeg_workspace bytes, 16-byte aligned) and are enqueued in this order.
+ * ---------------------------------------------------------------------------------------- */
+/* Bytes of workspace for F frames of W x H (int16 coefficients [F][block][64], then uint8 component planes at the padded MCU
+ * extent); 0 for arguments the decoder does not take.                                                                  */
+size_t vdx_mjpeg_workspace(int F, int W, int H, int layout);
+/* Stage 1, Huffman decode, one lane per segment.  data: the entropy-coded bytes of all frames, nbytes (% 4 == 0) of them.
+ * segs: int32 [nseg][4] = byte begin, byte end, first MCU, MCU count of every restart interval (a frame without DRI is one
+ * segment); seg_off: int32 [F + 1], frame f owns rows seg_off[f] .. seg_off[f + 1], at most max_segs_per_frame of them.
+ * huff: per frame four tables (DC 0, DC 1, AC 0, AC 1) of 384 words each: 512 uint16 entries (length << 8 | symbol) for a
+ * 9-bit lookahead, then int32 maxcode[17], int32 valoff[17] (indexed by code length), the 256 symbols, padding.
+ * sel: int32 [F][3], component c decodes with DC table sel & 1 and AC table (sel >> 4) & 1.  FF 00 is unstuffed here, the
+ * DC prediction restarts with each segment.  err: uint32 [nseg], 0 or (code | MCU within the segment << 8) with code
+ * 1: the data ended inside a symbol, 2: a coefficient index past 63, 3: no Huffman code matches, 4: a DC size above 15,
+ * 5: a segment row outside the clip; a lane stops at its first error.  No access depends on unchecked stream bytes.     */
+int vdx_mjpeg_entropy(const void* data, size_t nbytes, const int32_t* seg_off, const int32_t* segs, int nseg,
+                      int max_segs_per_frame, const void* huff, const int32_t* sel, int F, int W, int H, int layout,
+                      void* workspace, uint32_t* err, vdx_stream_t stream);
+/* Stage 2: coefficient * quant (uint16 [F][3][64] in natural order, per component), the 8x8 slow-integer IDCT in int32
+ * (13-bit constants, 2 pass-1 bits), + 128, clamp -> the component planes.                                              */
+int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, vdx_stream_t stream);
+/* Stage 3: 4:2:0 chroma through the h2v2 fancy upsampling (edges replicate at ceil(W/2) x ceil(H/2)), YCbCr -> RGB, crop:
+ * out uint8 (F, H, W, 3) RGB packed, or (F, H, W) for layout 0.  4-byte aligned.  4:2:0 needs W >= 5.                   */
+int vdx_mjpeg_color(const void* workspace, int F, int W, int H, int layout, void* out, vdx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

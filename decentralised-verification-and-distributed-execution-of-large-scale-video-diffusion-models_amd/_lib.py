@@ -133,7 +133,7 @@ SIGNATURES = {
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:200-264 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "vdx_mjpeg_idct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_mjpeg_idct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_mjpeg_color": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
 }
 

@@ -2,9 +2,10 @@
 // `cv2.VideoCapture(video_path)` (InferNet/template/validator/scoring.py:16, :110, :230, :272, :314) for the files
 // vdx/compat/cv2_shim.py:200-264 writes.  Three stages, integers only, no atomics: the same bits on every run and for any
 // number of frames per launch, and the bits of libjpeg's own decode (slow-integer IDCT, h2v2 "fancy" upsampling, the 16-bit
-// fixed-point YCbCr -> RGB), which is what Pillow returns.  The host (vdx/video.py) walks the markers, builds the Huffman
-// lookups from the stream's DHT segments and cuts the scan at its restart markers; nothing here trusts what it built beyond
-// the checks below: the entropy bytes come from another machine.
+// fixed-point YCbCr -> RGB), which is what Pillow returns, for every frame whose coefficients lie in the range 8-bit samples
+// produce; stage 2 flags the frames outside it (MJ_DOMAIN_* below), where decoders disagree, and the host refuses them.
+// The host (vdx/video.py) walks the markers, builds the Huffman lookups from the stream's DHT segments and cuts the scan at
+// its restart markers; nothing here trusts what it built beyond the checks below: the entropy bytes come from another machine.
 #include "vdx_common.h"
 
 #define MJ_HUFF_WORDS 384        // one Huffman table: 512 x u16 9-bit lookahead | maxcode[17] | valoff[17] | 256 symbols | pad
@@ -237,6 +238,15 @@ extern "C" int vdx_mjpeg_entropy(const void* data, size_t nbytes, const int32_t*
 // -fwrapv: absurd coefficients of a corrupt stream wrap, they are never undefined).
 #define MJ_CONST_BITS 13
 #define MJ_PASS1_BITS 2
+// The domain of the claim "the bits of libjpeg's decode".  An encoder that started from 8-bit samples leaves dequantised
+// products, pass-1 values and pre-limit samples far inside these bounds.  Outside them libjpeg's C code (this arithmetic: int32,
+// then a range-limit table indexed with 10 masked bits), libjpeg-turbo's 16-bit SIMD lanes and other decoders return different
+// pixels for the same bytes, so there is nothing to be bit-equal to: the kernel sets the frame's word in `flags` and the host
+// refuses the frame.  A frame is outside when a product c * q or a pass-1 value leaves [-B - 1, B] for its bound B below, or a
+// pass-2 result before the range limit leaves [-512, 511] (tests/test_video_host.py measures the bounds against Pillow;
+// profiles/mjpeg_domain.txt).
+#define MJ_DOMAIN_PRODUCT 32767
+#define MJ_DOMAIN_PASS1 32767
 __device__ __forceinline__ void mj_idct8(const int* in, int* out, int shift) {
     int z2 = in[2], z3 = in[6];
     int z1 = (z2 + z3) * 4433;
@@ -290,7 +300,7 @@ __device__ __forceinline__ void mj_idct8(const int* in, int* out, int shift) {
 #define MJ_WS_ROW 9
 #define MJ_WS_BLK 76
 __global__ __launch_bounds__(256) void mjpeg_idct_kernel(const short* coef, const unsigned short* quant, MjLayout L, long long nblocks,
-                                                         unsigned char* planes) {
+                                                         unsigned char* planes, uint32_t* flags) {
     __shared__ __attribute__((aligned(16))) short raw[32 * MJ_RAW_STRIDE];
     __shared__ int ws[32 * MJ_WS_BLK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -309,8 +319,14 @@ __global__ __launch_bounds__(256) void mjpeg_idct_kernel(const short* coef, cons
 #pragma unroll
             for (int r = 0; r < 8; ++r) in[r] = (int)raw[lb * MJ_RAW_STRIDE + r * 8 + j] * (int)q[r * 8];
             mj_idct8(in, out, MJ_CONST_BITS - MJ_PASS1_BITS);
+            bool outside = false;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) ws[lb * MJ_WS_BLK + r * MJ_WS_ROW + j] = out[r];
+            for (int r = 0; r < 8; ++r) {
+                ws[lb * MJ_WS_BLK + r * MJ_WS_ROW + j] = out[r];
+                outside |= in[r] < -MJ_DOMAIN_PRODUCT - 1 || in[r] > MJ_DOMAIN_PRODUCT || out[r] < -MJ_DOMAIN_PASS1 - 1 ||
+                           out[r] > MJ_DOMAIN_PASS1;
+            }
+            if (outside) flags[f] = 1;                                      // every writer stores the same word: no atomic
         }
         __syncthreads();
     }
@@ -322,29 +338,36 @@ __global__ __launch_bounds__(256) void mjpeg_idct_kernel(const short* coef, cons
     for (int c = 0; c < 8; ++c) in[c] = ws[lb * MJ_WS_BLK + i * MJ_WS_ROW + c];
     mj_idct8(in, out, MJ_CONST_BITS + MJ_PASS1_BITS + 3);
     uint32_t px[2] = {0, 0};
+    bool outside = false;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         // the decoder's range-limit table is indexed with 10 masked bits: sign-extend them, then +128 and clamp
         const int s = ((out[c] & 1023) ^ 512) - 512;
+        outside |= s != out[c];                                             // outside [-512, 511]: the table is no clamp there
         px[c >> 2] |= (uint32_t)min(max(s + 128, 0), 255) << ((c & 3) * 8);
     }
     const int f = (int)(g / L.bpf), bi = (int)(g % L.bpf);
+    if (outside) flags[f] = 1;
     const int c = L.ncomp == 3 ? (bi >= L.boff[1]) + (bi >= L.boff[2]) : 0;
     const int rel = bi - L.boff[c], by = rel / L.bw[c], bx = rel - by * L.bw[c];
     unsigned char* dst = planes + ((size_t)f * L.bpf + L.boff[c]) * 64 + (size_t)(by * 8 + i) * (L.bw[c] * 8) + bx * 8;
     *(uint2*)dst = make_uint2(px[0], px[1]);
 }
 
-extern "C" int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, vdx_stream_t stream) {
+extern "C" int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, uint32_t* flags,
+                              vdx_stream_t stream) {
     MjLayout L;
-    VDX_CHECK(quant_u16 && workspace, "mjpeg_idct: null pointer");
+    VDX_CHECK(quant_u16 && workspace && flags, "mjpeg_idct: null pointer");
     VDX_CHECK(F > 0 && F <= 65535 && mj_layout(W, H, layout, &L) == 0, "mjpeg_idct: F=%d W=%d H=%d layout=%d", F, W, H, layout);
     VDX_CHECK((long long)F * L.bpf < (1ll << 25), "mjpeg_idct: the clip has too many blocks");
-    VDX_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)quant_u16 & 1) == 0, "mjpeg_idct: misaligned pointer");
+    VDX_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)quant_u16 & 1) == 0 && ((uintptr_t)flags & 3) == 0,
+              "mjpeg_idct: misaligned pointer");
+    const hipError_t e = hipMemsetAsync(flags, 0, (size_t)F * 4, (hipStream_t)stream);
+    VDX_CHECK(e == hipSuccess, "mjpeg_idct: memset failed: %s", hipGetErrorString(e));
     const long long nb = (long long)F * L.bpf;
     unsigned char* planes = (unsigned char*)workspace + mj_round((size_t)nb * 64 * 2);
     hipLaunchKernelGGL(mjpeg_idct_kernel, dim3((unsigned)((nb + 31) / 32)), dim3(256), 0, (hipStream_t)stream, (const short*)workspace,
-                       (const unsigned short*)quant_u16, L, nb, planes);
+                       (const unsigned short*)quant_u16, L, nb, planes, flags);
     return vdx_launch_status("vdx_mjpeg_idct");
 }
 

@@ -12,9 +12,18 @@ The host walks the JPEG markers (numpy, no per-byte Python loop over entropy dat
 stream's own DHT segments, reads DQT / SOF0 / DRI / SOS, finds the restart markers and cuts the scan into segments; the device
 (csrc/mjpeg.hip) decodes the Huffman codes one lane per segment, runs the slow-integer IDCT and the fancy chroma upsampling +
 YCbCr -> RGB.  Baseline sequential 8-bit JPEG with one interleaved scan: 4:2:0, 4:4:4 or grey; every other kind is refused by
-name on the host.  The result is pinned bit for bit to Pillow's (libjpeg's) decode of the same bytes (tests/test_video_gpu.py).
+name on the host.
 
-One upload (entropy bytes and all tables in one buffer) and one synchronisation (the per-segment error words) per call.
+The result is pinned bit for bit to Pillow's (libjpeg-turbo's) decode of the same bytes (tests/test_video_gpu.py) for every
+frame whose coefficients lie in the range that 8-bit samples produce: every dequantised product and every value after the
+IDCT's first pass within int16, every sample before the range limit within [-512, 511] (csrc/mjpeg.hip MJ_DOMAIN_*;
+profiles/mjpeg_domain.txt).  Outside that range libjpeg's C code wraps the sample to 10 bits, libjpeg-turbo saturates and
+wraps in 16-bit lanes, and other decoders do something else again: one stream, several images.  No encoder that started from
+pixels writes such a frame, a peer who chooses the bytes can, so the IDCT stage flags it and `read_frames` refuses it by
+name instead of returning one of the possible images.
+
+One upload (entropy bytes and all tables in one buffer) and one synchronisation (the per-segment error words and the
+per-frame domain words, one buffer) per call.
 """
 from __future__ import annotations
 
@@ -470,7 +479,8 @@ def read_frames(src: Union[str, os.PathLike, bytes, Sequence[bytes]], device="cu
     """Decode a Motion-JPEG .mp4 (path or bytes), a bare JPEG, or a list of JPEG byte strings on the GPU ->
     (uint8 frames on `device`: (F, H, W, 3) RGB, or (F, H, W) for grey streams; info).  `info`: n_frames, width, height, fps,
     sampling ("4:2:0", "4:4:4", "L"), restart_interval (MCUs, 0 without DRI), n_segments.  Raises `VdxError` for whatever is
-    not Motion-JPEG / baseline JPEG, and, naming the frame, for entropy data the device found corrupt."""
+    not Motion-JPEG / baseline JPEG, and, naming the frame, for entropy data the device found corrupt and for coefficients
+    outside the range of 8-bit samples (decoders disagree on those: the module's docstring)."""
     jpegs, meta = _samples(src)
     blob, off, info, _ = plan(jpegs)
     if meta["width"] is not None and (meta["width"], meta["height"]) != (info["width"], info["height"]):
@@ -491,7 +501,7 @@ def read_frames(src: Union[str, os.PathLike, bytes, Sequence[bytes]], device="cu
         up = torch.from_numpy(blob).to(dev, non_blocking=False)           # the one upload
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         nseg = info["n_segments"]
-        err = torch.empty(nseg, dtype=torch.int32, device=dev)
+        err = torch.empty(nseg + F, dtype=torch.int32, device=dev)            # per segment: entropy errors; per frame: domain
         out = torch.empty((F, H, W, 3) if layout else (F, H, W), dtype=torch.uint8, device=dev)
         ptr = {k: up.data_ptr() + v[0] for k, v in off.items()}
         stream = torch.cuda.current_stream().cuda_stream
@@ -507,11 +517,13 @@ def read_frames(src: Union[str, os.PathLike, bytes, Sequence[bytes]], device="cu
                                          info["max_segments_per_frame"], ptr["huff"], ptr["sel"], F, W, H, layout, ws.data_ptr(),
                                          err.data_ptr(), stream), "vdx_mjpeg_entropy")
         mark()
-        _lib.check(lib.vdx_mjpeg_idct(ptr["quant"], F, W, H, layout, ws.data_ptr(), stream), "vdx_mjpeg_idct")
+        _lib.check(lib.vdx_mjpeg_idct(ptr["quant"], F, W, H, layout, ws.data_ptr(), err.data_ptr() + 4 * nseg, stream),
+                   "vdx_mjpeg_idct")
         mark()
         _lib.check(lib.vdx_mjpeg_color(ws.data_ptr(), F, W, H, layout, out.data_ptr(), stream), "vdx_mjpeg_color")
         mark()
-        words = err.cpu().numpy().view(np.uint32)                            # the one synchronisation
+        both = err.cpu().numpy().view(np.uint32)                             # the one synchronisation
+    words, outside = both[:nseg], both[nseg:]
     bad = np.flatnonzero(words)
     if len(bad):
         seg_off = blob[off["seg_off"][0]:off["seg_off"][0] + 4 * (F + 1)].view(np.int32)
@@ -520,4 +532,8 @@ def read_frames(src: Union[str, os.PathLike, bytes, Sequence[bytes]], device="cu
         code, mcu = int(words[s]) & 255, int(words[s]) >> 8
         raise VdxError(f"read_frames: frame {f} is corrupt: {ERRORS.get(code, f'error {code}')} (segment {s - int(seg_off[f])}, "
                        f"MCU {mcu} of it; {len(bad)} of {nseg} segments failed)")
+    if outside.any():
+        f = int(np.flatnonzero(outside)[0])
+        raise VdxError(f"read_frames: frame {f} holds coefficients outside the range of 8-bit samples, on which libjpeg, "
+                       f"libjpeg-turbo and this decoder disagree ({int(np.count_nonzero(outside))} of {F} frames)")
     return out, info

@@ -556,7 +556,8 @@ int vdx_flow_remap_absdiff_u8(const void* frames, size_t frame_pitch, int row_pi
  * (csrc/mjpeg.hip; vdx/video.py parses the container and the JPEG headers on the host).  Baseline sequential JPEG, 8 bit;
  * `layout` 0: one component, 1: three components 1x1 (4:4:4), 2: 2x2, 1x1, 1x1 (4:2:0).  All frames of a call share W, H and
  * layout.  Integers only and no atomics: the same bits on every run and for any number of frames per call, and bit for bit
- * libjpeg's decode (slow-integer IDCT, h2v2 fancy upsampling, 16-bit fixed-point YCbCr -> RGB), i.e. Pillow's.
+ * libjpeg's decode (slow-integer IDCT, h2v2 fancy upsampling, 16-bit fixed-point YCbCr -> RGB), i.e. Pillow's, for every
+ * frame whose coefficients lie in the range 8-bit samples produce; stage 2 flags the others (decoders disagree on them).
  * The three stages share `workspace` (vdx_mjpeg_workspace bytes, 16-byte aligned) and are enqueued in this order.
  * ---------------------------------------------------------------------------------------- */
 /* Bytes of workspace for F frames of W x H (int16 coefficients [F][block][64], then uint8 component planes at the padded MCU
@@ -575,8 +576,12 @@ int vdx_mjpeg_entropy(const void* data, size_t nbytes, const int32_t* seg_off, c
                       int max_segs_per_frame, const void* huff, const int32_t* sel, int F, int W, int H, int layout,
                       void* workspace, uint32_t* err, vdx_stream_t stream);
 /* Stage 2: coefficient * quant (uint16 [F][3][64] in natural order, per component), the 8x8 slow-integer IDCT in int32
- * (13-bit constants, 2 pass-1 bits), + 128, clamp -> the component planes.                                              */
-int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, vdx_stream_t stream);
+ * (13-bit constants, 2 pass-1 bits), + 128, clamp -> the component planes.  flags: uint32 [F], zeroed here on the stream;
+ * word f becomes 1 when frame f holds coefficients outside the range 8-bit samples produce (a dequantised product or a
+ * pass-1 value beyond the bounds in csrc/mjpeg.hip, or a sample before the range limit outside [-512, 511]): there libjpeg,
+ * libjpeg-turbo and this arithmetic return different pixels, and the caller refuses the frame.                          */
+int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, uint32_t* flags,
+                   vdx_stream_t stream);
 /* Stage 3: 4:2:0 chroma through the h2v2 fancy upsampling (edges replicate at ceil(W/2) x ceil(H/2)), YCbCr -> RGB, crop:
  * out uint8 (F, H, W, 3) RGB packed, or (F, H, W) for layout 0.  4-byte aligned.  4:2:0 needs W >= 5.                   */
 int vdx_mjpeg_color(const void* workspace, int F, int W, int H, int layout, void* out, vdx_stream_t stream);

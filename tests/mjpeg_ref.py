@@ -145,7 +145,7 @@ def entropy(blob, off, info):
 
 
 def _idct8(x, shift):
-    """The 1-D slow-integer inverse DCT along the last axis (int64 in, so nothing wraps)."""
+    """The 1-D slow-integer inverse DCT along the last axis, in the integer type of x (int64: nothing wraps; int32: wraps)."""
     i = [x[..., k] for k in range(8)]
     z2, z3 = i[2], i[6]
     z1 = (z2 + z3) * 4433
@@ -165,20 +165,60 @@ def _idct8(x, shift):
     return np.stack([(v + rnd) >> shift for v in o], -1)
 
 
-def idct(coef, quant, W, H, layout):
+# The domain of "bit-equal to Pillow": csrc/mjpeg.hip MJ_DOMAIN_PRODUCT / MJ_DOMAIN_PASS1 and the range of the decoder's
+# range-limit table.  A frame with a value outside is flagged by the kernel and refused by read_frames.
+DOMAIN_PRODUCT = 32767
+DOMAIN_PASS1 = 32767
+DOMAIN_SAMPLE = (-512, 511)
+
+
+def _stages(coef, quant, c, boff, int32):
+    """Component c of every frame -> (dequantised products, pass-1 values, samples before the range limit), each
+    [F][blocks][8][8].  int32=True computes in numpy int32, which wraps exactly as the kernel's -fwrapv int32 does, so the two
+    are comparable on ANY int16 x uint16 input; int64 never wraps on such input."""
+    dt = np.int32 if int32 else np.int64
+    x = coef[:, boff[c]:boff[c + 1]].astype(dt) * quant[:, c].astype(dt)[:, None, :]
+    prod = x.reshape(x.shape[0], -1, 8, 8)
+    p1 = np.swapaxes(_idct8(np.swapaxes(prod, -1, -2), 11), -1, -2)          # pass 1: columns
+    pre = _idct8(p1, 18)                                                     # pass 2: rows
+    assert prod.dtype == p1.dtype == pre.dtype == dt
+    return prod, p1, pre
+
+
+def idct(coef, quant, W, H, layout, int32=False):
     """coefficients [F][bpf][64], quant [F][3][64] -> list over components of uint8 planes [F][bh*8][bw*8]."""
     ncomp, mcux, mcuy, hs, bw, bh, boff = _geometry(W, H, layout)
     planes = []
     for c in range(ncomp):
-        x = coef[:, boff[c]:boff[c + 1]].astype(np.int64) * quant[:, c].astype(np.int64)[:, None, :]
-        x = x.reshape(x.shape[0], -1, 8, 8)
-        x = np.swapaxes(_idct8(np.swapaxes(x, -1, -2), 11), -1, -2)          # pass 1: columns
-        x = _idct8(x, 18)                                                    # pass 2: rows
+        x = _stages(coef, quant, c, boff, int32)[2]
         x = ((x & 1023) ^ 512) - 512
         x = np.clip(x + 128, 0, 255).astype(np.uint8)
         F = x.shape[0]
         planes.append(x.reshape(F, bh[c], bw[c], 8, 8).transpose(0, 1, 3, 2, 4).reshape(F, bh[c] * 8, bw[c] * 8))
     return planes
+
+
+def extents(coef, quant, W, H, layout, int32=False):
+    """-> int64 [F][3][2]: per frame the (min, max) of the dequantised products, of the pass-1 values and of the samples
+    before the range limit, over all components."""
+    ncomp, mcux, mcuy, hs, bw, bh, boff = _geometry(W, H, layout)
+    F = coef.shape[0]
+    out = np.zeros((F, 3, 2), np.int64)
+    for c in range(ncomp):
+        for i, v in enumerate(_stages(coef, quant, c, boff, int32)):
+            v = v.reshape(F, -1).astype(np.int64)
+            lo, hi = v.min(1), v.max(1)
+            out[:, i, 0] = lo if c == 0 else np.minimum(out[:, i, 0], lo)
+            out[:, i, 1] = hi if c == 0 else np.maximum(out[:, i, 1], hi)
+    return out
+
+
+def flagged(ext, product=None, pass1=None):
+    """extents -> bool [F]: outside the domain, the word vdx_mjpeg_idct leaves per frame."""
+    product = DOMAIN_PRODUCT if product is None else product
+    pass1 = DOMAIN_PASS1 if pass1 is None else pass1
+    return ((ext[:, 0, 0] < -product - 1) | (ext[:, 0, 1] > product) | (ext[:, 1, 0] < -pass1 - 1) | (ext[:, 1, 1] > pass1) |
+            (ext[:, 2, 0] < DOMAIN_SAMPLE[0]) | (ext[:, 2, 1] > DOMAIN_SAMPLE[1]))
 
 
 def _fancy_h2v2(p, W, H):
@@ -208,10 +248,11 @@ def color(planes, W, H, layout):
     return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
 
 
-def decode(jpegs):
-    """List of JPEG byte strings -> (uint8 frames, error words): the whole decoder on the CPU."""
+def decode(jpegs, with_extents=False):
+    """List of JPEG byte strings -> (uint8 frames, error words[, extents]): the whole decoder on the CPU."""
     blob, off, info, _ = video.plan(jpegs)
     F, W, H, layout = info["n_frames"], info["width"], info["height"], video.LAYOUTS[info["sampling"]]
     coef, err = entropy(blob, off, info)
     quant = blob[off["quant"][0]:off["quant"][0] + F * 3 * 64 * 2].view(np.uint16).reshape(F, 3, 64)
-    return color(idct(coef, quant, W, H, layout), W, H, layout), err
+    frames = color(idct(coef, quant, W, H, layout), W, H, layout)
+    return (frames, err, extents(coef, quant, W, H, layout)) if with_extents else (frames, err)

@@ -166,3 +166,143 @@ def test_the_integer_definition_equals_pillows_decode(h, w, mode, kw):
     want = np.asarray(Image.open(io.BytesIO(j)).convert(mode))
     assert not err.any()
     assert np.array_equal(got[0], want) and np.array_equal(got[1], want)
+
+
+# ---------------------------------------------------------------------------------------------
+# The hand writer (tests/mjpeg_enc.py) and the domain of "bit-equal to Pillow"
+# ---------------------------------------------------------------------------------------------
+import mjpeg_enc  # noqa: E402
+
+
+def pillow(jpeg, mode):
+    return np.asarray(Image.open(io.BytesIO(jpeg)).convert(mode))
+
+
+def test_hand_written_streams_open_in_pillow_and_carry_what_they_claim():
+    """Every valid output of the writer opens in Pillow; the restatement reads back the very coefficients (low 16 bits) and,
+    inside the domain, Pillow's pixels.  The special forms are really in the bytes."""
+    streams = mjpeg_enc.valid_streams()
+    assert set(streams) == {"zrl", "k63-ff00", "dc11", "dc-wrap", "huff16"}
+    for name, (sampling, W, H, blocks, quant, wr, in_domain) in streams.items():
+        mode = "L" if sampling == "L" else "RGB"
+        want = pillow(wr.jpeg, mode)
+        assert want.shape[:2] == (H, W)
+        info = video.parse_jpeg(wr.jpeg)
+        assert (info.width, info.height, info.sampling) == (W, H, sampling)
+        blob, off, pinfo, _ = video.plan([wr.jpeg])
+        coef, err = mjpeg_ref.entropy(blob, off, pinfo)
+        assert not err.any(), name
+        assert np.array_equal(coef[0], blocks.astype(np.int16)), name
+        got, _, ext = mjpeg_ref.decode([wr.jpeg], with_extents=True)
+        assert bool(mjpeg_ref.flagged(ext)[0]) == (not in_domain), name
+        if in_domain:
+            assert np.array_equal(got[0], want), name
+    s = streams["k63-ff00"]
+    seg = video.parse_jpeg(s[5].jpeg).segments
+    assert len(seg) == 2 and all(s[5].jpeg[e - 2:e] == b"\xff\x00" for e in seg[:, 1])       # FF 00 ends both segments
+    assert not np.array_equal(streams["dc-wrap"][3], streams["dc-wrap"][3].astype(np.int16))  # the DC sum left int16
+    assert max(abs(int(b[0]) - int(a[0])) for a, b in zip(streams["dc11"][3][:3], streams["dc11"][3][1:4])) >= 1024   # size 11
+    codes = mjpeg_enc.codes_of(video.parse_jpeg(streams["huff16"][5].jpeg).huffman[(1, 0)])
+    assert {n for _, n in codes.values()} == set(range(10, 17))
+    for mod8 in (0, 1):
+        blocks, wr = mjpeg_enc.sized(mod8)
+        assert wr.seg_bits[0] % 8 == mod8 and pillow(wr.jpeg, "L").shape == (8, 16)
+        assert not mjpeg_ref.decode([wr.jpeg])[1].any()
+
+
+def test_refused_streams_give_their_error_word_in_the_restatement():
+    for name, (jpeg, code, mcu) in mjpeg_enc.error_streams().items():
+        assert mjpeg_ref.decode([jpeg])[1].tolist() == [code | (mcu << 8)], name
+
+
+def test_domain_bounds_are_the_kernels():
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(video.__file__), "csrc", "mjpeg.hip")).read()
+    assert int(re.search(r"#define MJ_DOMAIN_PRODUCT (\d+)", src).group(1)) == mjpeg_ref.DOMAIN_PRODUCT
+    assert int(re.search(r"#define MJ_DOMAIN_PASS1 (\d+)", src).group(1)) == mjpeg_ref.DOMAIN_PASS1
+
+
+def test_int32_mode_equals_int64_where_nothing_wraps_and_wraps_elsewhere():
+    g = np.random.default_rng(0)
+    quant = g.integers(1, 17, (4, 3, 64)).astype(np.uint16)
+    small = g.integers(-8, 9, (4, 6, 64)).astype(np.int16)
+    for a, b in zip(mjpeg_ref.idct(small, quant, 16, 16, 2), mjpeg_ref.idct(small, quant, 16, 16, 2, int32=True)):
+        assert np.array_equal(a, b)
+    assert np.array_equal(mjpeg_ref.extents(small, quant, 16, 16, 2), mjpeg_ref.extents(small, quant, 16, 16, 2, int32=True))
+    big = g.integers(-32768, 32768, (4, 6, 64)).astype(np.int16)
+    wide = g.integers(0, 65536, (4, 3, 64)).astype(np.uint16)
+    e64, e32 = mjpeg_ref.extents(big, wide, 16, 16, 2), mjpeg_ref.extents(big, wide, 16, 16, 2, int32=True)
+    assert np.array_equal(e64[:, 0], e32[:, 0]) and np.abs(e64[:, 1]).max() > 2 ** 31 > np.abs(e32[:, 1]).max()
+
+
+def test_every_stream_inside_the_domain_decodes_as_pillow_does():
+    """The domain of the Pillow claim: a stream with every dequantised product and pass-1 value inside int16 and every sample
+    before the range limit inside [-512, 511] decodes to Pillow's pixels, with no exception among streams whose amplitude
+    sweeps across that boundary (profiles/mjpeg_domain.txt records a run).  A condition, not a tolerance."""
+    res = mjpeg_enc.domain_search(seed=0)
+    print({k: v for k, v in res.items() if k != "counterexamples"})
+    assert res["blocks"] >= 20000
+    assert res["unflagged"] >= 3000 and res["flagged_differ"] >= 3000        # the sweep straddles the boundary
+    assert res["nearest"][0] <= 8                                          # and comes within a few grey levels of it from outside
+    assert res["unflagged_differ"] == 0, res["counterexamples"][:3]
+
+
+def _content(kind, h, w, mode, seed=0):
+    g = np.random.default_rng(seed)
+    shape = (h, w) if mode == "L" else (h, w, 3)
+    if kind == "noise":
+        a = g.integers(0, 256, shape)
+    elif kind == "ramp":
+        yy, xx = np.mgrid[0:h, 0:w]
+        a = xx * 255 // max(w - 1, 1) if mode == "L" else np.stack([xx * 255 // max(w - 1, 1), yy * 255 // max(h - 1, 1),
+                                                                    (xx + yy) * 255 // (w + h - 2)], -1)
+    elif kind == "const":
+        a = np.full(shape, 77)
+    else:
+        a = g.integers(0, 256, shape)
+        a[: h // 2, : w // 3] = 0
+        a[h // 3:, w // 2:] = 255
+    return np.asarray(a, np.int64).clip(0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("kind", ["noise", "ramp", "const", "sat"])
+def test_no_stream_pillow_encoded_from_pixels_is_refused(kind):
+    """No false refusals: the contents of the GPU cases at quality 1 .. 100, both samplings and grey, stay inside the domain
+    (a flag here would mean the bound is wrong, not the image)."""
+    worst = np.zeros((3, 2), np.int64)
+    for quality in (1, 5, 30, 75, 92, 100):
+        for mode, kw in (("RGB", {}), ("RGB", {"subsampling": 0}), ("L", {})):
+            j = jpeg_of(_content(kind, 38, 50, mode, seed=quality), quality=quality, **kw)
+            blob, off, info, _ = video.plan([j])
+            coef = _fast_coefficients(j)
+            quant = blob[off["quant"][0]:off["quant"][0] + 3 * 64 * 2].view(np.uint16).reshape(1, 3, 64)
+            ext = mjpeg_ref.extents(coef[None], quant, 50, 38, video.LAYOUTS[info["sampling"]])
+            worst[:, 0], worst[:, 1] = np.minimum(worst[:, 0], ext[0, :, 0]), np.maximum(worst[:, 1], ext[0, :, 1])
+            assert not mjpeg_ref.flagged(ext)[0], (kind, quality, mode, kw, ext.tolist())
+    print(kind, "extents (product, pass 1, sample):", worst.tolist())
+
+
+def _fast_coefficients(jpeg):
+    blob, off, info, _ = video.plan([jpeg])
+    coef, err = mjpeg_ref.entropy(blob, off, info)
+    assert not err.any()
+    return coef[0]
+
+
+def test_dqt_patched_files_differ_from_pillow_only_outside_the_domain():
+    """A Pillow-encoded noise image whose quantisation tables alone were rewritten to larger legal values: where the
+    restatement (libjpeg's C arithmetic) and Pillow (libjpeg-turbo) return different pixels, the frame is flagged, every one;
+    the unmodified files are never flagged."""
+    differ = flagged = 0
+    for name, original, patched in mjpeg_enc.dqt_family():
+        mode = "RGB"
+        got, err, ext = mjpeg_ref.decode([original, patched], with_extents=True)
+        assert not err.any()
+        flag = mjpeg_ref.flagged(ext)
+        assert not flag[0] and np.array_equal(got[0], pillow(original, mode)), name
+        d = not np.array_equal(got[1], pillow(patched, mode))
+        differ, flagged = differ + d, flagged + int(flag[1])
+        assert flag[1] or not d, f"{name}: differs from Pillow by up to {np.abs(got[1].astype(int) - pillow(patched, mode)).max()} unflagged"
+    print(f"{differ} of 48 patched files differ from Pillow, {flagged} are flagged")
+    assert differ >= 1 and flagged < 48

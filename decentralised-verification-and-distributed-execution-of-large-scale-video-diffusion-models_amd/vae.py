@@ -13,9 +13,10 @@ the UNet's kernels on channels-last fp16 rows [n*h*w][C]:
     post_quant_conv, as in the reference (a plain bias fold would be wrong on the border pixels);
   * ResNet blocks = GroupNorm+SiLU kernels + implicit-GEMM 3x3 convolutions (residual / 1x1 shortcut fused);
   * mid-block attention (ONE head of 512 channels over h*w tokens): q and k GEMMs, V^T by the swapped GEMM (per
-    image), scores = one GEMM per image (fp16 [tokens][tokens], as diffusers' baddbmm materialises them), row softmax
-    kernel (fp32, scale applied in fp32), P.V^T GEMM, output projection with fused residual; the value bias is
-    folded into the output projection's bias (softmax rows sum to 1);
+    image), scores = one GEMM per image (fp16 [tokens][tokens], as diffusers' baddbmm materialises them; a power of two
+    of its 1/sqrt(C) rides in the packed to_q so that they are finite wherever diffusers' are: `qk_fold`), row softmax
+    kernel (fp32, the rest of the scale applied in fp32), P.V^T GEMM, output projection with fused residual; the value
+    bias is folded into the output projection's bias (softmax rows sum to 1);
   * upsamplers = the conv kernel's fused nearest-x2 gather;
   * the video path maps the last rows straight to uint8 HWC frames (`decode_frames_u8`), bit-exact with the
     reference's fp16 mapping given the same decoder output.
@@ -48,6 +49,17 @@ from ._lib import VdxError
 
 GN_PARTITION = 8      # GroupNorm statistics are reduced with the row-slab partition of an 8-frame batch whatever the
                       # batch: a frame decoded alone (as the reference does, :219-225) has the bits of its batched self
+
+
+def qk_fold(C: int) -> Tuple[float, float]:
+    """(pre, scale) of the mid-block attention at width C.  The score GEMM stores q.k^T as fp16 BEFORE the softmax kernel
+    applies 1/sqrt(C), where diffusers' baddbmm(alpha = 1/sqrt(C)) scales first: unscaled, a raw dot product above 65504
+    is +inf and its row NaN, while diffusers' form is finite up to 65504 sqrt(C).  So both loaders pack to_q (weight and
+    bias) times `pre`, the power of two 2^-ceil(log2(C)/2) <= 1/sqrt(C) (2^-5 at C = 512; exact in fp16 above the
+    subnormal range), and `_attention` hands `scale` = 1/(pre sqrt(C)) in [1, 2) to the softmax: pre * scale = 1/sqrt(C),
+    and the stored scores are never larger than diffusers' scaled ones."""
+    pre = 2.0 ** -(((C - 1).bit_length() + 1) // 2)
+    return pre, 1.0 / (pre * math.sqrt(C))
 
 
 @dataclass
@@ -122,9 +134,11 @@ class AutoencoderKL(nn.Module):
         resnet(mb + ".resnets.0", rev[0], rev[0])
         a = mb + ".attentions.0"
         norm(a + ".group_norm")
-        for n in "qk":
-            put(f"{a}.to_{n}.weight", packing.pack_conv1x1(get(f"{a}.to_{n}.weight")))
-            put(f"{a}.to_{n}.bias", get(f"{a}.to_{n}.bias"))
+        pre = qk_fold(rev[0])[0]                                                  # keeps the fp16 scores finite: qk_fold
+        put(a + ".to_q.weight", packing.pack_conv1x1(get(a + ".to_q.weight")).float() * pre)
+        put(a + ".to_q.bias", get(a + ".to_q.bias").float() * pre)
+        put(a + ".to_k.weight", packing.pack_conv1x1(get(a + ".to_k.weight")))
+        put(a + ".to_k.bias", get(a + ".to_k.bias"))
         put(a + ".to_v.weight", packing.pack_conv1x1(get(a + ".to_v.weight")))    # issued as the swapped GEMM (V^T)
         wo = packing.pack_conv1x1(get(a + ".to_out.0.weight"))
         put(a + ".to_out.0.weight", wo)
@@ -186,7 +200,7 @@ class AutoencoderKL(nn.Module):
         o = torch.empty((M, C), dtype=torch.float16, device=x.device)
         scores = torch.empty((S, S), dtype=torch.float16, device=x.device)
         vt = torch.empty((C, S), dtype=torch.float16, device=x.device)
-        scale = 1.0 / math.sqrt(C)
+        scale = qk_fold(C)[1]                                                     # q carries the other factor of 1/sqrt(C)
         for i in range(n):                                                        # one image at a time: [S][S] scores
             rows = slice(i * S, (i + 1) * S)
             ops.gemm(W[p + ".to_v.weight"], t[rows], M=C, out=vt)                 # V^T [C][S] (its bias: see load)
@@ -288,9 +302,11 @@ class AutoencoderKL(nn.Module):
         resnet(mb + ".resnets.0", ch[-1], ch[-1])
         a = mb + ".attentions.0"
         norm(a + ".group_norm")
-        for nm in "qk":
-            put(f"{a}.to_{nm}.weight", packing.pack_conv1x1(get(f"{a}.to_{nm}.weight")))
-            put(f"{a}.to_{nm}.bias", get(f"{a}.to_{nm}.bias"))
+        pre = qk_fold(ch[-1])[0]                                                  # keeps the fp16 scores finite: qk_fold
+        put(a + ".to_q.weight", packing.pack_conv1x1(get(a + ".to_q.weight")).float() * pre)
+        put(a + ".to_q.bias", get(a + ".to_q.bias").float() * pre)
+        put(a + ".to_k.weight", packing.pack_conv1x1(get(a + ".to_k.weight")))
+        put(a + ".to_k.bias", get(a + ".to_k.bias"))
         put(a + ".to_v.weight", packing.pack_conv1x1(get(a + ".to_v.weight")))
         wo = packing.pack_conv1x1(get(a + ".to_out.0.weight"))
         put(a + ".to_out.0.weight", wo)

@@ -1,14 +1,18 @@
 """CPU suite: the AutoencoderKL-decode oracle (structural pins — the diffusers boundary is parity-unpinned,
 oracle/__init__.py) and the product's weight ingest for it."""
+import math
+
 import numpy as np
 import pytest
 import torch
 
 import vdx  # noqa: F401
 from vdx._lib import VdxError
-from vdx.vae import AutoencoderKL, VaeConfig
+from vdx.vae import AutoencoderKL, VaeConfig, qk_fold
 
 from oracle import vae_ref
+
+import vae_blocks_ref as blocks
 
 
 def test_vae_oracle_structure_matches_published_decoder():
@@ -68,3 +72,48 @@ def test_vae_decode_has_no_cpu_path():
     m.load_diffusers_state_dict({k: v.half() for k, v in vae_ref.synthetic_state_dict(cfg).items()})
     with pytest.raises(VdxError):
         m.decode(torch.zeros(1, 4, 8, 8, dtype=torch.float16))
+
+
+def _loaded_attention(C, regime):
+    """Both loaders on the CPU on the tables of tests/vae_blocks_ref.py -> [(packed table, key prefix)], the raw parameters."""
+    dec, enc, ch, layers = blocks.tables(C, regime)
+    m = AutoencoderKL(VaeConfig(block_out_channels=ch, layers_per_block=layers))
+    m.load_diffusers_state_dict(dec).load_diffusers_encoder_state_dict(enc)
+    return [(m.W, f"decoder.{blocks.ATT}."), (m.E, f"encoder.{blocks.ATT}.")], blocks.attention_params(C, regime)
+
+
+@pytest.mark.parametrize("C", [128, 512])
+def test_vae_value_bias_is_folded_behind_to_out(C):
+    """P.(V + 1 b_v^T) = P.V + b_v: the packed to_out bias is b_out + W_out.b_v (fp64) to one fp16 rounding, with a value bias
+    of magnitude 5 that dominates it, and no to_v.bias is kept."""
+    tabs, p = _loaded_attention(C, "e")
+    want = p["to_out.0.bias"].double() + p["to_out.0.weight"].double() @ p["to_v.bias"].double()
+    assert float(want.abs().max()) > 1.0
+    for T, a in tabs:
+        assert a + "to_v.bias" not in T and T[a + "to_out.0.bias"].dtype == torch.float16
+        err = (T[a + "to_out.0.bias"].double() - want).abs()
+        ulp = 2.0 ** torch.floor(torch.log2(want.abs().clamp_min(2.0 ** -14))) * 2.0 ** -10
+        assert (err <= 0.5 * ulp * (1 + 2.0 ** -8)).all(), float((err / ulp).max())   # 2^-8: the loader forms it in fp32
+        assert torch.equal(T[a + "to_out.0.weight"], p["to_out.0.weight"])
+
+
+@pytest.mark.parametrize("C,regime", [(128, "a"), (512, "a"), (512, "d23")])
+def test_vae_to_q_carries_a_power_of_two_of_the_softmax_scale(C, regime):
+    """The fp16 scores stay finite wherever diffusers' scaled ones do: packed to_q = to_q * pre with pre a power of two
+    <= 1/sqrt(C), and the scale handed to the softmax restores to_q / sqrt(C) - exactly for every weight whose packed value
+    is a normal fp16 number, to half a subnormal step below that."""
+    pre, scale = qk_fold(C)
+    assert math.frexp(pre)[0] == 0.5 and pre * math.sqrt(C) <= 1.0 < 2 * pre * math.sqrt(C)
+    assert 1.0 <= scale < 2.0 and math.isclose(pre * scale, 1.0 / math.sqrt(C), rel_tol=2.0 ** -52)
+    assert qk_fold(512)[0] == 2.0 ** -5
+    tabs, p = _loaded_attention(C, regime)
+    for T, a in tabs:
+        for kind in ("weight", "bias"):
+            raw, packed = p[f"to_q.{kind}"].double(), T[a + f"to_q.{kind}"].double()
+            normal = (raw * pre).abs() >= 2.0 ** -14
+            assert normal.float().mean() > 0.9 or kind == "bias"
+            assert torch.equal(packed[normal] / pre, raw[normal])
+            assert torch.equal(packed[normal] * scale, raw[normal] * (pre * scale))               # pre * scale: 1/sqrt(C) as fp64 has it
+            assert torch.allclose(packed[normal] * scale, raw[normal] / math.sqrt(C), rtol=2.0 ** -50, atol=0.0)
+            assert ((packed / pre - raw).abs() <= 2.0 ** -25 / pre).all()
+            assert torch.equal(T[a + f"to_k.{kind}"], p[f"to_k.{kind}"])                      # to_k is packed as it is

@@ -130,11 +130,18 @@ SIGNATURES = {
     "vdx_flow_update_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vdx_flow_abs_sum_f32": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:200-264 the writer)
+    # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_mjpeg_idct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_mjpeg_color": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    # Motion-JPEG encode (fsdp_chunked_coherent.py:250-253 cv2.VideoWriter; cv2_shim.py VideoWriter.write the host path)
+    "vdx_mjpeg_enc_workspace": (_sz, [_i, _i, _i, _i]),
+    "vdx_mjpeg_enc_offsets": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "vdx_mjpeg_enc_color": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_mjpeg_enc_fdct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_mjpeg_enc_entropy": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vdx_mjpeg_enc_pack": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

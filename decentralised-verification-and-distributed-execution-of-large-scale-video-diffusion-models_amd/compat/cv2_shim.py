@@ -204,6 +204,46 @@ def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
     return _box(kind, struct.pack(">I", (version << 24) | flags) + payload)
 
 
+_FTYP = _box(b"ftyp", b"isom" + struct.pack(">I", 0x200) + b"isomiso2mp41")
+
+
+def moov_box(sizes, fps, w, h, mdat_pos) -> bytes:
+    """The index of a file whose one chunk of Motion-JPEG samples (`sizes` bytes each, back to back) starts 8 bytes after
+    `mdat_pos`: one video track, `mp4v` sample entry with object type 0x6C."""
+    n = len(sizes)
+    ts = max(int(round(fps * 1000)), 1)                        # media timescale; one sample lasts 1000 ticks
+    dur = n * 1000
+    mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIII", 0, 0, ts, dur) + struct.pack(">IH", 0x00010000, 0x0100) + b"\0" * 10 +
+                 struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000) + b"\0" * 24 + struct.pack(">I", 2))
+    tkhd = _full(b"tkhd", 0, 3, struct.pack(">IIIII", 0, 0, 1, 0, dur) + b"\0" * 8 + struct.pack(">HHHH", 0, 0, 0, 0) +
+                 struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000) +
+                 struct.pack(">II", w << 16, h << 16))
+    mdhd = _full(b"mdhd", 0, 0, struct.pack(">IIIIHH", 0, 0, ts, dur, 0x55C4, 0))
+    hdlr = _full(b"hdlr", 0, 0, struct.pack(">I", 0) + b"vide" + b"\0" * 12 + b"VideoHandler\0")
+    # ES descriptor: object type 0x6C = JPEG (ISO/IEC 10918-1), stream type 4 = visual
+    dcd = bytes([0x04, 13, 0x6C, 0x11, 0, 0, 0]) + struct.pack(">II", 0, 0)
+    esd = bytes([0x03, 3 + len(dcd) + 3, 0, 1, 0]) + dcd + bytes([0x06, 1, 2])
+    entry = (b"\0" * 6 + struct.pack(">H", 1) + b"\0" * 16 + struct.pack(">HH", w, h) +
+             struct.pack(">II", 0x00480000, 0x00480000) + struct.pack(">I", 0) + struct.pack(">H", 1) + b"\0" * 32 +
+             struct.pack(">Hh", 24, -1) + _full(b"esds", 0, 0, esd))
+    stsd = _full(b"stsd", 0, 0, struct.pack(">I", 1) + _box(b"mp4v", entry))
+    stts = _full(b"stts", 0, 0, struct.pack(">III", 1, n, 1000))
+    stsc = _full(b"stsc", 0, 0, struct.pack(">IIII", 1, 1, max(n, 1), 1))
+    stsz = _full(b"stsz", 0, 0, struct.pack(">II", 0, n) + b"".join(struct.pack(">I", s) for s in sizes))
+    stco = _full(b"stco", 0, 0, struct.pack(">II", 1, mdat_pos + 8))
+    stbl = _box(b"stbl", stsd + stts + stsc + stsz + stco)
+    dinf = _box(b"dinf", _full(b"dref", 0, 0, struct.pack(">I", 1) + _full(b"url ", 0, 1, b"")))
+    minf = _box(b"minf", _full(b"vmhd", 0, 1, b"\0" * 8) + dinf + stbl)
+    trak = _box(b"trak", tkhd + _box(b"mdia", mdhd + hdlr + minf))
+    return _box(b"moov", mvhd + trak)
+
+
+def mp4_bytes(jpegs, fps, w, h) -> bytes:
+    """The whole file `VideoWriter` leaves after writing these samples: ftyp, mdat, moov."""
+    body = b"".join(jpegs)
+    return _FTYP + _box(b"mdat", body) + moov_box([len(j) for j in jpegs], float(fps), int(w), int(h), len(_FTYP))
+
+
 class VideoWriter:
     def __init__(self, filename=None, fourcc=0, fps=0.0, frameSize=(0, 0), isColor=True, restart_rows=0):
         self._f = None
@@ -215,7 +255,7 @@ class VideoWriter:
         self._path, self._fps, (self._w, self._h) = filename, float(fps), (int(frameSize[0]), int(frameSize[1]))
         self._sizes = []
         self._f = open(filename, "wb")
-        self._f.write(_box(b"ftyp", b"isom" + struct.pack(">I", 0x200) + b"isomiso2mp41"))
+        self._f.write(_FTYP)
         self._mdat_pos = self._f.tell()
         self._f.write(struct.pack(">I", 0) + b"mdat")          # size patched in release()
         return True
@@ -239,36 +279,12 @@ class VideoWriter:
     def release(self):
         if self._f is None:
             return
-        f, n = self._f, len(self._sizes)
+        f = self._f
         end = f.tell()
         f.seek(self._mdat_pos)
         f.write(struct.pack(">I", end - self._mdat_pos))
         f.seek(end)
-        ts = max(int(round(self._fps * 1000)), 1)                  # media timescale; one sample lasts 1000 ticks
-        dur = n * 1000
-        mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIII", 0, 0, ts, dur) + struct.pack(">IH", 0x00010000, 0x0100) + b"\0" * 10 +
-                     struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000) + b"\0" * 24 + struct.pack(">I", 2))
-        tkhd = _full(b"tkhd", 0, 3, struct.pack(">IIIII", 0, 0, 1, 0, dur) + b"\0" * 8 + struct.pack(">HHHH", 0, 0, 0, 0) +
-                     struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000) +
-                     struct.pack(">II", self._w << 16, self._h << 16))
-        mdhd = _full(b"mdhd", 0, 0, struct.pack(">IIIIHH", 0, 0, ts, dur, 0x55C4, 0))
-        hdlr = _full(b"hdlr", 0, 0, struct.pack(">I", 0) + b"vide" + b"\0" * 12 + b"VideoHandler\0")
-        # ES descriptor: object type 0x6C = JPEG (ISO/IEC 10918-1), stream type 4 = visual
-        dcd = bytes([0x04, 13, 0x6C, 0x11, 0, 0, 0]) + struct.pack(">II", 0, 0)
-        esd = bytes([0x03, 3 + len(dcd) + 3, 0, 1, 0]) + dcd + bytes([0x06, 1, 2])
-        entry = (b"\0" * 6 + struct.pack(">H", 1) + b"\0" * 16 + struct.pack(">HH", self._w, self._h) +
-                 struct.pack(">II", 0x00480000, 0x00480000) + struct.pack(">I", 0) + struct.pack(">H", 1) + b"\0" * 32 +
-                 struct.pack(">Hh", 24, -1) + _full(b"esds", 0, 0, esd))
-        stsd = _full(b"stsd", 0, 0, struct.pack(">I", 1) + _box(b"mp4v", entry))
-        stts = _full(b"stts", 0, 0, struct.pack(">III", 1, n, 1000))
-        stsc = _full(b"stsc", 0, 0, struct.pack(">IIII", 1, 1, max(n, 1), 1))
-        stsz = _full(b"stsz", 0, 0, struct.pack(">II", 0, n) + b"".join(struct.pack(">I", s) for s in self._sizes))
-        stco = _full(b"stco", 0, 0, struct.pack(">II", 1, self._mdat_pos + 8))
-        stbl = _box(b"stbl", stsd + stts + stsc + stsz + stco)
-        dinf = _box(b"dinf", _full(b"dref", 0, 0, struct.pack(">I", 1) + _full(b"url ", 0, 1, b"")))
-        minf = _box(b"minf", _full(b"vmhd", 0, 1, b"\0" * 8) + dinf + stbl)
-        trak = _box(b"trak", tkhd + _box(b"mdia", mdhd + hdlr + minf))
-        f.write(_box(b"moov", mvhd + trak))
+        f.write(moov_box(self._sizes, self._fps, self._w, self._h, self._mdat_pos))
         f.close()
         self._f = None
 

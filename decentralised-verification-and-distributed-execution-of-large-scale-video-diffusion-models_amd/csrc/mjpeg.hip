@@ -1,12 +1,13 @@
 // mjpeg.hip — baseline JPEG decode of a whole Motion-JPEG clip on the device: the read side of the validator's
 // `cv2.VideoCapture(video_path)` (InferNet/template/validator/scoring.py:16, :110, :230, :272, :314) for the files
-// vdx/compat/cv2_shim.py:200-264 writes.  Three stages, integers only, no atomics: the same bits on every run and for any
+// vdx/compat/cv2_shim.py:199-289 writes.  Three stages, integers only, no atomics: the same bits on every run and for any
 // number of frames per launch, and the bits of libjpeg's own decode (slow-integer IDCT, h2v2 "fancy" upsampling, the 16-bit
 // fixed-point YCbCr -> RGB), which is what Pillow returns, for every frame whose coefficients lie in the range 8-bit samples
 // produce; stage 2 flags the frames outside it (MJ_DOMAIN_* below), where decoders disagree, and the host refuses them.
 // The host (vdx/video.py) walks the markers, builds the Huffman lookups from the stream's DHT segments and cuts the scan at
 // its restart markers; nothing here trusts what it built beyond the checks below: the entropy bytes come from another machine.
 #include "vdx_common.h"
+#include "mjpeg_common.h"
 
 #define MJ_HUFF_WORDS 384        // one Huffman table: 512 x u16 9-bit lookahead | maxcode[17] | valoff[17] | 256 symbols | pad
 #define MJ_FAST_BITS 9
@@ -15,35 +16,6 @@
 #define MJ_SYMS 290
 
 enum { MJ_OK = 0, MJ_ERR_DATA_END = 1, MJ_ERR_COEF_INDEX = 2, MJ_ERR_BAD_CODE = 3, MJ_ERR_DC_SIZE = 4, MJ_ERR_SEGMENT = 5 };
-
-// Block geometry of one frame.  layout 0: one component; 1: three components 1x1 (4:4:4); 2: 2x2, 1x1, 1x1 (4:2:0).
-// Component c holds bw[c] x bh[c] blocks (the padded MCU extent) from block boff[c] of the frame; bpf blocks per frame.
-struct MjLayout {
-    int ncomp, mcux, mcuy, nmcu, bpf;
-    int h[3], v[3], bw[3], bh[3], boff[3];
-};
-
-static int mj_layout(int W, int H, int layout, MjLayout* L) {
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || layout < 0 || layout > 2) return -1;
-    const int hmax = layout == 2 ? 2 : 1;
-    L->ncomp = layout == 0 ? 1 : 3;
-    L->mcux = (W + 8 * hmax - 1) / (8 * hmax);
-    L->mcuy = (H + 8 * hmax - 1) / (8 * hmax);
-    L->nmcu = L->mcux * L->mcuy;
-    int off = 0;
-    for (int c = 0; c < 3; ++c) {
-        const int s = (c == 0 && c < L->ncomp) ? hmax : (c < L->ncomp ? 1 : 0);
-        L->h[c] = L->v[c] = s;
-        L->bw[c] = L->mcux * s;
-        L->bh[c] = L->mcuy * s;
-        L->boff[c] = off;
-        off += L->bw[c] * L->bh[c];
-    }
-    L->bpf = off;
-    return 0;
-}
-
-static inline size_t mj_round(size_t n) { return (n + 255) & ~(size_t)255; }
 
 extern "C" size_t vdx_mjpeg_workspace(int F, int W, int H, int layout) {
     MjLayout L;
@@ -64,10 +36,6 @@ extern "C" size_t vdx_mjpeg_workspace(int F, int W, int H, int layout) {
 //   * tables: lookups index LDS with 9 or at most 8 masked bits;
 //   * coefficients: k is compared with 63 before the store, the block index follows from the MCU number alone, and the MCU
 //     range is clamped to the frame's MCU count.
-__device__ const unsigned char mj_natural[64] = {
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 struct MjBits {
     const uint32_t* words;
     uint32_t pos, end, cur, cur_idx;

@@ -70,10 +70,17 @@ def flow_warp_error(frames: Sequence[np.ndarray], ranges: Sequence[Tuple[int, in
     return float(np.mean(diffs)) if diffs else None
 
 
-def write_video(frames: Sequence[np.ndarray], path: str, fps: float, restart_rows: int = 0) -> None:
+def write_video(frames: Sequence[np.ndarray], path: str, fps: float, restart_rows: int = 0, device=None) -> None:
     """:250-253 — `cv2.VideoWriter(path, fourcc("mp4v"), fps, (W, H))`, frames RGB -> BGR, release.  `restart_rows` > 0 (not
     the reference's): the project's own Motion-JPEG writer with a restart marker every that many MCU rows, for the GPU
-    decoder (vdx/video.py); 0 writes what it always wrote."""
+    decoder (vdx/video.py); 0 writes what it always wrote.  With a `device` the frames (a uint8 tensor there, or host frames,
+    which are uploaded) are encoded in HIP kernels on it (vdx.video.write_frames): the file the project's own writer leaves,
+    byte for byte; the default is the host path."""
+    if device is not None:
+        from . import video
+        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.stack(frames)))
+        video.write_frames(path, t.to(device), fps, restart_rows=restart_rows)
+        return
     h, w = frames[0].shape[:2]
     if restart_rows > 0:
         from .compat import cv2_shim as cv2

@@ -516,7 +516,9 @@ def build_arg_parser():
     the MD-VQS record then carries `"flow": "gpu"`.  `--video_restart_rows N` writes the mp4's JPEG frames with a restart marker
     every N MCU rows (vdx/compat/cv2_shim.py), and `--score_from_file` makes `--clip_json` / `--mdvqs_json` score the frames
     decoded back from the written mp4 on the GPU (vdx/video.py: what a validator holding the file would score) instead of the
-    frames in memory; the records then carry `"source": "file"`."""
+    frames in memory; the records then carry `"source": "file"`.  `--gpu_video_write` encodes the mp4's JPEG frames in HIP
+    kernels (vdx/video.py `write_frames`, csrc/mjpeg_enc.hip) instead of in Pillow on the host: the same file byte for byte,
+    with or without `--video_restart_rows`."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -546,6 +548,8 @@ def build_arg_parser():
     p.add_argument("--gpu_flow", action="store_true", help="Farneback flow of flow_err and of MD-VQS' TC on the GPU (vdx/flow.py)")
     p.add_argument("--video_restart_rows", type=int, default=0,
                    help="restart marker every N MCU rows in the mp4's JPEG frames (0: none, the bytes written without this flag)")
+    p.add_argument("--gpu_video_write", action="store_true",
+                   help="encode the mp4's JPEG frames on the GPU (vdx.video.write_frames): the same file as without this flag")
     p.add_argument("--score_from_file", action="store_true",
                    help="--clip_json / --mdvqs_json score the frames decoded back from --out_video (vdx/video.py)")
     p.add_argument("--init_video", default=None,
@@ -642,7 +646,7 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev):
 
 
 def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
-            clip_inputs: Optional[dict] = None, video_restart_rows: int = 0) -> dict:
+            clip_inputs: Optional[dict] = None, video_restart_rows: int = 0, gpu_video_write: bool = False) -> dict:
     """The reference's `DistributedVideoDiffuser(cfg)()` (:47-276) end to end -> its result dict (:263-275): pipeline
     components (`model_id` = a local checkpoint directory in diffusers layout, else seeded synthetic weights: nothing can be
     downloaded here), text embeddings (:96-103), chunked denoising + exchange + blend, per-frame VAE decode (:219-225),
@@ -694,7 +698,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
         temp_instab = metrics.boundary_l1(frames, ranges)
         flow_err = metrics.flow_warp_error(frames, ranges, device=dev) if cfg.gpu_flow else metrics.flow_warp_error(frames, ranges)
     if d.rank == 0 and out_video:
-        metrics.write_video(frames, out_video, cfg.fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}))
+        metrics.write_video(frames, out_video, cfg.fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}),
+                            **({"device": dev} if gpu_video_write else {}))
     delay = emu_reduce_delay_s(cfg)             # :257-258
     if delay > 0:
         time.sleep(delay)
@@ -726,7 +731,8 @@ def main(argv=None) -> int:
     if a.score_from_file and not a.out_video:
         raise ValueError("--score_from_file needs --out_video")
     res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs,
-                  **({"video_restart_rows": a.video_restart_rows} if a.video_restart_rows else {}))
+                  **({"video_restart_rows": a.video_restart_rows} if a.video_restart_rows else {}),
+                  **({"gpu_video_write": True} if a.gpu_video_write else {}))
     if res["rank"] == 0:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)

@@ -4,7 +4,7 @@ validator entry point of the reference starts (InferNet/template/validator/scori
     read_frames(src, device="cuda") -> (uint8 frames (F, H, W, 3) RGB or (F, H, W) grey on the device, info)
 
 `src` is a path, the file's bytes, or a list of JPEG byte strings.  The container is the one `vdx/compat/cv2_shim.py`
-(:200-264) writes: ISO base media, `ftyp`, `mdat`, `moov`, one video track whose `stsd` holds an `mp4v` entry with an `esds`
+(:199-289) writes: ISO base media, `ftyp`, `mdat`, `moov`, one video track whose `stsd` holds an `mp4v` entry with an `esds`
 of object type 0x6C (JPEG), `stsz` / `stco` / `stsc` / `stts`; a bare JPEG is a clip of one frame.  Anything else (`avc1`, real
 MPEG-4 part 2: the reference miner's own files) raises `VdxError`: this is a Motion-JPEG reader and no more.
 
@@ -24,6 +24,10 @@ name instead of returning one of the possible images.
 
 One upload (entropy bytes and all tables in one buffer) and one synchronisation (the per-segment error words and the
 per-frame domain words, one buffer) per call.
+
+The write side is the second half of the module: `encode_frames` / `write_frames` turn uint8 frames on the GPU into the bytes
+`cv2_shim.VideoWriter` writes for them (csrc/mjpeg_enc.hip), pinned byte for byte to Pillow's encoder
+(tests/test_video_enc_host.py, tests/test_video_enc_gpu.py); the host builds the header and the container only.
 """
 from __future__ import annotations
 
@@ -537,3 +541,182 @@ def read_frames(src: Union[str, os.PathLike, bytes, Sequence[bytes]], device="cu
         raise VdxError(f"read_frames: frame {f} holds coefficients outside the range of 8-bit samples, on which libjpeg, "
                        f"libjpeg-turbo and this decoder disagree ({int(np.count_nonzero(outside))} of {F} frames)")
     return out, info
+
+
+# ---------------------------------------------------------------------------------------------
+# The write side: frames on the device -> the bytes cv2_shim.VideoWriter writes (csrc/mjpeg_enc.hip)
+# ---------------------------------------------------------------------------------------------
+# ITU-T T.81 Annex K: the example quantisation tables (natural order) and the typical Huffman tables (16 counts + symbols).
+_QUANT_LUMA = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
+               80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92,
+               95, 98, 112, 100, 103, 99]
+_QUANT_CHROMA = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99] + \
+    [99] * 36
+_AC_LUMA_SYMS = (
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43"
+    "4445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2"
+    "b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_AC_CHROMA_SYMS = (
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+    "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+    "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+STANDARD_HUFFMAN = {
+    (0, 0): bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]) + bytes(range(12)),
+    (0, 1): bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]) + bytes(range(12)),
+    (1, 0): bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D]) + bytes.fromhex(_AC_LUMA_SYMS),
+    (1, 1): bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]) + bytes.fromhex(_AC_CHROMA_SYMS),
+}
+ENC_TABLE_WORDS = 272                 # csrc/mjpeg_enc.hip MJE_TABLE_WORDS: 16 DC + 256 AC words of (length << 16 | code)
+ENC_SLOT_BYTES = 208                  # csrc/mjpeg_enc.hip MJE_SLOT_BYTES: the most one block's codes can take
+
+
+def quant_tables(quality: int = 92) -> np.ndarray:
+    """The Annex K tables scaled as libjpeg's jpeg_set_quality does (baseline: clamped to 1..255) -> int64 [2][64], natural
+    order: luma, chroma."""
+    quality = min(max(int(quality), 1), 100)
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    base = np.array([_QUANT_LUMA, _QUANT_CHROMA], np.int64)
+    return np.clip((base * scale + 50) // 100, 1, 255)
+
+
+def _marker(m: int, body: bytes) -> bytes:
+    return bytes([0xFF, m]) + struct.pack(">H", len(body) + 2) + body
+
+
+def _mcu_grid(W: int, H: int, sampling: str) -> Tuple[int, int]:
+    step = 16 if sampling == "4:2:0" else 8
+    return -(-W // step), -(-H // step)
+
+
+def jpeg_header(W: int, H: int, sampling: str, quality: int = 92, restart_rows: int = 0) -> bytes:
+    """Everything Pillow (libjpeg) writes before the entropy data of a baseline frame with the standard Huffman tables:
+    SOI, JFIF APP0, DQT per table, SOF0, DHT per table, DRI when `restart_rows` > 0, SOS.  `sampling`: "4:2:0" or "L"."""
+    if sampling not in ("4:2:0", "L"):
+        raise VdxError(f"jpeg_header: sampling {sampling!r} is not written here (\"4:2:0\" or \"L\")")
+    if not (0 < W <= 65535 and 0 < H <= 65535):
+        raise VdxError(f"jpeg_header: {W}x{H} is outside what a JPEG frame header holds")
+    ncomp = 1 if sampling == "L" else 3
+    q = quant_tables(quality)
+    out = b"\xff\xd8" + _marker(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for t in range(2 if ncomp == 3 else 1):
+        out += _marker(0xDB, bytes([t]) + bytes(int(v) for v in q[t][_ZIGZAG]))
+    comps = [(1, 0x22 if ncomp == 3 else 0x11, 0), (2, 0x11, 1), (3, 0x11, 1)][:ncomp]
+    out += _marker(0xC0, struct.pack(">BHHB", 8, H, W, ncomp) + b"".join(bytes(c) for c in comps))
+    for t in range(2 if ncomp == 3 else 1):
+        out += _marker(0xC4, bytes([t]) + STANDARD_HUFFMAN[(0, t)]) + _marker(0xC4, bytes([0x10 | t]) + STANDARD_HUFFMAN[(1, t)])
+    if restart_rows > 0:
+        dri = restart_rows * _mcu_grid(W, H, sampling)[0]
+        if dri > 65535:
+            raise VdxError(f"jpeg_header: a restart interval of {dri} MCUs does not fit the DRI segment")
+        out += _marker(0xDD, struct.pack(">H", dri))
+    out += _marker(0xDA, bytes([ncomp]) + b"".join(bytes([c + 1, 0x11 if c else 0]) for c in range(ncomp)) + bytes([0, 63, 0]))
+    return out
+
+
+def encoder_tables() -> np.ndarray:
+    """The standard tables as the encoder kernels index them -> uint32 [2][272]: per table id 16 DC words (by size) and 256
+    AC words (by run << 4 | size), each `length << 16 | code`; 0 for a symbol the table does not hold."""
+    out = np.zeros((2, ENC_TABLE_WORDS), np.uint32)
+    for (tc, th), payload in STANDARD_HUFFMAN.items():
+        code = k = 0
+        for ln in range(1, 17):
+            for _ in range(payload[ln - 1]):
+                out[th, (16 if tc else 0) + payload[16 + k]] = (ln << 16) | code
+                code += 1
+                k += 1
+            code <<= 1
+    return out
+
+
+ENC_STAGES = ("coef", "planes", "bits", "segbits", "slots", "raw")      # vdx_mjpeg_enc_offsets
+
+
+def encode_frames(frames: torch.Tensor, quality: int = 92, restart_rows: int = 0, sampling: Optional[str] = None,
+                  _events: Optional[list] = None, _stages: Optional[dict] = None) -> List[bytes]:
+    """Encode uint8 frames that are on the GPU as baseline JPEG there -> one byte string per frame, byte for byte what
+    `Image.save(format="JPEG", quality=quality)` (Pillow on libjpeg) writes for the same frame: (F, H, W, 3) RGB as 4:2:0,
+    (F, H, W) as grey; `restart_rows` > 0 as Pillow's `restart_marker_rows`.  One copy of the per-frame lengths and one of the
+    packed bytes come back from the device.  Raises `VdxError` for anything else."""
+    if not isinstance(frames, torch.Tensor):
+        raise VdxError("encode_frames: frames must be a torch tensor on the GPU")
+    if frames.device.type != "cuda":
+        raise VdxError("encode_frames: the encoder runs on the GPU (frames must be on a cuda device)")
+    if frames.dtype != torch.uint8:
+        raise VdxError(f"encode_frames: frames must be uint8, not {frames.dtype}")
+    if frames.dim() == 4 and frames.shape[3] == 3:
+        layout, want = 2, "4:2:0"
+    elif frames.dim() == 3:
+        layout, want = 0, "L"
+    else:
+        raise VdxError(f"encode_frames: frames of shape {tuple(frames.shape)}: (F, H, W, 3) RGB or (F, H, W) grey expected")
+    if sampling is not None and sampling != want:
+        raise VdxError(f"encode_frames: sampling {sampling!r} is not written for frames of shape {tuple(frames.shape)} "
+                       f"(only {want!r})")
+    F, H, W = (int(v) for v in frames.shape[:3])
+    if F * H * W == 0:
+        raise VdxError(f"encode_frames: empty frames {tuple(frames.shape)}")
+    if restart_rows < 0:
+        raise VdxError(f"encode_frames: restart_rows={restart_rows}")
+    header = jpeg_header(W, H, want, quality, restart_rows)
+    dri = restart_rows * _mcu_grid(W, H, want)[0]
+    lib = _lib.load()
+    ws_bytes = lib.vdx_mjpeg_enc_workspace(F, W, H, layout)
+    if ws_bytes == 0:
+        raise VdxError(f"encode_frames: {F} frames of {W}x{H} are outside what the encoder takes")
+    # the one upload: header | quantisation tables uint16 [2][64] | code tables uint32 [2][272]
+    hb = _align(len(header))
+    consts = np.zeros(hb + 256 + 2 * ENC_TABLE_WORDS * 4, np.uint8)
+    consts[:len(header)] = np.frombuffer(header, np.uint8)
+    consts[hb:hb + 256] = quant_tables(quality).astype(np.uint16).reshape(-1).view(np.uint8)
+    consts[hb + 256:] = encoder_tables().reshape(-1).view(np.uint8)
+    dev = frames.device
+    with torch.cuda.device(dev):
+        frames = frames.contiguous()
+        up = torch.from_numpy(consts).to(dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        lengths = torch.empty(F, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def mark():
+            if _events is not None:
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record()
+                _events.append(ev)
+
+        mark()
+        _lib.check(lib.vdx_mjpeg_enc_color(frames.data_ptr(), F, W, H, layout, ws.data_ptr(), stream), "vdx_mjpeg_enc_color")
+        mark()
+        _lib.check(lib.vdx_mjpeg_enc_fdct(up.data_ptr() + hb, F, W, H, layout, ws.data_ptr(), stream), "vdx_mjpeg_enc_fdct")
+        mark()
+        _lib.check(lib.vdx_mjpeg_enc_entropy(up.data_ptr() + hb + 256, F, W, H, layout, dri, len(header), ws.data_ptr(),
+                                             lengths.data_ptr(), stream), "vdx_mjpeg_enc_entropy")
+        mark()
+        sizes = lengths.cpu().numpy().astype(np.int64)                      # copy 1: the per-frame lengths
+        total = int(sizes.sum())
+        if sizes.min() < len(header) + 2 or total >= 1 << 40:
+            raise VdxError("encode_frames: the device returned impossible frame lengths")
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        mark()
+        _lib.check(lib.vdx_mjpeg_enc_pack(up.data_ptr(), len(header), F, W, H, layout, dri, ws.data_ptr(), lengths.data_ptr(),
+                                          out.data_ptr(), total, stream), "vdx_mjpeg_enc_pack")
+        mark()
+        data = out.cpu().numpy().tobytes()                                  # copy 2: the packed bytes
+        if _stages is not None:
+            import ctypes
+            offs = (ctypes.c_size_t * 6)()
+            _lib.check(lib.vdx_mjpeg_enc_offsets(F, W, H, layout, offs), "vdx_mjpeg_enc_offsets")
+            ends = list(offs[1:]) + [ws_bytes]
+            for name, a, b in zip(ENC_STAGES, offs, ends):
+                _stages[name] = ws[a:b].cpu().numpy()
+    ends = np.cumsum(sizes)
+    return [data[int(e - n):int(e)] for e, n in zip(ends, sizes)]
+
+
+def write_frames(path: Union[str, os.PathLike], frames: torch.Tensor, fps: float, restart_rows: int = 0) -> None:
+    """Write frames that are on the GPU as the Motion-JPEG .mp4 `cv2_shim.VideoWriter` writes for them (RGB frames; the same
+    file byte for byte): `encode_frames` on the device, the container through the writer's own box builder."""
+    from .compat import cv2_shim
+    jpegs = encode_frames(frames, 92, restart_rows)
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    with open(os.fspath(path), "wb") as f:
+        f.write(cv2_shim.mp4_bytes(jpegs, fps, W, H))

@@ -552,7 +552,7 @@ int vdx_flow_remap_absdiff_u8(const void* frames, size_t frame_pitch, int row_pi
 /* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
- *   vdx/compat/cv2_shim.py:200-264                                      the writer whose .mp4 this reads back
+ *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back
  * (csrc/mjpeg.hip; vdx/video.py parses the container and the JPEG headers on the host).  Baseline sequential JPEG, 8 bit;
  * `layout` 0: one component, 1: three components 1x1 (4:4:4), 2: 2x2, 1x1, 1x1 (4:2:0).  All frames of a call share W, H and
  * layout.  Integers only and no atomics: the same bits on every run and for any number of frames per call, and bit for bit
@@ -585,6 +585,41 @@ int vdx_mjpeg_idct(const void* quant_u16, int F, int W, int H, int layout, void*
 /* Stage 3: 4:2:0 chroma through the h2v2 fancy upsampling (edges replicate at ceil(W/2) x ceil(H/2)), YCbCr -> RGB, crop:
  * out uint8 (F, H, W, 3) RGB packed, or (F, H, W) for layout 0.  4-byte aligned.  4:2:0 needs W >= 5.                   */
 int vdx_mjpeg_color(const void* workspace, int F, int W, int H, int layout, void* out, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Motion-JPEG encode of a whole clip: the write side of the job's cv2.VideoWriter
+ *   fsdp_chunked_coherent.py:250-253            the reference writes the decoded frames to an .mp4
+ *   vdx/compat/cv2_shim.py VideoWriter.write    the host path (Pillow, quality 92) whose bytes this reproduces
+ * (csrc/mjpeg_enc.hip; vdx/video.py builds the header and the container on the host).  Baseline JPEG with the standard
+ * Huffman tables; `layout` 0: grey, 2: 4:2:0 (as above; 4:4:4 is not written).  Integers only; the only atomics are ORs into
+ * zeroed words: the same bytes on every run and for any number of frames per call, and byte for byte libjpeg's (Pillow's)
+ * for the same frames, every width and height included.  The four stages share `workspace` (vdx_mjpeg_enc_workspace bytes,
+ * 16-byte aligned) and are enqueued in this order; the coefficients and planes lie where vdx_mjpeg_workspace puts them.
+ * ---------------------------------------------------------------------------------------- */
+/* Bytes of workspace for F frames of W x H; 0 for arguments the encoder does not take.                                  */
+size_t vdx_mjpeg_enc_workspace(int F, int W, int H, int layout);
+/* offsets[6] (host memory): byte offsets in the workspace of the int16 coefficients [F][block][64], the uint8 component planes,
+ * the uint32 bit offsets [F][block] (scan order), the uint32 bits per restart interval [F][MCUs], the uint32 byte offsets of
+ * the slots [F][block] and the unstuffed bit stream (208 bytes per block, 32-bit words, first bit in the MSB).           */
+int vdx_mjpeg_enc_offsets(int F, int W, int H, int layout, size_t* offsets);
+/* Stage 1.  frames: uint8 (F, H, W, 3) RGB packed (layout 2) or (F, H, W) (layout 0).  libjpeg's 16-bit fixed-point RGB ->
+ * YCbCr, the h2v2 downsample (2x2 sum + 1, 2, 1, 2, ... along the columns, >> 2), edges replicated as libjpeg does: columns
+ * and a cut row pair at full resolution, the chroma rows below ceil(H / 2) from the last downsampled row.               */
+int vdx_mjpeg_enc_color(const void* frames, int F, int W, int H, int layout, void* workspace, vdx_stream_t stream);
+/* Stage 2.  quant: uint16 [2][64] (luma, chroma; natural order, 1..255).  - 128, the 8x8 slow-integer forward DCT (13-bit
+ * constants, 2 pass-1 bits, rows then columns), sign(v) (|v| + (8q >> 1)) / 8q with an exact quotient; luma blocks wholly
+ * outside ceil(extent / 8) blocks are libjpeg's dummy blocks (AC zero, DC of the block before them in the MCU).          */
+int vdx_mjpeg_enc_fdct(const void* quant_u16, int F, int W, int H, int layout, void* workspace, vdx_stream_t stream);
+/* Stage 3.  tables: uint32 [2][272], per table id 16 DC words (by size) and 256 AC words (by run << 4 | size) of
+ * length << 16 | code.  restart_interval: MCUs per restart interval, 0 for none.  Counts the bits of every block, scans them
+ * per interval, emits them (intervals padded to a byte with 1-bits), counts the bytes after FF -> FF 00 stuffing and scans
+ * those.  lengths: int32 [F] (device), the bytes of every frame's file: header_bytes + entropy data + RSTn markers + EOI. */
+int vdx_mjpeg_enc_entropy(const void* tables, int F, int W, int H, int layout, int restart_interval, int header_bytes,
+                          void* workspace, int32_t* lengths, vdx_stream_t stream);
+/* Stage 4.  header: the header_bytes bytes every frame starts with (device).  out: the frames' files back to back, frame f
+ * at the sum of lengths[0 .. f); out_bytes: the size of `out`, past which nothing is stored.                             */
+int vdx_mjpeg_enc_pack(const void* header, int header_bytes, int F, int W, int H, int layout, int restart_interval,
+                       const void* workspace, const int32_t* lengths, void* out, size_t out_bytes, vdx_stream_t stream);
 
 #ifdef __cplusplus
 }

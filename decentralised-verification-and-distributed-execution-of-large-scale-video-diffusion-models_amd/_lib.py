@@ -126,7 +126,7 @@ SIGNATURES = {
     "vdx_flow_grey_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
     "vdx_flow_corr1d_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "vdx_flow_resize_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
-    "vdx_flow_polyexp_f32": (_i, [_vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp]),
+    "vdx_flow_polyexp_f32": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp]),
     "vdx_flow_update_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vdx_flow_abs_sum_f32": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

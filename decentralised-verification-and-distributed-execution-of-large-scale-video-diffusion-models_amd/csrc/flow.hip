@@ -2,14 +2,16 @@
 // on it: MD-VQS temporal consistency (InferNet/template/validator/scoring.py:311-339) and the result row's `flow_err`
 // (Distribution/strategies/fsdp_chunked_coherent.py:236-246).  The algorithm is vdx/compat/cv2_shim.py's
 // `calcOpticalFlowFarneback` (pyr_scale 0.5, winsize 15, poly_n 5, poly_sigma 1.2, flags 0; levels and iterations free) stage
-// by stage; vdx/flow.py drives the launches.  All arithmetic is fp32, every sum runs in a fixed order and no floating-point
+// by stage; vdx/flow.py drives the launches.  Every plane in memory is fp32.  grey, corr1d, resize, abs_sum and remap compute in
+// fp32 (remap's sums in integers); polyexp and update compute in fp64 between their fp32 loads and stores, because the 2 x 2
+// systems of a straight edge on a flat background are nearly singular.  Every sum runs in a fixed order and no floating-point
 // atomic is used: the same bits on every run, and a pair's flow does not depend on how many pairs the batch holds.
 //
 //   grey         uint8 RGB -> fp32 grey, OpenCV's 14-bit weights
 //   corr1d       1-D correlation along one axis, mirror (reflect-101) border: the pyramid's Gaussian blur, taps from the host
 //   resize       bilinear, half-pixel centres, clamped (`_resize_linear`): pyramid levels (1 channel), flow upsampling (2, x2)
-//   polyexp      per frame and level: six separable 11-tap correlations -> inv(G) rows -> bx, by, axx, ayy, axy
-//   update       one displacement iteration for every pair in one launch; the five window products live in LDS only
+//   polyexp      per frame and level: six separable 11-tap correlations -> inv(G) rows -> bx, by, axx, ayy, axy (fp64 inside)
+//   update       one displacement iteration for every pair in one launch; the five window products live in LDS only (fp64)
 //   abs_sum      per pair sum |flow| (TC), two fixed-order stages
 //   remap        warp prev by the flow (bilinear, constant-0 border, round half to even), sum |warp - next| as integers
 #include "vdx_common.h"
@@ -140,12 +142,14 @@ extern "C" int vdx_flow_resize_f32(const float* in, int n_img, int Hi, int Wi, i
 // ---- polynomial expansion ---------------------------------------------------------------------------------------------
 // `_poly_exp`: with k0 = g, k1 = g x, k2 = g x^2 (x = -5..5) the moments m = (k0 k0, k0 k1, k1 k0, k0 k2, k2 k0, k1 k1) as
 // (row kernel) x (column kernel) correlations — columns first, then rows, mirror border — and r = inv(G) m; rows 1..5 of
-// inv(G) give bx, by, axx, ayy, axy.  One 16 x 64 tile per block: the image tile with its halo of 5 in LDS, the three
-// column passes in LDS (halo rows included: a mirrored row of a pass is the pass of the mirrored row), the row passes and
-// the 5 x 6 product in registers.  out: [n][5][H][W].
+// inv(G) give bx, by, axx, ayy, axy.  One 16 x 64 tile per block: the image tile with its halo of 5 in LDS (fp32, the input's
+// own values), the three column passes in LDS as doubles (halo rows included: a mirrored row of a pass is the pass of the
+// mirrored row), the row passes and the 5 x 6 product in double registers.  Every product and sum is fp64 with float64 tables:
+// along a straight edge the planes feed 2 x 2 systems whose determinant cancels to ~1e-7 of its terms, and fp32 sums here moved
+// such flows by a pixel.  Each result is rounded once to fp32.  out: [n][5][H][W].  LDS 47.6 KB: three workgroups per CU.
 struct flow_poly_tab {
-    float k[3][FLOW_POLY_TAPS];
-    float ig[5][6];
+    double k[3][FLOW_POLY_TAPS];
+    double ig[5][6];
 };
 #define POLY_TH 16
 #define POLY_TW 64
@@ -153,7 +157,7 @@ struct flow_poly_tab {
 #define POLY_IW (POLY_TW + 2 * FLOW_POLY_R)
 __global__ __launch_bounds__(256) void flow_polyexp_kernel(const float* in, int H, int W, flow_poly_tab tab, float* out) {
     __shared__ float img[POLY_IH][POLY_IW];
-    __shared__ float t[3][POLY_IH][POLY_TW];
+    __shared__ double t[3][POLY_IH][POLY_TW];
     const int x0 = blockIdx.x * POLY_TW, y0 = blockIdx.y * POLY_TH;
     const float* src = in + (size_t)blockIdx.z * H * W;
     for (int i = threadIdx.x; i < POLY_IH * POLY_IW; i += 256) {
@@ -163,10 +167,10 @@ __global__ __launch_bounds__(256) void flow_polyexp_kernel(const float* in, int 
     __syncthreads();
     for (int i = threadIdx.x; i < POLY_IH * POLY_TW; i += 256) {
         const int ly = i / POLY_TW, lx = i - ly * POLY_TW;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        double s0 = 0., s1 = 0., s2 = 0.;
 #pragma unroll
         for (int k = 0; k < FLOW_POLY_TAPS; ++k) {
-            const float v = img[ly][lx + k];
+            const double v = (double)img[ly][lx + k];
             s0 += tab.k[0][k] * v;
             s1 += tab.k[1][k] * v;
             s2 += tab.k[2][k] * v;
@@ -180,10 +184,10 @@ __global__ __launch_bounds__(256) void flow_polyexp_kernel(const float* in, int 
     for (int i = threadIdx.x; i < POLY_TH * POLY_TW; i += 256) {
         const int ly = i / POLY_TW, lx = i - ly * POLY_TW;
         const int y = y0 + ly, x = x0 + lx;
-        float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                  // 1, x, y, xx, yy, xy
+        double m[6] = {0., 0., 0., 0., 0., 0.};                       // 1, x, y, xx, yy, xy
 #pragma unroll
         for (int k = 0; k < FLOW_POLY_TAPS; ++k) {
-            const float a = t[0][ly + k][lx], b = t[1][ly + k][lx], c = t[2][ly + k][lx];
+            const double a = t[0][ly + k][lx], b = t[1][ly + k][lx], c = t[2][ly + k][lx];
             m[0] += tab.k[0][k] * a;
             m[2] += tab.k[1][k] * a;
             m[4] += tab.k[2][k] * a;
@@ -194,15 +198,15 @@ __global__ __launch_bounds__(256) void flow_polyexp_kernel(const float* in, int 
         if (y < H && x < W) {
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
-                float r = 0.f;
+                double r = 0.;
 #pragma unroll
                 for (int q = 0; q < 6; ++q) r += tab.ig[j][q] * m[q];
-                dst[(size_t)j * H * W + (size_t)y * W + x] = r;
+                dst[(size_t)j * H * W + (size_t)y * W + x] = (float)r;
             }
         }
     }
 }
-extern "C" int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, const float* taps_host, const float* inv_g_host,
+extern "C" int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, const double* taps_host, const double* inv_g_host,
                                     float* out, vdx_stream_t stream) {
     VDX_CHECK(img && out && taps_host && inv_g_host, "flow_polyexp: null pointer");
     VDX_CHECK(n_img > 0 && n_img <= 65535 && H > 0 && W > 0 && (long long)H * W * 5 < (1ll << 31), "flow_polyexp: n=%d H=%d W=%d", n_img,
@@ -217,86 +221,93 @@ extern "C" int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, c
 }
 
 // ---- one displacement update, all pairs ------------------------------------------------------------------------------------
-// `_update_flow` with the box window.  Pair p takes R0 = expansion of frame p*step, R1 = of frame p*step + 1.  Per 32 x 32
-// tile: the five products of every pixel of the tile and its halo of 7 (mirrored into the image) are formed from R0 at the
-// pixel and R1 sampled bilinearly at the pixel + its flow (coordinates clamped, `_sample`) and staged in LDS; the 15 x 15
-// box mean runs there as 15 rows then 15 columns, each divided by 15; the 2 x 2 solve writes the new flow.  The product
-// planes never reach memory.  LDS: 5 x 46 x 47 + 5 x 32 x 47 floats = 73 KB, two workgroups per CU.
-#define UPD_T 32
-#define UPD_S (UPD_T + 2 * FLOW_WIN_R)                // 46
-#define UPD_LD (UPD_S + 1)                            // odd row stride
-#define UPD_LDS_BYTES ((5 * UPD_S * UPD_LD + 5 * UPD_T * UPD_LD) * (int)sizeof(float))
-__device__ __forceinline__ float flow_bilerp(const float* p, int i00, int i01, int i10, int i11, float fx, float fy) {
-    return (p[i00] * (1.f - fx) + p[i01] * fx) * (1.f - fy) + (p[i10] * (1.f - fx) + p[i11] * fx) * fy;
+// `_update_flow` with the box window.  Pair p takes R0 = expansion of frame p*step, R1 = of frame p*step + 1.  Per
+// UPD_TH x 32 tile: the five products of every pixel of the tile and its halo of 7 (mirrored into the image) are formed from
+// R0 at the pixel and R1 sampled bilinearly at the pixel + its flow (coordinates clamped, `_sample`) and staged in LDS; the
+// 15 x 15 box mean runs there as 15 rows then 15 columns, each divided by 15; the 2 x 2 solve writes the new flow.  The product
+// planes never reach memory.  R and the flows are fp32 in memory; everything between the loads and the final store is fp64
+// (samples, products, both box passes, determinant, solve): det = g0 g2 - g1^2 + 1e-3 cancels to nothing in fp32 where the
+// window sees one straight edge.  LDS: (5 x 46 x 47 + 5 x 32 x 47) doubles = 143 KB, so one workgroup per CU, of 1024 threads.
+// Measured on an MI355X, temporal consistency of 24 frames of 576 x 1024 (fp32 kernels: 3.35 ms): this shape 5.40 ms; the same tile
+// with 256 threads 12.3 ms; a 16 x 32 tile (84 KB, still one workgroup per CU) 9.2 ms with 512 threads, 13.4 ms with 256.
+#define UPD_TH 32
+#define UPD_TW 32
+#define UPD_NT 1024                                   // threads: 16 waves hide the gather's latency in the one resident workgroup
+#define UPD_SH (UPD_TH + 2 * FLOW_WIN_R)
+#define UPD_SW (UPD_TW + 2 * FLOW_WIN_R)              // 46
+#define UPD_LD (UPD_SW + 1)                           // odd row stride
+#define UPD_LDS_BYTES ((5 * UPD_SH * UPD_LD + 5 * UPD_TH * UPD_LD) * (int)sizeof(double))
+__device__ __forceinline__ double flow_bilerp(const float* p, int i00, int i01, int i10, int i11, double fx, double fy) {
+    return ((double)p[i00] * (1. - fx) + (double)p[i01] * fx) * (1. - fy) + ((double)p[i10] * (1. - fx) + (double)p[i11] * fx) * fy;
 }
-__global__ __launch_bounds__(256) void flow_update_kernel(const float* R, const float* fin, float* fout, int step, int H, int W) {
-    extern __shared__ float lds[];
-    float* comp = lds;                                // [5][UPD_S][UPD_LD]
-    float* vs = lds + 5 * UPD_S * UPD_LD;             // [5][UPD_T][UPD_LD]
-    const int p = blockIdx.z, x0 = blockIdx.x * UPD_T, y0 = blockIdx.y * UPD_T;
+__global__ __launch_bounds__(UPD_NT) void flow_update_kernel(const float* R, const float* fin, float* fout, int step, int H, int W) {
+    extern __shared__ double lds[];
+    double* comp = lds;                               // [5][UPD_SH][UPD_LD]
+    double* vs = lds + 5 * UPD_SH * UPD_LD;           // [5][UPD_TH][UPD_LD]
+    const int p = blockIdx.z, x0 = blockIdx.x * UPD_TW, y0 = blockIdx.y * UPD_TH;
     const size_t hw = (size_t)H * W;
     const float* R0 = R + (size_t)p * step * 5 * hw;
     const float* R1 = R0 + 5 * hw;
     const float* f0 = fin + (size_t)p * hw * 2;
-    for (int i = threadIdx.x; i < UPD_S * UPD_S; i += 256) {
-        const int ly = i / UPD_S, lx = i - ly * UPD_S;
+    for (int i = threadIdx.x; i < UPD_SH * UPD_SW; i += UPD_NT) {
+        const int ly = i / UPD_SW, lx = i - ly * UPD_SW;
         const int gy = flow_mirror(y0 + ly - FLOW_WIN_R, H), gx = flow_mirror(x0 + lx - FLOW_WIN_R, W);
         const int o = gy * W + gx;
-        const float dx = f0[2 * (size_t)o], dy = f0[2 * (size_t)o + 1];
-        const float sx = fminf(fmaxf((float)gx + dx, 0.f), (float)(W - 1));
-        const float sy = fminf(fmaxf((float)gy + dy, 0.f), (float)(H - 1));
-        const float flx = floorf(sx), fly = floorf(sy);
-        const int ix = (int)flx, iy = (int)fly;       // a NaN flow clamps to 0 above (fmaxf), so both are in range
+        const double dx = (double)f0[2 * (size_t)o], dy = (double)f0[2 * (size_t)o + 1];
+        const double sx = fmin(fmax((double)gx + dx, 0.), (double)(W - 1));
+        const double sy = fmin(fmax((double)gy + dy, 0.), (double)(H - 1));
+        const double flx = floor(sx), fly = floor(sy);
+        const int ix = (int)flx, iy = (int)fly;       // a NaN flow clamps to 0 above (fmax), so both are in range
         const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);
-        const float fx = sx - flx, fy = sy - fly;
+        const double fx = sx - flx, fy = sy - fly;
         const int i00 = iy * W + ix, i01 = iy * W + ix1, i10 = iy1 * W + ix, i11 = iy1 * W + ix1;
-        const float bx1 = flow_bilerp(R1, i00, i01, i10, i11, fx, fy);
-        const float by1 = flow_bilerp(R1 + hw, i00, i01, i10, i11, fx, fy);
-        const float axx1 = flow_bilerp(R1 + 2 * hw, i00, i01, i10, i11, fx, fy);
-        const float ayy1 = flow_bilerp(R1 + 3 * hw, i00, i01, i10, i11, fx, fy);
-        const float axy1 = flow_bilerp(R1 + 4 * hw, i00, i01, i10, i11, fx, fy);
-        const float bx0 = R0[o], by0 = R0[hw + o], axx0 = R0[2 * hw + o], ayy0 = R0[3 * hw + o], axy0 = R0[4 * hw + o];
-        const float a11 = 0.5f * (axx0 + axx1), a22 = 0.5f * (ayy0 + ayy1), a12 = 0.25f * (axy0 + axy1);
-        const float dbx = -0.5f * (bx1 - bx0) + a11 * dx + a12 * dy;
-        const float dby = -0.5f * (by1 - by0) + a12 * dx + a22 * dy;
+        const double bx1 = flow_bilerp(R1, i00, i01, i10, i11, fx, fy);
+        const double by1 = flow_bilerp(R1 + hw, i00, i01, i10, i11, fx, fy);
+        const double axx1 = flow_bilerp(R1 + 2 * hw, i00, i01, i10, i11, fx, fy);
+        const double ayy1 = flow_bilerp(R1 + 3 * hw, i00, i01, i10, i11, fx, fy);
+        const double axy1 = flow_bilerp(R1 + 4 * hw, i00, i01, i10, i11, fx, fy);
+        const double bx0 = R0[o], by0 = R0[hw + o], axx0 = R0[2 * hw + o], ayy0 = R0[3 * hw + o], axy0 = R0[4 * hw + o];
+        const double a11 = 0.5 * (axx0 + axx1), a22 = 0.5 * (ayy0 + ayy1), a12 = 0.25 * (axy0 + axy1);
+        const double dbx = -0.5 * (bx1 - bx0) + a11 * dx + a12 * dy;
+        const double dby = -0.5 * (by1 - by0) + a12 * dx + a22 * dy;
         const int l = ly * UPD_LD + lx;
         comp[l] = a11 * a11 + a12 * a12;
-        comp[UPD_S * UPD_LD + l] = a11 * a12 + a12 * a22;
-        comp[2 * UPD_S * UPD_LD + l] = a12 * a12 + a22 * a22;
-        comp[3 * UPD_S * UPD_LD + l] = a11 * dbx + a12 * dby;
-        comp[4 * UPD_S * UPD_LD + l] = a12 * dbx + a22 * dby;
+        comp[UPD_SH * UPD_LD + l] = a11 * a12 + a12 * a22;
+        comp[2 * UPD_SH * UPD_LD + l] = a12 * a12 + a22 * a22;
+        comp[3 * UPD_SH * UPD_LD + l] = a11 * dbx + a12 * dby;
+        comp[4 * UPD_SH * UPD_LD + l] = a12 * dbx + a22 * dby;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < UPD_T * UPD_S; i += 256) {             // 15 rows, top to bottom
-        const int r = i / UPD_S, c = i - r * UPD_S;
+    for (int i = threadIdx.x; i < UPD_TH * UPD_SW; i += UPD_NT) {        // 15 rows, top to bottom
+        const int r = i / UPD_SW, c = i - r * UPD_SW;
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
-            const float* col = comp + q * UPD_S * UPD_LD + r * UPD_LD + c;
-            float s = 0.f;
+            const double* col = comp + q * UPD_SH * UPD_LD + r * UPD_LD + c;
+            double s = 0.;
 #pragma unroll
             for (int k = 0; k < FLOW_WIN; ++k) s += col[k * UPD_LD];
-            vs[q * UPD_T * UPD_LD + r * UPD_LD + c] = s / (float)FLOW_WIN;
+            vs[q * UPD_TH * UPD_LD + r * UPD_LD + c] = s / (double)FLOW_WIN;
         }
     }
     __syncthreads();
     float* out = fout + (size_t)p * hw * 2;
-    for (int i = threadIdx.x; i < UPD_T * UPD_T; i += 256) {             // 15 columns, left to right, and the solve
-        const int r = i / UPD_T, c = i - r * UPD_T;
+    for (int i = threadIdx.x; i < UPD_TH * UPD_TW; i += UPD_NT) {        // 15 columns, left to right, and the solve
+        const int r = i / UPD_TW, c = i - r * UPD_TW;
         const int y = y0 + r, x = x0 + c;
-        float g[5];
+        double g[5];
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
-            const float* row = vs + q * UPD_T * UPD_LD + r * UPD_LD + c;
-            float s = 0.f;
+            const double* row = vs + q * UPD_TH * UPD_LD + r * UPD_LD + c;
+            double s = 0.;
 #pragma unroll
             for (int k = 0; k < FLOW_WIN; ++k) s += row[k];
-            g[q] = s / (float)FLOW_WIN;
+            g[q] = s / (double)FLOW_WIN;
         }
         if (y < H && x < W) {
-            const float det = g[0] * g[2] - g[1] * g[1] + 1e-3f;
+            const double det = g[0] * g[2] - g[1] * g[1] + 1e-3;
             const size_t o = ((size_t)y * W + x) * 2;
-            out[o] = (g[2] * g[3] - g[1] * g[4]) / det;
-            out[o + 1] = (g[0] * g[4] - g[1] * g[3]) / det;
+            out[o] = (float)((g[2] * g[3] - g[1] * g[4]) / det);
+            out[o + 1] = (float)((g[0] * g[4] - g[1] * g[3]) / det);
         }
     }
 }
@@ -307,9 +318,9 @@ extern "C" int vdx_flow_update_f32(const float* R, const float* flow_in, float* 
     VDX_CHECK(H >= 2 && W >= 2 && (long long)H * W * 5 < (1ll << 31), "flow_update: H=%d W=%d", H, W);
     static const hipError_t reserved = vdx_reserve_lds(UPD_LDS_BYTES, flow_update_kernel);
     VDX_CHECK(reserved == hipSuccess, "flow_update: cannot reserve %d bytes of LDS: %s", UPD_LDS_BYTES, hipGetErrorString(reserved));
-    const dim3 grid((W + UPD_T - 1) / UPD_T, (H + UPD_T - 1) / UPD_T, P);
+    const dim3 grid((W + UPD_TW - 1) / UPD_TW, (H + UPD_TH - 1) / UPD_TH, P);
     VDX_CHECK(grid.y <= 65535, "flow_update: H=%d too tall", H);
-    hipLaunchKernelGGL(flow_update_kernel, grid, dim3(256), UPD_LDS_BYTES, (hipStream_t)stream, R, flow_in, flow_out, step, H, W);
+    hipLaunchKernelGGL(flow_update_kernel, grid, dim3(UPD_NT), UPD_LDS_BYTES, (hipStream_t)stream, R, flow_in, flow_out, step, H, W);
     return vdx_launch_status("vdx_flow_update_f32");
 }
 

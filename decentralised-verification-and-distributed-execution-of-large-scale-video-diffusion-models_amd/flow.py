@@ -4,8 +4,9 @@ on it:
     InferNet/template/validator/scoring.py:311-339             MD-VQS temporal consistency: mean over pairs of mean |flow|
     Distribution/strategies/fsdp_chunked_coherent.py:236-246   flow_err: mean |remap(prev, flow) - next| at chunk boundaries
 
-The algorithm is `vdx.compat.cv2_shim.calcOpticalFlowFarneback` (cv2_shim.py:99-182) stage by stage, in fp32 on the device
-(csrc/flow.hip): grey image, Gaussian pyramid, polynomial expansion, `iterations` displacement updates per level with a
+The algorithm is `vdx.compat.cv2_shim.calcOpticalFlowFarneback` (cv2_shim.py:99-182) stage by stage on the device (csrc/flow.hip;
+planes in memory are fp32, the arithmetic inside the polynomial expansion and the displacement update is fp64, because the
+2 x 2 systems of straight edges on flat backgrounds are nearly singular; the rest is fp32): grey image, Gaussian pyramid, polynomial expansion, `iterations` displacement updates per level with a
 15 x 15 box window, bilinear upsampling between levels.  What is pinned: this path against the project's own shim
 (tests/test_flow_gpu.py, profiles/flow_parity.txt).  What is not: the shim against OpenCV (no `cv2` was available where it
 was written), so the numbers' agreement with the reference's own remains unpinned as before.

@@ -1113,16 +1113,16 @@ def flow_resize(x, height: int, width: int, mul: float = 1.0):
 
 def flow_polyexp(img, taps, inv_g):
     """`_poly_exp` (poly_n 5) of fp32 images (n, H, W) -> (n, 5, H, W) = bx, by, axx, ayy, axy.  `taps` (3, 11) and `inv_g` (5, 6):
-    host arrays (`vdx.flow.poly_tables`), passed as kernel arguments (vdx_flow_polyexp_f32)."""
+    host arrays (`vdx.flow.poly_tables`), passed as float64 kernel arguments; fp64 arithmetic, fp32 planes (vdx_flow_polyexp_f32)."""
     import numpy as np
     if img.dim() != 3:
         raise VdxError(f"flow_polyexp: expected images (n, H, W), got {tuple(img.shape)}")
     n, H, W = img.shape
-    k, g = np.ascontiguousarray(taps, np.float32), np.ascontiguousarray(inv_g, np.float32)
+    k, g = np.ascontiguousarray(taps, np.float64), np.ascontiguousarray(inv_g, np.float64)
     if k.shape != (3, 11) or g.shape != (5, 6):
         raise VdxError(f"flow_polyexp: taps {k.shape} / inv_g {g.shape}: expected (3, 11) and (5, 6)")
     out = torch.empty((n, 5, H, W), dtype=torch.float32, device=img.device)
-    fp = C.POINTER(C.c_float)
+    fp = C.POINTER(C.c_double)
     _launch("vdx_flow_polyexp_f32", _f32(img, (n, H, W), "flow_polyexp", "img"), n, H, W, k.ctypes.data_as(fp), g.ctypes.data_as(fp),
             out.data_ptr())
     return out
@@ -1130,7 +1130,7 @@ def flow_polyexp(img, taps, inv_g):
 
 def flow_update(R, flow, step: int = 1, out=None):
     """One `_update_flow` iteration for every pair: R (n, 5, H, W) expansions, flow (P, H, W, 2); pair p uses images p*step and
-    p*step + 1 -> the new flow (P, H, W, 2) (`out`, which may not be `flow`).  vdx_flow_update_f32."""
+    p*step + 1 -> the new flow (P, H, W, 2) (`out`, which may not be `flow`); fp64 arithmetic on fp32 planes.  vdx_flow_update_f32."""
     if R.dim() != 4 or R.shape[1] != 5 or flow.dim() != 4 or flow.shape[3] != 2:
         raise VdxError(f"flow_update: expected R (n, 5, H, W) and flow (P, H, W, 2), got {tuple(R.shape)}, {tuple(flow.shape)}")
     n, _, H, W = R.shape

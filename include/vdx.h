@@ -511,7 +511,8 @@ int vdx_frame_stats_u8(const void* frames, size_t frame_pitch, int row_pitch, in
  *   Distribution/strategies/fsdp_chunked_coherent.py:236-246  flow_err = mean |remap(prev, flow) - next| at chunk boundaries
  * (csrc/flow.hip; vdx/flow.py).  The algorithm is vdx/compat/cv2_shim.py's calcOpticalFlowFarneback stage by stage
  * (cv2_shim.py:99-182; parameters 0.5, levels, 15, iterations, 5, 1.2, 0), which stands in for cv2's where OpenCV is not
- * installed: the GPU path is pinned against that shim, the shim against OpenCV is not.  fp32 throughout, fixed summation
+ * installed: the GPU path is pinned against that shim, the shim against OpenCV is not.  fp32 planes in memory; fp64 arithmetic
+ * inside polyexp and update (nearly singular 2 x 2 systems along straight edges), fp32 elsewhere; fixed summation
  * orders, no floating-point atomics: the same bits on every run and for every batch size.  Images are fp32 [n][H][W],
  * flows fp32 [P][H][W][2] (x, y), both packed.
  * ---------------------------------------------------------------------------------------- */
@@ -530,13 +531,14 @@ int vdx_flow_corr1d_f32(const float* in, float* out, int n_img, int H, int W, co
 int vdx_flow_resize_f32(const float* in, int n_img, int Hi, int Wi, int C, float* out, int Ho, int Wo, float mul,
                         vdx_stream_t stream);
 /* _poly_exp (cv2_shim.py:99-118) with poly_n = 5 of n_img images -> out [n][5][H][W] = bx, by, axx, ayy, axy.  taps_host:
- * fp32 [3][11] HOST memory, g, g x, g x^2; inv_g_host: fp32 [5][6] HOST memory, rows 1..5 of inv(G) (both from
- * vdx/flow.py poly_tables, evaluated in float64); they travel as kernel arguments.                                     */
-int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, const float* taps_host, const float* inv_g_host, float* out,
+ * fp64 [3][11] HOST memory, g, g x, g x^2; inv_g_host: fp64 [5][6] HOST memory, rows 1..5 of inv(G) (both from
+ * vdx/flow.py poly_tables); they travel as kernel arguments.  Sums and products are fp64, each result rounded once to fp32. */
+int vdx_flow_polyexp_f32(const float* img, int n_img, int H, int W, const double* taps_host, const double* inv_g_host, float* out,
                          vdx_stream_t stream);
 /* _update_flow (cv2_shim.py:132-153), box window of 15, for P pairs in one launch: pair p reads the expansions of images
  * p*step and p*step + 1 of R ([..][5][H][W]; step 1: consecutive frames, each expansion serving two pairs; step 2: disjoint
- * pairs) and flow_in[p], and writes flow_out[p] (may not alias flow_in).  The five window products stay in LDS.           */
+ * pairs) and flow_in[p], and writes flow_out[p] (may not alias flow_in).  The five window products stay in LDS.
+ * Samples, products, box sums, determinant and solve are fp64; the flow is rounded once to fp32.                          */
 int vdx_flow_update_f32(const float* R, const float* flow_in, float* flow_out, int P, int step, int H, int W,
                         vdx_stream_t stream);
 /* scoring.py:329-331: out[p] = sum of |flow[p]| over its n = H*W*2 values (the host divides).  workspace: fp32 [P][64].

@@ -9,11 +9,28 @@ Rows (tests/flow_inputs.py), the smallest inputs at which each part can go wrong
     (64, 200)   (3.0, 3.0)     wide aspect, many tiles in x
     (576, 1024) (1.5, -0.75)   the real extent, one pair
 
-Bounds.  FLOW_MAX_ABS / FLOW_REL_L2 are 4x the worst figures measured on an MI355X over all six rows
-(profiles/flow_parity.txt, tools/flow_parity.py; 4x is the project's head-room for fp32 summation-order differences
-between boxes; measured there: max-abs 8.9e-7 .. 1.7e-5 px, rel-L2 1.9e-7 .. 1.0e-6, remap bytes differing from the shim's at
+Content rows (tests/flow_inputs.py `content_clip`), all (72, 104) with integer pixel values, frame i moved by i x the shift:
+    diagonal    edge x + y < 90 + 3 i, grey 245 / 10: every window sees one straight edge, the 2 x 2 system is nearly singular
+    square      white 24 x 32 square on black, +3 px: flat inside and outside, edges in both directions, corners
+    noise_roll  uniform noise rolled by 2 px: texture at the pixel scale, above the pyramid's pass band at level 0
+    noise_pair  noise against unrelated noise: no motion to find, large flows that clamp at every border
+    mixed       left half the textured clip, right half the diagonal edge: well and badly conditioned windows side by side
+    step        vertical step, +2 px        \
+    bars        8-px bars, +1 px             | one-dimensional or flat: g12 = g22 = 0, the regularised solve gives a flow of ~0
+    ramp        2 grey levels per px, +2 px  | (the shim's is asserted < 1e-6 px); max-abs only, rel-L2 is undefined
+    constant    128 everywhere              /
+
+Bounds.  FLOW_MAX_ABS / FLOW_REL_L2 are 4x the worst figures measured on an MI355X over all six rows with the all-fp32
+kernels (tools/flow_parity.py; 4x is the project's head-room for fp32 summation-order differences
+between boxes; measured then: max-abs 8.9e-7 .. 1.7e-5 px, rel-L2 1.9e-7 .. 1.0e-6, remap bytes differing from the shim's at
 most 5.3e-5 of a frame, each by one grey level), and FLOW_MAX_ABS may not exceed 1e-3 px: a wrong tap, border mode, level size or off-by-one moves these
-fields by 1e-2 px or more, fp32 rounding sits near 1e-5 px."""
+fields by 1e-2 px or more, fp32 rounding sits near 1e-5 px.  The content rows have their own pair, STRUCT_MAX_ABS / STRUCT_REL_L2,
+4x the worst figures measured over those rows (same file, same tool), and STRUCT_MAX_ABS may not exceed 2e-3 px, a fifth of
+that 1e-2 px (profiles/flow_parity.txt holds the current figures of every row).  FLOW_MAX_ABS / FLOW_REL_L2 are kept as they were; since polyexp and update compute in fp64
+the six rows measure max-abs 1.2e-7 .. 4.8e-7 px and rel-L2 9.2e-9 .. 2.1e-8.  With the all-fp32 kernels the content rows measured,
+on the same device: diagonal max-abs 0.97 px (23 % of the values off by more than 1e-3 px, TC 5.0 % off), mixed 0.94 px, bars
+8.7e-3 px, step 3.1e-3 px, square 2.4e-4 px, noise_pair 2.1e-4 px: det = g0 g2 - g1^2 + 1e-3 cancels in fp32 where a window sees one
+straight edge."""
 import json
 
 import numpy as np
@@ -32,6 +49,10 @@ FLOW_MAX_ABS = 4 * 1.729e-5  # px; worst row measured: (72, 104) (6.0, -3.0)
 FLOW_REL_L2 = 4 * 1.005e-6   # worst row measured: (576, 1024)
 assert FLOW_MAX_ABS <= 1e-3
 REMAP_SHARE = 1e-3           # share of warped bytes that may differ from cv2_shim.remap (by one grey level at most)
+
+STRUCT_MAX_ABS = 4 * 4.005e-4  # px; worst content row measured: mixed
+STRUCT_REL_L2 = 4 * 1.333e-5   # worst content row measured: diagonal
+assert STRUCT_MAX_ABS <= 2e-3
 
 ROWS = FI.SMALL_ROWS + [FI.LARGE_ROW]
 IDS = [f"{h}x{w}_{dx}_{dy}" for (h, w), (dx, dy) in ROWS]
@@ -52,6 +73,46 @@ def test_flow_matches_the_shim(gpu, hw, sh):
     print(f"flow {hw} {sh}: max-abs {e_abs:.3e} px (bound {FLOW_MAX_ABS:.1e}), rel-L2 {e_rel:.3e} (bound {FLOW_REL_L2:.1e})")
     assert np.isfinite(got).all()
     assert e_abs <= FLOW_MAX_ABS and e_rel <= FLOW_REL_L2
+
+
+@pytest.mark.parametrize("name", FI.CONTENT_ROWS + FI.ZERO_ROWS)
+def test_content_flow_matches_the_shim(gpu, name):
+    """Edges, flat areas and noise: every pixel of the flow against the shim's, and TC against mean |shim flow|."""
+    fr = FI.content_clip(name)
+    got = flow.farneback_flows(torch.from_numpy(fr.copy()).to(gpu))[0].cpu().numpy().astype(np.float64)
+    want = FI.content_shim_flow(name)[0].astype(np.float64)
+    assert got.shape == want.shape == FI.CONTENT_HW + (2,)
+    e_abs = float(np.abs(got - want).max())
+    if name in FI.ZERO_ROWS:
+        e_rel = 0.0
+        assert float(np.abs(want).max()) < 1e-6                                    # the row is still of the ~0 kind
+    else:
+        e_rel = float(np.linalg.norm(got - want) / np.linalg.norm(want))
+        assert float(np.abs(want).max()) > 1.0                                     # ... and this one still moves
+    print(f"flow {name}: max-abs {e_abs:.3e} px (bound {STRUCT_MAX_ABS:.1e}), rel-L2 {e_rel:.3e} (bound {STRUCT_REL_L2:.1e})")
+    assert np.isfinite(got).all()
+    assert e_abs <= STRUCT_MAX_ABS and e_rel <= STRUCT_REL_L2
+    tc, tc_shim = flow.temporal_consistency(fr, device=gpu), float(np.mean(np.abs(want)))
+    # as in test_temporal_consistency_matches_the_cpu_path: every |flow| within STRUCT_MAX_ABS, so is their mean; the fixed
+    # order fp32 sum adds at most ~140 roundings on a value's path
+    margin = STRUCT_MAX_ABS + 140 * 2.0 ** -24 * tc_shim
+    print(f"TC {name}: gpu {tc!r} shim {tc_shim!r}: difference {abs(tc - tc_shim):.3e} (margin {margin:.3e})")
+    assert np.isfinite(tc) and abs(tc - tc_shim) <= margin
+
+
+@pytest.mark.parametrize("name", FI.CONTENT_ROWS + FI.ZERO_ROWS)
+def test_content_flow_warp_error_matches_the_host_metric(gpu, name):
+    """Four frames, one boundary: frame 1 warped by the flow 1 -> 2 against frame 2, on the GPU and through the shim."""
+    fr = FI.content_clip(name, 4)
+    ranges = [(0, 2), (2, 4)]
+    want = metrics.flow_warp_error(list(fr), ranges)
+    got = flow.flow_warp_error(torch.from_numpy(fr.copy()).to(gpu), ranges)
+    # the margin of test_flow_warp_error_matches_the_host_metric with this row's flow bound and this frame's largest step
+    f1 = fr[1].astype(np.int32)
+    G = max(int(np.abs(np.diff(f1, axis=0)).max()), int(np.abs(np.diff(f1, axis=1)).max()))
+    margin = REMAP_SHARE * 1.0 + 4 * G * STRUCT_MAX_ABS
+    print(f"flow_err {name}: gpu {got!r} host {want!r}: difference {abs(got - want):.3e} (margin {margin:.3e}, G = {G})")
+    assert np.isfinite(got) and abs(got - want) <= margin
 
 
 @pytest.mark.parametrize("hw,sh", FI.SMALL_ROWS, ids=IDS[:-1])

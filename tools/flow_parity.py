@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Measure the GPU Farneback flow (vdx/flow.py) against the float64 shim (vdx.compat.cv2_shim) on the inputs of
 tests/test_flow_gpu.py (tests/flow_inputs.py): per row the max-abs and rel-L2 difference of the flow, the interior median,
-and for the remap kernel the share of bytes that differ from `cv2_shim.remap` fed the GPU's own flow.  The test bounds are
-4x the worst flow figures this prints (tests/test_flow_gpu.py).  Measured numbers only.
+and for the remap kernel the share of bytes that differ from `cv2_shim.remap` fed the GPU's own flow; then the content rows
+(edges, flat areas, noise: `flow_inputs.content_clip`) with their own worst figures.  The test bounds are 4x the worst flow
+figures this prints, per group of rows (tests/test_flow_gpu.py).  Measured numbers only.
 
     python tools/flow_parity.py [--out profiles/flow_parity.txt] [--no-large]"""
 import argparse
@@ -47,6 +48,22 @@ def main():
         lines.append(f"{hw} {sh}: {e_abs:.3e} px, {e_rel:.3e}, median ({med[0]:.4f}, {med[1]:.4f}) [({smed[0]:.4f}, {smed[1]:.4f})]; "
                      f"remap {int((d > 0).sum())} of {d.size} bytes differ (share {float((d > 0).mean()):.2e}), largest difference {int(d.max())}")
     lines.append(f"worst flow max-abs {worst_abs:.3e} px, worst rel-L2 {worst_rel:.3e}; test bounds = 4x these")
+    lines.append("content rows (72, 104), integer pixel values: flow max-abs px, rel-L2 (n/a where the shim's flow is ~0), "
+                 "largest |shim flow| px, TC gpu / shim")
+    worst_abs = worst_rel = 0.0
+    for name in FI.CONTENT_ROWS + FI.ZERO_ROWS:
+        fr = FI.content_clip(name)
+        want = FI.content_shim_flow(name)[0].astype(np.float64)
+        got = flow.farneback_flows(torch.from_numpy(fr.copy()).to(dev))[0].cpu().numpy().astype(np.float64)
+        e_abs = float(np.abs(got - want).max())
+        worst_abs = max(worst_abs, e_abs)
+        if name in FI.CONTENT_ROWS:
+            e_rel = float(np.linalg.norm(got - want) / np.linalg.norm(want))
+            worst_rel = max(worst_rel, e_rel)
+        tc, tc_shim = flow.temporal_consistency(fr, device=dev), float(np.mean(np.abs(want)))
+        lines.append(f"{name}: {e_abs:.3e} px, {f'{e_rel:.3e}' if name in FI.CONTENT_ROWS else 'n/a'}, {float(np.abs(want).max()):.3e}, "
+                     f"TC {tc!r} / {tc_shim!r}")
+    lines.append(f"worst content max-abs {worst_abs:.3e} px, worst rel-L2 {worst_rel:.3e}; STRUCT bounds = 4x these, max-abs <= 2e-3 px")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:

@@ -106,6 +106,8 @@ SIGNATURES = {
     "vdx_cfg_input_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _vp]),
     "vdx_cfg_ddim_step_f16": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _sz, _vp]),
     "vdx_ddim_step_f16": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _sz, _vp]),
+    "vdx_cfg_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _sz, _vp]),
+    "vdx_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _sz, _vp]),
     "vdx_blend_accumulate_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vdx_blend_finalize_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "vdx_clip_preprocess_u8": (_i, [C.POINTER(ClipPreprocessArgs), _vp]),

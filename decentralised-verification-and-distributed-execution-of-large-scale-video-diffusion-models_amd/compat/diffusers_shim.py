@@ -80,6 +80,7 @@ class AutoencoderKL(_vae.AutoencoderKL):
 
 
 DDIMScheduler = _sched.DDIMScheduler
+DPMSolverMultistepScheduler = _sched.DPMSolverMultistepScheduler     # Zeroscope's recipe: .from_config(pipe.scheduler.config)
 
 
 class HashTokenizer:

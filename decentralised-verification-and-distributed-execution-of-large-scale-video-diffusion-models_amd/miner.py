@@ -30,7 +30,12 @@ def denoise_with_trace(unet, scheduler, z: torch.Tensor, encoder_hidden_states: 
     if z.dim() != 5 or z.shape[0] != 1 or z.dtype != torch.float16:
         raise VdxError(f"denoise_with_trace: z must be (1,C,T,h,w) fp16, got {tuple(z.shape)} {z.dtype}")
     scheduler.set_timesteps(num_steps, device=z.device)
+    if hasattr(scheduler, "reset"):         # a multistep scheduler starts every trace without history
+        scheduler.reset()
     timesteps: List[int] = list(scheduler._host_timesteps)
+    if timesteps and not 0 <= max(timesteps) < len(scheduler.alphas_cumprod):
+        raise ValueError(f"denoise_with_trace: timestep {max(timesteps)} of this {num_steps}-step schedule is outside the "
+                         f"{len(scheduler.alphas_cumprod)} training steps")
     alphas = [float(scheduler.alphas_cumprod[t]) for t in timesteps]                     # :534-544
     latents, noise_preds = [], []
     z = z.contiguous()

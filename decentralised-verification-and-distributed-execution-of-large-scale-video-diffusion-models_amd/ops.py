@@ -810,6 +810,47 @@ def ddim_step(eps, lat, coeffs, out=None):
     return out
 
 
+def _dpm_args(what, lat, x0_prev, x0_out, out, coeffs):
+    """Shared checks of the two DPM-Solver++ steps -> (x0_out, out, the six fp32 coefficients)."""
+    for name, t in (("x0_prev", x0_prev), ("x0_out", x0_out), ("out", out)):
+        if t is not None and (tuple(t.shape) != tuple(lat.shape) or not t.is_contiguous()):
+            raise VdxError(f"{what}: {name} must be contiguous and shaped like lat")
+    if x0_out is None:
+        x0_out = torch.empty_like(lat)
+    if out is None:
+        out = torch.empty_like(lat)
+    if x0_prev is not None and x0_out.data_ptr() == x0_prev.data_ptr():
+        raise VdxError(f"{what}: x0_out must not be x0_prev (the history ping-pongs two buffers)")
+    c = tuple(float(v) for v in coeffs)
+    if len(c) != 6:
+        raise VdxError(f"{what}: coeffs = (s0, 1/a0, st/s0, c_d0, c_d1, 1/r0)")
+    return x0_out, out, c
+
+
+def cfg_dpm_step(eps2, lat, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
+    """`u + gs*(c-u)` + one DPM-Solver++ step (vdx/scheduler.py `DPMSolverMultistepScheduler.step_cfg`) in one kernel ->
+    (lat', x0).  coeffs = (s0, 1/a0, st/s0, -at*(exp(-h)-1), half of that, 1/r0); `x0_prev=None`: the first-order form.
+    `out` may be `lat`; `x0_out` may not be `x0_prev`."""
+    if eps2.shape[0] != 2 or tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1:
+        raise VdxError("cfg_dpm_step: eps2 must be (2,...) matching lat (1,...)")
+    if not (eps2.is_contiguous() and lat.is_contiguous()):
+        raise VdxError("cfg_dpm_step: tensors must be contiguous")
+    x0_out, out, c = _dpm_args("cfg_dpm_step", lat, x0_prev, x0_out, out, coeffs)
+    _launch("vdx_cfg_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
+            _p(out, "out"), float(guidance), *c, lat.numel())
+    return out, x0_out
+
+
+def dpm_step(eps, lat, coeffs, x0_prev=None, x0_out=None, out=None):
+    """`scheduler.step(eps, t, lat)` of the DPM-Solver++ scheduler without the CFG combine -> (lat', x0)."""
+    if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
+        raise VdxError("dpm_step: eps and lat must be contiguous and of equal shape")
+    x0_out, out, c = _dpm_args("dpm_step", lat, x0_prev, x0_out, out, coeffs)
+    _launch("vdx_dpm_step_f16", _p(eps, "eps"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
+            _p(out, "out"), *c, lat.numel())
+    return out, x0_out
+
+
 def blend_accumulate(full, weight, chunk, w, s, e):
     _, Cc, T, H, W = full.shape
     if tuple(chunk.shape) != (1, Cc, e - s, H, W) or not (chunk.is_contiguous() and full.is_contiguous()):

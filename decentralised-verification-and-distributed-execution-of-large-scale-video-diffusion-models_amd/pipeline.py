@@ -64,6 +64,7 @@ class DiffuserConfig:
     strength: float = 0.6
     posterior: str = "sample"              # "sample" | "mode" of the encoder's diagonal Gaussian
     gpu_flow: bool = False                 # flow_err (and MD-VQS' TC) from the HIP Farneback kernels instead of the host path
+    scheduler: str = "ddim"                # "ddim" | "dpmpp_2m" (DPM-Solver++ 2M, vdx/scheduler.py): the sampler `run_job` uses
 
     @property
     def use_fsdp(self):
@@ -110,6 +111,20 @@ def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
     base = torch.randn(*shape, device=nd, dtype=dtype)
     base *= sigma
     return base.to(device)
+
+
+SCHEDULERS = ("ddim", "dpmpp_2m")
+
+
+def make_scheduler(name: str, base):
+    """The sampler `name` of `DiffuserConfig.scheduler` / `--scheduler`: "ddim" is `base` itself (the pipeline's scheduler,
+    untouched); "dpmpp_2m" is `DPMSolverMultistepScheduler.from_config(base.config)`, as Zeroscope's published recipe builds it."""
+    if name == "ddim":
+        return base
+    if name == "dpmpp_2m":
+        from .scheduler import DPMSolverMultistepScheduler
+        return base if isinstance(base, DPMSolverMultistepScheduler) else DPMSolverMultistepScheduler.from_config(base.config)
+    raise ValueError(f"unknown scheduler {name!r}: expected one of {SCHEDULERS}")
 
 
 def vid2vid_timesteps(scheduler, steps: int, strength: float) -> List[int]:
@@ -408,6 +423,9 @@ class DistributedVideoDiffuser:
         cfg, sched = self.cfg, self.scheduler
         emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0)
         lat = lat.contiguous()
+        reset = getattr(sched, "reset", None)
+        if reset is not None:       # a multistep scheduler must not carry the previous chunk's history into this one
+            reset()
         for t in (sched._host_timesteps if self.timesteps is None else self.timesteps):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb).sample
@@ -518,7 +536,9 @@ def build_arg_parser():
     decoded back from the written mp4 on the GPU (vdx/video.py: what a validator holding the file would score) instead of the
     frames in memory; the records then carry `"source": "file"`.  `--gpu_video_write` encodes the mp4's JPEG frames in HIP
     kernels (vdx/video.py `write_frames`, csrc/mjpeg_enc.hip) instead of in Pillow on the host: the same file byte for byte,
-    with or without `--video_restart_rows`."""
+    with or without `--video_restart_rows`.  `--scheduler dpmpp_2m` samples with DPM-Solver++ 2M (vdx/scheduler.py
+    `DPMSolverMultistepScheduler`, built from the pipeline scheduler's config) instead of DDIM; `--scheduler ddim`, the default,
+    is the run without the flag."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -556,6 +576,8 @@ def build_arg_parser():
                    help="video-to-video: refine this clip (.npy uint8 (T,H,W,3) or a directory of images) instead of starting from noise")
     p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
     p.add_argument("--posterior", choices=["sample", "mode"], default="sample", help="video-to-video: encoder posterior")
+    p.add_argument("--scheduler", choices=list(SCHEDULERS), default="ddim",
+                   help="sampler: ddim (the reference's, default) or dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality)")
     return p
 
 
@@ -564,7 +586,8 @@ def config_from_args(a) -> DiffuserConfig:
                           overlap=a.overlap, height=a.height, width=a.width, mode=a.mode, context_weight=a.context_weight,
                           device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
                           out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
-                          init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow)
+                          init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow,
+                          scheduler=a.scheduler)
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -680,7 +703,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     init_latents, encode_s = None, 0.0
     if cfg.init_video is not None:
         init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
-    d = DistributedVideoDiffuser(cfg, unet, pipe.scheduler, uncond, cond, init_latents=init_latents)
+    d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents)
     out, info = d(exchange=exchange)
     ranges = info["ranges"]
     if exchange == "allgather":
@@ -714,7 +737,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "net_gather_s": info["net_gather_s"], "net_reduce_s": reduce_s, "temp_instab": temp_instab, "flow_err": flow_err,
             "denoise_s": info["denoise_s"], "exchange": exchange, "rank": d.rank, "synthetic_weights": pipe.synthetic_weights,
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
-            "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s}
+            "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
+            "scheduler": cfg.scheduler}
 
 
 def main(argv=None) -> int:

@@ -7,6 +7,10 @@ the fused HIP kernel (`vdx_ddim_step_f16` / `vdx_cfg_ddim_step_f16`) — there i
 Config = Zeroscope `scheduler_config.json`: 1000 train steps,
 scaled-linear betas 0.00085..0.012, steps_offset 1, set_alpha_to_one False, epsilon, eta 0,
 leading spacing, no clipping.
+
+`DPMSolverMultistepScheduler` (DPM-Solver++ 2M, the sampler Zeroscope's published recipe swaps in) has the same call
+surface and is opt-in; DDIM stays the default everywhere.  Both share `_SchedulerBase`: the sync-free timestep lookup and
+`add_noise`.
 """
 from __future__ import annotations
 
@@ -18,10 +22,54 @@ import torch
 from . import ops
 
 
-class DDIMScheduler:
+class _SchedulerBase:
+    """What the schedulers share: the call-surface constants, the sync-free timestep lookup, `add_noise`, and a `reset()`
+    that single-step schedulers have nothing to do in."""
     init_noise_sigma = 1.0
     order = 1
+    timesteps = None
+    _host_timesteps = None
 
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def reset(self):
+        """Forget what earlier `step` calls left behind (multistep history, step index).  Nothing for DDIM."""
+
+    def _host_timestep(self, timestep) -> int:
+        """The step's timestep as a host integer, by VALUE (diffusers semantics) and — for the tensors the reference
+        hands in — without reading device memory.  The reference passes `step` the 0-d device tensors it iterates
+        over (`for t in scheduler.timesteps`, :132,142); `int(t)` on those is a device sync per step.  Such an element
+        is a view of `self.timesteps`' storage, so its index is its address: (data_ptr - base) / itemsize, checked
+        against the storage's extent.  Any other device tensor (a clone, arithmetic on a timestep, a foreign schedule)
+        is read with `int(t)` — one sync, never a guess.  Python numbers and host tensors are used as given."""
+        if torch.is_tensor(timestep) and timestep.is_cuda:
+            ts = self.timesteps
+            if ts is not None and ts.is_cuda and timestep.numel() == 1 and timestep.dtype == ts.dtype \
+                    and timestep.device == ts.device \
+                    and timestep.untyped_storage().data_ptr() == ts.untyped_storage().data_ptr():
+                off = timestep.data_ptr() - ts.data_ptr()
+                idx, rem = divmod(off, ts.element_size())
+                if rem == 0 and 0 <= idx < ts.numel():
+                    return self._host_timesteps[idx]
+            return int(timestep)
+        return int(timestep)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
+        then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers
+        does), then x_t = sqrt(a_t)*x0 + sqrt(1-a_t)*noise in the HIP kernel with fp16 rounding after each op.  Unpinned
+        boundary (diffusers is not installed: DESIGN §2)."""
+        t = self._host_timestep(timesteps) if torch.is_tensor(timesteps) else int(timesteps)
+        if not 0 <= t < len(self.alphas_cumprod):
+            raise ValueError(f"add_noise: timestep {t} is outside the {len(self.alphas_cumprod)} training steps")
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        sa = float(ac[t] ** 0.5)
+        s1 = float((1 - ac[t]) ** 0.5)
+        return ops.add_noise(original_samples.contiguous(), noise.contiguous(), sa, s1)
+
+
+class DDIMScheduler(_SchedulerBase):
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
                  beta_schedule="scaled_linear", steps_offset=1, set_alpha_to_one=False,
                  clip_sample=False, prediction_type="epsilon", timestep_spacing="leading"):
@@ -51,34 +99,12 @@ class DDIMScheduler:
         self._host_timesteps = [int(t) for t in ts]
         self.timesteps = torch.from_numpy(ts).to(device)
 
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
     def coefficients(self, t: int):
         """(sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev)) evaluated in fp32 like diffusers."""
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         return (float((1 - a_t) ** 0.5), float(a_t ** 0.5), float(a_prev ** 0.5), float((1 - a_prev) ** 0.5))
-
-    def _host_timestep(self, timestep) -> int:
-        """The step's timestep as a host integer, by VALUE (diffusers semantics) and — for the tensors the reference
-        hands in — without reading device memory.  The reference passes `step` the 0-d device tensors it iterates
-        over (`for t in scheduler.timesteps`, :132,142); `int(t)` on those is a device sync per step.  Such an element
-        is a view of `self.timesteps`' storage, so its index is its address: (data_ptr - base) / itemsize, checked
-        against the storage's extent.  Any other device tensor (a clone, arithmetic on a timestep, a foreign schedule)
-        is read with `int(t)` — one sync, never a guess.  Python numbers and host tensors are used as given."""
-        if torch.is_tensor(timestep) and timestep.is_cuda:
-            ts = self.timesteps
-            if ts is not None and ts.is_cuda and timestep.numel() == 1 and timestep.dtype == ts.dtype \
-                    and timestep.device == ts.device \
-                    and timestep.untyped_storage().data_ptr() == ts.untyped_storage().data_ptr():
-                off = timestep.data_ptr() - ts.data_ptr()
-                idx, rem = divmod(off, ts.element_size())
-                if rem == 0 and 0 <= idx < ts.numel():
-                    return self._host_timesteps[idx]
-            return int(timestep)
-        return int(timestep)
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, **_unused):
         if eta != 0.0:
@@ -89,17 +115,166 @@ class DDIMScheduler:
                              self.coefficients(self._host_timestep(timestep)))
         return SimpleNamespace(prev_sample=prev)
 
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
-        then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers
-        does), then x_t = sqrt(a_t)*x0 + sqrt(1-a_t)*noise in the HIP kernel with fp16 rounding after each op.  Unpinned
-        boundary (diffusers is not installed: DESIGN §2)."""
-        t = self._host_timestep(timesteps) if torch.is_tensor(timesteps) else int(timesteps)
-        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
-        sa = float(ac[t] ** 0.5)
-        s1 = float((1 - ac[t]) ** 0.5)
-        return ops.add_noise(original_samples.contiguous(), noise.contiguous(), sa, s1)
-
     def step_cfg(self, noise2, timestep, sample, guidance_scale: float):
         """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel."""
         return ops.cfg_ddim_step(noise2, sample, guidance_scale, self.coefficients(self._host_timestep(timestep)))
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """DPM-Solver++ 2M (Lu et al., 2022; diffusers `DPMSolverMultistepScheduler`, which Zeroscope's published recipe swaps in
+    with `from_config(pipe.scheduler.config)`), with `DDIMScheduler`'s call surface.  Opt-in: DDIM stays the default.
+
+    Implemented: algorithm_type "dpmsolver++", solver_order 2 (or 1), solver_type "midpoint", epsilon prediction, no
+    thresholding, lower_order_final, final_sigmas_type "zero", leading spacing, steps_offset 1, scaled-linear betas; anything
+    else raises NotImplementedError.  diffusers is not installed, so — exactly as for DDIM — the schedule and the expression
+    below are RESTATED and their parity with diffusers is unpinned; what is pinned, bit for bit, is the HIP kernel against
+    this expression (tests/test_dpm_gpu.py against tests/dpm_ref.py).
+
+      ratio = n_train // (n+1);  timesteps = (arange(0, n+1) * ratio).round()[::-1][:-1] + steps_offset        (int64)
+      sigmas = interp(timesteps, arange(n_train), sqrt((1-abar)/abar)) ++ [0]                                  (fp32, n+1)
+               (n = 999 is the one schedule whose first timestep, 1000, lies past the training range: `interp` clamps its
+                sigma to that of timestep 999, as diffusers' does, and the sampler runs; `add_noise` and the miner trace,
+                which read alphas_cumprod[t], refuse that timestep with a ValueError)
+      for a sigma:  alpha = 1/sqrt(sigma^2+1),  sig = sigma*alpha,  lambda = log(alpha) - log(sig)             (fp32, host)
+      step i, sample x, fp16 model output e:  (a0, s0, l0) from sigmas[i], (at, st, lt) from sigmas[i+1], h = lt - l0
+        x0 = (x - s0*e) / a0                                               (kept in fp16: the next step's history)
+        first order   x' = (st/s0)*x - (at*(exp(-h)-1))*x0                 (no history, solver_order 1, ALWAYS the last step)
+        second order  x' = (st/s0)*x - (at*(exp(-h)-1))*x0 - 0.5*(at*(exp(-h)-1))*D1,
+                      D1 = (1/r0)*(x0 - x0_prev),  r0 = (l0 - l1)/h,  l1 from sigmas[i-1]
+    Every scalar sub-expression is evaluated on the host in fp32 (0-d torch tensors) in the grouping written; every tensor
+    operation rounds to fp16, left to right; `/ a0` is `* (1/a0)` (csrc/dpm.hip).  On the last step sigma is 0: st/s0 = 0,
+    h = +inf, exp(-h) = 0, and x' is x0.
+
+    The step index is found by VALUE on the first `step` after `set_timesteps` / `reset()` (a video-to-video run starts
+    mid-schedule, and its first step is first-order) and then counts up; a timestep that does not continue the schedule is an
+    error — call `reset()` between trajectories (`DistributedVideoDiffuser.denoise` does, per chunk).  The x0 history
+    ping-pongs two buffers allocated once per `set_timesteps` and shape."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 steps_offset=1, prediction_type="epsilon", timestep_spacing="leading", algorithm_type="dpmsolver++",
+                 solver_order=2, solver_type="midpoint", thresholding=False, lower_order_final=True,
+                 final_sigmas_type="zero"):
+        if beta_schedule != "scaled_linear" or prediction_type != "epsilon" or timestep_spacing != "leading" \
+                or algorithm_type != "dpmsolver++" or solver_order not in (1, 2) or solver_type != "midpoint" \
+                or thresholding or not lower_order_final or final_sigmas_type != "zero" or steps_offset != 1:
+            raise NotImplementedError("only the Zeroscope DPM-Solver++ (2M, midpoint) configuration is implemented")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, steps_offset=steps_offset,
+                                      prediction_type=prediction_type, timestep_spacing=timestep_spacing,
+                                      algorithm_type=algorithm_type, solver_order=solver_order, solver_type=solver_type,
+                                      thresholding=thresholding, lower_order_final=lower_order_final,
+                                      final_sigmas_type=final_sigmas_type)
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.num_inference_steps = None
+        self.timesteps = None
+        self._host_timesteps = None
+        self.sigmas = None
+        self._x0 = None
+        self.reset()
+
+    _CONFIG_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset", "prediction_type",
+                    "timestep_spacing", "algorithm_type", "solver_order", "solver_type", "thresholding", "lower_order_final",
+                    "final_sigmas_type")
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """`DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`: the keys both schedulers know are taken from
+        `config` (a `DDIMScheduler.config`, this class's own, or a dict); DDIM-only keys are ignored."""
+        get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
+        kw = {k: get(k) for k in cls._CONFIG_KEYS if get(k, None) is not None}
+        kw.update(overrides)
+        return cls(**kw)
+
+    def reset(self):
+        self._step_index = None
+        self._have_prev = False
+        self._cur = 0
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n_train = self.config.num_train_timesteps
+        if not 0 < num_inference_steps < n_train:
+            raise ValueError("num_inference_steps must be in [1, num_train_timesteps)")
+        self.num_inference_steps = n = num_inference_steps
+        ratio = n_train // (n + 1)
+        ts = (np.arange(0, n + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+        ts += self.config.steps_offset
+        sigma_all = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        sig = np.interp(ts, np.arange(0, n_train), sigma_all)
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        self._host_timesteps = [int(t) for t in ts]
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._coef = {}
+        self._x0 = None
+        self.reset()
+
+    @staticmethod
+    def _alpha_sigma_lambda(sigma):
+        alpha = 1.0 / torch.sqrt(sigma * sigma + 1.0)
+        sig = sigma * alpha
+        return alpha, sig, torch.log(alpha) - torch.log(sig)
+
+    def coefficients(self, i: int, second_order: bool):
+        """Step i's host scalars for the kernel: (s0, 1/a0, st/s0, c_d0, c_d1, 1/r0) with c_d0 = -(at*(exp(-h)-1)) and
+        c_d1 = -(0.5*(at*(exp(-h)-1))); first order: c_d1 = 1/r0 = 0.  The last step's are (.., .., 0, 1, ..): x' = x0."""
+        key = (i, bool(second_order))
+        if key not in self._coef:
+            a0, s0, l0 = self._alpha_sigma_lambda(self.sigmas[i])
+            at, st, lt = self._alpha_sigma_lambda(self.sigmas[i + 1])
+            h = lt - l0
+            k = at * (torch.exp(-h) - 1.0)
+            c = [s0, 1.0 / a0, st / s0, -k, torch.zeros(()), torch.zeros(())]
+            if second_order:
+                _, _, l1 = self._alpha_sigma_lambda(self.sigmas[i - 1])
+                r0 = (l0 - l1) / h
+                c[4], c[5] = -(0.5 * k), 1.0 / r0
+            assert all(v.dtype == torch.float32 for v in c)
+            self._coef[key] = tuple(float(v) for v in c)
+        return self._coef[key]
+
+    def _plan(self, timestep, sample):
+        """-> (step index, x0_prev or None, x0_out) for this step.  Changes nothing a failed launch would have to undo: the
+        index moves and the history buffers flip in `_commit`, after the kernel was enqueued."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps first")
+        t = self._host_timestep(timestep)
+        n = self.num_inference_steps
+        if self._step_index is None:
+            if t not in self._host_timesteps:
+                raise ValueError(f"timestep {t} is not in the schedule set for {n} steps")
+            i = self._host_timesteps.index(t)
+        else:
+            i = self._step_index
+        if i >= n or self._host_timesteps[i] != t:
+            raise ValueError(f"timestep {t} does not continue the schedule (step index {i} of {n}): call reset() before a new "
+                             "trajectory")
+        key = (tuple(sample.shape), sample.device)
+        if self._x0 is None or self._x0[0] != key:
+            if self._have_prev:
+                raise ValueError("the sample's shape or device changed in mid-trajectory: call reset() first")
+            self._x0 = (key, [torch.empty_like(sample, memory_format=torch.contiguous_format) for _ in range(2)])
+        bufs = self._x0[1]
+        second = self._have_prev and self.config.solver_order == 2 and i != n - 1
+        return i, (bufs[1 - self._cur] if second else None), bufs[self._cur]
+
+    def _commit(self, i: int):
+        self._cur ^= 1
+        self._have_prev = True
+        self._step_index = i + 1
+
+    def step(self, model_output, timestep, sample, **_unused):
+        sample = sample.contiguous()
+        i, prev, x0_out = self._plan(timestep, sample)
+        new, _ = ops.dpm_step(model_output.contiguous(), sample, self.coefficients(i, prev is not None), x0_prev=prev,
+                              x0_out=x0_out)
+        self._commit(i)
+        return SimpleNamespace(prev_sample=new)
+
+    def step_cfg(self, noise2, timestep, sample, guidance_scale: float):
+        """Fused `u + gs*(c-u)` + step in one kernel (`vdx_cfg_dpm_step_f16`)."""
+        sample = sample.contiguous()
+        i, prev, x0_out = self._plan(timestep, sample)
+        new, _ = ops.cfg_dpm_step(noise2, sample, guidance_scale, self.coefficients(i, prev is not None), x0_prev=prev,
+                                  x0_out=x0_out)
+        self._commit(i)
+        return new

@@ -320,6 +320,24 @@ int vdx_cfg_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, floa
 int vdx_ddim_step_f16(const void* eps, const void* lat, void* lat_out, float sqrt_one_minus_at,
                       float sqrt_at, float sqrt_aprev, float sqrt_one_minus_aprev, size_t n,
                       vdx_stream_t stream);
+/* DPM-Solver++ (2M, midpoint; diffusers `DPMSolverMultistepScheduler.step`, the scheduler Zeroscope's published recipe
+ * swaps in for DDIM) fused with the CFG combine of :141 — replaces `u + gs*(c-u)` + `convert_model_output` +
+ * `dpm_solver_first_order_update` / `multistep_dpm_solver_second_order_update`, about a dozen elementwise launches per step.
+ * fp32 host coefficients, fp16 rounding after every tensor op, in this order (vdx/scheduler.py states the schedule):
+ *   e  = u + guidance*(c - u);        x0 = (lat - c_s0*e) * c_inv_a0        -> x0_out (the next step's history)
+ *   lat' = c_x*lat + c_d0*x0  [ + c_d1 * (c_inv_r0 * (x0 - x0_prev)) ]        -> lat_out
+ * x0_prev == NULL selects the first-order form (c_d1, c_inv_r0 unused).  c_d0 = -at*(exp(-h)-1), c_d1 = 0.5*c_d0,
+ * c_inv_r0 = 1/r0: D1 = (1/r0)*(x0 - x0_prev) is a tensor of its own and rounds before the 0.5*... product, so the two
+ * scalars cannot be folded into one.  lat_out may be lat; x0_out may not be x0_prev, and no other two may overlap.
+ * Every pointer 16-byte aligned (16-byte accesses; eps2's second half element-wise when n % 8 != 0); any n.             */
+int vdx_cfg_dpm_step_f16(const void* eps2, const void* lat, const void* x0_prev, void* x0_out, void* lat_out,
+                         float guidance, float c_s0, float c_inv_a0, float c_x, float c_d0, float c_d1,
+                         float c_inv_r0, size_t n, vdx_stream_t stream);
+/* the same step on a model output the caller already combined (or never guided: the miner loop, an unchanged
+ * reference-style script calling `scheduler.step`) — replaces diffusers' `DPMSolverMultistepScheduler.step` alone.     */
+int vdx_dpm_step_f16(const void* eps, const void* lat, const void* x0_prev, void* x0_out, void* lat_out, float c_s0,
+                     float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, size_t n,
+                     vdx_stream_t stream);
 /* :204-217 one chunk's contribution: full[s:e] += lat*w (fp16 accumulator), weight[s:e] += w;
  * w = fp32 device vector of length e-s (the linear ramps, built by the host exactly as :207-213) */
 int vdx_blend_accumulate_f16(void* full, float* weight, const void* chunk, const float* w, int C,

@@ -132,6 +132,8 @@ SIGNATURES = {
     "vdx_flow_update_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vdx_flow_abs_sum_f32": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    # motion-compensated frame interpolation (no reference counterpart; vdx/interp.py, csrc/interp.hip)
+    "vdx_interp_frames_u8": (_i, [_vp, _sz, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

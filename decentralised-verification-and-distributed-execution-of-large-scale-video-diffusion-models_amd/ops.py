@@ -1214,3 +1214,30 @@ def flow_remap_absdiff(frames, flow, step: int = 1, want_warped: bool = False):
             _f32(flow, flow.shape, "flow_remap_absdiff", "flow"), P, step, H, W, diff.data_ptr(),
             warped.data_ptr() if want_warped else None)
     return diff, warped
+
+
+# --------------------------------------------------------------------------------------------
+# Motion-compensated frame interpolation (no reference counterpart; include/vdx.h "interpolation"; csrc/interp.hip).
+# vdx/interp.py computes the flows and calls this.
+def interp_frames(frames, fab, fba, factor: int, out=None):
+    """uint8 RGB frames (F, H, W, 3), F >= 2, and their flows fab (frame i -> i+1) and fba (frame i+1 -> i), fp32 (F-1, H, W, 2),
+    all on the GPU -> uint8 ((F-1)*factor + 1, H, W, 3): frame i*factor is frame i, the factor-1 frames after it are the
+    motion-compensated blends at k / factor (tests/interp_ref.py states them).  One launch (vdx_interp_frames_u8)."""
+    F, H, W = _check_u8_frames(frames, "interp_frames")
+    if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= 64:
+        raise VdxError(f"interp_frames: factor must be an integer in 1..64, got {factor!r}")
+    if F < 2:
+        raise VdxError(f"interp_frames: at least two frames are needed, got {F}")
+    for name, fl in (("fab", fab), ("fba", fba)):
+        if fl.device != frames.device:
+            raise VdxError(f"interp_frames: {name} is on {fl.device}, the frames on {frames.device}")
+        _f32(fl, (F - 1, H, W, 2), "interp_frames", name)
+    n_out = (F - 1) * factor + 1
+    if out is None:
+        out = torch.empty((n_out, H, W, 3), dtype=torch.uint8, device=frames.device)
+    elif (not out.is_cuda or out.device != frames.device or out.dtype != torch.uint8 or tuple(out.shape) != (n_out, H, W, 3)
+          or not out.is_contiguous()):
+        raise VdxError(f"interp_frames: out must be contiguous uint8 {(n_out, H, W, 3)} on the frames' device")
+    _launch("vdx_interp_frames_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), fab.data_ptr(), fba.data_ptr(), F, H, W,
+            factor, out.data_ptr(), out.stride(0))
+    return out

@@ -65,6 +65,7 @@ class DiffuserConfig:
     posterior: str = "sample"              # "sample" | "mode" of the encoder's diagonal Gaussian
     gpu_flow: bool = False                 # flow_err (and MD-VQS' TC) from the HIP Farneback kernels instead of the host path
     scheduler: str = "ddim"                # "ddim" | "dpmpp_2m" (DPM-Solver++ 2M, vdx/scheduler.py): the sampler `run_job` uses
+    interpolate: int = 1                   # N > 1: write (F-1) N + 1 motion-interpolated frames at fps N (vdx/interp.py); 1 = as always
 
     @property
     def use_fsdp(self):
@@ -538,7 +539,10 @@ def build_arg_parser():
     kernels (vdx/video.py `write_frames`, csrc/mjpeg_enc.hip) instead of in Pillow on the host: the same file byte for byte,
     with or without `--video_restart_rows`.  `--scheduler dpmpp_2m` samples with DPM-Solver++ 2M (vdx/scheduler.py
     `DPMSolverMultistepScheduler`, built from the pipeline scheduler's config) instead of DDIM; `--scheduler ddim`, the default,
-    is the run without the flag."""
+    is the run without the flag.  `--interpolate N` (no reference counterpart) writes the mp4 with N - 1 motion-compensated
+    frames between every two generated ones (vdx/interp.py, csrc/interp.hip), (F - 1) N + 1 frames at fps N; the row's numbers
+    and the frames `--clip_json` / `--mdvqs_json` score stay those of the generated frames, unless `--score_from_file` asks for
+    what the file holds; `--interpolate 1`, the default, is the run without the flag."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -578,6 +582,8 @@ def build_arg_parser():
     p.add_argument("--posterior", choices=["sample", "mode"], default="sample", help="video-to-video: encoder posterior")
     p.add_argument("--scheduler", choices=list(SCHEDULERS), default="ddim",
                    help="sampler: ddim (the reference's, default) or dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality)")
+    p.add_argument("--interpolate", type=int, default=1,
+                   help="write N - 1 motion-interpolated frames between every two generated ones, at fps * N (1: none, the default)")
     return p
 
 
@@ -587,7 +593,7 @@ def config_from_args(a) -> DiffuserConfig:
                           device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
                           out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
                           init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow,
-                          scheduler=a.scheduler)
+                          scheduler=a.scheduler, interpolate=a.interpolate)
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -679,6 +685,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     from . import metrics
     from .compat.diffusers_shim import DiffusionPipeline
     from .compat import pynvml_shim
+    from .interp import check_factor
+    factor = check_factor(cfg.interpolate)      # refused before anything is loaded
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -720,9 +728,19 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     if d.rank == 0 and len(frames) > 1 and not cfg.no_chunking:
         temp_instab = metrics.boundary_l1(frames, ranges)
         flow_err = metrics.flow_warp_error(frames, ranges, device=dev) if cfg.gpu_flow else metrics.flow_warp_error(frames, ranges)
+    frames_written = None
     if d.rank == 0 and out_video:
-        metrics.write_video(frames, out_video, cfg.fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}),
+        to_write, fps = frames, cfg.fps
+        if factor > 1:
+            # after the metrics above, which are numbers about the generated frames; `frames` itself (what --clip_json and
+            # --mdvqs_json score) stays as it is
+            from .interp import interpolate_frames
+            to_write, fps = interpolate_frames(frames, factor, device=dev), cfg.fps * factor
+            if not gpu_video_write:
+                to_write = list(to_write.cpu().numpy())
+        metrics.write_video(to_write, out_video, fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}),
                             **({"device": dev} if gpu_video_write else {}))
+        frames_written = len(to_write)
     delay = emu_reduce_delay_s(cfg)             # :257-258
     if delay > 0:
         time.sleep(delay)
@@ -738,7 +756,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "denoise_s": info["denoise_s"], "exchange": exchange, "rank": d.rank, "synthetic_weights": pipe.synthetic_weights,
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
-            "scheduler": cfg.scheduler}
+            "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written}
 
 
 def main(argv=None) -> int:

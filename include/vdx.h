@@ -570,6 +570,23 @@ int vdx_flow_remap_absdiff_u8(const void* frames, size_t frame_pitch, int row_pi
                               int W, uint64_t* absdiff, void* warped, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Motion-compensated frame interpolation (no reference counterpart: fsdp_chunked_coherent.py:250-253 writes the generated
+ * frames as they are; the job's --interpolate N, vdx/interp.py, csrc/interp.hip).  tests/interp_ref.py states the expression.
+ * ------------------------------------------------------------------------------------------ */
+/* frames: uint8 RGB [F] (pitches in bytes); fab / fba: fp32 [F-1][H][W][2], the Farneback flows frame i -> i+1 and
+ * i+1 -> i (8-byte aligned, never NULL); out: uint8 [(F-1)*N + 1] frames of packed rows, out_frame_pitch >= 3*W*H bytes apart.
+ * Output frame i*N is frame i byte for byte; frame i*N + k, k = 1 .. N-1, with t = k/N and a = (N-k)/N, per pixel x:
+ *   gA = (t*t)*Fba(x) - (a*t)*Fab(x), gB = (a*a)*Fab(x) - (a*t)*Fba(x)  (a non-finite g: 0, and the side's weight * 1e-6);
+ *   S = bilinear sample of the frame at x + g clamped to the frame; v = 1 / (1 + |r|^2), r = the frame's own flow there plus
+ *   the other flow where that points (0 for a non-finite |r|^2; * 1e-6 when x + g is outside [-0.5, W-0.5] x [-0.5, H-0.5]);
+ *   out = (a*vA*SA + t*vB*SB) / (a*vA + t*vB), the plain a*SA + t*SB when that denominator is not positive, then
+ *   floor(out + 0.5) clamped to 0..255.  fp32 without contraction; every gather index is clamped as an integer after the float
+ *   was clamped, so no flow value reads outside the frames.  One launch, no atomics: the same bits on every run and for any F.
+ * 1 <= N <= 64, 1 <= F <= 65536.                                                                                          */
+int vdx_interp_frames_u8(const void* frames, size_t frame_pitch, int row_pitch, const float* fab, const float* fba, int F, int H,
+                         int W, int N, void* out, size_t out_frame_pitch, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

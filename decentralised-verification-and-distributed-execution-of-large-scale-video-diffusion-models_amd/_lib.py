@@ -134,6 +134,13 @@ SIGNATURES = {
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     # motion-compensated frame interpolation (no reference counterpart; vdx/interp.py, csrc/interp.hip)
     "vdx_interp_frames_u8": (_i, [_vp, _sz, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    # full-reference clip comparison: SSE / SSIM / MS-SSIM (no reference counterpart; vdx/compare.py, csrc/compare.hip)
+    "vdx_compare_tiles": (_i, [_i, _i]),
+    "vdx_compare_ssim_scale_u8": (_i, [_vp, _sz, _i, _vp, _sz, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp, _vp]),
+    "vdx_compare_ssim_scale_f32": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp]),
+    "vdx_compare_down2_u8": (_i, [_vp, _sz, _i, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vdx_compare_down2_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "vdx_compare_finalize": (_i, [_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -1241,3 +1241,102 @@ def interp_frames(frames, fab, fba, factor: int, out=None):
     _launch("vdx_interp_frames_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), fab.data_ptr(), fba.data_ptr(), F, H, W,
             factor, out.data_ptr(), out.stride(0))
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Full-reference clip comparison: SSE / SSIM / MS-SSIM (no reference counterpart; include/vdx.h "comparison"; csrc/compare.hip).
+# vdx/compare.py drives these and turns the means into the metrics; planes between the scales are packed fp32 [n][H][W].
+COMPARE_TAPS, COMPARE_SCALES = 11, 5
+
+
+def compare_tiles(H: int, W: int) -> int:
+    """Blocks per plane of `compare_ssim_scale` at H x W; `VdxError` for a size the kernel does not take (min(H, W) < 11)."""
+    n = _lib.load().vdx_compare_tiles(int(H), int(W))
+    if n <= 0:
+        raise VdxError(f"compare: planes of {H}x{W} are outside what the kernel takes (H, W >= {COMPARE_TAPS}, H*W < 2^28)")
+    return n
+
+
+def _compare_pair(a, b, what):
+    """-> (is_u8, n_planes, H, W) of two uint8 RGB clips (F, H, W, 3) or two packed fp32 plane stacks (n, H, W) on one GPU."""
+    if a.dtype == torch.uint8:
+        F, H, W = _check_u8_frames(a, what)
+        if b is not None and (_check_u8_frames(b, what) != (F, H, W) or b.device != a.device):
+            raise VdxError(f"{what}: b {tuple(b.shape)} on {b.device} does not match a {tuple(a.shape)} on {a.device}")
+        return True, 3 * F, H, W
+    if a.dim() != 3 or a.shape[0] < 1:
+        raise VdxError(f"{what}: expected uint8 frames (F, H, W, 3) or fp32 planes (n, H, W), got {a.dtype} {tuple(a.shape)}")
+    _f32(a, a.shape, what, "a")
+    if b is not None:
+        if b.device != a.device:
+            raise VdxError(f"{what}: b is on {b.device}, a on {a.device}")
+        _f32(b, a.shape, what, "b")
+    return False, int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+
+
+def _compare_taps(taps):
+    import numpy as np
+    t = np.ascontiguousarray(taps, np.float64)
+    if t.shape != (COMPARE_TAPS,):
+        raise VdxError(f"compare: taps {t.shape}: expected ({COMPARE_TAPS},)")
+    return t, t.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def compare_ssim_scale(a, b, taps):
+    """One scale of every plane pair: a, b uint8 RGB (F, H, W, 3) or packed fp32 planes (n, H, W) on the GPU; `taps` the 11
+    float64 window weights (host) -> (partials fp64 (planes, tiles, 2): every block's sums of ssim and cs; for uint8 input the
+    blocks' exact sums of (a - b)^2 int64 (planes, tiles), else None).  vdx_compare_ssim_scale_u8 / _f32."""
+    u8, n, H, W = _compare_pair(a, b, "compare_ssim_scale")
+    if b is None:
+        raise VdxError("compare_ssim_scale: two clips are needed")
+    tiles = compare_tiles(H, W)
+    t, tp = _compare_taps(taps)
+    part = torch.empty((n, tiles, 2), dtype=torch.float64, device=a.device)
+    if u8:
+        sse = torch.empty((n, tiles), dtype=torch.int64, device=a.device)
+        _launch("vdx_compare_ssim_scale_u8", a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), n // 3, H, W,
+                tp, part.data_ptr(), sse.data_ptr())
+        return part, sse
+    _launch("vdx_compare_ssim_scale_f32", a.data_ptr(), b.data_ptr(), n, H, W, tp, part.data_ptr())
+    return part, None
+
+
+def compare_down2(a, b=None):
+    """2x2 mean (fp32, ((p00 + p01) + (p10 + p11)) * 0.25; an odd last row or column is dropped) of every plane of `a` and, when
+    given, `b`: uint8 RGB (F, H, W, 3) -> fp32 (3F, H/2, W/2), fp32 (n, H, W) -> (n, H/2, W/2).  -> out_a, or (out_a, out_b).
+    vdx_compare_down2_u8 / _f32."""
+    u8, n, H, W = _compare_pair(a, b, "compare_down2")
+    if H < 2 or W < 2:
+        raise VdxError(f"compare_down2: planes of {H}x{W} cannot be halved")
+    oa = torch.empty((n, H // 2, W // 2), dtype=torch.float32, device=a.device)
+    ob = torch.empty_like(oa) if b is not None else None
+    pb, pob = (b.data_ptr(), ob.data_ptr()) if b is not None else (None, None)
+    if u8:
+        _launch("vdx_compare_down2_u8", a.data_ptr(), a.stride(0), a.stride(1), pb, b.stride(0) if b is not None else 0,
+                b.stride(1) if b is not None else 0, n // 3, H, W, oa.data_ptr(), pob)
+    else:
+        _launch("vdx_compare_down2_f32", a.data_ptr(), pb, n, H, W, oa.data_ptr(), pob)
+    return oa if b is None else (oa, ob)
+
+
+def compare_finalize(partials, sse_partials, count: int, scale: int, means, sse=None):
+    """The blocks' partials (planes, tiles, 2) of one scale, planes = 3 F, summed in a fixed order over `count` positions into
+    means[:, :, scale, :] (fp64 (F, 3, 5, 2): ssim, cs); with `sse_partials` (scale 0) also sse (int64 [F]).  vdx_compare_finalize."""
+    if (partials.dim() != 3 or partials.shape[2] != 2 or partials.shape[0] % 3 or partials.dtype != torch.float64
+            or not partials.is_cuda or not partials.is_contiguous()):
+        raise VdxError(f"compare_finalize: partials must be contiguous fp64 (3F, tiles, 2) on the GPU, got {tuple(partials.shape)}")
+    F, tiles = partials.shape[0] // 3, partials.shape[1]
+    if (means.dtype != torch.float64 or tuple(means.shape) != (F, 3, COMPARE_SCALES, 2) or not means.is_contiguous()
+            or means.device != partials.device):
+        raise VdxError(f"compare_finalize: means must be contiguous fp64 {(F, 3, COMPARE_SCALES, 2)} on the partials' device")
+    if (sse_partials is None) != (sse is None):
+        raise VdxError("compare_finalize: sse_partials and sse go together")
+    if sse is not None:
+        for name, t, shape in (("sse_partials", sse_partials, (3 * F, tiles)), ("sse", sse, (F,))):
+            if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != partials.device:
+                raise VdxError(f"compare_finalize: {name} must be contiguous int64 {shape} on the partials' device")
+    if not 0 <= int(scale) < COMPARE_SCALES or int(count) < 1:
+        raise VdxError(f"compare_finalize: scale {scale}, count {count}")
+    _launch("vdx_compare_finalize", partials.data_ptr(), sse_partials.data_ptr() if sse is not None else None, F, tiles,
+            float(count), int(scale), means.data_ptr(), sse.data_ptr() if sse is not None else None)
+    return means

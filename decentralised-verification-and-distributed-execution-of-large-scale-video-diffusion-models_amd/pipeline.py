@@ -542,7 +542,11 @@ def build_arg_parser():
     is the run without the flag.  `--interpolate N` (no reference counterpart) writes the mp4 with N - 1 motion-compensated
     frames between every two generated ones (vdx/interp.py, csrc/interp.hip), (F - 1) N + 1 frames at fps N; the row's numbers
     and the frames `--clip_json` / `--mdvqs_json` score stay those of the generated frames, unless `--score_from_file` asks for
-    what the file holds; `--interpolate 1`, the default, is the run without the flag."""
+    what the file holds; `--interpolate 1`, the default, is the run without the flag.  `--compare_to PATH --compare_json OUT`
+    (no reference counterpart; both or neither) compares the generated frames with the clip at PATH (a `.npy` of uint8 frames
+    or a Motion-JPEG mp4) on rank 0 after the row is written and writes the PSNR / SSIM / MS-SSIM record of vdx/compare.py,
+    with the job's chunk ranges (so the means at the seams and away from them) and `"compare_to": PATH`, to OUT; a missing PATH
+    or a `.npy` of another shape is refused before any model is loaded."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -584,6 +588,9 @@ def build_arg_parser():
                    help="sampler: ddim (the reference's, default) or dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality)")
     p.add_argument("--interpolate", type=int, default=1,
                    help="write N - 1 motion-interpolated frames between every two generated ones, at fps * N (1: none, the default)")
+    p.add_argument("--compare_to", default=None,
+                   help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
+    p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
     return p
 
 
@@ -634,6 +641,27 @@ def mdvqs_record(frames, prompt: str, lpips_model: Optional[str], clip_model: Op
     if flow != "cpu":
         rec["flow"] = flow
     return rec
+
+
+def check_compare_args(a) -> None:
+    """`--compare_to` and `--compare_json` go together, and the clip must be there and, where its header says so, of the job's
+    shape: `VdxError` before anything is loaded."""
+    from ._lib import VdxError
+    if bool(a.compare_to) != bool(a.compare_json):
+        raise VdxError("--compare_to PATH and --compare_json OUT are given together or not at all")
+    if a.compare_to:
+        from .compare import check_target
+        check_target(a.compare_to, (a.num_frames, a.height, a.width, 3))
+
+
+def compare_record(frames, path: str, ranges, device) -> dict:
+    """The record `--compare_json` writes: vdx/compare.py's comparison of the generated frames (a) with the clip at `path` (b),
+    seam and interior means by the job's chunk ranges.  MS-SSIM is left out below 176 pixels."""
+    from . import compare
+    other = compare.load_clip(path, device)
+    h, w = frames[0].shape[:2]
+    rec = compare.compare_frames(frames, other, ms_ssim=min(h, w) >= compare.MS_MIN_SIDE, ranges=ranges, device=device)
+    return {"compare_to": path, **rec}
 
 
 def encode_init_video(cfg: DiffuserConfig, vae, dev):
@@ -749,7 +777,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     end_mb = pynvml_shim.nvmlDeviceGetMemoryInfo(pynvml_shim.nvmlDeviceGetHandleByIndex(dev.index or 0)).used // 1024 ** 2
     if d.rank == 0 and clip_inputs is not None:
         # what `clip_score_record` needs, handed to the caller: the score runs outside the job (and outside main()'s timing)
-        clip_inputs.update(frames=frames, tokenizer=tok, device=dev)
+        clip_inputs.update(frames=frames, tokenizer=tok, device=dev, ranges=ranges)
     return {"world_size": d.world, "chunk_size": info["chunk_size"], "overlap": info["overlap"], "num_frames": cfg.num_frames,
             "peak_vram_mb": peak_mb, "end_vram_mb": int(end_mb), "network_bytes": int(info["payload_bytes"]),
             "net_gather_s": info["net_gather_s"], "net_reduce_s": reduce_s, "temp_instab": temp_instab, "flow_err": flow_err,
@@ -768,7 +796,8 @@ def main(argv=None) -> int:
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
-    clip_inputs = {} if a.clip_json or a.mdvqs_json else None
+    check_compare_args(a)
+    clip_inputs = {} if a.clip_json or a.mdvqs_json or a.compare_to else None
     t0 = time.time()
     if a.score_from_file and not a.out_video:
         raise ValueError("--score_from_file needs --out_video")
@@ -780,6 +809,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {}
+        generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
             from .video import read_frames
@@ -800,6 +830,12 @@ def main(argv=None) -> int:
             rec.update(source)
             with open(a.mdvqs_json, "w") as f:
                 json.dump(rec, f, indent=1)
+        if a.compare_to:
+            # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
+            from . import compare
+            rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
+            with open(a.compare_json, "w") as f:
+                f.write(compare.dumps(rec))
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
     return 0

@@ -587,6 +587,38 @@ int vdx_interp_frames_u8(const void* frames, size_t frame_pitch, int row_pitch, 
                          int W, int N, void* out, size_t out_frame_pitch, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Full-reference comparison of two uint8 RGB clips of one shape: SSE (PSNR), SSIM, MS-SSIM (nothing in the reference: it never
+ * holds two clips; vdx/compare.py, csrc/compare.hip).  tests/compare_ref.py states the definition: every R, G, B plane on its
+ * own, the 11-tap Gaussian window (sigma 1.5) as a valid correlation, C1 = (0.01*255)^2, C2 = (0.03*255)^2, a 2x2 mean between
+ * the five scales.  fp64 between the fp32 samples and the fp64 results, no mul-add contraction, fixed-order sums, no atomics:
+ * the same bits on every run, for any number of frames per call, and with the two clips exchanged.
+ * ------------------------------------------------------------------------------------------ */
+/* Blocks (16 x 32 tiles of the (H-10) x (W-10) map of window positions) per plane; 0 unless H, W >= 11 and H*W < 2^28.      */
+int vdx_compare_tiles(int H, int W);
+/* One scale of all 3 F plane pairs of uint8 RGB frames a, b (pitches in bytes).  taps: float64 [11] in HOST memory, read
+ * before the call returns.  partials: fp64 [3F][tiles][2], every block's sum of ssim and of cs over its valid positions;
+ * sse_partials: uint64 [3F][tiles], every block's sum of (a - b)^2 over the bytes it owns (each byte of a plane has one
+ * owner).  F <= 21845.  Replaces nothing in the reference.                                                               */
+int vdx_compare_ssim_scale_u8(const void* a, size_t a_frame_pitch, int a_row_pitch, const void* b, size_t b_frame_pitch,
+                              int b_row_pitch, int F, int H, int W, const double* taps, double* partials, uint64_t* sse_partials,
+                              vdx_stream_t stream);
+/* The same for packed fp32 planes [n_planes][H][W] (scales 1..4); no byte sums.  Replaces nothing in the reference.        */
+int vdx_compare_ssim_scale_f32(const float* a, const float* b, int n_planes, int H, int W, const double* taps, double* partials,
+                               vdx_stream_t stream);
+/* 2x2 mean, ((p00 + p01) + (p10 + p11)) * 0.25 in fp32, of every plane of uint8 RGB frames a and (unless NULL, with out_b) b ->
+ * packed fp32 planes [3F][H/2][W/2]; an odd last row or column is dropped.  Replaces nothing in the reference.            */
+int vdx_compare_down2_u8(const void* a, size_t a_frame_pitch, int a_row_pitch, const void* b, size_t b_frame_pitch, int b_row_pitch,
+                         int F, int H, int W, float* out_a, float* out_b, vdx_stream_t stream);
+/* The same for packed fp32 planes [n_planes][H][W].  Replaces nothing in the reference.                                   */
+int vdx_compare_down2_f32(const float* a, const float* b, int n_planes, int H, int W, float* out_a, float* out_b, vdx_stream_t stream);
+/* Per frame f and plane c: the n_tiles partials summed in a fixed order over `count` (the positions of a plane) ->
+ * means[f][c][scale][0..1] = mean ssim, mean cs (means: fp64 [F][3][5][2]; the other scales are left alone); with
+ * sse_partials, sse[f] = the exact sum of (a - b)^2 over the frame's 3 H W bytes (uint64 [F]).  Replaces nothing in the
+ * reference.                                                                                                             */
+int vdx_compare_finalize(const double* partials, const uint64_t* sse_partials, int F, int n_tiles, double count, int scale,
+                         double* means, uint64_t* sse, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

@@ -5,7 +5,7 @@
         Q = 1/F * sum_i cos(E_text, E_frame_i)        under openai/clip-vit-base-patch32
 
 What it computes, step by step (the same as the reference unless stated):
-  * frames: decoded uint8 RGB (F, H, W, 3), on the GPU or as host arrays.  DEVIATION: the reference re-reads the mp4
+  * frames: a decoded uint8 RGB clip in any form vdx/frames.py takes.  DEVIATION: the reference re-reads the mp4
     with OpenCV and converts BGR->RGB (:110-121); here the frames the pipeline decoded are scored directly — no lossy
     codec round trip, and OpenCV is not a dependency;
   * Resize((224, 224)) + ToTensor + Normalize (:81-85): Pillow's antialiased bilinear resize, bit for bit, then
@@ -31,10 +31,9 @@ import json
 import os
 from typing import Dict, Optional, Tuple
 
-import numpy as np
 import torch
 
-from . import ops
+from . import frames as _frames, ops
 from ._lib import VdxError
 from .clip_text import CLIPTextConfig, CLIPTextModel
 from .clip_vision import CLIPVisionConfig, CLIPVisionModel
@@ -79,19 +78,6 @@ def split_state_dict(sd: Dict[str, torch.Tensor]):
         if k not in proj:
             raise VdxError(f"CLIPScorer: missing key in state dict: {k}")
     return text, vision, proj
-
-
-def _frames_tensor(frames, device) -> torch.Tensor:
-    """uint8 (F, H, W, 3) on `device` from a tensor, an array or a list of (H, W, 3) arrays (the pipeline's frames)."""
-    if isinstance(frames, torch.Tensor):
-        t = frames
-    elif isinstance(frames, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(frames))
-    else:
-        t = torch.from_numpy(np.stack([np.asarray(f) for f in frames])) if len(frames) else torch.empty((0, 1, 1, 3), dtype=torch.uint8)
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-        raise VdxError(f"CLIPScorer: expected uint8 RGB frames (F, H, W, 3), got {t.dtype} {tuple(t.shape)}")
-    return t.to(device)
 
 
 class CLIPScorer:
@@ -157,9 +143,9 @@ class CLIPScorer:
     @torch.no_grad()
     def image_features(self, frames) -> torch.Tensor:
         """uint8 RGB frames (F, H, W, 3) -> `get_image_features(...).pooler_output` fp16 [F][projection_dim]."""
-        t = _frames_tensor(frames, self.device)
-        if t.shape[0] == 0:
+        if _frames.check(frames, "CLIPScorer")[0] == 0:
             raise VdxError("CLIPScorer.image_features: no frames")
+        t = _frames.on_device(frames, self.device)
         pooled = self.vision(t)
         return ops.gemm(pooled, self.W["visual_projection"], M=t.shape[0])
 
@@ -185,9 +171,9 @@ class CLIPScorer:
     @torch.no_grad()
     def score(self, frames, prompt_or_ids, tokenizer=None) -> Tuple[float, torch.Tensor]:
         """-> (Q, per-frame cosines fp32 [F] on the host).  Zero frames -> (0.0, empty) before anything else (:133-135)."""
-        t = _frames_tensor(frames, self.device)
-        if t.shape[0] == 0:
+        if _frames.check(frames, "CLIPScorer")[0] == 0:
             return 0.0, torch.empty(0, dtype=torch.float32)
+        t = _frames.on_device(frames, self.device)
         ids = prompt_or_ids if isinstance(prompt_or_ids, torch.Tensor) else self.tokenize(prompt_or_ids, tokenizer)
         if ids.dim() == 2 and ids.shape[0] != 1:
             raise VdxError("CLIPScorer.score: one prompt per video")

@@ -33,7 +33,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import flow as _flow
+from . import flow as _flow, frames as _frames
 from ._lib import VdxError
 
 WIN, SIGMA = 11, 1.5
@@ -52,10 +52,7 @@ def window() -> np.ndarray:
 
 def check_pair(a, b, ms_ssim: bool = True) -> Tuple[int, int, int]:
     """Two uint8 RGB clips of one shape, F >= 1, min(H, W) >= 11 (176 with `ms_ssim`) -> (F, H, W); `VdxError` otherwise."""
-    try:
-        sa, sb = _flow._check_frames(a), _flow._check_frames(b)
-    except VdxError as e:
-        raise VdxError(str(e).replace("flow:", "compare:", 1)) from None
+    sa, sb = _frames.check(a, "compare"), _frames.check(b, "compare")
     if sa != sb:
         raise VdxError(f"compare: the clips differ in shape: {sa} and {sb} (frames, height, width)")
     F, H, W = sa
@@ -121,16 +118,6 @@ def _mean(values: Sequence[float], index=None) -> float:
     return float(sum(v) / len(v))                     # inf when a PSNR in it is
 
 
-def _on_device(frames, F: int, dev: torch.device) -> torch.Tensor:
-    """The clip as a uint8 (F, H, W, 3) tensor on `dev`: a tensor already there with packed pixels (rows and frames may be
-    pitched) is used where it is, anything else is uploaded once."""
-    if isinstance(frames, torch.Tensor) and frames.is_cuda and frames.device == dev:
-        H, W = frames.shape[1:3]
-        if frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) >= 3 * W and frames.stride(0) >= frames.stride(1) * H:
-            return frames
-    return _flow._upload(frames, range(F), dev)
-
-
 def compare_frames(a, b, *, ms_ssim: bool = True, lpips=None, ranges=None, device=None) -> dict:
     """Two uint8 RGB clips of one shape (tensors, on the GPU used in place; arrays; sequences of (H, W, 3) frames) -> a record:
     per-frame lists `psnr` (floats, `math.inf` where the frames are equal), `sse` (ints), `ssim`, `ms_ssim` (unless
@@ -142,8 +129,8 @@ def compare_frames(a, b, *, ms_ssim: bool = True, lpips=None, ranges=None, devic
     if lpips is not None and not hasattr(lpips, "distances_device"):
         raise VdxError(f"compare: lpips must be a vdx.lpips.LPIPSAlex, got {type(lpips).__name__}")
     seams = seam_frames(F, ranges) if ranges is not None else []
-    dev = _flow._device_of(a if isinstance(a, torch.Tensor) and a.is_cuda else b, device)
-    ua, ub = _on_device(a, F, dev), _on_device(b, F, dev)
+    dev = _frames.device_for(a if isinstance(a, torch.Tensor) and a.is_cuda else b, device)
+    ua, ub = _frames.on_device(a, dev), _frames.on_device(b, dev)
     means, sse = plane_means(ua, ub, len(MS_WEIGHTS) if ms_ssim else 1)
     means, sse = means.cpu().numpy(), [int(v) for v in sse.cpu().tolist()]
     n = 3 * H * W

@@ -13,7 +13,7 @@ was written), so the numbers' agreement with the reference's own remains unpinne
 
 Only the parameters both callers use are provided: pyr_scale 0.5, winsize 15, poly_n 5, poly_sigma 1.2, flags 0
 (scoring.py:325-327, fsdp_chunked_coherent.py:240); `levels` and `iterations` are free.  Anything else, frames that are not
-uint8 RGB, or min(H, W) < 16 raise `VdxError` before any launch.
+a uint8 RGB clip (vdx/frames.py), or min(H, W) < 16 raise `VdxError` before any launch.
 
 Every frame's pyramid and polynomial expansion are computed once and serve both pairs the frame belongs to; each update
 iteration is one launch over all pairs.  All sums run in a fixed order without floating-point atomics, so a pair's flow has
@@ -27,6 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import frames as _frames
 from ._lib import VdxError
 
 PYR_SCALE, LEVELS, WINSIZE, ITERATIONS, POLY_N, POLY_SIGMA, FLAGS = 0.5, 3, 15, 3, 5, 1.2, 0     # the callers' arguments
@@ -84,47 +85,6 @@ def check_params(pyr_scale=PYR_SCALE, levels=LEVELS, winsize=WINSIZE, iterations
     return max(int(levels), 1), max(int(iterations), 1)
 
 
-def _is_u8(x) -> bool:
-    return x.dtype == (torch.uint8 if isinstance(x, torch.Tensor) else np.uint8)
-
-
-def _check_frames(frames):
-    """uint8 RGB frames as a (F, H, W, 3) tensor / array or a sequence of (H, W, 3) arrays -> (F, H, W); `VdxError` otherwise."""
-    if isinstance(frames, (torch.Tensor, np.ndarray)):
-        if not _is_u8(frames) or frames.ndim != 4 or frames.shape[3] != 3:
-            raise VdxError(f"flow: expected uint8 RGB frames (F, H, W, 3), got {frames.dtype} {tuple(frames.shape)}")
-        return tuple(int(v) for v in frames.shape[:3])
-    fr = [f if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
-    for f in fr:
-        if not _is_u8(f) or f.ndim != 3 or f.shape[2] != 3 or f.shape != fr[0].shape:
-            raise VdxError(f"flow: expected uint8 RGB frames (H, W, 3) of one size, got {f.dtype} {tuple(f.shape)}")
-    return (len(fr),) + (tuple(int(v) for v in fr[0].shape[:2]) if fr else (0, 0))
-
-
-def _device_of(frames, device) -> torch.device:
-    if device is not None:
-        return torch.device(device)
-    return frames.device if isinstance(frames, torch.Tensor) and frames.is_cuda else torch.device("cuda")
-
-
-def _writable(a) -> np.ndarray:
-    """Contiguous, and a copy when the array is read-only (torch tensors cannot wrap those)."""
-    a = np.ascontiguousarray(a)
-    return a if a.flags.writeable else a.copy()
-
-
-def _upload(frames, index: Sequence[int], device: torch.device) -> torch.Tensor:
-    """Frames `index` of `frames` as one packed uint8 (n, H, W, 3) tensor on `device`; only those frames are copied."""
-    index = list(index)
-    if isinstance(frames, torch.Tensor):
-        sel = frames if index == list(range(frames.shape[0])) else frames[torch.as_tensor(index, device=frames.device)]
-        return sel.to(device).contiguous()
-    if isinstance(frames, np.ndarray):
-        return torch.from_numpy(_writable(frames[index])).to(device)
-    return torch.stack([f if isinstance(f, torch.Tensor) else torch.from_numpy(_writable(f))
-                        for f in (frames[i] for i in index)]).to(device)
-
-
 # ---- the flow ------------------------------------------------------------------------------------------------------------
 _TAPS: dict = {}        # (device, radius) -> fp32 taps on the device
 
@@ -137,7 +97,7 @@ def _taps_on(device, sigma: float, radius: int) -> torch.Tensor:
 
 
 def _flows(u8: torch.Tensor, levels: int, iterations: int, step: int, bgr: bool) -> torch.Tensor:
-    """Flows of the pairs (p*step, p*step + 1) of packed uint8 frames on the GPU -> fp32 (P, H, W, 2)."""
+    """Flows of the pairs (p*step, p*step + 1) of uint8 frames on the GPU (`ops.check_u8_frames`) -> fp32 (P, H, W, 2)."""
     from . import ops
     F, H, W = (int(v) for v in u8.shape[:3])
     P = (F - 2) // step + 1
@@ -172,11 +132,11 @@ def farneback_flows(frames, levels: int = LEVELS, iterations: int = ITERATIONS, 
     consecutive pair of uint8 RGB `frames` (F, H, W, 3) -> fp32 (F-1, H, W, 2) on the GPU.  Grey is COLOR_RGB2GRAY, or with
     `bgr` COLOR_BGR2GRAY of the same bytes (what vdx/metrics.py does).  Frames on the GPU are used where they are."""
     levels, iterations = check_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
-    F, H, W = _check_frames(frames)
+    F, H, W = _frames.check(frames, "flow")
     if F < 2:
         raise VdxError(f"flow: at least two frames are needed, got {F}")
     level_plan(H, W, levels)                                            # the size check, before anything is uploaded
-    u8 = _upload(frames, range(F), _device_of(frames, device))
+    u8 = _frames.on_device(frames, _frames.device_for(frames, device))
     return _flows(u8, levels, iterations, 1, bgr)
 
 
@@ -185,11 +145,11 @@ def temporal_consistency(frames, device=None) -> float:
     of mean |Farneback flow| of the COLOR_RGB2GRAY frames; fewer than two frames -> 0.0 (:336-337)."""
     from . import ops
     levels, iterations = check_params()
-    F, H, W = _check_frames(frames)
+    F, H, W = _frames.check(frames, "flow")
     if F < 2:
         return 0.0
     level_plan(H, W, levels)
-    flows = _flows(_upload(frames, range(F), _device_of(frames, device)), levels, iterations, 1, False)
+    flows = _flows(_frames.on_device(frames, _frames.device_for(frames, device)), levels, iterations, 1, False)
     sums = ops.flow_abs_sum(flows).cpu().numpy()                        # fp32 [F-1]
     scores = sums / np.float32(H * W * 2)                               # np.mean(np.abs(flow)) of a float32 array
     return float(np.mean(scores))
@@ -207,12 +167,12 @@ def warp_pairs(frames, ends: Sequence[int], device=None, want_warped: bool = Fal
     |warp - frame e| over all bytes -> (flows fp32 (P, H, W, 2), sums int64 [P], warped uint8 (P, H, W, 3) or None), on the GPU."""
     from . import ops
     levels, iterations = check_params()
-    F, H, W = _check_frames(frames)
+    F, H, W = _frames.check(frames, "flow")
     level_plan(H, W, levels)
     index = [i for e in ends for i in (e - 1, e)]
     if not index or min(index) < 0 or max(index) >= F:
         raise VdxError(f"flow: boundaries {list(ends)} do not lie inside {F} frames")
-    u8 = _upload(frames, index, _device_of(frames, device))
+    u8 = _frames.on_device(frames, _frames.device_for(frames, device), index)
     flows = _flows(u8, levels, iterations, 2, True)
     sums, warped = ops.flow_remap_absdiff(u8, flows, step=2, want_warped=want_warped)
     return flows, sums, warped
@@ -221,7 +181,7 @@ def warp_pairs(frames, ends: Sequence[int], device=None, want_warped: bool = Fal
 def flow_warp_error(frames, ranges: Sequence[Tuple[int, int]], device=None) -> Optional[float]:
     """The result row's `flow_err` (fsdp_chunked_coherent.py:229-246; vdx/metrics.py `flow_warp_error`, same boundaries, same
     channel handling) on the GPU; None for a single frame or when there is no boundary."""
-    F, H, W = _check_frames(frames)
+    F, H, W = _frames.check(frames, "flow")
     if F <= 1:
         return None
     ends = boundary_pairs(F, ranges)

@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import flow as _flow
+from . import flow as _flow, frames as _frames
 from ._lib import VdxError
 
 MAX_FACTOR = 64
@@ -33,9 +33,8 @@ def check_factor(factor) -> int:
 
 
 def check_frames(frames):
-    """uint8 RGB (F, H, W, 3) or a sequence of (H, W, 3) frames, F >= 1, min(H, W) >= 16 (the flow's own limit) -> (F, H, W);
-    `VdxError` otherwise."""
-    F, H, W = _flow._check_frames(frames)
+    """A uint8 RGB clip (vdx/frames.py), F >= 1, min(H, W) >= 16 (the flow's own limit) -> (F, H, W); `VdxError` otherwise."""
+    F, H, W = _frames.check(frames, "interpolate")
     if F < 1:
         raise VdxError("interpolate: no frames")
     if min(H, W) < _flow.MIN_SIDE:
@@ -53,7 +52,7 @@ def interpolate_frames(frames, factor, device=None) -> torch.Tensor:
     input bytes.  Everything is checked before anything is uploaded or launched."""
     factor = check_factor(factor)
     F, H, W = check_frames(frames)
-    u8 = _flow._upload(frames, range(F), _flow._device_of(frames, device))
+    u8 = _frames.on_device(frames, _frames.device_for(frames, device))
     if factor == 1 or F == 1:
         return u8
     from . import ops

@@ -10,7 +10,7 @@ Metric", CVPR 2018; version 0.1 with the `lin` layers): parity with the package 
 unpinned").  The yardstick of the tests is an fp32 torch-CPU restatement of the same definition (tests/lpips_ref.py).
 
 What it computes, step by step (the same as the reference unless stated):
-  * frames: decoded uint8 RGB (F, H, W, 3), on the GPU or as host arrays.  DEVIATION: the reference re-reads the mp4 with
+  * frames: a decoded uint8 RGB clip in any form vdx/frames.py takes.  DEVIATION: the reference re-reads the mp4 with
     OpenCV (:272-281); here the frames the pipeline decoded are scored directly, as in vdx/clip_score.py;
   * Resize((224, 224)): Pillow's antialiased bilinear resize, bit for bit (`ops.resize_u8(..., "bilinear")`), then
     ((u / 255) - mean) / std in fp32 with the ImageNet statistics (:171-175);
@@ -44,9 +44,8 @@ from typing import Dict, List
 
 import torch
 
-from . import ops, packing
+from . import frames as _frames, ops, packing
 from ._lib import VdxError
-from .clip_score import _frames_tensor
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)            # scoring.py:174
 LPIPS_SHIFT, LPIPS_SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)             # lpips.ScalingLayer
@@ -169,10 +168,10 @@ class LPIPSAlex:
         """uint8 RGB frames (F, H, W, 3) -> the five ReLU taps as fp16 rows [F*S*S][C], S = 55, 27, 13, 13, 13."""
         if not self.w:
             raise VdxError("LPIPSAlex: no weights loaded")
-        t = _frames_tensor(frames, self.device)
-        F = t.shape[0]
+        F = _frames.check(frames, "LPIPSAlex")[0]
         if F == 0:
             raise VdxError("LPIPSAlex.features: no frames")
+        t = _frames.on_device(frames, self.device)
         u8 = ops.resize_u8(t, ops.CLIP_IMAGE, ops.CLIP_IMAGE, "bilinear")
         c1 = ops.gemm(ops.lpips_stem(u8, self.lut), self.w[0], M=F * 55 * 55, bias=self.b[0])
         p1 = ops.relu_maxpool(c1, n_img=F, H=55, W=55)                            # c1 is tap 1 from here on

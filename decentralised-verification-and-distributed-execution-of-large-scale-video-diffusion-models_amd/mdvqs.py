@@ -6,7 +6,7 @@
     InferNet/template/validator/scoring.py:13-67   verify_video_authenticity_common
 
 What it computes, term by term (the same as the reference unless stated):
-  * frames: decoded uint8 RGB (F, H, W, 3), on the GPU or as host arrays.  DEVIATION: every term of the reference re-reads
+  * frames: a decoded uint8 RGB clip in any form vdx/frames.py takes.  DEVIATION: every term of the reference re-reads
     the mp4 with OpenCV; here the frames the pipeline decoded are scored directly (vdx/clip_score.py's deviation).  The
     `*_file` entry points start from the file instead: it is decoded once on the GPU (vdx/video.py) and scored from there;
   * PF, prompt fidelity (:213-267): the CLIP score, `CLIPScorer.score` (vdx/clip_score.py), unchanged;
@@ -42,9 +42,9 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import frames as _frames, ops
 from ._lib import VdxError
-from .clip_score import CLIPScorer, _frames_tensor
+from .clip_score import CLIPScorer
 from .lpips import LPIPSAlex
 
 FARNEBACK = (0.5, 3, 15, 3, 5, 1.2, 0)          # scoring.py:325-327
@@ -76,12 +76,11 @@ def authenticity_from_counts(hist, diff_sums, bytes_per_frame: int) -> Tuple[boo
 
 def verify_video_authenticity(frames, device="cuda") -> Tuple[bool, Dict[str, Optional[float]]]:
     """`verify_video_authenticity_common` (scoring.py:13-67) of uint8 RGB frames (F, H, W, 3) -> (verdict, statistics)."""
-    t = _frames_tensor(frames, torch.device(device))
-    if t.shape[0] == 0:
+    F, H, W = _frames.check(frames, "verify_video_authenticity")
+    if F == 0:
         return authenticity_from_counts(np.zeros((0, 256), np.uint32), np.zeros((0,), np.uint64), 1)
-    hist, diff = ops.frame_stats(t)
-    return authenticity_from_counts(hist.cpu().numpy().view(np.uint32), diff.cpu().numpy().view(np.uint64),
-                                    t.shape[1] * t.shape[2] * 3)
+    hist, diff = ops.frame_stats(_frames.on_device(frames, device))
+    return authenticity_from_counts(hist.cpu().numpy().view(np.uint32), diff.cpu().numpy().view(np.uint64), H * W * 3)
 
 
 def verify_video_authenticity_file(src, device="cuda") -> Tuple[bool, Dict[str, Optional[float]]]:

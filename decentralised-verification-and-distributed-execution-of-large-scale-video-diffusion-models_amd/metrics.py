@@ -77,9 +77,8 @@ def write_video(frames: Sequence[np.ndarray], path: str, fps: float, restart_row
     which are uploaded) are encoded in HIP kernels on it (vdx.video.write_frames): the file the project's own writer leaves,
     byte for byte; the default is the host path."""
     if device is not None:
-        from . import video
-        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.stack(frames)))
-        video.write_frames(path, t.to(device), fps, restart_rows=restart_rows)
+        from . import frames as _frames, video
+        video.write_frames(path, _frames.on_device(frames, device), fps, restart_rows=restart_rows)
         return
     h, w = frames[0].shape[:2]
     if restart_rows > 0:

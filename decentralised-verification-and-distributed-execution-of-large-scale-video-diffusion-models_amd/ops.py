@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import GemmArgs, VdxError
+from .frames import is_packed
 
 PLAIN, CONV3X3, TCONV3 = 0, 1, 2
 EPI_GEGLU = 1
@@ -83,6 +84,23 @@ def _out(out, rows: int, cols: int, like: torch.Tensor, what: str):
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float16, device=like.device)
     return out, _covers(out, rows, cols, what, "out")
+
+
+def check_u8_frames(frames, what):
+    """-> (F, H, W) of a uint8 RGB clip the u8 kernels can read where it lies (vdx/frames.py `is_packed`); `VdxError` otherwise."""
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise VdxError(f"{what}: expected uint8 (F, H, W, 3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)}")
+    F, H, W, _ = frames.shape
+    if F == 0 or H == 0 or W == 0:
+        raise VdxError(f"{what}: empty frames")
+    if not is_packed(frames):
+        raise VdxError(f"{what}: pixels must be packed RGB with non-overlapping rows and frames")
+    return F, H, W
+
+
+def _u8_args(frames):
+    """(pointer, frame pitch, row pitch) of a checked clip, the leading arguments of every u8 entry point; zeros for None."""
+    return (frames.data_ptr(), frames.stride(0), frames.stride(1)) if frames is not None else (None, 0, 0)
 
 
 def _packed(blob, nbytes: int, what: str, packer: str) -> None:
@@ -422,7 +440,7 @@ def clip_preprocess(frames, out=None, return_u8=False):
     """uint8 RGB frames (F, H, W, 3) on the GPU (rows and frames may be pitched; pixels packed) -> the patch-GEMM rows
     fp16 [F*49][3072] of Resize((224, 224)) + ToTensor + Normalize(ImageNet).  `return_u8`: also the resized uint8
     (F, 224, 224, 3) image -> (rows, u8)."""
-    F, H, W = _check_u8_frames(frames, "clip_preprocess")
+    F, H, W = check_u8_frames(frames, "clip_preprocess")
     dev = frames.device
     xb, xk, _ = _clip_table(W, dev)
     yb, yk, yb_host = _clip_table(H, dev)
@@ -435,9 +453,10 @@ def clip_preprocess(frames, out=None, return_u8=False):
     out, ldo = _out(out, F * 49, 3072, frames, "clip_preprocess")
     u8 = torch.empty((F, CLIP_IMAGE, CLIP_IMAGE, 3), dtype=torch.uint8, device=dev) if return_u8 else None
     a = _lib.ClipPreprocessArgs()
-    a.frames, a.out, a.out_u8 = frames.data_ptr(), _p(out, "out"), (u8.data_ptr() if u8 is not None else None)
+    a.frames, a.frame_pitch, a.row_pitch = _u8_args(frames)
+    a.out, a.out_u8 = _p(out, "out"), (u8.data_ptr() if u8 is not None else None)
     a.x_bounds, a.x_coeffs, a.y_bounds, a.y_coeffs = xb.data_ptr(), xk.data_ptr(), yb.data_ptr(), yk.data_ptr()
-    a.frame_pitch, a.row_pitch, a.F, a.H, a.W = frames.stride(0), frames.stride(1), F, H, W
+    a.F, a.H, a.W = F, H, W
     a.kx, a.ky, a.band, a.span, a.ldo = xk.shape[1], yk.shape[1], band, span, ldo
     _launch("vdx_clip_preprocess_u8", C.byref(a))
     return (out, u8) if return_u8 else out
@@ -926,22 +945,11 @@ def _resize_table(in_size: int, out_size: int, filter: str, device):
     return t
 
 
-def _check_u8_frames(frames, what):
-    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise VdxError(f"{what}: expected uint8 (F, H, W, 3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)}")
-    F, H, W, _ = frames.shape
-    if F == 0 or H == 0 or W == 0:
-        raise VdxError(f"{what}: empty frames")
-    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) < 3 * W or frames.stride(0) < frames.stride(1) * H:
-        raise VdxError(f"{what}: pixels must be packed RGB with non-overlapping rows and frames")
-    return F, H, W
-
-
 def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     """uint8 RGB (F, Hi, Wi, 3) on the GPU -> (F, height, width, 3): `PIL.Image.resize((width, height))` bit for bit
     (default filter BICUBIC; 22-bit weights, horizontal pass then vertical, uint8 intermediate).  As in Pillow, a pass whose
     size does not change is skipped (both unchanged: a copy)."""
-    F, Hi, Wi = _check_u8_frames(frames, "resize_u8")
+    F, Hi, Wi = check_u8_frames(frames, "resize_u8")
     if height <= 0 or width <= 0:
         raise VdxError(f"resize_u8: target {height}x{width}")
     dev = frames.device
@@ -952,13 +960,11 @@ def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     if Wi != width:
         mid = out if Hi == height else torch.empty((F, Hi, width, 3), dtype=torch.uint8, device=dev)
         b, k = _resize_table(Wi, width, filter, dev)
-        _launch("vdx_resample_h_u8", src.data_ptr(), src.stride(0), src.stride(1), F, Hi, Wi, b.data_ptr(), k.data_ptr(),
-                k.shape[1], width, mid.data_ptr(), mid.stride(0), mid.stride(1))
+        _launch("vdx_resample_h_u8", *_u8_args(src), F, Hi, Wi, b.data_ptr(), k.data_ptr(), k.shape[1], width, *_u8_args(mid))
         src = mid
     if Hi != height:
         b, k = _resize_table(Hi, height, filter, dev)
-        _launch("vdx_resample_v_u8", src.data_ptr(), src.stride(0), src.stride(1), F, Hi, width, b.data_ptr(), k.data_ptr(),
-                k.shape[1], height, out.data_ptr(), out.stride(0), out.stride(1))
+        _launch("vdx_resample_v_u8", *_u8_args(src), F, Hi, width, b.data_ptr(), k.data_ptr(), k.shape[1], height, *_u8_args(out))
     return out
 
 
@@ -980,14 +986,13 @@ def frames_to_conv_in(frames, out=None):
     """uint8 (F, H, W, 3) on the GPU -> fp16 rows [F*H*W][64]: the im2col operand of the encoder's conv_in (K = tap*3 + c,
     columns 27..63 zero) of the mapped frames (`u8_to_unit_lut`), zero outside the image — the same rows `conv_in` builds
     from the mapped (F, 3, 1, H, W) tensor."""
-    F, H, W = _check_u8_frames(frames, "frames_to_conv_in")
+    F, H, W = check_u8_frames(frames, "frames_to_conv_in")
     dev = frames.device
     lut = _U8_MAP.get(str(dev))
     if lut is None:
         lut = _U8_MAP[str(dev)] = u8_to_unit_lut().to(dev)
     out, ldo = _out(out, F * H * W, 64, frames, "frames_to_conv_in")
-    _launch("vdx_frames_to_conv_in_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, lut.data_ptr(),
-            _p(out, "out"), ldo)
+    _launch("vdx_frames_to_conv_in_u8", *_u8_args(frames), F, H, W, lut.data_ptr(), _p(out, "out"), ldo)
     return out
 
 
@@ -1035,7 +1040,7 @@ LPIPS_STEM_OUT, LPIPS_STEM_K, LPIPS_STEM_KPAD = 55, 363, 384
 def lpips_stem(u8, lut, out=None):
     """Resized uint8 frames (F, 224, 224, 3), contiguous on the GPU, -> conv1's im2col rows fp16 [F*3025][384] through the
     fp16 [3][256] table of both affine maps (`vdx.lpips.stem_lut`); see vdx_lpips_stem_u8."""
-    F, H, W = _check_u8_frames(u8, "lpips_stem")
+    F, H, W = check_u8_frames(u8, "lpips_stem")
     if (H, W) != (CLIP_IMAGE, CLIP_IMAGE) or not u8.is_contiguous():
         raise VdxError(f"lpips_stem: expected contiguous (F, 224, 224, 3) frames, got {tuple(u8.shape)}")
     if lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != u8.device:
@@ -1100,13 +1105,12 @@ def frame_stats(frames):
     """uint8 RGB frames (F, H, W, 3) on the GPU (rows and frames may be pitched) -> (grey histograms int32 [F][256] holding
     the uint32 counts, absolute-difference sums int64 [F-1] holding the uint64 sums); vdx_frame_stats_u8.  torch has no
     arithmetic on unsigned 32 / 64-bit tensors: the counts (< 2^31 for H*W < 2^31) and sums (< 2^63) are read as signed."""
-    F, H, W = _check_u8_frames(frames, "frame_stats")
+    F, H, W = check_u8_frames(frames, "frame_stats")
     if H * W >= 1 << 31:
         raise VdxError("frame_stats: H*W must stay below 2^31")
     hist = torch.empty((F, 256), dtype=torch.int32, device=frames.device)
     diff = torch.empty((max(F - 1, 1),), dtype=torch.int64, device=frames.device)
-    _launch("vdx_frame_stats_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, hist.data_ptr(),
-            diff.data_ptr() if F > 1 else None)
+    _launch("vdx_frame_stats_u8", *_u8_args(frames), F, H, W, hist.data_ptr(), diff.data_ptr() if F > 1 else None)
     return hist, diff[:F - 1]
 
 
@@ -1122,9 +1126,9 @@ def _f32(t, shape, what, name):
 def flow_grey(frames, bgr: bool = False):
     """uint8 RGB frames (F, H, W, 3) on the GPU -> fp32 grey (F, H, W) with OpenCV's 8-bit weights; `bgr`: COLOR_BGR2GRAY
     applied to the same bytes (vdx_flow_grey_u8)."""
-    F, H, W = _check_u8_frames(frames, "flow_grey")
+    F, H, W = check_u8_frames(frames, "flow_grey")
     out = torch.empty((F, H, W), dtype=torch.float32, device=frames.device)
-    _launch("vdx_flow_grey_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), F, H, W, int(bool(bgr)), out.data_ptr())
+    _launch("vdx_flow_grey_u8", *_u8_args(frames), F, H, W, int(bool(bgr)), out.data_ptr())
     return out
 
 
@@ -1202,7 +1206,7 @@ def flow_remap_absdiff(frames, flow, step: int = 1, want_warped: bool = False):
     """uint8 RGB frames (F, H, W, 3) and flows (P, H, W, 2): pair p warps frame p*step by its flow (`cv2.remap`, bilinear,
     constant-0 border) and compares it with frame p*step + 1 -> (int64 [P] sums of |warp - next| over all bytes, the warped
     frames uint8 (P, H, W, 3) or None).  vdx_flow_remap_absdiff_u8."""
-    F, H, W = _check_u8_frames(frames, "flow_remap_absdiff")
+    F, H, W = check_u8_frames(frames, "flow_remap_absdiff")
     if flow.dim() != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (H, W, 2) or flow.device != frames.device:
         raise VdxError(f"flow_remap_absdiff: flow {tuple(flow.shape)} does not match frames {(H, W)}")
     P = flow.shape[0]
@@ -1210,9 +1214,8 @@ def flow_remap_absdiff(frames, flow, step: int = 1, want_warped: bool = False):
         raise VdxError(f"flow_remap_absdiff: {P} pairs of step {step} need more than {F} frames")
     diff = torch.empty((P,), dtype=torch.int64, device=frames.device)
     warped = torch.empty((P, H, W, 3), dtype=torch.uint8, device=frames.device) if want_warped else None
-    _launch("vdx_flow_remap_absdiff_u8", frames.data_ptr(), frames.stride(0), frames.stride(1),
-            _f32(flow, flow.shape, "flow_remap_absdiff", "flow"), P, step, H, W, diff.data_ptr(),
-            warped.data_ptr() if want_warped else None)
+    _launch("vdx_flow_remap_absdiff_u8", *_u8_args(frames), _f32(flow, flow.shape, "flow_remap_absdiff", "flow"), P, step, H, W,
+            diff.data_ptr(), warped.data_ptr() if want_warped else None)
     return diff, warped
 
 
@@ -1223,7 +1226,7 @@ def interp_frames(frames, fab, fba, factor: int, out=None):
     """uint8 RGB frames (F, H, W, 3), F >= 2, and their flows fab (frame i -> i+1) and fba (frame i+1 -> i), fp32 (F-1, H, W, 2),
     all on the GPU -> uint8 ((F-1)*factor + 1, H, W, 3): frame i*factor is frame i, the factor-1 frames after it are the
     motion-compensated blends at k / factor (tests/interp_ref.py states them).  One launch (vdx_interp_frames_u8)."""
-    F, H, W = _check_u8_frames(frames, "interp_frames")
+    F, H, W = check_u8_frames(frames, "interp_frames")
     if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= 64:
         raise VdxError(f"interp_frames: factor must be an integer in 1..64, got {factor!r}")
     if F < 2:
@@ -1238,8 +1241,7 @@ def interp_frames(frames, fab, fba, factor: int, out=None):
     elif (not out.is_cuda or out.device != frames.device or out.dtype != torch.uint8 or tuple(out.shape) != (n_out, H, W, 3)
           or not out.is_contiguous()):
         raise VdxError(f"interp_frames: out must be contiguous uint8 {(n_out, H, W, 3)} on the frames' device")
-    _launch("vdx_interp_frames_u8", frames.data_ptr(), frames.stride(0), frames.stride(1), fab.data_ptr(), fba.data_ptr(), F, H, W,
-            factor, out.data_ptr(), out.stride(0))
+    _launch("vdx_interp_frames_u8", *_u8_args(frames), fab.data_ptr(), fba.data_ptr(), F, H, W, factor, out.data_ptr(), out.stride(0))
     return out
 
 
@@ -1260,8 +1262,8 @@ def compare_tiles(H: int, W: int) -> int:
 def _compare_pair(a, b, what):
     """-> (is_u8, n_planes, H, W) of two uint8 RGB clips (F, H, W, 3) or two packed fp32 plane stacks (n, H, W) on one GPU."""
     if a.dtype == torch.uint8:
-        F, H, W = _check_u8_frames(a, what)
-        if b is not None and (_check_u8_frames(b, what) != (F, H, W) or b.device != a.device):
+        F, H, W = check_u8_frames(a, what)
+        if b is not None and (check_u8_frames(b, what) != (F, H, W) or b.device != a.device):
             raise VdxError(f"{what}: b {tuple(b.shape)} on {b.device} does not match a {tuple(a.shape)} on {a.device}")
         return True, 3 * F, H, W
     if a.dim() != 3 or a.shape[0] < 1:
@@ -1294,8 +1296,7 @@ def compare_ssim_scale(a, b, taps):
     part = torch.empty((n, tiles, 2), dtype=torch.float64, device=a.device)
     if u8:
         sse = torch.empty((n, tiles), dtype=torch.int64, device=a.device)
-        _launch("vdx_compare_ssim_scale_u8", a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), n // 3, H, W,
-                tp, part.data_ptr(), sse.data_ptr())
+        _launch("vdx_compare_ssim_scale_u8", *_u8_args(a), *_u8_args(b), n // 3, H, W, tp, part.data_ptr(), sse.data_ptr())
         return part, sse
     _launch("vdx_compare_ssim_scale_f32", a.data_ptr(), b.data_ptr(), n, H, W, tp, part.data_ptr())
     return part, None
@@ -1310,12 +1311,11 @@ def compare_down2(a, b=None):
         raise VdxError(f"compare_down2: planes of {H}x{W} cannot be halved")
     oa = torch.empty((n, H // 2, W // 2), dtype=torch.float32, device=a.device)
     ob = torch.empty_like(oa) if b is not None else None
-    pb, pob = (b.data_ptr(), ob.data_ptr()) if b is not None else (None, None)
+    pob = ob.data_ptr() if b is not None else None
     if u8:
-        _launch("vdx_compare_down2_u8", a.data_ptr(), a.stride(0), a.stride(1), pb, b.stride(0) if b is not None else 0,
-                b.stride(1) if b is not None else 0, n // 3, H, W, oa.data_ptr(), pob)
+        _launch("vdx_compare_down2_u8", *_u8_args(a), *_u8_args(b), n // 3, H, W, oa.data_ptr(), pob)
     else:
-        _launch("vdx_compare_down2_f32", a.data_ptr(), pb, n, H, W, oa.data_ptr(), pob)
+        _launch("vdx_compare_down2_f32", a.data_ptr(), b.data_ptr() if b is not None else None, n, H, W, oa.data_ptr(), pob)
     return oa if b is None else (oa, ob)
 
 

@@ -386,7 +386,7 @@ class AutoencoderKL(nn.Module):
         fp16; noise (T,4,h,w) fp16 is required for "sample"."""
         if posterior not in ("sample", "mode"):
             raise VdxError(f"encode_frames_u8: posterior must be 'sample' or 'mode', got {posterior!r}")
-        T, H, Wd = ops._check_u8_frames(frames, "encode_frames_u8")
+        T, H, Wd = ops.check_u8_frames(frames, "encode_frames_u8")
         self._check_encode_size(H, Wd)
         h, w = H // 8, Wd // 8
         hw = h * w

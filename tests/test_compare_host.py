@@ -81,9 +81,9 @@ def test_size_refusals():
     (np.zeros((0, 20, 20, 3), np.uint8), np.zeros((0, 20, 20, 3), np.uint8), "no frames"),
 ])
 def test_bad_pairs_are_refused_before_any_upload(a, b, what, monkeypatch):
-    from vdx import compare, flow
+    from vdx import compare, frames
     from vdx._lib import VdxError
-    monkeypatch.setattr(flow, "_upload", lambda *a, **k: pytest.fail("uploaded"))
+    monkeypatch.setattr(frames, "on_device", lambda *a, **k: pytest.fail("uploaded"))
     with pytest.raises(VdxError, match=what):
         compare.compare_frames(a, b, ms_ssim=False)
 

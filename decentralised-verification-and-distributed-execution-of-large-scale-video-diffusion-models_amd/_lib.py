@@ -141,6 +141,9 @@ SIGNATURES = {
     "vdx_compare_down2_u8": (_i, [_vp, _sz, _i, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_compare_down2_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_compare_finalize": (_i, [_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
+    # FreeInit's frequency mix (no reference counterpart; vdx/freeinit.py, csrc/freeinit.hip)
+    "vdx_freeinit_workspace": (_sz, [_i, _i, _i, _i]),
+    "vdx_freeinit_mix_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

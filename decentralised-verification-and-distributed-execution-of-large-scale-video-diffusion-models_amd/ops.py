@@ -1340,3 +1340,64 @@ def compare_finalize(partials, sse_partials, count: int, scale: int, means, sse=
     _launch("vdx_compare_finalize", partials.data_ptr(), sse_partials.data_ptr() if sse is not None else None, F, tiles,
             float(count), int(scale), means.data_ptr(), sse.data_ptr() if sse is not None else None)
     return means
+
+
+# --------------------------------------------------------------------------------------------
+# FreeInit's frequency mix (no reference counterpart; include/vdx.h "FreeInit"; csrc/freeinit.hip).  vdx/freeinit.py builds the
+# filter and calls this.
+FREEINIT_MAX_AXIS, FREEINIT_MAX_ELEMS = 512, 1 << 30
+_FREEINIT_WS: dict = {}     # the complex fp64 workspace of the five launches
+_FREEINIT_TW: dict = {}     # (device, N) -> the axis' twiddle table
+
+
+def freeinit_twiddles(n: int):
+    """The table of an axis of length n: float64 (n, 2) on the host, row j = (cos(2 pi j / n), -sin(2 pi j / n))."""
+    import numpy as np
+    ang = 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+    return torch.from_numpy(np.stack([np.cos(ang), -np.sin(ang)], axis=1))
+
+
+def _freeinit_table(n: int, device) -> torch.Tensor:
+    key = (device.index, n)
+    tw = _FREEINIT_TW.get(key)
+    if tw is None:
+        tw = _FREEINIT_TW[key] = freeinit_twiddles(n).to(device)
+    return tw
+
+
+def freeinit_check_sizes(shape) -> tuple:
+    """(n_vol, T, h, w) of a (B, C, T, h, w) latent the mix takes: every one of T, h, w in 1..512 and at most 2^30 elements;
+    `VdxError` otherwise.  Needs no library."""
+    if len(shape) != 5 or any(int(v) < 1 for v in shape):
+        raise VdxError(f"freeinit_mix: expected a (B, C, T, h, w) latent, got shape {tuple(shape)}")
+    B, Cc, T, h, w = (int(v) for v in shape)
+    if max(T, h, w) > FREEINIT_MAX_AXIS or B * Cc * T * h * w > FREEINIT_MAX_ELEMS:
+        raise VdxError(f"freeinit_mix: {tuple(shape)} is outside what the kernels take (T, h, w in 1..{FREEINIT_MAX_AXIS}, "
+                       f"at most 2^30 elements)")
+    return B * Cc, T, h, w
+
+
+def freeinit_mix(z_t, eta, filt, out=None):
+    """z_t fp16 and eta fp32, both (B, C, T, h, w), and the filter fp32 (T, h, w) in fftshift-ed coordinates, all contiguous on
+    one GPU -> fp16 (B, C, T, h, w): Re ifftn(ifftshift(fftshift(fftn(z_t)) filt + fftshift(fftn(eta)) (1 - filt))) over the
+    last three axes (tests/freeinit_ref.py states it).  Sizes are checked before anything is launched (vdx_freeinit_mix_f16)."""
+    n_vol, T, h, w = freeinit_check_sizes(z_t.shape)
+    if not z_t.is_cuda or z_t.dtype != torch.float16 or not z_t.is_contiguous():
+        raise VdxError(f"freeinit_mix: z_t must be a contiguous fp16 GPU tensor, got {z_t.dtype} on {z_t.device}")
+    for name, t, shape in (("eta", eta, tuple(z_t.shape)), ("filt", filt, (T, h, w))):
+        if t.device != z_t.device or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VdxError(f"freeinit_mix: {name} must be contiguous fp32 {shape} on {z_t.device}, got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device}")
+    if out is None:
+        out = torch.empty_like(z_t)
+    elif out.device != z_t.device or out.dtype != torch.float16 or out.shape != z_t.shape or not out.is_contiguous():
+        raise VdxError(f"freeinit_mix: out must be contiguous fp16 {tuple(z_t.shape)} on {z_t.device}")
+    nbytes = _lib.load().vdx_freeinit_workspace(n_vol, T, h, w)
+    if nbytes == 0:
+        raise VdxError(f"freeinit_mix: the library refuses the size {tuple(z_t.shape)}")
+    with torch.cuda.device(z_t.device):
+        ws = _scratch(_FREEINIT_WS, z_t.device, nbytes, torch.float64)
+        tw = [_freeinit_table(n, z_t.device) for n in (T, h, w)]
+        _launch("vdx_freeinit_mix_f16", z_t.data_ptr(), eta.data_ptr(), filt.data_ptr(), tw[0].data_ptr(), tw[1].data_ptr(),
+                tw[2].data_ptr(), n_vol, T, h, w, ws.data_ptr(), ws.numel() * 8, out.data_ptr())
+    return out

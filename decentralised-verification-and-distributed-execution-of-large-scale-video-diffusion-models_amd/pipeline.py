@@ -66,6 +66,13 @@ class DiffuserConfig:
     gpu_flow: bool = False                 # flow_err (and MD-VQS' TC) from the HIP Farneback kernels instead of the host path
     scheduler: str = "ddim"                # "ddim" | "dpmpp_2m" (DPM-Solver++ 2M, vdx/scheduler.py): the sampler `run_job` uses
     interpolate: int = 1                   # N > 1: write (F-1) N + 1 motion-interpolated frames at fps N (vdx/interp.py); 1 = as always
+    # FreeInit (vdx/freeinit.py; diffusers' enable_free_init, unpinned): sample, noise the blend back to t = 999 with the same
+    # base noise, keep its low frequencies, take the high ones from fresh noise, sample again.  1 = one sampling pass, as always
+    free_init_iters: int = 1
+    free_init_method: str = "butterworth"  # "butterworth" | "gaussian" | "ideal"
+    free_init_spatial: float = 0.25        # stop frequency d_s
+    free_init_temporal: float = 0.25       # stop frequency d_t
+    free_init_order: int = 4               # butterworth only
 
     @property
     def use_fsdp(self):
@@ -112,6 +119,31 @@ def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
     base = torch.randn(*shape, device=nd, dtype=dtype)
     base *= sigma
     return base.to(device)
+
+
+def iteration_noise(shape, iteration: int, device, noise_device=None):
+    """FreeInit's fresh noise of iteration `iteration` >= 1: fp32 N(0, 1) from a generator of its own seeded with the iteration
+    number (seed 0 is `seeded_noise`'s), generated on `noise_device` like the base noise; the global generator is left alone."""
+    nd = torch.device(noise_device) if noise_device is not None else torch.device(device)
+    g = torch.Generator(device=nd).manual_seed(int(iteration))
+    return torch.randn(*shape, generator=g, device=nd, dtype=torch.float32).to(device)
+
+
+def check_free_init(cfg, exchange: str = "allgather") -> int:
+    """`cfg.free_init_iters` when the job can run it; `ValueError` otherwise, before any work: the count is an integer >= 1,
+    and with more than one iteration the filter's arguments are valid, the exchange is "allgather" (every rank must hold the
+    whole blend to re-noise it) and there is no `init_video` (video-to-video starts from a clip, not from noise)."""
+    k = cfg.free_init_iters
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"free_init_iters must be an integer >= 1, got {k!r}")
+    if k > 1:
+        from .freeinit import check_filter_args
+        check_filter_args(cfg.free_init_method, cfg.free_init_spatial, cfg.free_init_temporal, cfg.free_init_order)
+        if exchange == "halo":
+            raise ValueError("free_init_iters > 1 needs exchange=\"allgather\": with \"halo\" no rank holds the whole blended latent")
+        if cfg.init_video is not None:
+            raise ValueError("free_init_iters > 1 and init_video exclude each other: FreeInit re-initialises a start from pure noise")
+    return k
 
 
 SCHEDULERS = ("ddim", "dpmpp_2m")
@@ -386,6 +418,9 @@ class DistributedVideoDiffuser:
         from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
         frame-mean of that start latent.  None: text-to-video, unchanged."""
         self.cfg = cfg
+        if check_free_init(cfg) > 1 and init_latents is not None:
+            raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
+        self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
         self.uncond_emb, self.cond_emb = uncond_emb, cond_emb
@@ -472,6 +507,7 @@ class DistributedVideoDiffuser:
         -> ([(s, e, lat fp32 (1,C,e-s,h,w))], info) — the same bits, 1/world of the blend and decode work.
         `comm` (vdx.comm.Comm): the halo transfers go through the C-ABI RCCL entry point instead of torch.distributed."""
         cfg = self.cfg
+        iters = check_free_init(cfg, exchange)
         T, H, W = cfg.num_frames, cfg.height // 8, cfg.width // 8
         cp = self.plan()
         C = self.unet.config.in_channels
@@ -479,6 +515,8 @@ class DistributedVideoDiffuser:
             start = seeded_noise((1, C, T, H, W), self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
         else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
             start = self._start
+        if iters > 1:
+            return self._call_free_init(start, cp, iters)
         t0 = time.time()
         mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
         if self.world > 1:
@@ -518,6 +556,60 @@ class DistributedVideoDiffuser:
         info["owned"] = [(s, e) for s, e, _ in owned]
         return owned, info
 
+    def _call_free_init(self, base: torch.Tensor, cp: ChunkPlan, iters: int):
+        """`__call__(exchange="allgather")` with `free_init_iters` > 1: denoise -> gather -> blend `iters` times, with
+        `freeinit.reinit` between (vdx/freeinit.py).  Iteration 0 starts from the base noise exactly as a job without the option;
+        the start of iteration i >= 1 is again one tensor for the whole clip that every window slices, computed by every rank
+        for itself from the whole blend it holds (identical bits, no collective); with `hybrid_ctx` its frame-mean is that
+        iteration's context (the rule video-to-video uses for its start latent).  The seconds, bytes and emulated delays in
+        `info` are sums over the iterations; `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`."""
+        from . import freeinit
+        cfg = self.cfg
+        T, H, W = cfg.num_frames, cfg.height // 8, cfg.width // 8
+        C = self.unet.config.in_channels
+        filt = freeinit.lowpass_filter((T, H, W), cfg.free_init_method, cfg.free_init_spatial, cfg.free_init_temporal,
+                                       cfg.free_init_order).to(base.device)
+        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": list(cp.ranges), "world_size": self.world,
+                "num_frames": T, "denoise_s": 0.0, "exchange": "allgather", "steps_run": len(self.scheduler._host_timesteps),
+                "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0, "payload_bytes_actual": 0}
+        rec = {"iters": iters, "method": cfg.free_init_method, "d_s": cfg.free_init_spatial, "d_t": cfg.free_init_temporal,
+               "order": cfg.free_init_order, "denoise_s": [], "reinit_s": []}
+        ctx0, start, starts = self.ctx, base, []
+        try:
+            for it in range(iters):
+                t0 = time.time()
+                mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
+                if self.world > 1:
+                    dist.barrier()
+                self._sync()
+                rec["denoise_s"].append(time.time() - t0)
+                delay = emu_gather_delay_s(sum(t.shape[2] * C * 2 for t in mine), cfg)
+                if delay > 0:
+                    time.sleep(delay)
+                info["emu_gather_delay_s"] += delay
+                t0 = time.time()
+                chunks = gather_chunks(mine, cp, self.rank, self.world)
+                self._sync()
+                info["net_gather_s"] += time.time() - t0
+                info["network_bytes"] += (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2
+                info["payload_bytes"] += sum(t.shape[2] * C * 2 for t in mine)
+                info["payload_bytes_actual"] += sum(t.numel() * 2 for t in mine)
+                lat = self.blend(chunks, start, cp.overlap)
+                if it + 1 < iters:
+                    t0 = time.time()
+                    start = freeinit.reinit(lat, base, self.scheduler, it + 1, filt, cfg.noise_device)
+                    if cfg.use_ctx:
+                        self.ctx = start.mean(dim=2, keepdim=True).contiguous()
+                    self._sync()
+                    rec["reinit_s"].append(time.time() - t0)
+                    starts.append(start)
+        finally:
+            self.ctx = ctx0                                            # the next call's iteration 0 starts as this one did
+        self.free_init_starts = starts
+        info["denoise_s"] = sum(rec["denoise_s"])
+        info["free_init"] = rec
+        return lat, info
+
 
 # ---------------------------------------------------------------------------------------------
 # the job's front end: the reference's `main()` (:279-340) on this build's own driver
@@ -546,7 +638,12 @@ def build_arg_parser():
     (no reference counterpart; both or neither) compares the generated frames with the clip at PATH (a `.npy` of uint8 frames
     or a Motion-JPEG mp4) on rank 0 after the row is written and writes the PSNR / SSIM / MS-SSIM record of vdx/compare.py,
     with the job's chunk ranges (so the means at the seams and away from them) and `"compare_to": PATH`, to OUT; a missing PATH
-    or a `.npy` of another shape is refused before any model is loaded."""
+    or a `.npy` of another shape is refused before any model is loaded.  `--free_init N` (no reference counterpart; diffusers'
+    `enable_free_init`, unpinned) runs N sampling passes, re-initialising the start of each from the blended latent of the one
+    before (vdx/freeinit.py, csrc/freeinit.hip): noised back to t = 999 with the same base noise, its low frequencies kept
+    (`--free_init_method` butterworth | gaussian | ideal, stop frequencies `--free_init_spatial` / `--free_init_temporal`,
+    `--free_init_order`), the high ones from fresh noise; the row's `latency_s` covers all passes; refused with `--exchange halo`
+    and with `--init_video`; `--free_init 1`, the default, is the run without the flag."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -588,6 +685,12 @@ def build_arg_parser():
                    help="sampler: ddim (the reference's, default) or dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality)")
     p.add_argument("--interpolate", type=int, default=1,
                    help="write N - 1 motion-interpolated frames between every two generated ones, at fps * N (1: none, the default)")
+    p.add_argument("--free_init", type=int, default=1,
+                   help="FreeInit: N sampling passes, the start of each re-initialised from the one before (1: none, the default)")
+    p.add_argument("--free_init_method", choices=["butterworth", "gaussian", "ideal"], default="butterworth")
+    p.add_argument("--free_init_spatial", type=float, default=0.25, help="FreeInit: spatial stop frequency d_s")
+    p.add_argument("--free_init_temporal", type=float, default=0.25, help="FreeInit: temporal stop frequency d_t")
+    p.add_argument("--free_init_order", type=int, default=4, help="FreeInit: order of the butterworth filter")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -600,7 +703,9 @@ def config_from_args(a) -> DiffuserConfig:
                           device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
                           out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
                           init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow,
-                          scheduler=a.scheduler, interpolate=a.interpolate)
+                          scheduler=a.scheduler, interpolate=a.interpolate, free_init_iters=a.free_init,
+                          free_init_method=a.free_init_method, free_init_spatial=a.free_init_spatial,
+                          free_init_temporal=a.free_init_temporal, free_init_order=a.free_init_order)
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -715,6 +820,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     from .compat import pynvml_shim
     from .interp import check_factor
     factor = check_factor(cfg.interpolate)      # refused before anything is loaded
+    free_init_iters = check_free_init(cfg, exchange)
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -784,7 +890,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "denoise_s": info["denoise_s"], "exchange": exchange, "rank": d.rank, "synthetic_weights": pipe.synthetic_weights,
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
-            "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written}
+            "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
+            **({"free_init": info["free_init"]} if free_init_iters > 1 else {})}
 
 
 def main(argv=None) -> int:

@@ -619,6 +619,26 @@ int vdx_compare_finalize(const double* partials, const uint64_t* sse_partials, i
                          double* means, uint64_t* sse, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FreeInit's frequency mix (Wu et al. 2023; diffusers' free_init_utils, unpinned) for n_vol = B*C independent volumes of
+ * extent (T, h, w) (nothing in the reference: fsdp_chunked_coherent.py:180-182 samples once from white noise; the job's
+ * --free_init N, vdx/freeinit.py, csrc/freeinit.hip).  tests/freeinit_ref.py states the definition:
+ *   out = fp16( Re ifftn( ifftshift( fftshift(fftn(z_t)) H + fftshift(fftn(eta)) (1 - H) ) ) )   over (T, h, w), in fp32,
+ * computed as eta + Re IDFT3( ifftshift(H) . DFT3(z_t - eta) ) / (T h w) with separable direct DFTs in fp64 (fp32 sums miss
+ * the fp16 rounding of results near zero, where fp16's spacing is 6e-8), one sum per output in a fixed order, no atomics: the same bits on every run, for any n_vol and wherever in the batch a volume lies.
+ * No index or branch depends on the data.  Each of T, h, w in 1..512 (any factorisation), n_vol*T*h*w <= 2^30.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of workspace (one complex fp64 per element); 0 for sizes the kernels do not take.                              */
+size_t vdx_freeinit_workspace(int n_vol, int T, int h, int w);
+/* z_t: fp16 [n_vol][T][h][w]; eta: fp32 of that shape; filt: fp32 [T][h][w], H in fftshift-ed coordinates (the ifftshift is
+ * an index computation in the kernel); tw_t, tw_h, tw_w: fp64 [N][2] on the device for N = T, h, w, entry j =
+ * (cos(2 pi j / N), -sin(2 pi j / N)) evaluated in float64 on the host (indexed by (k n) mod N kept in integers); workspace:
+ * vdx_freeinit_workspace bytes, 16-byte aligned like the tables; out: fp16 [n_vol][T][h][w], may not alias z_t's memory
+ * only in part (out == z_t is allowed: z_t is consumed by the first launch).  Five launches (three when h == 1).          */
+int vdx_freeinit_mix_f16(const void* z_t, const float* eta, const float* filt, const double* tw_t, const double* tw_h,
+                         const double* tw_w, int n_vol, int T, int h, int w, void* workspace, size_t workspace_bytes, void* out,
+                         vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

@@ -7,7 +7,7 @@ context_weight.  Differences in mechanism (results identical):
   * the per-step arithmetic (ctx injection, CFG combine, DDIM step) runs as two fused kernels;
   * denoised chunks stay on the device.  `__call__(exchange="allgather")` — the DEFAULT — keeps the reference's
     everyone-gets-everything semantics (`all_gather_object`, :201) as one fixed-shape `all_gather` and returns the whole
-    blended latent.  `exchange="halo"` returns a DIFFERENT type — the list of (s, e, latent) segments this rank owns:
+    blended latent.  `exchange="halo"` (vdx/halo.py) returns a DIFFERENT type — the list of (s, e, latent) segments this rank owns:
     every frame of the video has ONE owning rank (the rank of the first window that starts at or before it and whose
     successor starts after it); a rank sends only the frames of its windows that another rank owns — the `overlap`
     halo frames, 288 KiB per neighbour at XL size — as fixed-shape point-to-point transfers (RCCL send/recv over xGMI,
@@ -24,14 +24,16 @@ context_weight.  Differences in mechanism (results identical):
 """
 from __future__ import annotations
 
+import json
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
 from . import ops
+from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
 
 
@@ -111,10 +113,15 @@ def _world():
     return 0, 1
 
 
+def _noise_device(device, noise_device=None) -> torch.device:
+    """The device noise is generated on: `noise_device`, or like the reference `device` itself."""
+    return torch.device(device if noise_device is None else noise_device)
+
+
 def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
     """`torch.manual_seed(0); randn(...) * init_noise_sigma` (:180-182).  RNG streams are
     device-specific, so parity runs pass noise_device="cpu" (SURVEY.md §8 a2)."""
-    nd = torch.device(noise_device) if noise_device is not None else torch.device(device)
+    nd = _noise_device(device, noise_device)
     torch.manual_seed(0)
     base = torch.randn(*shape, device=nd, dtype=dtype)
     base *= sigma
@@ -124,7 +131,7 @@ def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
 def iteration_noise(shape, iteration: int, device, noise_device=None):
     """FreeInit's fresh noise of iteration `iteration` >= 1: fp32 N(0, 1) from a generator of its own seeded with the iteration
     number (seed 0 is `seeded_noise`'s), generated on `noise_device` like the base noise; the global generator is left alone."""
-    nd = torch.device(noise_device) if noise_device is not None else torch.device(device)
+    nd = _noise_device(device, noise_device)
     g = torch.Generator(device=nd).manual_seed(int(iteration))
     return torch.randn(*shape, generator=g, device=nd, dtype=torch.float32).to(device)
 
@@ -197,17 +204,6 @@ def load_init_video(path: str):
     return np.ascontiguousarray(arr)
 
 
-def ramp_weights(length: int, ov: int) -> torch.Tensor:
-    """Per-frame blend weights of one chunk (:206-213), built with the same torch calls."""
-    w = torch.ones(length)
-    if ov > 0:
-        ramp = torch.linspace(0, 1, ov)
-        k = min(ov, length)
-        w[:k] = ramp[:k]
-        w[-k:] = torch.flip(ramp[:k], [0])
-    return w
-
-
 def gather_chunks(mine: List[torch.Tensor], chunk_plan: ChunkPlan, rank: int, world: int):
     """Exchange denoised chunks; returns [(s, e, tensor)] in the reference's blend order
     (rank-major, then the rank's own order — `for lst in gathered: for s,e,latc in lst`, :208-209).
@@ -227,187 +223,6 @@ def gather_chunks(mine: List[torch.Tensor], chunk_plan: ChunkPlan, rank: int, wo
     for r in range(world):
         for i, (s, e) in enumerate(chunk_plan.for_rank(r)):
             out.append((s, e, bufs[r][i:i + 1, :, :e - s].contiguous()))
-    return out
-
-
-# ---------------------------------------------------------------------------------------------
-# halo exchange: who owns which frames, who sends what (host logic, integers only)
-# ---------------------------------------------------------------------------------------------
-@dataclass(frozen=True)
-class HaloTransfer:
-    chunk: int          # window index (position in ChunkPlan.ranges) the frames come from
-    src: int            # rank that denoised it
-    dst: int            # rank that owns the frames
-    s: int              # video frames [s, e)
-    e: int
-
-
-@dataclass(frozen=True)
-class HaloSegment:
-    s: int              # video frames [s, e): all covered by the same set of windows
-    e: int
-    chunks: Tuple[int, ...]     # covering window indices in the REFERENCE's accumulation order
-
-
-class HaloPlan:
-    """Frame ownership and transfers for a ChunkPlan.
-
-    Windows come out of the planner with increasing start frames; the tail may repeat the last window
-    (padding, :174-177) and `--mode fsdp` repeats the only window once per rank.  Distinct windows u = 0.. own the
-    frames [start_u, start_{u+1}) (the last one up to T); the owner rank is the rank of the FIRST window with that
-    range.  Every window (repeats included) that covers frames it does not own on its own rank sends them to the
-    owner.  The reference accumulates `full[s:e] += lat * w` window by window in rank-major order (:208-216); frames
-    are independent in that update, so replaying, per owned frame segment, the covering windows in that same order
-    reproduces the reference's bits."""
-
-    def __init__(self, cp: ChunkPlan, total: int):
-        self.cp, self.total = cp, total
-        W = cp.world
-        n = len(cp.ranges)
-        self.rank_of = [i % W for i in range(n)]
-        self.slot_of = [i // W for i in range(n)]                       # position in the rank's own list
-        # reference accumulation order: rank-major, then the rank's own order (:208-209)
-        self.ref_order = sorted(range(n), key=lambda i: (self.rank_of[i], self.slot_of[i]))
-        pos = {c: k for k, c in enumerate(self.ref_order)}
-        uniq: List[int] = []
-        for i, r in enumerate(cp.ranges):
-            if not uniq or r != cp.ranges[uniq[-1]]:
-                if uniq and r[0] <= cp.ranges[uniq[-1]][0]:
-                    raise ValueError(f"window starts must increase: {cp.ranges}")
-                uniq.append(i)
-        self.owner_chunks = uniq
-        self.owned: dict = {}                                            # rank -> [(s, e)] frames it owns
-        self.segments: dict = {}                                         # rank -> [HaloSegment]
-        self.transfers: List[HaloTransfer] = []
-        for k, i in enumerate(uniq):
-            s0 = cp.ranges[i][0]
-            e0 = cp.ranges[uniq[k + 1]][0] if k + 1 < len(uniq) else total
-            if k == 0:
-                s0 = 0
-            if e0 <= s0:
-                continue
-            owner = self.rank_of[i]
-            self.owned.setdefault(owner, []).append((s0, e0))
-            cover = [j for j, (s, e) in enumerate(cp.ranges) if s < e0 and e > s0]
-            cuts = sorted({s0, e0} | {x for j in cover for x in cp.ranges[j] if s0 < x < e0})
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                cs_ = tuple(sorted((j for j in cover if cp.ranges[j][0] <= a and cp.ranges[j][1] >= b), key=pos.get))
-                self.segments.setdefault(owner, []).append(HaloSegment(a, b, cs_))
-            for j in cover:
-                if self.rank_of[j] != owner:
-                    self.transfers.append(HaloTransfer(j, self.rank_of[j], owner, max(cp.ranges[j][0], s0),
-                                                       min(cp.ranges[j][1], e0)))
-        self.transfers.sort(key=lambda t: (t.chunk, t.s))
-        for r in range(W):
-            self.owned.setdefault(r, [])
-            self.segments.setdefault(r, [])
-
-    def bytes_sent(self, rank: int, frame_bytes: int) -> int:
-        return sum((t.e - t.s) * frame_bytes for t in self.transfers if t.src == rank)
-
-
-def exchange_halos(mine: List[torch.Tensor], hp: HaloPlan, rank: int, side_stream=None, comm=None):
-    """Send the frames other ranks own, receive the frames this rank owns from the windows other ranks denoised.
-    Returns ({(chunk, s, e): tensor (1,C,e-s,H,W)}, event or None): the received pieces are valid on the current
-    stream after `event.wait()` (GPU) or immediately (CPU).  `comm` (a `vdx.comm.Comm`): the transfers go through the
-    C-ABI entry point `vdx_halo_exchange` (RCCL send/recv), one grouped send + receive per neighbour.  (Executed with
-    more than one rank on no machine this build had: a one-GPU box cannot host two RCCL ranks.)"""
-    cp = hp.cp
-    ref = mine[0]
-    _, C, _, H, W = ref.shape
-    got, p2p, keep, native = {}, [], [], []
-    for t in hp.transfers:
-        if t.src == rank:
-            s0 = cp.ranges[t.chunk][0]
-            piece = mine[hp.slot_of[t.chunk]][:, :, t.s - s0:t.e - s0].contiguous()
-            keep.append(piece)
-            p2p.append(dist.P2POp(dist.isend, piece, t.dst))
-            native.append((piece, t.dst, None, -1))
-        elif t.dst == rank:
-            buf = ref.new_empty((1, C, t.e - t.s, H, W))
-            got[(t.chunk, t.s, t.e)] = buf
-            p2p.append(dist.P2POp(dist.irecv, buf, t.src))
-            native.append((None, -1, buf, t.src))
-    if not p2p:
-        return got, None
-    if ref.is_cuda and comm is not None:
-        cur = torch.cuda.current_stream(ref.device)
-        side = side_stream or torch.cuda.Stream(device=ref.device, priority=-1)   # own hardware queue: vdx/shard.py on `_side`
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        side.wait_event(ready)
-        # one grouped send + receive per neighbour and call (include/vdx.h), neighbours in ascending order: with every
-        # rank walking its pairs in that order the pairs are met in one global (lexicographic) order — no cycle of waits
-        per_peer = {}
-        for snd, to, rcv, frm in native:
-            ent = per_peer.setdefault(to if snd is not None else frm, ([], []))
-            (ent[0] if snd is not None else ent[1]).append(snd if snd is not None else rcv)
-        for peer in sorted(per_peer):
-            snds, rcvs = per_peer[peer]
-            for k in range(max(len(snds), len(rcvs))):
-                comm.halo(snds[k] if k < len(snds) else None, peer if k < len(snds) else -1,
-                          rcvs[k] if k < len(rcvs) else None, peer if k < len(rcvs) else -1, side)
-        done = torch.cuda.Event()
-        done.record(side)
-        for t_ in keep + list(got.values()):
-            t_.record_stream(side)
-        return got, done
-    if ref.is_cuda and dist.get_backend() == "gloo":
-        # rehearsal of a multi-rank job whose ranks share one GPU: gloo has no device transport for send / recv, so
-        # the pieces are staged through host memory (the product's transport is RCCL, below / above)
-        host = {id(op.tensor): op.tensor.cpu() for op in p2p}
-        for r in dist.batch_isend_irecv([dist.P2POp(op.op, host[id(op.tensor)], op.peer) for op in p2p]):
-            r.wait()
-        for buf in got.values():
-            buf.copy_(host[id(buf)])
-        return got, None
-    if ref.is_cuda:
-        cur = torch.cuda.current_stream(ref.device)
-        side = side_stream or torch.cuda.Stream(device=ref.device, priority=-1)   # own hardware queue: vdx/shard.py on `_side`
-        ready = torch.cuda.Event()
-        ready.record(cur)                                   # pieces / buffers exist once `cur` gets here
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            for r in dist.batch_isend_irecv(p2p):
-                r.wait()
-            done = torch.cuda.Event()
-            done.record(side)
-        for t_ in keep + list(got.values()):
-            t_.record_stream(side)
-        return got, done
-    for r in dist.batch_isend_irecv(p2p):
-        r.wait()
-    return got, None
-
-
-def blend_owned(mine: List[torch.Tensor], hp: HaloPlan, got: dict, done, like: torch.Tensor, rank: int):
-    """Blend the frames this rank owns (reference :204-217 restricted to them).  Segments whose covering windows
-    are all local are accumulated while the halo transfers are still in flight; the others after `done`.
-    Returns [(s, e, fp32 latent (1,C,e-s,H,W))] for the owned ranges, in frame order."""
-    cp, ov = hp.cp, hp.cp.overlap
-    out = []
-    for (o_s, o_e) in hp.owned[rank]:
-        n = o_e - o_s
-        full = like.new_zeros((1, like.shape[1], n, like.shape[3], like.shape[4]))
-        weight = torch.zeros(n, dtype=torch.float32, device=like.device)
-        segs = [g for g in hp.segments[rank] if o_s <= g.s and g.e <= o_e]
-        local = lambda g: all(hp.rank_of[c] == rank for c in g.chunks)    # noqa: E731
-        waited = done is None
-        for g in sorted(segs, key=lambda g: (not local(g), g.s)):
-            if not local(g) and not waited:
-                torch.cuda.current_stream(like.device).wait_event(done)
-                waited = True
-            for c in g.chunks:
-                cs_, ce_ = cp.ranges[c]
-                if hp.rank_of[c] == rank:
-                    piece = mine[hp.slot_of[c]][:, :, g.s - cs_:g.e - cs_]
-                else:
-                    key = next(k for k in got if k[0] == c and k[1] <= g.s and g.e <= k[2])
-                    piece = got[key][:, :, g.s - key[1]:g.e - key[1]]
-                w = ramp_weights(ce_ - cs_, ov)[g.s - cs_:g.e - cs_]
-                ops.blend_accumulate(full, weight, piece.contiguous(), w.contiguous().to(like.device),
-                                     g.s - o_s, g.e - o_s)
-        out.append((o_s, o_e, ops.blend_finalize(full, weight)))
     return out
 
 
@@ -432,9 +247,8 @@ class DistributedVideoDiffuser:
         self.init_latents = init_latents
         self.timesteps = None                                         # video-to-video only: the truncated schedule
         self._start = None
+        shape = self.latent_shape if init_latents is not None or cfg.use_ctx else None
         if init_latents is not None:
-            C = unet.config.in_channels
-            shape = (1, C, cfg.num_frames, cfg.height // 8, cfg.width // 8)
             if tuple(init_latents.shape) != shape:
                 raise ValueError(f"init_latents {tuple(init_latents.shape)} != {shape}")
             self.timesteps = vid2vid_timesteps(scheduler, cfg.steps, cfg.strength)
@@ -443,16 +257,24 @@ class DistributedVideoDiffuser:
             if cfg.use_ctx:                                           # the frame-mean of the whole clip's start latent
                 self.ctx = self._start.mean(dim=2, keepdim=True).contiguous()
         elif cfg.use_ctx:                                             # reference :105-127
-            C = unet.config.in_channels
-            shape = (1, C, cfg.num_frames, cfg.height // 8, cfg.width // 8)
             if self.rank == 0:
                 full = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
                 ctx = full.mean(dim=2, keepdim=True)
             else:
-                ctx = torch.empty((1, C, 1, shape[3], shape[4]), device=cfg.device, dtype=torch.float16)
+                ctx = torch.empty(shape[:2] + (1,) + shape[3:], device=cfg.device, dtype=torch.float16)
             if self.world > 1:
                 dist.broadcast(ctx, src=0)
             self.ctx = ctx.contiguous()
+
+    @property
+    def latent_shape(self) -> Tuple[int, int, int, int, int]:
+        cfg = self.cfg
+        return (1, self.unet.config.in_channels, cfg.num_frames, cfg.height // 8, cfg.width // 8)
+
+    @property
+    def schedule(self) -> List[int]:
+        """The timesteps this job runs: the scheduler's, or video-to-video's truncated ones."""
+        return self.scheduler._host_timesteps if self.timesteps is None else self.timesteps
 
     def denoise(self, lat: torch.Tensor) -> torch.Tensor:
         """Reference `_denoise` (:129-143) for one chunk."""
@@ -462,7 +284,7 @@ class DistributedVideoDiffuser:
         reset = getattr(sched, "reset", None)
         if reset is not None:       # a multistep scheduler must not carry the previous chunk's history into this one
             reset()
-        for t in (sched._host_timesteps if self.timesteps is None else self.timesteps):
+        for t in self.schedule:
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb).sample
             lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale)
@@ -481,9 +303,6 @@ class DistributedVideoDiffuser:
             ops.blend_accumulate(full, weight, lat.contiguous(), ramp_weights(e - s, ov).to(like.device), s, e)
         return ops.blend_finalize(full, weight)
 
-    def blend_owned(self, mine, hp, got, done, like):
-        return blend_owned(mine, hp, got, done, like, self.rank)
-
     def decode_frames(self, lat: torch.Tensor, vae, batch: int = 8) -> List:
         """Reference :219-225: the blended latent (1,C,T,h,w) -> T uint8 (H,W,3) frames (numpy, host).
         `z/0.18215` is formed in the latent's dtype and cast to fp16 at the VAE boundary (what the reference's
@@ -501,103 +320,81 @@ class DistributedVideoDiffuser:
         if torch.device(self.cfg.device).type == "cuda":
             torch.cuda.synchronize()
 
-    def __call__(self, exchange: str = "allgather", comm=None):
-        """exchange="allgather": every rank ends with the whole blended latent (reference semantics, :201-217)
-        -> (lat fp32 (1,C,T,h,w), info).  exchange="halo": a rank ends with the frames it owns
-        -> ([(s, e, lat fp32 (1,C,e-s,h,w))], info) — the same bits, 1/world of the blend and decode work.
-        `comm` (vdx.comm.Comm): the halo transfers go through the C-ABI RCCL entry point instead of torch.distributed."""
-        cfg = self.cfg
-        iters = check_free_init(cfg, exchange)
-        T, H, W = cfg.num_frames, cfg.height // 8, cfg.width // 8
-        cp = self.plan()
-        C = self.unet.config.in_channels
-        if self._start is None:
-            start = seeded_noise((1, C, T, H, W), self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
-        else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
-            start = self._start
-        if iters > 1:
-            return self._call_free_init(start, cp, iters)
+    def _round(self, start: torch.Tensor, cp: ChunkPlan, exchange: str, comm):
+        """One sampling round from the whole clip's start latent `start`: denoise this rank's windows, exchange, blend
+        -> (the blend: the latent, or with "halo" the owned segments; that round's seconds and bytes, under `info`'s names)."""
+        _, C, T, H, W = start.shape
         t0 = time.time()
         mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
         if self.world > 1:
             dist.barrier()
         self._sync()
         denoise_s = time.time() - t0
-        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": list(cp.ranges), "world_size": self.world,
-                "num_frames": T, "denoise_s": denoise_s, "exchange": exchange,
-                "steps_run": len(self.scheduler._host_timesteps if self.timesteps is None else self.timesteps)}
-        payload_ref = sum(t.shape[2] * C * 2 for t in mine)                 # the reference's `payload_bytes` (:194)
-        delay = emu_gather_delay_s(payload_ref, cfg)                        # :195-199, outside the timed gather like there
+        # `payload_bytes = sum((e-s) * in_channels * 2 ...)` (:194) — frames x channels x 2 bytes WITHOUT the h x w extent: the
+        # value the reference's CSV column `network_bytes` carries (its executed rows: tests/golden/ref_exec_planner.json);
+        # the bytes a rank's chunk list really has are `payload_bytes_actual`
+        payload = sum(t.shape[2] * C * 2 for t in mine)
+        delay = emu_gather_delay_s(payload, self.cfg)                       # :195-199, outside the timed gather like there
         if delay > 0:
             time.sleep(delay)
-        info["emu_gather_delay_s"] = delay
         t0 = time.time()
         if exchange == "allgather":
             chunks = gather_chunks(mine, cp, self.rank, self.world)
             self._sync()
-            info["net_gather_s"] = time.time() - t0
-            info["network_bytes"] = (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2    # received per rank
-            info["payload_bytes"] = sum(t.shape[2] * C * 2 for t in mine)          # the reference's formula (:194), see below
-            info["payload_bytes_actual"] = sum(t.numel() * 2 for t in mine)
-            return self.blend(chunks, start, cp.overlap), info
-        if exchange != "halo":
-            raise ValueError(f"unknown exchange {exchange!r}")
-        hp = HaloPlan(cp, T)
-        got, done = exchange_halos(mine, hp, self.rank, comm=comm) if self.world > 1 else ({}, None)
-        owned = self.blend_owned(mine, hp, got, done, start)
-        self._sync()
-        info["net_gather_s"] = time.time() - t0
-        info["network_bytes"] = sum(t.numel() * 2 for t in got.values())
-        # `payload_bytes = sum((e-s) * in_channels * 2 ...)` (:194) — frames x channels x 2 bytes WITHOUT the h x w extent: the
-        # value the reference's CSV column `network_bytes` carries (its executed rows: tests/golden/ref_exec_planner.json);
-        # the bytes a rank's chunk list really has are `payload_bytes_actual`
-        info["payload_bytes"] = sum(t.shape[2] * C * 2 for t in mine)
-        info["payload_bytes_actual"] = sum(t.numel() * 2 for t in mine)
-        info["owned"] = [(s, e) for s, e, _ in owned]
-        return owned, info
+            net_gather_s = time.time() - t0
+            received = (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2
+            out = self.blend(chunks, start, cp.overlap)
+        else:
+            hp = HaloPlan(cp, T)
+            got, done = exchange_halos(mine, hp, self.rank, comm=comm) if self.world > 1 else ({}, None)
+            out = blend_owned(mine, hp, got, done, start, self.rank)
+            self._sync()
+            net_gather_s = time.time() - t0
+            received = sum(t.numel() * 2 for t in got.values())
+        return out, {"denoise_s": denoise_s, "emu_gather_delay_s": delay, "net_gather_s": net_gather_s, "network_bytes": received,
+                     "payload_bytes": payload, "payload_bytes_actual": sum(t.numel() * 2 for t in mine)}
 
-    def _call_free_init(self, base: torch.Tensor, cp: ChunkPlan, iters: int):
-        """`__call__(exchange="allgather")` with `free_init_iters` > 1: denoise -> gather -> blend `iters` times, with
-        `freeinit.reinit` between (vdx/freeinit.py).  Iteration 0 starts from the base noise exactly as a job without the option;
-        the start of iteration i >= 1 is again one tensor for the whole clip that every window slices, computed by every rank
-        for itself from the whole blend it holds (identical bits, no collective); with `hybrid_ctx` its frame-mean is that
-        iteration's context (the rule video-to-video uses for its start latent).  The seconds, bytes and emulated delays in
-        `info` are sums over the iterations; `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`."""
-        from . import freeinit
+    def __call__(self, exchange: str = "allgather", comm=None):
+        """exchange="allgather": every rank ends with the whole blended latent (reference semantics, :201-217)
+        -> (lat fp32 (1,C,T,h,w), info).  exchange="halo": a rank ends with the frames it owns
+        -> ([(s, e, lat fp32 (1,C,e-s,h,w))], info) — the same bits, 1/world of the blend and decode work.
+        `comm` (vdx.comm.Comm): the halo transfers go through the C-ABI RCCL entry point instead of torch.distributed.
+
+        `free_init_iters` > 1 ("allgather" only): that many rounds, with `freeinit.reinit` between (vdx/freeinit.py).  Iteration
+        0 starts from the base noise exactly as a job without the option; the start of iteration i >= 1 is again one tensor for
+        the whole clip that every window slices, computed by every rank for itself from the whole blend it holds (identical
+        bits, no collective); with `hybrid_ctx` its frame-mean is that iteration's context (the rule video-to-video uses for its
+        start latent).  The seconds, bytes and emulated delays in `info` are then sums over the iterations, and
+        `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`."""
         cfg = self.cfg
-        T, H, W = cfg.num_frames, cfg.height // 8, cfg.width // 8
-        C = self.unet.config.in_channels
-        filt = freeinit.lowpass_filter((T, H, W), cfg.free_init_method, cfg.free_init_spatial, cfg.free_init_temporal,
-                                       cfg.free_init_order).to(base.device)
+        iters = check_free_init(cfg, exchange)
+        if exchange not in ("allgather", "halo"):
+            raise ValueError(f"unknown exchange {exchange!r}")
+        cp = self.plan()
+        if self._start is None:
+            base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+        else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
+            base = self._start
         info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": list(cp.ranges), "world_size": self.world,
-                "num_frames": T, "denoise_s": 0.0, "exchange": "allgather", "steps_run": len(self.scheduler._host_timesteps),
+                "num_frames": cfg.num_frames, "denoise_s": 0.0, "exchange": exchange, "steps_run": len(self.schedule),
                 "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0, "payload_bytes_actual": 0}
-        rec = {"iters": iters, "method": cfg.free_init_method, "d_s": cfg.free_init_spatial, "d_t": cfg.free_init_temporal,
-               "order": cfg.free_init_order, "denoise_s": [], "reinit_s": []}
+        if iters > 1:
+            from . import freeinit
+            filt = freeinit.lowpass_filter(base.shape[2:], cfg.free_init_method, cfg.free_init_spatial, cfg.free_init_temporal,
+                                           cfg.free_init_order).to(base.device)
+            rec = {"iters": iters, "method": cfg.free_init_method, "d_s": cfg.free_init_spatial, "d_t": cfg.free_init_temporal,
+                   "order": cfg.free_init_order, "denoise_s": [], "reinit_s": []}
         ctx0, start, starts = self.ctx, base, []
         try:
             for it in range(iters):
-                t0 = time.time()
-                mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
-                if self.world > 1:
-                    dist.barrier()
-                self._sync()
-                rec["denoise_s"].append(time.time() - t0)
-                delay = emu_gather_delay_s(sum(t.shape[2] * C * 2 for t in mine), cfg)
-                if delay > 0:
-                    time.sleep(delay)
-                info["emu_gather_delay_s"] += delay
-                t0 = time.time()
-                chunks = gather_chunks(mine, cp, self.rank, self.world)
-                self._sync()
-                info["net_gather_s"] += time.time() - t0
-                info["network_bytes"] += (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2
-                info["payload_bytes"] += sum(t.shape[2] * C * 2 for t in mine)
-                info["payload_bytes_actual"] += sum(t.numel() * 2 for t in mine)
-                lat = self.blend(chunks, start, cp.overlap)
+                out, spent = self._round(start, cp, exchange, comm)
+                for k, v in spent.items():
+                    info[k] += v
+                if iters > 1:
+                    rec["denoise_s"].append(spent["denoise_s"])
                 if it + 1 < iters:
                     t0 = time.time()
-                    start = freeinit.reinit(lat, base, self.scheduler, it + 1, filt, cfg.noise_device)
+                    start = freeinit.reinit(out, base, self.scheduler, it + 1, filt, cfg.noise_device)
                     if cfg.use_ctx:
                         self.ctx = start.mean(dim=2, keepdim=True).contiguous()
                     self._sync()
@@ -605,10 +402,12 @@ class DistributedVideoDiffuser:
                     starts.append(start)
         finally:
             self.ctx = ctx0                                            # the next call's iteration 0 starts as this one did
-        self.free_init_starts = starts
-        info["denoise_s"] = sum(rec["denoise_s"])
-        info["free_init"] = rec
-        return lat, info
+        if iters > 1:
+            self.free_init_starts = starts
+            info["free_init"] = rec
+        if exchange == "halo":
+            info["owned"] = [(s, e) for s, e, _ in out]
+        return out, info
 
 
 # ---------------------------------------------------------------------------------------------
@@ -697,15 +496,13 @@ def build_arg_parser():
     return p
 
 
+FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None}     # where the flag's name is not the field's; None: no flag
+
+
 def config_from_args(a) -> DiffuserConfig:
-    return DiffuserConfig(num_frames=a.num_frames, steps=a.steps, guidance_scale=a.guidance_scale, chunk_size=a.chunk_size,
-                          overlap=a.overlap, height=a.height, width=a.width, mode=a.mode, context_weight=a.context_weight,
-                          device=a.device, noise_device=a.noise_device, model_id=a.model_id, prompt=a.prompt, fps=a.fps,
-                          out_csv=a.out_csv, emu_bw_mbps=a.emu_bw_mbps, emu_rtt_ms=a.emu_rtt_ms, emu_jitter_ms=a.emu_jitter_ms,
-                          init_video=a.init_video, strength=a.strength, posterior=a.posterior, gpu_flow=a.gpu_flow,
-                          scheduler=a.scheduler, interpolate=a.interpolate, free_init_iters=a.free_init,
-                          free_init_method=a.free_init_method, free_init_spatial=a.free_init_spatial,
-                          free_init_temporal=a.free_init_temporal, free_init_order=a.free_init_order)
+    """The parsed flags as a `DiffuserConfig`: every field that has a flag takes that flag's value."""
+    flag_of = {f.name: FLAG_OF_FIELD.get(f.name, f.name) for f in fields(DiffuserConfig)}
+    return DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -797,7 +594,7 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev):
         frames = ops.resize_u8(frames, cfg.height, cfg.width)
     noise = None
     if cfg.posterior == "sample":
-        nd = torch.device(cfg.noise_device) if cfg.noise_device is not None else dev
+        nd = _noise_device(dev, cfg.noise_device)
         g = torch.Generator(device=nd).manual_seed(1)
         noise = torch.randn((cfg.num_frames, 4, cfg.height // 8, cfg.width // 8), generator=g, device=nd,
                             dtype=torch.float16).to(dev)
@@ -872,8 +669,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             to_write, fps = interpolate_frames(frames, factor, device=dev), cfg.fps * factor
             if not gpu_video_write:
                 to_write = list(to_write.cpu().numpy())
-        metrics.write_video(to_write, out_video, fps, **({"restart_rows": video_restart_rows} if video_restart_rows else {}),
-                            **({"device": dev} if gpu_video_write else {}))
+        metrics.write_video(to_write, out_video, fps, restart_rows=video_restart_rows, device=dev if gpu_video_write else None)
         frames_written = len(to_write)
     delay = emu_reduce_delay_s(cfg)             # :257-258
     if delay > 0:
@@ -894,6 +690,12 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {})}
 
 
+def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
+    """One of `main`'s JSON records."""
+    with open(path, "w") as f:
+        f.write(dumps(rec))
+
+
 def main(argv=None) -> int:
     """`python -m vdx.pipeline [the reference's flags]` (one process, or under torchrun like the reference's script): runs the
     job and appends the reference's CSV row (:313-333) to `--out_csv` on rank 0."""
@@ -909,8 +711,7 @@ def main(argv=None) -> int:
     if a.score_from_file and not a.out_video:
         raise ValueError("--score_from_file needs --out_video")
     res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs,
-                  **({"video_restart_rows": a.video_restart_rows} if a.video_restart_rows else {}),
-                  **({"gpu_video_write": True} if a.gpu_video_write else {}))
+                  video_restart_rows=a.video_restart_rows, gpu_video_write=a.gpu_video_write)
     if res["rank"] == 0:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
@@ -924,25 +725,18 @@ def main(argv=None) -> int:
             source = {"source": "file"}
         if a.clip_json:
             # scored after the row took its latency and memory readings: the row is that of a run without --clip_json
-            import json
             rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
-            rec.update(source)
-            with open(a.clip_json, "w") as f:
-                json.dump(rec, f, indent=1)
+            write_record(a.clip_json, {**rec, **source})
         if a.mdvqs_json:
             # likewise after the row: MD-VQS (its optical flow runs on the CPU unless --gpu_flow) never shows in `latency_s`
-            import json
             rec = mdvqs_record(clip_inputs["frames"], cfg.prompt, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
                                clip_inputs["device"], **({"flow": "gpu"} if a.gpu_flow else {}))
-            rec.update(source)
-            with open(a.mdvqs_json, "w") as f:
-                json.dump(rec, f, indent=1)
+            write_record(a.mdvqs_json, {**rec, **source})
         if a.compare_to:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            with open(a.compare_json, "w") as f:
-                f.write(compare.dumps(rec))
+            write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
     return 0

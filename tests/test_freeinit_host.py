@@ -161,3 +161,109 @@ def test_iteration_noise_is_seeded_by_the_iteration_and_leaves_the_global_genera
     assert a.dtype == torch.float32 and torch.equal(a, a2) and not torch.equal(a, b)
     base = seeded_noise((1, 4, 3, 5, 6), 1.0, "cpu", "cpu")
     assert not torch.equal(a.half(), base)                                 # the fresh noise is not the base noise again
+
+
+# ---- the round accounting of `DistributedVideoDiffuser.__call__`, on the CPU (tests/test_halo_host.py's arrangement) -----------
+from test_halo_host import cpu_blend  # noqa: E402,F401  (the fixture: ops.blend_* as their torch-CPU statements)
+
+T, CS, OV = 10, 6, 2                                                       # the smallest job with a seam and a ramp
+
+
+def _stub(lat):              # stands in for the UNet + scheduler steps: any deterministic function of the chunk's content
+    x = lat.float()
+    return (0.5 * x + 0.25 * torch.roll(x, 1, dims=2) - 0.1 * x.mean(dim=2, keepdim=True)).half()
+
+
+def _blend_of_stub(start):
+    from oracle.pipeline_ref import plan_chunks, ramp_blend
+    _, o, ranges = plan_chunks(T, 1, CS, OV, False)
+    return ramp_blend([(s, e, _stub(start[:, :, s:e].clone())) for s, e in ranges], T, o, start)
+
+
+class _Unet:                 # only .config.in_channels is used outside denoise()
+    class config:
+        in_channels = 4
+    W = None
+
+
+def _diffuser(monkeypatch, iters, fail_at=None):
+    """-> (the diffuser, reinit's calls [(z0, iteration, returned)], the context of every denoise call, the filters built)."""
+    import vdx.freeinit
+    from vdx.pipeline import DiffuserConfig, DistributedVideoDiffuser
+    from vdx.scheduler import DDIMScheduler
+    cfg = DiffuserConfig(num_frames=T, steps=2, chunk_size=CS, overlap=OV, height=32, width=32, mode="hybrid_ctx", device="cpu",
+                         noise_device="cpu", free_init_iters=iters)
+    d = DistributedVideoDiffuser(cfg, _Unet(), DDIMScheduler(), None, None)
+    reinits, ctxs, filters = [], [], []
+
+    def denoise(lat):
+        if len(ctxs) == fail_at:
+            raise RuntimeError("denoise failed")
+        ctxs.append(d.ctx.clone())
+        return _stub(lat)
+
+    def reinit(z0, base, scheduler, iteration, filt, noise_device=None):
+        out = (0.5 * z0.float() + 0.25 * base.float() + iteration).half()
+        reinits.append((z0.clone(), iteration, out))
+        return out
+
+    real_filter = vdx.freeinit.lowpass_filter
+    d.denoise = denoise
+    monkeypatch.setattr(vdx.freeinit, "reinit", reinit)
+    monkeypatch.setattr(vdx.freeinit, "lowpass_filter", lambda *a: filters.append(a) or real_filter(*a))
+    return d, reinits, ctxs, filters
+
+
+BYTES = ("network_bytes", "payload_bytes", "payload_bytes_actual")
+
+
+def test_rounds_are_summed_and_the_context_follows_the_start_latent(cpu_blend, monkeypatch):  # noqa: F811
+    from vdx.pipeline import seeded_noise
+    base = seeded_noise((1, 4, T, 4, 4), 1.0, "cpu", "cpu")
+    d1, reinits, ctxs, filters = _diffuser(monkeypatch, 1)
+    lat1, info1 = d1()
+    assert torch.equal(lat1, _blend_of_stub(base))
+    assert "free_init" not in info1 and reinits == [] and filters == [] and d1.free_init_starts == []
+    windows = len(info1["ranges"])
+    assert len(ctxs) == windows == 3                                       # (0, 6), (4, 10) and the reference's tail (8, 10)
+
+    d2, reinits, ctxs, filters = _diffuser(monkeypatch, 2)
+    ctx0 = d2.ctx
+    assert torch.equal(ctx0, base.mean(dim=2, keepdim=True))
+    lat2, info2 = d2()
+    rec = info2["free_init"]
+    assert set(info2) == set(info1) | {"free_init"}
+    assert [info2[k] for k in BYTES] == [2 * info1[k] for k in BYTES] and info1["payload_bytes"] == (6 + 6 + 2) * 4 * 2
+    assert len(rec["denoise_s"]) == 2 and len(rec["reinit_s"]) == 1 and info2["denoise_s"] == sum(rec["denoise_s"])
+    assert len(filters) == 1 and len(reinits) == 1
+    z0, iteration, start = reinits[0]
+    assert iteration == 1 and torch.equal(z0, lat1)                        # once, with the first round's blend
+    assert len(ctxs) == 2 * windows
+    assert all(torch.equal(c, ctx0) for c in ctxs[:windows])
+    assert all(torch.equal(c, start.mean(dim=2, keepdim=True)) for c in ctxs[windows:])
+    assert torch.equal(lat2, _blend_of_stub(start))
+    assert len(d2.free_init_starts) == 1 and d2.free_init_starts[0] is start
+    assert d2.ctx is ctx0
+
+
+def test_a_round_that_raises_leaves_the_context_and_the_recorded_starts_alone(cpu_blend, monkeypatch):  # noqa: F811
+    d, reinits, ctxs, _ = _diffuser(monkeypatch, 2, fail_at=3)             # the first denoise call of the second round
+    ctx0, before = d.ctx, ["the last call's"]
+    d.free_init_starts = before
+    with pytest.raises(RuntimeError, match="denoise failed"):
+        d()
+    assert len(reinits) == 1 and len(ctxs) == 3
+    assert d.ctx is ctx0 and d.free_init_starts is before
+
+
+def test_one_halo_round_reports_the_owned_ranges(cpu_blend, monkeypatch):  # noqa: F811
+    from vdx.pipeline import seeded_noise
+    d, reinits, _, filters = _diffuser(monkeypatch, 1)
+    owned, info = d(exchange="halo")
+    assert info["owned"] == [(s, e) for s, e, _ in owned] and "free_init" not in info and reinits == [] and filters == []
+    edges = sorted(info["owned"])
+    assert edges[0][0] == 0 and edges[-1][1] == T and all(a[1] == b[0] for a, b in zip(edges[:-1], edges[1:]))
+    want = _blend_of_stub(seeded_noise((1, 4, T, 4, 4), 1.0, "cpu", "cpu"))
+    assert all(torch.equal(lat, want[:, :, s:e]) for s, e, lat in owned)
+    allgather_info = d()[1]
+    assert set(info) == set(allgather_info) | {"owned"} and [info[k] for k in BYTES] == [allgather_info[k] for k in BYTES]

@@ -22,7 +22,8 @@ def test_owned_blend_bits_at_cfg5_full_size(gpu):
 
 def _owned_blend_case(gpu, T, W, cs, ov, nc, C, H, Wd):
     import vdx  # noqa: F401
-    from vdx.pipeline import DiffuserConfig, DistributedVideoDiffuser, HaloPlan, blend_owned
+    from vdx.halo import HaloPlan, blend_owned
+    from vdx.pipeline import DiffuserConfig, DistributedVideoDiffuser
     from vdx.planner import plan
     from oracle.pipeline_ref import ramp_blend
     cp = plan(T, W, cs, ov, no_chunking=nc)

@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 import vdx  # noqa: E402,F401
 from vdx import ops, pipeline  # noqa: E402
-from vdx.pipeline import HaloPlan, blend_owned  # noqa: E402
+from vdx.halo import HaloPlan, blend_owned  # noqa: E402
 from vdx.planner import PlannerError, plan  # noqa: E402
 from oracle.pipeline_ref import ramp_blend  # noqa: E402
 

@@ -144,6 +144,9 @@ SIGNATURES = {
     # FreeInit's frequency mix (no reference counterpart; vdx/freeinit.py, csrc/freeinit.hip)
     "vdx_freeinit_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_freeinit_mix_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    # FreeU's skip filter and backbone scale (no reference counterpart; unet3d.py enable_freeu, csrc/freeu.hip)
+    "vdx_freeu_filter_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
+    "vdx_freeu_scale_f16": (_i, [_vp, _i, _sz, _i, _f, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

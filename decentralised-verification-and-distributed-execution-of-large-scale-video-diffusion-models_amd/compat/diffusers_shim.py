@@ -227,6 +227,14 @@ class DiffusionPipeline:
             m.to(device)
         return self
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' pipeline-level `enable_freeu(s1, s2, b1, b2)`: the UNet's (vdx/unet3d.py; `pipe.unet.enable_freeu` is the
+        same switch)."""
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     def decode_latents(self, latents):
         """`fsdp.py:172` relies on this pipeline helper of older diffusers releases: latents (1,C,F,h,w) -> video
         (1,3,F,H,W) float32 in [-1, 1] scale of the decoder (the caller maps to uint8)."""

@@ -1401,3 +1401,76 @@ def freeinit_mix(z_t, eta, filt, out=None):
         _launch("vdx_freeinit_mix_f16", z_t.data_ptr(), eta.data_ptr(), filt.data_ptr(), tw[0].data_ptr(), tw[1].data_ptr(),
                 tw[2].data_ptr(), n_vol, T, h, w, ws.data_ptr(), ws.numel() * 8, out.data_ptr())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# FreeU's two operations on the up path's rows (no reference counterpart; include/vdx.h "FreeU"; csrc/freeu.hip).
+# unet3d.py calls both, in place, before the ResNets of up blocks 0 and 1.
+_FREEU_TW: dict = {}        # (device, N) -> the axis' twiddle table
+
+
+def freeu_twiddles(n: int):
+    """The table of an axis of length n: float64 (n, 2) on the host, row j = (cos(2 pi j / n), -sin(2 pi j / n)); the
+    multiples of a quarter turn are exact (numpy's sin(pi) is 1.2e-16)."""
+    import numpy as np
+    ang = 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+    tw = np.stack([np.cos(ang), -np.sin(ang)], axis=1)
+    for j in range(n):
+        if 4 * j % n == 0:
+            tw[j] = ((1.0, 0.0), (0.0, -1.0), (-1.0, 0.0), (0.0, 1.0))[4 * j // n]
+    return torch.from_numpy(tw)
+
+
+def _freeu_table(n: int, device) -> torch.Tensor:
+    key = (device.index, n)
+    tw = _FREEU_TW.get(key)
+    if tw is None:
+        tw = _FREEU_TW[key] = freeu_twiddles(n).to(device)
+    return tw
+
+
+def _freeu_number(what: str, v, positive: bool) -> float:
+    import math
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (positive and v <= 0):
+        raise ValueError(f"{what} must be a finite{' positive' if positive else ''} number, got {v!r}")
+    return float(v)
+
+
+def _freeu_ptr(t, name: str) -> int:
+    """`_p`, except that the one column of a [M][1] matrix has no stride to speak of."""
+    return _p(t.as_strided(t.shape, (t.stride(0), 1)) if t.dim() == 2 and t.shape[1] == 1 else t, name)
+
+
+def freeu_filter(x, *, n_img, h, w, s, out=None):
+    """x fp16 rows [n_img * h * w][C], image i owning rows [i h w, (i + 1) h w) -> the rows with every (h, w) plane through
+    diffusers' fourier_filter(threshold=1, scale=s): Re ifft2(ifftshift(fftshift(fft2(plane)) M)), M = s on the 2 x 2 centre
+    (tests/freeu_ref.py states it), computed in fp64 and rounded once.  `out=x` filters in place."""
+    s = _freeu_number("freeu_filter: s", s, False)
+    M, C, ldx = _rows(x, "x")
+    if n_img < 1 or h < 1 or w < 1 or C < 1 or M != n_img * h * w:
+        raise VdxError(f"freeu_filter: {M} rows are not {n_img} images of {h} x {w}")
+    out, ldo = _out(out, M, C, x, "freeu_filter")
+    if out.shape[0] != M or out.shape[1] != C:
+        raise VdxError(f"freeu_filter: out {tuple(out.shape)} != {(M, C)}")
+    if out.data_ptr() != x.data_ptr() or ldo != ldx:
+        lo, hi = x.data_ptr(), x.data_ptr() + ((M - 1) * ldx + C) * 2
+        if out.data_ptr() < hi and lo < out.data_ptr() + ((M - 1) * ldo + C) * 2:
+            raise VdxError("freeu_filter: out overlaps x without being x")
+    px, po = _freeu_ptr(x, "x"), _freeu_ptr(out, "out")
+    with torch.cuda.device(x.device):
+        _launch("vdx_freeu_filter_f16", px, ldx, _freeu_table(h, x.device).data_ptr(), _freeu_table(w, x.device).data_ptr(),
+                n_img, h, w, C, s, po, ldo)
+    return out
+
+
+def freeu_scale(x, b):
+    """x fp16 rows [M][C], IN PLACE: channels [0, C // 2) of every row become fp16(fp32(x) fp32(b)), torch's half-by-scalar
+    multiply; the other channels are not touched.  -> x."""
+    b = _freeu_number("freeu_scale: b", b, True)
+    M, C, ld = _rows(x, "x")
+    if M < 1 or C < 1:
+        raise VdxError(f"freeu_scale: empty rows {tuple(x.shape)}")
+    px = _freeu_ptr(x, "x")
+    with torch.cuda.device(x.device):
+        _launch("vdx_freeu_scale_f16", px, ld, M, C, b)
+    return x

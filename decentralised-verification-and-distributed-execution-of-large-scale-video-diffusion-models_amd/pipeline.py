@@ -75,6 +75,9 @@ class DiffuserConfig:
     free_init_spatial: float = 0.25        # stop frequency d_s
     free_init_temporal: float = 0.25       # stop frequency d_t
     free_init_order: int = 4               # butterworth only
+    # FreeU (UNet3DConditionModel.enable_freeu; diffusers' enable_freeu, unpinned): (b1, b2, s1, s2), the backbone factors and the
+    # skip filter's scales of up blocks 0 and 1, on every denoising step of the job.  None = off, as always
+    freeu: Optional[Tuple[float, float, float, float]] = None
 
     @property
     def use_fsdp(self):
@@ -151,6 +154,20 @@ def check_free_init(cfg, exchange: str = "allgather") -> int:
         if cfg.init_video is not None:
             raise ValueError("free_init_iters > 1 and init_video exclude each other: FreeInit re-initialises a start from pure noise")
     return k
+
+
+def check_freeu(cfg) -> Optional[dict]:
+    """`cfg.freeu` as {"b1", "b2", "s1", "s2"} (None when off); `ValueError` before any work unless it is four finite numbers
+    with b1, b2 > 0 (s may be any finite number: 0 removes the band)."""
+    if cfg.freeu is None:
+        return None
+    v = tuple(cfg.freeu) if isinstance(cfg.freeu, (tuple, list)) else ()
+    if len(v) != 4:
+        raise ValueError(f"freeu must be four numbers (b1, b2, s1, s2), got {cfg.freeu!r}")
+    rec = {}
+    for name, x, positive in zip(("b1", "b2", "s1", "s2"), v, (True, True, False, False)):
+        rec[name] = ops._freeu_number(f"freeu: {name}", x, positive)
+    return rec
 
 
 SCHEDULERS = ("ddim", "dpmpp_2m")
@@ -233,6 +250,7 @@ class DistributedVideoDiffuser:
         from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
         frame-mean of that start latent.  None: text-to-video, unchanged."""
         self.cfg = cfg
+        check_freeu(cfg)
         if check_free_init(cfg) > 1 and init_latents is not None:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
@@ -365,9 +383,14 @@ class DistributedVideoDiffuser:
         the whole clip that every window slices, computed by every rank for itself from the whole blend it holds (identical
         bits, no collective); with `hybrid_ctx` its frame-mean is that iteration's context (the rule video-to-video uses for its
         start latent).  The seconds, bytes and emulated delays in `info` are then sums over the iterations, and
-        `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`."""
+        `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`.
+
+        `freeu` (every exchange, mode and scheduler, every FreeInit iteration): the UNet samples with
+        `enable_freeu(s1, s2, b1, b2)` for the length of the call and is handed back in the state it came in; `info["freeu"]`
+        holds the four values."""
         cfg = self.cfg
         iters = check_free_init(cfg, exchange)
+        freeu = check_freeu(cfg)
         if exchange not in ("allgather", "halo"):
             raise ValueError(f"unknown exchange {exchange!r}")
         cp = self.plan()
@@ -385,6 +408,10 @@ class DistributedVideoDiffuser:
             rec = {"iters": iters, "method": cfg.free_init_method, "d_s": cfg.free_init_spatial, "d_t": cfg.free_init_temporal,
                    "order": cfg.free_init_order, "denoise_s": [], "reinit_s": []}
         ctx0, start, starts = self.ctx, base, []
+        if freeu is not None:
+            freeu0 = self.unet.freeu
+            self.unet.enable_freeu(**freeu)
+            info["freeu"] = freeu
         try:
             for it in range(iters):
                 out, spent = self._round(start, cp, exchange, comm)
@@ -402,6 +429,8 @@ class DistributedVideoDiffuser:
                     starts.append(start)
         finally:
             self.ctx = ctx0                                            # the next call's iteration 0 starts as this one did
+            if freeu is not None:
+                self.unet.enable_freeu(**freeu0) if freeu0 is not None else self.unet.disable_freeu()
         if iters > 1:
             self.free_init_starts = starts
             info["free_init"] = rec
@@ -442,7 +471,11 @@ def build_arg_parser():
     before (vdx/freeinit.py, csrc/freeinit.hip): noised back to t = 999 with the same base noise, its low frequencies kept
     (`--free_init_method` butterworth | gaussian | ideal, stop frequencies `--free_init_spatial` / `--free_init_temporal`,
     `--free_init_order`), the high ones from fresh noise; the row's `latency_s` covers all passes; refused with `--exchange halo`
-    and with `--init_video`; `--free_init 1`, the default, is the run without the flag."""
+    and with `--init_video`; `--free_init 1`, the default, is the run without the flag.  `--freeu B1 B2 S1 S2` (no reference
+    counterpart; diffusers' `enable_freeu(s1, s2, b1, b2)`, unpinned) samples every step of the job, whatever the mode, exchange,
+    scheduler and the other options, with FreeU in the UNet's up blocks 0 and 1 (vdx/unet3d.py `enable_freeu`, csrc/freeu.hip):
+    the first half of the hidden state's channels times B, the skip tensors' lowest frequencies times S; the result and the
+    JSON records then carry `"freeu": {"b1", "b2", "s1", "s2"}`; without the flag the run is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -490,6 +523,8 @@ def build_arg_parser():
     p.add_argument("--free_init_spatial", type=float, default=0.25, help="FreeInit: spatial stop frequency d_s")
     p.add_argument("--free_init_temporal", type=float, default=0.25, help="FreeInit: temporal stop frequency d_t")
     p.add_argument("--free_init_order", type=int, default=4, help="FreeInit: order of the butterworth filter")
+    p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
+                   help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -502,7 +537,10 @@ FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None}     # whe
 def config_from_args(a) -> DiffuserConfig:
     """The parsed flags as a `DiffuserConfig`: every field that has a flag takes that flag's value."""
     flag_of = {f.name: FLAG_OF_FIELD.get(f.name, f.name) for f in fields(DiffuserConfig)}
-    return DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
+    cfg = DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
+    if cfg.freeu is not None:
+        cfg.freeu = tuple(cfg.freeu)
+    return cfg
 
 
 def clip_score_record(frames, prompt: str, clip_model: Optional[str], pipe_tokenizer, device) -> dict:
@@ -618,6 +656,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     from .interp import check_factor
     factor = check_factor(cfg.interpolate)      # refused before anything is loaded
     free_init_iters = check_free_init(cfg, exchange)
+    freeu = check_freeu(cfg)
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -687,7 +726,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
-            **({"free_init": info["free_init"]} if free_init_iters > 1 else {})}
+            **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {})}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -716,13 +755,13 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {}
+        source = {"freeu": res["freeu"]} if "freeu" in res else {}
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
             from .video import read_frames
             clip_inputs["frames"] = read_frames(a.out_video, device=clip_inputs["device"])[0]
-            source = {"source": "file"}
+            source = {**source, "source": "file"}
         if a.clip_json:
             # scored after the row took its latency and memory readings: the row is that of a run without --clip_json
             rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
@@ -736,6 +775,8 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
+            if "freeu" in res:
+                rec["freeu"] = res["freeu"]
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -89,6 +89,35 @@ class UNet3DConditionModel(nn.Module):
         self.detect_cfg_duplicate = False      # untagged batch of two: COMPARE the halves on the device (one kernel + a host sync) before sharing
         self._text_ref = None                  # (encoder_hidden_states object, its version, (B, device), padded copy)
         self._text_kv: Dict[str, tuple] = {}   # cross-attention K / V^T of that text, per transformer
+        self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
+
+    # ------------------------------------------------------------------------------------------
+    # FreeU (Si et al. 2023; diffusers' enable_freeu / disable_freeu, unpinned; csrc/freeu.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' `enable_freeu(s1, s2, b1, b2)`: from the next forward on, before EACH ResNet of up block 0 (b1, s1) and of up
+        block 1 (b2, s2), the first half of the hidden state's channels is multiplied by b (`ops.freeu_scale`) and the skip tensor
+        about to be concatenated goes through `fourier_filter(threshold=1, scale=s)` (`ops.freeu_filter`); every other block is
+        untouched.  b must be finite and positive, s finite (0 is allowed): `ValueError` otherwise, and the state stays as it
+        was.  The forward keeps no plan of its launches: nothing else has to be invalidated."""
+        vals = {}
+        for name, v, positive in (("s1", s1, False), ("s2", s2, False), ("b1", b1, True), ("b2", b2, True)):
+            vals[name] = ops._freeu_number(f"enable_freeu: {name}", v, positive)
+        self._freeu = ((vals["b1"], vals["s1"]), (vals["b2"], vals["s2"]))
+        return self
+
+    def disable_freeu(self):
+        """diffusers' `disable_freeu()`: the forward is again the one without FreeU, launch for launch."""
+        self._freeu = None
+        return self
+
+    @property
+    def freeu(self) -> Optional[Dict[str, float]]:
+        """{"b1", "b2", "s1", "s2"} while FreeU is enabled, else None."""
+        if self._freeu is None:
+            return None
+        (b1, s1), (b2, s2) = self._freeu
+        return {"b1": b1, "b2": b2, "s1": s1, "s2": s2}
 
     # ------------------------------------------------------------------------------------------
     # weights
@@ -733,6 +762,12 @@ class UNet3DConditionModel(nn.Module):
                     raise VdxError("skip connection resolution mismatch")
                 if shared_skip and not skips:
                     skip = torch.cat([skip, skip])          # transformer_in's output stood for both items (one 2 x 141 MB copy at 24 frames)
+                if self._freeu is not None and i < 2:
+                    # FreeU, in place: both tensors are this loop's to consume (`owned` below), and every kernel that read the
+                    # skip tensor on the way down was enqueued on this stream before
+                    fb, fs = self._freeu[i]
+                    ops.freeu_scale(x, fb)
+                    ops.freeu_filter(skip, n_img=n_img, h=hh, w=ww, s=fs, out=skip)
                 owned = [x, skip]
                 x = skip = None
                 x = self._resnet(f"{p}.resnets.{j}", owned, None, temb_all, n_img, F, hh, ww)

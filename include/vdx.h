@@ -639,6 +639,27 @@ int vdx_freeinit_mix_f16(const void* z_t, const float* eta, const float* filt, c
                          vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FreeU (Si et al. 2023; diffusers' enable_freeu(s1, s2, b1, b2), unpinned) on the UNet's rows [n_img][H W][C] fp16 (nothing
+ * in the reference: it never touches the up path; UNet3DConditionModel.enable_freeu, the job's --freeu, csrc/freeu.hip).
+ * tests/freeu_ref.py states the definition.  No atomics, one fixed summation order per plane: the same bits on every run and
+ * for any n_img.  No index or branch depends on the data: NaN and inf stay inside their plane.
+ * ------------------------------------------------------------------------------------------ */
+/* The skip filter, diffusers' fourier_filter(threshold = 1, scale = s), per image and channel plane (H, W):
+ *   out = fp16( Re ifft2( ifftshift( fftshift(fft2(x)) M ) ) ),   M = 1 except M[H/2-1 : H/2+1, W/2-1 : W/2+1] = s
+ * computed as x + (s - 1) / (H W) Re sum X(ky, kx) e^{+2 pi i (ky y / H + kx x / W)} over ky in {0, H - 1}, kx in {0, W - 1}
+ * (one frequency on an axis of length 1) with the at most four coefficients X summed in fp64, the correction added in fp64
+ * and one rounding to fp16; an element whose fp64 result equals its input keeps its bits (s = 1: the identity).
+ * x, out: fp16 rows of stride ldx, ldo >= C elements, image i owns rows [i H W, (i + 1) H W); out == x is allowed, any other
+ * overlap is not.  tw_h, tw_w: fp64 [N][2] on the device for N = H, W, entry j = (cos(2 pi j / N), -sin(2 pi j / N))
+ * evaluated in float64 on the host, 16-byte aligned.  Any n_img, H, W, C >= 1; s finite.  One launch.                      */
+int vdx_freeu_filter_f16(const void* x, int ldx, const double* tw_h, const double* tw_w, int n_img, int H, int W, int C, double s,
+                         void* out, int ldo, vdx_stream_t stream);
+/* The backbone scale, in place: x[r][c] = fp16(fp32(x[r][c]) fp32(b)) for c < C / 2 of every row (torch's half-by-scalar
+ * multiply); channels >= C / 2 are not touched.  x: fp16 rows of stride ld >= C; b finite and positive.  One launch, none
+ * for C = 1.                                                                                                              */
+int vdx_freeu_scale_f16(void* x, int ld, size_t rows, int C, float b, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

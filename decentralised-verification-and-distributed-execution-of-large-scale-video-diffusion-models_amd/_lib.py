@@ -144,6 +144,11 @@ SIGNATURES = {
     # FreeInit's frequency mix (no reference counterpart; vdx/freeinit.py, csrc/freeinit.hip)
     "vdx_freeinit_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_freeinit_mix_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    # temporal co-denoising: window input and the fused whole-clip steps (no reference counterpart; vdx/codenoise.py, csrc/codenoise.hip)
+    "vdx_cfg_input_window_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
+                                         _vp]),
     # FreeU's skip filter and backbone scale (no reference counterpart; unet3d.py enable_freeu, csrc/freeu.hip)
     "vdx_freeu_filter_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
     "vdx_freeu_scale_f16": (_i, [_vp, _i, _sz, _i, _f, _vp]),

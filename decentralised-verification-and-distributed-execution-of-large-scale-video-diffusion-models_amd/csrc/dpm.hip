@@ -15,42 +15,7 @@
 #include <cstdint>
 
 #include "vdx_common.h"
-
-// fp32 -> fp16 as its own rounding step (elementwise.hip `rn16`): no v_fma_mixlo_f16 fusion with the op before it.
-__device__ __forceinline__ f16 rn16(float x) {
-    asm volatile("" : "+v"(x));
-    return (f16)x;
-}
-
-struct dpm_coef {
-    float gs, s0, inv_a0, cx, d0, d1, inv_r0;
-};
-
-template <bool CFG, bool O2>
-__device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
-    f16 g;
-    if (CFG) {
-        const f16 t1 = rn16(__fsub_rn(c, u));                     // c - u
-        const f16 t2 = rn16(__fmul_rn(k.gs, (float)t1));          // gs * (c - u)
-        g = rn16(__fadd_rn(u, (float)t2));                        // u + gs*(c-u)
-    } else {
-        g = (f16)u;
-    }
-    const f16 a1 = rn16(__fmul_rn(k.s0, (float)g));               // s0 * e
-    const f16 a2 = rn16(__fsub_rn(x, (float)a1));                 // x - s0*e
-    const f16 x0 = rn16(__fmul_rn((float)a2, k.inv_a0));          // / a0
-    const f16 A = rn16(__fmul_rn(k.cx, x));                       // (st/s0) * x
-    const f16 B = rn16(__fmul_rn(k.d0, (float)x0));               // -(at*(exp(-h)-1)) * x0
-    f16 r = rn16(__fadd_rn((float)A, (float)B));
-    if (O2) {
-        const f16 dx = rn16(__fsub_rn((float)x0, x0p));           // x0 - x0_prev
-        const f16 d1 = rn16(__fmul_rn(k.inv_r0, (float)dx));      // D1 = (1/r0) * (x0 - x0_prev)
-        const f16 C = rn16(__fmul_rn(k.d1, (float)d1));           // -(0.5*at*(exp(-h)-1)) * D1
-        r = rn16(__fadd_rn((float)r, (float)C));
-    }
-    x0_out = x0;
-    out = r;
-}
+#include "step_chains.h"   // rn16, dpm_coef, dpm_elem: shared with codenoise.hip
 
 // 8 halves of the conditional half of eps2, which starts n halves behind a 16-byte boundary: one 16-byte load where n is a
 // multiple of 8 (`al`, the same for every lane), else element by element.  Every other pointer is 16-byte aligned (checked).

@@ -7,14 +7,7 @@
 // injection and blend are bit-exact against the CPU oracle; for the DDIM step torch-CPU differs
 // from torch-GPU in exactly those two rules (oracle/ddim_ref.py `step_gpu_rules` restates them).
 #include "vdx_common.h"
-
-// fp32 -> fp16 as its own rounding step: the empty asm keeps hipcc from fusing the preceding fp32
-// op and this conversion into v_fma_mixlo_f16 (one rounding), so results match torch's
-// "compute in fp32, then cast" for fp16 tensors bit for bit.
-__device__ __forceinline__ f16 rn16(float x) {
-    asm volatile("" : "+v"(x));
-    return (f16)x;
-}
+#include "step_chains.h"   // rn16 and the CFG + DDIM chain, shared with codenoise.hip
 
 // ---- conv_in gather: (B,Cin,F,H,W) latent -> im2col rows [B*F*H*W][Kpad], K = (ky*3+kx)*Cin + ci
 // (zero padded to Kpad, a multiple of 64) so conv_in runs on the MFMA GEMM like every other conv.
@@ -158,17 +151,9 @@ extern "C" int vdx_cfg_input_f16(const void* lat, const void* ctx, float weight,
 // DDIMScheduler.step with fp32 0-d coefficients and fp16 tensors: every tensor op rounds to fp16.
 __global__ void cfg_ddim_kernel(const f16* eps2, const f16* lat, f16* out, float gs, float s1, float sa,
                                 float sp, float s1p, size_t n) {
+    const ddim_coef k = {gs, s1, sa, sp, s1p};
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float u = (float)eps2[i], c = (float)eps2[n + i], x = (float)lat[i];
-        const f16 t1 = rn16(__fsub_rn(c, u));                 // c - u
-        const f16 t2 = rn16(__fmul_rn(gs, (float)t1));        // gs * (c - u)
-        const f16 g = rn16(__fadd_rn(u, (float)t2));          // u + gs*(c-u)
-        const f16 a1 = rn16(__fmul_rn(s1, (float)g));         // sqrt(1-a_t) * eps
-        const f16 a2 = rn16(__fsub_rn(x, (float)a1));         // sample - ...
-        const f16 x0 = rn16(__fmul_rn((float)a2, sa));        // * (1/sqrt(a_t)): torch-GPU divides by a CPU scalar this way
-        const f16 d = rn16(__fmul_rn(s1p, (float)g));         // sqrt(1-a_prev) * eps
-        const f16 b1 = rn16(__fmul_rn(sp, (float)x0));        // sqrt(a_prev) * x0
-        out[i] = rn16(__fadd_rn((float)b1, (float)d));
+        out[i] = cfg_ddim_elem((float)eps2[i], (float)eps2[n + i], (float)lat[i], k);   // step_chains.h
     }
 }
 extern "C" int vdx_cfg_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, float guidance,

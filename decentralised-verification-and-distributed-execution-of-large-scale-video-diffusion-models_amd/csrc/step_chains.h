@@ -1,0 +1,64 @@
+// step_chains.h — the per-element rounding chains of the fused CFG + sampler steps, written once: elementwise.hip
+// (`vdx_cfg_ddim_step_f16`), dpm.hip (`vdx_cfg_dpm_step_f16`, `vdx_dpm_step_f16`) and codenoise.hip (the co-denoising steps,
+// which feed the same chains a fused noise) all call these, so the three cannot drift apart.  Every function is
+// __forceinline__: a kernel that calls one compiles to the instructions it had when the chain was written in its loop.
+#pragma once
+#include "vdx_common.h"
+
+// fp32 -> fp16 as its own rounding step: the empty asm keeps hipcc from fusing the preceding fp32
+// op and this conversion into v_fma_mixlo_f16 (one rounding), so results match torch's
+// "compute in fp32, then cast" for fp16 tensors bit for bit.
+__device__ __forceinline__ f16 rn16(float x) {
+    asm volatile("" : "+v"(x));
+    return (f16)x;
+}
+
+// ---- fsdp_chunked_coherent.py:141-142 -------------------------------------------------------
+//   u, c = noise.chunk(2);  lat = sched.step(u + gs*(c-u), t, lat).prev_sample     (DDIM, eta 0)
+// DDIMScheduler.step with fp32 0-d coefficients and fp16 tensors: every tensor op rounds to fp16.
+// `sa` is 1/sqrt(a_t): torch-GPU divides by a CPU scalar by multiplying with its reciprocal.
+struct ddim_coef {
+    float gs, s1, sa, sp, s1p;
+};
+__device__ __forceinline__ f16 cfg_ddim_elem(float u, float c, float x, const ddim_coef& k) {
+    const f16 t1 = rn16(__fsub_rn(c, u));                 // c - u
+    const f16 t2 = rn16(__fmul_rn(k.gs, (float)t1));      // gs * (c - u)
+    const f16 g = rn16(__fadd_rn(u, (float)t2));          // u + gs*(c-u)
+    const f16 a1 = rn16(__fmul_rn(k.s1, (float)g));       // sqrt(1-a_t) * eps
+    const f16 a2 = rn16(__fsub_rn(x, (float)a1));         // sample - ...
+    const f16 x0 = rn16(__fmul_rn((float)a2, k.sa));      // * (1/sqrt(a_t)): torch-GPU divides by a CPU scalar this way
+    const f16 d = rn16(__fmul_rn(k.s1p, (float)g));       // sqrt(1-a_prev) * eps
+    const f16 b1 = rn16(__fmul_rn(k.sp, (float)x0));      // sqrt(a_prev) * x0
+    return rn16(__fadd_rn((float)b1, (float)d));
+}
+
+// ---- DPM-Solver++ (2M, midpoint): dpm.hip's header states the expression ----------------------
+struct dpm_coef {
+    float gs, s0, inv_a0, cx, d0, d1, inv_r0;
+};
+
+template <bool CFG, bool O2>
+__device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
+    f16 g;
+    if (CFG) {
+        const f16 t1 = rn16(__fsub_rn(c, u));                     // c - u
+        const f16 t2 = rn16(__fmul_rn(k.gs, (float)t1));          // gs * (c - u)
+        g = rn16(__fadd_rn(u, (float)t2));                        // u + gs*(c-u)
+    } else {
+        g = (f16)u;
+    }
+    const f16 a1 = rn16(__fmul_rn(k.s0, (float)g));               // s0 * e
+    const f16 a2 = rn16(__fsub_rn(x, (float)a1));                 // x - s0*e
+    const f16 x0 = rn16(__fmul_rn((float)a2, k.inv_a0));          // / a0
+    const f16 A = rn16(__fmul_rn(k.cx, x));                       // (st/s0) * x
+    const f16 B = rn16(__fmul_rn(k.d0, (float)x0));               // -(at*(exp(-h)-1)) * x0
+    f16 r = rn16(__fadd_rn((float)A, (float)B));
+    if (O2) {
+        const f16 dx = rn16(__fsub_rn((float)x0, x0p));           // x0 - x0_prev
+        const f16 d1 = rn16(__fmul_rn(k.inv_r0, (float)dx));      // D1 = (1/r0) * (x0 - x0_prev)
+        const f16 C = rn16(__fmul_rn(k.d1, (float)d1));           // -(0.5*at*(exp(-h)-1)) * D1
+        r = rn16(__fadd_rn((float)r, (float)C));
+    }
+    x0_out = x0;
+    out = r;
+}

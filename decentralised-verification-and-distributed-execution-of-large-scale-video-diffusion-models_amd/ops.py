@@ -889,6 +889,75 @@ def blend_finalize(full, weight):
 
 
 # --------------------------------------------------------------------------------------------
+# Temporal co-denoising (vdx/codenoise.py, csrc/codenoise.hip; no reference counterpart)
+def cfg_input_window(z, ctx, weight, s: int, e: int, out=None):
+    """`cfg_input(z[:, :, s:e], ctx, weight)` without the slice copy: one launch reads frames [s, e) out of the whole clip's
+    latent z (1,C,T,H,W) and writes the contiguous (2,C,e-s,H,W) UNet input, TAGGED as a CFG duplicate exactly as `cfg_input`
+    tags its result (the same warning applies: never hand it to a vdx op as `out=`)."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError("cfg_input_window: z must be contiguous (1,C,T,H,W)")
+    _, Cc, T, H, W = z.shape
+    s, e = int(s), int(e)
+    if not 0 <= s < e <= T:
+        raise VdxError(f"cfg_input_window: bad range [{s},{e}) of {T} frames")
+    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
+        raise VdxError("cfg_input_window: ctx must be contiguous (1,C,1,H,W)")
+    if out is None:
+        out = torch.empty((2, Cc, e - s, H, W), dtype=torch.float16, device=z.device)
+    elif tuple(out.shape) != (2, Cc, e - s, H, W) or not out.is_contiguous():
+        raise VdxError("cfg_input_window: out must be contiguous (2,C,e-s,H,W)")
+    _launch("vdx_cfg_input_window_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H * W, s, e)
+    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
+    return out
+
+
+COFUSE_MAX_WINDOWS = 64
+
+
+def _cofuse_args(what, z, windows, table, wn):
+    """Shared checks of the two fused co-denoising steps -> the launch's leading arguments.  `table`: [(element offset into
+    `windows`, first frame, length)] per window, host integers; the library checks every row against T and the buffer."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError(f"{what}: z must be contiguous (1,C,T,H,W)")
+    if not windows.is_contiguous():
+        raise VdxError(f"{what}: the windows buffer must be contiguous")
+    _, Cc, T, H, W = z.shape
+    K = len(table)
+    if not 1 <= K <= COFUSE_MAX_WINDOWS:
+        raise VdxError(f"{what}: {K} windows, 1..{COFUSE_MAX_WINDOWS} are supported")
+    if tuple(wn.shape) != (K, T) or not wn.is_contiguous():
+        raise VdxError(f"{what}: wn must be contiguous fp32 ({K},{T})")
+    off = (C.c_int64 * K)(*(int(r[0]) for r in table))
+    st = (C.c_int32 * K)(*(int(r[1]) for r in table))
+    ln = (C.c_int32 * K)(*(int(r[2]) for r in table))
+    return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
+
+
+def cofuse_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
+    """One co-denoising DDIM step of the whole clip (include/vdx.h `vdx_cofuse_cfg_ddim_step_f16`): the windows' raw UNet
+    outputs, each a contiguous (2,C,L_k,H,W) block at its `table` offset inside `windows`, are averaged per frame with `wn`
+    and fed to `cfg_ddim_step`'s chain.  coeffs as for `cfg_ddim_step`; `out` may be `z`."""
+    head, tail = _cofuse_args("cofuse_cfg_ddim_step", z, windows, table, wn)
+    if out is None:
+        out = torch.empty_like(z)
+    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+        raise VdxError("cofuse_cfg_ddim_step: out must be contiguous and shaped like z")
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_cofuse_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
+    return out
+
+
+def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
+    """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cofuse_cfg_dpm_step_f16`) -> (z', x0), both of the whole
+    clip's shape.  coeffs, `x0_prev`, `x0_out` and `out` as for `cfg_dpm_step`."""
+    head, tail = _cofuse_args("cofuse_cfg_dpm_step", z, windows, table, wn)
+    x0_out, out, c = _dpm_args("cofuse_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
+    _launch("vdx_cofuse_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
+            *c, *tail)
+    return out, x0_out
+
+
+# --------------------------------------------------------------------------------------------
 # Persistent-grid reserve and box probes (include/vdx.h, last section): not on the denoising path
 def set_reserved_cus(n: int) -> int:
     """Leave `n` compute units free in every persistent grid (weights-stationary GEMMs, K5 / K7 / K8) for the channel kernels

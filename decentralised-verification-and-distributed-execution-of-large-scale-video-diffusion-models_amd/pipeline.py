@@ -33,6 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .codenoise import check_co_denoise, co_denoise_round
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
 
@@ -78,6 +79,10 @@ class DiffuserConfig:
     # FreeU (UNet3DConditionModel.enable_freeu; diffusers' enable_freeu, unpinned): (b1, b2, s1, s2), the backbone factors and the
     # skip filter's scales of up blocks 0 and 1, on every denoising step of the job.  None = off, as always
     freeu: Optional[Tuple[float, float, float, float]] = None
+    # temporal co-denoising (vdx/codenoise.py; MultiDiffusion along time, unpinned): ONE latent for the whole clip, the windows'
+    # noise predictions averaged at every step where they overlap, one scheduler step for the clip; no final blend.  False = one
+    # trajectory per window and the ramp blend after the loop, as always
+    co_denoise: bool = False
 
     @property
     def use_fsdp(self):
@@ -254,6 +259,7 @@ class DistributedVideoDiffuser:
         if check_free_init(cfg) > 1 and init_latents is not None:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
+        self._co_rec: List[dict] = []                              # co_denoise: the rounds' records of the last call
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
         self.uncond_emb, self.cond_emb = uncond_emb, cond_emb
@@ -340,7 +346,13 @@ class DistributedVideoDiffuser:
 
     def _round(self, start: torch.Tensor, cp: ChunkPlan, exchange: str, comm):
         """One sampling round from the whole clip's start latent `start`: denoise this rank's windows, exchange, blend
-        -> (the blend: the latent, or with "halo" the owned segments; that round's seconds and bytes, under `info`'s names)."""
+        -> (the blend: the latent, or with "halo" the owned segments; that round's seconds and bytes, under `info`'s names).
+        With `cfg.co_denoise` the round is `codenoise.co_denoise_round` instead: one latent, the windows meet at every step, no
+        blend; its record is added to `self._co_rec`."""
+        if self.cfg.co_denoise:
+            out, spent, rec = co_denoise_round(self, start, cp)
+            self._co_rec.append(rec)
+            return out, spent
         _, C, T, H, W = start.shape
         t0 = time.time()
         mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
@@ -387,8 +399,16 @@ class DistributedVideoDiffuser:
 
         `freeu` (every exchange, mode and scheduler, every FreeInit iteration): the UNet samples with
         `enable_freeu(s1, s2, b1, b2)` for the length of the call and is handed back in the state it came in; `info["freeu"]`
-        holds the four values."""
+        holds the four values.
+
+        `co_denoise` ("allgather" only; every mode and scheduler, `init_latents`, every FreeInit iteration, `freeu`): each round
+        is `codenoise.co_denoise_round`, and the result is that round's latent as fp32, with no blend after it.  The exchange
+        then happens once per STEP: `network_bytes`, `net_gather_s`, `payload_bytes` and the emulated delays are sums over the
+        steps (and the iterations), and `info["co_denoise"]` = {"windows": windows in the fuse, "steps": steps run,
+        "exchange_s": seconds in the per-step gathers, "bytes_per_step": bytes this rank receives per step}."""
         cfg = self.cfg
+        co = check_co_denoise(cfg, exchange)
+        self._co_rec = []
         iters = check_free_init(cfg, exchange)
         freeu = check_freeu(cfg)
         if exchange not in ("allgather", "halo"):
@@ -436,6 +456,10 @@ class DistributedVideoDiffuser:
             info["free_init"] = rec
         if exchange == "halo":
             info["owned"] = [(s, e) for s, e, _ in out]
+        if co:
+            info["co_denoise"] = {"windows": self._co_rec[0]["windows"], "steps": sum(r["steps"] for r in self._co_rec),
+                                  "exchange_s": sum(r["exchange_s"] for r in self._co_rec),
+                                  "bytes_per_step": self._co_rec[0]["bytes_per_step"]}
         return out, info
 
 
@@ -475,7 +499,12 @@ def build_arg_parser():
     counterpart; diffusers' `enable_freeu(s1, s2, b1, b2)`, unpinned) samples every step of the job, whatever the mode, exchange,
     scheduler and the other options, with FreeU in the UNet's up blocks 0 and 1 (vdx/unet3d.py `enable_freeu`, csrc/freeu.hip):
     the first half of the hidden state's channels times B, the skip tensors' lowest frequencies times S; the result and the
-    JSON records then carry `"freeu": {"b1", "b2", "s1", "s2"}`; without the flag the run is the one it always was."""
+    JSON records then carry `"freeu": {"b1", "b2", "s1", "s2"}`; without the flag the run is the one it always was.
+    `--co_denoise` (no reference counterpart; MultiDiffusion along time, unpinned) samples ONE latent for the whole clip: at every
+    step the windows' noise predictions are averaged where they overlap and one scheduler step advances the clip (vdx/codenoise.py,
+    csrc/codenoise.hip), so there is one exchange per step instead of one per job and no blend at the end; every mode, scheduler
+    and the other options; refused with `--exchange halo`; the result and the JSON records then carry `"co_denoise"`; without the
+    flag every launch, byte, CSV row and record is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -525,6 +554,8 @@ def build_arg_parser():
     p.add_argument("--free_init_order", type=int, default=4, help="FreeInit: order of the butterworth filter")
     p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
                    help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
+    p.add_argument("--co_denoise", action="store_true",
+                   help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -657,6 +688,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     factor = check_factor(cfg.interpolate)      # refused before anything is loaded
     free_init_iters = check_free_init(cfg, exchange)
     freeu = check_freeu(cfg)
+    co = check_co_denoise(cfg, exchange)
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -726,7 +758,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
-            **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {})}
+            **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
+            **({"co_denoise": info["co_denoise"]} if co else {})}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -756,6 +789,8 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {"freeu": res["freeu"]} if "freeu" in res else {}
+        if "co_denoise" in res:
+            source["co_denoise"] = res["co_denoise"]
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -777,6 +812,8 @@ def main(argv=None) -> int:
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             if "freeu" in res:
                 rec["freeu"] = res["freeu"]
+            if "co_denoise" in res:
+                rec["co_denoise"] = res["co_denoise"]
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

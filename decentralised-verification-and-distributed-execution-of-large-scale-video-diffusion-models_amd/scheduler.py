@@ -119,6 +119,12 @@ class DDIMScheduler(_SchedulerBase):
         """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel."""
         return ops.cfg_ddim_step(noise2, sample, guidance_scale, self.coefficients(self._host_timestep(timestep)))
 
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent `sample` on the noise fused from the
+        windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step`), one kernel."""
+        return ops.cofuse_cfg_ddim_step(sample.contiguous(), windows, table, wn, guidance_scale,
+                                        self.coefficients(self._host_timestep(timestep)))
+
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
     """DPM-Solver++ 2M (Lu et al., 2022; diffusers `DPMSolverMultistepScheduler`, which Zeroscope's published recipe swaps in
@@ -276,5 +282,16 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         i, prev, x0_out = self._plan(timestep, sample)
         new, _ = ops.cfg_dpm_step(noise2, sample, guidance_scale, self.coefficients(i, prev is not None), x0_prev=prev,
                                   x0_out=x0_out)
+        self._commit(i)
+        return new
+
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent on the noise fused from the windows' raw
+        UNet outputs (`vdx_cofuse_cfg_dpm_step_f16`), one kernel.  ONE x0 history of the whole clip's shape, planned and
+        committed as for `step_cfg`; `reset()` once per round."""
+        sample = sample.contiguous()
+        i, prev, x0_out = self._plan(timestep, sample)
+        new, _ = ops.cofuse_cfg_dpm_step(sample, windows, table, wn, guidance_scale, self.coefficients(i, prev is not None),
+                                         x0_prev=prev, x0_out=x0_out)
         self._commit(i)
         return new

@@ -338,6 +338,29 @@ int vdx_cfg_dpm_step_f16(const void* eps2, const void* lat, const void* x0_prev,
 int vdx_dpm_step_f16(const void* eps, const void* lat, const void* x0_prev, void* x0_out, void* lat_out, float c_s0,
                      float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, size_t n,
                      vdx_stream_t stream);
+/* Temporal co-denoising (MultiDiffusion along time; no reference counterpart, opt-in: vdx/codenoise.py, csrc/codenoise.hip).
+ * `vdx_cfg_input_f16` above, reading frames [s, e) out of the whole clip's latent z (1,C,T,H,W): x2 (2,C,e-s,H,W) contiguous,
+ * one launch, the ctx term with the same two fp16 roundings.  Pointers 16-byte aligned; x2 must not overlap z.           */
+int vdx_cfg_input_window_f16(const void* z, const void* ctx, float weight, void* x2, int C, int T, int HW, int s, int e,
+                             vdx_stream_t stream);
+/* One denoising step of the whole clip from K windows' raw UNet outputs.  `windows` + win_off[k] (elements) is window k's
+ * contiguous (2,C,L_k,H,W) block [u; c] for frames [win_start[k], win_start[k] + win_len[k]); the three tables are HOST
+ * arrays of K rows (they travel to the kernel as arguments, so every row is checked here first: 1 <= K <= 64, every range
+ * inside [0, T), every block inside the `windows_elems` halves behind `windows`, every frame in some window).  wn: DEVICE
+ * fp32 [K][T], the normalised weights (only entries inside a window's range are read).  Per element (c, t, p), over the
+ * windows that hold t, k ascending:  U = sum wn[k][t]*u_k,  Cc = sum wn[k][t]*c_k  (fp32; every product and every add its
+ * own rounding, the sum starts with the first product), u = fp16(U), c = fp16(Cc), and from there EXACTLY the chain of
+ * vdx_cfg_ddim_step_f16 with the same four coefficients: lat_out (1,C,T,H,W); lat_out may be z.                            */
+int vdx_cofuse_cfg_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                 const int* win_start, const int* win_len, int K, const float* wn, void* lat_out,
+                                 float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                                 float sqrt_one_minus_aprev, int C, int T, int HW, vdx_stream_t stream);
+/* The same fused noise into EXACTLY the chain of vdx_cfg_dpm_step_f16, with its seven scalars and its rules for x0_prev
+ * (NULL: first order), x0_out and lat_out, all of the whole clip's shape (1,C,T,H,W).                                      */
+int vdx_cofuse_cfg_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
+                                float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
 /* :204-217 one chunk's contribution: full[s:e] += lat*w (fp16 accumulator), weight[s:e] += w;
  * w = fp32 device vector of length e-s (the linear ramps, built by the host exactly as :207-213) */
 int vdx_blend_accumulate_f16(void* full, float* weight, const void* chunk, const float* w, int C,

@@ -149,6 +149,12 @@ SIGNATURES = {
     "vdx_cofuse_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
     "vdx_cofuse_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
                                          _vp]),
+    # masked video-to-video: the per-step select, the paste and the mask's two maps (no reference counterpart; vdx/inpaint.py,
+    # csrc/inpaint.hip)
+    "vdx_mask_renoise_f16": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _i, _vp]),
+    "vdx_mask_paste_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vdx_mask_to_latent_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vdx_mask_composite_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     # FreeU's skip filter and backbone scale (no reference counterpart; unet3d.py enable_freeu, csrc/freeu.hip)
     "vdx_freeu_filter_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
     "vdx_freeu_scale_f16": (_i, [_vp, _i, _sz, _i, _f, _vp]),

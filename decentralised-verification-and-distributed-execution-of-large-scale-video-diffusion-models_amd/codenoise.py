@@ -109,7 +109,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
     spent = {"denoise_s": 0.0, "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0,
              "payload_bytes_actual": 0}
     t_round = time.time()
-    for t in d.schedule:
+    for i, t in enumerate(d.schedule):
         for j, (s, e) in enumerate(mine):
             x = ops.cfg_input_window(z, d.ctx, cfg.context_weight, s, e)
             noise = d.unet(x, t, encoder_hidden_states=emb).sample
@@ -126,6 +126,8 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
             d._sync()
             spent["net_gather_s"] += time.time() - t0
         z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale)
+        if d.latent_mask is not None:                             # masked video-to-video (vdx/inpaint.py): the whole clip, s = 0
+            d._mask_step(z, i, 0)
         spent["network_bytes"] += bytes_step
         spent["payload_bytes"] += payload_step
         spent["payload_bytes_actual"] += actual_step

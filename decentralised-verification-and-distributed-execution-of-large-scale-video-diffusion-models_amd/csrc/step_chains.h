@@ -1,6 +1,7 @@
 // step_chains.h — the per-element rounding chains of the fused CFG + sampler steps, written once: elementwise.hip
 // (`vdx_cfg_ddim_step_f16`), dpm.hip (`vdx_cfg_dpm_step_f16`, `vdx_dpm_step_f16`) and codenoise.hip (the co-denoising steps,
-// which feed the same chains a fused noise) all call these, so the three cannot drift apart.  Every function is
+// which feed the same chains a fused noise) all call these, so the three cannot drift apart; likewise `add_noise`'s chain for
+// vid2vid.hip and inpaint.hip (the masked step re-noises the kept cells with exactly video-to-video's start).  Every function is
 // __forceinline__: a kernel that calls one compiles to the instructions it had when the chain was written in its loop.
 #pragma once
 #include "vdx_common.h"
@@ -11,6 +12,14 @@
 __device__ __forceinline__ f16 rn16(float x) {
     asm volatile("" : "+v"(x));
     return (f16)x;
+}
+
+// ---- DDIMScheduler.add_noise (diffusers; vid2vid.hip `vdx_add_noise_f16`, inpaint.hip `vdx_mask_renoise_f16`) ----------------
+//   x_t = sqrt(a_t) * x0 + sqrt(1 - a_t) * noise        fp16 tensors, fp16-valued 0-d coefficients: every op rounds to fp16
+__device__ __forceinline__ f16 add_noise_elem(float x0, float noise, float sa, float s1) {
+    const f16 a = rn16(__fmul_rn(sa, x0));                // sqrt(a_t) * x0
+    const f16 b = rn16(__fmul_rn(s1, noise));             // sqrt(1-a_t) * noise
+    return rn16(__fadd_rn((float)a, (float)b));
 }
 
 // ---- fsdp_chunked_coherent.py:141-142 -------------------------------------------------------

@@ -4,6 +4,7 @@
 // attention run on the UNet's kernels (vdx/vae.py); the (0,1,0,1) padding of its Downsample2D is gemm.hip's pad_mode 1.
 // Every element-wise map here rounds to fp16 after each op, as the torch evaluation it restates does.
 #include "vdx_common.h"
+#include "step_chains.h"
 
 namespace {
 
@@ -134,9 +135,7 @@ __global__ __launch_bounds__(256) void posterior_kernel(const f16* m, int ld, in
 
 __global__ __launch_bounds__(256) void add_noise_kernel(const f16* x0, const f16* noise, f16* out, float sa, float s1, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const f16 a = h16(__fmul_rn(sa, (float)x0[i]));
-        const f16 b = h16(__fmul_rn(s1, (float)noise[i]));
-        out[i] = h16(__fadd_rn((float)a, (float)b));
+        out[i] = add_noise_elem((float)x0[i], (float)noise[i], sa, s1);     // step_chains.h: shared with inpaint.hip
     }
 }
 

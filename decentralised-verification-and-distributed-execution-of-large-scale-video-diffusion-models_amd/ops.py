@@ -958,6 +958,107 @@ def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x
 
 
 # --------------------------------------------------------------------------------------------
+# Masked video-to-video (vdx/inpaint.py, csrc/inpaint.hip; no reference counterpart)
+def check_latent_mask(m, T: int, H: int, W: int, what: str = "latent mask"):
+    """`m` is a contiguous uint8 (T,H,W) GPU tensor holding only 0 (keep) and 1 (regenerate); `VdxError` / `ValueError`
+    otherwise, before any launch.  The values are read ONCE (one sync): the tensor is then tagged with torch's version counter,
+    as `cfg_input` tags its result, and checked again only after somebody wrote it."""
+    if not torch.is_tensor(m) or not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (T, H, W) or not m.is_contiguous():
+        raise VdxError(f"{what}: expected a contiguous uint8 ({T},{H},{W}) GPU tensor, got "
+                       f"{getattr(m, 'dtype', type(m))} {tuple(getattr(m, 'shape', ()))}")
+    if getattr(m, "_vdx_mask01", None) != m._version:
+        top = int(m.max())
+        if top > 1:
+            raise ValueError(f"{what}: values must be 0 (keep) or 1 (regenerate), found {top}")
+        m._vdx_mask01 = m._version
+    return m
+
+
+def _mask_clip_args(what, z, x0, base, m):
+    """Shared checks of the two latent selects: z (1,C,L,H,W), x0 / base (1,C,T,H,W) fp16, m (T,H,W) -> (C, T, L, HW)."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError(f"{what}: z must be contiguous (1,C,L,H,W)")
+    _, Cc, L, H, W = z.shape
+    if x0.dim() != 5 or tuple(x0.shape[:2]) != (1, Cc) or tuple(x0.shape[3:]) != (H, W) or not x0.is_contiguous():
+        raise VdxError(f"{what}: x0 {tuple(x0.shape)} must be contiguous (1,{Cc},T,{H},{W})")
+    T = x0.shape[2]
+    if base is not None and (tuple(base.shape) != tuple(x0.shape) or not base.is_contiguous()):
+        raise VdxError(f"{what}: base must be contiguous and shaped like x0")
+    check_latent_mask(m, T, H, W, f"{what}: mask")
+    if min(Cc, L, T, H * W) < 1:
+        raise VdxError(f"{what}: empty tensor")
+    return Cc, T, L, H * W
+
+
+def mask_renoise(z, x0, base, m, sqrt_ab: float, sqrt_1mab: float, last: bool, s: int):
+    """After a scheduler step, IN PLACE on a window's latent z (1,C,L,H,W) fp16 (include/vdx.h `vdx_mask_renoise_f16`): where
+    m == 1 z keeps its bits; where m == 0 it takes `add_noise(x0, base, sqrt_ab, sqrt_1mab)`'s, or x0's own with `last`.
+    x0, base (1,C,T,H,W) and m (T,H,W) uint8 in {0,1} are the clip's, read at frames [s, s + L).  -> z"""
+    Cc, T, L, HW = _mask_clip_args("mask_renoise", z, x0, None if last else base, m)
+    s = int(s)
+    if not (0 <= s and s + L <= T):
+        raise VdxError(f"mask_renoise: window [{s},{s + L}) leaves the clip's {T} frames")
+    _launch("vdx_mask_renoise_f16", _p(z, "z"), _p(x0, "x0"), None if last else _p(base, "base"), _p(m, "mask", torch.uint8),
+            float(sqrt_ab), float(sqrt_1mab), int(bool(last)), Cc, T, HW, s, L)
+    return z
+
+
+def mask_paste_f32(z, x0, m):
+    """IN PLACE on the fp32 blended latent z (1,C,T,H,W): `torch.where(m, z, x0.float())` (`vdx_mask_paste_f32`).  -> z"""
+    Cc, T, L, HW = _mask_clip_args("mask_paste_f32", z, x0, None, m)
+    if L != T:
+        raise VdxError(f"mask_paste_f32: z has {L} frames, the clip {T}")
+    _launch("vdx_mask_paste_f32", _p(z, "z", torch.float32), _p(x0, "x0"), _p(m, "mask", torch.uint8), Cc, T, HW)
+    return z
+
+
+MASK_RULES = ("nearest", "any")
+
+
+def mask_to_latent(pixel_mask, rule: str = "nearest"):
+    """Pixel mask (T,H,W) uint8 / bool on the GPU, nonzero = regenerate -> latent mask (T,H/8,W/8) uint8 in {0,1}
+    (`vdx_mask_to_latent_u8`).  "nearest": pixel (8y, 8x); "any": a cell regenerates if any of its 64 pixels does."""
+    if rule not in MASK_RULES:
+        raise ValueError(f"mask_to_latent: rule must be one of {MASK_RULES}, got {rule!r}")
+    if pixel_mask.dtype == torch.bool:
+        pixel_mask = pixel_mask.view(torch.uint8)
+    if not pixel_mask.is_cuda or pixel_mask.dtype != torch.uint8 or pixel_mask.dim() != 3 or not pixel_mask.is_contiguous():
+        raise VdxError(f"mask_to_latent: expected a contiguous uint8 (T,H,W) GPU tensor, got {pixel_mask.dtype} "
+                       f"{tuple(pixel_mask.shape)}")
+    T, H, W = pixel_mask.shape
+    if T < 1 or H < 8 or W < 8 or H % 8 or W % 8:
+        raise VdxError(f"mask_to_latent: ({T},{H},{W}): H and W must be positive multiples of 8")
+    out = torch.empty((T, H // 8, W // 8), dtype=torch.uint8, device=pixel_mask.device)
+    _launch("vdx_mask_to_latent_u8", _p(pixel_mask, "pixel_mask", torch.uint8), _p(out, "out", torch.uint8), T, H, W,
+            int(rule == "any"))
+    out._vdx_mask01 = out._version             # {0,1} by construction
+    return out
+
+
+def mask_composite_u8(generated, original, mask, out=None):
+    """`torch.where(mask[..., None] != 0, generated, original)` on contiguous uint8 (T,H,W,3) GPU frames with a (T,H,W) uint8
+    mask (`vdx_mask_composite_u8`).  `out` may be `generated`."""
+    if out is None:
+        out = torch.empty_like(generated)
+    for name, t in (("generated", generated), ("original", original), ("out", out)):
+        if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous() \
+                or tuple(t.shape) != tuple(generated.shape):
+            raise VdxError(f"mask_composite_u8: {name} must be contiguous uint8 (T,H,W,3) on the GPU, all of one shape; got "
+                           f"{t.dtype} {tuple(t.shape)}")
+    T, H, W, _ = generated.shape
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if not mask.is_cuda or mask.dtype != torch.uint8 or tuple(mask.shape) != (T, H, W) or not mask.is_contiguous():
+        raise VdxError(f"mask_composite_u8: mask must be contiguous uint8 ({T},{H},{W}) on the GPU, got {mask.dtype} "
+                       f"{tuple(mask.shape)}")
+    if T * H * W == 0:
+        raise VdxError("mask_composite_u8: empty frames")
+    ptr = lambda t: t.data_ptr()     # noqa: E731 (byte tensors: a view may start anywhere, the library picks the access width)
+    _launch("vdx_mask_composite_u8", ptr(generated), ptr(original), ptr(mask), ptr(out), T, H, W)
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Persistent-grid reserve and box probes (include/vdx.h, last section): not on the denoising path
 def set_reserved_cus(n: int) -> int:
     """Leave `n` compute units free in every persistent grid (weights-stationary GEMMs, K5 / K7 / K8) for the channel kernels

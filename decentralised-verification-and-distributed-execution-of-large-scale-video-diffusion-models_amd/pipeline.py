@@ -34,6 +34,7 @@ import torch.distributed as dist
 
 from . import ops
 from .codenoise import check_co_denoise, co_denoise_round
+from .inpaint import check_mask, known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
 
@@ -83,6 +84,13 @@ class DiffuserConfig:
     # noise predictions averaged at every step where they overlap, one scheduler step for the clip; no final blend.  False = one
     # trajectory per window and the ramp blend after the loop, as always
     co_denoise: bool = False
+    # masked video-to-video (vdx/inpaint.py; the replacement method / RePaint / diffusers' 4-channel inpainting, unpinned): hold
+    # part of `init_video` fixed and generate the rest.  `mask`: a .npy path (or an array) of uint8 / bool (T,H,W), (H,W) or (T,),
+    # nonzero = regenerate; `keep_frames`: "0:8,20:24", the frames to KEEP; one of the two.  None, None = off, as always
+    mask: Optional[object] = None
+    keep_frames: Optional[str] = None
+    mask_rule: str = "nearest"             # pixel -> latent mask: "nearest" (pixel (8y, 8x)) | "any" (any of the cell's 64 pixels)
+    mask_paste: bool = True                # the written frames' kept pixels are the input clip's bytes
 
     @property
     def use_fsdp(self):
@@ -249,11 +257,14 @@ def gather_chunks(mine: List[torch.Tensor], chunk_plan: ChunkPlan, rank: int, wo
 
 
 class DistributedVideoDiffuser:
-    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None):
+    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None, latent_mask=None):
         """`init_latents` (video-to-video): the scaled clean latent (1,C,T,h,w) fp16 of the whole clip (every rank encodes the
         whole clip: identical bits on every rank, no collective).  The denoise then runs `vid2vid_timesteps(cfg.strength)`
         from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
-        frame-mean of that start latent.  None: text-to-video, unchanged."""
+        frame-mean of that start latent.  None: text-to-video, unchanged.
+        `latent_mask` (masked video-to-video, vdx/inpaint.py; needs `init_latents`): uint8 (T,h,w) on the device, 1 = regenerate,
+        0 = keep, identical on every rank.  After every scheduler step the kept cells are set to `init_latents` noised to the
+        next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off."""
         self.cfg = cfg
         check_freeu(cfg)
         if check_free_init(cfg) > 1 and init_latents is not None:
@@ -271,13 +282,17 @@ class DistributedVideoDiffuser:
         self.init_latents = init_latents
         self.timesteps = None                                         # video-to-video only: the truncated schedule
         self._start = None
+        self._base = self._x0 = None                                  # video-to-video only: the seeded noise, the clean latent
+        self.latent_mask = None
+        self._known = None                                            # masked only: add_noise's scalars of each step's NEXT timestep
         shape = self.latent_shape if init_latents is not None or cfg.use_ctx else None
         if init_latents is not None:
             if tuple(init_latents.shape) != shape:
                 raise ValueError(f"init_latents {tuple(init_latents.shape)} != {shape}")
             self.timesteps = vid2vid_timesteps(scheduler, cfg.steps, cfg.strength)
             base = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
-            self._start = scheduler.add_noise(init_latents.to(cfg.device, torch.float16).contiguous(), base, self.timesteps[0])
+            self._x0, self._base = init_latents.to(cfg.device, torch.float16).contiguous(), base
+            self._start = scheduler.add_noise(self._x0, base, self.timesteps[0])
             if cfg.use_ctx:                                           # the frame-mean of the whole clip's start latent
                 self.ctx = self._start.mean(dim=2, keepdim=True).contiguous()
         elif cfg.use_ctx:                                             # reference :105-127
@@ -289,6 +304,11 @@ class DistributedVideoDiffuser:
             if self.world > 1:
                 dist.broadcast(ctx, src=0)
             self.ctx = ctx.contiguous()
+        if latent_mask is not None:
+            if init_latents is None:
+                raise ValueError("latent_mask needs init_latents: the kept content is that clip's")
+            self.latent_mask = ops.check_latent_mask(latent_mask, *shape[2:])
+            self._known = known_coefficients(scheduler, self.timesteps, self._x0)
 
     @property
     def latent_shape(self) -> Tuple[int, int, int, int, int]:
@@ -300,18 +320,28 @@ class DistributedVideoDiffuser:
         """The timesteps this job runs: the scheduler's, or video-to-video's truncated ones."""
         return self.scheduler._host_timesteps if self.timesteps is None else self.timesteps
 
-    def denoise(self, lat: torch.Tensor) -> torch.Tensor:
-        """Reference `_denoise` (:129-143) for one chunk."""
+    def _mask_step(self, z: torch.Tensor, i: int, s: int) -> None:
+        """Masked video-to-video, after step i of the schedule, in place on the latent z of the clip's frames [s, s + L)."""
+        k = self._known[i]
+        sa, s1 = k if k is not None else (0.0, 0.0)
+        ops.mask_renoise(z, self._x0, self._base, self.latent_mask, sa, s1, k is None, s)
+
+    def denoise(self, lat: torch.Tensor, s: Optional[int] = None) -> torch.Tensor:
+        """Reference `_denoise` (:129-143) for one chunk.  `s` (masked video-to-video only, with a `latent_mask`): the chunk's
+        first frame in the clip; None: the masked path is off."""
+        masked = s is not None and self.latent_mask is not None
         cfg, sched = self.cfg, self.scheduler
         emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0)
         lat = lat.contiguous()
         reset = getattr(sched, "reset", None)
         if reset is not None:       # a multistep scheduler must not carry the previous chunk's history into this one
             reset()
-        for t in self.schedule:
+        for i, t in enumerate(self.schedule):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb).sample
             lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale)
+            if masked:
+                self._mask_step(lat, i, s)
         return lat
 
     def plan(self) -> ChunkPlan:
@@ -327,16 +357,21 @@ class DistributedVideoDiffuser:
             ops.blend_accumulate(full, weight, lat.contiguous(), ramp_weights(e - s, ov).to(like.device), s, e)
         return ops.blend_finalize(full, weight)
 
-    def decode_frames(self, lat: torch.Tensor, vae, batch: int = 8) -> List:
+    def decode_frames(self, lat: torch.Tensor, vae, batch: int = 8, paste=None) -> List:
         """Reference :219-225: the blended latent (1,C,T,h,w) -> T uint8 (H,W,3) frames (numpy, host).
         `z/0.18215` is formed in the latent's dtype and cast to fp16 at the VAE boundary (what the reference's
         FSDP mixed-precision wrapper does to forward inputs); frames are decoded `batch` at a time instead of one
-        by one (frames are independent samples of the decoder)."""
+        by one (frames are independent samples of the decoder).  `paste` = (the original uint8 (T,H,W,3) frames, the pixel mask
+        uint8 (T,H,W), nonzero = generated), both on the device (masked video-to-video): each batch's kept pixels take the
+        originals' bytes before the copy to the host."""
         frames = []
         T = lat.shape[2]
         for i0 in range(0, T, batch):
             z = lat[0, :, i0:i0 + batch].permute(1, 0, 2, 3) / 0.18215
             u8 = vae.decode_frames_u8(z.to(self.cfg.device, torch.float16).contiguous())
+            if paste is not None:
+                orig, pm = paste
+                u8 = ops.mask_composite_u8(u8, orig[i0:i0 + batch], pm[i0:i0 + batch], out=u8)
             frames += [f for f in u8.cpu().numpy()]
         return frames
 
@@ -355,7 +390,8 @@ class DistributedVideoDiffuser:
             return out, spent
         _, C, T, H, W = start.shape
         t0 = time.time()
-        mine = [self.denoise(start[:, :, s:e].clone()) for s, e in cp.for_rank(self.rank)]
+        masked = self.latent_mask is not None
+        mine = [self.denoise(start[:, :, s:e].clone(), *((s,) if masked else ())) for s, e in cp.for_rank(self.rank)]
         if self.world > 1:
             dist.barrier()
         self._sync()
@@ -374,6 +410,8 @@ class DistributedVideoDiffuser:
             net_gather_s = time.time() - t0
             received = (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2
             out = self.blend(chunks, start, cp.overlap)
+            if masked:              # the ramp blend zeroes the clip's first and last frame and re-weights overlaps: kept cells again
+                ops.mask_paste_f32(out, self._x0, self.latent_mask)
         else:
             hp = HaloPlan(cp, T)
             got, done = exchange_halos(mine, hp, self.rank, comm=comm) if self.world > 1 else ({}, None)
@@ -405,9 +443,14 @@ class DistributedVideoDiffuser:
         is `codenoise.co_denoise_round`, and the result is that round's latent as fp32, with no blend after it.  The exchange
         then happens once per STEP: `network_bytes`, `net_gather_s`, `payload_bytes` and the emulated delays are sums over the
         steps (and the iterations), and `info["co_denoise"]` = {"windows": windows in the fuse, "steps": steps run,
-        "exchange_s": seconds in the per-step gathers, "bytes_per_step": bytes this rank receives per step}."""
+        "exchange_s": seconds in the per-step gathers, "bytes_per_step": bytes this rank receives per step}.
+
+        `latent_mask` ("allgather" only; both samplers, windowed and `co_denoise`, every mode): the constructor's docstring; `info`
+        is the one of the job without it."""
         cfg = self.cfg
         co = check_co_denoise(cfg, exchange)
+        if self.latent_mask is not None and exchange == "halo":
+            raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         self._co_rec = []
         iters = check_free_init(cfg, exchange)
         freeu = check_freeu(cfg)
@@ -504,7 +547,17 @@ def build_arg_parser():
     step the windows' noise predictions are averaged where they overlap and one scheduler step advances the clip (vdx/codenoise.py,
     csrc/codenoise.hip), so there is one exchange per step instead of one per job and no blend at the end; every mode, scheduler
     and the other options; refused with `--exchange halo`; the result and the JSON records then carry `"co_denoise"`; without the
-    flag every launch, byte, CSV row and record is the one it always was."""
+    flag every launch, byte, CSV row and record is the one it always was.
+    `--mask PATH` / `--keep_frames SPEC` (no reference counterpart; the replacement method, RePaint, diffusers' inpainting branch
+    for 4-channel UNets, unpinned; needs `--init_video`, one of the two) hold part of that clip fixed and generate the rest
+    (vdx/inpaint.py, csrc/inpaint.hip): PATH is a `.npy` of uint8 / bool shaped (T,H,W), (H,W) or (T,) at the job's size, nonzero =
+    regenerate; SPEC is comma-separated Python-style slices or indices of the frames to KEEP ("0:8,20:24").  `--mask_rule nearest`
+    (default: pixel (8y, 8x) decides a latent cell) | `any` (a cell regenerates if any of its 64 pixels does).  After every
+    scheduler step the kept latent cells are set to the clip's latent noised to the next timestep, after the blend to the clip's
+    latent itself, and with `--mask_paste on` (default) the written frames' kept pixels are the input's bytes (`off`: the
+    decoder's).  Refused with `--exchange halo` and when nothing is left to regenerate; the result and the JSON records then
+    carry `"mask": {"rule", "paste", "kept_fraction", "kept_frames"}`; without the flags every launch, byte, CSV row and record
+    is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -556,6 +609,14 @@ def build_arg_parser():
                    help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
     p.add_argument("--co_denoise", action="store_true",
                    help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
+    p.add_argument("--mask", default=None,
+                   help="masked video-to-video: .npy uint8 / bool (T,H,W), (H,W) or (T,), nonzero = regenerate, zero = keep (needs --init_video)")
+    p.add_argument("--keep_frames", default=None,
+                   help="masked video-to-video: frames of --init_video to KEEP, e.g. 0:8,20:24 (slices or indices; instead of --mask)")
+    p.add_argument("--mask_rule", choices=["nearest", "any"], default="nearest",
+                   help="pixel mask -> latent mask: pixel (8y, 8x) decides a cell (nearest), or any of its 64 pixels (any)")
+    p.add_argument("--mask_paste", choices=["on", "off"], default="on",
+                   help="masked video-to-video: kept pixels of the written frames are the input clip's bytes (on) or the decoder's (off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -571,6 +632,8 @@ def config_from_args(a) -> DiffuserConfig:
     cfg = DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
     if cfg.freeu is not None:
         cfg.freeu = tuple(cfg.freeu)
+    if isinstance(cfg.mask_paste, str):
+        cfg.mask_paste = cfg.mask_paste == "on"
     return cfg
 
 
@@ -635,8 +698,9 @@ def compare_record(frames, path: str, ranges, device) -> dict:
     return {"compare_to": path, **rec}
 
 
-def encode_init_video(cfg: DiffuserConfig, vae, dev):
-    """--init_video -> the scaled clean latent (1,4,T,h,w) fp16 on `dev`, seconds: the clip is loaded, resized on the GPU to
+def encode_init_video(cfg: DiffuserConfig, vae, dev, return_frames: bool = False):
+    """--init_video -> the scaled clean latent (1,4,T,h,w) fp16 on `dev`, seconds (and with `return_frames` the uint8 (T,H,W,3)
+    frames at job size the encoder saw, on `dev`: what masked video-to-video pastes back): the clip is loaded, resized on the GPU to
     (height, width) when its size differs (Image.resize, BICUBIC), and encoded (posterior noise: (T,4,h,w) fp16 from a
     torch.Generator seeded 1 on the noise device).  Encoder weights: `vae/` of a local checkpoint, else seeded synthetic ones."""
     import os
@@ -670,7 +734,7 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev):
     lat = vae.encode_frames_u8(frames, posterior=cfg.posterior, noise=noise)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
-    return lat, time.time() - t0
+    return (lat, time.time() - t0, frames) if return_frames else (lat, time.time() - t0)
 
 
 def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
@@ -689,6 +753,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     free_init_iters = check_free_init(cfg, exchange)
     freeu = check_freeu(cfg)
     co = check_co_denoise(cfg, exchange)
+    pixel_mask = check_mask(cfg, exchange)      # None: the option is off
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -710,14 +775,20 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     with torch.no_grad():
         emb = pipe.text_encoder(ids.to(dev))[0]
     cond, uncond = emb[:1].contiguous(), emb[1:].contiguous()
-    init_latents, encode_s = None, 0.0
-    if cfg.init_video is not None:
+    init_latents, encode_s, masking = None, 0.0, {}
+    if pixel_mask is not None:
+        init_latents, encode_s, originals = encode_init_video(cfg, pipe.vae, dev, return_frames=True)
+        pixel_mask = torch.from_numpy(pixel_mask).to(dev)
+        masking = {"latent_mask": ops.mask_to_latent(pixel_mask, cfg.mask_rule)}
+    elif cfg.init_video is not None:
         init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
-    d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents)
+    d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents,
+                                 **masking)
     out, info = d(exchange=exchange)
     ranges = info["ranges"]
     if exchange == "allgather":
-        frames = d.decode_frames(out, pipe.vae)
+        paste = {"paste": (originals.contiguous(), pixel_mask)} if pixel_mask is not None and cfg.mask_paste else {}
+        frames = d.decode_frames(out, pipe.vae, **paste)
     else:                                       # every rank decodes the frames it owns; rank 0 collects them for the metrics / mp4
         mine = [(s, d.decode_frames(lat, pipe.vae)) for s, _e, lat in out]
         allf = [None] * d.world
@@ -759,7 +830,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
-            **({"co_denoise": info["co_denoise"]} if co else {})}
+            **({"co_denoise": info["co_denoise"]} if co else {}),
+            **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {})}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -791,6 +863,8 @@ def main(argv=None) -> int:
         source = {"freeu": res["freeu"]} if "freeu" in res else {}
         if "co_denoise" in res:
             source["co_denoise"] = res["co_denoise"]
+        if "mask" in res:
+            source["mask"] = res["mask"]
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -814,6 +888,8 @@ def main(argv=None) -> int:
                 rec["freeu"] = res["freeu"]
             if "co_denoise" in res:
                 rec["co_denoise"] = res["co_denoise"]
+            if "mask" in res:
+                rec["mask"] = res["mask"]
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -60,13 +60,17 @@ class _SchedulerBase:
         then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers
         does), then x_t = sqrt(a_t)*x0 + sqrt(1-a_t)*noise in the HIP kernel with fp16 rounding after each op.  Unpinned
         boundary (diffusers is not installed: DESIGN §2)."""
+        sa, s1 = self.add_noise_coefficients(timesteps, original_samples)
+        return ops.add_noise(original_samples.contiguous(), noise.contiguous(), sa, s1)
+
+    def add_noise_coefficients(self, timesteps, like):
+        """`add_noise`'s two scalars for one timestep, (sqrt(a_t), sqrt(1 - a_t)), evaluated as it always evaluated them: in
+        `like`'s dtype on `like`'s device.  The masked job (vdx/inpaint.py) computes them once per step of its schedule."""
         t = self._host_timestep(timesteps) if torch.is_tensor(timesteps) else int(timesteps)
         if not 0 <= t < len(self.alphas_cumprod):
             raise ValueError(f"add_noise: timestep {t} is outside the {len(self.alphas_cumprod)} training steps")
-        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
-        sa = float(ac[t] ** 0.5)
-        s1 = float((1 - ac[t]) ** 0.5)
-        return ops.add_noise(original_samples.contiguous(), noise.contiguous(), sa, s1)
+        ac = self.alphas_cumprod.to(device=like.device, dtype=like.dtype)
+        return float(ac[t] ** 0.5), float((1 - ac[t]) ** 0.5)
 
 
 class DDIMScheduler(_SchedulerBase):

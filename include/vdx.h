@@ -361,6 +361,26 @@ int vdx_cofuse_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
                                 void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
                                 float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
+/* Masked video-to-video (keep frames or regions of --init_video, generate the rest; no reference counterpart, opt-in:
+ * vdx/inpaint.py, csrc/inpaint.hip).  Masks are uint8, 1 = regenerate, 0 = keep; every entry point is a SELECT of bits (no
+ * arithmetic on the mask: no 0*inf, -0 keeps its sign, NaN / inf stay in their element).  tests/inpaint_ref.py states it.
+ * In place on a window's latent z (1,C,L,H,W) after a scheduler step: where mask == 1 z keeps its bits; where mask == 0 z takes
+ * the bits of `known` = fp16(fp16(sqrt_ab*x0) + fp16(sqrt_1mab*base)), EXACTLY the chain of vdx_add_noise_f16 (one function,
+ * csrc/step_chains.h), or with last != 0 the bits of x0 itself.  x0, base (1,C,T_clip,H,W) fp16 and mask (T_clip,H,W) are the
+ * whole CLIP's tensors, read at frame s + f for the window's frame f: 0 <= s, L >= 1, s + L <= T_clip, refused otherwise.
+ * Pointers 16-byte aligned; z must not overlap an input; base may be NULL with last != 0.  Any C, T_clip, L, HW >= 1.        */
+int vdx_mask_renoise_f16(void* z, const void* x0, const void* base, const void* mask, float sqrt_ab, float sqrt_1mab, int last,
+                         int C, int T_clip, int HW, int s, int L, vdx_stream_t stream);
+/* The same select on the fp32 blended latent z (1,C,T,H,W), in place: mask ? z : float(x0).                                */
+int vdx_mask_paste_f32(float* z, const void* x0, const void* mask, int C, int T, int HW, vdx_stream_t stream);
+/* Pixel mask (T,H,W) uint8, nonzero = regenerate, H and W multiples of 8 -> latent mask (T,H/8,W/8) in {0,1}.
+ * any == 0 ("nearest"): pixel (8y, 8x), what F.interpolate(mode="nearest") takes at the exact factor 8; any == 1: a cell
+ * regenerates if any of its 64 pixels does.  pixel_mask 8-byte aligned.                                                     */
+int vdx_mask_to_latent_u8(const void* pixel_mask, void* latent_mask, int T, int H, int W, int any, vdx_stream_t stream);
+/* out = mask ? generated : original on packed uint8 (T,H,W,3) frames with a (T,H,W) mask (nonzero = generated); out may be
+ * `generated`.  16 pixels per lane where W % 16 == 0, 4 where W % 4 == 0 (and the pointers allow), else one.                */
+int vdx_mask_composite_u8(const void* generated, const void* original, const void* mask, void* out, int T, int H, int W,
+                          vdx_stream_t stream);
 /* :204-217 one chunk's contribution: full[s:e] += lat*w (fp16 accumulator), weight[s:e] += w;
  * w = fp32 device vector of length e-s (the linear ramps, built by the host exactly as :207-213) */
 int vdx_blend_accumulate_f16(void* full, float* weight, const void* chunk, const float* w, int C,

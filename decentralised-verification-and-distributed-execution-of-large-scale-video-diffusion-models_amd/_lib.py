@@ -149,6 +149,18 @@ SIGNATURES = {
     "vdx_cofuse_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
     "vdx_cofuse_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
                                          _vp]),
+    # CFG rescale: the statistics pass and the fused steps, plain and co-fused (no reference counterpart; vdx/scheduler.py
+    # `guidance_rescale`, csrc/rescale.hip)
+    "vdx_cfg_rescale_rows": (_i, [_sz]),
+    "vdx_cfg_rescale_stats_f16": (_i, [_vp, _sz, _f, _vp, _vp]),
+    "vdx_cfg_rescale_ddim_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _sz, _vp]),
+    "vdx_cfg_rescale_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _vp]),
+    "vdx_cofuse_cfg_rescale_rows": (_i, [_i, _i]),
+    "vdx_cofuse_cfg_rescale_stats_f16": (_i, [_vp, _sz, _vp, _vp, _vp, _i, _vp, _f, _vp, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_rescale_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i,
+                                                  _i, _i, _vp]),
+    "vdx_cofuse_cfg_rescale_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f,
+                                                 _f, _f, _f, _f, _i, _i, _i, _vp]),
     # masked video-to-video: the per-step select, the paste and the mask's two maps (no reference counterpart; vdx/inpaint.py,
     # csrc/inpaint.hip)
     "vdx_mask_renoise_f16": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _i, _vp]),

@@ -4,6 +4,8 @@
         ids = tokenizer([prompt, ""], padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids
         emb = self.text_encoder(ids.to(device))[0]            # (2, 77, 1024) last hidden state
     (InferNet/neurons/miner.py:553-565 makes the same call.)
+    `run_job` (vdx/pipeline.py) makes it with `[prompt, negative_prompt]`: the second sequence, the reference's hard-wired "",
+    is `DiffuserConfig.negative_prompt`, whose default "" sends the token ids above.
 
 The arithmetic is `transformers.CLIPTextModel` (pins: `transformers>=4.30.0`; Zeroscope ships the OpenCLIP ViT-H
 text tower as packaged for Stable-Diffusion 2.x: hidden 1024, 23 layers, 16 heads of 64, MLP 4096 with exact

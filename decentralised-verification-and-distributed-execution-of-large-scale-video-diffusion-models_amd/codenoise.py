@@ -85,7 +85,8 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
     the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  Per step: this rank's windows go
     through `ops.cfg_input_window` -> UNet into one packed buffer `[per_rank][2][C][cp.chunk][h][w]` (a window shorter than the
     chunk fills the front of its slot; the rest is never read); with more than one rank, one `all_gather_into_tensor` of that
-    buffer; then every rank runs the fused step on its own copy of z (identical bits on every rank: no broadcast).  There is no
+    buffer; then every rank runs the fused step on its own copy of z (identical bits on every rank: no broadcast; with
+    `guidance_rescale` the step's statistic is taken over that same gathered buffer, so every rank gets the same r).  There is no
     final blend, so the zeroed first and last frame of the reference's ramp blend does not occur."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
@@ -125,7 +126,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
             dist.all_gather_into_tensor(packed.view(-1), local.view(-1))
             d._sync()
             spent["net_gather_s"] += time.time() - t0
-        z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale)
+        z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale, **d._rescale_kw)
         if d.latent_mask is not None:                             # masked video-to-video (vdx/inpaint.py): the whole clip, s = 0
             d._mask_step(z, i, 0)
         spent["network_bytes"] += bytes_step

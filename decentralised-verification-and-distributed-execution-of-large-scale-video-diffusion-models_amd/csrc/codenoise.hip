@@ -23,49 +23,7 @@
 
 #include "vdx_common.h"
 #include "step_chains.h"
-
-#define COFUSE_MAX_WINDOWS 64
-
-// the window table, by value in the kernel arguments (1 KiB): uniform reads, and the host has checked every row
-struct cofuse_tab {
-    long long off[COFUSE_MAX_WINDOWS];     // element offset of window k's (2,C,L_k,h,w) block from the base pointer
-    int s[COFUSE_MAX_WINDOWS];             // first frame
-    int len[COFUSE_MAX_WINDOWS];           // L_k
-};
-
-template <int E> struct halves;
-template <> struct halves<8> { typedef f16x8 type; };
-template <> struct halves<4> { typedef f16x4 type; };
-template <> struct halves<1> { typedef f16 type; };
-
-template <int E>
-__device__ __forceinline__ void load_halves(const f16* p, f16 (&v)[E]) {
-    if constexpr (E == 1) {
-        v[0] = p[0];
-    } else {
-        const typename halves<E>::type h = *(const typename halves<E>::type*)p;
-#pragma unroll
-        for (int j = 0; j < E; ++j) v[j] = h[j];
-    }
-}
-template <int E>
-__device__ __forceinline__ void store_halves(f16* p, const f16 (&v)[E]) {
-    if constexpr (E == 1) {
-        p[0] = v[0];
-    } else {
-        typename halves<E>::type h;
-#pragma unroll
-        for (int j = 0; j < E; ++j) h[j] = v[j];
-        *(typename halves<E>::type*)p = h;
-    }
-}
-
-// acc = first ? w * x : acc + w * x, the product and the sum rounded separately (blend_acc_kernel's guard: no fma_mix)
-__device__ __forceinline__ float fuse_term(float acc, float w, float x, bool first) {
-    float prod = __fmul_rn(w, x);
-    asm volatile("" : "+v"(prod));
-    return first ? prod : __fadd_rn(acc, prod);
-}
+#include "cofuse_common.h"   // the window table, the fuse, the host checks: shared with rescale.hip
 
 // MODE 0: DDIM; 1: DPM-Solver++ first order; 2: second order
 template <int MODE, int E>
@@ -76,26 +34,8 @@ __global__ __launch_bounds__(256) void cofuse_kernel(const f16* z, const f16* wi
     const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
     const int p = (int)((tile * 256u + threadIdx.x) * (unsigned)E);
     if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
-    float U[E], Cc[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) U[j] = Cc[j] = 0.f;
-    bool first = true;
-    for (int k = 0; k < K; ++k) {                                 // uniform over the block: t is
-        const int f = t - tab.s[k], L = tab.len[k];
-        if (f < 0 || f >= L) continue;
-        const float w = wn[(size_t)k * T + t];
-        const f16* up = win + tab.off[k] + ((size_t)c * L + f) * HW + p;
-        const f16* cp = up + (size_t)C * L * HW;
-        f16 u[E], cc[E];
-        load_halves<E>(up, u);
-        load_halves<E>(cp, cc);
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            U[j] = fuse_term(U[j], w, (float)u[j], first);
-            Cc[j] = fuse_term(Cc[j], w, (float)cc[j], first);
-        }
-        first = false;
-    }
+    float uf[E], cf[E];
+    cofuse_uc<E>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);      // uniform over the block: t is
     const size_t i = (size_t)line * HW + p;
     f16 x[E], xp[E];
     load_halves<E>(z + i, x);
@@ -103,63 +43,22 @@ __global__ __launch_bounds__(256) void cofuse_kernel(const f16* z, const f16* wi
     f16 o[E], x0[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        const float uf = (float)rn16(U[j]), cf = (float)rn16(Cc[j]);
-        if (MODE == 0) o[j] = cfg_ddim_elem(uf, cf, (float)x[j], kd);
-        else dpm_elem<true, MODE == 2>(uf, cf, (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, kp, x0[j], o[j]);
+        if (MODE == 0) o[j] = cfg_ddim_elem(uf[j], cf[j], (float)x[j], kd);
+        else dpm_elem<true, MODE == 2>(uf[j], cf[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, kp, x0[j], o[j]);
     }
     if (MODE != 0) store_halves<E>(x0_out + i, x0);
     store_halves<E>(out + i, o);
-}
-
-static inline bool co_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
 }
 
 static int cofuse_launch(const char* what, int mode, const void* z, const void* windows, size_t windows_elems,
                          const int64_t* win_off, const int* win_start, const int* win_len, int K, const float* wn,
                          const void* x0_prev, void* x0_out, void* lat_out, ddim_coef kd, dpm_coef kp, int C, int T, int HW,
                          vdx_stream_t stream) {
-    VDX_CHECK(z && windows && win_off && win_start && win_len && wn && lat_out, "%s: null pointer", what);
-    VDX_CHECK(C > 0 && T > 0 && HW > 0 && HW <= 1 << 30, "%s: bad shape C=%d T=%d HW=%d", what, C, T, HW);
-    VDX_CHECK(K >= 1 && K <= COFUSE_MAX_WINDOWS, "%s: %d windows, 1..%d are supported", what, K, COFUSE_MAX_WINDOWS);
-    VDX_CHECK(mode == 0 || x0_out, "%s: x0_out is null", what);
-    const size_t n = (size_t)C * T * HW, nb = n * sizeof(f16);
-    VDX_CHECK((size_t)C * T <= (size_t)1 << 30 && n <= (size_t)1 << 40, "%s: latent too large", what);
-    for (const void* ptr : {z, windows, (const void*)wn, x0_prev, (const void*)x0_out, (const void*)lat_out})
-        VDX_CHECK(((uintptr_t)ptr & 15) == 0, "%s: pointer not 16-byte aligned", what);
-    cofuse_tab tab = {};
-    int e = HW % 8 == 0 ? 8 : HW % 4 == 0 ? 4 : 1;
-    for (int k = 0; k < K; ++k) {
-        const long long off = (long long)win_off[k];
-        const int s = win_start[k], L = win_len[k];
-        VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= T - s, "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s, L, T);
-        const size_t need = 2 * (size_t)C * L * HW;
-        VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && need <= windows_elems - (size_t)off,
-                  "%s: window %d (offset %lld, %zu elements) leaves the buffer of %zu elements", what, k, off, need, windows_elems);
-        if (e == 8 && off % 8) e = off % 4 ? 1 : 4;
-        if (e == 4 && off % 4) e = 1;
-        tab.off[k] = off;
-        tab.s[k] = s;
-        tab.len[k] = L;
-    }
-    for (int t = 0; t < T; ++t) {                                 // a frame nobody predicts has no noise to step with
-        bool hit = false;
-        for (int k = 0; k < K && !hit; ++k) hit = t >= tab.s[k] && t - tab.s[k] < tab.len[k];
-        VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
-    }
-    const size_t wb = windows_elems * sizeof(f16);
-    VDX_CHECK(lat_out == z || !co_overlap(lat_out, nb, z, nb), "%s: lat_out overlaps z without being z", what);
-    VDX_CHECK(!co_overlap(lat_out, nb, windows, wb) && !co_overlap(lat_out, nb, wn, (size_t)K * T * sizeof(float)),
-              "%s: lat_out overlaps an input", what);
-    if (mode != 0) {
-        VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-        VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, z, nb) && !co_overlap(x0_out, nb, windows, wb) &&
-                      !co_overlap(x0_out, nb, wn, (size_t)K * T * sizeof(float)),
-                  "%s: x0_out overlaps an input or lat_out", what);
-        VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-                  "%s: x0_prev overlaps an output", what);
-    }
+    cofuse_tab tab;
+    int e;
+    if (int rc = cofuse_check(what, mode, true, z, windows, windows_elems, win_off, win_start, win_len, K, wn, x0_prev, x0_out, lat_out,
+                              C, T, HW, tab, e))
+        return rc;
     const size_t per_tile = 256 * (size_t)e;
     const size_t tiles_per_line = ((size_t)HW + per_tile - 1) / per_tile;
     const size_t blocks = tiles_per_line * C * T;

@@ -1,6 +1,7 @@
 // step_chains.h — the per-element rounding chains of the fused CFG + sampler steps, written once: elementwise.hip
 // (`vdx_cfg_ddim_step_f16`), dpm.hip (`vdx_cfg_dpm_step_f16`, `vdx_dpm_step_f16`) and codenoise.hip (the co-denoising steps,
-// which feed the same chains a fused noise) all call these, so the three cannot drift apart; likewise `add_noise`'s chain for
+// which feed the same chains a fused noise) and rescale.hip (the CFG-rescale steps: the same combine, `cfg_rescale_elem`,
+// the same tails) all call these, so they cannot drift apart; likewise `add_noise`'s chain for
 // vid2vid.hip and inpaint.hip (the masked step re-noises the kept cells with exactly video-to-video's start).  Every function is
 // __forceinline__: a kernel that calls one compiles to the instructions it had when the chain was written in its loop.
 #pragma once
@@ -29,10 +30,14 @@ __device__ __forceinline__ f16 add_noise_elem(float x0, float noise, float sa, f
 struct ddim_coef {
     float gs, s1, sa, sp, s1p;
 };
-__device__ __forceinline__ f16 cfg_ddim_elem(float u, float c, float x, const ddim_coef& k) {
+// the classifier-free-guidance combine both samplers start with:  g = u + gs*(c - u)
+__device__ __forceinline__ f16 cfg_combine(float u, float c, float gs) {
     const f16 t1 = rn16(__fsub_rn(c, u));                 // c - u
-    const f16 t2 = rn16(__fmul_rn(k.gs, (float)t1));      // gs * (c - u)
-    const f16 g = rn16(__fadd_rn(u, (float)t2));          // u + gs*(c-u)
+    const f16 t2 = rn16(__fmul_rn(gs, (float)t1));        // gs * (c - u)
+    return rn16(__fadd_rn(u, (float)t2));                 // u + gs*(c-u)
+}
+// the DDIM step on a (guided) noise g
+__device__ __forceinline__ f16 ddim_tail(f16 g, float x, const ddim_coef& k) {
     const f16 a1 = rn16(__fmul_rn(k.s1, (float)g));       // sqrt(1-a_t) * eps
     const f16 a2 = rn16(__fsub_rn(x, (float)a1));         // sample - ...
     const f16 x0 = rn16(__fmul_rn((float)a2, k.sa));      // * (1/sqrt(a_t)): torch-GPU divides by a CPU scalar this way
@@ -40,22 +45,27 @@ __device__ __forceinline__ f16 cfg_ddim_elem(float u, float c, float x, const dd
     const f16 b1 = rn16(__fmul_rn(k.sp, (float)x0));      // sqrt(a_prev) * x0
     return rn16(__fadd_rn((float)b1, (float)d));
 }
+__device__ __forceinline__ f16 cfg_ddim_elem(float u, float c, float x, const ddim_coef& k) {
+    return ddim_tail(cfg_combine(u, c, k.gs), x, k);
+}
+
+// ---- CFG rescale (Lin et al. 2023, section 3.4; diffusers `rescale_noise_cfg`; rescale.hip states the statistics) ------------
+//   g' = phi * (g * r) + (1 - phi) * g        r = std(c) / std(g), one fp16-valued scalar per sample; phi1 = fp32(1 - phi)
+__device__ __forceinline__ f16 cfg_rescale_elem(f16 g, float r, float phi, float phi1) {
+    const f16 h1 = rn16(__fmul_rn((float)g, r));          // g * r
+    const f16 h2 = rn16(__fmul_rn(phi, (float)h1));       // phi * (g * r)
+    const f16 h3 = rn16(__fmul_rn(phi1, (float)g));       // (1 - phi) * g
+    return rn16(__fadd_rn((float)h2, (float)h3));
+}
 
 // ---- DPM-Solver++ (2M, midpoint): dpm.hip's header states the expression ----------------------
 struct dpm_coef {
     float gs, s0, inv_a0, cx, d0, d1, inv_r0;
 };
 
-template <bool CFG, bool O2>
-__device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
-    f16 g;
-    if (CFG) {
-        const f16 t1 = rn16(__fsub_rn(c, u));                     // c - u
-        const f16 t2 = rn16(__fmul_rn(k.gs, (float)t1));          // gs * (c - u)
-        g = rn16(__fadd_rn(u, (float)t2));                        // u + gs*(c-u)
-    } else {
-        g = (f16)u;
-    }
+// the DPM-Solver++ step on a (guided) noise g
+template <bool O2>
+__device__ __forceinline__ void dpm_tail(f16 g, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
     const f16 a1 = rn16(__fmul_rn(k.s0, (float)g));               // s0 * e
     const f16 a2 = rn16(__fsub_rn(x, (float)a1));                 // x - s0*e
     const f16 x0 = rn16(__fmul_rn((float)a2, k.inv_a0));          // / a0
@@ -70,4 +80,9 @@ __device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, c
     }
     x0_out = x0;
     out = r;
+}
+
+template <bool CFG, bool O2>
+__device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
+    dpm_tail<O2>(CFG ? cfg_combine(u, c, k.gs) : (f16)u, x, x0p, k, x0_out, out);
 }

@@ -958,6 +958,127 @@ def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x
 
 
 # --------------------------------------------------------------------------------------------
+# CFG rescale (vdx/scheduler.py `guidance_rescale`, csrc/rescale.hip; no reference counterpart)
+RESCALE_MAX_ROWS = 256
+_RESCALE_WS: dict = {}  # the statistics pass's partial rows, per (device, stream)
+
+
+def rescale_factors(guidance_rescale):
+    """`guidance_rescale` -> the kernels' two scalars (phi, 1 - phi), each formed in Python double and rounded to fp32 ONCE (as
+    Python floats holding fp32 values); `ValueError` unless it is a finite number in [0, 1]."""
+    import math
+    import struct
+    if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float)) or not math.isfinite(guidance_rescale) \
+            or not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale!r}")
+    f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]     # noqa: E731
+    return f32(float(guidance_rescale)), f32(1.0 - float(guidance_rescale))
+
+
+def _rescale_buffers(what, rows: int, like, partials, stats_out):
+    """-> (partials, its pointer, stats_out's pointer or None): a float64 buffer of at least `rows` rows [4] (the per-stream
+    workspace when none is given), and the optional 3 halves."""
+    if rows < 1:
+        raise VdxError(f"{what}: empty or oversized sample")
+    if partials is None:
+        partials = _scratch(_RESCALE_WS, like.device, RESCALE_MAX_ROWS * 32, torch.float64)
+    elif partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < rows * 4:
+        raise VdxError(f"{what}: partials must be contiguous float64 with at least {rows} rows of 4")
+    if stats_out is not None and (stats_out.numel() < 3 or not stats_out.is_contiguous()):
+        raise VdxError(f"{what}: stats_out must be 3 contiguous halves")
+    return partials, _p(partials, "partials", torch.float64), _p(stats_out, "stats_out")
+
+
+def _eps2_like(what, eps2, lat):
+    if eps2.dim() < 1 or eps2.shape[0] != 2 or (lat is not None and (tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1)):
+        raise VdxError(f"{what}: eps2 must be (2,...) matching lat (1,...)")
+    if not (eps2.is_contiguous() and (lat is None or lat.is_contiguous())):
+        raise VdxError(f"{what}: tensors must be contiguous")
+
+
+def cfg_rescale_rows(n: int) -> int:
+    """Rows the statistics pass writes for a sample of n elements (`vdx_cfg_rescale_rows`): a function of n alone, <= 256."""
+    return int(_lib.load().vdx_cfg_rescale_rows(int(n)))
+
+
+def cofuse_cfg_rescale_rows(C_: int, T: int) -> int:
+    return int(_lib.load().vdx_cofuse_cfg_rescale_rows(int(C_), int(T)))
+
+
+def cfg_rescale_stats(eps2, guidance, partials=None):
+    """The statistics pass of the rescaled step (include/vdx.h `vdx_cfg_rescale_stats_f16`) -> float64 (rows, 4): every block's
+    [sum c, sum c*c, sum g, sum g*g] with g = u + gs*(c - u), eps2 = [u; c].  A view of the per-stream workspace unless `partials`
+    is given: valid until the next statistics pass on this stream."""
+    _eps2_like("cfg_rescale_stats", eps2, None)
+    n = eps2.numel() // 2
+    rows = cfg_rescale_rows(n)
+    partials, pp, _ = _rescale_buffers("cfg_rescale_stats", rows, eps2, partials, None)
+    _launch("vdx_cfg_rescale_stats_f16", _p(eps2, "eps2"), n, float(guidance), pp)
+    return partials.view(-1)[:rows * 4].view(rows, 4)
+
+
+def cfg_rescale_ddim_step(eps2, lat, guidance, rescale, coeffs, partials, out=None, stats_out=None):
+    """`cfg_ddim_step` with the guided noise rescaled by `rescale` (`rescale_factors`' pair) from `cfg_rescale_stats`' rows of
+    the same eps2 (`vdx_cfg_rescale_ddim_step_f16`).  `stats_out`: 3 halves that receive [sd_c, sd_g, r], or None."""
+    _eps2_like("cfg_rescale_ddim_step", eps2, lat)
+    if out is None:
+        out = torch.empty_like(lat)
+    _, pp, sp_ = _rescale_buffers("cfg_rescale_ddim_step", cfg_rescale_rows(lat.numel()), lat, partials, stats_out)
+    phi, phi1 = (float(v) for v in rescale)
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_cfg_rescale_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), pp, sp_, float(guidance), phi, phi1,
+            s1, sa, sp, s1p, lat.numel())
+    return out
+
+
+def cfg_rescale_dpm_step(eps2, lat, guidance, rescale, coeffs, partials, x0_prev=None, x0_out=None, out=None, stats_out=None):
+    """`cfg_dpm_step` with the rescaled guided noise (`vdx_cfg_rescale_dpm_step_f16`) -> (lat', x0)."""
+    _eps2_like("cfg_rescale_dpm_step", eps2, lat)
+    x0_out, out, c = _dpm_args("cfg_rescale_dpm_step", lat, x0_prev, x0_out, out, coeffs)
+    _, pp, sp_ = _rescale_buffers("cfg_rescale_dpm_step", cfg_rescale_rows(lat.numel()), lat, partials, stats_out)
+    phi, phi1 = (float(v) for v in rescale)
+    _launch("vdx_cfg_rescale_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
+            _p(out, "out"), pp, sp_, float(guidance), phi, phi1, *c, lat.numel())
+    return out, x0_out
+
+
+def cofuse_cfg_rescale_stats(z, windows, table, wn, guidance, partials=None):
+    """The statistics pass of the rescaled co-denoising step (`vdx_cofuse_cfg_rescale_stats_f16`): `cfg_rescale_stats` of the noise
+    fused from the windows as `cofuse_cfg_ddim_step` fuses it, over the whole clip.  z gives the shape only."""
+    head, tail = _cofuse_args("cofuse_cfg_rescale_stats", z, windows, table, wn)
+    rows = cofuse_cfg_rescale_rows(tail[0], tail[1])
+    partials, pp, _ = _rescale_buffers("cofuse_cfg_rescale_stats", rows, z, partials, None)
+    _launch("vdx_cofuse_cfg_rescale_stats_f16", *head[1:], float(guidance), pp, *tail)
+    return partials.view(-1)[:rows * 4].view(rows, 4)
+
+
+def cofuse_cfg_rescale_ddim_step(z, windows, table, wn, guidance, rescale, coeffs, partials, out=None, stats_out=None):
+    """`cofuse_cfg_ddim_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_ddim_step_f16`)."""
+    head, tail = _cofuse_args("cofuse_cfg_rescale_ddim_step", z, windows, table, wn)
+    if out is None:
+        out = torch.empty_like(z)
+    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+        raise VdxError("cofuse_cfg_rescale_ddim_step: out must be contiguous and shaped like z")
+    _, pp, sp_ = _rescale_buffers("cofuse_cfg_rescale_ddim_step", cofuse_cfg_rescale_rows(tail[0], tail[1]), z, partials, stats_out)
+    phi, phi1 = (float(v) for v in rescale)
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_cofuse_cfg_rescale_ddim_step_f16", *head, _p(out, "out"), pp, sp_, float(guidance), phi, phi1, s1, sa, sp, s1p, *tail)
+    return out
+
+
+def cofuse_cfg_rescale_dpm_step(z, windows, table, wn, guidance, rescale, coeffs, partials, x0_prev=None, x0_out=None, out=None,
+                                stats_out=None):
+    """`cofuse_cfg_dpm_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_dpm_step_f16`) -> (z', x0)."""
+    head, tail = _cofuse_args("cofuse_cfg_rescale_dpm_step", z, windows, table, wn)
+    x0_out, out, c = _dpm_args("cofuse_cfg_rescale_dpm_step", z, x0_prev, x0_out, out, coeffs)
+    _, pp, sp_ = _rescale_buffers("cofuse_cfg_rescale_dpm_step", cofuse_cfg_rescale_rows(tail[0], tail[1]), z, partials, stats_out)
+    phi, phi1 = (float(v) for v in rescale)
+    _launch("vdx_cofuse_cfg_rescale_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), pp, sp_,
+            float(guidance), phi, phi1, *c, *tail)
+    return out, x0_out
+
+
+# --------------------------------------------------------------------------------------------
 # Masked video-to-video (vdx/inpaint.py, csrc/inpaint.hip; no reference counterpart)
 def check_latent_mask(m, T: int, H: int, W: int, what: str = "latent mask"):
     """`m` is a contiguous uint8 (T,H,W) GPU tensor holding only 0 (keep) and 1 (regenerate); `VdxError` / `ValueError`

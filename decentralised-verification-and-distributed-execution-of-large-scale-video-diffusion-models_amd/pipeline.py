@@ -91,6 +91,12 @@ class DiffuserConfig:
     keep_frames: Optional[str] = None
     mask_rule: str = "nearest"             # pixel -> latent mask: "nearest" (pixel (8y, 8x)) | "any" (any of the cell's 64 pixels)
     mask_paste: bool = True                # the written frames' kept pixels are the input clip's bytes
+    # the guidance itself (both arguments of every diffusers pipeline call; unpinned).  `negative_prompt`: the text of the
+    # unconditional branch ("" = the empty prompt, as always).  `guidance_rescale`: phi of Lin et al. 2023 / diffusers'
+    # `rescale_noise_cfg`, in [0, 1]: the guided noise is pulled towards the conditional one's standard deviation, per sample and
+    # step (vdx/scheduler.py, csrc/rescale.hip).  0 = off, as always
+    negative_prompt: str = ""
+    guidance_rescale: float = 0.0
 
     @property
     def use_fsdp(self):
@@ -183,6 +189,17 @@ def check_freeu(cfg) -> Optional[dict]:
     return rec
 
 
+def check_guidance_rescale(cfg) -> float:
+    """`cfg.guidance_rescale` as a float (0.0 when off); `ValueError` before any work unless it is a finite number in [0, 1], and
+    when it is non-zero with `guidance_scale <= 1`: the job still runs the CFG combine there, as the reference does, but the
+    guided noise then lies between the two predictions and rescale has nothing to correct, so refuse rather than guess."""
+    phi = cfg.guidance_rescale
+    ops.rescale_factors(phi)
+    if phi != 0 and not cfg.guidance_scale > 1:
+        raise ValueError(f"guidance_rescale {phi!r} needs guidance_scale > 1, got {cfg.guidance_scale!r}")
+    return float(phi)
+
+
 SCHEDULERS = ("ddim", "dpmpp_2m")
 
 
@@ -267,6 +284,8 @@ class DistributedVideoDiffuser:
         next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off."""
         self.cfg = cfg
         check_freeu(cfg)
+        phi = check_guidance_rescale(cfg)
+        self._rescale_kw = {"guidance_rescale": phi} if phi != 0 else {}     # off: the step is called as it always was
         if check_free_init(cfg) > 1 and init_latents is not None:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
@@ -339,7 +358,7 @@ class DistributedVideoDiffuser:
         for i, t in enumerate(self.schedule):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb).sample
-            lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale)
+            lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale, **self._rescale_kw)
             if masked:
                 self._mask_step(lat, i, s)
         return lat
@@ -446,7 +465,12 @@ class DistributedVideoDiffuser:
         "exchange_s": seconds in the per-step gathers, "bytes_per_step": bytes this rank receives per step}.
 
         `latent_mask` ("allgather" only; both samplers, windowed and `co_denoise`, every mode): the constructor's docstring; `info`
-        is the one of the job without it."""
+        is the one of the job without it.
+
+        `guidance_rescale` != 0 (every exchange, mode, sampler and option above; the mask step runs after the rescaled step,
+        untouched): every scheduler step rescales its guided noise (vdx/scheduler.py `step_cfg`), the statistic being that of
+        the sample the step advances, a window's latent or with `co_denoise` the whole clip's, so no collective is added;
+        `info["guidance_rescale"]` holds the value."""
         cfg = self.cfg
         co = check_co_denoise(cfg, exchange)
         if self.latent_mask is not None and exchange == "halo":
@@ -499,6 +523,8 @@ class DistributedVideoDiffuser:
             info["free_init"] = rec
         if exchange == "halo":
             info["owned"] = [(s, e) for s, e, _ in out]
+        if self._rescale_kw:
+            info.update(self._rescale_kw)
         if co:
             info["co_denoise"] = {"windows": self._co_rec[0]["windows"], "steps": sum(r["steps"] for r in self._co_rec),
                                   "exchange_s": sum(r["exchange_s"] for r in self._co_rec),
@@ -557,7 +583,13 @@ def build_arg_parser():
     latent itself, and with `--mask_paste on` (default) the written frames' kept pixels are the input's bytes (`off`: the
     decoder's).  Refused with `--exchange halo` and when nothing is left to regenerate; the result and the JSON records then
     carry `"mask": {"rule", "paste", "kept_fraction", "kept_frames"}`; without the flags every launch, byte, CSV row and record
-    is the one it always was."""
+    is the one it always was.
+    `--negative_prompt TEXT` (diffusers' `negative_prompt`) is the text of the unconditional branch of classifier-free guidance
+    instead of the empty prompt; CLIP and MD-VQS prompt fidelity keep scoring against `--prompt` alone.  `--guidance_rescale PHI`
+    (Lin et al. 2023; diffusers' `guidance_rescale`, unpinned) rescales the guided noise of every step towards the conditional
+    prediction's standard deviation (vdx/scheduler.py, csrc/rescale.hip): PHI in [0, 1], refused with `--guidance_scale` <= 1; every
+    mode, exchange, scheduler and the other options.  The result and the JSON records then carry `"negative_prompt"` /
+    `"guidance_rescale"`; without the flags every launch, byte, CSV row and record is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -617,6 +649,10 @@ def build_arg_parser():
                    help="pixel mask -> latent mask: pixel (8y, 8x) decides a cell (nearest), or any of its 64 pixels (any)")
     p.add_argument("--mask_paste", choices=["on", "off"], default="on",
                    help="masked video-to-video: kept pixels of the written frames are the input clip's bytes (on) or the decoder's (off)")
+    p.add_argument("--negative_prompt", default="",
+                   help="text of the unconditional branch of classifier-free guidance (default: the empty prompt)")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="CFG rescale phi in [0, 1] (Lin et al. 2023): 0, the default, is off; needs --guidance_scale > 1")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -754,6 +790,11 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     freeu = check_freeu(cfg)
     co = check_co_denoise(cfg, exchange)
     pixel_mask = check_mask(cfg, exchange)      # None: the option is off
+    phi = check_guidance_rescale(cfg)
+    if not isinstance(cfg.negative_prompt, str):
+        raise ValueError(f"negative_prompt must be a string, got {cfg.negative_prompt!r}")
+    guidance = {**({"negative_prompt": cfg.negative_prompt} if cfg.negative_prompt else {}),
+                **({"guidance_rescale": phi} if phi != 0 else {})}       # the two keys the result and the records gain
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -771,7 +812,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     for m in (unet, pipe.text_encoder, pipe.vae):
         m.to(dev)
     tok = pipe.tokenizer
-    ids = tok([cfg.prompt, ""], padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
+    ids = tok([cfg.prompt, cfg.negative_prompt], padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
     with torch.no_grad():
         emb = pipe.text_encoder(ids.to(dev))[0]
     cond, uncond = emb[:1].contiguous(), emb[1:].contiguous()
@@ -831,7 +872,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
             **({"co_denoise": info["co_denoise"]} if co else {}),
-            **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {})}
+            **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -865,6 +906,8 @@ def main(argv=None) -> int:
             source["co_denoise"] = res["co_denoise"]
         if "mask" in res:
             source["mask"] = res["mask"]
+        guidance = {k: res[k] for k in ("negative_prompt", "guidance_rescale") if k in res}
+        source.update(guidance)
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -890,6 +933,7 @@ def main(argv=None) -> int:
                 rec["co_denoise"] = res["co_denoise"]
             if "mask" in res:
                 rec["mask"] = res["mask"]
+            rec.update(guidance)
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

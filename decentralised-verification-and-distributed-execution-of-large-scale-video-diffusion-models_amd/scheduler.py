@@ -29,6 +29,7 @@ class _SchedulerBase:
     order = 1
     timesteps = None
     _host_timesteps = None
+    rescale_stats = None
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -54,6 +55,14 @@ class _SchedulerBase:
                     return self._host_timesteps[idx]
             return int(timestep)
         return int(timestep)
+
+    def _rescale(self, guidance_rescale, device):
+        """CFG rescale (csrc/rescale.hip): `ops.rescale_factors(guidance_rescale)` and this scheduler's 3 halves on `device` that
+        every rescaled step leaves [sd_c, sd_g, r] in (`rescale_stats`: read it after the loop, never inside)."""
+        st = self.rescale_stats
+        if st is None or st.device != device:
+            st = self.rescale_stats = torch.zeros(8, dtype=torch.float16, device=device)
+        return ops.rescale_factors(guidance_rescale), st
 
     def add_noise(self, original_samples, noise, timesteps):
         """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
@@ -119,15 +128,29 @@ class DDIMScheduler(_SchedulerBase):
                              self.coefficients(self._host_timestep(timestep)))
         return SimpleNamespace(prev_sample=prev)
 
-    def step_cfg(self, noise2, timestep, sample, guidance_scale: float):
-        """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel."""
-        return ops.cfg_ddim_step(noise2, sample, guidance_scale, self.coefficients(self._host_timestep(timestep)))
+    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+        """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel.  `guidance_rescale` != 0 (Lin et al.
+        2023, diffusers' `rescale_noise_cfg`; csrc/rescale.hip): the guided noise is rescaled towards the standard deviation of
+        the conditional one over this sample, in two launches (the statistics, then the step) and without a host read."""
+        coeffs = self.coefficients(self._host_timestep(timestep))
+        if guidance_rescale == 0.0:
+            return ops.cfg_ddim_step(noise2, sample, guidance_scale, coeffs)
+        rescale, stats = self._rescale(guidance_rescale, sample.device)
+        sample = sample.contiguous()
+        part = ops.cfg_rescale_stats(noise2, guidance_scale)
+        return ops.cfg_rescale_ddim_step(noise2, sample, guidance_scale, rescale, coeffs, part, stats_out=stats)
 
-    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float):
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
         """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent `sample` on the noise fused from the
-        windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step`), one kernel."""
-        return ops.cofuse_cfg_ddim_step(sample.contiguous(), windows, table, wn, guidance_scale,
-                                        self.coefficients(self._host_timestep(timestep)))
+        windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step`), one kernel; with
+        `guidance_rescale` != 0 two, the statistics being those of the fused noise over the whole clip."""
+        coeffs = self.coefficients(self._host_timestep(timestep))
+        sample = sample.contiguous()
+        if guidance_rescale == 0.0:
+            return ops.cofuse_cfg_ddim_step(sample, windows, table, wn, guidance_scale, coeffs)
+        rescale, stats = self._rescale(guidance_rescale, sample.device)
+        part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
+        return ops.cofuse_cfg_rescale_ddim_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, stats_out=stats)
 
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
@@ -280,22 +303,35 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self._commit(i)
         return SimpleNamespace(prev_sample=new)
 
-    def step_cfg(self, noise2, timestep, sample, guidance_scale: float):
-        """Fused `u + gs*(c-u)` + step in one kernel (`vdx_cfg_dpm_step_f16`)."""
+    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+        """Fused `u + gs*(c-u)` + step in one kernel (`vdx_cfg_dpm_step_f16`); with `guidance_rescale` != 0 the statistics
+        pass and `vdx_cfg_rescale_dpm_step_f16` (as `DDIMScheduler.step_cfg`)."""
         sample = sample.contiguous()
         i, prev, x0_out = self._plan(timestep, sample)
-        new, _ = ops.cfg_dpm_step(noise2, sample, guidance_scale, self.coefficients(i, prev is not None), x0_prev=prev,
-                                  x0_out=x0_out)
+        coeffs = self.coefficients(i, prev is not None)
+        if guidance_rescale == 0.0:
+            new, _ = ops.cfg_dpm_step(noise2, sample, guidance_scale, coeffs, x0_prev=prev, x0_out=x0_out)
+        else:
+            rescale, stats = self._rescale(guidance_rescale, sample.device)
+            part = ops.cfg_rescale_stats(noise2, guidance_scale)
+            new, _ = ops.cfg_rescale_dpm_step(noise2, sample, guidance_scale, rescale, coeffs, part, x0_prev=prev, x0_out=x0_out,
+                                              stats_out=stats)
         self._commit(i)
         return new
 
-    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float):
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
         """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent on the noise fused from the windows' raw
         UNet outputs (`vdx_cofuse_cfg_dpm_step_f16`), one kernel.  ONE x0 history of the whole clip's shape, planned and
-        committed as for `step_cfg`; `reset()` once per round."""
+        committed as for `step_cfg`; `reset()` once per round.  `guidance_rescale` as for `DDIMScheduler.step_cfg_windows`."""
         sample = sample.contiguous()
         i, prev, x0_out = self._plan(timestep, sample)
-        new, _ = ops.cofuse_cfg_dpm_step(sample, windows, table, wn, guidance_scale, self.coefficients(i, prev is not None),
-                                         x0_prev=prev, x0_out=x0_out)
+        coeffs = self.coefficients(i, prev is not None)
+        if guidance_rescale == 0.0:
+            new, _ = ops.cofuse_cfg_dpm_step(sample, windows, table, wn, guidance_scale, coeffs, x0_prev=prev, x0_out=x0_out)
+        else:
+            rescale, stats = self._rescale(guidance_rescale, sample.device)
+            part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
+            new, _ = ops.cofuse_cfg_rescale_dpm_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, x0_prev=prev,
+                                                     x0_out=x0_out, stats_out=stats)
         self._commit(i)
         return new

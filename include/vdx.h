@@ -361,6 +361,41 @@ int vdx_cofuse_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
                                 void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
                                 float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
+/* Classifier-free guidance with CFG rescale (Lin et al. 2023, section 3.4; diffusers `rescale_noise_cfg`; no reference counterpart,
+ * opt-in: `guidance_rescale` of vdx/scheduler.py, csrc/rescale.hip, restated in tests/rescale_ref.py).  With g the combine above,
+ * over the N = n elements of the sample (fp64 sums S1 = sum x, S2 = sum x*x of the fp16 values):
+ *   var(x) = (N*S2 - S1*S1) / (N*(N-1))    (fp64, each operation rounded; 0 for a constant x),   sd_x = fp16(sqrt(var(x)))
+ *   r = fp16(fp32(sd_c) / fp32(sd_g)),     g' = fp16(fp16(phi * fp16(g * r)) + fp16(phi1 * g)),  phi1 = fp32(1 - rescale)
+ * and g' takes g's place in the step.  No clamp: N = 1, sd_g = 0, NaN and infinity give what the lines give.  Two launches:
+ * the statistics pass writes `rows` rows [S1c, S2c, S1g, S2g] of doubles (rows: the query next to it, a function of the shapes
+ * alone, <= 256; fixed summation order, no atomics), the step adds them in ascending order in every block and forms r itself.
+ * stats_out: NULL, or 3 halves that receive [sd_c, sd_g, r].  phi and phi1 outside [0, 1] are refused.  Everything else as
+ * for the step of the same name without "rescale"; partials 16-byte aligned and apart from every other buffer.              */
+int vdx_cfg_rescale_rows(size_t n);
+int vdx_cfg_rescale_stats_f16(const void* eps2, size_t n, float guidance, double* partials, vdx_stream_t stream);
+int vdx_cfg_rescale_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, const double* partials, void* stats_out,
+                                  float guidance, float phi, float phi1, float sqrt_one_minus_at, float sqrt_at,
+                                  float sqrt_aprev, float sqrt_one_minus_aprev, size_t n, vdx_stream_t stream);
+int vdx_cfg_rescale_dpm_step_f16(const void* eps2, const void* lat, const void* x0_prev, void* x0_out, void* lat_out,
+                                 const double* partials, void* stats_out, float guidance, float phi, float phi1, float c_s0,
+                                 float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, size_t n,
+                                 vdx_stream_t stream);
+/* The same for co-denoising: U and Cc fused from the windows exactly as in vdx_cofuse_cfg_ddim_step_f16 (in both launches), the
+ * statistics those of the fused Cc and of g(U, Cc) over the whole clip, N = C*T*HW.                                          */
+int vdx_cofuse_cfg_rescale_rows(int C, int T);
+int vdx_cofuse_cfg_rescale_stats_f16(const void* windows, size_t windows_elems, const int64_t* win_off, const int* win_start,
+                                     const int* win_len, int K, const float* wn, float guidance, double* partials, int C, int T,
+                                     int HW, vdx_stream_t stream);
+int vdx_cofuse_cfg_rescale_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                         const int* win_start, const int* win_len, int K, const float* wn, void* lat_out,
+                                         const double* partials, void* stats_out, float guidance, float phi, float phi1,
+                                         float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float sqrt_one_minus_aprev,
+                                         int C, int T, int HW, vdx_stream_t stream);
+int vdx_cofuse_cfg_rescale_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                        const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                        void* x0_out, void* lat_out, const double* partials, void* stats_out, float guidance,
+                                        float phi, float phi1, float c_s0, float c_inv_a0, float c_x, float c_d0, float c_d1,
+                                        float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
 /* Masked video-to-video (keep frames or regions of --init_video, generate the rest; no reference counterpart, opt-in:
  * vdx/inpaint.py, csrc/inpaint.hip).  Masks are uint8, 1 = regenerate, 0 = keep; every entry point is a SELECT of bits (no
  * arithmetic on the mask: no 0*inf, -0 keeps its sign, NaN / inf stay in their element).  tests/inpaint_ref.py states it.

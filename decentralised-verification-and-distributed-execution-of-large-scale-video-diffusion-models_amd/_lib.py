@@ -149,6 +149,13 @@ SIGNATURES = {
     "vdx_cofuse_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
     "vdx_cofuse_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
                                          _vp]),
+    # spatially tiled co-denoising: a tile's input and the fused whole-clip steps over time x row x column windows (no reference
+    # counterpart; vdx/codenoise.py, csrc/cotile.hip)
+    "vdx_cfg_input_tile_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vdx_cotile_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _f, _f, _f,
+                                          _f, _f, _i, _i, _i, _i, _vp]),
+    "vdx_cotile_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _f,
+                                         _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _vp]),
     # CFG rescale: the statistics pass and the fused steps, plain and co-fused (no reference counterpart; vdx/scheduler.py
     # `guidance_rescale`, csrc/rescale.hip)
     "vdx_cfg_rescale_rows": (_i, [_sz]),

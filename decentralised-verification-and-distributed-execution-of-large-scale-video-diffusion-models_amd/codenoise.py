@@ -12,12 +12,17 @@ Pinned (tests/test_codenoise_gpu.py, bit for bit): the kernels against the torch
 one-window job against `DistributedVideoDiffuser.denoise`, a several-window job against a Python loop over the same windows, and
 a two-rank job against the one-rank job.  NOT pinned and not claimed: agreement with any external implementation, and any
 seam-quality effect on real Zeroscope weights.
+
+With `DiffuserConfig(tile=(TH, TW))` / `--tile TH TW` the windows are additionally tiled in space (MultiDiffusion's original form;
+csrc/cotile.hip): a window is the product of a time window, a row band and a column band, every UNet call is a crop of one tile's
+size, and the fused step averages with the product of three per-axis normalised weights (`tile_plan`, `check_tile` below).  Pinned
+in tests/test_cotile_gpu.py against tests/cotile_ref.py; again no external implementation and no quality claim.
 """
 from __future__ import annotations
 
 import time
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -80,29 +85,153 @@ def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
     return bool(getattr(cfg, "co_denoise", False))
 
 
-def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
+# ---- spatial tiles (MultiDiffusion's original form; csrc/cotile.hip) ------------------------------------------------------------
+def tile_starts(n: int, tile: int, overlap: int) -> List[int]:
+    """First cells of the tiles of `tile` cells that cover `n` cells: 0, tile - overlap, 2 (tile - overlap), ..., the last one
+    moved back so that its tile ends at `n` (all tiles have ONE size, so every UNet call and every slot of the packed buffer has
+    one shape); a start the move repeats is dropped.  `n == tile` gives [0]."""
+    if not 1 <= tile <= n or not 0 <= overlap < tile:
+        raise ValueError(f"tile_starts: a tile of {tile} cells (overlap {overlap}) for {n} cells: need 1 <= tile <= n, 0 <= overlap < tile")
+    starts, step = [], tile - overlap
+    for s in range(0, n, step):
+        s = min(s, n - tile)
+        if not starts or s != starts[-1]:
+            starts.append(s)
+        if s == n - tile:
+            break
+    return starts
+
+
+def axis_weights(n: int, tile: int, overlap: int, starts: List[int]) -> torch.Tensor:
+    """fp32 (len(starts), n): `fuse_weights(tile, overlap)` of every tile along one axis, normalised over the tiles that cover a
+    cell in float64 and rounded to fp32 once, exactly as `window_table` does along time: zero outside a tile, exactly 1.0 where
+    one tile covers a cell.  A cell in no tile is a `ValueError`."""
+    raw = np.zeros((len(starts), n), dtype=np.float64)
+    for k, s in enumerate(starts):
+        if not 0 <= s <= n - tile:
+            raise ValueError(f"axis_weights: tile {k} = [{s}, {s + tile}) leaves the {n} cells")
+        raw[k, s:s + tile] = fuse_weights(tile, overlap)
+    total = raw.sum(axis=0)
+    if (total <= 0).any():
+        raise ValueError(f"axis_weights: cell {int(np.argmin(total > 0))} is in no tile")
+    return torch.from_numpy((raw / total).astype(np.float32))
+
+
+@dataclass(frozen=True)
+class TilePlan:
+    """The spatial windows of a tiled job, in latent cells: tiles of `th` x `tw` at rows `ys` and columns `xs` (the windows are the
+    Cartesian product time x `ys` x `xs`, fused in ascending (kt, ky, kx)), and the per-axis normalised weights `wyn` (ny, h),
+    `wxn` (nx, w): the product of three weights that are each normalised is normalised."""
+    th: int
+    tw: int
+    oy: int
+    ox: int
+    ys: Tuple[int, ...]
+    xs: Tuple[int, ...]
+    wyn: torch.Tensor
+    wxn: torch.Tensor
+
+    @property
+    def count(self) -> int:
+        return len(self.ys) * len(self.xs)
+
+    @property
+    def boxes(self) -> List[Tuple[int, int, int, int]]:
+        """(y0, th, x0, tw) per tile, in the order of the packed buffer's slots: ky-major."""
+        return [(y, self.th, x, self.tw) for y in self.ys for x in self.xs]
+
+    def grid(self, stride: int, device) -> "ops.TileGrid":
+        return ops.TileGrid(stride, self.ys, self.xs, self.th, self.tw, self.wyn.to(device), self.wxn.to(device))
+
+    def record(self, time_windows: int) -> dict:
+        return {"tile": [self.th, self.tw], "overlap": [self.oy, self.ox], "grid": [len(self.ys), len(self.xs)],
+                "windows": time_windows * self.count}
+
+
+def tile_plan(h: int, w: int, th: int, tw: int, oy: int, ox: int) -> TilePlan:
+    """The tiles of a `h` x `w` latent frame (everything in latent cells); more than `ops.COTILE_MAX_TILES` is a `ValueError`."""
+    ys, xs = tile_starts(h, th, oy), tile_starts(w, tw, ox)
+    if len(ys) * len(xs) > ops.COTILE_MAX_TILES:
+        raise ValueError(f"tile_plan: {len(ys)} x {len(xs)} tiles, the fused step takes {ops.COTILE_MAX_TILES}")
+    return TilePlan(th, tw, oy, ox, tuple(ys), tuple(xs), axis_weights(h, th, oy, ys), axis_weights(w, tw, ox, xs))
+
+
+MIN_TILE_CELLS = 8   # 2^(levels - 1) of the four-level UNet: below it the deepest level is a single ceil-rounded cell per side
+
+
+def check_tile(cfg, exchange: str = "allgather") -> Optional[Tuple[int, int, int, int]]:
+    """`cfg.tile` / `cfg.tile_overlap` (pixels) as (th, tw, oy, ox) in latent cells, None when off; `ValueError` before any work
+    when the job cannot run it: tiling exists only as co-denoising (the windowed job's ramp blend has no spatial form), never
+    with the halo exchange, not with `guidance_rescale` (its statistics pass has no tiled fuse yet); a tile is two multiples of 8
+    pixels, no larger than the frame and no smaller than the UNet takes for a frame (`MIN_TILE_CELLS` latent cells a side); the
+    overlap, multiples of 8 pixels too, lies in [0, tile) per axis and defaults to a quarter of the tile in latent cells."""
+    tile, ov = getattr(cfg, "tile", None), getattr(cfg, "tile_overlap", None)
+    if tile is None:
+        if ov is not None:
+            raise ValueError("tile_overlap needs tile")
+        return None
+
+    def pair(v, what):
+        if not isinstance(v, (tuple, list)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, int) for x in v):
+            raise ValueError(f"{what} must be two integers (pixels), got {v!r}")
+        if any(x % 8 for x in v):
+            raise ValueError(f"{what} {tuple(v)} must be multiples of 8 pixels (one latent cell)")
+        return v[0] // 8, v[1] // 8
+
+    if not getattr(cfg, "co_denoise", False):
+        raise ValueError("tile needs co_denoise: tiles meet at every step in the fused noise; the windowed job's blend has no tiled form")
+    if exchange == "halo":
+        raise ValueError("tile needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
+    if getattr(cfg, "guidance_rescale", 0.0) != 0:
+        raise ValueError("tile and guidance_rescale exclude each other: the rescale's statistics pass has no tiled form yet")
+    th, tw = pair(tile, "tile")
+    h, w = cfg.height // 8, cfg.width // 8
+    if cfg.height % 8 or cfg.width % 8:
+        raise ValueError(f"tile: the frame {cfg.height}x{cfg.width} must be a multiple of 8 pixels")
+    if th > h or tw > w:
+        raise ValueError(f"tile {tuple(tile)} is larger than the frame {cfg.height}x{cfg.width}")
+    if th < MIN_TILE_CELLS or tw < MIN_TILE_CELLS:
+        raise ValueError(f"tile {tuple(tile)} is smaller than the UNet takes for a frame: {MIN_TILE_CELLS * 8} pixels a side at least")
+    oy, ox = (th // 4, tw // 4) if ov is None else pair(ov, "tile_overlap")
+    if not (0 <= oy < th and 0 <= ox < tw):
+        raise ValueError(f"tile_overlap {(oy * 8, ox * 8)} must lie in [0, tile) per axis, tile is {tuple(tile)}")
+    ny, nx = len(tile_starts(h, th, oy)), len(tile_starts(w, tw, ox))
+    if ny * nx > ops.COTILE_MAX_TILES:
+        raise ValueError(f"tile {tuple(tile)}: {ny} x {nx} tiles, the fused step takes {ops.COTILE_MAX_TILES}")
+    return th, tw, oy, ox
+
+
+def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[TilePlan] = None):
     """One co-denoised sampling round of `d` (a `DistributedVideoDiffuser`) from the whole clip's start latent -> (z.float(),
     the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  Per step: this rank's windows go
     through `ops.cfg_input_window` -> UNet into one packed buffer `[per_rank][2][C][cp.chunk][h][w]` (a window shorter than the
     chunk fills the front of its slot; the rest is never read); with more than one rank, one `all_gather_into_tensor` of that
     buffer; then every rank runs the fused step on its own copy of z (identical bits on every rank: no broadcast; with
     `guidance_rescale` the step's statistic is taken over that same gathered buffer, so every rank gets the same r).  There is no
-    final blend, so the zeroed first and last frame of the reference's ramp blend does not occur."""
+    final blend, so the zeroed first and last frame of the reference's ramp blend does not occur.
+    `tiles` (a `TilePlan`, spatially tiled co-denoising): every window of this rank is run once per tile, through
+    `ops.cfg_input_tile` on the tile's crop of z (and of the whole frame's ctx), into `tiles.count` consecutive slots of the
+    packed buffer `[per_rank][ny nx][2][C][cp.chunk][th][tw]`; the step is `step_cfg_tiles`; the record gains `"tile"`.  The
+    ranks' shares, the repeated tail window and the one gather per step are as without it."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
     table = window_table(cp, T)
     per, world, rank = cp.per_rank, d.world, d.rank
-    slot = 2 * C * cp.chunk * H * W
-    rows = table.rows(world, per, slot)
+    boxes = [None] if tiles is None else tiles.boxes              # None: the whole frame, as always
+    nt = len(boxes)
+    area = H * W if tiles is None else tiles.th * tiles.tw
+    slot = 2 * C * cp.chunk * area
+    rows = table.rows(world, per, nt * slot)
     wn = table.wn.to(start.device)
+    grid = None if tiles is None else tiles.grid(slot, start.device)
     mine = cp.for_rank(rank)
     emb = torch.cat([d.uncond_emb, d.cond_emb], dim=0)
-    local = torch.zeros((per, slot), dtype=torch.float16, device=start.device)
-    packed = torch.zeros((world, per, slot), dtype=torch.float16, device=start.device) if world > 1 else local
+    local = torch.zeros((per, nt * slot), dtype=torch.float16, device=start.device)
+    packed = torch.zeros((world, per, nt * slot), dtype=torch.float16, device=start.device) if world > 1 else local
     payload_step = sum((e - s) * C * 2 for s, e in mine)          # the reference's formula (:194), per exchange
-    actual_step = sum(2 * C * (e - s) * H * W * 2 for s, e in mine)
-    bytes_step = (world - 1) * per * slot * 2
+    actual_step = sum(2 * C * (e - s) * area * nt * 2 for s, e in mine)
+    bytes_step = (world - 1) * per * nt * slot * 2
     z = start.clone()
     reset = getattr(sched, "reset", None)
     if reset is not None:                                         # ONE x0 history for the whole clip, fresh per round
@@ -112,9 +241,13 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
     t_round = time.time()
     for i, t in enumerate(d.schedule):
         for j, (s, e) in enumerate(mine):
-            x = ops.cfg_input_window(z, d.ctx, cfg.context_weight, s, e)
-            noise = d.unet(x, t, encoder_hidden_states=emb).sample
-            local[j, :noise.numel()].copy_(noise.reshape(-1))
+            for k, box in enumerate(boxes):
+                if box is None:
+                    x = ops.cfg_input_window(z, d.ctx, cfg.context_weight, s, e)
+                else:
+                    x = ops.cfg_input_tile(z, d.ctx, cfg.context_weight, s, e, *box)
+                noise = d.unet(x, t, encoder_hidden_states=emb).sample
+                local[j, k * slot:k * slot + noise.numel()].copy_(noise.reshape(-1))
         delay = emu_gather_delay_s(payload_step, cfg)             # per step: one exchange per step is what the method costs
         if delay > 0:
             d._sync()
@@ -126,7 +259,10 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
             dist.all_gather_into_tensor(packed.view(-1), local.view(-1))
             d._sync()
             spent["net_gather_s"] += time.time() - t0
-        z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale, **d._rescale_kw)
+        if grid is None:
+            z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale, **d._rescale_kw)
+        else:
+            z = sched.step_cfg_tiles(packed, rows, wn, grid, t, z, cfg.guidance_scale)
         if d.latent_mask is not None:                             # masked video-to-video (vdx/inpaint.py): the whole clip, s = 0
             d._mask_step(z, i, 0)
         spent["network_bytes"] += bytes_step
@@ -137,4 +273,6 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan):
     d._sync()
     spent["denoise_s"] = time.time() - t_round - spent["net_gather_s"] - spent["emu_gather_delay_s"]
     rec = {"windows": len(table.fused), "steps": len(d.schedule), "exchange_s": spent["net_gather_s"], "bytes_per_step": bytes_step}
+    if tiles is not None:
+        rec["tile"] = tiles.record(len(table.fused))
     return z.float(), spent, rec

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -953,6 +953,90 @@ def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x
     head, tail = _cofuse_args("cofuse_cfg_dpm_step", z, windows, table, wn)
     x0_out, out, c = _dpm_args("cofuse_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
     _launch("vdx_cofuse_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
+            *c, *tail)
+    return out, x0_out
+
+
+# --------------------------------------------------------------------------------------------
+# Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`, csrc/cotile.hip; no reference counterpart)
+COTILE_MAX_TILES = 64
+
+
+class TileGrid(NamedTuple):
+    """The spatial half of a tiled step's window table: `stride` elements between consecutive tiles' blocks of one time window
+    (tile (ky, kx) at `(ky * len(xs) + kx) * stride`), the bands' first rows `ys` and columns `xs` (host integers), the tile's
+    size `th` x `tw`, and the per-axis normalised weights `wyn` (ny, H), `wxn` (nx, W), fp32 on the device."""
+    stride: int
+    ys: Tuple[int, ...]
+    xs: Tuple[int, ...]
+    th: int
+    tw: int
+    wyn: torch.Tensor
+    wxn: torch.Tensor
+
+
+def cfg_input_tile(z, ctx, weight, s: int, e: int, y0: int, th: int, x0: int, tw: int, out=None):
+    """`cfg_input(z[:, :, s:e, y0:y0+th, x0:x0+tw], ctx[..., y0:y0+th, x0:x0+tw], weight)` without the slice copies: one launch
+    writes the contiguous (2,C,e-s,th,tw) UNet input of one tile of one window, TAGGED as a CFG duplicate exactly as
+    `cfg_input_window` tags its result."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError("cfg_input_tile: z must be contiguous (1,C,T,H,W)")
+    _, Cc, T, H, W = z.shape
+    s, e, y0, th, x0, tw = (int(v) for v in (s, e, y0, th, x0, tw))
+    if not 0 <= s < e <= T:
+        raise VdxError(f"cfg_input_tile: bad range [{s},{e}) of {T} frames")
+    if not (1 <= th <= H and 0 <= y0 <= H - th and 1 <= tw <= W and 0 <= x0 <= W - tw):
+        raise VdxError(f"cfg_input_tile: tile [{y0},{y0}+{th}) x [{x0},{x0}+{tw}) leaves the {H}x{W} frame")
+    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
+        raise VdxError("cfg_input_tile: ctx must be contiguous (1,C,1,H,W)")
+    if out is None:
+        out = torch.empty((2, Cc, e - s, th, tw), dtype=torch.float16, device=z.device)
+    elif tuple(out.shape) != (2, Cc, e - s, th, tw) or not out.is_contiguous():
+        raise VdxError("cfg_input_tile: out must be contiguous (2,C,e-s,th,tw)")
+    _launch("vdx_cfg_input_tile_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H, W, s, e, y0, th, x0, tw)
+    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
+    return out
+
+
+def _cotile_args(what, z, windows, table, wn, tiles: TileGrid):
+    """Shared checks of the two tiled steps -> the launch's leading arguments (those of `_cofuse_args`, then the tile grid) and
+    its trailing shape.  The library checks every row and band against the shape and the buffer."""
+    head, (Cc, T, _) = _cofuse_args(what, z, windows, table, wn)
+    H, W = z.shape[3:]
+    ny, nx = len(tiles.ys), len(tiles.xs)
+    if ny < 1 or nx < 1 or ny * nx > COTILE_MAX_TILES:
+        raise VdxError(f"{what}: {ny} x {nx} tiles, at most {COTILE_MAX_TILES} are supported")
+    if tuple(tiles.wyn.shape) != (ny, H) or tuple(tiles.wxn.shape) != (nx, W) or not (tiles.wyn.is_contiguous() and tiles.wxn.is_contiguous()):
+        raise VdxError(f"{what}: wyn must be contiguous fp32 ({ny},{H}) and wxn ({nx},{W})")
+    if int(tiles.stride) < 0:
+        raise VdxError(f"{what}: bad tile stride {tiles.stride}")
+    ys = (C.c_int32 * ny)(*(int(v) for v in tiles.ys))
+    xs = (C.c_int32 * nx)(*(int(v) for v in tiles.xs))
+    grid = (int(tiles.stride), ys, ny, _p(tiles.wyn, "wyn", torch.float32), xs, nx, _p(tiles.wxn, "wxn", torch.float32),
+            int(tiles.th), int(tiles.tw))
+    return head + grid, (Cc, T, H, W)
+
+
+def cotile_cfg_ddim_step(z, windows, table, wn, tiles: TileGrid, guidance, coeffs, out=None):
+    """One tiled co-denoising DDIM step of the whole clip (include/vdx.h `vdx_cotile_cfg_ddim_step_f16`): `table`, `wn` as for
+    `cofuse_cfg_ddim_step`, each time window's block now holding the `len(ys) * len(xs)` tiles' (2,C,L_k,th,tw) outputs at
+    `tiles.stride` from one another; the noise is averaged per cell with `wn[kt][t] * wyn[ky][y] * wxn[kx][x]` and fed to
+    `cfg_ddim_step`'s chain.  `out` may be `z`."""
+    head, tail = _cotile_args("cotile_cfg_ddim_step", z, windows, table, wn, tiles)
+    if out is None:
+        out = torch.empty_like(z)
+    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+        raise VdxError("cotile_cfg_ddim_step: out must be contiguous and shaped like z")
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_cotile_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
+    return out
+
+
+def cotile_cfg_dpm_step(z, windows, table, wn, tiles: TileGrid, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
+    """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cotile_cfg_dpm_step_f16`) -> (z', x0)."""
+    head, tail = _cotile_args("cotile_cfg_dpm_step", z, windows, table, wn, tiles)
+    x0_out, out, c = _dpm_args("cotile_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
+    _launch("vdx_cotile_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
             *c, *tail)
     return out, x0_out
 

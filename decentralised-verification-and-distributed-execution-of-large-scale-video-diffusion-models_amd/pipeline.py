@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .codenoise import check_co_denoise, co_denoise_round
+from .codenoise import check_co_denoise, check_tile, co_denoise_round, tile_plan
 from .inpaint import check_mask, known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
@@ -97,6 +97,12 @@ class DiffuserConfig:
     # step (vdx/scheduler.py, csrc/rescale.hip).  0 = off, as always
     negative_prompt: str = ""
     guidance_rescale: float = 0.0
+    # spatially tiled co-denoising (vdx/codenoise.py `tile_plan`, csrc/cotile.hip; MultiDiffusion along space, unpinned; needs
+    # `co_denoise`): every window is run per tile of `tile` = (TH, TW) pixels, a crop at a size the UNet was trained at, and the
+    # tiles' noise predictions are averaged where they overlap.  `tile_overlap` = (OY, OX) pixels, None = a quarter of the tile.
+    # All four are multiples of 8.  None = the UNet runs on the whole frame, as always
+    tile: Optional[Tuple[int, int]] = None
+    tile_overlap: Optional[Tuple[int, int]] = None
 
     @property
     def use_fsdp(self):
@@ -290,6 +296,7 @@ class DistributedVideoDiffuser:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
         self._co_rec: List[dict] = []                              # co_denoise: the rounds' records of the last call
+        self._tiles = None                                         # tile: the spatial plan of the last call
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
         self.uncond_emb, self.cond_emb = uncond_emb, cond_emb
@@ -385,6 +392,8 @@ class DistributedVideoDiffuser:
         originals' bytes before the copy to the host."""
         frames = []
         T = lat.shape[2]
+        if self.cfg.tile is not None:   # a tiled job's frame may be many times the headline's: keep the headline decode's activations
+            batch = min(batch, max(1, 8 * 576 * 1024 // (self.cfg.height * self.cfg.width)))
         for i0 in range(0, T, batch):
             z = lat[0, :, i0:i0 + batch].permute(1, 0, 2, 3) / 0.18215
             u8 = vae.decode_frames_u8(z.to(self.cfg.device, torch.float16).contiguous())
@@ -404,7 +413,7 @@ class DistributedVideoDiffuser:
         With `cfg.co_denoise` the round is `codenoise.co_denoise_round` instead: one latent, the windows meet at every step, no
         blend; its record is added to `self._co_rec`."""
         if self.cfg.co_denoise:
-            out, spent, rec = co_denoise_round(self, start, cp)
+            out, spent, rec = co_denoise_round(self, start, cp, *((self._tiles,) if self._tiles is not None else ()))
             self._co_rec.append(rec)
             return out, spent
         _, C, T, H, W = start.shape
@@ -470,9 +479,17 @@ class DistributedVideoDiffuser:
         `guidance_rescale` != 0 (every exchange, mode, sampler and option above; the mask step runs after the rescaled step,
         untouched): every scheduler step rescales its guided noise (vdx/scheduler.py `step_cfg`), the statistic being that of
         the sample the step advances, a window's latent or with `co_denoise` the whole clip's, so no collective is added;
-        `info["guidance_rescale"]` holds the value."""
+        `info["guidance_rescale"]` holds the value.
+
+        `tile` (with `co_denoise` only; both samplers, every mode, `init_latents`, `latent_mask`, every FreeInit iteration, `freeu`;
+        refused with "halo" and with `guidance_rescale`): every window of every round is run once per spatial tile
+        (`codenoise.tile_plan`; with `hybrid_ctx` each tile reads its crop of the whole frame's context) and the fused step
+        averages over time x row x column windows; `info["tile"]` = {"tile": [th, tw], "overlap": [oy, ox] (latent cells),
+        "grid": [ny, nx], "windows": fused windows in all}.  A tile equal to the frame is plain co-denoising, bit for bit."""
         cfg = self.cfg
         co = check_co_denoise(cfg, exchange)
+        tile = check_tile(cfg, exchange)
+        self._tiles = tile_plan(cfg.height // 8, cfg.width // 8, *tile) if tile is not None else None
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         self._co_rec = []
@@ -529,6 +546,8 @@ class DistributedVideoDiffuser:
             info["co_denoise"] = {"windows": self._co_rec[0]["windows"], "steps": sum(r["steps"] for r in self._co_rec),
                                   "exchange_s": sum(r["exchange_s"] for r in self._co_rec),
                                   "bytes_per_step": self._co_rec[0]["bytes_per_step"]}
+            if tile is not None:
+                info["tile"] = self._co_rec[0]["tile"]
         return out, info
 
 
@@ -589,7 +608,14 @@ def build_arg_parser():
     (Lin et al. 2023; diffusers' `guidance_rescale`, unpinned) rescales the guided noise of every step towards the conditional
     prediction's standard deviation (vdx/scheduler.py, csrc/rescale.hip): PHI in [0, 1], refused with `--guidance_scale` <= 1; every
     mode, exchange, scheduler and the other options.  The result and the JSON records then carry `"negative_prompt"` /
-    `"guidance_rescale"`; without the flags every launch, byte, CSV row and record is the one it always was."""
+    `"guidance_rescale"`; without the flags every launch, byte, CSV row and record is the one it always was.
+    `--tile TH TW` (with `--co_denoise`; no reference counterpart; MultiDiffusion along space, unpinned) runs the UNet on overlapping
+    TH x TW pixel tiles of the frame instead of the whole frame, at every step, and averages the tiles' noise predictions where
+    they overlap in the same fused step that averages the time windows (vdx/codenoise.py `tile_plan`, csrc/cotile.hip), so a frame
+    can be larger than the size the UNet was trained at while a UNet call keeps a tile's memory; `--tile_overlap OY OX` (pixels,
+    default a quarter of the tile); all multiples of 8; refused without `--co_denoise`, with `--exchange halo` and with
+    `--guidance_rescale`; the frames are then decoded in smaller batches; the result and the JSON records carry `"tile"`; without
+    the flag every launch, byte, CSV row and record is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -641,6 +667,10 @@ def build_arg_parser():
                    help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
     p.add_argument("--co_denoise", action="store_true",
                    help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
+    p.add_argument("--tile", type=int, nargs=2, default=None, metavar=("TH", "TW"),
+                   help="with --co_denoise: run the UNet on overlapping TH x TW pixel tiles (multiples of 8) of the frame (default: off)")
+    p.add_argument("--tile_overlap", type=int, nargs=2, default=None, metavar=("OY", "OX"),
+                   help="--tile: overlap of neighbouring tiles in pixels (multiples of 8; default: a quarter of the tile)")
     p.add_argument("--mask", default=None,
                    help="masked video-to-video: .npy uint8 / bool (T,H,W), (H,W) or (T,), nonzero = regenerate, zero = keep (needs --init_video)")
     p.add_argument("--keep_frames", default=None,
@@ -668,6 +698,10 @@ def config_from_args(a) -> DiffuserConfig:
     cfg = DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
     if cfg.freeu is not None:
         cfg.freeu = tuple(cfg.freeu)
+    if cfg.tile is not None:
+        cfg.tile = tuple(cfg.tile)
+    if cfg.tile_overlap is not None:
+        cfg.tile_overlap = tuple(cfg.tile_overlap)
     if isinstance(cfg.mask_paste, str):
         cfg.mask_paste = cfg.mask_paste == "on"
     return cfg
@@ -789,6 +823,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     free_init_iters = check_free_init(cfg, exchange)
     freeu = check_freeu(cfg)
     co = check_co_denoise(cfg, exchange)
+    tile = check_tile(cfg, exchange)            # None: the option is off
     pixel_mask = check_mask(cfg, exchange)      # None: the option is off
     phi = check_guidance_rescale(cfg)
     if not isinstance(cfg.negative_prompt, str):
@@ -871,7 +906,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
-            **({"co_denoise": info["co_denoise"]} if co else {}),
+            **({"co_denoise": info["co_denoise"]} if co else {}), **({"tile": info["tile"]} if tile is not None else {}),
             **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
 
 
@@ -904,6 +939,8 @@ def main(argv=None) -> int:
         source = {"freeu": res["freeu"]} if "freeu" in res else {}
         if "co_denoise" in res:
             source["co_denoise"] = res["co_denoise"]
+        if "tile" in res:
+            source["tile"] = res["tile"]
         if "mask" in res:
             source["mask"] = res["mask"]
         guidance = {k: res[k] for k in ("negative_prompt", "guidance_rescale") if k in res}
@@ -931,6 +968,8 @@ def main(argv=None) -> int:
                 rec["freeu"] = res["freeu"]
             if "co_denoise" in res:
                 rec["co_denoise"] = res["co_denoise"]
+            if "tile" in res:
+                rec["tile"] = res["tile"]
             if "mask" in res:
                 rec["mask"] = res["mask"]
             rec.update(guidance)

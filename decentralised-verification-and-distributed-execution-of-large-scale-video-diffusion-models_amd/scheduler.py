@@ -152,6 +152,13 @@ class DDIMScheduler(_SchedulerBase):
         part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
         return ops.cofuse_cfg_rescale_ddim_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, stats_out=stats)
 
+    def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
+        """Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`): `step_cfg_windows` with every time window's block holding
+        its row x column tiles' outputs (`tiles`: an `ops.TileGrid`; `ops.cotile_cfg_ddim_step`), one kernel.  There is no
+        `guidance_rescale` form: its statistics pass has no tiled fuse."""
+        coeffs = self.coefficients(self._host_timestep(timestep))
+        return ops.cotile_cfg_ddim_step(sample.contiguous(), windows, table, wn, tiles, guidance_scale, coeffs)
+
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
     """DPM-Solver++ 2M (Lu et al., 2022; diffusers `DPMSolverMultistepScheduler`, which Zeroscope's published recipe swaps in
@@ -333,5 +340,15 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
             new, _ = ops.cofuse_cfg_rescale_dpm_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, x0_prev=prev,
                                                      x0_out=x0_out, stats_out=stats)
+        self._commit(i)
+        return new
+
+    def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
+        """Spatially tiled co-denoising: `step_cfg_windows` over time x row x column windows (`vdx_cotile_cfg_dpm_step_f16`), one
+        kernel and ONE x0 history of the whole clip's shape, as there.  No `guidance_rescale` form."""
+        sample = sample.contiguous()
+        i, prev, x0_out = self._plan(timestep, sample)
+        new, _ = ops.cotile_cfg_dpm_step(sample, windows, table, wn, tiles, guidance_scale, self.coefficients(i, prev is not None),
+                                         x0_prev=prev, x0_out=x0_out)
         self._commit(i)
         return new

@@ -361,6 +361,33 @@ int vdx_cofuse_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
                                 void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
                                 float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
+/* Spatially tiled co-denoising (MultiDiffusion along space on top of the above; no reference counterpart, opt-in: vdx/codenoise.py
+ * `DiffuserConfig.tile`, csrc/cotile.hip, restated in tests/cotile_ref.py).  `vdx_cfg_input_window_f16` additionally cropped to rows
+ * [y0, y0 + th) and columns [x0, x0 + tw) of z (1,C,T,H,W) and of ctx (1,C,1,H,W): x2 (2,C,e-s,th,tw) contiguous, one launch, the ctx
+ * term with the same two fp16 roundings.  Every range is checked; pointers 16-byte aligned; x2 must not overlap z or ctx.          */
+int vdx_cfg_input_tile_f16(const void* z, const void* ctx, float weight, void* x2, int C, int T, int H, int W, int s, int e, int y0,
+                           int th, int x0, int tw, vdx_stream_t stream);
+/* One denoising step of the whole clip from Kt x ny x nx windows' raw UNet outputs: the Cartesian product of the Kt time windows of
+ * vdx_cofuse_cfg_ddim_step_f16 (same three HOST tables, same wn), ny row bands [tile_y0[ky], + th) and nx column bands
+ * [tile_x0[kx], + tw) (HOST arrays; 1 <= Kt <= 64, ny*nx <= 64, every band inside the frame, every frame, row and column in some
+ * band).  `windows` + win_off[kt] + (ky*nx + kx)*tile_stride (elements) is the contiguous (2,C,L_kt,th,tw) block [u; c] of that
+ * window; blocks may not overlap and must lie inside the `windows_elems` halves.  wyn: DEVICE fp32 [ny][H], wxn: DEVICE fp32 [nx][W],
+ * the per-axis normalised weights (only entries inside a band are read).  Per element (c, t, y, x), over the windows that hold it,
+ * in ascending (kt, ky, kx):  w = fp32(fp32(wn[kt][t]*wyn[ky][y])*wxn[kx][x]),  U = sum w*u_k,  Cc = sum w*c_k  (fp32; every product
+ * and every add its own rounding, the sum starts with the first product), u = fp16(U), c = fp16(Cc), and from there EXACTLY the
+ * chain of vdx_cfg_ddim_step_f16 / vdx_cfg_dpm_step_f16 with their scalars and their rules for x0_prev, x0_out and lat_out (which
+ * may be z).  With ny = nx = 1 and th = H, tw = W the result has the bits of the vdx_cofuse_* step.  16-byte accesses where W, tw,
+ * every tile_x0, every win_off and tile_stride are multiples of 8, 8-byte for multiples of 4, else element-wise.               */
+int vdx_cotile_cfg_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                 const int* win_start, const int* win_len, int Kt, const float* wn, size_t tile_stride,
+                                 const int* tile_y0, int ny, const float* wyn, const int* tile_x0, int nx, const float* wxn, int th,
+                                 int tw, void* lat_out, float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                                 float sqrt_one_minus_aprev, int C, int T, int H, int W, vdx_stream_t stream);
+int vdx_cotile_cfg_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                const int* win_start, const int* win_len, int Kt, const float* wn, size_t tile_stride,
+                                const int* tile_y0, int ny, const float* wyn, const int* tile_x0, int nx, const float* wxn, int th,
+                                int tw, const void* x0_prev, void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0,
+                                float c_x, float c_d0, float c_d1, float c_inv_r0, int C, int T, int H, int W, vdx_stream_t stream);
 /* Classifier-free guidance with CFG rescale (Lin et al. 2023, section 3.4; diffusers `rescale_noise_cfg`; no reference counterpart,
  * opt-in: `guidance_rescale` of vdx/scheduler.py, csrc/rescale.hip, restated in tests/rescale_ref.py).  With g the combine above,
  * over the N = n elements of the sample (fp64 sums S1 = sum x, S2 = sum x*x of the fp16 values):

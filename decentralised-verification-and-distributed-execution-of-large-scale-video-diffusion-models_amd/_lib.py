@@ -156,6 +156,12 @@ SIGNATURES = {
                                           _f, _f, _i, _i, _i, _i, _vp]),
     "vdx_cotile_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _f,
                                          _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _vp]),
+    # seamless looping: a ring window's input and the fused whole-clip steps over windows that wrap (no reference counterpart;
+    # vdx/codenoise.py `loop_plan`, csrc/coloop.hip)
+    "vdx_cfg_input_loop_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vdx_coloop_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_coloop_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
+                                         _vp]),
     # CFG rescale: the statistics pass and the fused steps, plain and co-fused (no reference counterpart; vdx/scheduler.py
     # `guidance_rescale`, csrc/rescale.hip)
     "vdx_cfg_rescale_rows": (_i, [_sz]),

@@ -17,6 +17,13 @@ With `DiffuserConfig(tile=(TH, TW))` / `--tile TH TW` the windows are additional
 csrc/cotile.hip): a window is the product of a time window, a row band and a column band, every UNet call is a crop of one tile's
 size, and the fused step averages with the product of three per-axis normalised weights (`tile_plan`, `check_tile` below).  Pinned
 in tests/test_cotile_gpu.py against tests/cotile_ref.py; again no external implementation and no quality claim.
+
+With `DiffuserConfig(loop=True)` / `--loop` the windows lie on a RING (AnimateDiff's `closed_loop` context option; MultiDiffusion
+along time with periodic windows; csrc/coloop.hip): `loop_plan` spreads windows of one length evenly over the clip and lets the
+last ones wrap over its end into the first frames, so frames T-1 and 0 are denoised together in one UNet call at every step like
+any other neighbouring pair, and the clip played as a loop has no jump there (`loop_table`, `check_loop` below).  Pinned in
+tests/test_coloop_gpu.py against tests/coloop_ref.py, the wrap itself by rotation equivariance; NOT pinned and not claimed: no
+external implementation is pinned, and there is no quality claim on real Zeroscope weights.
 """
 from __future__ import annotations
 
@@ -29,7 +36,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .planner import ChunkPlan
+from .planner import ChunkPlan, PlannerError, auto_chunk
 
 
 def fuse_weights(length: int, overlap: int) -> List[float]:
@@ -83,6 +90,89 @@ def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
     if getattr(cfg, "co_denoise", False) and exchange == "halo":
         raise ValueError("co_denoise needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
     return bool(getattr(cfg, "co_denoise", False))
+
+
+# ---- ring windows (seamless looping; csrc/coloop.hip) -----------------------------------------------------------------------------
+def loop_plan(total: int, world: int, chunk_size: int = 0, overlap: int = 4, overlap_rule: str = "coherent") -> ChunkPlan:
+    """The windows of a looping clip: `size` and `ov` by the planner's own rules (`auto_chunk`, the overlap rule), `ov >= 1`;
+    with `step = size - ov`, `n = world * ceil(ceil(total / step) / world)` windows `(s_i, s_i + size)`, `s_i = (i * total) // n`:
+    evenly spread, ascending, ALL of one length (no short tail window, no repeated window).  A range's end may exceed `total`: it
+    means the frames `(s + f) mod total`.  Consecutive starts (cyclically) are at most `step` apart, so every cyclically
+    adjacent pair of windows shares at least `ov` frames and every pair of frames `(t, (t + 1) mod total)` lies together in some
+    window.  `PlannerError` when `size >= total` (one window is a line, not a ring, and the UNet's temporal layers are not
+    circular) and when `n > total` (the starts could not be distinct)."""
+    if total <= 0 or world <= 0:
+        raise PlannerError("num_frames and world size must be positive")
+    size = chunk_size if chunk_size > 0 else auto_chunk(total, world)
+    if overlap_rule == "coherent":
+        ov = overlap if overlap > 0 else max(4, size // 3)
+    elif overlap_rule == "third":
+        ov = min(overlap, size // 3)
+    else:
+        raise PlannerError(f"unknown overlap rule {overlap_rule!r}")
+    if size >= total:
+        raise PlannerError(f"a window of {size} frames holds the whole clip of {total}: one window is a line, not a ring "
+                           "(the UNet's temporal layers are not circular); use a chunk shorter than the clip")
+    if ov < 1:
+        raise PlannerError(f"overlap {ov}: neighbouring ring windows must share at least one frame")
+    step = size - ov
+    if step <= 0:
+        raise PlannerError(f"overlap {ov} >= chunk {size}: windows would never advance")
+    n = world * -(-(-(-total // step)) // world)
+    if n > total:
+        raise PlannerError(f"{n} ring windows for {total} frames: their starts could not be distinct")
+    return ChunkPlan(size, ov, tuple(((i * total) // n, (i * total) // n + size) for i in range(n)), world)
+
+
+def loop_plan_of(cfg, world: int) -> ChunkPlan:
+    """`loop_plan` of a job's config; mode "fsdp" (`no_chunking`) asks for one window of the whole clip, which it refuses."""
+    return loop_plan(cfg.num_frames, world, cfg.num_frames if cfg.no_chunking else cfg.chunk_size, cfg.overlap, cfg.overlap_rule)
+
+
+def loop_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
+    """`window_table` for a ring plan: `wn[k][t] = fuse_weights(size, ov)[(t - s_k) mod T]` where that index is `< size`, else 0,
+    normalised over the windows that hold `t` in float64, then rounded to fp32 once: exactly 1.0 where one window holds the
+    frame.  Every window enters the fuse (a ring plan repeats none); `rows()` is unchanged: (offset, first frame, length)."""
+    fused = []
+    for i, (s, e) in enumerate(chunk_plan.ranges):
+        if not (0 <= s < T and 1 <= e - s <= T):
+            raise ValueError(f"loop_table: window {i} = [{s}, {e}) is no ring window of {T} frames")
+        fused.append((i, s, e))
+    if len(fused) > ops.COFUSE_MAX_WINDOWS:
+        raise ValueError(f"loop_table: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
+    raw = np.zeros((len(fused), T), dtype=np.float64)
+    for k, (_, s, e) in enumerate(fused):
+        raw[k, (s + np.arange(e - s)) % T] = fuse_weights(e - s, chunk_plan.overlap)
+    total = raw.sum(axis=0)
+    if (total <= 0).any():
+        raise ValueError(f"loop_table: frame {int(np.argmin(total > 0))} is in no window")
+    return WindowTable(tuple(fused), torch.from_numpy((raw / total).astype(np.float32)))
+
+
+def check_loop(cfg, exchange: str = "allgather", world: Optional[int] = None) -> bool:
+    """`cfg.loop`; `ValueError` before any work when the job cannot run it: ring windows exist only as co-denoising (the
+    windowed job's trajectories never meet before the blend), never with the halo exchange, not with `tile` (the tiled kernels
+    have no ring form yet), not with `guidance_rescale` (its statistics pass has none either), and not when `loop_plan` refuses
+    the plan (mode "fsdp", a chunk as long as the clip, no overlap, more windows than frames or than the fused step takes)."""
+    if not getattr(cfg, "loop", False):
+        return False
+    if not getattr(cfg, "co_denoise", False):
+        raise ValueError("loop needs co_denoise: ring windows meet at every step in the fused noise; the windowed job's blend has no ring form")
+    if exchange == "halo":
+        raise ValueError("loop needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
+    if getattr(cfg, "tile", None) is not None:
+        raise ValueError("loop and tile exclude each other: the tiled kernels have no ring form yet")
+    if getattr(cfg, "guidance_rescale", 0.0) != 0:
+        raise ValueError("loop and guidance_rescale exclude each other: the rescale's statistics pass has no ring form yet")
+    if world is None:
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    try:
+        cp = loop_plan_of(cfg, world)
+    except PlannerError as err:
+        raise ValueError(f"loop: {err}") from None
+    if len(cp.ranges) > ops.COFUSE_MAX_WINDOWS:
+        raise ValueError(f"loop: {len(cp.ranges)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
+    return True
 
 
 # ---- spatial tiles (MultiDiffusion's original form; csrc/cotile.hip) ------------------------------------------------------------
@@ -212,11 +302,15 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     `tiles` (a `TilePlan`, spatially tiled co-denoising): every window of this rank is run once per tile, through
     `ops.cfg_input_tile` on the tile's crop of z (and of the whole frame's ctx), into `tiles.count` consecutive slots of the
     packed buffer `[per_rank][ny nx][2][C][cp.chunk][th][tw]`; the step is `step_cfg_tiles`; the record gains `"tile"`.  The
-    ranks' shares, the repeated tail window and the one gather per step are as without it."""
+    ranks' shares, the repeated tail window and the one gather per step are as without it.
+    `cfg.loop` (ring windows; `cp` is then a `loop_plan`): the table is `loop_table`'s, a window's input comes from
+    `ops.cfg_input_loop` (frames `(s + f) mod T`), the step is `step_cfg_loop`, and the record gains `"loop"`: the windows as
+    [first frame, length]; everything else, the packed buffer and the mask step on the whole clip included, is as without it."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
-    table = window_table(cp, T)
+    loop = bool(getattr(cfg, "loop", False))
+    table = loop_table(cp, T) if loop else window_table(cp, T)
     per, world, rank = cp.per_rank, d.world, d.rank
     boxes = [None] if tiles is None else tiles.boxes              # None: the whole frame, as always
     nt = len(boxes)
@@ -242,7 +336,9 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     for i, t in enumerate(d.schedule):
         for j, (s, e) in enumerate(mine):
             for k, box in enumerate(boxes):
-                if box is None:
+                if loop:
+                    x = ops.cfg_input_loop(z, d.ctx, cfg.context_weight, s, e - s)
+                elif box is None:
                     x = ops.cfg_input_window(z, d.ctx, cfg.context_weight, s, e)
                 else:
                     x = ops.cfg_input_tile(z, d.ctx, cfg.context_weight, s, e, *box)
@@ -259,7 +355,9 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
             dist.all_gather_into_tensor(packed.view(-1), local.view(-1))
             d._sync()
             spent["net_gather_s"] += time.time() - t0
-        if grid is None:
+        if loop:
+            z = sched.step_cfg_loop(packed, rows, wn, t, z, cfg.guidance_scale)
+        elif grid is None:
             z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale, **d._rescale_kw)
         else:
             z = sched.step_cfg_tiles(packed, rows, wn, grid, t, z, cfg.guidance_scale)
@@ -275,4 +373,6 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     rec = {"windows": len(table.fused), "steps": len(d.schedule), "exchange_s": spent["net_gather_s"], "bytes_per_step": bytes_step}
     if tiles is not None:
         rec["tile"] = tiles.record(len(table.fused))
+    if loop:
+        rec["loop"] = {"windows": [[s, e - s] for _, s, e in table.fused]}
     return z.float(), spent, rec

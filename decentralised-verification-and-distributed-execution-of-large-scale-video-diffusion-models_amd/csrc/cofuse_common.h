@@ -52,7 +52,9 @@ __device__ __forceinline__ float fuse_term(float acc, float w, float x, bool fir
 
 // U, Cc of the E elements at (c, t, p) fused over the windows that hold frame t, k ascending, then rounded to fp16 (returned as
 // the floats the chains take).  t is uniform over a block, so the window loop, the table reads and the weights are too.
-template <int E>
+// RING (coloop.hip): window k holds the frames (s_k + f) mod T, f in [0, L_k), with 0 <= s_k < T and L_k <= T, so the one
+// wrap is a compare and an add; the default leaves the plain instantiations as they were.
+template <int E, bool RING = false>
 __device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab, int K, const float* wn, int C, int T, int HW, int c,
                                           int t, int p, float (&uf)[E], float (&cf)[E]) {
     float U[E], Cc[E];
@@ -60,8 +62,14 @@ __device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab,
     for (int j = 0; j < E; ++j) U[j] = Cc[j] = 0.f;
     bool first = true;
     for (int k = 0; k < K; ++k) {
-        const int f = t - tab.s[k], L = tab.len[k];
-        if (f < 0 || f >= L) continue;
+        int f = t - tab.s[k];
+        const int L = tab.len[k];
+        if constexpr (RING) {
+            if (f < 0) f += T;
+            if (f >= L) continue;
+        } else {
+            if (f < 0 || f >= L) continue;
+        }
         const float w = wn[(size_t)k * T + t];
         const f16* up = win + tab.off[k] + ((size_t)c * L + f) * HW + p;
         const f16* cp = up + (size_t)C * L * HW;
@@ -89,10 +97,13 @@ static inline bool co_overlap(const void* a, size_t na, const void* b, size_t nb
 
 // Every check of a co-fused step, before a launch -> 0 and the table `tab` and the access width `e` (8, 4 or 1 halves), else the
 // error.  mode 0: DDIM (no x0 history); otherwise DPM-Solver++.  `writes` false: a statistics pass, which reads
-// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).
+// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).  `ring`
+// (coloop.hip): a row (off, s, L) means the frames (s + f) mod T, so 0 <= s < T and 1 <= L <= T replace s + L <= T, and a
+// frame is held under that rule; everything else, the choice of `e` included, is the same.
 static inline int cofuse_check(const char* what, int mode, bool writes, const void* z, const void* windows, size_t windows_elems,
                                const int64_t* win_off, const int* win_start, const int* win_len, int K, const float* wn,
-                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, cofuse_tab& tab, int& e) {
+                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, cofuse_tab& tab, int& e,
+                               bool ring = false) {
     VDX_CHECK((z || !writes) && windows && win_off && win_start && win_len && wn && (lat_out || !writes), "%s: null pointer", what);
     VDX_CHECK(C > 0 && T > 0 && HW > 0 && HW <= 1 << 30, "%s: bad shape C=%d T=%d HW=%d", what, C, T, HW);
     VDX_CHECK(K >= 1 && K <= COFUSE_MAX_WINDOWS, "%s: %d windows, 1..%d are supported", what, K, COFUSE_MAX_WINDOWS);
@@ -106,7 +117,8 @@ static inline int cofuse_check(const char* what, int mode, bool writes, const vo
     for (int k = 0; k < K; ++k) {
         const long long off = (long long)win_off[k];
         const int s = win_start[k], L = win_len[k];
-        VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= T - s, "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s, L, T);
+        VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= (ring ? T : T - s), "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s,
+                  L, T);
         const size_t need = 2 * (size_t)C * L * HW;
         VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && need <= windows_elems - (size_t)off,
                   "%s: window %d (offset %lld, %zu elements) leaves the buffer of %zu elements", what, k, off, need, windows_elems);
@@ -118,7 +130,11 @@ static inline int cofuse_check(const char* what, int mode, bool writes, const vo
     }
     for (int t = 0; t < T; ++t) {                                 // a frame nobody predicts has no noise to step with
         bool hit = false;
-        for (int k = 0; k < K && !hit; ++k) hit = t >= tab.s[k] && t - tab.s[k] < tab.len[k];
+        for (int k = 0; k < K && !hit; ++k) {
+            int f = t - tab.s[k];
+            if (ring && f < 0) f += T;
+            hit = f >= 0 && f < tab.len[k];
+        }
         VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
     }
     if (!writes) return 0;

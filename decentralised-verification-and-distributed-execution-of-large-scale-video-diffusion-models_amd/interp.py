@@ -10,7 +10,9 @@ weight; tests/interp_ref.py states the expression in float64 numpy and the tests
 kernel against that restatement on the same flows, and that the result beats the plain blend on a moving texture.  What is
 not, and is not claimed: agreement with any external interpolator.
 
-The output has (F - 1) N + 1 frames; frame i N is input frame i byte for byte.  Frames on the GPU stay there.
+The output has (F - 1) N + 1 frames; frame i N is input frame i byte for byte.  Frames on the GPU stay there.  With `loop`
+(the job's `--loop`) frame 0 is appended first and the last output frame, its copy, is dropped: F N frames, the last of which
+leads back into the first.
 """
 from __future__ import annotations
 
@@ -42,19 +44,23 @@ def check_frames(frames):
     return F, H, W
 
 
-def n_output_frames(n_frames: int, factor: int) -> int:
-    return (int(n_frames) - 1) * int(factor) + 1
+def n_output_frames(n_frames: int, factor: int, loop: bool = False) -> int:
+    return int(n_frames) * int(factor) if loop else (int(n_frames) - 1) * int(factor) + 1
 
 
-def interpolate_frames(frames, factor, device=None) -> torch.Tensor:
+def interpolate_frames(frames, factor, device=None, loop: bool = False) -> torch.Tensor:
     """uint8 RGB `frames` (F, H, W, 3) (a tensor, an array or a sequence of (H, W, 3) frames) -> uint8 ((F-1)*factor + 1, H, W, 3)
     on the GPU.  Host frames are uploaded once; frames on the GPU are used where they are.  factor 1 or a single frame: the
-    input bytes.  Everything is checked before anything is uploaded or launched."""
+    input bytes.  Everything is checked before anything is uploaded or launched.  `loop`: the clip is a loop, so the pair
+    (F-1, 0) is interpolated too: frame 0 is appended, the F + 1 frames go through the same kernels, and the last output frame
+    (frame 0 again) is dropped -> (F*factor, H, W, 3), whose last frame leads back into its first."""
     factor = check_factor(factor)
     F, H, W = check_frames(frames)
     u8 = _frames.on_device(frames, _frames.device_for(frames, device))
     if factor == 1 or F == 1:
         return u8
+    if loop:
+        return interpolate_frames(torch.cat([u8, u8[:1]]), factor)[:-1].contiguous()
     from . import ops
     fab = _flow.farneback_flows(u8)
     fba = _flow.farneback_flows(u8.flip(0)).flip(0).contiguous()        # pair i of the reversed clip's flows is frame F-1-i -> F-2-i

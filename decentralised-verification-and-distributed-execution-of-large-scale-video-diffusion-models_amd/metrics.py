@@ -35,6 +35,17 @@ def boundary_l1(frames: Sequence[np.ndarray], ranges: Sequence[Tuple[int, int]])
     return float(np.mean(diffs)) if diffs else None
 
 
+def loop_l1(frames: Sequence[np.ndarray]) -> Tuple[Optional[float], Optional[float]]:
+    """The seam of a clip played as a loop -> (`wrap_l1`: mean |frames[T-1] - frames[0]|, `mean_l1`: the mean over the T - 1
+    consecutive pairs of mean |frames[t+1] - frames[t]|), in float32 like `boundary_l1`; (None, None) for fewer than two
+    frames.  A loop closes as smoothly as it plays when the first is no larger than the second."""
+    if len(frames) <= 1:
+        return None, None
+    l1 = lambda a, b: np.mean(np.abs(a.astype(np.float32) - b.astype(np.float32)))   # noqa: E731
+    pairs = [l1(frames[t + 1], frames[t]) for t in range(len(frames) - 1)]
+    return float(l1(frames[-1], frames[0])), float(np.mean(pairs))
+
+
 def _cv2():
     try:
         import cv2

@@ -958,6 +958,51 @@ def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x
 
 
 # --------------------------------------------------------------------------------------------
+# Seamless looping: ring windows (vdx/codenoise.py `loop_plan`, csrc/coloop.hip; no reference counterpart)
+def cfg_input_loop(z, ctx, weight, s: int, L: int, out=None):
+    """`cfg_input_window` on a ring: one launch reads the frames `(s + f) mod T`, f in [0, L), out of the whole clip's latent z
+    (1,C,T,H,W), `0 <= s < T`, `1 <= L <= T`, and writes the contiguous (2,C,L,H,W) UNet input, TAGGED as a CFG duplicate
+    exactly as `cfg_input_window` tags its result.  The library checks `s` and `L`."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError("cfg_input_loop: z must be contiguous (1,C,T,H,W)")
+    _, Cc, T, H, W = z.shape
+    s, L = int(s), int(L)
+    if L < 1:
+        raise VdxError(f"cfg_input_loop: bad ring window start {s}, length {L} of {T} frames")
+    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
+        raise VdxError("cfg_input_loop: ctx must be contiguous (1,C,1,H,W)")
+    if out is None:
+        out = torch.empty((2, Cc, L, H, W), dtype=torch.float16, device=z.device)
+    elif tuple(out.shape) != (2, Cc, L, H, W) or not out.is_contiguous():
+        raise VdxError("cfg_input_loop: out must be contiguous (2,C,L,H,W)")
+    _launch("vdx_cfg_input_loop_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H * W, s, L)
+    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
+    return out
+
+
+def coloop_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
+    """`cofuse_cfg_ddim_step` over ring windows (include/vdx.h `vdx_coloop_cfg_ddim_step_f16`): a `table` row (offset, s, L)
+    means the frames `(s + f) mod T`; the fuse, the chain, `coeffs` and `out` (which may be `z`) are the same."""
+    head, tail = _cofuse_args("coloop_cfg_ddim_step", z, windows, table, wn)
+    if out is None:
+        out = torch.empty_like(z)
+    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+        raise VdxError("coloop_cfg_ddim_step: out must be contiguous and shaped like z")
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_coloop_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
+    return out
+
+
+def coloop_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
+    """`cofuse_cfg_dpm_step` over ring windows (`vdx_coloop_cfg_dpm_step_f16`) -> (z', x0)."""
+    head, tail = _cofuse_args("coloop_cfg_dpm_step", z, windows, table, wn)
+    x0_out, out, c = _dpm_args("coloop_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
+    _launch("vdx_coloop_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
+            *c, *tail)
+    return out, x0_out
+
+
+# --------------------------------------------------------------------------------------------
 # Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`, csrc/cotile.hip; no reference counterpart)
 COTILE_MAX_TILES = 64
 

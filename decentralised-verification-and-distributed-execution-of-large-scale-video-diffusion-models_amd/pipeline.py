@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .codenoise import check_co_denoise, check_tile, co_denoise_round, tile_plan
+from .codenoise import check_co_denoise, check_loop, check_tile, co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import check_mask, known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
@@ -103,6 +103,10 @@ class DiffuserConfig:
     # All four are multiples of 8.  None = the UNet runs on the whole frame, as always
     tile: Optional[Tuple[int, int]] = None
     tile_overlap: Optional[Tuple[int, int]] = None
+    # seamless looping (vdx/codenoise.py `loop_plan`, csrc/coloop.hip; AnimateDiff's `closed_loop` context option, unpinned; needs
+    # `co_denoise`): the windows lie on a ring, the last wrapping over the clip's end into its first frames, so frames T-1 and 0
+    # are denoised together at every step.  False = the windows stop at the clip's end, as always
+    loop: bool = False
 
     @property
     def use_fsdp(self):
@@ -372,6 +376,8 @@ class DistributedVideoDiffuser:
 
     def plan(self) -> ChunkPlan:
         cfg = self.cfg
+        if getattr(cfg, "loop", False):     # ring windows of one length; a range's end may exceed num_frames (codenoise.loop_plan)
+            return loop_plan_of(cfg, self.world)
         return plan(cfg.num_frames, self.world, cfg.chunk_size, cfg.overlap, cfg.no_chunking, cfg.overlap_rule)
 
     def blend(self, chunks: List[Tuple[int, int, torch.Tensor]], like: torch.Tensor, ov: int) -> torch.Tensor:
@@ -485,10 +491,17 @@ class DistributedVideoDiffuser:
         refused with "halo" and with `guidance_rescale`): every window of every round is run once per spatial tile
         (`codenoise.tile_plan`; with `hybrid_ctx` each tile reads its crop of the whole frame's context) and the fused step
         averages over time x row x column windows; `info["tile"]` = {"tile": [th, tw], "overlap": [oy, ox] (latent cells),
-        "grid": [ny, nx], "windows": fused windows in all}.  A tile equal to the frame is plain co-denoising, bit for bit."""
+        "grid": [ny, nx], "windows": fused windows in all}.  A tile equal to the frame is plain co-denoising, bit for bit.
+
+        `loop` (with `co_denoise` only; both samplers, every chunked mode, `init_latents`, `latent_mask`, every FreeInit iteration,
+        `freeu`; refused with "halo", `tile`, `guidance_rescale` and a plan `codenoise.loop_plan` refuses, mode "fsdp" among
+        them): the windows of every round lie on a ring (`codenoise.loop_plan` / `loop_table`, `ops.cfg_input_loop`,
+        `step_cfg_loop`); `info["ranges"]` holds each window clipped to the clip, (s, min(e, T)), and `info["loop"]` =
+        {"windows": [[first frame, length], ...]}."""
         cfg = self.cfg
         co = check_co_denoise(cfg, exchange)
         tile = check_tile(cfg, exchange)
+        loop = check_loop(cfg, exchange, self.world)
         self._tiles = tile_plan(cfg.height // 8, cfg.width // 8, *tile) if tile is not None else None
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
@@ -502,7 +515,9 @@ class DistributedVideoDiffuser:
             base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
         else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
             base = self._start
-        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": list(cp.ranges), "world_size": self.world,
+        T = cfg.num_frames
+        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": [(s, min(e, T)) for s, e in cp.ranges] if loop else list(cp.ranges),
+                "world_size": self.world,
                 "num_frames": cfg.num_frames, "denoise_s": 0.0, "exchange": exchange, "steps_run": len(self.schedule),
                 "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0, "payload_bytes_actual": 0}
         if iters > 1:
@@ -548,6 +563,8 @@ class DistributedVideoDiffuser:
                                   "bytes_per_step": self._co_rec[0]["bytes_per_step"]}
             if tile is not None:
                 info["tile"] = self._co_rec[0]["tile"]
+            if loop:
+                info["loop"] = self._co_rec[0]["loop"]
         return out, info
 
 
@@ -615,7 +632,13 @@ def build_arg_parser():
     can be larger than the size the UNet was trained at while a UNet call keeps a tile's memory; `--tile_overlap OY OX` (pixels,
     default a quarter of the tile); all multiples of 8; refused without `--co_denoise`, with `--exchange halo` and with
     `--guidance_rescale`; the frames are then decoded in smaller batches; the result and the JSON records carry `"tile"`; without
-    the flag every launch, byte, CSV row and record is the one it always was."""
+    the flag every launch, byte, CSV row and record is the one it always was.
+    `--loop` (with `--co_denoise`; no reference counterpart; AnimateDiff's `closed_loop` context option, unpinned) makes the clip a
+    seamless loop: the windows lie on a ring, the last wrapping over the clip's end into its first frames (vdx/codenoise.py
+    `loop_plan`, csrc/coloop.hip), so frames T-1 and 0 are denoised together in one UNet call at every step; `--interpolate N`
+    then also fills the pair (T-1, 0) and writes T N frames; refused without `--co_denoise`, with `--exchange halo`, `--tile`,
+    `--guidance_rescale`, `--mode fsdp` and a chunk as long as the clip; the result and the JSON records carry `"loop"`:
+    {"windows", "wrap_l1", "mean_l1"}; without the flag every launch, byte, CSV row and record is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -671,6 +694,8 @@ def build_arg_parser():
                    help="with --co_denoise: run the UNet on overlapping TH x TW pixel tiles (multiples of 8) of the frame (default: off)")
     p.add_argument("--tile_overlap", type=int, nargs=2, default=None, metavar=("OY", "OX"),
                    help="--tile: overlap of neighbouring tiles in pixels (multiples of 8; default: a quarter of the tile)")
+    p.add_argument("--loop", action="store_true",
+                   help="with --co_denoise: ring windows, so that the clip's last frame leads back into its first (default: off)")
     p.add_argument("--mask", default=None,
                    help="masked video-to-video: .npy uint8 / bool (T,H,W), (H,W) or (T,), nonzero = regenerate, zero = keep (needs --init_video)")
     p.add_argument("--keep_frames", default=None,
@@ -824,6 +849,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     freeu = check_freeu(cfg)
     co = check_co_denoise(cfg, exchange)
     tile = check_tile(cfg, exchange)            # None: the option is off
+    loop = check_loop(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
     pixel_mask = check_mask(cfg, exchange)      # None: the option is off
     phi = check_guidance_rescale(cfg)
     if not isinstance(cfg.negative_prompt, str):
@@ -877,6 +903,9 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     if d.rank == 0 and len(frames) > 1 and not cfg.no_chunking:
         temp_instab = metrics.boundary_l1(frames, ranges)
         flow_err = metrics.flow_warp_error(frames, ranges, device=dev) if cfg.gpu_flow else metrics.flow_warp_error(frames, ranges)
+    if loop:                                    # the loop's seam beside the clip's ordinary frame-to-frame change, on the host
+        wrap_l1, mean_l1 = metrics.loop_l1(frames)
+        info["loop"] = {**info["loop"], "wrap_l1": wrap_l1, "mean_l1": mean_l1}
     frames_written = None
     if d.rank == 0 and out_video:
         to_write, fps = frames, cfg.fps
@@ -884,7 +913,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             # after the metrics above, which are numbers about the generated frames; `frames` itself (what --clip_json and
             # --mdvqs_json score) stays as it is
             from .interp import interpolate_frames
-            to_write, fps = interpolate_frames(frames, factor, device=dev), cfg.fps * factor
+            to_write, fps = interpolate_frames(frames, factor, device=dev, **({"loop": True} if loop else {})), cfg.fps * factor
             if not gpu_video_write:
                 to_write = list(to_write.cpu().numpy())
         metrics.write_video(to_write, out_video, fps, restart_rows=video_restart_rows, device=dev if gpu_video_write else None)
@@ -907,6 +936,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
             **({"co_denoise": info["co_denoise"]} if co else {}), **({"tile": info["tile"]} if tile is not None else {}),
+            **({"loop": info["loop"]} if loop else {}),
             **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
 
 
@@ -941,6 +971,8 @@ def main(argv=None) -> int:
             source["co_denoise"] = res["co_denoise"]
         if "tile" in res:
             source["tile"] = res["tile"]
+        if "loop" in res:
+            source["loop"] = res["loop"]
         if "mask" in res:
             source["mask"] = res["mask"]
         guidance = {k: res[k] for k in ("negative_prompt", "guidance_rescale") if k in res}
@@ -970,6 +1002,8 @@ def main(argv=None) -> int:
                 rec["co_denoise"] = res["co_denoise"]
             if "tile" in res:
                 rec["tile"] = res["tile"]
+            if "loop" in res:
+                rec["loop"] = res["loop"]
             if "mask" in res:
                 rec["mask"] = res["mask"]
             rec.update(guidance)

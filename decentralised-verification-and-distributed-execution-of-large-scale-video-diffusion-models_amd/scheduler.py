@@ -159,6 +159,12 @@ class DDIMScheduler(_SchedulerBase):
         coeffs = self.coefficients(self._host_timestep(timestep))
         return ops.cotile_cfg_ddim_step(sample.contiguous(), windows, table, wn, tiles, guidance_scale, coeffs)
 
+    def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Seamless looping (vdx/codenoise.py `loop_plan`): `step_cfg_windows` with every window on a ring, a `table` row
+        (offset, s, L) meaning the frames (s + f) mod T (`ops.coloop_cfg_ddim_step`), one kernel.  No `guidance_rescale` form."""
+        coeffs = self.coefficients(self._host_timestep(timestep))
+        return ops.coloop_cfg_ddim_step(sample.contiguous(), windows, table, wn, guidance_scale, coeffs)
+
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
     """DPM-Solver++ 2M (Lu et al., 2022; diffusers `DPMSolverMultistepScheduler`, which Zeroscope's published recipe swaps in
@@ -349,6 +355,16 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         sample = sample.contiguous()
         i, prev, x0_out = self._plan(timestep, sample)
         new, _ = ops.cotile_cfg_dpm_step(sample, windows, table, wn, tiles, guidance_scale, self.coefficients(i, prev is not None),
+                                         x0_prev=prev, x0_out=x0_out)
+        self._commit(i)
+        return new
+
+    def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Seamless looping: `step_cfg_windows` over ring windows (`vdx_coloop_cfg_dpm_step_f16`), one kernel and ONE x0 history of
+        the whole clip's shape, as there.  No `guidance_rescale` form."""
+        sample = sample.contiguous()
+        i, prev, x0_out = self._plan(timestep, sample)
+        new, _ = ops.coloop_cfg_dpm_step(sample, windows, table, wn, guidance_scale, self.coefficients(i, prev is not None),
                                          x0_prev=prev, x0_out=x0_out)
         self._commit(i)
         return new

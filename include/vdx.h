@@ -388,6 +388,27 @@ int vdx_cotile_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 const int* tile_y0, int ny, const float* wyn, const int* tile_x0, int nx, const float* wxn, int th,
                                 int tw, const void* x0_prev, void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0,
                                 float c_x, float c_d0, float c_d1, float c_inv_r0, int C, int T, int H, int W, vdx_stream_t stream);
+/* Seamless looping for co-denoising: ring windows (AnimateDiff's `closed_loop` context option; MultiDiffusion along time with
+ * periodic windows; no reference counterpart, opt-in: vdx/codenoise.py `loop_plan`, `DiffuserConfig.loop`, csrc/coloop.hip, restated
+ * in tests/coloop_ref.py).  A window (s, L) holds the frames (s + f) mod T, f in [0, L), with 0 <= s < T and 1 <= L <= T.
+ * vdx_cfg_input_loop_f16: `vdx_cfg_input_window_f16` under that rule (note: a LENGTH, not an end): x2 (2,C,L,h,w) contiguous, one
+ * launch, the ctx term with the same two fp16 roundings; 16-byte accesses where HW % 8 == 0, else element-wise; x2 must not overlap
+ * z; pointers 16-byte aligned.  A call with s + L <= T has the bits of vdx_cfg_input_window_f16(…, s, s + L).                     */
+int vdx_cfg_input_loop_f16(const void* z, const void* ctx, float weight, void* x2, int C, int T, int HW, int s, int L,
+                           vdx_stream_t stream);
+/* `vdx_cofuse_cfg_ddim_step_f16` / `vdx_cofuse_cfg_dpm_step_f16` (same arguments, same three HOST tables, same wn, same fuse term
+ * for term, same chains, same rules for x0_prev, x0_out and lat_out, same alignment and overlap rules and access widths) with every
+ * window row meaning the frames (win_start[k] + f) mod T: per (c, t), for k ascending, f = t - s_k, f += T if f < 0, window k enters
+ * if f < L_k.  Checked: 0 <= s_k < T, 1 <= L_k <= T, every block inside the buffer, every frame in some window under the modular
+ * rule, 1 <= K <= 64.  A table in which no window wraps gives the bits of the vdx_cofuse_* step.                                 */
+int vdx_coloop_cfg_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                 const int* win_start, const int* win_len, int K, const float* wn, void* lat_out, float guidance,
+                                 float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float sqrt_one_minus_aprev, int C, int T,
+                                 int HW, vdx_stream_t stream);
+int vdx_coloop_cfg_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
+                                float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
 /* Classifier-free guidance with CFG rescale (Lin et al. 2023, section 3.4; diffusers `rescale_noise_cfg`; no reference counterpart,
  * opt-in: `guidance_rescale` of vdx/scheduler.py, csrc/rescale.hip, restated in tests/rescale_ref.py).  With g the combine above,
  * over the N = n elements of the sample (fp64 sums S1 = sum x, S2 = sum x*x of the fp16 values):

@@ -39,6 +39,15 @@ class ClipPreprocessArgs(C.Structure):
     ]
 
 
+class TomeArgs(C.Structure):
+    """Mirror of `vdx_tome_args` (include/vdx.h)."""
+    _fields_ = [
+        ("src_idx", C.c_void_p), ("dst_idx", C.c_void_p), ("inv", C.c_void_p), ("node_max", C.c_void_p),
+        ("node_idx", C.c_void_p), ("slot", C.c_void_p), ("off", C.c_void_p), ("items", C.c_void_p),
+        ("n_img", C.c_int32), ("S", C.c_int32), ("n_src", C.c_int32), ("n_dst", C.c_int32), ("r", C.c_int32), ("C", C.c_int32),
+    ]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/vdx.h declares
@@ -183,6 +192,12 @@ SIGNATURES = {
     # FreeU's skip filter and backbone scale (no reference counterpart; unet3d.py enable_freeu, csrc/freeu.hip)
     "vdx_freeu_filter_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
     "vdx_freeu_scale_f16": (_i, [_vp, _i, _sz, _i, _f, _vp]),
+    # token merging around the spatial self-attention (no reference counterpart; unet3d.py enable_tome, vdx/tome.py, csrc/tome.hip)
+    "vdx_tome_match_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp]),
+    "vdx_tome_select_lds": (_sz, [_i, _i]),
+    "vdx_tome_select": (_i, [C.POINTER(TomeArgs), _vp]),
+    "vdx_tome_merge_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp, _i, _vp]),
+    "vdx_tome_unmerge_add_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp, _i, _vp, _i, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -235,6 +235,14 @@ class DiffusionPipeline:
     def disable_freeu(self):
         self.unet.disable_freeu()
 
+    def enable_tome(self, ratio=0.5, sx=2, sy=2, seed=None, max_downsample=1):
+        """`tomesd.apply_patch(pipe, ratio=..., max_downsample=..., sx=..., sy=...)` as a pipeline method: the UNet's switch
+        (vdx/unet3d.py `enable_tome`)."""
+        self.unet.enable_tome(ratio=ratio, sx=sx, sy=sy, seed=seed, max_downsample=max_downsample)
+
+    def disable_tome(self):
+        self.unet.disable_tome()
+
     def decode_latents(self, latents):
         """`fsdp.py:172` relies on this pipeline helper of older diffusers releases: latents (1,C,F,h,w) -> video
         (1,3,F,H,W) float32 in [-1, 1] scale of the decoder (the caller maps to uint8)."""

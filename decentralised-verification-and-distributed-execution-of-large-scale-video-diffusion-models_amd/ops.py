@@ -1894,3 +1894,135 @@ def freeu_scale(x, b):
     with torch.cuda.device(x.device):
         _launch("vdx_freeu_scale_f16", px, ld, M, C, b)
     return x
+
+
+# --------------------------------------------------------------------------------------------
+# Token merging around the spatial self-attention (no reference counterpart; include/vdx.h "Token merging"; csrc/tome.hip).
+# unet3d.py calls the four in turn when `enable_tome` is set; vdx/tome.py builds the tables.
+def _tome_buf(t, n: int, dtype, what: str, name: str, device) -> int:
+    """Pointer of a caller-made device buffer of at least n elements of `dtype`."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != device or t.dtype != dtype or not t.is_contiguous():
+        raise VdxError(f"{what}: {name} must be a contiguous {dtype} tensor on {device}")
+    if t.numel() < n:
+        raise VdxError(f"{what}: {name} has {t.numel()} elements, need {n}")
+    return t.data_ptr()
+
+
+def _tome_args(what, x, src_idx, dst_idx, n_img, S, r, C):
+    """The plan's struct with its tables checked: `x` names the device, the tables are int32 of n_src + n_dst = S entries."""
+    for name, v in (("n_img", n_img), ("S", S), ("r", r)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise VdxError(f"{what}: {name} must be an integer, got {v!r}")
+    if not torch.is_tensor(src_idx) or not torch.is_tensor(dst_idx):
+        raise VdxError(f"{what}: src_idx / dst_idx must be tensors")
+    n_src, n_dst = src_idx.numel(), dst_idx.numel()
+    if n_img < 1 or S < 1 or n_src < 1 or n_dst < 1 or n_src + n_dst != S or not 1 <= r <= n_src or n_img * S > 0x7fffffff // 4:
+        raise VdxError(f"{what}: n_img={n_img} S={S} n_src={n_src} n_dst={n_dst} r={r} is not a plan "
+                       "(n_src + n_dst = S, each at least 1, 1 <= r <= n_src)")
+    a = _lib.TomeArgs()
+    a.src_idx = _tome_buf(src_idx, n_src, torch.int32, what, "src_idx", x.device)
+    a.dst_idx = _tome_buf(dst_idx, n_dst, torch.int32, what, "dst_idx", x.device)
+    a.n_img, a.S, a.n_src, a.n_dst, a.r, a.C = n_img, S, n_src, n_dst, r, C
+    return a
+
+
+def _tome_rows(t, rows: int, C: int, what: str, name: str):
+    """-> (pointer, ld) of fp16 rows covering [rows][C] with a row stride that keeps every row 16-byte aligned."""
+    n, c, ld = _rows(t, name)
+    if n < rows or c != C or ld % 8:
+        raise VdxError(f"{what}: {name} {tuple(t.shape)} with row stride {ld} does not cover [{rows}][{C}] in 16-byte rows")
+    return _p(t, name), ld
+
+
+def _tome_disjoint(a, b, what: str, names: str) -> None:
+    la, lb = a.data_ptr(), b.data_ptr()
+    ha = la + ((a.shape[0] - 1) * a.stride(0) + a.shape[1]) * 2
+    hb = lb + ((b.shape[0] - 1) * b.stride(0) + b.shape[1]) * 2
+    if la < hb and lb < ha:
+        raise VdxError(f"{what}: {names} overlap")
+
+
+def tome_match(t, src_idx, dst_idx, *, n_img, S):
+    """t fp16 rows [n_img * S][C] -> (node_max fp32 [n_img][n_src], node_idx int32 [n_img][n_src]): per image and source i the
+    largest cosine similarity to a destination and the lowest j that reaches it (tests/tome_ref.py `match`).  C % 64 == 0,
+    C <= 1280.  The score matrix is never stored."""
+    what = "tome_match"
+    Cc = t.shape[1] if t.dim() == 2 else 0
+    if Cc < 64 or Cc % 64 or Cc > 1280:
+        raise VdxError(f"{what}: C={Cc} (a multiple of 64 up to 1280)")
+    a = _tome_args(what, t, src_idx, dst_idx, n_img, S, 1, Cc)
+    pt, ld = _tome_rows(t, n_img * S, Cc, what, "t")
+    inv = torch.empty((n_img, S), dtype=torch.float32, device=t.device)
+    node_max = torch.empty((n_img, a.n_src), dtype=torch.float32, device=t.device)
+    node_idx = torch.empty((n_img, a.n_src), dtype=torch.int32, device=t.device)
+    a.inv, a.node_max, a.node_idx = inv.data_ptr(), node_max.data_ptr(), node_idx.data_ptr()
+    with torch.cuda.device(t.device):
+        _launch("vdx_tome_match_f16", C.byref(a), pt, ld)
+    return node_max, node_idx
+
+
+def tome_select(node_max, node_idx, src_idx, dst_idx, *, S, r):
+    """(node_max fp32, node_idx int32) [n_img][n_src] -> (slot int32 [n_img][S], off int32 [n_img][n_dst + 1], items int32
+    [n_img][r]): the r sources with the largest node_max (ties: lower i; NaN last) are merged into destination
+    clamp(node_idx[i]); slot is the merged row of every token, (off, items) each destination's merged sources in ascending i."""
+    what = "tome_select"
+    if not torch.is_tensor(node_max) or node_max.dim() != 2:
+        raise VdxError(f"{what}: node_max must be [n_img][n_src]")
+    n_img = node_max.shape[0]
+    a = _tome_args(what, node_max, src_idx, dst_idx, n_img, S, r, 0)
+    if node_max.shape[1] != a.n_src or not torch.is_tensor(node_idx) or tuple(node_idx.shape) != tuple(node_max.shape):
+        raise VdxError(f"{what}: node_max / node_idx must both be [{n_img}][{a.n_src}]")
+    if _lib.load().vdx_tome_select_lds(a.n_src, a.n_dst) > 160 * 1024 - 256:
+        raise VdxError(f"{what}: {a.n_src} sources and {a.n_dst} destinations do not fit the select kernel's LDS")
+    a.node_max = _tome_buf(node_max, n_img * a.n_src, torch.float32, what, "node_max", node_max.device)
+    a.node_idx = _tome_buf(node_idx, n_img * a.n_src, torch.int32, what, "node_idx", node_max.device)
+    slot = torch.zeros((n_img, S), dtype=torch.int32, device=node_max.device)
+    off = torch.empty((n_img, a.n_dst + 1), dtype=torch.int32, device=node_max.device)
+    items = torch.empty((n_img, r), dtype=torch.int32, device=node_max.device)
+    a.slot, a.off, a.items = slot.data_ptr(), off.data_ptr(), items.data_ptr()
+    with torch.cuda.device(node_max.device):
+        _launch("vdx_tome_select", C.byref(a))
+    return slot, off, items
+
+
+def tome_merge(y, src_idx, dst_idx, slot, off, items, *, n_img, S, r, out=None):
+    """y fp16 rows [n_img * S][C] -> the merged rows [n_img * (S - r)][C]: unmerged sources copied in ascending token index,
+    then the destinations, each the fp32 mean of itself and its merged sources in ascending i."""
+    what = "tome_merge"
+    Cc = y.shape[1] if y.dim() == 2 else 0
+    if Cc < 8 or Cc % 8:
+        raise VdxError(f"{what}: C={Cc} (a multiple of 8)")
+    a = _tome_args(what, y, src_idx, dst_idx, n_img, S, r, Cc)
+    py, ldy = _tome_rows(y, n_img * S, Cc, what, "y")
+    a.slot = _tome_buf(slot, n_img * S, torch.int32, what, "slot", y.device)
+    a.off = _tome_buf(off, n_img * (a.n_dst + 1), torch.int32, what, "off", y.device)
+    a.items = _tome_buf(items, n_img * r, torch.int32, what, "items", y.device)
+    if out is None:
+        out = torch.empty((n_img * (S - r), Cc), dtype=torch.float16, device=y.device)
+    po, ldo = _tome_rows(out, n_img * (S - r), Cc, what, "out")
+    _tome_disjoint(y, out, what, "y and out")
+    with torch.cuda.device(y.device):
+        _launch("vdx_tome_merge_f16", C.byref(a), py, ldy, po, ldo)
+    return out
+
+
+def tome_unmerge_add(x, slot, t, src_idx, dst_idx, *, n_img, S, r, out=None):
+    """x fp16 merged rows [n_img * (S - r)][C], t fp16 rows [n_img * S][C] -> fp16(fp32(x[slot[p]]) + fp32(t[p])) for every token;
+    `out=t` adds in place."""
+    what = "tome_unmerge_add"
+    Cc = t.shape[1] if t.dim() == 2 else 0
+    if Cc < 8 or Cc % 8:
+        raise VdxError(f"{what}: C={Cc} (a multiple of 8)")
+    a = _tome_args(what, t, src_idx, dst_idx, n_img, S, r, Cc)
+    px, ldx = _tome_rows(x, n_img * (S - r), Cc, what, "x")
+    pt, ldt = _tome_rows(t, n_img * S, Cc, what, "t")
+    a.slot = _tome_buf(slot, n_img * S, torch.int32, what, "slot", t.device)
+    if out is None:
+        out = torch.empty((n_img * S, Cc), dtype=torch.float16, device=t.device)
+    po, ldo = _tome_rows(out, n_img * S, Cc, what, "out")
+    _tome_disjoint(x, out, what, "x and out")
+    if out.data_ptr() != t.data_ptr() or ldo != ldt:
+        _tome_disjoint(t, out, what, "t and out (unless out is t)")
+    with torch.cuda.device(t.device):
+        _launch("vdx_tome_unmerge_add_f16", C.byref(a), px, ldx, pt, ldt, po, ldo)
+    return out

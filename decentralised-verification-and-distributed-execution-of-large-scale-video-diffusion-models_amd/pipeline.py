@@ -80,6 +80,10 @@ class DiffuserConfig:
     # FreeU (UNet3DConditionModel.enable_freeu; diffusers' enable_freeu, unpinned): (b1, b2, s1, s2), the backbone factors and the
     # skip filter's scales of up blocks 0 and 1, on every denoising step of the job.  None = off, as always
     freeu: Optional[Tuple[float, float, float, float]] = None
+    # token merging (UNet3DConditionModel.enable_tome; tomesd's apply_patch(ratio, max_downsample=1, sx=2, sy=2), unpinned): the share
+    # of the level-0 spatial self-attentions' tokens merged away on every denoising step of the job.  None = off, as always
+    tome: Optional[float] = None
+    tome_seed: Optional[int] = None        # draw the cells' destination offsets once from this seed (None: every cell's first token)
     # temporal co-denoising (vdx/codenoise.py; MultiDiffusion along time, unpinned): ONE latent for the whole clip, the windows'
     # noise predictions averaged at every step where they overlap, one scheduler step for the clip; no final blend.  False = one
     # trajectory per window and the ramp blend after the loop, as always
@@ -210,6 +214,17 @@ def check_guidance_rescale(cfg) -> float:
     return float(phi)
 
 
+def check_tome(cfg) -> Optional[dict]:
+    """`cfg.tome` / `cfg.tome_seed` as {"ratio", "sx", "sy", "seed", "max_downsample"} (None when off); `ValueError` before any work
+    for a ratio `enable_tome` refuses, or a seed without a ratio."""
+    if cfg.tome is None:
+        if cfg.tome_seed is not None:
+            raise ValueError("tome_seed needs tome")
+        return None
+    from .tome import check_params
+    return check_params(cfg.tome, seed=cfg.tome_seed)
+
+
 SCHEDULERS = ("ddim", "dpmpp_2m")
 
 
@@ -294,6 +309,7 @@ class DistributedVideoDiffuser:
         next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off."""
         self.cfg = cfg
         check_freeu(cfg)
+        check_tome(cfg)
         phi = check_guidance_rescale(cfg)
         self._rescale_kw = {"guidance_rescale": phi} if phi != 0 else {}     # off: the step is called as it always was
         if check_free_init(cfg) > 1 and init_latents is not None:
@@ -508,6 +524,7 @@ class DistributedVideoDiffuser:
         self._co_rec = []
         iters = check_free_init(cfg, exchange)
         freeu = check_freeu(cfg)
+        tome = check_tome(cfg)
         if exchange not in ("allgather", "halo"):
             raise ValueError(f"unknown exchange {exchange!r}")
         cp = self.plan()
@@ -531,6 +548,11 @@ class DistributedVideoDiffuser:
             freeu0 = self.unet.freeu
             self.unet.enable_freeu(**freeu)
             info["freeu"] = freeu
+        if tome is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            tome0 = self.unet.tome
+            self.unet.enable_tome(**tome)
+            info["tome"] = tome
         try:
             for it in range(iters):
                 out, spent = self._round(start, cp, exchange, comm)
@@ -550,6 +572,8 @@ class DistributedVideoDiffuser:
             self.ctx = ctx0                                            # the next call's iteration 0 starts as this one did
             if freeu is not None:
                 self.unet.enable_freeu(**freeu0) if freeu0 is not None else self.unet.disable_freeu()
+            if tome is not None:
+                self.unet.enable_tome(**tome0) if tome0 is not None else self.unet.disable_tome()
         if iters > 1:
             self.free_init_starts = starts
             info["free_init"] = rec
@@ -605,6 +629,11 @@ def build_arg_parser():
     scheduler and the other options, with FreeU in the UNet's up blocks 0 and 1 (vdx/unet3d.py `enable_freeu`, csrc/freeu.hip):
     the first half of the hidden state's channels times B, the skip tensors' lowest frequencies times S; the result and the
     JSON records then carry `"freeu": {"b1", "b2", "s1", "s2"}`; without the flag the run is the one it always was.
+    `--tome RATIO [--tome_seed N]` (no reference counterpart; `tomesd.apply_patch(ratio, max_downsample=1, sx=2, sy=2)`, unpinned)
+    samples every step of the job, whatever the mode, exchange, scheduler and the other options, with token merging around the
+    level-0 spatial self-attentions (vdx/unet3d.py `enable_tome`, csrc/tome.hip): int(S RATIO) of an image's S tokens are merged
+    into their most similar destination before the attention and read its row back after; the result and the JSON records
+    then carry `"tome": {"ratio", "sx", "sy", "seed", "max_downsample"}`; without the flag the run is the one it always was.
     `--co_denoise` (no reference counterpart; MultiDiffusion along time, unpinned) samples ONE latent for the whole clip: at every
     step the windows' noise predictions are averaged where they overlap and one scheduler step advances the clip (vdx/codenoise.py,
     csrc/codenoise.hip), so there is one exchange per step instead of one per job and no blend at the end; every mode, scheduler
@@ -688,6 +717,9 @@ def build_arg_parser():
     p.add_argument("--free_init_order", type=int, default=4, help="FreeInit: order of the butterworth filter")
     p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
                    help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
+    p.add_argument("--tome", type=float, default=None, metavar="RATIO",
+                   help="token merging around the level-0 spatial self-attentions: share of the tokens merged away, in (0, 0.75] (default: off)")
+    p.add_argument("--tome_seed", type=int, default=None, help="token merging: draw the cells' destination offsets once from this seed")
     p.add_argument("--co_denoise", action="store_true",
                    help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
     p.add_argument("--tile", type=int, nargs=2, default=None, metavar=("TH", "TW"),
@@ -847,8 +879,12 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     factor = check_factor(cfg.interpolate)      # refused before anything is loaded
     free_init_iters = check_free_init(cfg, exchange)
     freeu = check_freeu(cfg)
+    tome = check_tome(cfg)
     co = check_co_denoise(cfg, exchange)
     tile = check_tile(cfg, exchange)            # None: the option is off
+    if tome is not None:                        # the UNet's frame is a tile where tiling is on, else the whole latent frame
+        from .tome import check_grid
+        check_grid(*((tile[0], tile[1]) if tile is not None else (cfg.height // 8, cfg.width // 8)), tome)
     loop = check_loop(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
     pixel_mask = check_mask(cfg, exchange)      # None: the option is off
     phi = check_guidance_rescale(cfg)
@@ -935,6 +971,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
+            **({"tome": tome} if tome is not None else {}),
             **({"co_denoise": info["co_denoise"]} if co else {}), **({"tile": info["tile"]} if tile is not None else {}),
             **({"loop": info["loop"]} if loop else {}),
             **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
@@ -967,6 +1004,8 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {"freeu": res["freeu"]} if "freeu" in res else {}
+        if "tome" in res:
+            source["tome"] = res["tome"]
         if "co_denoise" in res:
             source["co_denoise"] = res["co_denoise"]
         if "tile" in res:
@@ -998,6 +1037,8 @@ def main(argv=None) -> int:
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             if "freeu" in res:
                 rec["freeu"] = res["freeu"]
+            if "tome" in res:
+                rec["tome"] = res["tome"]
             if "co_denoise" in res:
                 rec["co_denoise"] = res["co_denoise"]
             if "tile" in res:

@@ -90,6 +90,8 @@ class UNet3DConditionModel(nn.Module):
         self._text_ref = None                  # (encoder_hidden_states object, its version, (B, device), padded copy)
         self._text_kv: Dict[str, tuple] = {}   # cross-attention K / V^T of that text, per transformer
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
+        self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
+        self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
 
     # ------------------------------------------------------------------------------------------
     # FreeU (Si et al. 2023; diffusers' enable_freeu / disable_freeu, unpinned; csrc/freeu.hip)
@@ -118,6 +120,48 @@ class UNet3DConditionModel(nn.Module):
             return None
         (b1, s1), (b2, s2) = self._freeu
         return {"b1": b1, "b2": b2, "s1": s1, "s2": s2}
+
+    # ------------------------------------------------------------------------------------------
+    # Token merging (Bolya & Hoffman 2023; tomesd's apply_patch, unpinned; vdx/tome.py, csrc/tome.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_tome(self, ratio=0.5, sx=2, sy=2, seed=None, max_downsample=1):
+        """`tomesd.apply_patch(model, ratio, max_downsample, sx, sy)` for the spatial self-attentions (`attn1`) of the levels
+        whose downsample factor is at most `max_downsample` (1: level 0, two transformers on the way down and three on the way
+        up): before each, the r = int(S ratio) sources most similar to a destination are merged into it, the attention runs on
+        S - r tokens and every token reads its row back.  Cross-attention, feed-forward, temporal transformers and the VAE see
+        all S tokens.  `seed`: the cells' destination offsets are drawn once per token grid from that seed and then held
+        (`tomesd` redraws per call); None: every cell's first token.  Refused with `ValueError`, the state left as it was: a
+        ratio that is not finite or outside (0, 1 - 1 / (sx sy)], sx or sy below 1 or sx sy < 2, a max_downsample outside
+        {1, 2, 4, 8}."""
+        from .tome import check_params
+        self._tome = check_params(ratio, sx=sx, sy=sy, seed=seed, max_downsample=max_downsample)
+        self._tome_tables = {}
+        return self
+
+    def disable_tome(self):
+        """The forward is again the one without token merging, launch for launch."""
+        self._tome = None
+        self._tome_tables = {}
+        return self
+
+    @property
+    def tome(self) -> Optional[Dict[str, object]]:
+        """{"ratio", "sx", "sy", "seed", "max_downsample"} while token merging is enabled, else None."""
+        return dict(self._tome) if self._tome is not None else None
+
+    def _tome_plan(self, hh, ww, down, device):
+        """(src_idx, dst_idx, r) on `device` for the self-attention of a transformer on an (hh, ww) grid, or None where token
+        merging does not apply: disabled, a level above max_downsample, a grid without cells, r = 0."""
+        tm = self._tome
+        if tm is None or down > tm["max_downsample"]:
+            return None
+        key = (hh, ww, str(device))
+        plan = self._tome_tables.get(key)
+        if plan is None:
+            from .tome import partition
+            part = partition(hh, ww, tm["ratio"], tm["sx"], tm["sy"], tm["seed"])
+            plan = self._tome_tables[key] = (part.src_idx.to(device), part.dst_idx.to(device), part.r)
+        return plan if plan[2] > 0 and plan[1].numel() > 0 else None
 
     # ------------------------------------------------------------------------------------------
     # weights
@@ -512,33 +556,56 @@ class UNet3DConditionModel(nn.Module):
                           rows_per_sample=rows_per_sample, eps=1e-6, silu_act=False, partition_samples=part)
         return ops.gemm(n, w, M=M, bias=W[p + ".proj_in.bias"])
 
-    def _spatial_transformer(self, p, x, ehs_pad, n_img, F, hh, ww, dup=False):
-        """`dup` (the first spatial transformer of a CFG batch whose two items are the same tensor, forward): x holds ONE
-        item's rows [n_img/2 * S][C].  `norm` -> `proj_in` -> self-attention -> + and the LayerNorm and query projection
-        of the cross-attention see no text, so they are computed once; the two items part at the cross-attention's keys /
-        values.  Returns the rows of both items."""
-        W, g = self.W, self.cfg.norm_num_groups
+    def _level_down_of(self, p):
+        """The downsample factor of the level a spatial transformer named p ("down_blocks.i...", "mid_block...",
+        "up_blocks.i...") sits on: 1 at level 0."""
+        nlev = len(self.cfg.block_out_channels)
+        kind, _, rest = p.partition(".")
+        if kind == "down_blocks":
+            return 1 << int(rest.split(".")[0])
+        if kind == "up_blocks":
+            return 1 << (nlev - 1 - int(rest.split(".")[0]))
+        return 1 << (nlev - 1)
+
+    def _self_attention(self, b, t, n_img, hh, ww, down=1):
+        """`t + attn1(norm1(t))` of transformer block b on the rows t [n_img * hh * ww][C]; `down`: the level's downsample
+        factor (token merging applies up to `enable_tome`'s max_downsample)."""
+        W = self.W
         S = hh * ww
-        M_out = n_img * S
-        if dup:
-            n_img //= 2
         M = n_img * S
-        C = x.shape[1]
+        C = t.shape[1]
         heads = C // 64
         scale = 64 ** -0.5
-        b = p + ".transformer_blocks.0"
-        t = self._norm_proj_in(p, x, n_img, S, M, part=2 * n_img if dup else 0)
         # --- self-attention: q | k | v from ONE projection; the flash kernel takes V as rows (transposed by its LDS read),
         # so there is no V^T product and no padded copy for token counts that are no multiple of 8 (latent 40x72 ->
         # 5x9 = 45 tokens at the mid block, InferNet/tests/test_pipeline.py:293; 16x16 -> 2x2 = 4, InferNet/neurons/miner.py:491-494)
         ln = ops.layernorm(t, W[b + ".norm1.weight"], W[b + ".norm1.bias"], M=M)
         wqkv = W[b + ".attn1.to_qkv.weight"]
-        if self.ff_block_bytes and self.lean_attn and n_img % 2 == 0 and M * C * 2 > (128 << 20):
+        tome = self._tome_plan(hh, ww, down, t.device) if self._tome is not None else None
+        if tome is not None:
+            # token merging: the block's input t is the metric; the attention runs on S - r rows per image (the single q|k|v
+            # path, whatever the memory-lean switches say) and every token reads its merged row back under the residual
+            src_idx, dst_idx, r = tome
+            node_max, node_idx = ops.tome_match(t, src_idx, dst_idx, n_img=n_img, S=S)
+            slot, off, items = ops.tome_select(node_max, node_idx, src_idx, dst_idx, S=S, r=r)
+            lm = ops.tome_merge(ln, src_idx, dst_idx, slot, off, items, n_img=n_img, S=S, r=r)
+            del ln, node_max, node_idx, off, items
+            Sm, Mm = S - r, n_img * (S - r)
+            qkv = ops.gemm(lm, wqkv, M=Mm)
+            del lm
+            o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_seq=n_img, sq=Sm, skv=Sm, skv_pad=Sm, heads=heads,
+                               seq_per_kv=1, scale=scale, v_rows=True)
+            del qkv
+            am = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=Mm, bias=W[b + ".attn1.to_out.0.bias"])
+            del o
+            t = ops.tome_unmerge_add(am, slot, t, src_idx, dst_idx, n_img=n_img, S=S, r=r)
+            del am, slot
+        elif self.ff_block_bytes and self.lean_attn and n_img % 2 == 0 and M * C * 2 > (128 << 20):
             # memory-lean mode: images are independent in the self-attention, so the projection and the attention run
             # over the images in two halves and only half of [rows][3C] is alive at a time.
             # (level 0 only: 0.6 ms per step on a 16-frame window for 45 MB of its peak — measured 4.33 against 4.374 GB
             # with the concat pieces on, gpurun_out r3n — which is what keeps the per-device share under 15 %)
-            o = torch.empty((M, C), dtype=torch.float16, device=x.device)
+            o = torch.empty((M, C), dtype=torch.float16, device=t.device)
             hm, hn = M // 2, n_img // 2
             for r0 in (0, hm):
                 qkv = ops.gemm(ln[r0:r0 + hm], wqkv, M=hm)
@@ -559,8 +626,28 @@ class UNet3DConditionModel(nn.Module):
             o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_seq=n_img, sq=S, skv=S, skv_pad=S, heads=heads,
                                seq_per_kv=1, scale=scale, v_rows=True)
             del qkv
-        t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)
-        del o
+        if tome is None:
+            t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)
+            del o
+        return t
+
+    def _spatial_transformer(self, p, x, ehs_pad, n_img, F, hh, ww, dup=False):
+        """`dup` (the first spatial transformer of a CFG batch whose two items are the same tensor, forward): x holds ONE
+        item's rows [n_img/2 * S][C].  `norm` -> `proj_in` -> self-attention -> + and the LayerNorm and query projection
+        of the cross-attention see no text, so they are computed once; the two items part at the cross-attention's keys /
+        values.  Returns the rows of both items."""
+        W, g = self.W, self.cfg.norm_num_groups
+        S = hh * ww
+        M_out = n_img * S
+        if dup:
+            n_img //= 2
+        M = n_img * S
+        C = x.shape[1]
+        heads = C // 64
+        scale = 64 ** -0.5
+        b = p + ".transformer_blocks.0"
+        t = self._norm_proj_in(p, x, n_img, S, M, part=2 * n_img if dup else 0)
+        t = self._self_attention(b, t, n_img, hh, ww, self._level_down_of(p))
         # --- cross-attention over the (padded) text tokens; all F frames of a sample share K/V
         nb = ehs_pad.shape[0] // TEXT_PAD
         k5 = self.fuse_cross_attn and b + ".attn2.k5" in W and ops.cross_attn_block_supported(C, self._text_len)

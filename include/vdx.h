@@ -786,6 +786,52 @@ int vdx_freeu_filter_f16(const void* x, int ldx, const double* tw_h, const doubl
 int vdx_freeu_scale_f16(void* x, int ld, size_t rows, int C, float b, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Token merging (Bolya & Hoffman, "Token Merging for Stable Diffusion", CVPRW 2023; the tomesd package's
+ * bipartite_soft_matching_random2d, unpinned) around a spatial self-attention, on rows [n_img][S][C] fp16 (nothing in the
+ * reference; UNet3DConditionModel.enable_tome, the job's --tome, vdx/tome.py, csrc/tome.hip).  tests/tome_ref.py states the
+ * definition.  The S tokens of an image are partitioned on the host into n_dst destinations and n_src = S - n_dst sources
+ * (tables of token indices, ascending, shared by all images).  Per image: every source finds its most similar destination
+ * (match); the r sources with the largest similarity are merged into it (select); a tensor's merged layout has
+ * S' = S - r rows, first the unmerged sources in ascending token index, then the destinations (merge); after the attention
+ * every token reads its row back (unmerge).  No float atomics; a result depends on its own image alone and is the same on
+ * every run and for any n_img.  Every index read from a device buffer is clamped to its range before it addresses anything.
+ * "The same on every run" holds for tables that are a partition (every token once, as vdx/tome.py builds them): with
+ * caller-made tables that name a token twice, several writers meet in slot[] and which one stays is not defined; every
+ * value is still in range and nothing faults.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vdx_tome_args {
+    const int32_t* src_idx;  /* [n_src] token index of source i, in [0, S)                                          */
+    const int32_t* dst_idx;  /* [n_dst] token index of destination j                                                */
+    float* inv;              /* [n_img][S] match: workspace, 1 / sqrt(sum_c fp32(t)^2) of every token               */
+    float* node_max;         /* [n_img][n_src] match out, select in: the largest score of source i (-inf: none)     */
+    int32_t* node_idx;       /* [n_img][n_src] match out, select in: its j, the lowest of equal ones, in [0, n_dst) */
+    int32_t* slot;           /* [n_img][S] select out: the merged row token p reads back from, in [0, S - r)        */
+    int32_t* off;            /* [n_img][n_dst + 1] select out: CSR offsets into items, off[n_dst] = r               */
+    int32_t* items;          /* [n_img][r] select out: the merged sources of each destination, ascending i          */
+    int32_t n_img, S, n_src, n_dst;  /* n_src + n_dst = S, each at least 1                                          */
+    int32_t r;               /* sources merged per image, 1 <= r <= n_src                                           */
+    int32_t C;               /* channels of the rows handed to match / merge / unmerge                              */
+} vdx_tome_args;
+/* score[i][j] = (sum_c t[src i][c] t[dst j][c]) inv[src i] inv[dst j], fp32 accumulation on MFMA; node_max / node_idx are its
+ * maximum over j and the lowest such j.  A NaN score never wins; a source with no winning score keeps (-inf, 0).  The score
+ * matrix is never stored.  t: rows of stride ld >= C (a multiple of 8), 16-byte aligned; C a multiple of 64, at most 1280.
+ * Two launches (the inverse norms, the match).                                                                          */
+int vdx_tome_match_f16(const vdx_tome_args* a, const void* t, int ld, vdx_stream_t stream);
+/* Bytes of LDS the select needs for (n_src, n_dst); it refuses plans above 160 KiB - 256.                               */
+size_t vdx_tome_select_lds(int n_src, int n_dst);
+/* Order the sources by node_max descending (ties: lower i; NaN below every number; -0 = +0); the first r are merged into
+ * destination clamp(node_idx[i]).  Writes slot, off and items.  One workgroup per image, one launch.                    */
+int vdx_tome_select(const vdx_tome_args* a, vdx_stream_t stream);
+/* out rows [n_img][S - r][C]: an unmerged source's row is y's, bit for bit; destination j's row is
+ * fp16((fp32(y[dst j]) + sum fp32(y[src i])) / fp32(1 + count)) over its items in ascending i, each add rounded to fp32.
+ * C a multiple of 8; out must not overlap y.  One launch.                                                               */
+int vdx_tome_merge_f16(const vdx_tome_args* a, const void* y, int ldy, void* out, int ldo, vdx_stream_t stream);
+/* out[p] = fp16(fp32(x[slot[p]]) + fp32(t[p])) for every token p of every image; x: the merged rows [n_img][S - r][C],
+ * t, out: [n_img][S][C]; out may be t, it must not overlap x.  One launch.                                              */
+int vdx_tome_unmerge_add_f16(const vdx_tome_args* a, const void* x, int ldx, const void* t, int ldt, void* out, int ldo,
+                             vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

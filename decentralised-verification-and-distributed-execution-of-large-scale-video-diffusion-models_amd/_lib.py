@@ -166,7 +166,7 @@ SIGNATURES = {
     "vdx_cotile_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _f,
                                          _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _vp]),
     # seamless looping: a ring window's input and the fused whole-clip steps over windows that wrap (no reference counterpart;
-    # vdx/codenoise.py `loop_plan`, csrc/coloop.hip)
+    # vdx/codenoise.py `loop_plan`, csrc/codenoise.hip, its RING flag)
     "vdx_cfg_input_loop_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
     "vdx_coloop_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
     "vdx_coloop_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,

@@ -19,7 +19,7 @@ size, and the fused step averages with the product of three per-axis normalised 
 in tests/test_cotile_gpu.py against tests/cotile_ref.py; again no external implementation and no quality claim.
 
 With `DiffuserConfig(loop=True)` / `--loop` the windows lie on a RING (AnimateDiff's `closed_loop` context option; MultiDiffusion
-along time with periodic windows; csrc/coloop.hip): `loop_plan` spreads windows of one length evenly over the clip and lets the
+along time with periodic windows; csrc/codenoise.hip, its RING flag): `loop_plan` spreads windows of one length evenly over the clip and lets the
 last ones wrap over its end into the first frames, so frames T-1 and 0 are denoised together in one UNet call at every step like
 any other neighbouring pair, and the clip played as a loop has no jump there (`loop_table`, `check_loop` below).  Pinned in
 tests/test_coloop_gpu.py against tests/coloop_ref.py, the wrap itself by rotation equivariance; NOT pinned and not claimed: no
@@ -92,7 +92,7 @@ def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
     return bool(getattr(cfg, "co_denoise", False))
 
 
-# ---- ring windows (seamless looping; csrc/coloop.hip) -----------------------------------------------------------------------------
+# ---- ring windows (seamless looping; csrc/codenoise.hip, its RING flag) -----------------------------------------------------------------------------
 def loop_plan(total: int, world: int, chunk_size: int = 0, overlap: int = 4, overlap_rule: str = "coherent") -> ChunkPlan:
     """The windows of a looping clip: `size` and `ov` by the planner's own rules (`auto_chunk`, the overlap rule), `ov >= 1`;
     with `step = size - ov`, `n = world * ceil(ceil(total / step) / world)` windows `(s_i, s_i + size)`, `s_i = (i * total) // n`:
@@ -312,7 +312,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     loop = bool(getattr(cfg, "loop", False))
     table = loop_table(cp, T) if loop else window_table(cp, T)
     per, world, rank = cp.per_rank, d.world, d.rank
-    boxes = [None] if tiles is None else tiles.boxes              # None: the whole frame, as always
+    boxes = [()] if tiles is None else tiles.boxes                # (): the whole frame, as always
     nt = len(boxes)
     area = H * W if tiles is None else tiles.th * tiles.tw
     slot = 2 * C * cp.chunk * area
@@ -332,17 +332,21 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
         reset()
     spent = {"denoise_s": 0.0, "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0,
              "payload_bytes_actual": 0}
+    # the window's UNet input and the step, decided once per round: the op with the range it takes, the method with its leading arguments
+    if loop:
+        input_op, spans = ops.cfg_input_loop, [(s, e - s) for s, e in mine]
+        step, head, step_kw = sched.step_cfg_loop, (packed, rows, wn), {}
+    elif tiles is None:
+        input_op, spans = ops.cfg_input_window, mine
+        step, head, step_kw = sched.step_cfg_windows, (packed, rows, wn), d._rescale_kw
+    else:
+        input_op, spans = ops.cfg_input_tile, mine
+        step, head, step_kw = sched.step_cfg_tiles, (packed, rows, wn, grid), {}
     t_round = time.time()
     for i, t in enumerate(d.schedule):
-        for j, (s, e) in enumerate(mine):
+        for j, span in enumerate(spans):
             for k, box in enumerate(boxes):
-                if loop:
-                    x = ops.cfg_input_loop(z, d.ctx, cfg.context_weight, s, e - s)
-                elif box is None:
-                    x = ops.cfg_input_window(z, d.ctx, cfg.context_weight, s, e)
-                else:
-                    x = ops.cfg_input_tile(z, d.ctx, cfg.context_weight, s, e, *box)
-                noise = d.unet(x, t, encoder_hidden_states=emb).sample
+                noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=emb).sample
                 local[j, k * slot:k * slot + noise.numel()].copy_(noise.reshape(-1))
         delay = emu_gather_delay_s(payload_step, cfg)             # per step: one exchange per step is what the method costs
         if delay > 0:
@@ -355,12 +359,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
             dist.all_gather_into_tensor(packed.view(-1), local.view(-1))
             d._sync()
             spent["net_gather_s"] += time.time() - t0
-        if loop:
-            z = sched.step_cfg_loop(packed, rows, wn, t, z, cfg.guidance_scale)
-        elif grid is None:
-            z = sched.step_cfg_windows(packed, rows, wn, t, z, cfg.guidance_scale, **d._rescale_kw)
-        else:
-            z = sched.step_cfg_tiles(packed, rows, wn, grid, t, z, cfg.guidance_scale)
+        z = step(*head, t, z, cfg.guidance_scale, **step_kw)
         if d.latent_mask is not None:                             # masked video-to-video (vdx/inpaint.py): the whole clip, s = 0
             d._mask_step(z, i, 0)
         spent["network_bytes"] += bytes_step

@@ -1,8 +1,11 @@
 // cofuse_common.h — what the co-fused whole-clip steps share: the window table, the fp32 fuse of the windows' noise, the vector
-// accesses and the host checks.  codenoise.hip (the plain co-denoising steps) and rescale.hip (the same steps with CFG rescale and
-// their statistics pass) both fuse U and Cc through these, so the two cannot drift apart.
+// accesses, the ONE line-per-block step kernel with its tail, dispatch and launcher, and the host checks.  codenoise.hip (the plain
+// co-denoising steps, flat and ring), rescale.hip (the same steps with CFG rescale and their statistics pass) and cotile.hip (the
+// row-per-block tiled steps) all go through these, so the variants cannot drift apart.  A variant is a guidance policy (what turns
+// the fused u, c into the guided noise), the RING flag, or a block map of its own that ends in `cofuse_tail`.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "vdx_common.h"
 #include "step_chains.h"   // rn16
@@ -43,6 +46,18 @@ __device__ __forceinline__ void store_halves(f16* p, const f16 (&v)[E]) {
     }
 }
 
+// x = fp16(x + fp16(weight * ctx)) on E elements: the ctx term of every UNet-input kernel, with `cfg_input_kernel`'s two roundings
+template <int E>
+__device__ __forceinline__ void add_ctx(f16 (&x)[E], const f16* ctx, float weight) {
+    f16 cx[E];
+    load_halves<E>(ctx, cx);
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const f16 t = rn16(__fmul_rn((float)cx[j], weight));      // fp16(cw * ctx)
+        x[j] = rn16(__fadd_rn((float)x[j], (float)t));            // fp16(x + t)
+    }
+}
+
 // acc = first ? w * x : acc + w * x, the product and the sum rounded separately (blend_acc_kernel's guard: no fma_mix)
 __device__ __forceinline__ float fuse_term(float acc, float w, float x, bool first) {
     float prod = __fmul_rn(w, x);
@@ -52,7 +67,7 @@ __device__ __forceinline__ float fuse_term(float acc, float w, float x, bool fir
 
 // U, Cc of the E elements at (c, t, p) fused over the windows that hold frame t, k ascending, then rounded to fp16 (returned as
 // the floats the chains take).  t is uniform over a block, so the window loop, the table reads and the weights are too.
-// RING (coloop.hip): window k holds the frames (s_k + f) mod T, f in [0, L_k), with 0 <= s_k < T and L_k <= T, so the one
+// RING (the vdx_coloop_* steps): window k holds the frames (s_k + f) mod T, f in [0, L_k), with 0 <= s_k < T and L_k <= T, so the one
 // wrap is a compare and an add; the default leaves the plain instantiations as they were.
 template <int E, bool RING = false>
 __device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab, int K, const float* wn, int C, int T, int HW, int c,
@@ -90,40 +105,110 @@ __device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab,
     }
 }
 
+
+// ---- the step itself ---------------------------------------------------------------------------------------------------------------
+// A guidance policy turns the fused (u, c) of one element into the new latent (and x0).  `prologue()` is called by all 256 lanes of
+// a block before any of them leaves and gives one scalar per block; `elem<MODE>` is the chain of step_chains.h.  MODE 0: DDIM;
+// 1: DPM-Solver++ first order; 2: second order.  This one is plain classifier-free guidance: no state, no LDS, no prologue.
+struct cfg_guidance {
+    __device__ __forceinline__ float prologue() const { return 0.f; }
+    template <int MODE>
+    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, float, const ddim_coef& kd, const dpm_coef& kp, f16& x0,
+                                         f16& o) const {
+        if (MODE == 0) o = cfg_ddim_elem(u, c, x, kd);
+        else dpm_elem<true, MODE == 2>(u, c, x, x0p, kp, x0, o);
+    }
+};
+
+// the tail of every co-fused step kernel: a lane's E elements at i, from their fused (u, c) to the stores
+template <int MODE, int E, class G>
+__device__ __forceinline__ void cofuse_tail(const f16* z, const f16* x0_prev, f16* x0_out, f16* out, size_t i, const float (&uf)[E],
+                                            const float (&cf)[E], const G& g, float r, const ddim_coef& kd, const dpm_coef& kp) {
+    f16 x[E], xp[E];
+    load_halves<E>(z + i, x);
+    if (MODE == 2) load_halves<E>(x0_prev + i, xp);
+    f16 o[E], x0[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) g.template elem<MODE>(uf[j], cf[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, r, kd, kp, x0[j], o[j]);
+    if (MODE != 0) store_halves<E>(x0_out + i, x0);
+    store_halves<E>(out + i, o);
+}
+
+// Block map: a block works on ONE (c, t) line of h*w elements (tiles of 256 lanes x E elements): see codenoise.hip.
+template <int MODE, int E, bool RING, class G>
+__global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f16* win, cofuse_tab tab, int K, const float* wn,
+                                                          const f16* x0_prev, f16* x0_out, f16* out, ddim_coef kd, dpm_coef kp, G g,
+                                                          int C, int T, int HW, unsigned tiles_per_line) {
+    const float r = g.prologue();                                 // all 256 lanes, before any of them leaves
+    const unsigned line = blockIdx.x / tiles_per_line, tile = blockIdx.x - line * tiles_per_line;
+    const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
+    const int p = (int)((tile * 256u + threadIdx.x) * (unsigned)E);
+    if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
+    float uf[E], cf[E];
+    cofuse_uc<E, RING>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);   // uniform over the block: t is
+    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, r, kd, kp);
+}
+
+// go(MODE, E) as integral constants, for the one rule of the mode and an access width of 8, 4 or 1 halves
+template <class F>
+static inline void step_dispatch(int mode, const void* x0_prev, int e, F&& go) {
+    const auto width = [&](auto m) {
+        if (e == 8) go(m, std::integral_constant<int, 8>{});
+        else if (e == 4) go(m, std::integral_constant<int, 4>{});
+        else go(m, std::integral_constant<int, 1>{});
+    };
+    switch (mode == 0 ? 0 : x0_prev ? 2 : 1) {
+    case 0: width(std::integral_constant<int, 0>{}); break;
+    case 1: width(std::integral_constant<int, 1>{}); break;
+    default: width(std::integral_constant<int, 2>{}); break;
+    }
+}
+
+// the launch of a line-per-block step whose arguments `cofuse_check` has passed (it gave `tab` and `e`)
+template <bool RING, class G>
+static int cofuse_launch(const char* what, int mode, const void* z, const void* windows, const cofuse_tab& tab, int e, int K,
+                         const float* wn, const void* x0_prev, void* x0_out, void* lat_out, ddim_coef kd, dpm_coef kp, G g, int C, int T,
+                         int HW, vdx_stream_t stream) {
+    const size_t per_tile = 256 * (size_t)e;
+    const size_t tiles_per_line = ((size_t)HW + per_tile - 1) / per_tile;
+    const size_t blocks = tiles_per_line * C * T;
+    VDX_CHECK(blocks <= 0x7fffffffull, "%s: %zu blocks exceed the grid", what, blocks);
+    step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
+        hipLaunchKernelGGL((cofuse_step_kernel<decltype(m)::value, decltype(ee)::value, RING, G>), dim3((unsigned)blocks), dim3(256), 0,
+                           (hipStream_t)stream, (const f16*)z, (const f16*)windows, tab, K, wn, (const f16*)x0_prev, (f16*)x0_out,
+                           (f16*)lat_out, kd, kp, g, C, T, HW, (unsigned)tiles_per_line);
+    });
+    return vdx_launch_status(what);
+}
+
+// ---- the host checks ---------------------------------------------------------------------------------------------------------------
 static inline bool co_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + nb && pb < pa + na;
 }
 
-// Every check of a co-fused step, before a launch -> 0 and the table `tab` and the access width `e` (8, 4 or 1 halves), else the
-// error.  mode 0: DDIM (no x0 history); otherwise DPM-Solver++.  `writes` false: a statistics pass, which reads
-// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).  `ring`
-// (coloop.hip): a row (off, s, L) means the frames (s + f) mod T, so 0 <= s < T and 1 <= L <= T replace s + L <= T, and a
-// frame is held under that rule; everything else, the choice of `e` included, is the same.
-static inline int cofuse_check(const char* what, int mode, bool writes, const void* z, const void* windows, size_t windows_elems,
-                               const int64_t* win_off, const int* win_start, const int* win_len, int K, const float* wn,
-                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, cofuse_tab& tab, int& e,
-                               bool ring = false) {
-    VDX_CHECK((z || !writes) && windows && win_off && win_start && win_len && wn && (lat_out || !writes), "%s: null pointer", what);
-    VDX_CHECK(C > 0 && T > 0 && HW > 0 && HW <= 1 << 30, "%s: bad shape C=%d T=%d HW=%d", what, C, T, HW);
-    VDX_CHECK(K >= 1 && K <= COFUSE_MAX_WINDOWS, "%s: %d windows, 1..%d are supported", what, K, COFUSE_MAX_WINDOWS);
-    VDX_CHECK(mode == 0 || !writes || x0_out, "%s: x0_out is null", what);
-    const size_t n = (size_t)C * T * HW, nb = n * sizeof(f16);
-    VDX_CHECK((size_t)C * T <= (size_t)1 << 30 && n <= (size_t)1 << 40, "%s: latent too large", what);
-    for (const void* ptr : {z, windows, (const void*)wn, x0_prev, (const void*)x0_out, (const void*)lat_out})
-        VDX_CHECK(((uintptr_t)ptr & 15) == 0, "%s: pointer not 16-byte aligned", what);
-    tab = cofuse_tab{};
-    e = HW % 8 == 0 ? 8 : HW % 4 == 0 ? 4 : 1;
+// the widest access (8, 4 or 1 halves, at most `e`) that still divides v
+static inline void co_narrow(int& e, long long v) {
+    if (e == 8 && v % 8) e = v % 4 ? 1 : 4;
+    if (e == 4 && v % 4) e = 1;
+}
+
+// The time-window table of a step: every row (off, s, L) against T and the buffer, `e` narrowed to what every offset allows, and
+// every frame in some window.  `ring`: a row means the frames (s + f) mod T, so 0 <= s < T and 1 <= L <= T replace s + L <= T, and
+// a frame is held under that rule.  `need(k, L, elems)` gives the elements window k occupies from its offset (it may refuse the row).
+template <class Tab, class Need>
+static inline int cofuse_windows(const char* what, bool ring, size_t windows_elems, const int64_t* win_off, const int* win_start,
+                                 const int* win_len, int K, int T, Need&& need, Tab& tab, int& e) {
     for (int k = 0; k < K; ++k) {
         const long long off = (long long)win_off[k];
         const int s = win_start[k], L = win_len[k];
         VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= (ring ? T : T - s), "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s,
                   L, T);
-        const size_t need = 2 * (size_t)C * L * HW;
-        VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && need <= windows_elems - (size_t)off,
-                  "%s: window %d (offset %lld, %zu elements) leaves the buffer of %zu elements", what, k, off, need, windows_elems);
-        if (e == 8 && off % 8) e = off % 4 ? 1 : 4;
-        if (e == 4 && off % 4) e = 1;
+        size_t elems = 0;
+        if (int rc = need(k, L, elems)) return rc;
+        VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && elems <= windows_elems - (size_t)off,
+                  "%s: window %d (offset %lld, %zu elements) leaves the buffer of %zu elements", what, k, off, elems, windows_elems);
+        co_narrow(e, off);
         tab.off[k] = off;
         tab.s[k] = s;
         tab.len[k] = L;
@@ -137,18 +222,53 @@ static inline int cofuse_check(const char* what, int mode, bool writes, const vo
         }
         VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
     }
-    if (!writes) return 0;
-    const size_t wb = windows_elems * sizeof(f16);
-    VDX_CHECK(lat_out == z || !co_overlap(lat_out, nb, z, nb), "%s: lat_out overlaps z without being z", what);
-    VDX_CHECK(!co_overlap(lat_out, nb, windows, wb) && !co_overlap(lat_out, nb, wn, (size_t)K * T * sizeof(float)),
-              "%s: lat_out overlaps an input", what);
-    if (mode != 0) {
-        VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-        VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, z, nb) && !co_overlap(x0_out, nb, windows, wb) &&
-                      !co_overlap(x0_out, nb, wn, (size_t)K * T * sizeof(float)),
-                  "%s: x0_out overlaps an input or lat_out", what);
-        VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-                  "%s: x0_prev overlaps an output", what);
-    }
     return 0;
+}
+
+struct co_buf {
+    const void* p;
+    size_t bytes;
+};
+
+// What a step's outputs (nb bytes each) may share: lat_out may be z itself; otherwise no output touches z, another output, x0_prev or
+// one of `inputs`.  `x0_z` / `x0_in` end the message of an x0_out that overlaps z or lat_out / one of `inputs`.
+template <size_t N>
+static inline int cofuse_alias(const char* what, int mode, const void* z, const void* x0_prev, const void* x0_out, const void* lat_out,
+                               size_t nb, const co_buf (&inputs)[N], const char* x0_z, const char* x0_in) {
+    VDX_CHECK(lat_out == z || !co_overlap(lat_out, nb, z, nb), "%s: lat_out overlaps z without being z", what);
+    for (const co_buf& in : inputs) VDX_CHECK(!co_overlap(lat_out, nb, in.p, in.bytes), "%s: lat_out overlaps an input", what);
+    if (mode == 0) return 0;
+    VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
+    VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, z, nb), "%s: x0_out overlaps %s", what, x0_z);
+    for (const co_buf& in : inputs) VDX_CHECK(!co_overlap(x0_out, nb, in.p, in.bytes), "%s: x0_out overlaps %s", what, x0_in);
+    VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
+              "%s: x0_prev overlaps an output", what);
+    return 0;
+}
+
+// Every check of a line-per-block co-fused step, before a launch -> 0 and the table `tab` and the access width `e` (8, 4 or 1
+// halves), else the error.  mode 0: DDIM (no x0 history); otherwise DPM-Solver++.  `writes` false: a statistics pass, which reads
+// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).
+static inline int cofuse_check(const char* what, int mode, bool writes, const void* z, const void* windows, size_t windows_elems,
+                               const int64_t* win_off, const int* win_start, const int* win_len, int K, const float* wn,
+                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, cofuse_tab& tab, int& e,
+                               bool ring = false) {
+    VDX_CHECK((z || !writes) && windows && win_off && win_start && win_len && wn && (lat_out || !writes), "%s: null pointer", what);
+    VDX_CHECK(C > 0 && T > 0 && HW > 0 && HW <= 1 << 30, "%s: bad shape C=%d T=%d HW=%d", what, C, T, HW);
+    VDX_CHECK(K >= 1 && K <= COFUSE_MAX_WINDOWS, "%s: %d windows, 1..%d are supported", what, K, COFUSE_MAX_WINDOWS);
+    VDX_CHECK(mode == 0 || !writes || x0_out, "%s: x0_out is null", what);
+    const size_t n = (size_t)C * T * HW;
+    VDX_CHECK((size_t)C * T <= (size_t)1 << 30 && n <= (size_t)1 << 40, "%s: latent too large", what);
+    for (const void* ptr : {z, windows, (const void*)wn, x0_prev, (const void*)x0_out, (const void*)lat_out})
+        VDX_CHECK(((uintptr_t)ptr & 15) == 0, "%s: pointer not 16-byte aligned", what);
+    tab = cofuse_tab{};
+    e = HW % 8 == 0 ? 8 : HW % 4 == 0 ? 4 : 1;
+    const auto need = [&](int, int L, size_t& elems) {
+        elems = 2 * (size_t)C * L * HW;
+        return 0;
+    };
+    if (int rc = cofuse_windows(what, ring, windows_elems, win_off, win_start, win_len, K, T, need, tab, e)) return rc;
+    if (!writes) return 0;
+    const co_buf inputs[] = {{windows, windows_elems * sizeof(f16)}, {wn, (size_t)K * T * sizeof(float)}};
+    return cofuse_alias(what, mode, z, x0_prev, x0_out, lat_out, n * sizeof(f16), inputs, "an input or lat_out", "an input or lat_out");
 }

@@ -23,7 +23,7 @@
 
 #include "vdx_common.h"
 #include "step_chains.h"
-#include "cofuse_common.h"   // load_halves / store_halves, fuse_term, co_overlap, COFUSE_MAX_WINDOWS
+#include "cofuse_common.h"   // the vector accesses, fuse_term, the step tail and dispatch, the window-table and aliasing checks
 
 #define COTILE_MAX_TILES 64
 
@@ -86,19 +86,13 @@ __global__ __launch_bounds__(256) void cotile_kernel(const f16* z, const f16* wi
             }
         }
     }
-    const size_t i = (size_t)row * g.W + x;
-    f16 xs[E], xp[E];
-    load_halves<E>(z + i, xs);
-    if (MODE == 2) load_halves<E>(x0_prev + i, xp);
-    f16 o[E], x0[E];
+    float uf[E], cf[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        const float uf = (float)rn16(U[j]), cf = (float)rn16(Cc[j]);
-        if (MODE == 0) o[j] = cfg_ddim_elem(uf, cf, (float)xs[j], kd);
-        else dpm_elem<true, MODE == 2>(uf, cf, (float)xs[j], MODE == 2 ? (float)xp[j] : 0.f, kp, x0[j], o[j]);
+        uf[j] = (float)rn16(U[j]);
+        cf[j] = (float)rn16(Cc[j]);
     }
-    if (MODE != 0) store_halves<E>(x0_out + i, x0);
-    store_halves<E>(out + i, o);
+    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)row * g.W + x, uf, cf, cfg_guidance{}, 0.f, kd, kp);
 }
 
 // every band of `n0` inside [0, N), and every cell of [0, N) in some band
@@ -138,69 +132,30 @@ static int cotile_launch(const char* what, int mode, const void* z, const void* 
     const int ntile = ny * nx;
     VDX_CHECK(tile_stride <= (size_t)1 << 40, "%s: bad tile stride %zu", what, tile_stride);
     int e = W % 8 == 0 && tw % 8 == 0 ? 8 : W % 4 == 0 && tw % 4 == 0 ? 4 : 1;
-    const auto narrow = [&e](long long v) {                        // the widest access that still divides v
-        if (e == 8 && v % 8) e = v % 4 ? 1 : 4;
-        if (e == 4 && v % 4) e = 1;
-    };
-    for (int k = 0; k < nx; ++k) narrow(tab.x0[k]);
-    if (ntile > 1) narrow((long long)tile_stride);
-    for (int k = 0; k < Kt; ++k) {
-        const long long off = (long long)win_off[k];
-        const int s = win_start[k], L = win_len[k];
-        VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= T - s, "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s, L, T);
+    for (int k = 0; k < nx; ++k) co_narrow(e, tab.x0[k]);         // and by every window offset, below
+    if (ntile > 1) co_narrow(e, (long long)tile_stride);
+    const auto need = [&](int k, int L, size_t& elems) {
         const size_t block = 2 * (size_t)C * L * plane;           // one tile's (2,C,L,th,tw)
         VDX_CHECK(ntile == 1 || tile_stride >= block, "%s: window %d: tiles of %zu elements overlap at stride %zu", what, k, block,
                   tile_stride);
-        const size_t need = (size_t)(ntile - 1) * tile_stride + block;
-        VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && need <= windows_elems - (size_t)off,
-                  "%s: window %d (offset %lld, %zu elements) leaves the buffer of %zu elements", what, k, off, need, windows_elems);
-        narrow(off);
-        tab.off[k] = off;
-        tab.s[k] = s;
-        tab.len[k] = L;
-    }
-    for (int t = 0; t < T; ++t) {                                 // a frame nobody predicts has no noise to step with
-        bool hit = false;
-        for (int k = 0; k < Kt && !hit; ++k) hit = t >= tab.s[k] && t - tab.s[k] < tab.len[k];
-        VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
-    }
-    const size_t wb = windows_elems * sizeof(f16);
-    const struct {
-        const void* p;
-        size_t bytes;
-    } inputs[] = {{windows, wb}, {wn, (size_t)Kt * T * sizeof(float)}, {wyn, (size_t)ny * H * sizeof(float)}, {wxn, (size_t)nx * W * sizeof(float)}};
-    VDX_CHECK(lat_out == z || !co_overlap(lat_out, nb, z, nb), "%s: lat_out overlaps z without being z", what);
-    for (const auto& in : inputs) VDX_CHECK(!co_overlap(lat_out, nb, in.p, in.bytes), "%s: lat_out overlaps an input", what);
-    if (mode != 0) {
-        VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-        VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, z, nb), "%s: x0_out overlaps z or lat_out", what);
-        for (const auto& in : inputs) VDX_CHECK(!co_overlap(x0_out, nb, in.p, in.bytes), "%s: x0_out overlaps an input", what);
-        VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-                  "%s: x0_prev overlaps an output", what);
-    }
+        elems = (size_t)(ntile - 1) * tile_stride + block;
+        return 0;
+    };
+    if (int rc = cofuse_windows(what, false, windows_elems, win_off, win_start, win_len, Kt, T, need, tab, e)) return rc;
+    const co_buf inputs[] = {{windows, windows_elems * sizeof(f16)}, {wn, (size_t)Kt * T * sizeof(float)},
+                             {wyn, (size_t)ny * H * sizeof(float)}, {wxn, (size_t)nx * W * sizeof(float)}};
+    if (int rc = cofuse_alias(what, mode, z, x0_prev, x0_out, lat_out, nb, inputs, "z or lat_out", "an input")) return rc;
     const unsigned vecs = (unsigned)(W / e);                      // vectors per row
     const unsigned threads = vecs >= 256 ? 256u : (vecs + 63u) / 64u * 64u;
     const size_t segs = (vecs + threads - 1) / threads;
     const size_t blocks = segs * C * T * H;
     VDX_CHECK(blocks <= 0x7fffffffull, "%s: %zu blocks exceed the grid", what, blocks);
     const cotile_geom g = {Kt, ny, nx, th, tw, (long long)tile_stride, C, T, H, W};
-    const dim3 grid((unsigned)blocks), block(threads);
-    const hipStream_t st = (hipStream_t)stream;
-    const f16 *zz = (const f16*)z, *ww = (const f16*)windows, *pp = (const f16*)x0_prev;
-    f16 *xo = (f16*)x0_out, *oo = (f16*)lat_out;
-    const unsigned spr = (unsigned)segs;
-#define COTILE_GO(M, EE) hipLaunchKernelGGL((cotile_kernel<M, EE>), grid, block, 0, st, zz, ww, tab, g, wn, wyn, wxn, pp, xo, oo, kd, kp, spr)
-#define COTILE_E(M)                  \
-    do {                             \
-        if (e == 8) COTILE_GO(M, 8); \
-        else if (e == 4) COTILE_GO(M, 4); \
-        else COTILE_GO(M, 1);        \
-    } while (0)
-    if (mode == 0) COTILE_E(0);
-    else if (!x0_prev) COTILE_E(1);
-    else COTILE_E(2);
-#undef COTILE_E
-#undef COTILE_GO
+    step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
+        hipLaunchKernelGGL((cotile_kernel<decltype(m)::value, decltype(ee)::value>), dim3((unsigned)blocks), dim3(threads), 0,
+                           (hipStream_t)stream, (const f16*)z, (const f16*)windows, tab, g, wn, wyn, wxn, (const f16*)x0_prev,
+                           (f16*)x0_out, (f16*)lat_out, kd, kp, (unsigned)segs);
+    });
     return vdx_launch_status(what);
 }
 
@@ -243,15 +198,7 @@ __global__ __launch_bounds__(256) void cfg_input_tile_kernel(const f16* z, const
         const size_t at = (size_t)(y0 + r) * W + x0 + q;          // inside one frame of z, or of ctx
         f16 o[E];
         load_halves<E>(z + ((size_t)c * T + s + f) * H * W + at, o);
-        if (ctx) {
-            f16 cx[E];
-            load_halves<E>(ctx + (size_t)c * H * W + at, cx);
-#pragma unroll
-            for (int j = 0; j < E; ++j) {
-                const f16 t = rn16(__fmul_rn((float)cx[j], weight));   // fp16(cw * ctx)
-                o[j] = rn16(__fadd_rn((float)o[j], (float)t));         // fp16(x + t)
-            }
-        }
+        if (ctx) add_ctx<E>(o, ctx + (size_t)c * H * W + at, weight);
         const size_t d = (((size_t)c * L + f) * th + r) * tw + q;
         store_halves<E>(x2 + d, o);
         store_halves<E>(x2 + n + d, o);

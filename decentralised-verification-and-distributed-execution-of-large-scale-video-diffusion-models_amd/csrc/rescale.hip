@@ -22,7 +22,8 @@
 // The same order of additions on every run and every rank: the same bits.
 //
 // The co-fused variants take the windows' raw UNet outputs as codenoise.hip's steps do, fuse U and Cc through the same function
-// (cofuse_common.h) in both launches, and take the statistics of the fused Cc and of g(U, Cc) over the whole clip.
+// (cofuse_common.h) in both launches, and take the statistics of the fused Cc and of g(U, Cc) over the whole clip.  Their step is
+// codenoise.hip's kernel and launcher (cofuse_common.h `cofuse_step_kernel`, `cofuse_launch`) with `rescale_guidance` as its policy.
 #include <cstdint>
 
 #include "vdx_common.h"
@@ -105,6 +106,17 @@ __device__ __forceinline__ void rescale_step_elem(float u, float c, float x, flo
     if (MODE == 0) out = ddim_tail(g2, x, kd);
     else dpm_tail<MODE == 2>(g2, x, x0p, kp, x0_out, out);
 }
+
+// the guidance policy of the co-fused step (cofuse_common.h `cofuse_step_kernel`): the block's r, then g' in g's place
+struct rescale_guidance {
+    rescale_args ra;
+    __device__ __forceinline__ float prologue() const { return rescale_ratio(ra); }
+    template <int MODE>
+    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, float r, const ddim_coef& kd, const dpm_coef& kp, f16& x0,
+                                         f16& o) const {
+        rescale_step_elem<MODE>(u, c, x, x0p, r, ra, kd, kp, x0, o);
+    }
+};
 
 // ---- one sample in one buffer: eps2 = [u; c], n elements each, E halves per access (n is a multiple of E) ---------------------
 template <int E>
@@ -209,19 +221,9 @@ static int rescale_step_launch(const char* what, int mode, const void* eps2, con
     const rescale_args ra = {partials, (f16*)stats_out, rows, (double)n, phi, phi1};
     const f16 *ep = (const f16*)eps2, *x = (const f16*)lat, *p = (const f16*)x0_prev;
     f16 *z = (f16*)x0_out, *o = (f16*)lat_out;
-    const int m = mode == 0 ? 0 : x0_prev ? 2 : 1;
-#define RESCALE_GO(M, EE) hipLaunchKernelGGL((rescale_step_kernel<M, EE>), grid, block, 0, s, ep, x, p, z, o, kd, kp, ra, n)
-#define RESCALE_E(M)                   \
-    do {                               \
-        if (e == 8) RESCALE_GO(M, 8);  \
-        else if (e == 4) RESCALE_GO(M, 4); \
-        else RESCALE_GO(M, 1);         \
-    } while (0)
-    if (m == 0) RESCALE_E(0);
-    else if (m == 1) RESCALE_E(1);
-    else RESCALE_E(2);
-#undef RESCALE_E
-#undef RESCALE_GO
+    step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
+        hipLaunchKernelGGL((rescale_step_kernel<decltype(m)::value, decltype(ee)::value>), grid, block, 0, s, ep, x, p, z, o, kd, kp, ra, n);
+    });
     return vdx_launch_status(what);
 }
 
@@ -260,29 +262,6 @@ __global__ __launch_bounds__(256) void cofuse_stats_kernel(const f16* win, cofus
         }
     }
     block_row(a, partials + (size_t)blockIdx.x * 4);
-}
-
-// codenoise.hip's block map: one (c, t) line tile per block
-template <int MODE, int E>
-__global__ __launch_bounds__(256) void cofuse_rescale_kernel(const f16* z, const f16* win, cofuse_tab tab, int K, const float* wn,
-                                                             const f16* x0_prev, f16* x0_out, f16* out, ddim_coef kd, dpm_coef kp,
-                                                             rescale_args ra, int C, int T, int HW, unsigned tiles_per_line) {
-    const float r = rescale_ratio(ra);
-    const unsigned line = blockIdx.x / tiles_per_line, tile = blockIdx.x - line * tiles_per_line;
-    const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
-    const int p = (int)((tile * 256u + threadIdx.x) * (unsigned)E);
-    if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
-    float uf[E], cf[E];
-    cofuse_uc<E>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);
-    const size_t i = (size_t)line * HW + p;
-    f16 x[E], xp[E], o[E], x0[E];
-    load_halves<E>(z + i, x);
-    if (MODE == 2) load_halves<E>(x0_prev + i, xp);
-#pragma unroll
-    for (int j = 0; j < E; ++j)
-        rescale_step_elem<MODE>(uf[j], cf[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, r, ra, kd, kp, x0[j], o[j]);
-    if (MODE != 0) store_halves<E>(x0_out + i, x0);
-    store_halves<E>(out + i, o);
 }
 
 static inline int cofuse_rescale_rows(int C, int T) {
@@ -339,31 +318,9 @@ static int cofuse_rescale_launch(const char* what, int mode, const void* z, cons
                       !co_overlap(stats_out, sb, wn, (size_t)K * T * sizeof(float)) && !co_overlap(stats_out, sb, partials, pb) &&
                       (!x0_prev || !co_overlap(stats_out, sb, x0_prev, nb)) && (!x0_out || !co_overlap(stats_out, sb, x0_out, nb)),
                   "%s: stats_out overlaps another buffer", what);
-    const size_t per_tile = 256 * (size_t)e;
-    const size_t tiles_per_line = ((size_t)HW + per_tile - 1) / per_tile;
-    const size_t blocks = tiles_per_line * C * T;
-    VDX_CHECK(blocks <= 0x7fffffffull, "%s: %zu blocks exceed the grid", what, blocks);
-    const dim3 grid((unsigned)blocks), block(256);
-    const hipStream_t st = (hipStream_t)stream;
     const rescale_args ra = {partials, (f16*)stats_out, rows, (double)((size_t)C * T * HW), phi, phi1};
-    const f16 *zz = (const f16*)z, *ww = (const f16*)windows, *pp = (const f16*)x0_prev;
-    f16 *xo = (f16*)x0_out, *oo = (f16*)lat_out;
-    const unsigned tpl = (unsigned)tiles_per_line;
-    const int m = mode == 0 ? 0 : x0_prev ? 2 : 1;
-#define CORESCALE_GO(M, EE) \
-    hipLaunchKernelGGL((cofuse_rescale_kernel<M, EE>), grid, block, 0, st, zz, ww, tab, K, wn, pp, xo, oo, kd, kp, ra, C, T, HW, tpl)
-#define CORESCALE_E(M)                   \
-    do {                                 \
-        if (e == 8) CORESCALE_GO(M, 8);  \
-        else if (e == 4) CORESCALE_GO(M, 4); \
-        else CORESCALE_GO(M, 1);         \
-    } while (0)
-    if (m == 0) CORESCALE_E(0);
-    else if (m == 1) CORESCALE_E(1);
-    else CORESCALE_E(2);
-#undef CORESCALE_E
-#undef CORESCALE_GO
-    return vdx_launch_status(what);
+    return cofuse_launch<false>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp, rescale_guidance{ra}, C, T, HW,
+                                stream);
 }
 
 extern "C" int vdx_cofuse_cfg_rescale_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,

@@ -890,6 +890,22 @@ def blend_finalize(full, weight):
 
 # --------------------------------------------------------------------------------------------
 # Temporal co-denoising (vdx/codenoise.py, csrc/codenoise.hip; no reference counterpart)
+def _cfg_input_of(what, symbol, z, ctx, weight, out, shape, named, tail):
+    """What `cfg_input_window`, `cfg_input_loop` and `cfg_input_tile` share once z and their own range are checked (z first: the
+    range is read against its shape): the checks of ctx and of out (`shape`, which the error calls `named`), the launch of
+    `symbol`(z, ctx, weight, out, C, T, *tail) and the duplicate tag.  ONE call per launch: these ops are launch-bound."""
+    _, Cc, T, H, W = z.shape
+    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
+        raise VdxError(f"{what}: ctx must be contiguous (1,C,1,H,W)")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=z.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise VdxError(f"{what}: out must be contiguous {named}")
+    _launch(symbol, _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, *tail)
+    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
+    return out
+
+
 def cfg_input_window(z, ctx, weight, s: int, e: int, out=None):
     """`cfg_input(z[:, :, s:e], ctx, weight)` without the slice copy: one launch reads frames [s, e) out of the whole clip's
     latent z (1,C,T,H,W) and writes the contiguous (2,C,e-s,H,W) UNet input, TAGGED as a CFG duplicate exactly as `cfg_input`
@@ -900,15 +916,8 @@ def cfg_input_window(z, ctx, weight, s: int, e: int, out=None):
     s, e = int(s), int(e)
     if not 0 <= s < e <= T:
         raise VdxError(f"cfg_input_window: bad range [{s},{e}) of {T} frames")
-    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
-        raise VdxError("cfg_input_window: ctx must be contiguous (1,C,1,H,W)")
-    if out is None:
-        out = torch.empty((2, Cc, e - s, H, W), dtype=torch.float16, device=z.device)
-    elif tuple(out.shape) != (2, Cc, e - s, H, W) or not out.is_contiguous():
-        raise VdxError("cfg_input_window: out must be contiguous (2,C,e-s,H,W)")
-    _launch("vdx_cfg_input_window_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H * W, s, e)
-    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
-    return out
+    return _cfg_input_of("cfg_input_window", "vdx_cfg_input_window_f16", z, ctx, weight, out, (2, Cc, e - s, H, W), "(2,C,e-s,H,W)",
+                         (H * W, s, e))
 
 
 COFUSE_MAX_WINDOWS = 64
@@ -933,32 +942,54 @@ def _cofuse_args(what, z, windows, table, wn):
     return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
 
 
+def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None):
+    """The DDIM form of every whole-clip fused step, launched as `symbol`(head, out, extras, tail) and named in errors as the
+    wrapper, `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head, else `_cotile_args`'; `rescaled`: the
+    rescale variants' ((phi, 1 - phi), partials, stats_out).  One call below the public wrapper and no closure: launch-bound."""
+    what = symbol[4:-4]
+    head, tail = _cofuse_args(what, z, windows, table, wn) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
+    if out is None:
+        out = torch.empty_like(z)
+    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+        raise VdxError(f"{what}: out must be contiguous and shaped like z")
+    bufs = phis = ()
+    if rescaled is not None:
+        _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
+        bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch(symbol, *head, _p(out, "out"), *bufs, float(guidance), *phis, s1, sa, sp, s1p, *tail)
+    return out
+
+
+def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None):
+    """The DPM-Solver++ form of the same, through `_dpm_args` -> (z', x0)."""
+    what = symbol[4:-4]
+    head, tail = _cofuse_args(what, z, windows, table, wn) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
+    x0_out, out, c = _dpm_args(what, z, x0_prev, x0_out, out, coeffs)
+    bufs = phis = ()
+    if rescaled is not None:
+        _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
+        bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
+    _launch(symbol, *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), *bufs, float(guidance), *phis,
+            *c, *tail)
+    return out, x0_out
+
+
 def cofuse_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
     """One co-denoising DDIM step of the whole clip (include/vdx.h `vdx_cofuse_cfg_ddim_step_f16`): the windows' raw UNet
     outputs, each a contiguous (2,C,L_k,H,W) block at its `table` offset inside `windows`, are averaged per frame with `wn`
     and fed to `cfg_ddim_step`'s chain.  coeffs as for `cfg_ddim_step`; `out` may be `z`."""
-    head, tail = _cofuse_args("cofuse_cfg_ddim_step", z, windows, table, wn)
-    if out is None:
-        out = torch.empty_like(z)
-    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
-        raise VdxError("cofuse_cfg_ddim_step: out must be contiguous and shaped like z")
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cofuse_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
-    return out
+    return _co_ddim_step("vdx_cofuse_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out)
 
 
 def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cofuse_cfg_dpm_step_f16`) -> (z', x0), both of the whole
     clip's shape.  coeffs, `x0_prev`, `x0_out` and `out` as for `cfg_dpm_step`."""
-    head, tail = _cofuse_args("cofuse_cfg_dpm_step", z, windows, table, wn)
-    x0_out, out, c = _dpm_args("cofuse_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
-    _launch("vdx_cofuse_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
-            *c, *tail)
-    return out, x0_out
+    return _co_dpm_step("vdx_cofuse_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out)
 
 
 # --------------------------------------------------------------------------------------------
-# Seamless looping: ring windows (vdx/codenoise.py `loop_plan`, csrc/coloop.hip; no reference counterpart)
+# Seamless looping: ring windows (vdx/codenoise.py `loop_plan`, csrc/codenoise.hip's RING flag; no reference counterpart)
 def cfg_input_loop(z, ctx, weight, s: int, L: int, out=None):
     """`cfg_input_window` on a ring: one launch reads the frames `(s + f) mod T`, f in [0, L), out of the whole clip's latent z
     (1,C,T,H,W), `0 <= s < T`, `1 <= L <= T`, and writes the contiguous (2,C,L,H,W) UNet input, TAGGED as a CFG duplicate
@@ -969,37 +1000,18 @@ def cfg_input_loop(z, ctx, weight, s: int, L: int, out=None):
     s, L = int(s), int(L)
     if L < 1:
         raise VdxError(f"cfg_input_loop: bad ring window start {s}, length {L} of {T} frames")
-    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
-        raise VdxError("cfg_input_loop: ctx must be contiguous (1,C,1,H,W)")
-    if out is None:
-        out = torch.empty((2, Cc, L, H, W), dtype=torch.float16, device=z.device)
-    elif tuple(out.shape) != (2, Cc, L, H, W) or not out.is_contiguous():
-        raise VdxError("cfg_input_loop: out must be contiguous (2,C,L,H,W)")
-    _launch("vdx_cfg_input_loop_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H * W, s, L)
-    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
-    return out
+    return _cfg_input_of("cfg_input_loop", "vdx_cfg_input_loop_f16", z, ctx, weight, out, (2, Cc, L, H, W), "(2,C,L,H,W)", (H * W, s, L))
 
 
 def coloop_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
     """`cofuse_cfg_ddim_step` over ring windows (include/vdx.h `vdx_coloop_cfg_ddim_step_f16`): a `table` row (offset, s, L)
     means the frames `(s + f) mod T`; the fuse, the chain, `coeffs` and `out` (which may be `z`) are the same."""
-    head, tail = _cofuse_args("coloop_cfg_ddim_step", z, windows, table, wn)
-    if out is None:
-        out = torch.empty_like(z)
-    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
-        raise VdxError("coloop_cfg_ddim_step: out must be contiguous and shaped like z")
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_coloop_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
-    return out
+    return _co_ddim_step("vdx_coloop_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out)
 
 
 def coloop_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """`cofuse_cfg_dpm_step` over ring windows (`vdx_coloop_cfg_dpm_step_f16`) -> (z', x0)."""
-    head, tail = _cofuse_args("coloop_cfg_dpm_step", z, windows, table, wn)
-    x0_out, out, c = _dpm_args("coloop_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
-    _launch("vdx_coloop_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
-            *c, *tail)
-    return out, x0_out
+    return _co_dpm_step("vdx_coloop_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1032,15 +1044,8 @@ def cfg_input_tile(z, ctx, weight, s: int, e: int, y0: int, th: int, x0: int, tw
         raise VdxError(f"cfg_input_tile: bad range [{s},{e}) of {T} frames")
     if not (1 <= th <= H and 0 <= y0 <= H - th and 1 <= tw <= W and 0 <= x0 <= W - tw):
         raise VdxError(f"cfg_input_tile: tile [{y0},{y0}+{th}) x [{x0},{x0}+{tw}) leaves the {H}x{W} frame")
-    if ctx is not None and (tuple(ctx.shape) != (1, Cc, 1, H, W) or not ctx.is_contiguous()):
-        raise VdxError("cfg_input_tile: ctx must be contiguous (1,C,1,H,W)")
-    if out is None:
-        out = torch.empty((2, Cc, e - s, th, tw), dtype=torch.float16, device=z.device)
-    elif tuple(out.shape) != (2, Cc, e - s, th, tw) or not out.is_contiguous():
-        raise VdxError("cfg_input_tile: out must be contiguous (2,C,e-s,th,tw)")
-    _launch("vdx_cfg_input_tile_f16", _p(z, "z"), _p(ctx, "ctx"), float(weight), _p(out, "out"), Cc, T, H, W, s, e, y0, th, x0, tw)
-    out._vdx_cfg_dup = out._version        # both batch items hold the same values until somebody writes the tensor
-    return out
+    return _cfg_input_of("cfg_input_tile", "vdx_cfg_input_tile_f16", z, ctx, weight, out, (2, Cc, e - s, th, tw), "(2,C,e-s,th,tw)",
+                         (H, W, s, e, y0, th, x0, tw))
 
 
 def _cotile_args(what, z, windows, table, wn, tiles: TileGrid):
@@ -1067,23 +1072,12 @@ def cotile_cfg_ddim_step(z, windows, table, wn, tiles: TileGrid, guidance, coeff
     `cofuse_cfg_ddim_step`, each time window's block now holding the `len(ys) * len(xs)` tiles' (2,C,L_k,th,tw) outputs at
     `tiles.stride` from one another; the noise is averaged per cell with `wn[kt][t] * wyn[ky][y] * wxn[kx][x]` and fed to
     `cfg_ddim_step`'s chain.  `out` may be `z`."""
-    head, tail = _cotile_args("cotile_cfg_ddim_step", z, windows, table, wn, tiles)
-    if out is None:
-        out = torch.empty_like(z)
-    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
-        raise VdxError("cotile_cfg_ddim_step: out must be contiguous and shaped like z")
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cotile_cfg_ddim_step_f16", *head, _p(out, "out"), float(guidance), s1, sa, sp, s1p, *tail)
-    return out
+    return _co_ddim_step("vdx_cotile_cfg_ddim_step_f16", z, windows, table, wn, tiles, guidance, coeffs, out)
 
 
 def cotile_cfg_dpm_step(z, windows, table, wn, tiles: TileGrid, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cotile_cfg_dpm_step_f16`) -> (z', x0)."""
-    head, tail = _cotile_args("cotile_cfg_dpm_step", z, windows, table, wn, tiles)
-    x0_out, out, c = _dpm_args("cotile_cfg_dpm_step", z, x0_prev, x0_out, out, coeffs)
-    _launch("vdx_cotile_cfg_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), float(guidance),
-            *c, *tail)
-    return out, x0_out
+    return _co_dpm_step("vdx_cotile_cfg_dpm_step_f16", z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1183,28 +1177,15 @@ def cofuse_cfg_rescale_stats(z, windows, table, wn, guidance, partials=None):
 
 def cofuse_cfg_rescale_ddim_step(z, windows, table, wn, guidance, rescale, coeffs, partials, out=None, stats_out=None):
     """`cofuse_cfg_ddim_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_ddim_step_f16`)."""
-    head, tail = _cofuse_args("cofuse_cfg_rescale_ddim_step", z, windows, table, wn)
-    if out is None:
-        out = torch.empty_like(z)
-    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
-        raise VdxError("cofuse_cfg_rescale_ddim_step: out must be contiguous and shaped like z")
-    _, pp, sp_ = _rescale_buffers("cofuse_cfg_rescale_ddim_step", cofuse_cfg_rescale_rows(tail[0], tail[1]), z, partials, stats_out)
-    phi, phi1 = (float(v) for v in rescale)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cofuse_cfg_rescale_ddim_step_f16", *head, _p(out, "out"), pp, sp_, float(guidance), phi, phi1, s1, sa, sp, s1p, *tail)
-    return out
+    return _co_ddim_step("vdx_cofuse_cfg_rescale_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out,
+                         (rescale, partials, stats_out))
 
 
 def cofuse_cfg_rescale_dpm_step(z, windows, table, wn, guidance, rescale, coeffs, partials, x0_prev=None, x0_out=None, out=None,
                                 stats_out=None):
     """`cofuse_cfg_dpm_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_dpm_step_f16`) -> (z', x0)."""
-    head, tail = _cofuse_args("cofuse_cfg_rescale_dpm_step", z, windows, table, wn)
-    x0_out, out, c = _dpm_args("cofuse_cfg_rescale_dpm_step", z, x0_prev, x0_out, out, coeffs)
-    _, pp, sp_ = _rescale_buffers("cofuse_cfg_rescale_dpm_step", cofuse_cfg_rescale_rows(tail[0], tail[1]), z, partials, stats_out)
-    phi, phi1 = (float(v) for v in rescale)
-    _launch("vdx_cofuse_cfg_rescale_dpm_step_f16", *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), pp, sp_,
-            float(guidance), phi, phi1, *c, *tail)
-    return out, x0_out
+    return _co_dpm_step("vdx_cofuse_cfg_rescale_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
+                        (rescale, partials, stats_out))
 
 
 # --------------------------------------------------------------------------------------------

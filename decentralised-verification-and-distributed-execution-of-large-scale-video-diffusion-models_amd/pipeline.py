@@ -107,7 +107,7 @@ class DiffuserConfig:
     # All four are multiples of 8.  None = the UNet runs on the whole frame, as always
     tile: Optional[Tuple[int, int]] = None
     tile_overlap: Optional[Tuple[int, int]] = None
-    # seamless looping (vdx/codenoise.py `loop_plan`, csrc/coloop.hip; AnimateDiff's `closed_loop` context option, unpinned; needs
+    # seamless looping (vdx/codenoise.py `loop_plan`, csrc/codenoise.hip, its RING flag; AnimateDiff's `closed_loop` context option, unpinned; needs
     # `co_denoise`): the windows lie on a ring, the last wrapping over the clip's end into its first frames, so frames T-1 and 0
     # are denoised together at every step.  False = the windows stop at the clip's end, as always
     loop: bool = False
@@ -664,7 +664,7 @@ def build_arg_parser():
     the flag every launch, byte, CSV row and record is the one it always was.
     `--loop` (with `--co_denoise`; no reference counterpart; AnimateDiff's `closed_loop` context option, unpinned) makes the clip a
     seamless loop: the windows lie on a ring, the last wrapping over the clip's end into its first frames (vdx/codenoise.py
-    `loop_plan`, csrc/coloop.hip), so frames T-1 and 0 are denoised together in one UNet call at every step; `--interpolate N`
+    `loop_plan`, csrc/codenoise.hip, its RING flag), so frames T-1 and 0 are denoised together in one UNet call at every step; `--interpolate N`
     then also fills the pair (T-1, 0) and writes T N frames; refused without `--co_denoise`, with `--exchange halo`, `--tile`,
     `--guidance_rescale`, `--mode fsdp` and a chunk as long as the clip; the result and the JSON records carry `"loop"`:
     {"windows", "wrap_l1", "mean_l1"}; without the flag every launch, byte, CSV row and record is the one it always was."""

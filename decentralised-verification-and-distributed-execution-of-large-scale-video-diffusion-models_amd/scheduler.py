@@ -64,6 +64,60 @@ class _SchedulerBase:
             st = self.rescale_stats = torch.zeros(8, dtype=torch.float16, device=device)
         return ops.rescale_factors(guidance_rescale), st
 
+    _dpm = None         # False / True: which of an `ops` step's two forms, (DDIM, DPM-Solver++), this scheduler launches
+
+    def _begin(self, timestep, sample):
+        """The one hook of the `step_cfg*` methods -> (this step's coefficients, the `ops` step's history keywords, what to call
+        once the kernel was enqueued).  It changes nothing that a launch which raises would have to undo."""
+        raise NotImplementedError
+
+    def _fused_step(self, steps, head, timestep, sample, guidance_scale, guidance_rescale=0.0, rescaled=None):
+        """`steps[self._dpm](*head, ...)`, `steps` = the (DDIM, DPM-Solver++) pair of an `ops` step.  With `guidance_rescale` != 0
+        `rescaled` = (the statistics op, its leading arguments, the pair of rescaled steps): two launches and no host read."""
+        coeffs, history, commit = self._begin(timestep, sample)
+        if guidance_rescale == 0.0:
+            res = steps[self._dpm](*head, guidance_scale, coeffs, **history)
+        else:
+            stats_op, stats_head, steps = rescaled
+            rescale, stats = self._rescale(guidance_rescale, sample.device)
+            part = stats_op(*stats_head, guidance_scale)
+            res = steps[self._dpm](*head, guidance_scale, rescale, coeffs, part, stats_out=stats, **history)
+        commit()
+        return res[0] if self._dpm else res                       # the DPM-Solver++ ops return (the new latent, x0)
+
+    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+        """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel (`vdx_cfg_ddim_step_f16` /
+        `vdx_cfg_dpm_step_f16`).  `guidance_rescale` != 0 (Lin et al. 2023, diffusers' `rescale_noise_cfg`; csrc/rescale.hip): the
+        guided noise is rescaled towards the standard deviation of the conditional one over this sample, in two launches (the
+        statistics, then the step) and without a host read."""
+        if self._dpm or guidance_rescale != 0.0:                  # the plain DDIM op refuses a non-contiguous sample itself
+            sample = sample.contiguous()
+        return self._fused_step((ops.cfg_ddim_step, ops.cfg_dpm_step), (noise2, sample), timestep, sample, guidance_scale,
+                                guidance_rescale, (ops.cfg_rescale_stats, (noise2,), (ops.cfg_rescale_ddim_step, ops.cfg_rescale_dpm_step)))
+
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+        """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent `sample` on the noise fused from the
+        windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step` / `ops.cofuse_cfg_dpm_step`), one
+        kernel; with `guidance_rescale` != 0 two, the statistics being those of the fused noise over the whole clip."""
+        head = (sample.contiguous(), windows, table, wn)
+        return self._fused_step((ops.cofuse_cfg_ddim_step, ops.cofuse_cfg_dpm_step), head, timestep, head[0], guidance_scale,
+                                guidance_rescale, (ops.cofuse_cfg_rescale_stats, head,
+                                                   (ops.cofuse_cfg_rescale_ddim_step, ops.cofuse_cfg_rescale_dpm_step)))
+
+    def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
+        """Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`): `step_cfg_windows` with every time window's block holding
+        its row x column tiles' outputs (`tiles`: an `ops.TileGrid`; `ops.cotile_cfg_ddim_step` / `ops.cotile_cfg_dpm_step`), one
+        kernel.  There is no `guidance_rescale` form: its statistics pass has no tiled fuse."""
+        head = (sample.contiguous(), windows, table, wn, tiles)
+        return self._fused_step((ops.cotile_cfg_ddim_step, ops.cotile_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+
+    def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Seamless looping (vdx/codenoise.py `loop_plan`): `step_cfg_windows` with every window on a ring, a `table` row
+        (offset, s, L) meaning the frames (s + f) mod T (`ops.coloop_cfg_ddim_step` / `ops.coloop_cfg_dpm_step`), one kernel.
+        No `guidance_rescale` form."""
+        head = (sample.contiguous(), windows, table, wn)
+        return self._fused_step((ops.coloop_cfg_ddim_step, ops.coloop_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+
     def add_noise(self, original_samples, noise, timesteps):
         """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
         then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers
@@ -128,42 +182,10 @@ class DDIMScheduler(_SchedulerBase):
                              self.coefficients(self._host_timestep(timestep)))
         return SimpleNamespace(prev_sample=prev)
 
-    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
-        """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel.  `guidance_rescale` != 0 (Lin et al.
-        2023, diffusers' `rescale_noise_cfg`; csrc/rescale.hip): the guided noise is rescaled towards the standard deviation of
-        the conditional one over this sample, in two launches (the statistics, then the step) and without a host read."""
-        coeffs = self.coefficients(self._host_timestep(timestep))
-        if guidance_rescale == 0.0:
-            return ops.cfg_ddim_step(noise2, sample, guidance_scale, coeffs)
-        rescale, stats = self._rescale(guidance_rescale, sample.device)
-        sample = sample.contiguous()
-        part = ops.cfg_rescale_stats(noise2, guidance_scale)
-        return ops.cfg_rescale_ddim_step(noise2, sample, guidance_scale, rescale, coeffs, part, stats_out=stats)
+    _dpm = False
 
-    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
-        """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent `sample` on the noise fused from the
-        windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step`), one kernel; with
-        `guidance_rescale` != 0 two, the statistics being those of the fused noise over the whole clip."""
-        coeffs = self.coefficients(self._host_timestep(timestep))
-        sample = sample.contiguous()
-        if guidance_rescale == 0.0:
-            return ops.cofuse_cfg_ddim_step(sample, windows, table, wn, guidance_scale, coeffs)
-        rescale, stats = self._rescale(guidance_rescale, sample.device)
-        part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
-        return ops.cofuse_cfg_rescale_ddim_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, stats_out=stats)
-
-    def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
-        """Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`): `step_cfg_windows` with every time window's block holding
-        its row x column tiles' outputs (`tiles`: an `ops.TileGrid`; `ops.cotile_cfg_ddim_step`), one kernel.  There is no
-        `guidance_rescale` form: its statistics pass has no tiled fuse."""
-        coeffs = self.coefficients(self._host_timestep(timestep))
-        return ops.cotile_cfg_ddim_step(sample.contiguous(), windows, table, wn, tiles, guidance_scale, coeffs)
-
-    def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
-        """Seamless looping (vdx/codenoise.py `loop_plan`): `step_cfg_windows` with every window on a ring, a `table` row
-        (offset, s, L) meaning the frames (s + f) mod T (`ops.coloop_cfg_ddim_step`), one kernel.  No `guidance_rescale` form."""
-        coeffs = self.coefficients(self._host_timestep(timestep))
-        return ops.coloop_cfg_ddim_step(sample.contiguous(), windows, table, wn, guidance_scale, coeffs)
+    def _begin(self, timestep, sample):
+        return self.coefficients(self._host_timestep(timestep)), {}, lambda: None
 
 
 class DPMSolverMultistepScheduler(_SchedulerBase):
@@ -316,55 +338,10 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self._commit(i)
         return SimpleNamespace(prev_sample=new)
 
-    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
-        """Fused `u + gs*(c-u)` + step in one kernel (`vdx_cfg_dpm_step_f16`); with `guidance_rescale` != 0 the statistics
-        pass and `vdx_cfg_rescale_dpm_step_f16` (as `DDIMScheduler.step_cfg`)."""
-        sample = sample.contiguous()
-        i, prev, x0_out = self._plan(timestep, sample)
-        coeffs = self.coefficients(i, prev is not None)
-        if guidance_rescale == 0.0:
-            new, _ = ops.cfg_dpm_step(noise2, sample, guidance_scale, coeffs, x0_prev=prev, x0_out=x0_out)
-        else:
-            rescale, stats = self._rescale(guidance_rescale, sample.device)
-            part = ops.cfg_rescale_stats(noise2, guidance_scale)
-            new, _ = ops.cfg_rescale_dpm_step(noise2, sample, guidance_scale, rescale, coeffs, part, x0_prev=prev, x0_out=x0_out,
-                                              stats_out=stats)
-        self._commit(i)
-        return new
+    _dpm = True
 
-    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
-        """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent on the noise fused from the windows' raw
-        UNet outputs (`vdx_cofuse_cfg_dpm_step_f16`), one kernel.  ONE x0 history of the whole clip's shape, planned and
-        committed as for `step_cfg`; `reset()` once per round.  `guidance_rescale` as for `DDIMScheduler.step_cfg_windows`."""
-        sample = sample.contiguous()
+    def _begin(self, timestep, sample):
+        """ONE x0 history of the sample's shape (with co-denoising the whole clip's; `reset()` once per round), planned here and
+        committed by the returned callable after the kernel was enqueued."""
         i, prev, x0_out = self._plan(timestep, sample)
-        coeffs = self.coefficients(i, prev is not None)
-        if guidance_rescale == 0.0:
-            new, _ = ops.cofuse_cfg_dpm_step(sample, windows, table, wn, guidance_scale, coeffs, x0_prev=prev, x0_out=x0_out)
-        else:
-            rescale, stats = self._rescale(guidance_rescale, sample.device)
-            part = ops.cofuse_cfg_rescale_stats(sample, windows, table, wn, guidance_scale)
-            new, _ = ops.cofuse_cfg_rescale_dpm_step(sample, windows, table, wn, guidance_scale, rescale, coeffs, part, x0_prev=prev,
-                                                     x0_out=x0_out, stats_out=stats)
-        self._commit(i)
-        return new
-
-    def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
-        """Spatially tiled co-denoising: `step_cfg_windows` over time x row x column windows (`vdx_cotile_cfg_dpm_step_f16`), one
-        kernel and ONE x0 history of the whole clip's shape, as there.  No `guidance_rescale` form."""
-        sample = sample.contiguous()
-        i, prev, x0_out = self._plan(timestep, sample)
-        new, _ = ops.cotile_cfg_dpm_step(sample, windows, table, wn, tiles, guidance_scale, self.coefficients(i, prev is not None),
-                                         x0_prev=prev, x0_out=x0_out)
-        self._commit(i)
-        return new
-
-    def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
-        """Seamless looping: `step_cfg_windows` over ring windows (`vdx_coloop_cfg_dpm_step_f16`), one kernel and ONE x0 history of
-        the whole clip's shape, as there.  No `guidance_rescale` form."""
-        sample = sample.contiguous()
-        i, prev, x0_out = self._plan(timestep, sample)
-        new, _ = ops.coloop_cfg_dpm_step(sample, windows, table, wn, guidance_scale, self.coefficients(i, prev is not None),
-                                         x0_prev=prev, x0_out=x0_out)
-        self._commit(i)
-        return new
+        return self.coefficients(i, prev is not None), {"x0_prev": prev, "x0_out": x0_out}, lambda: self._commit(i)

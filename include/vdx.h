@@ -389,7 +389,7 @@ int vdx_cotile_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 int tw, const void* x0_prev, void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0,
                                 float c_x, float c_d0, float c_d1, float c_inv_r0, int C, int T, int H, int W, vdx_stream_t stream);
 /* Seamless looping for co-denoising: ring windows (AnimateDiff's `closed_loop` context option; MultiDiffusion along time with
- * periodic windows; no reference counterpart, opt-in: vdx/codenoise.py `loop_plan`, `DiffuserConfig.loop`, csrc/coloop.hip, restated
+ * periodic windows; no reference counterpart, opt-in: vdx/codenoise.py `loop_plan`, `DiffuserConfig.loop`, csrc/codenoise.hip, its RING flag, restated
  * in tests/coloop_ref.py).  A window (s, L) holds the frames (s + f) mod T, f in [0, L), with 0 <= s < T and 1 <= L <= T.
  * vdx_cfg_input_loop_f16: `vdx_cfg_input_window_f16` under that rule (note: a LENGTH, not an end): x2 (2,C,L,h,w) contiguous, one
  * launch, the ctx term with the same two fp16 roundings; 16-byte accesses where HW % 8 == 0, else element-wise; x2 must not overlap

@@ -1,4 +1,4 @@
-"""Torch-CPU restatement of the ring-window kernels (csrc/coloop.hip): the yardstick of tests/test_coloop_host.py and
+"""Torch-CPU restatement of the ring-window kernels (csrc/codenoise.hip, its RING flag): the yardstick of tests/test_coloop_host.py and
 tests/test_coloop_gpu.py.  It does not import the product's kernels.
 
 A window (s, L) holds the frames (s + arange(L)) % T of the clip.  Per element (c, t, p), over the windows k = 0..K-1 IN

@@ -1,4 +1,4 @@
-"""-m gpu: seamless looping, ring windows for co-denoising (csrc/coloop.hip, vdx/codenoise.py `loop_plan`).  Everything bit for
+"""-m gpu: seamless looping, ring windows for co-denoising (csrc/codenoise.hip, its RING flag, vdx/codenoise.py `loop_plan`).  Everything bit for
 bit: the kernels against the torch-CPU restatement of tests/coloop_ref.py (every operation a correctly rounded fp32 operation in
 a stated order, so equality is derived, not measured), a table without a wrap against the `cofuse` steps, one window against the
 plain fused steps on the rolled noise, the wrap itself by rotation equivariance, and the looping job on the tiny golden UNet

@@ -229,3 +229,70 @@ def test_front_end_flag_and_config():
     assert make_scheduler("ddim", d) is d and isinstance(make_scheduler("dpmpp_2m", d), DPMSolverMultistepScheduler)
     with pytest.raises(ValueError):
         make_scheduler("euler", d)
+
+
+STEP_CFG = ("step_cfg", "step_cfg_windows", "step_cfg_tiles", "step_cfg_loop")
+
+
+def _fused_calls(s, x):
+    """One call of each `step_cfg*` method on the sample `x` at the scheduler's next timestep -> nothing; the arguments beside the
+    sample are tokens that only the recording stubs see."""
+    return {"step_cfg": lambda t: s.step_cfg("noise2", t, x, 7.5),
+            "step_cfg_windows": lambda t: s.step_cfg_windows("windows", "table", "wn", t, x, 7.5),
+            "step_cfg_tiles": lambda t: s.step_cfg_tiles("windows", "table", "wn", "tiles", t, x, 7.5),
+            "step_cfg_loop": lambda t: s.step_cfg_loop("windows", "table", "wn", t, x, 7.5)}
+
+
+def test_step_cfg_methods_are_defined_once_and_a_failed_launch_changes_nothing(monkeypatch):
+    """The four `step_cfg*` names are ONE function object each on both schedulers (`_SchedulerBase`'s); with `ops` replaced by
+    recording stubs nothing launches: each scheduler reaches its own sampler's op with its coefficients, the DPM-Solver++ history
+    ping-pongs, and a launch that raises leaves `_step_index`, `_cur` and `_have_prev` where they were."""
+    import vdx  # noqa: F401
+    from vdx import scheduler as S
+    for name in STEP_CFG:
+        assert getattr(S.DDIMScheduler, name) is getattr(S.DPMSolverMultistepScheduler, name) is getattr(S._SchedulerBase, name)
+        assert name not in vars(S.DDIMScheduler) and name not in vars(S.DPMSolverMultistepScheduler)
+    calls, fail = [], []
+
+    class Stubs:
+        def __getattr__(self, op):
+            def stub(*args, **kw):
+                calls.append((op, args, kw))
+                if fail:
+                    raise RuntimeError("launch failed")
+                return ("new", kw["x0_out"]) if op.endswith("_dpm_step") else "new"
+            return stub
+    monkeypatch.setattr(S, "ops", Stubs())
+    x = torch.zeros(1, 2, 3, 1, 4)
+    heads = {"step_cfg": ("cfg", ("noise2", x)), "step_cfg_windows": ("cofuse_cfg", (x, "windows", "table", "wn")),
+             "step_cfg_tiles": ("cotile_cfg", (x, "windows", "table", "wn", "tiles")),
+             "step_cfg_loop": ("coloop_cfg", (x, "windows", "table", "wn"))}
+    d = S.DDIMScheduler()
+    d.set_timesteps(4)
+    for name, call in _fused_calls(d, x).items():
+        calls.clear()
+        t = d._host_timesteps[1]
+        assert call(t) == "new"
+        stem, head = heads[name]
+        (op, args, kw), = calls
+        assert op == f"{stem}_ddim_step" and kw == {} and len(args) == len(head) + 2
+        assert all(a is b for a, b in zip(args, head)) and args[-2:] == (7.5, d.coefficients(t))
+    for name in STEP_CFG:
+        p = S.DPMSolverMultistepScheduler()
+        p.set_timesteps(4)
+        call = _fused_calls(p, x)[name]
+        stem, head = heads[name]
+        calls.clear()
+        assert call(p._host_timesteps[0]) == "new" and call(p._host_timesteps[1]) == "new"
+        (op0, a0, k0), (op1, a1, k1) = calls
+        assert op0 == op1 == f"{stem}_dpm_step" and all(a is b for a, b in zip(a1, head))
+        assert a0[-2:] == (7.5, p.coefficients(0, False)) and a1[-2:] == (7.5, p.coefficients(1, True))
+        assert k0["x0_prev"] is None and k1["x0_prev"] is k0["x0_out"] and k1["x0_out"] is not k0["x0_out"]
+        before = (p._step_index, p._cur, p._have_prev)
+        assert before == (2, 0, True)
+        fail.append(True)
+        with pytest.raises(RuntimeError, match="launch failed"):
+            call(p._host_timesteps[2])
+        fail.clear()
+        assert (p._step_index, p._cur, p._have_prev) == before
+        assert call(p._host_timesteps[2]) == "new" and p._step_index == 3      # the same step goes through afterwards

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the ring-window kernels (csrc/coloop.hip) at the headline latent (1,4,24,72,128) with the looping job's default plan:
+"""Time the ring-window kernels (csrc/codenoise.hip, its RING flag) at the headline latent (1,4,24,72,128) with the looping job's default plan:
 two ring windows of 16 frames, (0, 16) and (12, 28), the second wrapping into frames 0..3.  Measured numbers only: medians of
 `--iters` (default 20) event-timed calls, each taken in `--rounds` (default 3) rounds that alternate between a ring kernel and
 its sibling, so that the spread between a kernel's own rounds stands beside the difference between the two.

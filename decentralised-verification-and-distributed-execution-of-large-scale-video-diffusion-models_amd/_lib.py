@@ -171,6 +171,12 @@ SIGNATURES = {
     "vdx_coloop_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
     "vdx_coloop_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i,
                                          _vp]),
+    # strided context windows: a strided window's input and the fused whole-clip steps over rows (off, s, L, d) (no reference
+    # counterpart; vdx/codenoise.py `stride_plan`, csrc/codenoise.hip, its `costride_tab`)
+    "vdx_cfg_input_stride_f16": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vdx_costride_cfg_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_costride_cfg_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i,
+                                           _i, _vp]),
     # CFG rescale: the statistics pass and the fused steps, plain and co-fused (no reference counterpart; vdx/scheduler.py
     # `guidance_rescale`, csrc/rescale.hip)
     "vdx_cfg_rescale_rows": (_i, [_sz]),

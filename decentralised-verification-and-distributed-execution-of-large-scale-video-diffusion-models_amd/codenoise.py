@@ -24,6 +24,14 @@ last ones wrap over its end into the first frames, so frames T-1 and 0 are denoi
 any other neighbouring pair, and the clip played as a loop has no jump there (`loop_table`, `check_loop` below).  Pinned in
 tests/test_coloop_gpu.py against tests/coloop_ref.py, the wrap itself by rotation equivariance; NOT pinned and not claimed: no
 external implementation is pinned, and there is no quality claim on real Zeroscope weights.
+
+With `DiffuserConfig(context_stride=N)` / `--context_stride N`, N > 1, the job also denoises STRIDED windows (AnimateDiff-Evolved's
+`context_stride`, the "uniform" context schedule; csrc/codenoise.hip, its `costride_tab`): level l < N adds windows that take
+every 2^l-th frame, so frames further apart than a window share a UNet call at every step, and every level has the share 1/N of a
+frame's fused noise (`stride_plan`, `stride_table`, `check_stride` below).  Each level costs its windows' UNet calls.  Pinned in
+tests/test_costride_gpu.py against tests/costride_ref.py, the stride itself by permuting the clip; NOT pinned and not claimed:
+no external implementation is pinned (the schedule is restated), and there is no quality claim on real Zeroscope weights, whose
+temporal layers were trained on consecutive frames and see faster motion in a strided window.
 """
 from __future__ import annotations
 
@@ -175,6 +183,145 @@ def check_loop(cfg, exchange: str = "allgather", world: Optional[int] = None) ->
     return True
 
 
+# ---- strided context windows (AnimateDiff-Evolved's `context_stride`; csrc/codenoise.hip, its `costride_tab`) -----------------------
+@dataclass(frozen=True)
+class StridePlan:
+    """The windows of a strided job in plan order, `(s, L, d)` = the frames `s + f * d`, f in [0, L): window i belongs to rank
+    `i % world`.  `chunk` is the longest window (it sizes a slot of the packed buffer), `overlap` the planner's, `levels` the
+    number of strides 1, 2, 4, ...; `base` is the level-0 `ChunkPlan`, the job's plan without the option."""
+    chunk: int
+    overlap: int
+    windows: Tuple[Tuple[int, int, int], ...]
+    world: int
+    levels: int
+    base: ChunkPlan
+
+    def for_rank(self, rank: int) -> List[Tuple[int, int, int]]:
+        return [w for i, w in enumerate(self.windows) if i % self.world == rank]
+
+    @property
+    def per_rank(self) -> int:
+        return len(self.windows) // self.world
+
+    @property
+    def strides(self) -> List[int]:
+        return [1 << l for l in range(self.levels)]
+
+
+def stride_plan(total: int, world: int, chunk_size: int = 0, overlap: int = 4, overlap_rule: str = "coherent", levels: int = 1,
+                no_chunking: bool = False) -> StridePlan:
+    """The "uniform" context schedule: level l in [0, levels) has stride d = 2^l.  Level 0 is the planner's own plan (`plan`, its
+    repeated tail window included), as `(s, e - s, 1)`.  For d > 1 every residue r in [0, d) has the subsequence r, r + d, ... of
+    `n_r = ceil((total - r) / d)` frames, covered by windows of ONE length `min(size, n_r)` by `tile_starts`' rule (starts 0,
+    size - ov, ..., the last moved back to end at the edge; `size`, `ov` the level-0 plan's) and mapped back to
+    `(r + d * s', L, d)`.  Levels ascending, residues ascending, starts ascending; the count is then padded to a multiple of
+    `world` by repeating the last window (denoised, so the ranks stay in lockstep, but not fused: `stride_table`).  With
+    `ov >= 1` (every "coherent" plan) any two frames t, t + d with t + d < total lie together in some window of the level of d.
+    `PlannerError` for `levels < 1` and for `2^levels > total` (a level whose subsequences hold fewer than two frames adds
+    nothing); `no_chunking` (mode "fsdp") makes level 0 one window of the whole clip and every residue one window."""
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 1:
+        raise PlannerError(f"context_stride {levels!r}: the number of stride levels must be an integer >= 1")
+    if total <= 0 or world <= 0:
+        raise PlannerError("num_frames and world size must be positive")
+    if levels > 1 and (1 << levels) > total:
+        raise PlannerError(f"context_stride {levels}: stride {1 << (levels - 1)} leaves fewer than two frames per window "
+                           f"in a clip of {total}")
+    from .planner import plan
+    base = plan(total, world, chunk_size, overlap, no_chunking, overlap_rule)
+    size, ov = base.chunk, base.overlap
+    wins = [(s, e - s, 1) for s, e in base.ranges]
+    for l in range(1, levels):
+        d = 1 << l
+        for r in range(d):
+            n_r = -(-(total - r) // d)
+            L = min(size, n_r)
+            wins += [(r + d * s, L, d) for s in tile_starts(n_r, L, min(ov, L - 1))]
+    if len(wins) % world:
+        wins += [wins[-1]] * (world - len(wins) % world)
+    return StridePlan(max(L for _, L, _ in wins), ov, tuple(wins), world, levels, base)
+
+
+def stride_plan_of(cfg, world: int) -> StridePlan:
+    """`stride_plan` of a job's config."""
+    return stride_plan(cfg.num_frames, world, cfg.chunk_size, cfg.overlap, cfg.overlap_rule, cfg.context_stride, cfg.no_chunking)
+
+
+@dataclass(frozen=True)
+class StrideTable:
+    """`fused`: (index in the plan, s, L, d) of the windows that enter the fuse, in plan order; `wn`: fp32 (K, T), the normalised
+    weights, zero outside a window."""
+    fused: Tuple[Tuple[int, int, int, int], ...]
+    wn: torch.Tensor
+
+    def rows(self, world: int, per_rank: int, slot_elems: int) -> List[Tuple[int, int, int, int]]:
+        """(element offset, first frame, length, stride) per fused window in the packed buffer `[world][per_rank][slot]`."""
+        return [(((i % world) * per_rank + i // world) * slot_elems, s, L, d) for i, s, L, d in self.fused]
+
+
+def stride_table(sp: StridePlan, T: int) -> StrideTable:
+    """`window_table` for a strided plan.  A window that repeats an earlier one (the planner's repeated tail, the padding) is
+    denoised but left out of the fuse.  Raw weights `fuse_weights(L, ov)[f]` at frame `s + f * d`, normalised in float64 PER
+    LEVEL over the fused windows of that stride that hold the frame (every frame must be in one, else `ValueError`), times
+    `1 / levels` in float64 (levels = the number of distinct strides), rounded to fp32 once: every level has the share 1/levels of
+    every frame's noise.  With one level that is `window_table`'s table, bit for bit."""
+    seen, fused = set(), []
+    for i, (s, L, d) in enumerate(sp.windows):
+        if not (d >= 1 and L >= 1 and 0 <= s and s + (L - 1) * d < T):
+            raise ValueError(f"stride_table: window {i} = ({s}, {L}, {d}) leaves the {T} frames")
+        if (s, L, d) not in seen:
+            seen.add((s, L, d))
+            fused.append((i, s, L, d))
+    if len(fused) > ops.COFUSE_MAX_WINDOWS:
+        raise ValueError(f"stride_table: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
+    strides = sorted({d for _, _, _, d in fused})
+    raw = np.zeros((len(fused), T), dtype=np.float64)
+    for k, (_, s, L, d) in enumerate(fused):
+        raw[k, s + d * np.arange(L)] = fuse_weights(L, sp.overlap)
+    wn = np.zeros_like(raw)
+    for d in strides:
+        level = np.array([w[3] == d for w in fused])
+        total = raw[level].sum(axis=0)
+        if (total <= 0).any():
+            raise ValueError(f"stride_table: frame {int(np.argmin(total > 0))} is in no window of stride {d}")
+        wn[level] = raw[level] / total
+    if len(strides) > 1:
+        wn = wn * (1.0 / len(strides))
+    return StrideTable(tuple(fused), torch.from_numpy(wn.astype(np.float32)))
+
+
+def check_stride(cfg, exchange: str = "allgather", world: Optional[int] = None) -> int:
+    """`cfg.context_stride`, the number of stride levels (1 = off: the job is then plain co-denoising or the windowed job, as
+    always); `ValueError` before any work when the job cannot run it: strided windows exist only as co-denoising, never with the
+    halo exchange, not with `tile`, `loop` or `guidance_rescale` (none has a strided form yet), and not when `stride_plan` refuses
+    the plan or the fused step cannot take its windows."""
+    levels = getattr(cfg, "context_stride", 1)
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 1:
+        raise ValueError(f"context_stride: the number of stride levels must be an integer >= 1, got {levels!r}")
+    if levels == 1:
+        return 1
+    if not getattr(cfg, "co_denoise", False):
+        raise ValueError("context_stride needs co_denoise: strided windows meet the others at every step in the fused noise; "
+                         "the windowed job's blend has no strided form")
+    if exchange == "halo":
+        raise ValueError("context_stride needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
+    if getattr(cfg, "tile", None) is not None:
+        raise ValueError("context_stride and tile exclude each other: the tiled kernels have no strided form yet")
+    if getattr(cfg, "loop", False):
+        raise ValueError("context_stride and loop exclude each other: ring windows have no strided form yet")
+    if getattr(cfg, "guidance_rescale", 0.0) != 0:
+        raise ValueError("context_stride and guidance_rescale exclude each other: the rescale's statistics pass has no strided form yet")
+    if world is None:
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    try:
+        sp = stride_plan_of(cfg, world)
+    except PlannerError as err:
+        raise ValueError(f"context_stride: {err}") from None
+    fused = len(set(sp.windows))
+    if fused > ops.COFUSE_MAX_WINDOWS:
+        raise ValueError(f"context_stride: {fused} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
+    return levels
+
+
 # ---- spatial tiles (MultiDiffusion's original form; csrc/cotile.hip) ------------------------------------------------------------
 def tile_starts(n: int, tile: int, overlap: int) -> List[int]:
     """First cells of the tiles of `tile` cells that cover `n` cells: 0, tile - overlap, 2 (tile - overlap), ..., the last one
@@ -291,7 +438,7 @@ def check_tile(cfg, exchange: str = "allgather") -> Optional[Tuple[int, int, int
     return th, tw, oy, ox
 
 
-def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[TilePlan] = None):
+def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[TilePlan] = None, strided: Optional[StridePlan] = None):
     """One co-denoised sampling round of `d` (a `DistributedVideoDiffuser`) from the whole clip's start latent -> (z.float(),
     the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  Per step: this rank's windows go
     through `ops.cfg_input_window` -> UNet into one packed buffer `[per_rank][2][C][cp.chunk][h][w]` (a window shorter than the
@@ -305,12 +452,20 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     ranks' shares, the repeated tail window and the one gather per step are as without it.
     `cfg.loop` (ring windows; `cp` is then a `loop_plan`): the table is `loop_table`'s, a window's input comes from
     `ops.cfg_input_loop` (frames `(s + f) mod T`), the step is `step_cfg_loop`, and the record gains `"loop"`: the windows as
-    [first frame, length]; everything else, the packed buffer and the mask step on the whole clip included, is as without it."""
+    [first frame, length]; everything else, the packed buffer and the mask step on the whole clip included, is as without it.
+    `strided` (a `StridePlan` of more than one level; `cp` is its level 0): the windows, their ranks and the slot (sized by the
+    longest window) are the strided plan's, the table is `stride_table`'s, a window's input comes from `ops.cfg_input_stride`
+    (frames `s + f * d`), the step is `step_cfg_strided`, and the record gains `"context_stride"`: the levels, their strides and
+    the fused windows as [s, L, d]; still one gather per step, and the mask step on the whole clip as without it."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
     loop = bool(getattr(cfg, "loop", False))
-    table = loop_table(cp, T) if loop else window_table(cp, T)
+    if strided is not None:
+        cp = strided                                              # the same names: chunk, per_rank, for_rank
+        table = stride_table(strided, T)
+    else:
+        table = loop_table(cp, T) if loop else window_table(cp, T)
     per, world, rank = cp.per_rank, d.world, d.rank
     boxes = [()] if tiles is None else tiles.boxes                # (): the whole frame, as always
     nt = len(boxes)
@@ -320,6 +475,8 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     wn = table.wn.to(start.device)
     grid = None if tiles is None else tiles.grid(slot, start.device)
     mine = cp.for_rank(rank)
+    if strided is not None:                                       # (s, L, d) -> the (s, e) the byte counts below read: e - s = L
+        mine, spans_strided = [(s, s + L) for s, L, _ in mine], mine
     emb = torch.cat([d.uncond_emb, d.cond_emb], dim=0)
     local = torch.zeros((per, nt * slot), dtype=torch.float16, device=start.device)
     packed = torch.zeros((world, per, nt * slot), dtype=torch.float16, device=start.device) if world > 1 else local
@@ -333,7 +490,10 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     spent = {"denoise_s": 0.0, "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0,
              "payload_bytes_actual": 0}
     # the window's UNet input and the step, decided once per round: the op with the range it takes, the method with its leading arguments
-    if loop:
+    if strided is not None:
+        input_op, spans = ops.cfg_input_stride, spans_strided
+        step, head, step_kw = sched.step_cfg_strided, (packed, rows, wn), {}
+    elif loop:
         input_op, spans = ops.cfg_input_loop, [(s, e - s) for s, e in mine]
         step, head, step_kw = sched.step_cfg_loop, (packed, rows, wn), {}
     elif tiles is None:
@@ -374,4 +534,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
         rec["tile"] = tiles.record(len(table.fused))
     if loop:
         rec["loop"] = {"windows": [[s, e - s] for _, s, e in table.fused]}
+    if strided is not None:
+        rec["context_stride"] = {"levels": strided.levels, "strides": strided.strides,
+                                 "windows": [[s, L, dd] for _, s, L, dd in table.fused]}
     return z.float(), spent, rec

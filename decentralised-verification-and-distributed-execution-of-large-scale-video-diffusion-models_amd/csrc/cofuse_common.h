@@ -2,7 +2,8 @@
 // accesses, the ONE line-per-block step kernel with its tail, dispatch and launcher, and the host checks.  codenoise.hip (the plain
 // co-denoising steps, flat and ring), rescale.hip (the same steps with CFG rescale and their statistics pass) and cotile.hip (the
 // row-per-block tiled steps) all go through these, so the variants cannot drift apart.  A variant is a guidance policy (what turns
-// the fused u, c into the guided noise), the RING flag, or a block map of its own that ends in `cofuse_tail`.
+// the fused u, c into the guided noise), the RING flag, the table type (`costride_tab`: a frame stride per row), or a block map of
+// its own that ends in `cofuse_tail`.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -18,6 +19,13 @@ struct cofuse_tab {
     int s[COFUSE_MAX_WINDOWS];             // first frame
     int len[COFUSE_MAX_WINDOWS];           // L_k
 };
+
+// the table of the strided steps (vdx_costride_*): row k holds the frames s_k + f * d_k, f in [0, L_k).  1.25 KiB by value, well
+// inside the 4 KiB of kernel arguments; the flat and ring steps keep the 1 KiB table above
+struct costride_tab : cofuse_tab {
+    int d[COFUSE_MAX_WINDOWS];             // frame stride, >= 1
+};
+template <class Tab> constexpr bool co_strided = std::is_same<Tab, costride_tab>::value;
 
 template <int E> struct halves;
 template <> struct halves<8> { typedef f16x8 type; };
@@ -69,8 +77,10 @@ __device__ __forceinline__ float fuse_term(float acc, float w, float x, bool fir
 // the floats the chains take).  t is uniform over a block, so the window loop, the table reads and the weights are too.
 // RING (the vdx_coloop_* steps): window k holds the frames (s_k + f) mod T, f in [0, L_k), with 0 <= s_k < T and L_k <= T, so the one
 // wrap is a compare and an add; the default leaves the plain instantiations as they were.
-template <int E, bool RING = false>
-__device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab, int K, const float* wn, int C, int T, int HW, int c,
+// A `costride_tab` (the vdx_costride_* steps): window k holds frame t as its frame q / d_k where q = t - s_k >= 0, q % d_k == 0 and
+// q / d_k < L_k: one unsigned division per window, on block-uniform integers.
+template <int E, bool RING = false, class Tab = cofuse_tab>
+__device__ __forceinline__ void cofuse_uc(const f16* win, const Tab& tab, int K, const float* wn, int C, int T, int HW, int c,
                                           int t, int p, float (&uf)[E], float (&cf)[E]) {
     float U[E], Cc[E];
 #pragma unroll
@@ -79,7 +89,12 @@ __device__ __forceinline__ void cofuse_uc(const f16* win, const cofuse_tab& tab,
     for (int k = 0; k < K; ++k) {
         int f = t - tab.s[k];
         const int L = tab.len[k];
-        if constexpr (RING) {
+        if constexpr (co_strided<Tab>) {
+            if (f < 0) continue;
+            const unsigned d = (unsigned)tab.d[k], q = (unsigned)f / d;
+            if (q * d != (unsigned)f || q >= (unsigned)L) continue;
+            f = (int)q;
+        } else if constexpr (RING) {
             if (f < 0) f += T;
             if (f >= L) continue;
         } else {
@@ -135,8 +150,8 @@ __device__ __forceinline__ void cofuse_tail(const f16* z, const f16* x0_prev, f1
 }
 
 // Block map: a block works on ONE (c, t) line of h*w elements (tiles of 256 lanes x E elements): see codenoise.hip.
-template <int MODE, int E, bool RING, class G>
-__global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f16* win, cofuse_tab tab, int K, const float* wn,
+template <int MODE, int E, bool RING, class G, class Tab = cofuse_tab>
+__global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f16* win, Tab tab, int K, const float* wn,
                                                           const f16* x0_prev, f16* x0_out, f16* out, ddim_coef kd, dpm_coef kp, G g,
                                                           int C, int T, int HW, unsigned tiles_per_line) {
     const float r = g.prologue();                                 // all 256 lanes, before any of them leaves
@@ -145,7 +160,7 @@ __global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f1
     const int p = (int)((tile * 256u + threadIdx.x) * (unsigned)E);
     if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
     float uf[E], cf[E];
-    cofuse_uc<E, RING>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);   // uniform over the block: t is
+    cofuse_uc<E, RING, Tab>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);   // uniform over the block: t is
     cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, r, kd, kp);
 }
 
@@ -165,8 +180,8 @@ static inline void step_dispatch(int mode, const void* x0_prev, int e, F&& go) {
 }
 
 // the launch of a line-per-block step whose arguments `cofuse_check` has passed (it gave `tab` and `e`)
-template <bool RING, class G>
-static int cofuse_launch(const char* what, int mode, const void* z, const void* windows, const cofuse_tab& tab, int e, int K,
+template <bool RING, class G, class Tab>
+static int cofuse_launch(const char* what, int mode, const void* z, const void* windows, const Tab& tab, int e, int K,
                          const float* wn, const void* x0_prev, void* x0_out, void* lat_out, ddim_coef kd, dpm_coef kp, G g, int C, int T,
                          int HW, vdx_stream_t stream) {
     const size_t per_tile = 256 * (size_t)e;
@@ -174,7 +189,7 @@ static int cofuse_launch(const char* what, int mode, const void* z, const void* 
     const size_t blocks = tiles_per_line * C * T;
     VDX_CHECK(blocks <= 0x7fffffffull, "%s: %zu blocks exceed the grid", what, blocks);
     step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
-        hipLaunchKernelGGL((cofuse_step_kernel<decltype(m)::value, decltype(ee)::value, RING, G>), dim3((unsigned)blocks), dim3(256), 0,
+        hipLaunchKernelGGL((cofuse_step_kernel<decltype(m)::value, decltype(ee)::value, RING, G, Tab>), dim3((unsigned)blocks), dim3(256), 0,
                            (hipStream_t)stream, (const f16*)z, (const f16*)windows, tab, K, wn, (const f16*)x0_prev, (f16*)x0_out,
                            (f16*)lat_out, kd, kp, g, C, T, HW, (unsigned)tiles_per_line);
     });
@@ -196,14 +211,23 @@ static inline void co_narrow(int& e, long long v) {
 // The time-window table of a step: every row (off, s, L) against T and the buffer, `e` narrowed to what every offset allows, and
 // every frame in some window.  `ring`: a row means the frames (s + f) mod T, so 0 <= s < T and 1 <= L <= T replace s + L <= T, and
 // a frame is held under that rule.  `need(k, L, elems)` gives the elements window k occupies from its offset (it may refuse the row).
+// `win_stride` (read for a `costride_tab` only, never with `ring`): a row means the frames s + f * d, so d >= 1 and
+// s + (L - 1) * d < T, formed in 64 bits, replace s + L <= T, and a frame is held under that rule.
 template <class Tab, class Need>
 static inline int cofuse_windows(const char* what, bool ring, size_t windows_elems, const int64_t* win_off, const int* win_start,
-                                 const int* win_len, int K, int T, Need&& need, Tab& tab, int& e) {
+                                 const int* win_len, int K, int T, Need&& need, Tab& tab, int& e, const int* win_stride = nullptr) {
     for (int k = 0; k < K; ++k) {
         const long long off = (long long)win_off[k];
         const int s = win_start[k], L = win_len[k];
-        VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= (ring ? T : T - s), "%s: window %d covers [%d, %d + %d) of %d frames", what, k, s, s,
-                  L, T);
+        if constexpr (co_strided<Tab>) {
+            const int d = win_stride[k];
+            VDX_CHECK(d >= 1 && L >= 1 && s >= 0 && (long long)s + ((long long)L - 1) * d < T,
+                      "%s: window %d holds the frames %d + f * %d, f < %d, of %d frames", what, k, s, d, L, T);
+            tab.d[k] = d;
+        } else {
+            VDX_CHECK(L >= 1 && s >= 0 && s < T && L <= (ring ? T : T - s), "%s: window %d covers [%d, %d + %d) of %d frames", what, k,
+                      s, s, L, T);
+        }
         size_t elems = 0;
         if (int rc = need(k, L, elems)) return rc;
         VDX_CHECK(off >= 0 && (size_t)off <= windows_elems && elems <= windows_elems - (size_t)off,
@@ -218,7 +242,8 @@ static inline int cofuse_windows(const char* what, bool ring, size_t windows_ele
         for (int k = 0; k < K && !hit; ++k) {
             int f = t - tab.s[k];
             if (ring && f < 0) f += T;
-            hit = f >= 0 && f < tab.len[k];
+            if constexpr (co_strided<Tab>) hit = f >= 0 && f % tab.d[k] == 0 && f / tab.d[k] < tab.len[k];
+            else hit = f >= 0 && f < tab.len[k];
         }
         VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
     }
@@ -248,12 +273,15 @@ static inline int cofuse_alias(const char* what, int mode, const void* z, const 
 
 // Every check of a line-per-block co-fused step, before a launch -> 0 and the table `tab` and the access width `e` (8, 4 or 1
 // halves), else the error.  mode 0: DDIM (no x0 history); otherwise DPM-Solver++.  `writes` false: a statistics pass, which reads
-// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).
+// no latent and writes none (z, x0_prev, x0_out and lat_out are then not looked at beyond their alignment).  `Tab` a
+// `costride_tab`: `win_stride` is the rows' fourth column.
+template <class Tab>
 static inline int cofuse_check(const char* what, int mode, bool writes, const void* z, const void* windows, size_t windows_elems,
                                const int64_t* win_off, const int* win_start, const int* win_len, int K, const float* wn,
-                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, cofuse_tab& tab, int& e,
-                               bool ring = false) {
-    VDX_CHECK((z || !writes) && windows && win_off && win_start && win_len && wn && (lat_out || !writes), "%s: null pointer", what);
+                               const void* x0_prev, void* x0_out, void* lat_out, int C, int T, int HW, Tab& tab, int& e,
+                               bool ring = false, const int* win_stride = nullptr) {
+    VDX_CHECK((z || !writes) && windows && win_off && win_start && win_len && wn && (lat_out || !writes) &&
+                  (win_stride || !co_strided<Tab>), "%s: null pointer", what);
     VDX_CHECK(C > 0 && T > 0 && HW > 0 && HW <= 1 << 30, "%s: bad shape C=%d T=%d HW=%d", what, C, T, HW);
     VDX_CHECK(K >= 1 && K <= COFUSE_MAX_WINDOWS, "%s: %d windows, 1..%d are supported", what, K, COFUSE_MAX_WINDOWS);
     VDX_CHECK(mode == 0 || !writes || x0_out, "%s: x0_out is null", what);
@@ -261,13 +289,13 @@ static inline int cofuse_check(const char* what, int mode, bool writes, const vo
     VDX_CHECK((size_t)C * T <= (size_t)1 << 30 && n <= (size_t)1 << 40, "%s: latent too large", what);
     for (const void* ptr : {z, windows, (const void*)wn, x0_prev, (const void*)x0_out, (const void*)lat_out})
         VDX_CHECK(((uintptr_t)ptr & 15) == 0, "%s: pointer not 16-byte aligned", what);
-    tab = cofuse_tab{};
+    tab = Tab{};
     e = HW % 8 == 0 ? 8 : HW % 4 == 0 ? 4 : 1;
     const auto need = [&](int, int L, size_t& elems) {
         elems = 2 * (size_t)C * L * HW;
         return 0;
     };
-    if (int rc = cofuse_windows(what, ring, windows_elems, win_off, win_start, win_len, K, T, need, tab, e)) return rc;
+    if (int rc = cofuse_windows(what, ring, windows_elems, win_off, win_start, win_len, K, T, need, tab, e, win_stride)) return rc;
     if (!writes) return 0;
     const co_buf inputs[] = {{windows, windows_elems * sizeof(f16)}, {wn, (size_t)K * T * sizeof(float)}};
     return cofuse_alias(what, mode, z, x0_prev, x0_out, lat_out, n * sizeof(f16), inputs, "an input or lat_out", "an input or lat_out");

@@ -923,9 +923,10 @@ def cfg_input_window(z, ctx, weight, s: int, e: int, out=None):
 COFUSE_MAX_WINDOWS = 64
 
 
-def _cofuse_args(what, z, windows, table, wn):
+def _cofuse_args(what, z, windows, table, wn, strided=False):
     """Shared checks of the two fused co-denoising steps -> the launch's leading arguments.  `table`: [(element offset into
-    `windows`, first frame, length)] per window, host integers; the library checks every row against T and the buffer."""
+    `windows`, first frame, length)] per window, host integers; the library checks every row against T and the buffer.
+    `strided`: a row has a fourth entry, the frame stride, which travels as a fourth host array after the lengths."""
     if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
         raise VdxError(f"{what}: z must be contiguous (1,C,T,H,W)")
     if not windows.is_contiguous():
@@ -939,15 +940,17 @@ def _cofuse_args(what, z, windows, table, wn):
     off = (C.c_int64 * K)(*(int(r[0]) for r in table))
     st = (C.c_int32 * K)(*(int(r[1]) for r in table))
     ln = (C.c_int32 * K)(*(int(r[2]) for r in table))
-    return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
+    sd = ((C.c_int32 * K)(*(int(r[3]) for r in table)),) if strided else ()
+    return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, *sd, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
 
 
-def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None):
+def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None, strided=False):
     """The DDIM form of every whole-clip fused step, launched as `symbol`(head, out, extras, tail) and named in errors as the
-    wrapper, `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head, else `_cotile_args`'; `rescaled`: the
-    rescale variants' ((phi, 1 - phi), partials, stats_out).  One call below the public wrapper and no closure: launch-bound."""
+    wrapper, `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head (`strided`: with its fourth column), else
+    `_cotile_args`'; `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out).  One call below the public wrapper
+    and no closure: launch-bound."""
     what = symbol[4:-4]
-    head, tail = _cofuse_args(what, z, windows, table, wn) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
+    head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
     if out is None:
         out = torch.empty_like(z)
     elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
@@ -961,10 +964,10 @@ def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, r
     return out
 
 
-def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None):
+def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None, strided=False):
     """The DPM-Solver++ form of the same, through `_dpm_args` -> (z', x0)."""
     what = symbol[4:-4]
-    head, tail = _cofuse_args(what, z, windows, table, wn) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
+    head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
     x0_out, out, c = _dpm_args(what, z, x0_prev, x0_out, out, coeffs)
     bufs = phis = ()
     if rescaled is not None:
@@ -1012,6 +1015,34 @@ def coloop_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
 def coloop_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """`cofuse_cfg_dpm_step` over ring windows (`vdx_coloop_cfg_dpm_step_f16`) -> (z', x0)."""
     return _co_dpm_step("vdx_coloop_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out)
+
+
+# --------------------------------------------------------------------------------------------
+# Strided context windows (vdx/codenoise.py `stride_plan`, csrc/codenoise.hip's `costride_tab`; no reference counterpart)
+def cfg_input_stride(z, ctx, weight, s: int, L: int, d: int, out=None):
+    """`cfg_input_window` with a frame stride: one launch reads the frames `s + f * d`, f in [0, L), out of the whole clip's latent
+    z (1,C,T,H,W), `d >= 1`, `s + (L - 1) * d < T`, and writes the contiguous (2,C,L,H,W) UNet input, TAGGED as a CFG duplicate
+    exactly as `cfg_input_window` tags its result.  The library checks `s`, `L` and `d`; `d = 1` gives `cfg_input_window`'s bits."""
+    if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
+        raise VdxError("cfg_input_stride: z must be contiguous (1,C,T,H,W)")
+    _, Cc, T, H, W = z.shape
+    s, L, d = int(s), int(L), int(d)
+    if L < 1:
+        raise VdxError(f"cfg_input_stride: bad strided window start {s}, length {L}, stride {d} of {T} frames")
+    return _cfg_input_of("cfg_input_stride", "vdx_cfg_input_stride_f16", z, ctx, weight, out, (2, Cc, L, H, W), "(2,C,L,H,W)",
+                         (H * W, s, L, d))
+
+
+def costride_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
+    """`cofuse_cfg_ddim_step` over strided windows (include/vdx.h `vdx_costride_cfg_ddim_step_f16`): a `table` row
+    (offset, s, L, d) means the frames `s + f * d`; the fuse, the chain, `coeffs` and `out` (which may be `z`) are the same."""
+    return _co_ddim_step("vdx_costride_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out, strided=True)
+
+
+def costride_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
+    """`cofuse_cfg_dpm_step` over strided windows (`vdx_costride_cfg_dpm_step_f16`) -> (z', x0)."""
+    return _co_dpm_step("vdx_costride_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
+                        strided=True)
 
 
 # --------------------------------------------------------------------------------------------

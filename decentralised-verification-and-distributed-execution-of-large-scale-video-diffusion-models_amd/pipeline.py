@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .codenoise import check_co_denoise, check_loop, check_tile, co_denoise_round, loop_plan_of, tile_plan
+from .codenoise import check_co_denoise, check_loop, check_stride, check_tile, co_denoise_round, loop_plan_of, stride_plan_of, tile_plan
 from .inpaint import check_mask, known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .planner import ChunkPlan, plan
@@ -111,6 +111,11 @@ class DiffuserConfig:
     # `co_denoise`): the windows lie on a ring, the last wrapping over the clip's end into its first frames, so frames T-1 and 0
     # are denoised together at every step.  False = the windows stop at the clip's end, as always
     loop: bool = False
+    # strided context windows (vdx/codenoise.py `stride_plan`, csrc/codenoise.hip, its `costride_tab`; AnimateDiff-Evolved's
+    # `context_stride`, unpinned; needs `co_denoise`): the number of stride levels 1, 2, 4, ...; every level above the first adds
+    # windows that take every 2nd, 4th, ... frame, so frames further apart than a window are denoised together at every step, at
+    # the price of those windows' UNet calls.  1 = consecutive frames only, as always
+    context_stride: int = 1
 
     @property
     def use_fsdp(self):
@@ -317,6 +322,7 @@ class DistributedVideoDiffuser:
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
         self._co_rec: List[dict] = []                              # co_denoise: the rounds' records of the last call
         self._tiles = None                                         # tile: the spatial plan of the last call
+        self._stride = None                                        # context_stride > 1: the strided plan of the last call
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
         self.uncond_emb, self.cond_emb = uncond_emb, cond_emb
@@ -435,7 +441,8 @@ class DistributedVideoDiffuser:
         With `cfg.co_denoise` the round is `codenoise.co_denoise_round` instead: one latent, the windows meet at every step, no
         blend; its record is added to `self._co_rec`."""
         if self.cfg.co_denoise:
-            out, spent, rec = co_denoise_round(self, start, cp, *((self._tiles,) if self._tiles is not None else ()))
+            out, spent, rec = co_denoise_round(self, start, cp, *((self._tiles,) if self._tiles is not None else ()),
+                                               **({"strided": self._stride} if self._stride is not None else {}))
             self._co_rec.append(rec)
             return out, spent
         _, C, T, H, W = start.shape
@@ -513,11 +520,19 @@ class DistributedVideoDiffuser:
         `freeu`; refused with "halo", `tile`, `guidance_rescale` and a plan `codenoise.loop_plan` refuses, mode "fsdp" among
         them): the windows of every round lie on a ring (`codenoise.loop_plan` / `loop_table`, `ops.cfg_input_loop`,
         `step_cfg_loop`); `info["ranges"]` holds each window clipped to the clip, (s, min(e, T)), and `info["loop"]` =
-        {"windows": [[first frame, length], ...]}."""
+        {"windows": [[first frame, length], ...]}.
+
+        `context_stride` > 1 (with `co_denoise` only; both samplers, every mode, `init_latents`, `latent_mask`, every FreeInit
+        iteration, `freeu`, `tome`; refused with "halo", `tile`, `loop`, `guidance_rescale` and a plan `codenoise.stride_plan`
+        refuses): every round also denoises the strided windows of `codenoise.stride_plan` (`ops.cfg_input_stride`,
+        `step_cfg_strided`); `info["ranges"]`, `info["chunk_size"]` and `info["overlap"]` stay the level-0 plan's, and
+        `info["co_denoise"]` and `info` gain `"context_stride"` = {"levels", "strides", "windows": [[s, L, d], ...]}."""
         cfg = self.cfg
         co = check_co_denoise(cfg, exchange)
         tile = check_tile(cfg, exchange)
         loop = check_loop(cfg, exchange, self.world)
+        levels = check_stride(cfg, exchange, self.world)
+        self._stride = stride_plan_of(cfg, self.world) if levels > 1 else None
         self._tiles = tile_plan(cfg.height // 8, cfg.width // 8, *tile) if tile is not None else None
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
@@ -589,6 +604,8 @@ class DistributedVideoDiffuser:
                 info["tile"] = self._co_rec[0]["tile"]
             if loop:
                 info["loop"] = self._co_rec[0]["loop"]
+            if levels > 1:
+                info["context_stride"] = info["co_denoise"]["context_stride"] = self._co_rec[0]["context_stride"]
         return out, info
 
 
@@ -667,7 +684,14 @@ def build_arg_parser():
     `loop_plan`, csrc/codenoise.hip, its RING flag), so frames T-1 and 0 are denoised together in one UNet call at every step; `--interpolate N`
     then also fills the pair (T-1, 0) and writes T N frames; refused without `--co_denoise`, with `--exchange halo`, `--tile`,
     `--guidance_rescale`, `--mode fsdp` and a chunk as long as the clip; the result and the JSON records carry `"loop"`:
-    {"windows", "wrap_l1", "mean_l1"}; without the flag every launch, byte, CSV row and record is the one it always was."""
+    {"windows", "wrap_l1", "mean_l1"}; without the flag every launch, byte, CSV row and record is the one it always was.
+    `--context_stride N` (with `--co_denoise`; no reference counterpart; AnimateDiff-Evolved's `context_stride`, the "uniform" context
+    schedule, unpinned) adds, beside the windows of consecutive frames, windows that take every 2nd, 4th, ... 2^(N-1)-th frame
+    (vdx/codenoise.py `stride_plan`, csrc/codenoise.hip, its `costride_tab`), so frames further apart than a window are denoised
+    together in one UNet call at every step; every level has an equal share of the fused noise and costs its windows' UNet calls;
+    refused without `--co_denoise`, with `--exchange halo`, `--tile`, `--loop`, `--guidance_rescale` and when 2^N exceeds the clip;
+    the result and the JSON records carry `"context_stride"`: {"levels", "strides", "windows"}; with N = 1, the default, every
+    launch, byte, CSV row and record is the one it always was."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -728,6 +752,8 @@ def build_arg_parser():
                    help="--tile: overlap of neighbouring tiles in pixels (multiples of 8; default: a quarter of the tile)")
     p.add_argument("--loop", action="store_true",
                    help="with --co_denoise: ring windows, so that the clip's last frame leads back into its first (default: off)")
+    p.add_argument("--context_stride", type=int, default=1, metavar="N",
+                   help="with --co_denoise: N stride levels; level l adds windows of every 2^l-th frame (1, the default: consecutive frames only)")
     p.add_argument("--mask", default=None,
                    help="masked video-to-video: .npy uint8 / bool (T,H,W), (H,W) or (T,), nonzero = regenerate, zero = keep (needs --init_video)")
     p.add_argument("--keep_frames", default=None,
@@ -886,6 +912,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
         from .tome import check_grid
         check_grid(*((tile[0], tile[1]) if tile is not None else (cfg.height // 8, cfg.width // 8)), tome)
     loop = check_loop(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
+    levels = check_stride(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
     pixel_mask = check_mask(cfg, exchange)      # None: the option is off
     phi = check_guidance_rescale(cfg)
     if not isinstance(cfg.negative_prompt, str):
@@ -973,7 +1000,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
             **({"tome": tome} if tome is not None else {}),
             **({"co_denoise": info["co_denoise"]} if co else {}), **({"tile": info["tile"]} if tile is not None else {}),
-            **({"loop": info["loop"]} if loop else {}),
+            **({"loop": info["loop"]} if loop else {}), **({"context_stride": info["context_stride"]} if levels > 1 else {}),
             **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
 
 
@@ -1012,6 +1039,8 @@ def main(argv=None) -> int:
             source["tile"] = res["tile"]
         if "loop" in res:
             source["loop"] = res["loop"]
+        if "context_stride" in res:
+            source["context_stride"] = res["context_stride"]
         if "mask" in res:
             source["mask"] = res["mask"]
         guidance = {k: res[k] for k in ("negative_prompt", "guidance_rescale") if k in res}
@@ -1045,6 +1074,8 @@ def main(argv=None) -> int:
                 rec["tile"] = res["tile"]
             if "loop" in res:
                 rec["loop"] = res["loop"]
+            if "context_stride" in res:
+                rec["context_stride"] = res["context_stride"]
             if "mask" in res:
                 rec["mask"] = res["mask"]
             rec.update(guidance)

@@ -118,6 +118,13 @@ class _SchedulerBase:
         head = (sample.contiguous(), windows, table, wn)
         return self._fused_step((ops.coloop_cfg_ddim_step, ops.coloop_cfg_dpm_step), head, timestep, head[0], guidance_scale)
 
+    def step_cfg_strided(self, windows, table, wn, timestep, sample, guidance_scale: float):
+        """Strided context windows (vdx/codenoise.py `stride_plan`): `step_cfg_windows` with a `table` row (offset, s, L, d)
+        meaning the frames s + f * d (`ops.costride_cfg_ddim_step` / `ops.costride_cfg_dpm_step`), one kernel.
+        No `guidance_rescale` form."""
+        head = (sample.contiguous(), windows, table, wn)
+        return self._fused_step((ops.costride_cfg_ddim_step, ops.costride_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+
     def add_noise(self, original_samples, noise, timesteps):
         """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,
         then sqrt(a_t) and sqrt(1 - a_t) are fp16 tensor ops (evaluated here with torch on the sample's device, as diffusers

@@ -409,6 +409,29 @@ int vdx_coloop_cfg_dpm_step_f16(const void* z, const void* windows, size_t windo
                                 const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
                                 void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
                                 float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
+/* Strided context windows for co-denoising (AnimateDiff-Evolved's `context_stride`, the "uniform" context schedule, restated, not
+ * pinned against it; no reference counterpart, opt-in: vdx/codenoise.py `stride_plan`, `DiffuserConfig.context_stride`,
+ * csrc/codenoise.hip, restated in tests/costride_ref.py).  A window (s, L, d) holds the frames s + f * d, f in [0, L), with d >= 1,
+ * 0 <= s, L >= 1 and s + (L - 1) * d < T (checked in 64 bits).
+ * vdx_cfg_input_stride_f16: `vdx_cfg_input_window_f16` under that rule (a LENGTH, not an end): x2 (2,C,L,h,w) contiguous, one
+ * launch, no slice copy, the ctx term with the same two fp16 roundings; 16-byte accesses where HW % 8 == 0, else element-wise; x2
+ * must not overlap z; pointers 16-byte aligned.  A call with d = 1 has the bits of vdx_cfg_input_window_f16(…, s, s + L).        */
+int vdx_cfg_input_stride_f16(const void* z, const void* ctx, float weight, void* x2, int C, int T, int HW, int s, int L, int d,
+                             vdx_stream_t stream);
+/* `vdx_cofuse_cfg_ddim_step_f16` / `vdx_cofuse_cfg_dpm_step_f16` (same arguments, same wn, same fuse term for term, same chains,
+ * same rules for x0_prev, x0_out and lat_out, same alignment and overlap rules and access widths) with a fourth HOST table,
+ * win_stride[K]: per (c, t), for k ascending, q = t - s_k; window k enters with its frame q / d_k if q >= 0, q % d_k == 0 and
+ * q / d_k < L_k.  Checked: every row as above, every block (2,C,L_k,h,w) inside the buffer, every frame in some window under the
+ * strided rule, 1 <= K <= 64.  The table travels by value in the kernel arguments: 64 rows of (8 + 4 + 4 + 4) bytes, 1.25 KiB.  A
+ * table whose strides are all 1 gives the bits of the vdx_cofuse_* step.                                                       */
+int vdx_costride_cfg_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                   const int* win_start, const int* win_len, const int* win_stride, int K, const float* wn,
+                                   void* lat_out, float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                                   float sqrt_one_minus_aprev, int C, int T, int HW, vdx_stream_t stream);
+int vdx_costride_cfg_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                  const int* win_start, const int* win_len, const int* win_stride, int K, const float* wn,
+                                  const void* x0_prev, void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0,
+                                  float c_x, float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
 /* Classifier-free guidance with CFG rescale (Lin et al. 2023, section 3.4; diffusers `rescale_noise_cfg`; no reference counterpart,
  * opt-in: `guidance_rescale` of vdx/scheduler.py, csrc/rescale.hip, restated in tests/rescale_ref.py).  With g the combine above,
  * over the N = n elements of the sample (fp64 sums S1 = sum x, S2 = sum x*x of the fp16 values):

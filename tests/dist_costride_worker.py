@@ -1,0 +1,51 @@
+"""Worker of tests/test_dist_costride_gpu.py (not a test): one rank of a real multi-process co-denoised job with STRIDED context
+windows (vdx/codenoise.py `stride_plan`).  All ranks compute on cuda:0 and talk over gloo (the share-GPU rehearsal of
+tests/dist_pipeline_worker.py).  Every rank runs its windows of every level, the packed noise buffers are gathered once per step,
+and every rank steps its own copy of the whole clip's latent; the ranks then check over gloo that their latents carry the same
+bits; rank 0 saves its latent and `info`.  The rank, the world size and the rendezvous come from the environment (RANK,
+WORLD_SIZE, MASTER_ADDR, MASTER_PORT): the test starts each rank as a process of its own.
+
+    RANK=r WORLD_SIZE=W MASTER_ADDR=127.0.0.1 MASTER_PORT=p python tests/dist_costride_worker.py OUT.pt T CHUNK OVERLAP STEPS SCHEDULER LEVELS"""
+import os
+import sys
+
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import vdx  # noqa: E402,F401
+from dist_pipeline_worker import build  # noqa: E402
+from vdx.pipeline import DiffuserConfig, DistributedVideoDiffuser, make_scheduler  # noqa: E402
+from vdx.scheduler import DDIMScheduler  # noqa: E402
+
+
+def main():
+    out = sys.argv[1]
+    T, chunk, ov, steps = (int(a) for a in sys.argv[2:6])
+    sampler, levels = sys.argv[6], int(sys.argv[7])
+    dist.init_process_group("gloo")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    m, emb = build(dev, rank, world)
+    cfg = DiffuserConfig(num_frames=T, steps=steps, chunk_size=chunk, overlap=ov, height=256, width=256, mode="hybrid_ctx",
+                         device="cuda", noise_device="cpu", scheduler=sampler, co_denoise=True, context_stride=levels)
+    d = DistributedVideoDiffuser(cfg, m, make_scheduler(sampler, DDIMScheduler()), emb[1:], emb[:1])
+    lat, info = d(exchange="allgather")
+    mine = lat.cpu()
+    every = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(every, mine)
+    for r, t in enumerate(every):
+        assert torch.equal(t.view(torch.int32), mine.view(torch.int32)), (rank, r)
+    if rank == 0:
+        keep = ("ranges", "chunk_size", "overlap", "world_size", "network_bytes", "payload_bytes", "payload_bytes_actual",
+                "steps_run", "co_denoise", "context_stride")
+        torch.save({"lat": mine, "info": {k: info[k] for k in keep}, "gathers": getattr(m.W, "gathers", None)}, out)
+    dist.barrier()
+    dist.destroy_process_group()
+    print("rank", rank, "ok", flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -15,20 +15,20 @@ seam-quality effect on real Zeroscope weights.
 
 With `DiffuserConfig(tile=(TH, TW))` / `--tile TH TW` the windows are additionally tiled in space (MultiDiffusion's original form;
 csrc/cotile.hip): a window is the product of a time window, a row band and a column band, every UNet call is a crop of one tile's
-size, and the fused step averages with the product of three per-axis normalised weights (`tile_plan`, `check_tile` below).  Pinned
+size, and the fused step averages with the product of three per-axis normalised weights (`tile_plan` below; `check_tile` in vdx/options.py).  Pinned
 in tests/test_cotile_gpu.py against tests/cotile_ref.py; again no external implementation and no quality claim.
 
 With `DiffuserConfig(loop=True)` / `--loop` the windows lie on a RING (AnimateDiff's `closed_loop` context option; MultiDiffusion
 along time with periodic windows; csrc/codenoise.hip, its RING flag): `loop_plan` spreads windows of one length evenly over the clip and lets the
 last ones wrap over its end into the first frames, so frames T-1 and 0 are denoised together in one UNet call at every step like
-any other neighbouring pair, and the clip played as a loop has no jump there (`loop_table`, `check_loop` below).  Pinned in
+any other neighbouring pair, and the clip played as a loop has no jump there (`loop_table` below; `check_loop` in vdx/options.py).  Pinned in
 tests/test_coloop_gpu.py against tests/coloop_ref.py, the wrap itself by rotation equivariance; NOT pinned and not claimed: no
 external implementation is pinned, and there is no quality claim on real Zeroscope weights.
 
 With `DiffuserConfig(context_stride=N)` / `--context_stride N`, N > 1, the job also denoises STRIDED windows (AnimateDiff-Evolved's
 `context_stride`, the "uniform" context schedule; csrc/codenoise.hip, its `costride_tab`): level l < N adds windows that take
 every 2^l-th frame, so frames further apart than a window share a UNet call at every step, and every level has the share 1/N of a
-frame's fused noise (`stride_plan`, `stride_table`, `check_stride` below).  Each level costs its windows' UNet calls.  Pinned in
+frame's fused noise (`stride_plan`, `stride_table` below; `check_stride` in vdx/options.py).  Each level costs its windows' UNet calls.  Pinned in
 tests/test_costride_gpu.py against tests/costride_ref.py, the stride itself by permuting the clip; NOT pinned and not claimed:
 no external implementation is pinned (the schedule is restated), and there is no quality claim on real Zeroscope weights, whose
 temporal layers were trained on consecutive frames and see faster motion in a strided window.
@@ -44,6 +44,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .options import MIN_TILE_CELLS, check_co_denoise, check_loop, check_stride, check_tile  # noqa: F401  (their home is vdx/options.py)
 from .planner import ChunkPlan, PlannerError, auto_chunk
 
 
@@ -90,14 +91,6 @@ def window_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
     if (total <= 0).any():
         raise ValueError(f"window_table: frame {int(np.argmin(total > 0))} is in no window")
     return WindowTable(tuple(fused), torch.from_numpy((raw / total).astype(np.float32)))
-
-
-def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
-    """`cfg.co_denoise`; `ValueError` before any work when it is asked for together with the halo exchange: every rank holds the
-    whole latent at every step anyway, there are no owned segments to return."""
-    if getattr(cfg, "co_denoise", False) and exchange == "halo":
-        raise ValueError("co_denoise needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
-    return bool(getattr(cfg, "co_denoise", False))
 
 
 # ---- ring windows (seamless looping; csrc/codenoise.hip, its RING flag) -----------------------------------------------------------------------------
@@ -155,32 +148,6 @@ def loop_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
     if (total <= 0).any():
         raise ValueError(f"loop_table: frame {int(np.argmin(total > 0))} is in no window")
     return WindowTable(tuple(fused), torch.from_numpy((raw / total).astype(np.float32)))
-
-
-def check_loop(cfg, exchange: str = "allgather", world: Optional[int] = None) -> bool:
-    """`cfg.loop`; `ValueError` before any work when the job cannot run it: ring windows exist only as co-denoising (the
-    windowed job's trajectories never meet before the blend), never with the halo exchange, not with `tile` (the tiled kernels
-    have no ring form yet), not with `guidance_rescale` (its statistics pass has none either), and not when `loop_plan` refuses
-    the plan (mode "fsdp", a chunk as long as the clip, no overlap, more windows than frames or than the fused step takes)."""
-    if not getattr(cfg, "loop", False):
-        return False
-    if not getattr(cfg, "co_denoise", False):
-        raise ValueError("loop needs co_denoise: ring windows meet at every step in the fused noise; the windowed job's blend has no ring form")
-    if exchange == "halo":
-        raise ValueError("loop needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
-    if getattr(cfg, "tile", None) is not None:
-        raise ValueError("loop and tile exclude each other: the tiled kernels have no ring form yet")
-    if getattr(cfg, "guidance_rescale", 0.0) != 0:
-        raise ValueError("loop and guidance_rescale exclude each other: the rescale's statistics pass has no ring form yet")
-    if world is None:
-        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-    try:
-        cp = loop_plan_of(cfg, world)
-    except PlannerError as err:
-        raise ValueError(f"loop: {err}") from None
-    if len(cp.ranges) > ops.COFUSE_MAX_WINDOWS:
-        raise ValueError(f"loop: {len(cp.ranges)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
-    return True
 
 
 # ---- strided context windows (AnimateDiff-Evolved's `context_stride`; csrc/codenoise.hip, its `costride_tab`) -----------------------
@@ -289,39 +256,6 @@ def stride_table(sp: StridePlan, T: int) -> StrideTable:
     return StrideTable(tuple(fused), torch.from_numpy(wn.astype(np.float32)))
 
 
-def check_stride(cfg, exchange: str = "allgather", world: Optional[int] = None) -> int:
-    """`cfg.context_stride`, the number of stride levels (1 = off: the job is then plain co-denoising or the windowed job, as
-    always); `ValueError` before any work when the job cannot run it: strided windows exist only as co-denoising, never with the
-    halo exchange, not with `tile`, `loop` or `guidance_rescale` (none has a strided form yet), and not when `stride_plan` refuses
-    the plan or the fused step cannot take its windows."""
-    levels = getattr(cfg, "context_stride", 1)
-    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 1:
-        raise ValueError(f"context_stride: the number of stride levels must be an integer >= 1, got {levels!r}")
-    if levels == 1:
-        return 1
-    if not getattr(cfg, "co_denoise", False):
-        raise ValueError("context_stride needs co_denoise: strided windows meet the others at every step in the fused noise; "
-                         "the windowed job's blend has no strided form")
-    if exchange == "halo":
-        raise ValueError("context_stride needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
-    if getattr(cfg, "tile", None) is not None:
-        raise ValueError("context_stride and tile exclude each other: the tiled kernels have no strided form yet")
-    if getattr(cfg, "loop", False):
-        raise ValueError("context_stride and loop exclude each other: ring windows have no strided form yet")
-    if getattr(cfg, "guidance_rescale", 0.0) != 0:
-        raise ValueError("context_stride and guidance_rescale exclude each other: the rescale's statistics pass has no strided form yet")
-    if world is None:
-        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-    try:
-        sp = stride_plan_of(cfg, world)
-    except PlannerError as err:
-        raise ValueError(f"context_stride: {err}") from None
-    fused = len(set(sp.windows))
-    if fused > ops.COFUSE_MAX_WINDOWS:
-        raise ValueError(f"context_stride: {fused} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
-    return levels
-
-
 # ---- spatial tiles (MultiDiffusion's original form; csrc/cotile.hip) ------------------------------------------------------------
 def tile_starts(n: int, tile: int, overlap: int) -> List[int]:
     """First cells of the tiles of `tile` cells that cover `n` cells: 0, tile - overlap, 2 (tile - overlap), ..., the last one
@@ -393,51 +327,6 @@ def tile_plan(h: int, w: int, th: int, tw: int, oy: int, ox: int) -> TilePlan:
     return TilePlan(th, tw, oy, ox, tuple(ys), tuple(xs), axis_weights(h, th, oy, ys), axis_weights(w, tw, ox, xs))
 
 
-MIN_TILE_CELLS = 8   # 2^(levels - 1) of the four-level UNet: below it the deepest level is a single ceil-rounded cell per side
-
-
-def check_tile(cfg, exchange: str = "allgather") -> Optional[Tuple[int, int, int, int]]:
-    """`cfg.tile` / `cfg.tile_overlap` (pixels) as (th, tw, oy, ox) in latent cells, None when off; `ValueError` before any work
-    when the job cannot run it: tiling exists only as co-denoising (the windowed job's ramp blend has no spatial form), never
-    with the halo exchange, not with `guidance_rescale` (its statistics pass has no tiled fuse yet); a tile is two multiples of 8
-    pixels, no larger than the frame and no smaller than the UNet takes for a frame (`MIN_TILE_CELLS` latent cells a side); the
-    overlap, multiples of 8 pixels too, lies in [0, tile) per axis and defaults to a quarter of the tile in latent cells."""
-    tile, ov = getattr(cfg, "tile", None), getattr(cfg, "tile_overlap", None)
-    if tile is None:
-        if ov is not None:
-            raise ValueError("tile_overlap needs tile")
-        return None
-
-    def pair(v, what):
-        if not isinstance(v, (tuple, list)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, int) for x in v):
-            raise ValueError(f"{what} must be two integers (pixels), got {v!r}")
-        if any(x % 8 for x in v):
-            raise ValueError(f"{what} {tuple(v)} must be multiples of 8 pixels (one latent cell)")
-        return v[0] // 8, v[1] // 8
-
-    if not getattr(cfg, "co_denoise", False):
-        raise ValueError("tile needs co_denoise: tiles meet at every step in the fused noise; the windowed job's blend has no tiled form")
-    if exchange == "halo":
-        raise ValueError("tile needs exchange=\"allgather\": every rank holds the whole clip's latent at every step")
-    if getattr(cfg, "guidance_rescale", 0.0) != 0:
-        raise ValueError("tile and guidance_rescale exclude each other: the rescale's statistics pass has no tiled form yet")
-    th, tw = pair(tile, "tile")
-    h, w = cfg.height // 8, cfg.width // 8
-    if cfg.height % 8 or cfg.width % 8:
-        raise ValueError(f"tile: the frame {cfg.height}x{cfg.width} must be a multiple of 8 pixels")
-    if th > h or tw > w:
-        raise ValueError(f"tile {tuple(tile)} is larger than the frame {cfg.height}x{cfg.width}")
-    if th < MIN_TILE_CELLS or tw < MIN_TILE_CELLS:
-        raise ValueError(f"tile {tuple(tile)} is smaller than the UNet takes for a frame: {MIN_TILE_CELLS * 8} pixels a side at least")
-    oy, ox = (th // 4, tw // 4) if ov is None else pair(ov, "tile_overlap")
-    if not (0 <= oy < th and 0 <= ox < tw):
-        raise ValueError(f"tile_overlap {(oy * 8, ox * 8)} must lie in [0, tile) per axis, tile is {tuple(tile)}")
-    ny, nx = len(tile_starts(h, th, oy)), len(tile_starts(w, tw, ox))
-    if ny * nx > ops.COTILE_MAX_TILES:
-        raise ValueError(f"tile {tuple(tile)}: {ny} x {nx} tiles, the fused step takes {ops.COTILE_MAX_TILES}")
-    return th, tw, oy, ox
-
-
 def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[TilePlan] = None, strided: Optional[StridePlan] = None):
     """One co-denoised sampling round of `d` (a `DistributedVideoDiffuser`) from the whole clip's start latent -> (z.float(),
     the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  Per step: this rank's windows go
@@ -460,7 +349,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
-    loop = bool(getattr(cfg, "loop", False))
+    loop = bool(cfg.loop)
     if strided is not None:
         cp = strided                                              # the same names: chunk, per_rank, for_rank
         table = stride_table(strided, T)

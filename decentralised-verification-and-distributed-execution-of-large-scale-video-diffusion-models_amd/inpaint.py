@@ -89,7 +89,7 @@ def expand_mask(arr: np.ndarray, T: int, H: int, W: int, what: str = "mask") -> 
 
 
 def masked(cfg) -> bool:
-    return getattr(cfg, "mask", None) is not None or getattr(cfg, "keep_frames", None) is not None
+    return cfg.mask is not None or cfg.keep_frames is not None
 
 
 def pixel_mask(cfg) -> Optional[np.ndarray]:
@@ -120,7 +120,7 @@ def check_mask(cfg, exchange: str = "allgather") -> Optional[np.ndarray]:
     mask without `init_video`, `mask` together with `keep_frames`, the halo exchange (the paste needs the whole blend on every
     rank), a rule that is not one, a mask of another shape, or a mask that regenerates nothing."""
     if not masked(cfg):
-        if getattr(cfg, "mask_rule", "nearest") not in MASK_RULES:
+        if cfg.mask_rule not in MASK_RULES:
             raise ValueError(f"mask_rule must be one of {MASK_RULES}, got {cfg.mask_rule!r}")
         return None
     if cfg.mask is not None and cfg.keep_frames is not None:

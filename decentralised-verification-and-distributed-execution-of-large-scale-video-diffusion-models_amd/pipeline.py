@@ -33,9 +33,11 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .codenoise import check_co_denoise, check_loop, check_stride, check_tile, co_denoise_round, loop_plan_of, stride_plan_of, tile_plan
-from .inpaint import check_mask, known_coefficients, mask_record
+from .codenoise import co_denoise_round, loop_plan_of, tile_plan
+from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
+from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
+from .options import info_options, record_options, resolve, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -177,59 +179,6 @@ def iteration_noise(shape, iteration: int, device, noise_device=None):
     return torch.randn(*shape, generator=g, device=nd, dtype=torch.float32).to(device)
 
 
-def check_free_init(cfg, exchange: str = "allgather") -> int:
-    """`cfg.free_init_iters` when the job can run it; `ValueError` otherwise, before any work: the count is an integer >= 1,
-    and with more than one iteration the filter's arguments are valid, the exchange is "allgather" (every rank must hold the
-    whole blend to re-noise it) and there is no `init_video` (video-to-video starts from a clip, not from noise)."""
-    k = cfg.free_init_iters
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise ValueError(f"free_init_iters must be an integer >= 1, got {k!r}")
-    if k > 1:
-        from .freeinit import check_filter_args
-        check_filter_args(cfg.free_init_method, cfg.free_init_spatial, cfg.free_init_temporal, cfg.free_init_order)
-        if exchange == "halo":
-            raise ValueError("free_init_iters > 1 needs exchange=\"allgather\": with \"halo\" no rank holds the whole blended latent")
-        if cfg.init_video is not None:
-            raise ValueError("free_init_iters > 1 and init_video exclude each other: FreeInit re-initialises a start from pure noise")
-    return k
-
-
-def check_freeu(cfg) -> Optional[dict]:
-    """`cfg.freeu` as {"b1", "b2", "s1", "s2"} (None when off); `ValueError` before any work unless it is four finite numbers
-    with b1, b2 > 0 (s may be any finite number: 0 removes the band)."""
-    if cfg.freeu is None:
-        return None
-    v = tuple(cfg.freeu) if isinstance(cfg.freeu, (tuple, list)) else ()
-    if len(v) != 4:
-        raise ValueError(f"freeu must be four numbers (b1, b2, s1, s2), got {cfg.freeu!r}")
-    rec = {}
-    for name, x, positive in zip(("b1", "b2", "s1", "s2"), v, (True, True, False, False)):
-        rec[name] = ops._freeu_number(f"freeu: {name}", x, positive)
-    return rec
-
-
-def check_guidance_rescale(cfg) -> float:
-    """`cfg.guidance_rescale` as a float (0.0 when off); `ValueError` before any work unless it is a finite number in [0, 1], and
-    when it is non-zero with `guidance_scale <= 1`: the job still runs the CFG combine there, as the reference does, but the
-    guided noise then lies between the two predictions and rescale has nothing to correct, so refuse rather than guess."""
-    phi = cfg.guidance_rescale
-    ops.rescale_factors(phi)
-    if phi != 0 and not cfg.guidance_scale > 1:
-        raise ValueError(f"guidance_rescale {phi!r} needs guidance_scale > 1, got {cfg.guidance_scale!r}")
-    return float(phi)
-
-
-def check_tome(cfg) -> Optional[dict]:
-    """`cfg.tome` / `cfg.tome_seed` as {"ratio", "sx", "sy", "seed", "max_downsample"} (None when off); `ValueError` before any work
-    for a ratio `enable_tome` refuses, or a seed without a ratio."""
-    if cfg.tome is None:
-        if cfg.tome_seed is not None:
-            raise ValueError("tome_seed needs tome")
-        return None
-    from .tome import check_params
-    return check_params(cfg.tome, seed=cfg.tome_seed)
-
-
 SCHEDULERS = ("ddim", "dpmpp_2m")
 
 
@@ -320,9 +269,6 @@ class DistributedVideoDiffuser:
         if check_free_init(cfg) > 1 and init_latents is not None:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
-        self._co_rec: List[dict] = []                              # co_denoise: the rounds' records of the last call
-        self._tiles = None                                         # tile: the spatial plan of the last call
-        self._stride = None                                        # context_stride > 1: the strided plan of the last call
         self.rank, self.world = _world()
         self.unet, self.scheduler = unet, scheduler
         self.uncond_emb, self.cond_emb = uncond_emb, cond_emb
@@ -398,7 +344,7 @@ class DistributedVideoDiffuser:
 
     def plan(self) -> ChunkPlan:
         cfg = self.cfg
-        if getattr(cfg, "loop", False):     # ring windows of one length; a range's end may exceed num_frames (codenoise.loop_plan)
+        if cfg.loop:                        # ring windows of one length; a range's end may exceed num_frames (codenoise.loop_plan)
             return loop_plan_of(cfg, self.world)
         return plan(cfg.num_frames, self.world, cfg.chunk_size, cfg.overlap, cfg.no_chunking, cfg.overlap_rule)
 
@@ -435,15 +381,15 @@ class DistributedVideoDiffuser:
         if torch.device(self.cfg.device).type == "cuda":
             torch.cuda.synchronize()
 
-    def _round(self, start: torch.Tensor, cp: ChunkPlan, exchange: str, comm):
+    def _round(self, start: torch.Tensor, cp: ChunkPlan, exchange: str, comm, co_recs: Optional[list] = None, tiles=None, strided=None):
         """One sampling round from the whole clip's start latent `start`: denoise this rank's windows, exchange, blend
         -> (the blend: the latent, or with "halo" the owned segments; that round's seconds and bytes, under `info`'s names).
-        With `cfg.co_denoise` the round is `codenoise.co_denoise_round` instead: one latent, the windows meet at every step, no
-        blend; its record is added to `self._co_rec`."""
-        if self.cfg.co_denoise:
-            out, spent, rec = co_denoise_round(self, start, cp, *((self._tiles,) if self._tiles is not None else ()),
-                                               **({"strided": self._stride} if self._stride is not None else {}))
-            self._co_rec.append(rec)
+        `co_recs` (`co_denoise`; the call's list of its rounds' records): the round is `codenoise.co_denoise_round` instead, with
+        the call's `tiles` (a `TilePlan`) and `strided` (a `StridePlan`) where it has them: one latent, the windows meet at every
+        step, no blend; its record is added to `co_recs`."""
+        if co_recs is not None:
+            out, spent, rec = co_denoise_round(self, start, cp, tiles, strided)
+            co_recs.append(rec)
             return out, spent
         _, C, T, H, W = start.shape
         t0 = time.time()
@@ -479,76 +425,34 @@ class DistributedVideoDiffuser:
         return out, {"denoise_s": denoise_s, "emu_gather_delay_s": delay, "net_gather_s": net_gather_s, "network_bytes": received,
                      "payload_bytes": payload, "payload_bytes_actual": sum(t.numel() * 2 for t in mine)}
 
-    def __call__(self, exchange: str = "allgather", comm=None):
+    def __call__(self, exchange: str = "allgather", comm=None, options: Optional[JobOptions] = None):
         """exchange="allgather": every rank ends with the whole blended latent (reference semantics, :201-217)
         -> (lat fp32 (1,C,T,h,w), info).  exchange="halo": a rank ends with the frames it owns
         -> ([(s, e, lat fp32 (1,C,e-s,h,w))], info) — the same bits, 1/world of the blend and decode work.
         `comm` (vdx.comm.Comm): the halo transfers go through the C-ABI RCCL entry point instead of torch.distributed.
+        `options`: the job's `options.resolve`d options (`run_job` has them); None: the call resolves, and so validates, itself.
 
-        `free_init_iters` > 1 ("allgather" only): that many rounds, with `freeinit.reinit` between (vdx/freeinit.py).  Iteration
-        0 starts from the base noise exactly as a job without the option; the start of iteration i >= 1 is again one tensor for
-        the whole clip that every window slices, computed by every rank for itself from the whole blend it holds (identical
-        bits, no collective); with `hybrid_ctx` its frame-mean is that iteration's context (the rule video-to-video uses for its
-        start latent).  The seconds, bytes and emulated delays in `info` are then sums over the iterations, and
-        `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`.
-
-        `freeu` (every exchange, mode and scheduler, every FreeInit iteration): the UNet samples with
-        `enable_freeu(s1, s2, b1, b2)` for the length of the call and is handed back in the state it came in; `info["freeu"]`
-        holds the four values.
-
-        `co_denoise` ("allgather" only; every mode and scheduler, `init_latents`, every FreeInit iteration, `freeu`): each round
-        is `codenoise.co_denoise_round`, and the result is that round's latent as fp32, with no blend after it.  The exchange
-        then happens once per STEP: `network_bytes`, `net_gather_s`, `payload_bytes` and the emulated delays are sums over the
-        steps (and the iterations), and `info["co_denoise"]` = {"windows": windows in the fuse, "steps": steps run,
-        "exchange_s": seconds in the per-step gathers, "bytes_per_step": bytes this rank receives per step}.
-
-        `latent_mask` ("allgather" only; both samplers, windowed and `co_denoise`, every mode): the constructor's docstring; `info`
-        is the one of the job without it.
-
-        `guidance_rescale` != 0 (every exchange, mode, sampler and option above; the mask step runs after the rescaled step,
-        untouched): every scheduler step rescales its guided noise (vdx/scheduler.py `step_cfg`), the statistic being that of
-        the sample the step advances, a window's latent or with `co_denoise` the whole clip's, so no collective is added;
-        `info["guidance_rescale"]` holds the value.
-
-        `tile` (with `co_denoise` only; both samplers, every mode, `init_latents`, `latent_mask`, every FreeInit iteration, `freeu`;
-        refused with "halo" and with `guidance_rescale`): every window of every round is run once per spatial tile
-        (`codenoise.tile_plan`; with `hybrid_ctx` each tile reads its crop of the whole frame's context) and the fused step
-        averages over time x row x column windows; `info["tile"]` = {"tile": [th, tw], "overlap": [oy, ox] (latent cells),
-        "grid": [ny, nx], "windows": fused windows in all}.  A tile equal to the frame is plain co-denoising, bit for bit.
-
-        `loop` (with `co_denoise` only; both samplers, every chunked mode, `init_latents`, `latent_mask`, every FreeInit iteration,
-        `freeu`; refused with "halo", `tile`, `guidance_rescale` and a plan `codenoise.loop_plan` refuses, mode "fsdp" among
-        them): the windows of every round lie on a ring (`codenoise.loop_plan` / `loop_table`, `ops.cfg_input_loop`,
-        `step_cfg_loop`); `info["ranges"]` holds each window clipped to the clip, (s, min(e, T)), and `info["loop"]` =
-        {"windows": [[first frame, length], ...]}.
-
-        `context_stride` > 1 (with `co_denoise` only; both samplers, every mode, `init_latents`, `latent_mask`, every FreeInit
-        iteration, `freeu`, `tome`; refused with "halo", `tile`, `loop`, `guidance_rescale` and a plan `codenoise.stride_plan`
-        refuses): every round also denoises the strided windows of `codenoise.stride_plan` (`ops.cfg_input_stride`,
-        `step_cfg_strided`); `info["ranges"]`, `info["chunk_size"]` and `info["overlap"]` stay the level-0 plan's, and
-        `info["co_denoise"]` and `info` gain `"context_stride"` = {"levels", "strides", "windows": [[s, L, d], ...]}."""
+        What each option does stands in `DiffuserConfig`'s field comments, what goes with what in vdx/options.py (`RULES`, the
+        `check_*`).  `info` holds the plan (`chunk_size`, `overlap`, `ranges`: with `loop` each window clipped to the clip, with
+        `context_stride` the level-0 plan's), the seconds and bytes of the rounds, `owned` with "halo", and one entry per option
+        that is on (`freeu`, `tome`, `free_init`, `options.info_options`).  With `free_init_iters` > 1 the seconds, bytes and
+        emulated delays are sums over the iterations, `info["free_init"]` holds the per-iteration `denoise_s` and `reinit_s`, and
+        the UNet is handed back in the FreeU / ToMe state it came in.  With `co_denoise` the exchange happens once per STEP:
+        `network_bytes`, `net_gather_s`, `payload_bytes` and the emulated delays are then sums over the steps too."""
         cfg = self.cfg
-        co = check_co_denoise(cfg, exchange)
-        tile = check_tile(cfg, exchange)
-        loop = check_loop(cfg, exchange, self.world)
-        levels = check_stride(cfg, exchange, self.world)
-        self._stride = stride_plan_of(cfg, self.world) if levels > 1 else None
-        self._tiles = tile_plan(cfg.height // 8, cfg.width // 8, *tile) if tile is not None else None
+        opts = options or resolve(cfg, exchange, self.world)
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
-        self._co_rec = []
-        iters = check_free_init(cfg, exchange)
-        freeu = check_freeu(cfg)
-        tome = check_tome(cfg)
-        if exchange not in ("allgather", "halo"):
-            raise ValueError(f"unknown exchange {exchange!r}")
+        iters, freeu, tome = opts.free_init_iters, opts.freeu, opts.tome
+        tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
+        co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
         if self._start is None:
             base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
         else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
             base = self._start
         T = cfg.num_frames
-        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": [(s, min(e, T)) for s, e in cp.ranges] if loop else list(cp.ranges),
+        info = {"chunk_size": cp.chunk, "overlap": cp.overlap, "ranges": [(s, min(e, T)) for s, e in cp.ranges] if opts.loop else list(cp.ranges),
                 "world_size": self.world,
                 "num_frames": cfg.num_frames, "denoise_s": 0.0, "exchange": exchange, "steps_run": len(self.schedule),
                 "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0, "payload_bytes_actual": 0}
@@ -570,7 +474,7 @@ class DistributedVideoDiffuser:
             info["tome"] = tome
         try:
             for it in range(iters):
-                out, spent = self._round(start, cp, exchange, comm)
+                out, spent = self._round(start, cp, exchange, comm, co_recs, tiles, opts.stride_plan)
                 for k, v in spent.items():
                     info[k] += v
                 if iters > 1:
@@ -594,18 +498,7 @@ class DistributedVideoDiffuser:
             info["free_init"] = rec
         if exchange == "halo":
             info["owned"] = [(s, e) for s, e, _ in out]
-        if self._rescale_kw:
-            info.update(self._rescale_kw)
-        if co:
-            info["co_denoise"] = {"windows": self._co_rec[0]["windows"], "steps": sum(r["steps"] for r in self._co_rec),
-                                  "exchange_s": sum(r["exchange_s"] for r in self._co_rec),
-                                  "bytes_per_step": self._co_rec[0]["bytes_per_step"]}
-            if tile is not None:
-                info["tile"] = self._co_rec[0]["tile"]
-            if loop:
-                info["loop"] = self._co_rec[0]["loop"]
-            if levels > 1:
-                info["context_stride"] = info["co_denoise"]["context_stride"] = self._co_rec[0]["context_stride"]
+        info.update(info_options(opts, co_recs))
         return out, info
 
 
@@ -614,84 +507,9 @@ class DistributedVideoDiffuser:
 # ---------------------------------------------------------------------------------------------
 def build_arg_parser():
     """The reference's argparse, flag for flag and default for default (`fsdp_chunked_coherent.py:281-300`) — the sweep script
-    `Distribution/full_experiments_ZeroscopeXL.sh` drives the job through these.  Two additions, both off by default:
-    `--exchange` (allgather | halo, the module docstring) and `--noise_device` (parity runs generate the seeded noise on the CPU).
-    Two more, also off by default: `--clip_json` scores the decoded frames with the validator's CLIP quality score
-    (vdx/clip_score.py) on rank 0 and writes it there; `--clip_model` names the scorer's weights (a local directory in
-    transformers layout; without it, seeded synthetic ViT-B/32 weights, recorded as such).  `--mdvqs_json` does the same with
-    the validator's MD-VQS record (vdx/mdvqs.py: PF, VQ, TC, the weighted total and the authenticity gate); `--lpips_model`
-    names the LPIPS weights (a local file in the `lpips` state-dict layout; without it, seeded synthetic ones).  `--gpu_flow`
-    computes the Farneback flow behind `flow_err` and behind MD-VQS' TC in HIP kernels (vdx/flow.py) instead of on the host;
-    the MD-VQS record then carries `"flow": "gpu"`.  `--video_restart_rows N` writes the mp4's JPEG frames with a restart marker
-    every N MCU rows (vdx/compat/cv2_shim.py), and `--score_from_file` makes `--clip_json` / `--mdvqs_json` score the frames
-    decoded back from the written mp4 on the GPU (vdx/video.py: what a validator holding the file would score) instead of the
-    frames in memory; the records then carry `"source": "file"`.  `--gpu_video_write` encodes the mp4's JPEG frames in HIP
-    kernels (vdx/video.py `write_frames`, csrc/mjpeg_enc.hip) instead of in Pillow on the host: the same file byte for byte,
-    with or without `--video_restart_rows`.  `--scheduler dpmpp_2m` samples with DPM-Solver++ 2M (vdx/scheduler.py
-    `DPMSolverMultistepScheduler`, built from the pipeline scheduler's config) instead of DDIM; `--scheduler ddim`, the default,
-    is the run without the flag.  `--interpolate N` (no reference counterpart) writes the mp4 with N - 1 motion-compensated
-    frames between every two generated ones (vdx/interp.py, csrc/interp.hip), (F - 1) N + 1 frames at fps N; the row's numbers
-    and the frames `--clip_json` / `--mdvqs_json` score stay those of the generated frames, unless `--score_from_file` asks for
-    what the file holds; `--interpolate 1`, the default, is the run without the flag.  `--compare_to PATH --compare_json OUT`
-    (no reference counterpart; both or neither) compares the generated frames with the clip at PATH (a `.npy` of uint8 frames
-    or a Motion-JPEG mp4) on rank 0 after the row is written and writes the PSNR / SSIM / MS-SSIM record of vdx/compare.py,
-    with the job's chunk ranges (so the means at the seams and away from them) and `"compare_to": PATH`, to OUT; a missing PATH
-    or a `.npy` of another shape is refused before any model is loaded.  `--free_init N` (no reference counterpart; diffusers'
-    `enable_free_init`, unpinned) runs N sampling passes, re-initialising the start of each from the blended latent of the one
-    before (vdx/freeinit.py, csrc/freeinit.hip): noised back to t = 999 with the same base noise, its low frequencies kept
-    (`--free_init_method` butterworth | gaussian | ideal, stop frequencies `--free_init_spatial` / `--free_init_temporal`,
-    `--free_init_order`), the high ones from fresh noise; the row's `latency_s` covers all passes; refused with `--exchange halo`
-    and with `--init_video`; `--free_init 1`, the default, is the run without the flag.  `--freeu B1 B2 S1 S2` (no reference
-    counterpart; diffusers' `enable_freeu(s1, s2, b1, b2)`, unpinned) samples every step of the job, whatever the mode, exchange,
-    scheduler and the other options, with FreeU in the UNet's up blocks 0 and 1 (vdx/unet3d.py `enable_freeu`, csrc/freeu.hip):
-    the first half of the hidden state's channels times B, the skip tensors' lowest frequencies times S; the result and the
-    JSON records then carry `"freeu": {"b1", "b2", "s1", "s2"}`; without the flag the run is the one it always was.
-    `--tome RATIO [--tome_seed N]` (no reference counterpart; `tomesd.apply_patch(ratio, max_downsample=1, sx=2, sy=2)`, unpinned)
-    samples every step of the job, whatever the mode, exchange, scheduler and the other options, with token merging around the
-    level-0 spatial self-attentions (vdx/unet3d.py `enable_tome`, csrc/tome.hip): int(S RATIO) of an image's S tokens are merged
-    into their most similar destination before the attention and read its row back after; the result and the JSON records
-    then carry `"tome": {"ratio", "sx", "sy", "seed", "max_downsample"}`; without the flag the run is the one it always was.
-    `--co_denoise` (no reference counterpart; MultiDiffusion along time, unpinned) samples ONE latent for the whole clip: at every
-    step the windows' noise predictions are averaged where they overlap and one scheduler step advances the clip (vdx/codenoise.py,
-    csrc/codenoise.hip), so there is one exchange per step instead of one per job and no blend at the end; every mode, scheduler
-    and the other options; refused with `--exchange halo`; the result and the JSON records then carry `"co_denoise"`; without the
-    flag every launch, byte, CSV row and record is the one it always was.
-    `--mask PATH` / `--keep_frames SPEC` (no reference counterpart; the replacement method, RePaint, diffusers' inpainting branch
-    for 4-channel UNets, unpinned; needs `--init_video`, one of the two) hold part of that clip fixed and generate the rest
-    (vdx/inpaint.py, csrc/inpaint.hip): PATH is a `.npy` of uint8 / bool shaped (T,H,W), (H,W) or (T,) at the job's size, nonzero =
-    regenerate; SPEC is comma-separated Python-style slices or indices of the frames to KEEP ("0:8,20:24").  `--mask_rule nearest`
-    (default: pixel (8y, 8x) decides a latent cell) | `any` (a cell regenerates if any of its 64 pixels does).  After every
-    scheduler step the kept latent cells are set to the clip's latent noised to the next timestep, after the blend to the clip's
-    latent itself, and with `--mask_paste on` (default) the written frames' kept pixels are the input's bytes (`off`: the
-    decoder's).  Refused with `--exchange halo` and when nothing is left to regenerate; the result and the JSON records then
-    carry `"mask": {"rule", "paste", "kept_fraction", "kept_frames"}`; without the flags every launch, byte, CSV row and record
-    is the one it always was.
-    `--negative_prompt TEXT` (diffusers' `negative_prompt`) is the text of the unconditional branch of classifier-free guidance
-    instead of the empty prompt; CLIP and MD-VQS prompt fidelity keep scoring against `--prompt` alone.  `--guidance_rescale PHI`
-    (Lin et al. 2023; diffusers' `guidance_rescale`, unpinned) rescales the guided noise of every step towards the conditional
-    prediction's standard deviation (vdx/scheduler.py, csrc/rescale.hip): PHI in [0, 1], refused with `--guidance_scale` <= 1; every
-    mode, exchange, scheduler and the other options.  The result and the JSON records then carry `"negative_prompt"` /
-    `"guidance_rescale"`; without the flags every launch, byte, CSV row and record is the one it always was.
-    `--tile TH TW` (with `--co_denoise`; no reference counterpart; MultiDiffusion along space, unpinned) runs the UNet on overlapping
-    TH x TW pixel tiles of the frame instead of the whole frame, at every step, and averages the tiles' noise predictions where
-    they overlap in the same fused step that averages the time windows (vdx/codenoise.py `tile_plan`, csrc/cotile.hip), so a frame
-    can be larger than the size the UNet was trained at while a UNet call keeps a tile's memory; `--tile_overlap OY OX` (pixels,
-    default a quarter of the tile); all multiples of 8; refused without `--co_denoise`, with `--exchange halo` and with
-    `--guidance_rescale`; the frames are then decoded in smaller batches; the result and the JSON records carry `"tile"`; without
-    the flag every launch, byte, CSV row and record is the one it always was.
-    `--loop` (with `--co_denoise`; no reference counterpart; AnimateDiff's `closed_loop` context option, unpinned) makes the clip a
-    seamless loop: the windows lie on a ring, the last wrapping over the clip's end into its first frames (vdx/codenoise.py
-    `loop_plan`, csrc/codenoise.hip, its RING flag), so frames T-1 and 0 are denoised together in one UNet call at every step; `--interpolate N`
-    then also fills the pair (T-1, 0) and writes T N frames; refused without `--co_denoise`, with `--exchange halo`, `--tile`,
-    `--guidance_rescale`, `--mode fsdp` and a chunk as long as the clip; the result and the JSON records carry `"loop"`:
-    {"windows", "wrap_l1", "mean_l1"}; without the flag every launch, byte, CSV row and record is the one it always was.
-    `--context_stride N` (with `--co_denoise`; no reference counterpart; AnimateDiff-Evolved's `context_stride`, the "uniform" context
-    schedule, unpinned) adds, beside the windows of consecutive frames, windows that take every 2nd, 4th, ... 2^(N-1)-th frame
-    (vdx/codenoise.py `stride_plan`, csrc/codenoise.hip, its `costride_tab`), so frames further apart than a window are denoised
-    together in one UNet call at every step; every level has an equal share of the fused noise and costs its windows' UNet calls;
-    refused without `--co_denoise`, with `--exchange halo`, `--tile`, `--loop`, `--guidance_rescale` and when 2^N exceeds the clip;
-    the result and the JSON records carry `"context_stride"`: {"levels", "strides", "windows"}; with N = 1, the default, every
-    launch, byte, CSV row and record is the one it always was."""
+    `Distribution/full_experiments_ZeroscopeXL.sh` drives the job through these.  Every flag beyond the reference's is off by
+    default, and without it every launch, byte, CSV row and record is the one it always was: what an option does stands in
+    `DiffuserConfig`'s field comments and, flag by flag; what goes with what in vdx/options.py."""
     import argparse
     p = argparse.ArgumentParser(description="hybrid FSDP + frame-chunked video denoising on the HIP path")
     p.add_argument("--model_id", default="cerspense/zeroscope_v2_XL")
@@ -901,24 +719,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     from . import metrics
     from .compat.diffusers_shim import DiffusionPipeline
     from .compat import pynvml_shim
-    from .interp import check_factor
-    factor = check_factor(cfg.interpolate)      # refused before anything is loaded
-    free_init_iters = check_free_init(cfg, exchange)
-    freeu = check_freeu(cfg)
-    tome = check_tome(cfg)
-    co = check_co_denoise(cfg, exchange)
-    tile = check_tile(cfg, exchange)            # None: the option is off
-    if tome is not None:                        # the UNet's frame is a tile where tiling is on, else the whole latent frame
-        from .tome import check_grid
-        check_grid(*((tile[0], tile[1]) if tile is not None else (cfg.height // 8, cfg.width // 8)), tome)
-    loop = check_loop(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
-    levels = check_stride(cfg, exchange, dist.get_world_size() if dist.is_initialized() else int(os.environ.get("WORLD_SIZE", 1)))
-    pixel_mask = check_mask(cfg, exchange)      # None: the option is off
-    phi = check_guidance_rescale(cfg)
-    if not isinstance(cfg.negative_prompt, str):
-        raise ValueError(f"negative_prompt must be a string, got {cfg.negative_prompt!r}")
-    guidance = {**({"negative_prompt": cfg.negative_prompt} if cfg.negative_prompt else {}),
-                **({"guidance_rescale": phi} if phi != 0 else {})}       # the two keys the result and the records gain
+    opts = resolve(cfg, exchange, world_size(env=True), job=True)        # every refusal, before anything is loaded
+    factor, loop, pixel_mask = opts.interpolate, opts.loop, opts.pixel_mask
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
         # VDX_DIST_BACKEND=gloo + VDX_SHARE_GPU=1 let several ranks of a real multi-process job compute on ONE GPU
@@ -949,7 +751,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
         init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
     d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents,
                                  **masking)
-    out, info = d(exchange=exchange)
+    out, info = d(exchange=exchange, options=opts)
     ranges = info["ranges"]
     if exchange == "allgather":
         paste = {"paste": (originals.contiguous(), pixel_mask)} if pixel_mask is not None and cfg.mask_paste else {}
@@ -990,6 +792,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     if d.rank == 0 and clip_inputs is not None:
         # what `clip_score_record` needs, handed to the caller: the score runs outside the job (and outside main()'s timing)
         clip_inputs.update(frames=frames, tokenizer=tok, device=dev, ranges=ranges)
+    # the options' entries: what the call recorded in `info`, the mask's record, the guidance keys
+    mask = {"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}
     return {"world_size": d.world, "chunk_size": info["chunk_size"], "overlap": info["overlap"], "num_frames": cfg.num_frames,
             "peak_vram_mb": peak_mb, "end_vram_mb": int(end_mb), "network_bytes": int(info["payload_bytes"]),
             "net_gather_s": info["net_gather_s"], "net_reduce_s": reduce_s, "temp_instab": temp_instab, "flow_err": flow_err,
@@ -997,11 +801,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "emu_gather_delay_s": info["emu_gather_delay_s"], "emu_reduce_delay_s": delay,
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
-            **({"free_init": info["free_init"]} if free_init_iters > 1 else {}), **({"freeu": freeu} if freeu is not None else {}),
-            **({"tome": tome} if tome is not None else {}),
-            **({"co_denoise": info["co_denoise"]} if co else {}), **({"tile": info["tile"]} if tile is not None else {}),
-            **({"loop": info["loop"]} if loop else {}), **({"context_stride": info["context_stride"]} if levels > 1 else {}),
-            **({"mask": mask_record(d.latent_mask, cfg.mask_rule, cfg.mask_paste)} if pixel_mask is not None else {}), **guidance}
+            **({"free_init": info["free_init"]} if "free_init" in info else {}),
+            **record_options({**info, **mask, **opts.guidance})}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -1030,21 +831,7 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {"freeu": res["freeu"]} if "freeu" in res else {}
-        if "tome" in res:
-            source["tome"] = res["tome"]
-        if "co_denoise" in res:
-            source["co_denoise"] = res["co_denoise"]
-        if "tile" in res:
-            source["tile"] = res["tile"]
-        if "loop" in res:
-            source["loop"] = res["loop"]
-        if "context_stride" in res:
-            source["context_stride"] = res["context_stride"]
-        if "mask" in res:
-            source["mask"] = res["mask"]
-        guidance = {k: res[k] for k in ("negative_prompt", "guidance_rescale") if k in res}
-        source.update(guidance)
+        source = record_options(res)
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -1064,21 +851,7 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            if "freeu" in res:
-                rec["freeu"] = res["freeu"]
-            if "tome" in res:
-                rec["tome"] = res["tome"]
-            if "co_denoise" in res:
-                rec["co_denoise"] = res["co_denoise"]
-            if "tile" in res:
-                rec["tile"] = res["tile"]
-            if "loop" in res:
-                rec["loop"] = res["loop"]
-            if "context_stride" in res:
-                rec["context_stride"] = res["context_stride"]
-            if "mask" in res:
-                rec["mask"] = res["mask"]
-            rec.update(guidance)
+            rec.update(record_options(res))
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

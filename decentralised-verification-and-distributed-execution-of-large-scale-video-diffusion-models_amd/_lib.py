@@ -204,6 +204,10 @@ SIGNATURES = {
     "vdx_tome_select": (_i, [C.POINTER(TomeArgs), _vp]),
     "vdx_tome_merge_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp, _i, _vp]),
     "vdx_tome_unmerge_add_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp, _i, _vp, _i, _vp]),
+    # prompt travel: a window's per-frame text and K5's key / value blobs in one launch each (no reference counterpart; vdx/travel.py,
+    # csrc/travel.hip)
+    "vdx_text_travel_f16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_cross_attn_block_pack_kv_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

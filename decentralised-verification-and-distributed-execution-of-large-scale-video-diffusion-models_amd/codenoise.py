@@ -345,7 +345,9 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     `strided` (a `StridePlan` of more than one level; `cp` is its level 0): the windows, their ranks and the slot (sized by the
     longest window) are the strided plan's, the table is `stride_table`'s, a window's input comes from `ops.cfg_input_stride`
     (frames `s + f * d`), the step is `step_cfg_strided`, and the record gains `"context_stride"`: the levels, their strides and
-    the fused windows as [s, L, d]; still one gather per step, and the mask step on the whole clip as without it."""
+    the fused windows as [s, L, d]; still one gather per step, and the mask step on the whole clip as without it.
+    `d.travel` (prompt travel, vdx/travel.py): every window is called with its own text, `d.window_text` of its (s, L, d, ring),
+    built once; every tile of a window shares the window's text; nothing else changes."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
@@ -366,7 +368,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     mine = cp.for_rank(rank)
     if strided is not None:                                       # (s, L, d) -> the (s, e) the byte counts below read: e - s = L
         mine, spans_strided = [(s, s + L) for s, L, _ in mine], mine
-    emb = torch.cat([d.uncond_emb, d.cond_emb], dim=0)
+    emb = torch.cat([d.uncond_emb, d.cond_emb], dim=0) if d.travel is None else None
     local = torch.zeros((per, nt * slot), dtype=torch.float16, device=start.device)
     packed = torch.zeros((world, per, nt * slot), dtype=torch.float16, device=start.device) if world > 1 else local
     payload_step = sum((e - s) * C * 2 for s, e in mine)          # the reference's formula (:194), per exchange
@@ -391,11 +393,20 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     else:
         input_op, spans = ops.cfg_input_tile, mine
         step, head, step_kw = sched.step_cfg_tiles, (packed, rows, wn, grid), {}
+    # prompt travel: every window has its own text (every tile of a window shares it), built once; else the one text of the job
+    if d.travel is None:
+        texts = [emb] * len(spans)
+    elif strided is not None:
+        texts = [d.window_text(s, L, dd) for s, L, dd in spans]
+    elif loop:
+        texts = [d.window_text(s, L, 1, True) for s, L in spans]
+    else:
+        texts = [d.window_text(s, e - s) for s, e in spans]
     t_round = time.time()
     for i, t in enumerate(d.schedule):
         for j, span in enumerate(spans):
             for k, box in enumerate(boxes):
-                noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=emb).sample
+                noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=texts[j]).sample
                 local[j, k * slot:k * slot + noise.numel()].copy_(noise.reshape(-1))
         delay = emu_gather_delay_s(payload_step, cfg)             # per step: one exchange per step is what the method costs
         if delay > 0:

@@ -2038,3 +2038,63 @@ def tome_unmerge_add(x, slot, t, src_idx, dst_idx, *, n_img, S, r, out=None):
     with torch.cuda.device(t.device):
         _launch("vdx_tome_unmerge_add_f16", C.byref(a), px, ldx, pt, ldt, po, ldo)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Prompt travel: per-frame text (vdx/travel.py, csrc/travel.hip; no reference counterpart)
+def text_travel(keys, uncond, lo, hi, w, s: int, L: int, d: int = 1, ring: bool = False, out=None):
+    """One window's UNet text in one launch (include/vdx.h `vdx_text_travel_f16`) -> fp16 (2, L, N, D): item 0 is `uncond` on every
+    frame; item 1, frame f, is the plan's blend for the clip frame `s + f * d` (`ring`: mod T) of `keys` fp16 (n_keys, N, D).
+    `uncond`: fp16 (N, D) or (1, N, D); `lo`, `hi`: int32 (T,), `w`: fp32 (T,) on the device (`travel.TravelPlan.to`).  `lo` and
+    `hi` are checked against n_keys here (one host sync: the call is made once per window, before the loop) and clamped on the
+    device; the library checks `s`, `L` and `d` against T."""
+    if keys.dim() != 3 or not keys.is_contiguous():
+        raise VdxError(f"text_travel: keys must be contiguous (n_keys, N, D), got {tuple(keys.shape)}")
+    n_keys, N, D = keys.shape
+    if uncond.dim() == 3 and uncond.shape[0] == 1:
+        uncond = uncond[0]
+    if tuple(uncond.shape) != (N, D) or not uncond.is_contiguous():
+        raise VdxError(f"text_travel: uncond must be contiguous ({N}, {D}) or (1, {N}, {D}), got {tuple(uncond.shape)}")
+    T = lo.numel()
+    for t, name, dt in ((lo, "lo", torch.int32), (hi, "hi", torch.int32), (w, "w", torch.float32)):
+        if t.dim() != 1 or t.numel() != T or T < 1 or not t.is_contiguous() or t.dtype != dt or t.device != keys.device:
+            raise VdxError(f"text_travel: {name} must be a contiguous {dt} ({T},) on the keys' device")
+    lo_min, lo_max, hi_min, hi_max = (int(v) for v in torch.stack([lo.min(), lo.max(), hi.min(), hi.max()]).tolist())
+    if min(lo_min, hi_min) < 0 or max(lo_max, hi_max) >= n_keys:
+        raise VdxError(f"text_travel: lo / hi name keys outside [0, {n_keys})")
+    s, L, d = int(s), int(L), int(d)
+    if L < 1:
+        raise VdxError(f"text_travel: bad window start {s}, length {L}, stride {d} of {T} frames")
+    shape = (2, L, N, D)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=keys.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise VdxError("text_travel: out must be contiguous (2, L, N, D)")
+    if D % 8:       # the scalar path reads where the tensors lie; `_p` asks for the vector path's alignment
+        for t, name in ((keys, "keys"), (uncond, "uncond"), (out, "out")):
+            if not t.is_cuda or t.dtype != torch.float16:
+                raise VdxError(f"text_travel: {name} must be an fp16 GPU tensor")
+        ptrs = (keys.data_ptr(), uncond.data_ptr(), out.data_ptr())
+    else:
+        ptrs = (_p(keys, "keys"), _p(uncond, "uncond"), _p(out, "out"))
+    _launch("vdx_text_travel_f16", ptrs[0], n_keys, ptrs[1], _p(lo, "lo", torch.int32), _p(hi, "hi", torch.int32), _p(w, "w", torch.float32),
+            T, s, L, d, int(bool(ring)), N, D, ptrs[2])
+    return out
+
+
+def cross_attn_block_pack_kv(k_rows, vt, n_items: int, text_pad: int, out=None):
+    """`packing.pack_k5_kv` as one launch (include/vdx.h `vdx_cross_attn_block_pack_kv_f16`): k_rows [n_items*text_pad][inner], vt
+    [inner][n_items*text_pad] -> K5's key / value blobs [n_items][heads][3 * 4096] fp16, bit for bit what the torch chain builds."""
+    kr, inner, ldk = _rows(k_rows, "k_rows")
+    vr, vc, ldvt = _rows(vt, "vt")
+    if not cross_attn_block_supported(inner, 1):
+        raise VdxError(f"cross_attn_block_pack_kv: inner={inner} not supported by the fused kernel")
+    if n_items < 1 or kr < n_items * text_pad or vr < inner or vc < n_items * text_pad:
+        raise VdxError(f"cross_attn_block_pack_kv: k_rows {tuple(k_rows.shape)} / vt {tuple(vt.shape)} do not cover {n_items} items of {text_pad} keys")
+    shape = (n_items, inner // 64, _lib.load().vdx_cross_attn_block_kv_bytes(inner) // (2 * (inner // 64)))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=k_rows.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise VdxError(f"cross_attn_block_pack_kv: out must be contiguous {shape}")
+    _launch("vdx_cross_attn_block_pack_kv_f16", _p(k_rows, "k_rows"), ldk, _p(vt, "vt"), ldvt, int(n_items), int(text_pad), inner, _p(out, "out"))
+    return out

@@ -213,6 +213,17 @@ def check_stride(cfg, exchange: str = "allgather", world: Optional[int] = None) 
     return _stride(cfg, exchange, world)[0]
 
 
+def check_prompt_travel(cfg) -> Optional[Tuple[Tuple[int, str], ...]]:
+    """`cfg.prompt_travel` as the job's keys, ((frame, text), ...) sorted by frame with `cfg.prompt` at frame 0 unless a key names
+    frame 0 (None when off); `ValueError` before any work for a malformed entry, a frame that is no integer inside the clip, a
+    frame named twice, a text that is no string, and more than 64 keys (vdx/travel.py).  One key is valid: a constant prompt
+    through the per-frame path."""
+    if getattr(cfg, "prompt_travel", None) is None:
+        return None
+    from .travel import keys_of
+    return keys_of(cfg)
+
+
 # ---- the resolved job ---------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class JobOptions:
@@ -232,6 +243,7 @@ class JobOptions:
     pixel_mask: Optional[np.ndarray] = None
     guidance_rescale: float = 0.0
     guidance: dict = field(default_factory=dict)       # the keys the result and the records gain: negative_prompt, guidance_rescale
+    prompt_travel: Optional[Tuple[Tuple[int, str], ...]] = None     # the keys, sorted, the prompt at frame 0 among them
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -257,6 +269,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         if not isinstance(cfg.negative_prompt, str):
             raise ValueError(f"negative_prompt must be a string, got {cfg.negative_prompt!r}")
         guidance = {"negative_prompt": cfg.negative_prompt} if cfg.negative_prompt else {}
+        travel = check_prompt_travel(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -264,11 +277,12 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         if exchange not in ("allgather", "halo"):
             raise ValueError(f"unknown exchange {exchange!r}")
         factor, pixel_mask, phi, guidance = cfg.interpolate, None, float(cfg.guidance_rescale), {}
+        travel = check_prompt_travel(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
-                      guidance_rescale=phi, guidance=guidance)
+                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -287,11 +301,23 @@ def info_options(opts: JobOptions, rounds) -> dict:
             out["loop"] = first["loop"]
         if opts.context_stride > 1:
             out["context_stride"] = out["co_denoise"]["context_stride"] = first["context_stride"]
+    out.update(travel_record(opts))
     return out
 
 
 # the option entries of `run_job`'s result dict (after "free_init") and of `main`'s JSON records, in their order
 RECORD_KEYS = ("freeu", "tome", "co_denoise", "tile", "loop", "context_stride", "mask", "negative_prompt", "guidance_rescale")
+
+
+def travel_record(src) -> dict:
+    """`{"prompt_travel": {"keys": [[frame, text], ...]}}` beside `record_options`' entries, only when the option is set (else
+    {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"prompt_travel": src["prompt_travel"]} if "prompt_travel" in src else {}
+    if src.prompt_travel is None:
+        return {}
+    from .travel import record
+    return {"prompt_travel": record(src.prompt_travel)}
 
 
 def record_options(res: dict) -> dict:

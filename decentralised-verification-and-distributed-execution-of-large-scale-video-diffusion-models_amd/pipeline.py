@@ -37,7 +37,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, record_options, resolve, world_size
+from .options import info_options, record_options, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -118,6 +118,11 @@ class DiffuserConfig:
     # windows that take every 2nd, 4th, ... frame, so frames further apart than a window are denoised together at every step, at
     # the price of those windows' UNet calls.  1 = consecutive frames only, as always
     context_stride: int = 1
+    # prompt travel (vdx/travel.py, csrc/travel.hip; AnimateDiff-Evolved's batch prompt schedule, unpinned): ((frame, text), ...),
+    # key frames and their prompts; `prompt` is the key at frame 0 unless a key names frame 0.  A frame between two keys is
+    # conditioned on the linear blend of their CLIP embeddings, a frame after the last key on the last key (with `loop`: on the
+    # blend back to the first), in every window of every mode.  None = one prompt for the whole clip, as always
+    prompt_travel: Optional[Tuple[Tuple[int, str], ...]] = None
 
     @property
     def use_fsdp(self):
@@ -253,14 +258,17 @@ def gather_chunks(mine: List[torch.Tensor], chunk_plan: ChunkPlan, rank: int, wo
 
 
 class DistributedVideoDiffuser:
-    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None, latent_mask=None):
+    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None, latent_mask=None, travel=None):
         """`init_latents` (video-to-video): the scaled clean latent (1,C,T,h,w) fp16 of the whole clip (every rank encodes the
         whole clip: identical bits on every rank, no collective).  The denoise then runs `vid2vid_timesteps(cfg.strength)`
         from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
         frame-mean of that start latent.  None: text-to-video, unchanged.
         `latent_mask` (masked video-to-video, vdx/inpaint.py; needs `init_latents`): uint8 (T,h,w) on the device, 1 = regenerate,
         0 = keep, identical on every rank.  After every scheduler step the kept cells are set to `init_latents` noised to the
-        next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off."""
+        next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off.
+        `travel` (prompt travel, vdx/travel.py): (key_embs, plan), the keys' text embeddings fp16 (n_keys, N, D) on the device in
+        the order of the plan's frames and the `travel.TravelPlan` of the clip.  Every window's UNet text is then built once, by
+        `ops.text_travel` (`window_text`), and passed where `cat([uncond_emb, cond_emb])` is passed without it.  None: off."""
         self.cfg = cfg
         check_freeu(cfg)
         check_tome(cfg)
@@ -283,6 +291,14 @@ class DistributedVideoDiffuser:
         self._base = self._x0 = None                                  # video-to-video only: the seeded noise, the clean latent
         self.latent_mask = None
         self._known = None                                            # masked only: add_noise's scalars of each step's NEXT timestep
+        self.travel = None                                            # prompt travel only: (key_embs, the plan's device arrays)
+        self._travel_text = {}                                        # (s, L, d, ring) -> that window's (2, L, N, D) text
+        if travel is not None:
+            key_embs, tplan = travel
+            if key_embs.dim() != 3 or key_embs.shape[0] != len(tplan.frames) or tplan.T != cfg.num_frames:
+                raise ValueError(f"travel: {tuple(key_embs.shape)} key embeddings for a plan of {len(tplan.frames)} keys and {tplan.T} "
+                                 f"frames; the clip has {cfg.num_frames}")
+            self.travel = (key_embs.to(cfg.device, torch.float16).contiguous(), tplan.to(cfg.device))
         shape = self.latent_shape if init_latents is not None or cfg.use_ctx else None
         if init_latents is not None:
             if tuple(init_latents.shape) != shape:
@@ -324,12 +340,23 @@ class DistributedVideoDiffuser:
         sa, s1 = k if k is not None else (0.0, 0.0)
         ops.mask_renoise(z, self._x0, self._base, self.latent_mask, sa, s1, k is None, s)
 
-    def denoise(self, lat: torch.Tensor, s: Optional[int] = None) -> torch.Tensor:
+    def window_text(self, s: int, L: int, d: int = 1, ring: bool = False) -> torch.Tensor:
+        """Prompt travel: the (2, L, N, D) UNet text of the window of the clip frames `s + f * d` (`ring`: mod T), built on first
+        use and then held: the UNet's text cache knows a text by the tensor it is handed."""
+        key = (int(s), int(L), int(d), bool(ring))
+        text = self._travel_text.get(key)
+        if text is None:
+            key_embs, (lo, hi, w) = self.travel
+            text = self._travel_text[key] = ops.text_travel(key_embs, self.uncond_emb.to(key_embs.device, torch.float16).contiguous(),
+                                                            lo, hi, w, *key)
+        return text
+
+    def denoise(self, lat: torch.Tensor, s: Optional[int] = None, text: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reference `_denoise` (:129-143) for one chunk.  `s` (masked video-to-video only, with a `latent_mask`): the chunk's
-        first frame in the clip; None: the masked path is off."""
+        first frame in the clip; None: the masked path is off.  `text` (prompt travel): the chunk's `window_text`."""
         masked = s is not None and self.latent_mask is not None
         cfg, sched = self.cfg, self.scheduler
-        emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0)
+        emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0) if text is None else text
         lat = lat.contiguous()
         reset = getattr(sched, "reset", None)
         if reset is not None:       # a multistep scheduler must not carry the previous chunk's history into this one
@@ -394,7 +421,10 @@ class DistributedVideoDiffuser:
         _, C, T, H, W = start.shape
         t0 = time.time()
         masked = self.latent_mask is not None
-        mine = [self.denoise(start[:, :, s:e].clone(), *((s,) if masked else ())) for s, e in cp.for_rank(self.rank)]
+        if self.travel is None:             # the call as it always was
+            mine = [self.denoise(start[:, :, s:e].clone(), *((s,) if masked else ())) for s, e in cp.for_rank(self.rank)]
+        else:                               # prompt travel: every window with its own text
+            mine = [self.denoise(start[:, :, s:e].clone(), s if masked else None, self.window_text(s, e - s)) for s, e in cp.for_rank(self.rank)]
         if self.world > 1:
             dist.barrier()
         self._sync()
@@ -463,6 +493,13 @@ class DistributedVideoDiffuser:
             rec = {"iters": iters, "method": cfg.free_init_method, "d_s": cfg.free_init_spatial, "d_t": cfg.free_init_temporal,
                    "order": cfg.free_init_order, "denoise_s": [], "reinit_s": []}
         ctx0, start, starts = self.ctx, base, []
+        if self.travel is not None:
+            # a rank's windows alternate within a step (co_denoise) or follow one another (windowed): one slot of the UNet's text
+            # cache per window, 8 at most (an entry is ~150 MB at XL widths); beyond that a call recomputes
+            runs = len((opts.stride_plan or cp).for_rank(self.rank))
+            slots0 = getattr(self.unet, "text_cache_slots", None)
+            if slots0 is not None:
+                self.unet.text_cache_slots = max(slots0, min(runs, 8))
         if freeu is not None:
             freeu0 = self.unet.freeu
             self.unet.enable_freeu(**freeu)
@@ -489,6 +526,8 @@ class DistributedVideoDiffuser:
                     starts.append(start)
         finally:
             self.ctx = ctx0                                            # the next call's iteration 0 starts as this one did
+            if self.travel is not None and slots0 is not None:
+                self.unet.text_cache_slots = slots0
             if freeu is not None:
                 self.unet.enable_freeu(**freeu0) if freeu0 is not None else self.unet.disable_freeu()
             if tome is not None:
@@ -584,13 +623,16 @@ def build_arg_parser():
                    help="text of the unconditional branch of classifier-free guidance (default: the empty prompt)")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="CFG rescale phi in [0, 1] (Lin et al. 2023): 0, the default, is off; needs --guidance_scale > 1")
+    p.add_argument("--prompt_at", nargs=2, action="append", default=None, metavar=("FRAME", "TEXT"),
+                   help="prompt travel: TEXT is the prompt at frame FRAME, frames between two such keys blend them (repeatable; "
+                        "--prompt is the key at frame 0 unless one names it; default: off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
     return p
 
 
-FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None}     # where the flag's name is not the field's; None: no flag
+FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None, "prompt_travel": "prompt_at"}     # where the flag's name is not the field's; None: no flag
 
 
 def config_from_args(a) -> DiffuserConfig:
@@ -605,6 +647,13 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.tile_overlap = tuple(cfg.tile_overlap)
     if isinstance(cfg.mask_paste, str):
         cfg.mask_paste = cfg.mask_paste == "on"
+    if cfg.prompt_travel is not None:           # FRAME arrives as text; what is no integer stays as it came, for the check to refuse
+        def frame(v):
+            try:
+                return int(v)
+            except ValueError:
+                return v
+        cfg.prompt_travel = tuple((frame(f), text) for f, text in cfg.prompt_travel)
     return cfg
 
 
@@ -738,10 +787,15 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     for m in (unet, pipe.text_encoder, pipe.vae):
         m.to(dev)
     tok = pipe.tokenizer
-    ids = tok([cfg.prompt, cfg.negative_prompt], padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
+    texts = [cfg.prompt, cfg.negative_prompt] + [text for _, text in opts.prompt_travel or ()]     # one text-encoder call
+    ids = tok(texts, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
     with torch.no_grad():
         emb = pipe.text_encoder(ids.to(dev))[0]
-    cond, uncond = emb[:1].contiguous(), emb[1:].contiguous()
+    cond, uncond = emb[:1].contiguous(), emb[1:2].contiguous()
+    travel = {}
+    if opts.prompt_travel is not None:
+        from .travel import travel_plan
+        travel = {"travel": (emb[2:].contiguous(), travel_plan(opts.prompt_travel, cfg.num_frames, loop=loop))}
     init_latents, encode_s, masking = None, 0.0, {}
     if pixel_mask is not None:
         init_latents, encode_s, originals = encode_init_video(cfg, pipe.vae, dev, return_frames=True)
@@ -750,7 +804,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     elif cfg.init_video is not None:
         init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
     d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents,
-                                 **masking)
+                                 **masking, **travel)
     out, info = d(exchange=exchange, options=opts)
     ranges = info["ranges"]
     if exchange == "allgather":
@@ -802,7 +856,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
-            **record_options({**info, **mask, **opts.guidance})}
+            **record_options({**info, **mask, **opts.guidance}), **travel_record(info)}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -831,7 +885,7 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = record_options(res)
+        source = {**record_options(res), **travel_record(res)}
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -851,7 +905,7 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update(record_options(res))
+            rec.update({**record_options(res), **travel_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

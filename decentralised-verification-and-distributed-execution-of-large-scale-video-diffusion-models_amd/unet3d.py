@@ -89,6 +89,10 @@ class UNet3DConditionModel(nn.Module):
         self.detect_cfg_duplicate = False      # untagged batch of two: COMPARE the halves on the device (one kernel + a host sync) before sharing
         self._text_ref = None                  # (encoder_hidden_states object, its version, (B, device), padded copy)
         self._text_kv: Dict[str, tuple] = {}   # cross-attention K / V^T of that text, per transformer
+        self.text_cache_slots = 1              # texts whose K / V^T are kept (least recently used dropped); 1: the last text only, as always
+        self._text_store: List[tuple] = []     # the other kept texts' (_text_ref, _text_kv), most recently used first
+        self.text_cache_misses = 0             # forwards that had to project their text's keys / values
+        self._text_per_frame = False           # the forward's text is (B, F, N, D): one K / V item per frame (prompt travel)
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
         self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
         self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
@@ -319,7 +323,7 @@ class UNet3DConditionModel(nn.Module):
             raise VdxError(f"unexpected keys in state dict: {sorted(missing)[:5]} ... ({len(missing)})")
         self.W = W
         self._device = dev
-        self._text_ref, self._text_kv = None, {}
+        self._text_ref, self._text_kv, self._text_store = None, {}, []
         return self
 
     def _apply(self, fn, recurse=True):
@@ -648,25 +652,32 @@ class UNet3DConditionModel(nn.Module):
         b = p + ".transformer_blocks.0"
         t = self._norm_proj_in(p, x, n_img, S, M, part=2 * n_img if dup else 0)
         t = self._self_attention(b, t, n_img, hh, ww, self._level_down_of(p))
-        # --- cross-attention over the (padded) text tokens; all F frames of a sample share K/V
+        # --- cross-attention over the (padded) text tokens; all F frames of a sample share K/V — or, with per-frame text
+        # (`encoder_hidden_states` (B, F, N, D): prompt travel), every frame has its own item: nb = B F, `fpi` = F items per sample
         nb = ehs_pad.shape[0] // TEXT_PAD
+        per_frame = self._text_per_frame
+        fpi = F if per_frame else 1
         k5 = self.fuse_cross_attn and b + ".attn2.k5" in W and ops.cross_attn_block_supported(C, self._text_len)
         kv = self._text_kv.get(p)
         if kv is None:
             k = ops.gemm(ehs_pad, W[b + ".attn2.to_k.weight"], M=ehs_pad.shape[0])
             vt = ops.gemm(W[b + ".attn2.to_v.weight"], ehs_pad, M=C)              # [C][nb*TEXT_PAD]
-            kv = self._text_kv[p] = (k, vt, packing.pack_k5_kv(k, vt, nb, TEXT_PAD) if k5 else None)
+            # (per-frame text packs its B F items in one launch, csrc/travel.hip; one text per sample keeps the torch chain)
+            pack_kv = ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv
+            kv = self._text_kv[p] = (k, vt, pack_kv(k, vt, nb, TEXT_PAD) if k5 else None)
         k, vt, kvb = kv
         if k5 and kvb is None:
-            kvb = packing.pack_k5_kv(k, vt, nb, TEXT_PAD)
+            kvb = (ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv)(k, vt, nb, TEXT_PAD)
             self._text_kv[p] = (k, vt, kvb)
         if k5:
             # K5 (level 0): LayerNorm -> q -> softmax(q K^T) V -> to_out + residual in one kernel; the text keys / values were
-            # packed once per prompt.  A shared-prefix batch (`dup`): the same rows against each item's text in turn.
+            # packed once per prompt.  A shared-prefix batch (`dup`): the same rows against each item's text in turn (per-frame
+            # text: against that item's F consecutive K / V items, a frame's rows each).
             if dup:
                 t2 = torch.empty((M_out, C), dtype=torch.float16, device=x.device)
-                for i in range(nb):
-                    ops.cross_attn_block(t, W[b + ".attn2.k5"], kvb[i:i + 1], kv_len=self._text_len, n_items=1, rows_per_item=M, out=t2[i * M:(i + 1) * M])
+                for i in range(nb // fpi):
+                    ops.cross_attn_block(t, W[b + ".attn2.k5"], kvb[i * fpi:(i + 1) * fpi], kv_len=self._text_len, n_items=fpi, rows_per_item=M // fpi,
+                                         out=t2[i * M:(i + 1) * M])
             else:
                 t2 = ops.cross_attn_block(t, W[b + ".attn2.k5"], kvb, kv_len=self._text_len, n_items=nb, rows_per_item=M // nb)
             return self._ff_proj_out(b, p, t2, x, M_out, xrows=M)
@@ -677,9 +688,9 @@ class UNet3DConditionModel(nn.Module):
             # one query tensor, the keys / values of each item in turn; the residual rows (and, at the block's end, the
             # transformer's input rows) are the shared item's for both — two launches over half the rows each, no copy
             t2 = torch.empty((M_out, C), dtype=torch.float16, device=x.device)
-            for i in range(nb):
-                o = ops.flash_attn(q, k[i * TEXT_PAD:(i + 1) * TEXT_PAD], vt[:, i * TEXT_PAD:(i + 1) * TEXT_PAD], n_seq=n_img, sq=S,
-                                   skv=self._text_len, skv_pad=TEXT_PAD, heads=heads, seq_per_kv=n_img, scale=scale)
+            for i in range(nb // fpi):
+                o = ops.flash_attn(q, k[i * fpi * TEXT_PAD:(i + 1) * fpi * TEXT_PAD], vt[:, i * fpi * TEXT_PAD:(i + 1) * fpi * TEXT_PAD], n_seq=n_img, sq=S,
+                                   skv=self._text_len, skv_pad=TEXT_PAD, heads=heads, seq_per_kv=n_img // fpi, scale=scale)
                 ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=M, bias=W[b + ".attn2.to_out.0.bias"], residual=t, out=t2[i * M:(i + 1) * M])
                 del o
             del q
@@ -751,9 +762,17 @@ class UNet3DConditionModel(nn.Module):
         cfg_dup = ops.is_cfg_duplicate(sample)
         sample = sample.to(torch.float16).contiguous()
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.float16)
-        if ehs.shape[0] != B or ehs.shape[2] != c.cross_attention_dim or ehs.shape[1] > TEXT_PAD:
+        per_frame = ehs.dim() == 4              # (B, F, N, D): a text per frame (prompt travel); (B, N, D): one per sample, as always
+        if per_frame:
+            if ehs.shape[0] != B or ehs.shape[3] != c.cross_attention_dim or ehs.shape[2] > TEXT_PAD:
+                raise VdxError(f"encoder_hidden_states shape {tuple(ehs.shape)} does not fit (B={B}, dim={c.cross_attention_dim})")
+            if ehs.shape[1] != F:
+                raise VdxError(f"encoder_hidden_states holds text for {ehs.shape[1]} frames, the sample has {F}")
+        elif ehs.dim() != 3 or ehs.shape[0] != B or ehs.shape[2] != c.cross_attention_dim or ehs.shape[1] > TEXT_PAD:
             raise VdxError(f"encoder_hidden_states shape {tuple(ehs.shape)} does not fit (B={B}, dim={c.cross_attention_dim})")
-        self._text_len = ehs.shape[1]
+        self._text_len = ehs.shape[-2]
+        self._text_per_frame = per_frame
+        nt = B * F if per_frame else B          # K / V items
         # The text keys / values of the 16 cross-attentions depend on the prompt only: they are projected once and kept
         # while the caller keeps passing the SAME tensor object, unmodified (identity + version, not the address: a new
         # tensor may reuse a freed address with other contents).  `pipeline.denoise` and bench.py pass one tensor for
@@ -761,17 +780,31 @@ class UNet3DConditionModel(nn.Module):
         # every step (fsdp_chunked_coherent.py:138): on the unchanged script each step is a miss — 32 small K / V
         # projections and one padded copy, ~0.2 ms of a 180 ms step — never a stale hit.  Tensors without a version
         # counter (inference mode) are not cached.
+        # `text_cache_slots` > 1 (a job whose windows each have their own text: prompt travel) keeps that many texts, the least
+        # recently used dropped: `_text_ref` / `_text_kv` are the text in use, `_text_store` the others.  1 is the above exactly.
         ref = self._text_ref
         try:
             ver = encoder_hidden_states._version
         except Exception:       # inference-mode tensors do not track versions
             ver = None
-        if not (ref is not None and ver is not None and ref[0] is encoder_hidden_states and ref[1] == ver
-                and ref[2] == (B, dev)):
-            ehs_pad = torch.zeros((B * TEXT_PAD, c.cross_attention_dim), dtype=torch.float16, device=dev)
-            ehs_pad.view(B, TEXT_PAD, -1)[:, :ehs.shape[1]] = ehs
-            self._text_ref = (encoder_hidden_states, ver, (B, dev), ehs_pad)
-            self._text_kv = {}
+        key = (tuple(ehs.shape), dev)
+
+        def same(r):
+            return r is not None and ver is not None and r[0] is encoder_hidden_states and r[1] == ver and r[2] == key
+
+        if not same(ref):
+            slots = max(1, int(self.text_cache_slots))
+            held = next((i for i, (r, _) in enumerate(self._text_store) if same(r)), None) if slots > 1 else None
+            entry = self._text_store.pop(held) if held is not None else None
+            if slots > 1 and ref is not None:
+                self._text_store.insert(0, (ref, self._text_kv))
+            del self._text_store[slots - 1:]
+            if entry is None:
+                ehs_pad = torch.zeros((nt * TEXT_PAD, c.cross_attention_dim), dtype=torch.float16, device=dev)
+                ehs_pad.view(nt, TEXT_PAD, -1)[:, :self._text_len] = ehs.reshape(nt, self._text_len, -1)
+                entry = ((encoder_hidden_states, ver, key, ehs_pad), {})
+                self.text_cache_misses += 1
+            self._text_ref, self._text_kv = entry
         ehs_pad = self._text_ref[3]
         n_img = B * F
 

@@ -855,6 +855,28 @@ int vdx_tome_unmerge_add_f16(const vdx_tome_args* a, const void* x, int ldx, con
                              vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prompt travel: per-frame text through every cross-attention (nothing in the reference: it encodes one prompt per job;
+ * AnimateDiff-Evolved's batch prompt schedule, unpinned; vdx/travel.py, the job's --prompt_at, csrc/travel.hip).
+ * tests/travel_ref.py states the schedule and the blend.  No atomics: the same bits on every run.
+ * ------------------------------------------------------------------------------------------ */
+/* One window's UNet text in one launch.  keys: fp16 (n_keys, N, D); uncond: fp16 (N, D); lo, hi: int32 [T], w: fp32 [T] on the
+ * device, the plan of vdx/travel.py `travel_plan`; out: fp16 (2, L, N, D).  out[0][f] = uncond; out[1][f], for the clip frame
+ * t = s + f d (with `ring`, t - T where that is >= T), is keys[lo[t]]'s bits where w[t] == 0 or lo[t] == hi[t], else
+ *   fp16( fp32( fp32(1 - w[t]) fp32(keys[lo[t]]) ) + fp32( w[t] fp32(keys[hi[t]]) ) )
+ * with every product and the sum rounded on its own.  lo and hi are clamped to [0, n_keys) on the device before use.
+ * 0 <= s < T, L >= 1, d >= 1, s + (L - 1) d < T (with `ring`: < 2 T).  16 bytes per lane where D % 8 == 0 (keys, uncond and
+ * out then 16-byte aligned), else one element.                                                                            */
+int vdx_text_travel_f16(const void* keys, int n_keys, const void* uncond, const int32_t* lo, const int32_t* hi, const float* w,
+                        int T, int s, int L, int d, int ring, int N, int D, void* out, vdx_stream_t stream);
+/* vdx/packing.py pack_k5_kv as one launch: k_rows fp16 [n_items text_pad][inner] (stride ldk), vt fp16 [inner][n_items
+ * text_pad] (stride ldvt) -> out [n_items][heads][3 * 4096] fp16, K5's key / value blobs (vdx_cross_attn_block_kv_bytes each),
+ * the zeroed rest of the third unit included; the first 80 keys of every item are read.  Supported where
+ * vdx_cross_attn_block_supported(inner, .) is; text_pad >= 80 and a multiple of 4, ldk and ldvt multiples of 4, k_rows and
+ * vt 8-byte, out 16-byte aligned.  Every index is a function of the thread's position only.                               */
+int vdx_cross_attn_block_pack_kv_f16(const void* k_rows, int ldk, const void* vt, int ldvt, int n_items, int text_pad, int inner,
+                                     void* out, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

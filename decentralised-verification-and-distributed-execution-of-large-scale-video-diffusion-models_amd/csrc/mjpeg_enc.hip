@@ -17,11 +17,13 @@
 #include "vdx_common.h"
 #include "mjpeg_common.h"
 
-// One block: DC code <= 9 bits + 11 value bits; each of the 63 AC coefficients <= 16 + 10 bits (a ZRL is 11 bits for 16
+// One luma block: DC code <= 9 bits + 11 value bits; each of the 63 AC coefficients <= 16 + 10 bits (a ZRL is 11 bits for 16
 // coefficients: cheaper).  20 + 63 * 26 = 1658 bits; the up to 7 padding bits of a segment fit the last block's slot too:
-// ceil(n * 1658 / 8) <= 208 n.  Sizes are clamped to 11 / 10 in the coder, so the bound holds for ANY int16 coefficients; from
-// 8-bit samples nothing is ever clamped: |DC| <= 64 * 128 * 8 / 8 = 1024 (a difference of at most 2047: size 11) and
-// |AC| <= 1020 (the largest basis sum, 8, times 127.5) before the division by q >= 1.
+// ceil(n * 1658 / 8) <= 208 n.  A chroma block stays below that: its DC code is up to 11 bits, but run 0 / size 10 has a
+// 12-bit code, and a 16-bit code needs a run, which halves the coefficients coded: 22 + 63 * 22 = 1408 bits at most
+// (tests/mjpeg_enc_ref.py `coef_sets` reaches both).  Sizes are clamped to 11 / 10 in the coder, so the bound holds for ANY
+// int16 coefficients; from 8-bit samples nothing is ever clamped: |DC| <= 64 * 128 * 8 / 8 = 1024 (a difference of at most
+// 2047: size 11) and |AC| <= 1020 (the largest basis sum, 8, times 127.5) before the division by q >= 1.
 #define MJE_SLOT_BYTES 208
 #define MJE_SLOT_WORDS 52
 #define MJE_TABLE_WORDS 272      // per table id: 16 DC words by size, 256 AC words by run << 4 | size; length << 16 | code

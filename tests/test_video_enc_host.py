@@ -156,3 +156,85 @@ def test_restatement_coefficients_are_the_ones_pillow_coded():
     blob, off, info, _ = video.plan([E.pillow_encode(img)])
     coef, err = mjpeg_ref.entropy(blob, off, info)
     assert not err.any() and np.array_equal(coef, stages["coef"])
+
+
+# ---------------------------------------------------------------------------------------------
+# The edges of every stage: the inputs tests/test_video_enc_stages_gpu.py puts before the kernels, pinned here without a GPU
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("quality", E.QUALITIES)
+def test_restatement_bytes_are_pillows_at_every_quality(quality):
+    """Quality 1 (every divisor clamped to 255) to 100 (every divisor 1: the longest codes, the largest DC differences)."""
+    for kind in E.KINDS:
+        for W, H in E.SWEEP_SIZES:
+            for mode in E.MODES:
+                img = E.content(kind, W, H, mode)
+                for rr in (0, 1):
+                    assert E.encode(img[None], quality, rr)[0] == E.pillow_encode(img, rr, quality), (kind, W, H, mode, rr)
+
+
+def test_quality_reaches_both_ends_of_the_divisors():
+    assert (video.quant_tables(100) == 1).all() and (video.quant_tables(1) == 255).all()
+    assert len(np.unique(video.quant_tables(50))) > 20
+
+
+def test_basis_blocks_reach_the_extremes_of_stage_2():
+    """The 0 / 255 sign pattern of each basis function at quality 100: bytes are Pillow's for grey and RGB, the coefficients
+    are those Pillow coded, and they reach |AC| = 1020, DC -1024 ... 1016 and a DC difference of size 11."""
+    blocks = E.basis_blocks()
+    assert blocks.shape == (130, 8, 8) and set(np.unique(blocks)) == {0, 255}
+    assert (blocks[0] == 255).all() and (blocks[1] == 0).all() and (blocks[128] == 0).all() and (blocks[129] == 255).all()
+    assert all(np.array_equal(blocks[2 * k + 1], 255 - blocks[2 * k]) for k in range(64))
+    assert len({b.tobytes() for b in blocks}) == 128
+    for mode in E.MODES:
+        img = E.basis_image(mode)
+        stages, counters = {}, E.Counters()
+        jpeg = E.encode(img[None], 100, 0, counters, stages)[0]
+        assert jpeg == E.pillow_encode(img, 0, 100), mode
+        assert E.encode(img[None], 100, 1)[0] == E.pillow_encode(img, 1, 100), mode
+        blob, off, info, _ = video.plan([E.pillow_encode(img, 0, 100)])
+        coef, err = mjpeg_ref.entropy(blob, off, info)
+        assert not err.any() and np.array_equal(coef, stages["coef"]), mode
+        if mode == "L":
+            E.check_basis(stages["coef"], counters)
+            zz = np.abs(stages["coef"][0].astype(np.int64))
+            assert (zz.max(0)[1:] >= 127 * 8 * 0.4).all(), "every basis function's coefficient is driven far from zero"
+    # the planes of the stage-2 test hold nothing but these blocks, in every component, dummy blocks included
+    pl = E.basis_planes(24, 40, 2, 22)
+    assert [p.shape for p in pl] == [(22, 48, 32), (22, 24, 16), (22, 24, 16)]
+    for p in pl:
+        seen = {p[f, y:y + 8, x:x + 8].tobytes() for f in range(22) for y in range(0, p.shape[1], 8) for x in range(0, p.shape[2], 8)}
+        assert seen == {b.tobytes() for b in blocks}
+
+
+SETS = E.coef_sets()
+
+
+def test_the_coefficient_sets_are_the_ones_the_issue_names():
+    assert sorted(SETS) == sorted(["max-bits-L-dri0", "max-bits-L-dri1", "max-bits-420-dri0", "max-bits-420-dri1", "all-ones", "zrl-L",
+                                   "zrl-420", "zeros-300", "rst-wrap", "one-segment-dri2", "one-segment-dri7"] +
+                                  [f"mod8-{m}" for m in range(8)])
+    in_domain = {n for n, e in SETS.items() if E.in_reader_domain(e)}
+    assert in_domain == {n for n in SETS if not n.startswith(("max-bits", "all-ones"))}
+
+
+@pytest.mark.parametrize("name", sorted(SETS))
+def test_coefficient_set_has_one_stream_by_two_hands_and_reads_back(name):
+    """The restatement's scan equals the hand writer's (tests/mjpeg_enc.py: another definition of the stream), the reader's
+    restatement finds the coefficients that were put in, and the set reaches what it exists for."""
+    entry = SETS[name]
+    header, scan, jpeg, hand = E.coef_stream(entry)
+    assert hand[:len(header)] == header and hand[-2:] == b"\xff\xd9"
+    assert scan == hand[len(header):-2]
+    blob, off, info, _ = video.plan([jpeg])
+    assert info["restart_interval"] == entry[4]
+    coef, err = mjpeg_ref.entropy(blob, off, info)
+    assert not err.any() and np.array_equal(coef[0], entry[3])
+    E.check_coef_set(name, entry)
+
+
+def test_slots_of_adds_up_to_the_scan():
+    for name, (layout, W, H, coef, dri) in SETS.items():
+        raws, lengths, step = E.segments(coef, W, H, layout, dri)
+        slots = E.slots_of(raws, step, len(lengths))
+        assert len(slots) == len(lengths) and sum(slots) == len(E.entropy(coef, W, H, layout, dri)[0]), name
+        assert max(slots) <= 2 * E.SLOT_BYTES + 2

@@ -208,6 +208,9 @@ SIGNATURES = {
     # csrc/travel.hip)
     "vdx_text_travel_f16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vdx_cross_attn_block_pack_kv_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # regional prompts: the per-pixel blend of the cross-attention sub-block's per-text results (no reference counterpart;
+    # vdx/region.py, csrc/region.hip)
+    "vdx_region_blend_f16": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

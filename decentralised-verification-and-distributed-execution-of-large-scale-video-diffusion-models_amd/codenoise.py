@@ -347,7 +347,8 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     (frames `s + f * d`), the step is `step_cfg_strided`, and the record gains `"context_stride"`: the levels, their strides and
     the fused windows as [s, L, d]; still one gather per step, and the mask step on the whole clip as without it.
     `d.travel` (prompt travel, vdx/travel.py): every window is called with its own text, `d.window_text` of its (s, L, d, ring),
-    built once; every tile of a window shares the window's text; nothing else changes."""
+    built once; every tile of a window shares the window's text; nothing else changes.
+    `d.regions` (regional prompts, vdx/region.py): every window's UNet call gains `d.region_kw` of its (s, L, d, ring)."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
@@ -402,11 +403,20 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
         texts = [d.window_text(s, L, 1, True) for s, L in spans]
     else:
         texts = [d.window_text(s, e - s) for s, e in spans]
+    # regional prompts: every window's UNet call gains the plan and the window's place in the clip ({} when off; never with tiles)
+    if getattr(d, "regions", None) is None:
+        region_kws = [{}] * len(spans)
+    elif strided is not None:
+        region_kws = [d.region_kw(s, L, dd) for s, L, dd in spans]
+    elif loop:
+        region_kws = [d.region_kw(s, L, 1, True) for s, L in spans]
+    else:
+        region_kws = [d.region_kw(s, e - s) for s, e in spans]
     t_round = time.time()
     for i, t in enumerate(d.schedule):
         for j, span in enumerate(spans):
             for k, box in enumerate(boxes):
-                noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=texts[j]).sample
+                noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=texts[j], **region_kws[j]).sample
                 local[j, k * slot:k * slot + noise.numel()].copy_(noise.reshape(-1))
         delay = emu_gather_delay_s(payload_step, cfg)             # per step: one exchange per step is what the method costs
         if delay > 0:

@@ -2098,3 +2098,41 @@ def cross_attn_block_pack_kv(k_rows, vt, n_items: int, text_pad: int, out=None):
         raise VdxError(f"cross_attn_block_pack_kv: out must be contiguous {shape}")
     _launch("vdx_cross_attn_block_pack_kv_f16", _p(k_rows, "k_rows"), ldk, _p(vt, "vt"), ldvt, int(n_items), int(text_pad), inner, _p(out, "out"))
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Regional prompts: the per-pixel blend of the cross-attention sub-block's per-text results (vdx/region.py, csrc/region.hip; no
+# reference counterpart)
+def region_blend(inputs, table, s: int, L: int, d: int = 1, ring: bool = False, out=None):
+    """One window's blend in one launch (include/vdx.h `vdx_region_blend_f16`).  `inputs`: a sequence of 1 to 8 entries, entry j
+    the sub-block's rows for text j, fp16 contiguous [L * S][C], or None for a text that was not launched (no weight on any cell
+    of the window: it is skipped whatever the table holds); `table`: fp32 contiguous (T, S, len(inputs)) on the device, the
+    level's weights (`region.RegionPlan.to`).  Row (f, p) takes the weights of the clip frame `s + f * d` (`ring`: mod T).
+    `out`: fp16 [L * S][C], which may be `inputs[0]` (or any one input); by default a new tensor."""
+    n_in = len(inputs)
+    if not 1 <= n_in <= 8:
+        raise VdxError(f"region_blend: {n_in} inputs, 1 to 8 are taken (the base text and at most 7 regions)")
+    given = [t for t in inputs if t is not None]
+    if not given:
+        raise VdxError("region_blend: every input is None")
+    if table.dim() != 3 or table.shape[2] != n_in or table.dtype != torch.float32 or not table.is_contiguous() or not table.is_cuda:
+        raise VdxError(f"region_blend: the table must be a contiguous fp32 GPU tensor (T, S, {n_in}), got {tuple(table.shape)} {table.dtype}")
+    T, S = int(table.shape[0]), int(table.shape[1])
+    s, L, d = int(s), int(L), int(d)
+    if L < 1 or d < 1 or not 0 <= s < T or s + (L - 1) * d >= (2 * T if ring else T):
+        raise VdxError(f"region_blend: bad window start {s}, length {L}, stride {d}{' on the ring' if ring else ''} of {T} frames")
+    M, Cc = L * S, int(given[0].shape[-1])
+    if out is None:
+        out = torch.empty((M, Cc), dtype=torch.float16, device=table.device)
+    align = 16 if Cc % 8 == 0 else (8 if Cc % 4 == 0 else 2)
+    for t, name in [(t, f"input {j}") for j, t in enumerate(inputs) if t is not None] + [(out, "out")]:
+        if not t.is_cuda or t.dtype != torch.float16 or t.device != table.device:
+            raise VdxError(f"region_blend: {name} must be an fp16 tensor on the table's device")
+        if tuple(t.shape) != (M, Cc) or not t.is_contiguous():
+            raise VdxError(f"region_blend: {name} must be contiguous ({M}, {Cc}), got {tuple(t.shape)}")
+        if t.data_ptr() % align:
+            raise VdxError(f"region_blend: {name} must be {align}-byte aligned at C = {Cc}")
+    ptrs = (C.c_void_p * n_in)(*[None if t is None else t.data_ptr() for t in inputs])
+    with torch.cuda.device(table.device):
+        _launch("vdx_region_blend_f16", ptrs, n_in, _p(table, "table", torch.float32), T, s, L, d, int(bool(ring)), S, Cc, out.data_ptr())
+    return out

@@ -224,6 +224,17 @@ def check_prompt_travel(cfg) -> Optional[Tuple[Tuple[int, str], ...]]:
     return keys_of(cfg)
 
 
+def check_regions(cfg):
+    """`cfg.regions` as the job's `region.RegionPlan` (None when off): the per-level weight tables and launch flags of the masks
+    and the regions' texts, computed once, on the host; `ValueError` before any work for a malformed entry, a text that is no
+    string, a mask of the wrong dtype or shape, more than 7 regions, an (H, W) or T that does not match the job, and with `tile` or
+    `prompt_travel` (vdx/region.py)."""
+    if getattr(cfg, "regions", None) is None:
+        return None
+    from .region import UNET_LEVELS, VAE_SCALE, check_regions as check, region_plan
+    return region_plan(check(cfg), cfg.num_frames, cfg.height // VAE_SCALE, cfg.width // VAE_SCALE, UNET_LEVELS)
+
+
 # ---- the resolved job ---------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class JobOptions:
@@ -244,6 +255,7 @@ class JobOptions:
     guidance_rescale: float = 0.0
     guidance: dict = field(default_factory=dict)       # the keys the result and the records gain: negative_prompt, guidance_rescale
     prompt_travel: Optional[Tuple[Tuple[int, str], ...]] = None     # the keys, sorted, the prompt at frame 0 among them
+    regions: Optional[object] = None                                # regional prompts: the job's `region.RegionPlan` (host tables)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -270,6 +282,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
             raise ValueError(f"negative_prompt must be a string, got {cfg.negative_prompt!r}")
         guidance = {"negative_prompt": cfg.negative_prompt} if cfg.negative_prompt else {}
         travel = check_prompt_travel(cfg)
+        regions = check_regions(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -278,11 +291,12 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
             raise ValueError(f"unknown exchange {exchange!r}")
         factor, pixel_mask, phi, guidance = cfg.interpolate, None, float(cfg.guidance_rescale), {}
         travel = check_prompt_travel(cfg)
+        regions = check_regions(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
-                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel)
+                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -302,6 +316,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
         if opts.context_stride > 1:
             out["context_stride"] = out["co_denoise"]["context_stride"] = first["context_stride"]
     out.update(travel_record(opts))
+    out.update(region_record(opts))
     return out
 
 
@@ -318,6 +333,17 @@ def travel_record(src) -> dict:
         return {}
     from .travel import record
     return {"prompt_travel": record(src.prompt_travel)}
+
+
+def region_record(src) -> dict:
+    """`{"regions": {"count", "texts", "coverage"}}` beside `record_options`' entries, only when the option is set (else {}):
+    from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"regions": src["regions"]} if "regions" in src else {}
+    if src.regions is None:
+        return {}
+    from .region import record
+    return record(src.regions)
 
 
 def record_options(res: dict) -> dict:

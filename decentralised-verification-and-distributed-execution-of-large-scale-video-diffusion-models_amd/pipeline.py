@@ -37,7 +37,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, record_options, resolve, travel_record, world_size
+from .options import info_options, record_options, region_record, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -123,6 +123,12 @@ class DiffuserConfig:
     # conditioned on the linear blend of their CLIP embeddings, a frame after the last key on the last key (with `loop`: on the
     # blend back to the first), in every window of every mode.  None = one prompt for the whole clip, as always
     prompt_travel: Optional[Tuple[Tuple[int, str], ...]] = None
+    # regional prompts (vdx/region.py, csrc/region.hip; "attention couple" / regional conditioning, unpinned): ((mask, text), ...),
+    # up to 7; a mask is a uint8 / bool array (H, W) or (T, H, W) in pixels, 0..255 (soft edges allowed), or the path of a .npy
+    # file that holds one.  In every spatial cross-attention the conditional item's pixels under a mask are conditioned on that
+    # region's text, the rest on `prompt`, in every window of every mode.  Not with `tile` or `prompt_travel`.  None = one prompt
+    # for the whole frame, as always
+    regions: Optional[tuple] = None
 
     @property
     def use_fsdp(self):
@@ -258,7 +264,8 @@ def gather_chunks(mine: List[torch.Tensor], chunk_plan: ChunkPlan, rank: int, wo
 
 
 class DistributedVideoDiffuser:
-    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None, latent_mask=None, travel=None):
+    def __init__(self, cfg: DiffuserConfig, unet, scheduler, uncond_emb, cond_emb, init_latents=None, latent_mask=None, travel=None,
+                 regions=None):
         """`init_latents` (video-to-video): the scaled clean latent (1,C,T,h,w) fp16 of the whole clip (every rank encodes the
         whole clip: identical bits on every rank, no collective).  The denoise then runs `vid2vid_timesteps(cfg.strength)`
         from add_noise(init_latents, base, t_first) (base = the seeded noise of text-to-video); with `hybrid_ctx`, ctx is the
@@ -268,7 +275,10 @@ class DistributedVideoDiffuser:
         next timestep with `base` (to `init_latents` itself after the last one), and pasted again after the blend.  None: off.
         `travel` (prompt travel, vdx/travel.py): (key_embs, plan), the keys' text embeddings fp16 (n_keys, N, D) on the device in
         the order of the plan's frames and the `travel.TravelPlan` of the clip.  Every window's UNet text is then built once, by
-        `ops.text_travel` (`window_text`), and passed where `cat([uncond_emb, cond_emb])` is passed without it.  None: off."""
+        `ops.text_travel` (`window_text`), and passed where `cat([uncond_emb, cond_emb])` is passed without it.  None: off.
+        `regions` (regional prompts, vdx/region.py): (region_embs, plan), the regions' text embeddings fp16 (R, N, D) and the
+        `region.RegionPlan` of the clip.  Every UNet call then gains `regions=(region_embs, plan, its window)` (`region_kw`).
+        None: off."""
         self.cfg = cfg
         check_freeu(cfg)
         check_tome(cfg)
@@ -299,6 +309,16 @@ class DistributedVideoDiffuser:
                 raise ValueError(f"travel: {tuple(key_embs.shape)} key embeddings for a plan of {len(tplan.frames)} keys and {tplan.T} "
                                  f"frames; the clip has {cfg.num_frames}")
             self.travel = (key_embs.to(cfg.device, torch.float16).contiguous(), tplan.to(cfg.device))
+        self.regions = None                                           # regional prompts only: (region_embs, the plan on the device)
+        if regions is not None:
+            if travel is not None:
+                raise ValueError("regions cannot be combined with prompt travel")
+            region_embs, rplan = regions
+            if (region_embs.dim() != 3 or region_embs.shape[0] != rplan.n_texts - 1 or rplan.T != cfg.num_frames
+                    or (rplan.h, rplan.w) != (cfg.height // 8, cfg.width // 8)):
+                raise ValueError(f"regions: {tuple(region_embs.shape)} text embeddings for a plan of {rplan.n_texts - 1} regions, {rplan.T} "
+                                 f"frames and latent {rplan.h}x{rplan.w}; the clip has {cfg.num_frames} frames of {cfg.height // 8}x{cfg.width // 8}")
+            self.regions = (region_embs.to(cfg.device, torch.float16).contiguous(), rplan.to(cfg.device))
         shape = self.latent_shape if init_latents is not None or cfg.use_ctx else None
         if init_latents is not None:
             if tuple(init_latents.shape) != shape:
@@ -351,9 +371,19 @@ class DistributedVideoDiffuser:
                                                             lo, hi, w, *key)
         return text
 
-    def denoise(self, lat: torch.Tensor, s: Optional[int] = None, text: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def region_kw(self, s: int, L: int, d: int = 1, ring: bool = False) -> dict:
+        """Regional prompts: what the UNet call of the window of the clip frames `s + f * d` (`ring`: mod T) gains; {} when off."""
+        if self.regions is None:
+            return {}
+        return {"regions": (*self.regions, (int(s), int(L), int(d), bool(ring)))}
+
+    def denoise(self, lat: torch.Tensor, s: Optional[int] = None, text: Optional[torch.Tensor] = None, window=None) -> torch.Tensor:
         """Reference `_denoise` (:129-143) for one chunk.  `s` (masked video-to-video only, with a `latent_mask`): the chunk's
-        first frame in the clip; None: the masked path is off.  `text` (prompt travel): the chunk's `window_text`."""
+        first frame in the clip; None: the masked path is off.  `text` (prompt travel): the chunk's `window_text`.  `window`
+        (regional prompts; required with them): the chunk's (s, L) in the clip."""
+        if self.regions is not None and window is None:
+            raise ValueError("denoise: with regions the chunk's window (s, L) in the clip must be given: the masks are per clip frame")
+        region_kw = self.region_kw(*window) if window is not None else {}
         masked = s is not None and self.latent_mask is not None
         cfg, sched = self.cfg, self.scheduler
         emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0) if text is None else text
@@ -363,7 +393,7 @@ class DistributedVideoDiffuser:
             reset()
         for i, t in enumerate(self.schedule):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
-            noise = self.unet(x, t, encoder_hidden_states=emb).sample
+            noise = self.unet(x, t, encoder_hidden_states=emb, **region_kw).sample
             lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale, **self._rescale_kw)
             if masked:
                 self._mask_step(lat, i, s)
@@ -421,7 +451,9 @@ class DistributedVideoDiffuser:
         _, C, T, H, W = start.shape
         t0 = time.time()
         masked = self.latent_mask is not None
-        if self.travel is None:             # the call as it always was
+        if self.regions is not None:        # regional prompts: every window with its place in the clip
+            mine = [self.denoise(start[:, :, s:e].clone(), s if masked else None, None, (s, e - s)) for s, e in cp.for_rank(self.rank)]
+        elif self.travel is None:           # the call as it always was
             mine = [self.denoise(start[:, :, s:e].clone(), *((s,) if masked else ())) for s, e in cp.for_rank(self.rank)]
         else:                               # prompt travel: every window with its own text
             mine = [self.denoise(start[:, :, s:e].clone(), s if masked else None, self.window_text(s, e - s)) for s, e in cp.for_rank(self.rank)]
@@ -626,13 +658,16 @@ def build_arg_parser():
     p.add_argument("--prompt_at", nargs=2, action="append", default=None, metavar=("FRAME", "TEXT"),
                    help="prompt travel: TEXT is the prompt at frame FRAME, frames between two such keys blend them (repeatable; "
                         "--prompt is the key at frame 0 unless one names it; default: off)")
+    p.add_argument("--region", nargs=2, action="append", default=None, metavar=("MASK.npy", "TEXT"),
+                   help="regional prompt: the pixels under the mask (uint8 (H, W) or (T, H, W), 0..255) are conditioned on TEXT, the "
+                        "rest on --prompt (repeatable, up to 7; not with --tile or --prompt_at; default: off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
     return p
 
 
-FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None, "prompt_travel": "prompt_at"}     # where the flag's name is not the field's; None: no flag
+FLAG_OF_FIELD = {"free_init_iters": "free_init", "overlap_rule": None, "prompt_travel": "prompt_at", "regions": "region"}     # where the flag's name is not the field's; None: no flag
 
 
 def config_from_args(a) -> DiffuserConfig:
@@ -654,6 +689,8 @@ def config_from_args(a) -> DiffuserConfig:
             except ValueError:
                 return v
         cfg.prompt_travel = tuple((frame(f), text) for f, text in cfg.prompt_travel)
+    if cfg.regions is not None:
+        cfg.regions = tuple((mask, text) for mask, text in cfg.regions)
     return cfg
 
 
@@ -788,14 +825,18 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
         m.to(dev)
     tok = pipe.tokenizer
     texts = [cfg.prompt, cfg.negative_prompt] + [text for _, text in opts.prompt_travel or ()]     # one text-encoder call
+    if opts.regions is not None:                # (never with prompt travel: `check_regions`)
+        texts += list(opts.regions.texts)
     ids = tok(texts, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
     with torch.no_grad():
         emb = pipe.text_encoder(ids.to(dev))[0]
     cond, uncond = emb[:1].contiguous(), emb[1:2].contiguous()
-    travel = {}
+    text_kw = {}
     if opts.prompt_travel is not None:
         from .travel import travel_plan
-        travel = {"travel": (emb[2:].contiguous(), travel_plan(opts.prompt_travel, cfg.num_frames, loop=loop))}
+        text_kw = {"travel": (emb[2:].contiguous(), travel_plan(opts.prompt_travel, cfg.num_frames, loop=loop))}
+    if opts.regions is not None:
+        text_kw = {"regions": (emb[2:].contiguous(), opts.regions)}
     init_latents, encode_s, masking = None, 0.0, {}
     if pixel_mask is not None:
         init_latents, encode_s, originals = encode_init_video(cfg, pipe.vae, dev, return_frames=True)
@@ -804,7 +845,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     elif cfg.init_video is not None:
         init_latents, encode_s = encode_init_video(cfg, pipe.vae, dev)
     d = DistributedVideoDiffuser(cfg, unet, make_scheduler(cfg.scheduler, pipe.scheduler), uncond, cond, init_latents=init_latents,
-                                 **masking, **travel)
+                                 **masking, **text_kw)
     out, info = d(exchange=exchange, options=opts)
     ranges = info["ranges"]
     if exchange == "allgather":
@@ -856,7 +897,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
-            **record_options({**info, **mask, **opts.guidance}), **travel_record(info)}
+            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info)}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -885,7 +926,7 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {**record_options(res), **travel_record(res)}
+        source = {**record_options(res), **travel_record(res), **region_record(res)}
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -905,7 +946,7 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update({**record_options(res), **travel_record(res)})
+            rec.update({**record_options(res), **travel_record(res), **region_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -93,6 +93,7 @@ class UNet3DConditionModel(nn.Module):
         self._text_store: List[tuple] = []     # the other kept texts' (_text_ref, _text_kv), most recently used first
         self.text_cache_misses = 0             # forwards that had to project their text's keys / values
         self._text_per_frame = False           # the forward's text is (B, F, N, D): one K / V item per frame (prompt travel)
+        self._regions = None                   # the forward's regional prompts: (R, the device RegionPlan, (s, L, d, ring)); None: off
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
         self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
         self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
@@ -669,6 +670,8 @@ class UNet3DConditionModel(nn.Module):
         if k5 and kvb is None:
             kvb = (ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv)(k, vt, nb, TEXT_PAD)
             self._text_kv[p] = (k, vt, kvb)
+        if self._regions is not None:
+            return self._regional_cross_attention(b, p, t, x, k, vt, kvb if k5 else None, nb, n_img, S, M, M_out, dup)
         if k5:
             # K5 (level 0): LayerNorm -> q -> softmax(q K^T) V -> to_out + residual in one kernel; the text keys / values were
             # packed once per prompt.  A shared-prefix batch (`dup`): the same rows against each item's text in turn (per-frame
@@ -701,6 +704,59 @@ class UNet3DConditionModel(nn.Module):
         t = ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=M, bias=W[b + ".attn2.to_out.0.bias"], residual=t)
         del o
         return self._ff_proj_out(b, p, t, x, M)
+
+    def _regional_cross_attention(self, b, p, t, x, k, vt, kvb, nb, n_img, S, M, M_out, dup):
+        """The cross-attention sub-block and the transformer's end with regional prompts (vdx/region.py): the K / V items are the
+        batch's own texts followed by the R region texts.  Every item but the last (the conditional one; at batch 1 the only one)
+        runs its sub-block as always, one launch set per item.  The conditional item's rows run it once per text j with a non-zero
+        weight somewhere on the window's frames at this level (the plan's flags: the others are not launched), j = 0 its own
+        text, and `ops.region_blend` blends the results per pixel into its rows of t2; where one text has all the weight, its
+        result IS the rows (weight exactly 1.0f everywhere) and no blend runs.  `kvb`: K5's key / value blobs where K5 runs,
+        else None: LayerNorm and the query projection once, then flash attention and `to_out` + residual per text.  `dup`: t
+        holds one item's rows, which stand for both items."""
+        W = self.W
+        R, plan, (ws, wL, wd, wring) = self._regions
+        B = nb - R
+        C = t.shape[1]
+        heads = C // 64
+        scale = 64 ** -0.5
+        Mi = M if dup else M // B                                  # rows of one item
+        ni = n_img if dup else n_img // B                          # images of one item
+        level = self._level_down_of(p).bit_length() - 1
+        table = plan.tables[level]
+        if table.shape[1] != S:
+            raise VdxError(f"regions: the plan's level {level} has {table.shape[1]} cells, the UNet's grid there {S}")
+        active = plan.active(level, ws, wL, wd, wring)             # ascending j; never empty: the weights of a cell sum to 1
+        t2 = torch.empty((M_out, C), dtype=torch.float16, device=t.device)
+        q = None
+        if kvb is None:
+            ln = ops.layernorm(t, W[b + ".norm2.weight"], W[b + ".norm2.bias"], M=M)
+            q = ops.gemm(ln, W[b + ".attn2.to_q.weight"], M=M)
+            del ln
+
+        def sub_block(i, item, out):
+            """`t + attn2(norm2(t), text item)` on batch item i's rows -> out"""
+            rows = t if dup else t[i * Mi:(i + 1) * Mi]
+            if kvb is not None:
+                ops.cross_attn_block(rows, W[b + ".attn2.k5"], kvb[item:item + 1], kv_len=self._text_len, n_items=1, rows_per_item=Mi, out=out)
+                return
+            qi = q if dup else q[i * Mi:(i + 1) * Mi]
+            o = ops.flash_attn(qi, k[item * TEXT_PAD:(item + 1) * TEXT_PAD], vt[:, item * TEXT_PAD:(item + 1) * TEXT_PAD], n_seq=ni, sq=S,
+                               skv=self._text_len, skv_pad=TEXT_PAD, heads=heads, seq_per_kv=ni, scale=scale)
+            ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=Mi, bias=W[b + ".attn2.to_out.0.bias"], residual=rows, out=out)
+
+        for i in range(B - 1):
+            sub_block(i, i, t2[i * Mi:(i + 1) * Mi])
+        ci = B - 1
+        dst = t2[ci * Mi:(ci + 1) * Mi]
+        subs = [None] * (R + 1)
+        for n, j in enumerate(active):
+            subs[j] = dst if n == 0 else torch.empty((Mi, C), dtype=torch.float16, device=t.device)
+            sub_block(ci, ci if j == 0 else B + j - 1, subs[j])
+        if len(active) > 1:
+            ops.region_blend(subs, table, ws, wL, wd, wring, out=dst)          # in place on the first launched text's result
+        del q, subs
+        return self._ff_proj_out(b, p, t2, x, M_out, xrows=M)
 
     def _temporal_transformer(self, p, x, B, F, S, heads, part=0, ksplit_ok=True):
         W, g = self.W, self.cfg.norm_num_groups
@@ -741,7 +797,12 @@ class UNet3DConditionModel(nn.Module):
         return ops.timestep_embedding(t.contiguous(), B, self.cfg.block_out_channels[0])
 
     @torch.no_grad()
-    def forward(self, sample, timestep, encoder_hidden_states, **_unused):
+    def forward(self, sample, timestep, encoder_hidden_states, regions=None, **_unused):
+        """`regions` (regional prompts, vdx/region.py; None, the default: off, and not one launch differs):
+        `(text, plan, (s, L, d, ring))` — the R region texts' embeddings fp16 (R, N, D) with the N of `encoder_hidden_states`
+        (which must be (B, N, D): one text per sample), the `region.RegionPlan` of the clip moved to the device (`plan.to`), and
+        the window this sample's F = L frames are of the clip: frame f is the clip frame `s + f d` (`ring`: mod T).  They apply
+        to the LAST item of the batch: the conditional one of a CFG batch of two, the only one at batch 1."""
         if not self.W:
             raise VdxError("UNet3DConditionModel: no weights loaded (load_diffusers_state_dict)")
         if not sample.is_cuda:
@@ -773,6 +834,26 @@ class UNet3DConditionModel(nn.Module):
         self._text_len = ehs.shape[-2]
         self._text_per_frame = per_frame
         nt = B * F if per_frame else B          # K / V items
+        self._regions = rtext = rtext_in = None
+        if regions is not None:
+            rtext_in, rplan, window = regions
+            if per_frame:
+                raise VdxError("regions need one text per sample: encoder_hidden_states (B, N, D), not per-frame text")
+            rtext = rtext_in.to(device=dev, dtype=torch.float16)
+            if rtext.dim() != 3 or tuple(rtext.shape[1:]) != tuple(ehs.shape[1:]) or not 1 <= rtext.shape[0] <= 7:
+                raise VdxError(f"regions: text shape {tuple(rtext.shape)} does not fit (1..7, {ehs.shape[1]}, {ehs.shape[2]})")
+            R = rtext.shape[0]
+            ws, wL, wd, wring = (int(window[0]), int(window[1]), int(window[2]), bool(window[3]))
+            if not getattr(rplan, "on_device", False) or any(t.device != dev for t in rplan.tables):
+                raise VdxError("regions: the plan's tables must be on the sample's device (RegionPlan.to)")
+            if rplan.n_texts != R + 1 or (rplan.h, rplan.w) != (H, Wd) or rplan.levels < nlev:
+                raise VdxError(f"regions: a plan of {rplan.n_texts - 1} regions, latent {rplan.h}x{rplan.w} and {rplan.levels} levels for "
+                               f"{R} texts, latent {H}x{Wd} and {nlev} levels")
+            if wL != F or wd < 1 or not 0 <= ws < rplan.T or ws + (wL - 1) * wd >= (2 * rplan.T if wring else rplan.T):
+                raise VdxError(f"regions: window (start {ws}, length {wL}, stride {wd}{', ring' if wring else ''}) for a sample of {F} "
+                               f"frames and a clip of {rplan.T}")
+            self._regions = (R, rplan, (ws, wL, wd, wring))
+            nt = B + R                           # the batch's own texts, then the region texts: their K / V come from the same GEMMs
         # The text keys / values of the 16 cross-attentions depend on the prompt only: they are projected once and kept
         # while the caller keeps passing the SAME tensor object, unmodified (identity + version, not the address: a new
         # tensor may reuse a freed address with other contents).  `pipeline.denoise` and bench.py pass one tensor for
@@ -788,9 +869,17 @@ class UNet3DConditionModel(nn.Module):
         except Exception:       # inference-mode tensors do not track versions
             ver = None
         key = (tuple(ehs.shape), dev)
+        rver = None
+        if rtext is not None:                   # the region texts are part of what is cached: known by identity + version as well
+            try:
+                rver = rtext_in._version
+            except Exception:       # no version counter (inference mode): this forward is not cached, as for such a text above
+                ver = None
+            key = key + (tuple(rtext.shape),)
 
         def same(r):
-            return r is not None and ver is not None and r[0] is encoder_hidden_states and r[1] == ver and r[2] == key
+            return (r is not None and ver is not None and r[0] is encoder_hidden_states and r[1] == ver and r[2] == key
+                    and (rtext is None or (r[4] is rtext_in and r[5] == rver)))
 
         if not same(ref):
             slots = max(1, int(self.text_cache_slots))
@@ -801,8 +890,12 @@ class UNet3DConditionModel(nn.Module):
             del self._text_store[slots - 1:]
             if entry is None:
                 ehs_pad = torch.zeros((nt * TEXT_PAD, c.cross_attention_dim), dtype=torch.float16, device=dev)
-                ehs_pad.view(nt, TEXT_PAD, -1)[:, :self._text_len] = ehs.reshape(nt, self._text_len, -1)
-                entry = ((encoder_hidden_states, ver, key, ehs_pad), {})
+                if rtext is None:
+                    ehs_pad.view(nt, TEXT_PAD, -1)[:, :self._text_len] = ehs.reshape(nt, self._text_len, -1)
+                else:
+                    ehs_pad.view(nt, TEXT_PAD, -1)[:B, :self._text_len] = ehs
+                    ehs_pad.view(nt, TEXT_PAD, -1)[B:, :self._text_len] = rtext
+                entry = ((encoder_hidden_states, ver, key, ehs_pad, rtext_in, rver), {})
                 self.text_cache_misses += 1
             self._text_ref, self._text_kv = entry
         ehs_pad = self._text_ref[3]

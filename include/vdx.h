@@ -877,6 +877,26 @@ int vdx_cross_attn_block_pack_kv_f16(const void* k_rows, int ldk, const void* vt
                                      void* out, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Regional prompts: per-region text through every spatial cross-attention (nothing in the reference: it conditions every
+ * pixel of a frame on one prompt; "attention couple" / regional conditioning of ComfyUI and AnimateDiff-Evolved, unpinned;
+ * vdx/region.py, the job's --region, csrc/region.hip).  tests/region_ref.py states the weights and the blend.  No atomics:
+ * the same bits on every run.
+ * ------------------------------------------------------------------------------------------ */
+/* The per-pixel blend of one window's cross-attention sub-block results.  in: a HOST array of n_in device pointers
+ * (1 <= n_in <= 8: the base text and at most 7 regions), in[j] fp16 [L S][C] contiguous, the sub-block evaluated with text j,
+ * or NULL for a text that was not launched (no weight on any cell of the window); table: fp32 [T][S][n_in] on the device, the
+ * level's weights of vdx/region.py `region_plan`; out: fp16 [L S][C], which may be in[0] (or any one input).  Row (f, p) is the clip frame
+ * tau = s + f d (with `ring`, tau - T where that is >= T), clamped to [0, T).  out[row] is in[j][row]'s bits for the first j
+ * with table[tau][p][j] == 1.0f, else
+ *   fp16( ... fp32( fp32( w_a fp32(in[a][row]) ) + fp32( w_b fp32(in[b][row]) ) ) ... )
+ * over the j with a non-zero weight (and a non-NULL input) in ascending order, every product and every sum rounded on its own;
+ * a zero-weight input is not read for that row.  0 <= s < T, L >= 1, d >= 1, s + (L - 1) d < T (with `ring`: < 2 T).
+ * A block owns whole rows (groups of consecutive rows, never a part of one).  16 bytes per lane where C % 8 == 0 (inputs and
+ * out then 16-byte aligned), 8 where C % 4 == 0 (8-byte aligned), else one element.                                                                                                                  */
+int vdx_region_blend_f16(const void* const* in, int n_in, const float* table, int T, int s, int L, int d, int ring, int S, int C,
+                         void* out, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

@@ -36,6 +36,7 @@ from .. import scheduler as _sched
 from .. import unet3d as _unet
 from .. import vae as _vae
 from .. import weights as _weights
+from .._lib import VdxError as _VdxError
 
 __version__ = "0.0-vdx-shim"
 
@@ -168,10 +169,16 @@ def _clip_config(d):
 
 
 class DiffusionPipeline:
-    def __init__(self, unet, text_encoder, vae, tokenizer, scheduler, synthetic):
+    def __init__(self, unet, text_encoder, vae, tokenizer, scheduler, synthetic, sources=None):
         self.unet, self.text_encoder, self.vae = unet, text_encoder, vae
         self.tokenizer, self.scheduler = tokenizer, scheduler
         self.synthetic_weights = synthetic
+        # LoRA adapters (vdx/lora.py).  `sources`: {"unet" | "text_encoder": a callable that returns the component's base state
+        # dict again} (the checkpoint's files, or the synthetic seeds and configs): no base copy is kept resident
+        self._sources = dict(sources or {})
+        self._lora = {}                 # name -> lora.LoraAdapter, in the order they were loaded
+        self._lora_active = []          # [(name, weight)]: what set_adapters asked for
+        self._lora_loaded = {"unet": (), "text_encoder": ()}    # per component, the (name, weight) pairs merged into its weights now
 
     @classmethod
     def from_pretrained(cls, model_id, torch_dtype=None, low_cpu_mem_usage=True, use_safetensors=None, device_map=None,
@@ -196,6 +203,8 @@ class DiffusionPipeline:
         sched_kw, tokenizer, synthetic = {}, None, True
         if os.path.isdir(str(model_id)):
             d = str(model_id)
+            sources = {"unet": lambda: _load_file([f"{d}/unet/diffusion_pytorch_model.safetensors", f"{d}/unet/diffusion_pytorch_model.bin"]),
+                       "text_encoder": lambda: _load_file([f"{d}/text_encoder/model.safetensors", f"{d}/text_encoder/pytorch_model.bin"])}
             usd = _load_file([f"{d}/unet/diffusion_pytorch_model.safetensors", f"{d}/unet/diffusion_pytorch_model.bin"])
             tsd = _load_file([f"{d}/text_encoder/model.safetensors", f"{d}/text_encoder/pytorch_model.bin"])
             vsd = _load_file([f"{d}/vae/diffusion_pytorch_model.safetensors", f"{d}/vae/diffusion_pytorch_model.bin"])
@@ -217,10 +226,12 @@ class DiffusionPipeline:
             if str(model_id) != "synthetic:tiny":
                 warnings.warn(f"diffusers shim: {model_id!r} is not a local directory and nothing can be downloaded here — "
                               "using seeded SYNTHETIC weights of the Zeroscope architecture and a hash tokenizer")
+            sources = {"unet": lambda: _weights.synthetic_state_dict(unet.cfg, 1234, "cpu"),
+                       "text_encoder": lambda: _weights.synthetic_clip_state_dict(text.cfg, 11, "cpu")}
             unet.load_diffusers_state_dict(_weights.synthetic_state_dict(unet.cfg, 1234, "cpu"), device="cpu")
             text.load_transformers_state_dict(_weights.synthetic_clip_state_dict(text.cfg, 11, "cpu"), device="cpu")
             vae.load_diffusers_state_dict(_weights.synthetic_vae_state_dict(vae.cfg, 7, "cpu"), device="cpu")
-        return cls(unet, text, vae, tokenizer or HashTokenizer(), DDIMScheduler(**sched_kw), synthetic)
+        return cls(unet, text, vae, tokenizer or HashTokenizer(), DDIMScheduler(**sched_kw), synthetic, sources=sources)
 
     def to(self, device):
         for m in (self.unet, self.text_encoder, self.vae):
@@ -242,6 +253,106 @@ class DiffusionPipeline:
 
     def disable_tome(self):
         self.unet.disable_tome()
+
+    # ------------------------------------------------------------------------------------------
+    # LoRA adapters (diffusers' LoraLoaderMixin surface, unpinned; vdx/lora.py, csrc/lora.hip).  Adapters here are always fused:
+    # a change of the active set re-obtains the component's base state dict from where `from_pretrained` got it, merges the
+    # active adapters into it on the GPU and hands the result to the component's own loader, which packs it like any checkpoint
+    # (and clears the UNet's text K / V cache, as it always does).
+    # ------------------------------------------------------------------------------------------
+    def _lora_refuse_sharded(self, what):
+        if not isinstance(self.unet.W, dict):
+            raise _VdxError(f"{what}: the UNet's weights are sharded (shard_): adapters change before the diffuser is built, "
+                            "never after")
+
+    def load_lora_weights(self, path_or_dict, adapter_name=None, device=None):
+        """diffusers' `load_lora_weights(path_or_dict, adapter_name=...)`: read the adapter (`lora.read_lora`: a local
+        `.safetensors` / `torch.load` file or a dict, peft / diffusers or kohya keys; every refusal names the key), add it to the
+        active set at weight 1.0 beside the adapters already active, and merge.  `adapter_name`: default `default_<n>`, as
+        diffusers numbers them.  `device`: the GPU the merge runs on (default: the component's, else the current one)."""
+        from .. import lora as _lora
+        self._lora_refuse_sharded("load_lora_weights")
+        name = f"default_{len(self._lora)}" if adapter_name is None else adapter_name
+        if name in self._lora:
+            raise ValueError(f"load_lora_weights: an adapter named {name!r} is already loaded")
+        if len(self._lora_active) >= _lora.MAX_ADAPTERS:
+            raise ValueError(f"load_lora_weights: {_lora.MAX_ADAPTERS} adapters are active already, the most a merge takes")
+        adapter = _lora.read_lora(path_or_dict, name, unet_cfg=self.unet.cfg, text_cfg=self.text_encoder.cfg)
+        self._lora[name] = adapter
+        try:
+            self._lora_apply(self._lora_active + [(name, 1.0)], device)
+        except Exception:
+            del self._lora[name]
+            raise
+        return adapter
+
+    def set_adapters(self, adapter_names, adapter_weights=None, device=None):
+        """diffusers' `set_adapters(names, adapter_weights=None)`: the active set is exactly `names` (a name or a list, at most 8,
+        each loaded, none twice) at `adapter_weights` (a number or one per name; default 1.0).  A weight of 0 is the base, bit for
+        bit.  The components whose merged set changes are re-loaded; the others are left as they are."""
+        import math
+        self._lora_refuse_sharded("set_adapters")
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None:
+            weights = [1.0] * len(names)
+        elif isinstance(adapter_weights, (int, float)):
+            weights = [float(adapter_weights)] * len(names)
+        else:
+            weights = [float(w) for w in adapter_weights]
+        if len(weights) != len(names):
+            raise ValueError(f"set_adapters: {len(names)} names and {len(weights)} weights")
+        if len(set(names)) != len(names):
+            raise ValueError(f"set_adapters: a name is given twice: {names}")
+        for n, w in zip(names, weights):
+            if n not in self._lora:
+                raise ValueError(f"set_adapters: no adapter named {n!r} is loaded (loaded: {list(self._lora)})")
+            if not math.isfinite(w):
+                raise ValueError(f"set_adapters: the weight of {n!r} is not finite: {w!r}")
+        self._lora_apply(list(zip(names, weights)), device)
+
+    def get_active_adapters(self):
+        """diffusers' `get_active_adapters()`: the names of the active set, in `set_adapters`' order."""
+        return [n for n, _ in self._lora_active]
+
+    def fuse_lora(self, lora_scale=1.0):
+        """diffusers' `fuse_lora(lora_scale)`: adapters here are always fused, so this sets every loaded adapter active at
+        `lora_scale`."""
+        self.set_adapters(list(self._lora), float(lora_scale))
+
+    def unfuse_lora(self):
+        """diffusers' `unfuse_lora()`: `set_adapters([])`, the base weights, bit for bit."""
+        self.set_adapters([])
+
+    def unload_lora_weights(self):
+        """diffusers' `unload_lora_weights()`: the base weights again, bit for bit, and no adapter stays loaded."""
+        self._lora_refuse_sharded("unload_lora_weights")
+        self._lora_apply([], None)
+        self._lora = {}
+
+    def lora_records(self):
+        """The active adapters as the job records them: [{"name", "scale", "rank", "unet_modules", "text_modules"}]."""
+        return [self._lora[n].record(w) for n, w in self._lora_active]
+
+    def _lora_apply(self, active, device):
+        from .. import lora as _lora
+        if len(active) > _lora.MAX_ADAPTERS:
+            raise ValueError(f"lora: {len(active)} adapters, {_lora.MAX_ADAPTERS} at most are active at once")
+        loaders = {"unet": (self.unet, "load_diffusers_state_dict"), "text_encoder": (self.text_encoder, "load_transformers_state_dict")}
+        for comp, (model, loader) in loaders.items():
+            want = tuple((n, w) for n, w in active if w != 0 and self._lora[n].of(comp))
+            if want == self._lora_loaded[comp]:
+                continue
+            if comp not in self._sources:
+                raise _VdxError(f"lora: this pipeline does not know where its {comp} weights came from (it was not built by "
+                                "from_pretrained): the base cannot be re-obtained")
+            dev = torch.device(device) if device is not None else model._device
+            if dev.type != "cuda":
+                dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else dev
+            base = self._sources[comp]()
+            merged = _lora.merge_state_dict(base, comp, [self._lora[n] for n, _ in want], [w for _, w in want], dev)
+            getattr(model, loader)(merged, device=model._device)
+            self._lora_loaded[comp] = want
+        self._lora_active = list(active)
 
     def decode_latents(self, latents):
         """`fsdp.py:172` relies on this pipeline helper of older diffusers releases: latents (1,C,F,h,w) -> video

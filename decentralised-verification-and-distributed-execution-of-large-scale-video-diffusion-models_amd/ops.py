@@ -2136,3 +2136,63 @@ def region_blend(inputs, table, s: int, L: int, d: int = 1, ring: bool = False, 
     with torch.cuda.device(table.device):
         _launch("vdx_region_blend_f16", ptrs, n_in, _p(table, "table", torch.float32), T, s, L, d, int(bool(ring)), S, Cc, out.data_ptr())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# LoRA adapters: one weight of the diffusers layout with its adapters merged in (vdx/lora.py, csrc/lora.hip; no reference counterpart)
+LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 512
+
+
+def lora_merge(W, adapters, out=None):
+    """`W + sum_a s_a up_a @ down_a` in one launch (include/vdx.h `vdx_lora_merge_f16`: fp32 products and sums in a stated order, the
+    result rounded to fp16 once).  `W`: fp16 contiguous (n_out, n_in) on the GPU; `adapters`: 1 to 8 entries (up, down, s), `up`
+    fp32 contiguous (n_out, R) and `down` fp32 contiguous (R, n_in) on W's device, 1 <= R <= 512, `s` a finite number (rounded to
+    fp32 here).  `out`: fp16 contiguous (n_out, n_in), which may be `W`; by default a new tensor."""
+    import math
+    if not isinstance(W, torch.Tensor) or not W.is_cuda:
+        raise VdxError("lora_merge: W must be a GPU tensor (the merge has no CPU fallback)")
+    if W.dtype != torch.float16:
+        raise VdxError(f"lora_merge: W must be fp16, got {W.dtype}")
+    if W.dim() != 2 or not W.is_contiguous() or W.shape[0] < 1 or W.shape[1] < 1:
+        raise VdxError(f"lora_merge: W must be contiguous (n_out, n_in), got {tuple(W.shape)}")
+    n_out, n_in = int(W.shape[0]), int(W.shape[1])
+    adapters = list(adapters)
+    A = len(adapters)
+    if not 1 <= A <= LORA_MAX_ADAPTERS:
+        raise VdxError(f"lora_merge: {A} adapters, 1 to {LORA_MAX_ADAPTERS} are taken")
+    if out is None:
+        out = torch.empty_like(W)
+    elif not isinstance(out, torch.Tensor) or out.device != W.device or out.dtype != torch.float16 or tuple(out.shape) != (n_out, n_in) \
+            or not out.is_contiguous():
+        raise VdxError(f"lora_merge: out must be a contiguous fp16 ({n_out}, {n_in}) tensor on W's device")
+    ranks, scales = [], []
+    for a, entry in enumerate(adapters):
+        if not isinstance(entry, (tuple, list)) or len(entry) != 3:
+            raise VdxError(f"lora_merge: adapter {a} must be (up, down, s)")
+        up, down, s = entry
+        for t, name in ((up, "up"), (down, "down")):
+            if not isinstance(t, torch.Tensor) or t.device != W.device:
+                raise VdxError(f"lora_merge: adapter {a}: {name} must be a tensor on W's device")
+            if t.dtype != torch.float32:
+                raise VdxError(f"lora_merge: adapter {a}: {name} must be fp32, got {t.dtype}")
+            if t.dim() != 2 or not t.is_contiguous():
+                raise VdxError(f"lora_merge: adapter {a}: {name} must be a contiguous matrix, got {tuple(t.shape)}")
+            if t.data_ptr() % 4:
+                raise VdxError(f"lora_merge: adapter {a}: {name} must be 4-byte aligned")
+        R = int(up.shape[1])
+        if not 1 <= R <= LORA_MAX_RANK:
+            raise VdxError(f"lora_merge: adapter {a}: rank {R}, 1 to {LORA_MAX_RANK} are taken")
+        if tuple(up.shape) != (n_out, R) or tuple(down.shape) != (R, n_in):
+            raise VdxError(f"lora_merge: adapter {a}: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit W ({n_out}, {n_in}) at rank {R}")
+        s = float(s)
+        if not math.isfinite(s) or not math.isfinite(C.c_float(s).value):
+            raise VdxError(f"lora_merge: adapter {a}: the scale {s!r} is not a finite fp32 number")
+        ranks.append(R)
+        scales.append(s)
+    if W.data_ptr() % 2 or out.data_ptr() % 2:
+        raise VdxError("lora_merge: W and out must be 2-byte aligned")
+    ups = (C.c_void_p * A)(*[e[0].data_ptr() for e in adapters])
+    downs = (C.c_void_p * A)(*[e[1].data_ptr() for e in adapters])
+    with torch.cuda.device(W.device):
+        _launch("vdx_lora_merge_f16", W.data_ptr(), n_out, n_in, A, ups, downs, (C.c_int32 * A)(*ranks), (C.c_float * A)(*scales), out.data_ptr())
+    return out

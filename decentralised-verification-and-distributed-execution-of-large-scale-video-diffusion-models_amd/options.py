@@ -235,6 +235,42 @@ def check_regions(cfg):
     return region_plan(check(cfg), cfg.num_frames, cfg.height // VAE_SCALE, cfg.width // VAE_SCALE, UNET_LEVELS)
 
 
+def check_lora(cfg) -> Optional[Tuple[Tuple[str, float], ...]]:
+    """`cfg.lora` as ((path, scale), ...) with float scales (None when off); `ValueError` before anything is loaded for a malformed
+    entry, a path that is no string or names no local file, a scale that is no finite number, more than 8 adapters, and a path
+    given twice.  The files are read once the pipeline's configs are known (`run_job`, vdx/lora.py `read_lora`)."""
+    if getattr(cfg, "lora", None) is None:
+        return None
+    import math
+    entries = cfg.lora
+    if not isinstance(entries, (tuple, list)) or not entries:
+        raise ValueError(f"lora must be a non-empty sequence of (path, scale) pairs, got {entries!r}")
+    if len(entries) > 8:
+        raise ValueError(f"lora: {len(entries)} adapters, at most 8 are merged at once")
+    out, seen = [], set()
+    for e in entries:
+        if not isinstance(e, (tuple, list)) or len(e) != 2:
+            raise ValueError(f"lora: every entry is a (path, scale) pair, got {e!r}")
+        path, scale = e
+        if not isinstance(path, (str, os.PathLike)):
+            raise ValueError(f"lora: the path must be a string, got {path!r}")
+        path = os.fspath(path)
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"lora: the scale of {path!r} must be a number, got {scale!r}") from None
+        if isinstance(e[1], bool) or not math.isfinite(scale):
+            raise ValueError(f"lora: the scale of {path!r} must be a finite number, got {e[1]!r}")
+        if "://" in path or not os.path.isfile(path):
+            raise ValueError(f"lora: {path!r} is not a local file (nothing is ever downloaded)")
+        real = os.path.realpath(path)
+        if real in seen:
+            raise ValueError(f"lora: {path!r} is given twice")
+        seen.add(real)
+        out.append((path, scale))
+    return tuple(out)
+
+
 # ---- the resolved job ---------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class JobOptions:
@@ -256,6 +292,8 @@ class JobOptions:
     guidance: dict = field(default_factory=dict)       # the keys the result and the records gain: negative_prompt, guidance_rescale
     prompt_travel: Optional[Tuple[Tuple[int, str], ...]] = None     # the keys, sorted, the prompt at frame 0 among them
     regions: Optional[object] = None                                # regional prompts: the job's `region.RegionPlan` (host tables)
+    lora: Optional[Tuple[Tuple[str, float], ...]] = None            # LoRA adapters: the job's (path, scale) pairs
+    lora_found: Optional[tuple] = None                              # what `read_lora` found in them (`run_job` fills it in): the record
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -283,6 +321,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         guidance = {"negative_prompt": cfg.negative_prompt} if cfg.negative_prompt else {}
         travel = check_prompt_travel(cfg)
         regions = check_regions(cfg)
+        lora = check_lora(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -292,11 +331,12 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         factor, pixel_mask, phi, guidance = cfg.interpolate, None, float(cfg.guidance_rescale), {}
         travel = check_prompt_travel(cfg)
         regions = check_regions(cfg)
+        lora = check_lora(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
-                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions)
+                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -317,6 +357,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
             out["context_stride"] = out["co_denoise"]["context_stride"] = first["context_stride"]
     out.update(travel_record(opts))
     out.update(region_record(opts))
+    out.update(lora_record(opts))
     return out
 
 
@@ -344,6 +385,17 @@ def region_record(src) -> dict:
         return {}
     from .region import record
     return record(src.regions)
+
+
+def lora_record(src) -> dict:
+    """`{"lora": [{"name", "scale", "rank", "unet_modules", "text_modules"}, ...]}` beside `record_options`' entries, only when the
+    option is set and its files have been read (else {}): from the resolved options, or copied from a dict (`info`, the result)
+    that holds the entry."""
+    if isinstance(src, dict):
+        return {"lora": src["lora"]} if "lora" in src else {}
+    if src.lora_found is None:
+        return {}
+    return {"lora": [dict(r) for r in src.lora_found]}
 
 
 def record_options(res: dict) -> dict:

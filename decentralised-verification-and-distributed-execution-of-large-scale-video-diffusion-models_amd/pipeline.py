@@ -37,7 +37,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, record_options, region_record, resolve, travel_record, world_size
+from .options import info_options, lora_record, record_options, region_record, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -129,6 +129,11 @@ class DiffuserConfig:
     # region's text, the rest on `prompt`, in every window of every mode.  Not with `tile` or `prompt_travel`.  None = one prompt
     # for the whole frame, as always
     regions: Optional[tuple] = None
+    # LoRA adapters (vdx/lora.py, csrc/lora.hip; diffusers' load_lora_weights / set_adapters, unpinned): ((path, scale), ...), up to
+    # 8 local adapter files (.safetensors or torch.load; peft / diffusers or kohya keys) and their weights.  They are merged into
+    # the UNet's and the text encoder's weights on the GPU before those are packed, moved and sharded; the forward itself is the
+    # one it always was.  Goes with every other option.  None = the checkpoint's weights, as always
+    lora: Optional[tuple] = None
 
     @property
     def use_fsdp(self):
@@ -661,6 +666,9 @@ def build_arg_parser():
     p.add_argument("--region", nargs=2, action="append", default=None, metavar=("MASK.npy", "TEXT"),
                    help="regional prompt: the pixels under the mask (uint8 (H, W) or (T, H, W), 0..255) are conditioned on TEXT, the "
                         "rest on --prompt (repeatable, up to 7; not with --tile or --prompt_at; default: off)")
+    p.add_argument("--lora", nargs=2, action="append", default=None, metavar=("PATH", "SCALE"),
+                   help="LoRA adapter: merge the local file PATH (.safetensors or torch.load; peft / diffusers or kohya keys) into the "
+                        "UNet and text encoder at weight SCALE (repeatable, up to 8; default: off)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -691,6 +699,13 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.prompt_travel = tuple((frame(f), text) for f, text in cfg.prompt_travel)
     if cfg.regions is not None:
         cfg.regions = tuple((mask, text) for mask, text in cfg.regions)
+    if cfg.lora is not None:                    # SCALE arrives as text; what is no number stays as it came, for the check to refuse
+        def number(v):
+            try:
+                return float(v)
+            except ValueError:
+                return v
+        cfg.lora = tuple((path, number(scale)) for path, scale in cfg.lora)
     return cfg
 
 
@@ -819,6 +834,13 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     if pipe is None:
         pipe = DiffusionPipeline.from_pretrained(cfg.model_id, torch_dtype=torch.float16, low_cpu_mem_usage=True,
                                                  use_safetensors=False, device_map=None)
+    if opts.lora is not None:
+        # before the models move and shard: the job's adapters replace whatever the pipe had loaded, merged on this rank's GPU
+        # (every rank reads the same files and merges the same bits: no collective)
+        import dataclasses
+
+        from .lora import apply_job_adapters
+        opts = dataclasses.replace(opts, lora_found=tuple(apply_job_adapters(pipe, opts.lora, dev)))
     unet = pipe.unet
     unet.detect_cfg_duplicate = False           # this driver builds its CFG batch with ops.cfg_input: tagged, no compare needed
     for m in (unet, pipe.text_encoder, pipe.vae):
@@ -897,7 +919,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
-            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info)}
+            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **lora_record(info)}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -926,7 +948,7 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {**record_options(res), **travel_record(res), **region_record(res)}
+        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res)}
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -946,7 +968,7 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update({**record_options(res), **travel_record(res), **region_record(res)})
+            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

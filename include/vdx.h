@@ -897,6 +897,24 @@ int vdx_region_blend_f16(const void* const* in, int n_in, const float* table, in
                          void* out, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA adapters, merged into the weights in the diffusers layout before the loader packs them (nothing in the reference: it
+ * loads one checkpoint; diffusers' load_lora_weights / set_adapters / fuse_lora and peft's merge, unpinned; vdx/lora.py, the
+ * job's --lora, csrc/lora.hip).  tests/lora_ref.py states the expression.  No atomics: the same bits on every run and rank.
+ * ------------------------------------------------------------------------------------------ */
+/* out = W + sum_a s_a up_a down_a on one weight.  W, out: fp16 [n_out][n_in] contiguous (a conv weight flattened over its input
+ * axes), out may be W.  up, down, rank, scale: HOST arrays of A entries (1 <= A <= 8): up[a] fp32 [n_out][rank[a]] and down[a]
+ * fp32 [rank[a]][n_in] on the device, contiguous, 1 <= rank[a] <= 512, scale[a] finite.  Per element, every product and every
+ * sum rounded to fp32 on its own:
+ *   acc_a = 0;  for r ascending: acc_a = acc_a + up_a[o][r] down_a[r][i];     d = 0;  for a ascending: d = d + scale[a] acc_a;
+ *   out[o][i] = fp16_rn( fp32(W[o][i]) + d )
+ * VALU fp32, not MFMA: the order of summation is part of the contract.  A block owns a 32 x 256 tile of W and stages up and
+ * down through LDS 32 ranks at a time.  Accesses along n_in are 16 bytes where n_in % 8 == 0 and W, out and every down are
+ * 16-byte aligned, 8 bytes where n_in % 4 == 0 and they are 8-byte aligned, else one element (fp16 2-byte, fp32 4-byte
+ * aligned).  Any n_out, n_in >= 1.                                                                                          */
+int vdx_lora_merge_f16(const void* W, int n_out, int n_in, int A, const float* const* up, const float* const* down,
+                       const int32_t* rank, const float* scale, void* out, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

@@ -213,6 +213,9 @@ SIGNATURES = {
     "vdx_region_blend_f16": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     # LoRA adapters merged into a weight in the diffusers layout (no reference counterpart; vdx/lora.py, csrc/lora.hip)
     "vdx_lora_merge_f16": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(_f), _vp, _vp]),
+    # prompt emphasis: per-token weights on the text encoder's output, mean restored (no reference counterpart; vdx/prompt.py,
+    # csrc/prompt.hip)
+    "vdx_prompt_weight_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     # Motion-JPEG decode (scoring.py:16, :110, :230, :272, :314 cv2.VideoCapture; cv2_shim.py:199-289 the writer)
     "vdx_mjpeg_workspace": (_sz, [_i, _i, _i, _i]),
     "vdx_mjpeg_entropy": (_i, [_vp, _sz, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

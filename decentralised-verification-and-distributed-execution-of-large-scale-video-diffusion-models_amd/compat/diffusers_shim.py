@@ -91,16 +91,35 @@ class HashTokenizer:
     model_max_length = 77
     bos_token_id, eos_token_id = 49406, 49407
 
-    def __call__(self, text, padding="max_length", max_length=None, truncation=True, return_tensors="pt", **_kw):
+    def __call__(self, text, padding="max_length", max_length=None, truncation=True, return_tensors="pt", add_special_tokens=True, **_kw):
+        """`add_special_tokens=False` / `truncation=False` / `padding=False` (vdx/prompt.py tokenises a prompt's segments so): the
+        words' ids alone, all of them, as lists (one list for one string) when `return_tensors` is None."""
         texts = [text] if isinstance(text, str) else list(text)
         n = max_length or self.model_max_length
+        pad = padding not in (False, "do_not_pad")
         rows = []
         for t in texts:
-            ids = [self.bos_token_id] + [1000 + zlib.crc32(w.lower().encode()) % 48000 for w in t.split()]
-            ids = ids[:n - 1] + [self.eos_token_id]
-            rows.append(ids + [self.eos_token_id] * (n - len(ids)))
+            ids = [1000 + zlib.crc32(w.lower().encode()) % 48000 for w in t.split()]
+            if add_special_tokens:
+                ids = [self.bos_token_id] + ids
+                ids = (ids[:n - 1] if truncation else ids) + [self.eos_token_id]
+            elif truncation:
+                ids = ids[:n]
+            rows.append(ids + [self.eos_token_id] * (n - len(ids)) if pad else ids)
+        if return_tensors is None:
+            return SimpleNamespace(input_ids=rows[0] if isinstance(text, str) else rows)
         ids = torch.tensor(rows, dtype=torch.int64)
         return SimpleNamespace(input_ids=ids, attention_mask=(ids != self.eos_token_id).long())
+
+
+def tokenizer_for(model_id):
+    """The tokenizer `from_pretrained(model_id)` gives its pipeline: the CLIP tokenizer of a local checkpoint's `tokenizer/`, else
+    the hash stand-in.  Reads no weights: the job's options are checked with it before anything is loaded."""
+    d = str(model_id)
+    if os.path.isdir(f"{d}/tokenizer"):
+        import transformers
+        return transformers.CLIPTokenizer.from_pretrained(f"{d}/tokenizer")
+    return HashTokenizer()
 
 
 def _load_file(path_no_ext_candidates):
@@ -200,7 +219,7 @@ class DiffusionPipeline:
             unet = UNet3DConditionModel(_unet.UNet3DConfig.zeroscope())
             text = CLIPTextModel(_clip.CLIPTextConfig.sd2())
             vae = AutoencoderKL(_vae.VaeConfig.sd())
-        sched_kw, tokenizer, synthetic = {}, None, True
+        sched_kw, synthetic = {}, True
         if os.path.isdir(str(model_id)):
             d = str(model_id)
             sources = {"unet": lambda: _load_file([f"{d}/unet/diffusion_pytorch_model.safetensors", f"{d}/unet/diffusion_pytorch_model.bin"]),
@@ -218,9 +237,6 @@ class DiffusionPipeline:
                 known = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset",
                          "set_alpha_to_one", "clip_sample", "prediction_type", "timestep_spacing")
                 sched_kw = {k: v for k, v in json.load(open(cfgp)).items() if k in known}
-            if os.path.isdir(f"{d}/tokenizer"):
-                import transformers
-                tokenizer = transformers.CLIPTokenizer.from_pretrained(f"{d}/tokenizer")
             synthetic = False
         else:
             if str(model_id) != "synthetic:tiny":
@@ -231,7 +247,7 @@ class DiffusionPipeline:
             unet.load_diffusers_state_dict(_weights.synthetic_state_dict(unet.cfg, 1234, "cpu"), device="cpu")
             text.load_transformers_state_dict(_weights.synthetic_clip_state_dict(text.cfg, 11, "cpu"), device="cpu")
             vae.load_diffusers_state_dict(_weights.synthetic_vae_state_dict(vae.cfg, 7, "cpu"), device="cpu")
-        return cls(unet, text, vae, tokenizer or HashTokenizer(), DDIMScheduler(**sched_kw), synthetic, sources=sources)
+        return cls(unet, text, vae, tokenizer_for(model_id), DDIMScheduler(**sched_kw), synthetic, sources=sources)
 
     def to(self, device):
         for m in (self.unet, self.text_encoder, self.vae):

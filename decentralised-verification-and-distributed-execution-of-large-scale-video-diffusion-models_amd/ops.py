@@ -2196,3 +2196,53 @@ def lora_merge(W, adapters, out=None):
     with torch.cuda.device(W.device):
         _launch("vdx_lora_merge_f16", W.data_ptr(), n_out, n_in, A, ups, downs, (C.c_int32 * A)(*ranks), (C.c_float * A)(*scales), out.data_ptr())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Prompt emphasis: per-token weights on the text encoder's output, mean restored (vdx/prompt.py, csrc/prompt.hip; no reference counterpart)
+PROMPT_MAX_TOK = 77
+
+
+def prompt_weight(z, w, out=None):
+    """A1111's emphasis with mean restoration in one launch (include/vdx.h `vdx_prompt_weight_f16`): per sequence
+    `y = fp16(fp32(z) w[tok])`, `r = fp32(sum z / sum y)` (fp64 sums and quotient), `out = fp16(fp32(y) r)`.  `z`: fp16 contiguous
+    (n_seq, n_tok, D) on the GPU, the CLIP last hidden state, 1 <= n_tok <= 77; `w`: fp32 (n_seq, n_tok), on the host or the device,
+    finite (checked here: one copy to the host where it is on the device).  `out`: fp16 contiguous like z, which may be z; by default
+    a new tensor.  A sequence whose weights are all exactly 1.0 is not passed to the kernel: its bits are z's, and where that is
+    every sequence nothing is launched and, without `out`, z itself is returned."""
+    if not isinstance(z, torch.Tensor) or not z.is_cuda:
+        raise VdxError("prompt_weight: z must be a GPU tensor (the weighting has no CPU fallback)")
+    if z.dtype != torch.float16 or z.dim() != 3 or not z.is_contiguous():
+        raise VdxError(f"prompt_weight: z must be contiguous fp16 (n_seq, n_tok, D), got {z.dtype} {tuple(z.shape)}")
+    n_seq, n_tok, D = (int(v) for v in z.shape)
+    if n_seq < 1 or not 1 <= n_tok <= PROMPT_MAX_TOK or D < 1:
+        raise VdxError(f"prompt_weight: z {tuple(z.shape)}: n_seq >= 1, n_tok in 1..{PROMPT_MAX_TOK} and D >= 1 are taken")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (n_seq, n_tok):
+        raise VdxError(f"prompt_weight: w must be fp32 ({n_seq}, {n_tok}), got {getattr(w, 'dtype', type(w))} {tuple(getattr(w, 'shape', ()))}")
+    wh = w.detach().cpu().contiguous()
+    if not bool(torch.isfinite(wh).all()):
+        raise VdxError("prompt_weight: w holds a weight that is not finite")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != z.device or out.dtype != torch.float16
+                            or tuple(out.shape) != (n_seq, n_tok, D) or not out.is_contiguous()):
+        raise VdxError(f"prompt_weight: out must be a contiguous fp16 ({n_seq}, {n_tok}, {D}) tensor on z's device")
+    weighted = [i for i in range(n_seq) if bool((wh[i] != 1.0).any())]
+    if not weighted:
+        if out is None or out.data_ptr() == z.data_ptr():
+            return z
+        return out.copy_(z)
+    with torch.cuda.device(z.device):
+        if len(weighted) == n_seq:
+            out = torch.empty_like(z) if out is None else out
+            _launch("vdx_prompt_weight_f16", z.data_ptr(), _p(wh.to(z.device), "w", torch.float32), out.data_ptr(), n_seq, n_tok, D)
+            return out
+        # some sequences keep the encoder's bits: the weighted ones are gathered, weighted in place in one launch, and put back
+        idx = torch.tensor(weighted, dtype=torch.int64, device=z.device)
+        sel = z.index_select(0, idx)
+        _launch("vdx_prompt_weight_f16", sel.data_ptr(), _p(wh[weighted].contiguous().to(z.device), "w", torch.float32), sel.data_ptr(),
+                len(weighted), n_tok, D)
+        if out is None:
+            out = z.clone()
+        elif out.data_ptr() != z.data_ptr():
+            out.copy_(z)
+        out.index_copy_(0, idx, sel)
+    return out

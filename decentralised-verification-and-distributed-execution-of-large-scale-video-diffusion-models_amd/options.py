@@ -271,6 +271,31 @@ def check_lora(cfg) -> Optional[Tuple[Tuple[str, float], ...]]:
     return tuple(out)
 
 
+def job_texts(cfg, travel=None, regions=None) -> list:
+    """The texts of a job in the order `run_job` encodes them: the prompt, the negative prompt, the prompt-travel keys' texts, the
+    regions' texts (`travel`, `regions`: what `check_prompt_travel` and `check_regions` returned)."""
+    texts = [cfg.prompt, cfg.negative_prompt] + [text for _, text in travel or ()]
+    if regions is not None:
+        texts += list(regions.texts)
+    return texts
+
+
+def check_prompt_syntax(cfg, texts=None) -> str:
+    """`cfg.prompt_syntax`, "plain" (off: one tokeniser call, 77 positions, every token at weight 1, as always) or "a1111"
+    (vdx/prompt.py: `(text:1.3)` emphasis and 75-token chunks); `ValueError` before anything is loaded for any other value and,
+    with `texts` (the job's front end: `job_texts`), for a text that is no string or that makes more chunks than the UNet takes,
+    counted with the tokenizer the job's `model_id` will bring (its `tokenizer/` files, else the hash stand-in: no weights are read)."""
+    syntax = getattr(cfg, "prompt_syntax", "plain")
+    from .prompt import SYNTAXES
+    if syntax not in SYNTAXES:
+        raise ValueError(f"prompt_syntax must be one of {SYNTAXES}, got {syntax!r}")
+    if syntax != "plain" and texts is not None:
+        from .compat.diffusers_shim import tokenizer_for
+        from .prompt import check_texts
+        check_texts(texts, tokenizer_for(cfg.model_id))
+    return syntax
+
+
 # ---- the resolved job ---------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class JobOptions:
@@ -294,6 +319,8 @@ class JobOptions:
     regions: Optional[object] = None                                # regional prompts: the job's `region.RegionPlan` (host tables)
     lora: Optional[Tuple[Tuple[str, float], ...]] = None            # LoRA adapters: the job's (path, scale) pairs
     lora_found: Optional[tuple] = None                              # what `read_lora` found in them (`run_job` fills it in): the record
+    prompt_syntax: str = "plain"                                    # "plain" | "a1111" (vdx/prompt.py)
+    prompt_found: Optional[dict] = None                             # the chunked texts' record (`run_job` fills it in once they are encoded)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -322,6 +349,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         travel = check_prompt_travel(cfg)
         regions = check_regions(cfg)
         lora = check_lora(cfg)
+        syntax = check_prompt_syntax(cfg, job_texts(cfg, travel, regions))
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -332,11 +360,12 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         travel = check_prompt_travel(cfg)
         regions = check_regions(cfg)
         lora = check_lora(cfg)
+        syntax = check_prompt_syntax(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
-                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora)
+                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -358,6 +387,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(travel_record(opts))
     out.update(region_record(opts))
     out.update(lora_record(opts))
+    out.update(prompt_record(opts))
     return out
 
 
@@ -396,6 +426,17 @@ def lora_record(src) -> dict:
     if src.lora_found is None:
         return {}
     return {"lora": [dict(r) for r in src.lora_found]}
+
+
+def prompt_record(src) -> dict:
+    """`{"prompt_syntax": {"syntax", "chunks", "tokens", "weighted"}}` beside `record_options`' entries, only when the option is set
+    and the texts have been chunked (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the
+    entry.  `chunks`: the job's k (every text has 77 k positions); `tokens`: per text, in `job_texts`' order."""
+    if isinstance(src, dict):
+        return {"prompt_syntax": src["prompt_syntax"]} if "prompt_syntax" in src else {}
+    if src.prompt_found is None:
+        return {}
+    return {"prompt_syntax": dict(src.prompt_found)}
 
 
 def record_options(res: dict) -> dict:

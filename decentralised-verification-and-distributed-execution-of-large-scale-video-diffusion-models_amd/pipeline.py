@@ -37,7 +37,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, lora_record, record_options, region_record, resolve, travel_record, world_size
+from .options import info_options, job_texts, lora_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -134,6 +134,12 @@ class DiffuserConfig:
     # the UNet's and the text encoder's weights on the GPU before those are packed, moved and sharded; the forward itself is the
     # one it always was.  Goes with every other option.  None = the checkpoint's weights, as always
     lora: Optional[tuple] = None
+    # weighted and long prompts (vdx/prompt.py, csrc/prompt.hip; the AUTOMATIC1111 web UI's prompt emphasis and 75-token chunks,
+    # unpinned): "a1111" reads `(text:1.3)`, `(text)`, `[text]` and `BREAK` in the prompt, the negative prompt, every prompt-travel
+    # key and every region text, and encodes a text of more than 75 tokens as up to four 77-position chunks side by side (all texts
+    # of a job at the same length); the UNet's cross-attentions then see up to 308 rows.  A text of at most 75 tokens without
+    # emphasis gives the same job bit for bit.  "plain" = one 77-position sequence, the rest truncated, every token alike, as always
+    prompt_syntax: str = "plain"
 
     @property
     def use_fsdp(self):
@@ -669,6 +675,9 @@ def build_arg_parser():
     p.add_argument("--lora", nargs=2, action="append", default=None, metavar=("PATH", "SCALE"),
                    help="LoRA adapter: merge the local file PATH (.safetensors or torch.load; peft / diffusers or kohya keys) into the "
                         "UNet and text encoder at weight SCALE (repeatable, up to 8; default: off)")
+    p.add_argument("--prompt_syntax", choices=["plain", "a1111"], default="plain",
+                   help="a1111: (text:1.3) / (text) / [text] emphasis and BREAK in every text of the job, and texts of more than 75 tokens "
+                        "as up to four 75-token chunks (default: plain, one truncated 77-position sequence)")
     p.add_argument("--compare_to", default=None,
                    help="compare the generated frames with this clip (.npy of uint8 frames or Motion-JPEG mp4); needs --compare_json")
     p.add_argument("--compare_json", default=None, help="write the PSNR / SSIM / MS-SSIM record of --compare_to here (rank 0)")
@@ -846,12 +855,17 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     for m in (unet, pipe.text_encoder, pipe.vae):
         m.to(dev)
     tok = pipe.tokenizer
-    texts = [cfg.prompt, cfg.negative_prompt] + [text for _, text in opts.prompt_travel or ()]     # one text-encoder call
-    if opts.regions is not None:                # (never with prompt travel: `check_regions`)
-        texts += list(opts.regions.texts)
-    ids = tok(texts, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
-    with torch.no_grad():
-        emb = pipe.text_encoder(ids.to(dev))[0]
+    texts = job_texts(cfg, opts.prompt_travel, opts.regions)     # one text-encoder call (regions never with prompt travel: `check_regions`)
+    if opts.prompt_syntax == "plain":
+        ids = tok(texts, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
+        with torch.no_grad():
+            emb = pipe.text_encoder(ids.to(dev))[0]
+    else:                                       # weights and 75-token chunks: every text of the job at 77 k rows (vdx/prompt.py)
+        import dataclasses
+
+        from .prompt import encode_texts
+        emb, pplan = encode_texts(pipe, texts, opts.prompt_syntax, dev, return_plan=True)
+        opts = dataclasses.replace(opts, prompt_found=pplan.record(opts.prompt_syntax))
     cond, uncond = emb[:1].contiguous(), emb[1:2].contiguous()
     text_kw = {}
     if opts.prompt_travel is not None:
@@ -919,7 +933,8 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
-            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **lora_record(info)}
+            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **lora_record(info),
+            **prompt_record(info)}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -948,7 +963,14 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res)}
+        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res)}
+        scored = cfg.prompt
+        if "prompt_syntax" in res:
+            # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
+            # syntax characters stripped, and the records say so
+            from .prompt import strip_syntax
+            scored = strip_syntax(cfg.prompt)
+            source = {**source, "scored_prompt": scored}
         generated = clip_inputs["frames"] if clip_inputs is not None else None
         if clip_inputs is not None and a.score_from_file:
             # what a validator holding the file would score: the mp4 just written, decoded back on the GPU
@@ -957,18 +979,18 @@ def main(argv=None) -> int:
             source = {**source, "source": "file"}
         if a.clip_json:
             # scored after the row took its latency and memory readings: the row is that of a run without --clip_json
-            rec = clip_score_record(clip_inputs["frames"], cfg.prompt, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
+            rec = clip_score_record(clip_inputs["frames"], scored, a.clip_model, clip_inputs["tokenizer"], clip_inputs["device"])
             write_record(a.clip_json, {**rec, **source})
         if a.mdvqs_json:
             # likewise after the row: MD-VQS (its optical flow runs on the CPU unless --gpu_flow) never shows in `latency_s`
-            rec = mdvqs_record(clip_inputs["frames"], cfg.prompt, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
+            rec = mdvqs_record(clip_inputs["frames"], scored, a.lpips_model, a.clip_model, clip_inputs["tokenizer"],
                                clip_inputs["device"], **({"flow": "gpu"} if a.gpu_flow else {}))
             write_record(a.mdvqs_json, {**rec, **source})
         if a.compare_to:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res)})
+            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -50,6 +50,13 @@ class UNet3DConfig:
 
 
 TEXT_PAD = 128   # text tokens (77) padded to 2 key tiles; also keeps the K/V GEMM N % 64 == 0
+MAX_TEXT_LEN = 308   # four 77-position chunks of a long prompt (vdx/prompt.py); beyond it the forward refuses
+
+
+def text_pad_of(text_len: int) -> int:
+    """Rows a text item of `text_len` tokens is padded to: `TEXT_PAD` up to 128 tokens (every shape the forward ever took keeps its
+    bits and its cache layout), else `text_len` rounded up to a multiple of 64 (whole key tiles; the K / V GEMMs' N % 64 == 0)."""
+    return TEXT_PAD if text_len <= TEXT_PAD else (text_len + 63) // 64 * 64
 
 
 class UNet3DConditionModel(nn.Module):
@@ -92,6 +99,8 @@ class UNet3DConditionModel(nn.Module):
         self.text_cache_slots = 1              # texts whose K / V^T are kept (least recently used dropped); 1: the last text only, as always
         self._text_store: List[tuple] = []     # the other kept texts' (_text_ref, _text_kv), most recently used first
         self.text_cache_misses = 0             # forwards that had to project their text's keys / values
+        self.force_text_pad = None             # tests: rows a text item is padded to instead of `text_pad_of(text_len)` (a multiple of 64 >= text_len)
+        self._text_pad = TEXT_PAD              # the forward's padding: `text_pad_of` of its text length
         self._text_per_frame = False           # the forward's text is (B, F, N, D): one K / V item per frame (prompt travel)
         self._regions = None                   # the forward's regional prompts: (R, the device RegionPlan, (s, L, d, ring)); None: off
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
@@ -655,20 +664,21 @@ class UNet3DConditionModel(nn.Module):
         t = self._self_attention(b, t, n_img, hh, ww, self._level_down_of(p))
         # --- cross-attention over the (padded) text tokens; all F frames of a sample share K/V — or, with per-frame text
         # (`encoder_hidden_states` (B, F, N, D): prompt travel), every frame has its own item: nb = B F, `fpi` = F items per sample
-        nb = ehs_pad.shape[0] // TEXT_PAD
+        pad = self._text_pad
+        nb = ehs_pad.shape[0] // pad
         per_frame = self._text_per_frame
         fpi = F if per_frame else 1
         k5 = self.fuse_cross_attn and b + ".attn2.k5" in W and ops.cross_attn_block_supported(C, self._text_len)
         kv = self._text_kv.get(p)
         if kv is None:
             k = ops.gemm(ehs_pad, W[b + ".attn2.to_k.weight"], M=ehs_pad.shape[0])
-            vt = ops.gemm(W[b + ".attn2.to_v.weight"], ehs_pad, M=C)              # [C][nb*TEXT_PAD]
+            vt = ops.gemm(W[b + ".attn2.to_v.weight"], ehs_pad, M=C)              # [C][nb*pad]
             # (per-frame text packs its B F items in one launch, csrc/travel.hip; one text per sample keeps the torch chain)
             pack_kv = ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv
-            kv = self._text_kv[p] = (k, vt, pack_kv(k, vt, nb, TEXT_PAD) if k5 else None)
+            kv = self._text_kv[p] = (k, vt, pack_kv(k, vt, nb, pad) if k5 else None)
         k, vt, kvb = kv
         if k5 and kvb is None:
-            kvb = (ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv)(k, vt, nb, TEXT_PAD)
+            kvb = (ops.cross_attn_block_pack_kv if per_frame else packing.pack_k5_kv)(k, vt, nb, pad)
             self._text_kv[p] = (k, vt, kvb)
         if self._regions is not None:
             return self._regional_cross_attention(b, p, t, x, k, vt, kvb if k5 else None, nb, n_img, S, M, M_out, dup)
@@ -692,13 +702,13 @@ class UNet3DConditionModel(nn.Module):
             # transformer's input rows) are the shared item's for both — two launches over half the rows each, no copy
             t2 = torch.empty((M_out, C), dtype=torch.float16, device=x.device)
             for i in range(nb // fpi):
-                o = ops.flash_attn(q, k[i * fpi * TEXT_PAD:(i + 1) * fpi * TEXT_PAD], vt[:, i * fpi * TEXT_PAD:(i + 1) * fpi * TEXT_PAD], n_seq=n_img, sq=S,
-                                   skv=self._text_len, skv_pad=TEXT_PAD, heads=heads, seq_per_kv=n_img // fpi, scale=scale)
+                o = ops.flash_attn(q, k[i * fpi * pad:(i + 1) * fpi * pad], vt[:, i * fpi * pad:(i + 1) * fpi * pad], n_seq=n_img, sq=S,
+                                   skv=self._text_len, skv_pad=pad, heads=heads, seq_per_kv=n_img // fpi, scale=scale)
                 ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=M, bias=W[b + ".attn2.to_out.0.bias"], residual=t, out=t2[i * M:(i + 1) * M])
                 del o
             del q
             return self._ff_proj_out(b, p, t2, x, M_out, xrows=M)
-        o = ops.flash_attn(q, k, vt, n_seq=n_img, sq=S, skv=self._text_len, skv_pad=TEXT_PAD, heads=heads,
+        o = ops.flash_attn(q, k, vt, n_seq=n_img, sq=S, skv=self._text_len, skv_pad=pad, heads=heads,
                            seq_per_kv=n_img // nb, scale=scale)
         del q
         t = ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=M, bias=W[b + ".attn2.to_out.0.bias"], residual=t)
@@ -716,6 +726,7 @@ class UNet3DConditionModel(nn.Module):
         holds one item's rows, which stand for both items."""
         W = self.W
         R, plan, (ws, wL, wd, wring) = self._regions
+        pad = self._text_pad
         B = nb - R
         C = t.shape[1]
         heads = C // 64
@@ -741,8 +752,8 @@ class UNet3DConditionModel(nn.Module):
                 ops.cross_attn_block(rows, W[b + ".attn2.k5"], kvb[item:item + 1], kv_len=self._text_len, n_items=1, rows_per_item=Mi, out=out)
                 return
             qi = q if dup else q[i * Mi:(i + 1) * Mi]
-            o = ops.flash_attn(qi, k[item * TEXT_PAD:(item + 1) * TEXT_PAD], vt[:, item * TEXT_PAD:(item + 1) * TEXT_PAD], n_seq=ni, sq=S,
-                               skv=self._text_len, skv_pad=TEXT_PAD, heads=heads, seq_per_kv=ni, scale=scale)
+            o = ops.flash_attn(qi, k[item * pad:(item + 1) * pad], vt[:, item * pad:(item + 1) * pad], n_seq=ni, sq=S,
+                               skv=self._text_len, skv_pad=pad, heads=heads, seq_per_kv=ni, scale=scale)
             ops.gemm(o, W[b + ".attn2.to_out.0.weight"], M=Mi, bias=W[b + ".attn2.to_out.0.bias"], residual=rows, out=out)
 
         for i in range(B - 1):
@@ -825,13 +836,17 @@ class UNet3DConditionModel(nn.Module):
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.float16)
         per_frame = ehs.dim() == 4              # (B, F, N, D): a text per frame (prompt travel); (B, N, D): one per sample, as always
         if per_frame:
-            if ehs.shape[0] != B or ehs.shape[3] != c.cross_attention_dim or ehs.shape[2] > TEXT_PAD:
+            if ehs.shape[0] != B or ehs.shape[3] != c.cross_attention_dim or ehs.shape[2] > MAX_TEXT_LEN:
                 raise VdxError(f"encoder_hidden_states shape {tuple(ehs.shape)} does not fit (B={B}, dim={c.cross_attention_dim})")
             if ehs.shape[1] != F:
                 raise VdxError(f"encoder_hidden_states holds text for {ehs.shape[1]} frames, the sample has {F}")
-        elif ehs.dim() != 3 or ehs.shape[0] != B or ehs.shape[2] != c.cross_attention_dim or ehs.shape[1] > TEXT_PAD:
+        elif ehs.dim() != 3 or ehs.shape[0] != B or ehs.shape[2] != c.cross_attention_dim or ehs.shape[1] > MAX_TEXT_LEN:
             raise VdxError(f"encoder_hidden_states shape {tuple(ehs.shape)} does not fit (B={B}, dim={c.cross_attention_dim})")
         self._text_len = ehs.shape[-2]
+        pad = text_pad_of(self._text_len) if self.force_text_pad is None else int(self.force_text_pad)
+        if pad % 64 or pad < self._text_len:
+            raise VdxError(f"force_text_pad {pad} must be a multiple of 64 and at least the text's {self._text_len} rows")
+        self._text_pad = pad
         self._text_per_frame = per_frame
         nt = B * F if per_frame else B          # K / V items
         self._regions = rtext = rtext_in = None
@@ -868,7 +883,7 @@ class UNet3DConditionModel(nn.Module):
             ver = encoder_hidden_states._version
         except Exception:       # inference-mode tensors do not track versions
             ver = None
-        key = (tuple(ehs.shape), dev)
+        key = (tuple(ehs.shape), dev, pad)       # the padding is part of what the cached K / V^T are laid out by
         rver = None
         if rtext is not None:                   # the region texts are part of what is cached: known by identity + version as well
             try:
@@ -889,12 +904,12 @@ class UNet3DConditionModel(nn.Module):
                 self._text_store.insert(0, (ref, self._text_kv))
             del self._text_store[slots - 1:]
             if entry is None:
-                ehs_pad = torch.zeros((nt * TEXT_PAD, c.cross_attention_dim), dtype=torch.float16, device=dev)
+                ehs_pad = torch.zeros((nt * pad, c.cross_attention_dim), dtype=torch.float16, device=dev)
                 if rtext is None:
-                    ehs_pad.view(nt, TEXT_PAD, -1)[:, :self._text_len] = ehs.reshape(nt, self._text_len, -1)
+                    ehs_pad.view(nt, pad, -1)[:, :self._text_len] = ehs.reshape(nt, self._text_len, -1)
                 else:
-                    ehs_pad.view(nt, TEXT_PAD, -1)[:B, :self._text_len] = ehs
-                    ehs_pad.view(nt, TEXT_PAD, -1)[B:, :self._text_len] = rtext
+                    ehs_pad.view(nt, pad, -1)[:B, :self._text_len] = ehs
+                    ehs_pad.view(nt, pad, -1)[B:, :self._text_len] = rtext
                 entry = ((encoder_hidden_states, ver, key, ehs_pad, rtext_in, rver), {})
                 self.text_cache_misses += 1
             self._text_ref, self._text_kv = entry

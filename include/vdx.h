@@ -915,6 +915,24 @@ int vdx_lora_merge_f16(const void* W, int n_out, int n_in, int A, const float* c
                        const int32_t* rank, const float* scale, void* out, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prompt emphasis: `(text:1.3)` weights on the text encoder's output, with mean restoration (nothing in the reference: it
+ * encodes one plain prompt; the AUTOMATIC1111 web UI's prompt emphasis, diffusers' lpw_stable_diffusion and compel, unpinned;
+ * vdx/prompt.py, the job's --prompt_syntax, csrc/prompt.hip).  tests/prompt_ref.py states the expression.  No atomics: the
+ * same bits on every run and rank.
+ * ------------------------------------------------------------------------------------------ */
+/* z: fp16 [n_seq][n_tok][D] contiguous, the CLIP last hidden state, one sequence per (text, 75-token chunk); w: fp32
+ * [n_seq][n_tok] on the device; out: fp16 like z, which may be z.  1 <= n_tok <= 77, 1 <= D <= 2^20.  Per sequence, every
+ * product rounded on its own:
+ *   y = fp16( fp32(z) w[tok] );   m0 = sum z, m1 = sum y (fp64, over the sequence's n_tok D elements);   r = fp32( m0 / m1 ),
+ *   the quotient in fp64;   out = fp16( fp32(y) r )
+ * One block of 1024 lanes owns one sequence and passes over it twice.  The sums' order: lane l adds the elements of its
+ * accesses l, l + 1024, ... (V elements each, ascending) to its partials, and the partials meet in a binary tree, p[l] += p[l + h]
+ * for h = 512, ..., 1.  V = 8 where D % 8 == 0 and z and out are 16-byte aligned, 4 where D % 4 == 0 and they are 8-byte aligned,
+ * else 1.  No branch on data: m1 = 0, a NaN or an infinity give what the lines give, in that sequence only.  The caller (vdx/ops.py
+ * `prompt_weight`) refuses a non-finite w and does not pass a sequence whose weights are all 1.0.                              */
+int vdx_prompt_weight_f16(const void* z, const float* w, void* out, int n_seq, int n_tok, int D, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG decode of a whole clip: the read side of the validator's cv2.VideoCapture(video_path)
  *   InferNet/template/validator/scoring.py:16, :110, :230, :272, :314   every score opens the FILE the miner sent
  *   vdx/compat/cv2_shim.py:199-289                                      the writer whose .mp4 this reads back

@@ -228,6 +228,14 @@ SIGNATURES = {
     "vdx_mjpeg_enc_fdct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "vdx_mjpeg_enc_entropy": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_mjpeg_enc_pack": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    # animated GIF of a whole clip (no reference counterpart; vdx/gif.py, csrc/gif.hip)
+    "vdx_gif_hist_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp]),
+    "vdx_gif_lut": (_i, [_vp, _i, _vp, _vp]),
+    "vdx_gif_index_u8": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "vdx_gif_lzw_workspace": (_sz, [_i, _i, _i, _i]),
+    "vdx_gif_lzw_offsets": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
+    "vdx_gif_lzw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vdx_gif_pack": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2246,3 +2246,102 @@ def prompt_weight(z, w, out=None):
             out.copy_(z)
         out.index_copy_(0, idx, sel)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Animated GIF of a whole clip: histogram, LUT, index map, strip LZW, sub-blocks (vdx/gif.py, csrc/gif.hip; no reference counterpart)
+GIF_BINS = 32768
+GIF_DITHERS = {"none": 0, "bayer": 1}
+GIF_LZW_STAGES = ("sbits", "soff", "fbits", "slots", "stream", "foff")         # vdx_gif_lzw_offsets
+
+
+def _gif_u8(t, n: int, what: str, name: str) -> int:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n:
+        raise VdxError(f"{what}: {name} must be a contiguous uint8 GPU tensor of at least {n} bytes")
+    return t.data_ptr()
+
+
+def gif_hist(frames) -> torch.Tensor:
+    """Pixels of the whole clip per 5-5-5 bin -> int32 [32768] on the clip's device holding the uint32 counts (include/vdx.h
+    `vdx_gif_hist_u8`); a clip of 2^32 pixels or more is refused."""
+    T, H, W = check_u8_frames(frames, "gif_hist")
+    if T * H * W >= 1 << 32:
+        raise VdxError(f"gif_hist: {T * H * W} pixels do not fit the uint32 counts (2^32 or more)")
+    with torch.cuda.device(frames.device):
+        hist = torch.empty(GIF_BINS, dtype=torch.int32, device=frames.device)
+        _launch("vdx_gif_hist_u8", *_u8_args(frames), T, H, W, hist.data_ptr())
+    return hist
+
+
+def gif_lut(palette) -> torch.Tensor:
+    """uint8 [32768]: for every 5-5-5 bin the entry of `palette` (uint8 (n, 3) on the GPU, n in 1..256) nearest to the bin's
+    centre, a tie to the lowest index (`vdx_gif_lut`)."""
+    if (not isinstance(palette, torch.Tensor) or not palette.is_cuda or palette.dtype != torch.uint8 or palette.dim() != 2
+            or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256 or not palette.is_contiguous()):
+        raise VdxError(f"gif_lut: palette must be a contiguous uint8 (n, 3) GPU tensor with n in 1..256, got "
+                       f"{getattr(palette, 'dtype', type(palette))} {tuple(getattr(palette, 'shape', ()))}")
+    with torch.cuda.device(palette.device):
+        lut = torch.empty(GIF_BINS, dtype=torch.uint8, device=palette.device)
+        _launch("vdx_gif_lut", palette.data_ptr(), int(palette.shape[0]), lut.data_ptr())
+    return lut
+
+
+def gif_index(frames, lut, dither: str = "bayer") -> torch.Tensor:
+    """One palette index per pixel -> uint8 (T, H, W): the ordered dither ("bayer") or none, the bin, `lut` (`vdx_gif_index_u8`)."""
+    T, H, W = check_u8_frames(frames, "gif_index")
+    if dither not in GIF_DITHERS:
+        raise VdxError(f"gif_index: dither {dither!r} is not one of {sorted(GIF_DITHERS)}")
+    if T * H * W >= 1 << 32:
+        raise VdxError(f"gif_index: {T * H * W} pixels (2^32 or more)")
+    with torch.cuda.device(frames.device):
+        out = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
+        _launch("vdx_gif_index_u8", *_u8_args(frames), T, H, W, _gif_u8(lut, GIF_BINS, "gif_index", "lut"), GIF_DITHERS[dither],
+                out.data_ptr())
+    return out
+
+
+def gif_lzw_workspace(T: int, H: int, W: int, strip_rows: int) -> int:
+    """Bytes of workspace `gif_lzw` / `gif_pack` need; `VdxError` for a geometry the encoder does not take."""
+    n = _lib.load().vdx_gif_lzw_workspace(T, H, W, strip_rows)
+    if n == 0:
+        raise VdxError(f"gif_lzw: {T} frames of {W}x{H} in strips of {strip_rows} rows are outside what the encoder takes")
+    return n
+
+
+def gif_lzw_offsets(T: int, H: int, W: int, strip_rows: int) -> dict:
+    """The workspace's layout: byte offsets of `GIF_LZW_STAGES`, then "nstrips" and "slot_words" (`vdx_gif_lzw_offsets`)."""
+    offs = (C.c_size_t * 8)()
+    _lib.check(_lib.load().vdx_gif_lzw_offsets(T, H, W, strip_rows, offs), "vdx_gif_lzw_offsets")
+    return dict(zip(GIF_LZW_STAGES + ("nstrips", "slot_words"), (int(v) for v in offs)))
+
+
+def gif_lzw(idx, strip_rows: int, workspace, lengths=None) -> torch.Tensor:
+    """LZW of every strip of `strip_rows` rows of uint8 (T, H, W) indices into `workspace` (`gif_lzw_workspace` bytes, uint8,
+    16-byte aligned) -> int32 [T]: the bytes of every frame's data sub-blocks (`vdx_gif_lzw`)."""
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.uint8 or idx.dim() != 3 or not idx.is_contiguous():
+        raise VdxError(f"gif_lzw: idx must be a contiguous uint8 (T, H, W) GPU tensor, got {getattr(idx, 'dtype', type(idx))} "
+                       f"{tuple(getattr(idx, 'shape', ()))}")
+    T, H, W = (int(v) for v in idx.shape)
+    if T < 1 or H < 1 or W < 1:
+        raise VdxError(f"gif_lzw: empty indices {tuple(idx.shape)}")
+    need = gif_lzw_workspace(T, H, W, strip_rows)
+    with torch.cuda.device(idx.device):
+        if lengths is None:
+            lengths = torch.empty(T, dtype=torch.int32, device=idx.device)
+        elif lengths.dtype != torch.int32 or lengths.numel() < T or not lengths.is_cuda or not lengths.is_contiguous():
+            raise VdxError(f"gif_lzw: lengths must be a contiguous int32 GPU tensor of at least {T} elements")
+        ws = _gif_u8(workspace, need, "gif_lzw", "workspace")
+        if ws % 16:
+            raise VdxError("gif_lzw: workspace not 16-byte aligned")
+        _launch("vdx_gif_lzw", idx.data_ptr(), T, H, W, strip_rows, ws, lengths.data_ptr())
+    return lengths
+
+
+def gif_pack(workspace, T: int, H: int, W: int, strip_rows: int, out) -> torch.Tensor:
+    """Every frame's data sub-blocks back to back into `out` (uint8, the sum of `gif_lzw`'s lengths in bytes), from the workspace
+    `gif_lzw` left (`vdx_gif_pack`)."""
+    need = gif_lzw_workspace(T, H, W, strip_rows)
+    with torch.cuda.device(out.device):
+        _launch("vdx_gif_pack", _gif_u8(workspace, need, "gif_pack", "workspace"), T, H, W, strip_rows, _gif_u8(out, 1, "gif_pack", "out"),
+                out.numel())
+    return out

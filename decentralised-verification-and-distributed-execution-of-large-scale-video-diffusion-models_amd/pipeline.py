@@ -623,6 +623,10 @@ def build_arg_parser():
                    help="restart marker every N MCU rows in the mp4's JPEG frames (0: none, the bytes written without this flag)")
     p.add_argument("--gpu_video_write", action="store_true",
                    help="encode the mp4's JPEG frames on the GPU (vdx.video.write_frames): the same file as without this flag")
+    p.add_argument("--out_gif", default=None,
+                   help="also write the clip (what --out_video gets, interpolated frames included) as an animated GIF on the GPU (vdx/gif.py)")
+    p.add_argument("--gif_dither", choices=["none", "bayer"], default="bayer", help="--out_gif: ordered 8x8 dither (default) or none")
+    p.add_argument("--gif_loop", type=int, default=0, help="--out_gif: the repeat count, 0 (default) for ever")
     p.add_argument("--score_from_file", action="store_true",
                    help="--clip_json / --mdvqs_json score the frames decoded back from --out_video (vdx/video.py)")
     p.add_argument("--init_video", default=None,
@@ -819,17 +823,23 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev, return_frames: bool = False
 
 
 def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optional[str] = "out.mp4", pipe=None,
-            clip_inputs: Optional[dict] = None, video_restart_rows: int = 0, gpu_video_write: bool = False) -> dict:
+            clip_inputs: Optional[dict] = None, video_restart_rows: int = 0, gpu_video_write: bool = False,
+            out_gif: Optional[str] = None, gif_dither: str = "bayer", gif_loop: int = 0) -> dict:
     """The reference's `DistributedVideoDiffuser(cfg)()` (:47-276) end to end -> its result dict (:263-275): pipeline
     components (`model_id` = a local checkpoint directory in diffusers layout, else seeded synthetic weights: nothing can be
     downloaded here), text embeddings (:96-103), chunked denoising + exchange + blend, per-frame VAE decode (:219-225),
-    boundary metrics (:227-247) and the mp4 (:250-253) on rank 0, peak memory reduced over the ranks (:255-261)."""
+    boundary metrics (:227-247) and the mp4 (:250-253) on rank 0, peak memory reduced over the ranks (:255-261).  `out_gif`
+    (no reference counterpart): rank 0 also writes the frames the mp4 gets, interpolated ones included, as an animated GIF on
+    the GPU (vdx/gif.py) with `gif_dither` and the repeat count `gif_loop`; the result then carries "gif"."""
     import os
 
     from . import metrics
     from .compat.diffusers_shim import DiffusionPipeline
     from .compat import pynvml_shim
     opts = resolve(cfg, exchange, world_size(env=True), job=True)        # every refusal, before anything is loaded
+    if out_gif:                                 # the GIF's own refusals that need no frames, before anything is loaded too
+        from . import gif
+        gif.check_job_args(cfg.fps * opts.interpolate, gif_dither, gif_loop)
     factor, loop, pixel_mask = opts.interpolate, opts.loop, opts.pixel_mask
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
         # like the reference (:41-50): one process per GPU, backend "nccl" (= RCCL).  Rehearsal aids, never set by a real run:
@@ -902,18 +912,22 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     if loop:                                    # the loop's seam beside the clip's ordinary frame-to-frame change, on the host
         wrap_l1, mean_l1 = metrics.loop_l1(frames)
         info["loop"] = {**info["loop"], "wrap_l1": wrap_l1, "mean_l1": mean_l1}
-    frames_written = None
-    if d.rank == 0 and out_video:
+    frames_written = gif_info = None
+    if d.rank == 0 and (out_video or out_gif):
         to_write, fps = frames, cfg.fps
         if factor > 1:
             # after the metrics above, which are numbers about the generated frames; `frames` itself (what --clip_json and
             # --mdvqs_json score) stays as it is
             from .interp import interpolate_frames
             to_write, fps = interpolate_frames(frames, factor, device=dev, **({"loop": True} if loop else {})), cfg.fps * factor
-            if not gpu_video_write:
-                to_write = list(to_write.cpu().numpy())
-        metrics.write_video(to_write, out_video, fps, restart_rows=video_restart_rows, device=dev if gpu_video_write else None)
-        frames_written = len(to_write)
+        if out_video:
+            host = factor > 1 and not gpu_video_write
+            metrics.write_video(list(to_write.cpu().numpy()) if host else to_write, out_video, fps, restart_rows=video_restart_rows,
+                                device=dev if gpu_video_write else None)
+            frames_written = len(to_write)
+        if out_gif:                             # the same frames at the same rate; interpolated frames stay on the device
+            from . import gif
+            gif_info = gif.write_gif(out_gif, to_write, fps, loop=gif_loop, dither=gif_dither, device=dev)
     delay = emu_reduce_delay_s(cfg)             # :257-258
     if delay > 0:
         time.sleep(delay)
@@ -934,7 +948,15 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **lora_record(info),
-            **prompt_record(info)}
+            **prompt_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+
+
+GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
+
+
+def gif_record(res: dict) -> dict:
+    """{"gif": what `--out_gif` wrote} of a job's result for the JSON records; {} for a job without the flag."""
+    return {"gif": res["gif"]} if "gif" in res else {}
 
 
 def write_record(path: str, rec: dict, dumps=lambda rec: json.dumps(rec, indent=1)) -> None:
@@ -958,12 +980,14 @@ def main(argv=None) -> int:
     if a.score_from_file and not a.out_video:
         raise ValueError("--score_from_file needs --out_video")
     res = run_job(cfg, exchange=a.exchange, out_video=a.out_video, clip_inputs=clip_inputs,
-                  video_restart_rows=a.video_restart_rows, gpu_video_write=a.gpu_video_write)
+                  video_restart_rows=a.video_restart_rows, gpu_video_write=a.gpu_video_write,
+                  **({"out_gif": a.out_gif, "gif_dither": a.gif_dither, "gif_loop": a.gif_loop} if a.out_gif else {}))
     if res["rank"] == 0:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res)}
+        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res),
+                  **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -990,7 +1014,8 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res)})
+            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res),
+                        **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

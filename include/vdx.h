@@ -1004,6 +1004,50 @@ int vdx_mjpeg_enc_entropy(const void* tables, int F, int W, int H, int layout, i
 int vdx_mjpeg_enc_pack(const void* header, int header_bytes, int F, int W, int H, int layout, int restart_interval,
                        const void* workspace, const int32_t* lengths, void* out, size_t out_bytes, vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Animated GIF89a of a whole clip (no reference counterpart: the reference leaves through an .mp4 alone)
+ * (csrc/gif.hip; vdx/gif.py cuts the palette and writes the headers on the host; tests/gif_ref.py is the definition).
+ * One global colour table of at most 256 entries for the clip, an ordered dither, and LZW with a minimum code size of 8 over
+ * independent strips of rows.  Integers only; the only atomics are integer adds (the histogram) and ORs into zeroed words (the
+ * strips' bits): the same bytes on every run and for any number of frames per call.  u8 frames are (T, H, W, 3) RGB with
+ * packed pixels, frame_pitch and row_pitch in bytes; T * H * W < 2^32, H and W in 1..65535.
+ * ---------------------------------------------------------------------------------------- */
+/* Stage 1.  hist: uint32 [32768] (device), zeroed here on the stream, then the pixels of the whole clip per 5-5-5 bin
+ * (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3).  Plain global integer atomics (a thread adds a run of equal bins at once): the
+ * counts are exact.                                                                                                     */
+int vdx_gif_hist_u8(const void* frames, size_t frame_pitch, int row_pitch, int T, int H, int W, uint32_t* hist,
+                    vdx_stream_t stream);
+/* Stage 3.  palette: uint8 [n][3] (device), n in 1..256.  lut: uint8 [32768], for every bin the entry nearest to the bin's
+ * centre (v << 3 | 4 per channel) by integer squared distance, a tie to the lowest index.  One launch, the palette in LDS. */
+int vdx_gif_lut(const void* palette, int n, void* lut, vdx_stream_t stream);
+/* Stage 4.  dither 1 (bayer): v' = clamp(v + D[y & 7][x & 7], 0, 255) per channel with D = ((B8 * 8 + 4) >> 6) - 4 in -4..3, B8
+ * the standard 8x8 Bayer matrix; dither 0: v' = v.  out: uint8 (T, H, W) contiguous = lut[bin(v')].  A pixel's index depends
+ * on that pixel, its position in its frame and the lut alone.                                                           */
+int vdx_gif_index_u8(const void* frames, size_t frame_pitch, int row_pitch, int T, int H, int W, const void* lut, int dither,
+                     void* out, vdx_stream_t stream);
+/* Bytes of workspace of stages 5 and 6 for T frames of W x H cut into strips of strip_rows rows (>= H: one strip); 0 for
+ * arguments the encoder does not take (a frame whose strips' slots reach 2^32 bits among them).                        */
+size_t vdx_gif_lzw_workspace(int T, int H, int W, int strip_rows);
+/* offsets[8] (host memory): byte offsets in the workspace of the uint32 bits of every strip [T][strips], their uint32 bit
+ * offsets in the frame [T][strips], the uint32 bits of every frame [T], the strips' slots uint32 [T][strips][slot_words] and
+ * the frames' streams uint32 [T][strips * slot_words] (bit i of a stream is bit i & 31 of word i >> 5) and the uint64 byte
+ * offsets of the frames' sub-blocks in the packed output [T]; then the strips of a frame and slot_words.  The slot bound: a strip of n pixels emits at most n data codes (each consumes a pixel), one CLEAR
+ * per 3838 of them (what the table takes between resets), its opening CLEAR and its closing CLEAR / EOI, at most 12 bits
+ * each: slot_words = ceil(12 (n + n / 3838 + 3) / 32), n = min(strip_rows, H) * W.                                      */
+int vdx_gif_lzw_offsets(int T, int H, int W, int strip_rows, size_t* offsets);
+/* Stage 5.  idx: uint8 (T, H, W) contiguous.  Strip s of a frame is rows [s * strip_rows, ...); its codes are [CLEAR, for
+ * the frame's first strip] data codes, then CLEAR, or EOI for the frame's last strip, from an empty table at width 9: no
+ * strip's bits depend on another strip.  CLEAR = 256, EOI = 257; the table holds 4096 codes and a full table is answered by
+ * CLEAR; the width grows when the next free code exceeds 1 << width, up to 12, and the closing code is written at the width
+ * after the entry the decoder adds for the last data code.  One strip per wave, the dictionary an open-addressed table of
+ * 8192 words in LDS (33 024 bytes per workgroup with the staged pixels: four strips per compute unit); every probe sequence is bounded by the table's slots, the pixel loop by the strip's pixels.  The strips'
+ * bits are concatenated per frame, LSB first.  lengths: int32 [T] (device): the bytes of every frame's data sub-blocks,
+ * L + ceil(L / 255) + 1 for L stream bytes; their exclusive sums go to the workspace for stage 6.                        */
+int vdx_gif_lzw(const void* idx, int T, int H, int W, int strip_rows, void* workspace, int32_t* lengths, vdx_stream_t stream);
+/* Stage 6, on the workspace stage 5 left.  out: every frame's stream as data sub-blocks (a length byte, up to 255 bytes, ..., a
+ * 00 terminator), frame f at the sum of stage 5's lengths[0 .. f); out_bytes: the size of `out`, past which nothing is stored. */
+int vdx_gif_pack(const void* workspace, int T, int H, int W, int strip_rows, void* out, size_t out_bytes, vdx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,17 @@ SIGNATURES = {
                                                   _i, _i, _vp]),
     "vdx_cofuse_cfg_rescale_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f,
                                                  _f, _f, _f, _f, _i, _i, _i, _vp]),
+    # dynamic thresholding with a mimic scale: the statistics pass (sums, histogram, select) and the fused steps, plain and
+    # co-fused (no reference counterpart; vdx/scheduler.py `cfg_mimic`, csrc/dynthresh.hip)
+    "vdx_cfg_mimic_ws_bytes": (_sz, [_i, _i, _i]),
+    "vdx_cfg_mimic_stats_f16": (_i, [_vp, _i, _i, _i, _f, _f, _sz, _f, _vp, _i, _vp]),
+    "vdx_cfg_mimic_ddim_step_f16": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_cfg_mimic_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_mimic_ws_bytes": (_sz, [_i, _i, _i]),
+    "vdx_cofuse_cfg_mimic_stats_f16": (_i, [_vp, _sz, _vp, _vp, _vp, _i, _vp, _f, _f, _sz, _f, _vp, _i, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_mimic_ddim_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_mimic_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i,
+                                               _i, _i, _vp]),
     # masked video-to-video: the per-step select, the paste and the mask's two maps (no reference counterpart; vdx/inpaint.py,
     # csrc/inpaint.hip)
     "vdx_mask_renoise_f16": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _i, _vp]),

@@ -58,6 +58,17 @@ __device__ __forceinline__ f16 cfg_rescale_elem(f16 g, float r, float phi, float
     return rn16(__fadd_rn((float)h2, (float)h3));
 }
 
+// ---- dynamic thresholding with a mimic scale (dynthresh.hip states the statistics) -------------------------------------------
+//   dc = clamp(d, -s, s),  g' = ((dc / s) * ref_lo) + mg      d = g - mg, the guided noise less its channel's mean; s, ref_lo, mg:
+//   the channel's fp16-valued scalars.  The compares are float compares (a NaN d stays NaN), the division is a division.
+__device__ __forceinline__ f16 cfg_mimic_elem(f16 d, float s, float ref_lo, float mg) {
+    const float df = (float)d;
+    const float dc = df > s ? s : (df < -s ? -s : df);
+    const f16 h1 = rn16(__fdiv_rn(dc, s));                // dc / s
+    const f16 h2 = rn16(__fmul_rn((float)h1, ref_lo));    // (dc / s) * ref_lo
+    return rn16(__fadd_rn((float)h2, mg));
+}
+
 // ---- DPM-Solver++ (2M, midpoint): dpm.hip's header states the expression ----------------------
 struct dpm_coef {
     float gs, s0, inv_a0, cx, d0, d1, inv_r0;

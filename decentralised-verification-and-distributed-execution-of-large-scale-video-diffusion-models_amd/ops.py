@@ -944,11 +944,11 @@ def _cofuse_args(what, z, windows, table, wn, strided=False):
     return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, *sd, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
 
 
-def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None, strided=False):
+def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None, strided=False, mimic_ws=None):
     """The DDIM form of every whole-clip fused step, launched as `symbol`(head, out, extras, tail) and named in errors as the
     wrapper, `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head (`strided`: with its fourth column), else
-    `_cotile_args`'; `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out).  One call below the public wrapper
-    and no closure: launch-bound."""
+    `_cotile_args`'; `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out); `mimic_ws`: the thresholded variants'
+    statistics workspace.  One call below the public wrapper and no closure: launch-bound."""
     what = symbol[4:-4]
     head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
     if out is None:
@@ -959,12 +959,15 @@ def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, r
     if rescaled is not None:
         _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
         bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
+    elif mimic_ws is not None:
+        bufs = (_mimic_ws(what, z.shape, z, mimic_ws)[1],)
     s1, sa, sp, s1p = (float(c) for c in coeffs)
     _launch(symbol, *head, _p(out, "out"), *bufs, float(guidance), *phis, s1, sa, sp, s1p, *tail)
     return out
 
 
-def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None, strided=False):
+def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None, strided=False,
+                 mimic_ws=None):
     """The DPM-Solver++ form of the same, through `_dpm_args` -> (z', x0)."""
     what = symbol[4:-4]
     head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
@@ -973,6 +976,8 @@ def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev
     if rescaled is not None:
         _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
         bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
+    elif mimic_ws is not None:
+        bufs = (_mimic_ws(what, z.shape, z, mimic_ws)[1],)
     _launch(symbol, *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), *bufs, float(guidance), *phis,
             *c, *tail)
     return out, x0_out
@@ -1217,6 +1222,128 @@ def cofuse_cfg_rescale_dpm_step(z, windows, table, wn, guidance, rescale, coeffs
     """`cofuse_cfg_dpm_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_dpm_step_f16`) -> (z', x0)."""
     return _co_dpm_step("vdx_cofuse_cfg_rescale_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
                         (rescale, partials, stats_out))
+
+
+# --------------------------------------------------------------------------------------------
+# Dynamic thresholding with a mimic scale (vdx/scheduler.py `cfg_mimic`, csrc/dynthresh.hip; no reference counterpart)
+MIMIC_BINS, MIMIC_MAX_ROWS = 32768, 64
+_MIMIC_WS: dict = {}    # the statistics pass's workspace, per (device, stream)
+
+
+def mimic_factors(mimic_scale, percentile, M: int):
+    """(`cfg_mimic`, `cfg_mimic_percentile`, the elements per channel) -> the kernels' scalars (fp32 ms, k, f): ms rounded to fp32
+    ONCE (a Python float holding the fp32 value), and the rank pos = q * (M - 1) formed ONCE in Python double and split into
+    k = floor(pos) and f = fp32(pos - k).  `ValueError` for a scale that is not a finite number > 0 and a percentile outside
+    (0, 1]."""
+    import math
+    import struct
+    if isinstance(mimic_scale, bool) or not isinstance(mimic_scale, (int, float)) or not math.isfinite(mimic_scale) or not mimic_scale > 0:
+        raise ValueError(f"cfg_mimic must be a finite number > 0, got {mimic_scale!r}")
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float)) or not 0.0 < percentile <= 1.0:
+        raise ValueError(f"cfg_mimic_percentile must be a number in (0, 1], got {percentile!r}")
+    if isinstance(M, bool) or not isinstance(M, int) or not 1 <= M < 1 << 32:
+        raise ValueError(f"cfg_mimic: a channel must hold between 1 and 2^32 - 1 elements, got {M!r}")
+    f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]     # noqa: E731
+    pos = float(percentile) * float(M - 1)
+    k = min(int(math.floor(pos)), M - 1)
+    f = f32(pos - k)
+    if not f < 1.0:                                                # the fraction rounded up to 1: the next rank, exactly
+        k, f = min(k + 1, M - 1), 0.0
+    return f32(float(mimic_scale)), k, f
+
+
+def mimic_ws_bytes(C_: int, T: int, HW: int) -> int:
+    """Bytes of the statistics workspace of a (C, T, HW) sample (`vdx_cfg_mimic_ws_bytes`); 0 for a shape the kernels refuse."""
+    return int(_lib.load().vdx_cfg_mimic_ws_bytes(int(C_), int(T), int(HW)))
+
+
+def mimic_ws_views(ws, C_: int):
+    """The workspace's parts as views (include/vdx.h states the layout) -> {"scal": fp16 (C, 4) = (mg, ref_lo, ref_hi, s),
+    "maxbits": int32 (C,), "partials": float64 (C, 64, 2), "hist": int32 (C, 32768)}.  For tests and tools: the loop never reads them."""
+    up = lambda v: (v + 15) // 16 * 16                              # noqa: E731
+    o_max = up(C_ * 8)
+    o_part = o_max + up(C_ * 4)
+    o_hist = o_part + C_ * MIMIC_MAX_ROWS * 16
+    end = o_hist + C_ * MIMIC_BINS * 4
+    b = ws.view(torch.uint8).reshape(-1)
+    return {"scal": b[:C_ * 8].view(torch.float16).view(C_, 4), "maxbits": b[o_max:o_max + C_ * 4].view(torch.int32),
+            "partials": b[o_part:o_hist].view(torch.float64).view(C_, MIMIC_MAX_ROWS, 2),
+            "hist": b[o_hist:end].view(torch.int32).view(C_, MIMIC_BINS)}
+
+
+def _mimic_ws(what, shape, like, ws):
+    """-> (the workspace, its pointer, (C, T, HW)) for a sample of `shape` = (.., C, T, h, w): the per-stream workspace when none
+    is given, else a contiguous uint8 tensor of at least `mimic_ws_bytes`."""
+    Cc, T, HW = int(shape[-4]), int(shape[-3]), int(shape[-2]) * int(shape[-1])
+    need = mimic_ws_bytes(Cc, T, HW)
+    if need < 1:
+        raise VdxError(f"{what}: empty or oversized sample")
+    if ws is None:
+        ws = _scratch(_MIMIC_WS, like.device, need, torch.uint8)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise VdxError(f"{what}: the workspace must be contiguous uint8 with at least {need} bytes")
+    return ws, _p(ws, "ws", torch.uint8), (Cc, T, HW)
+
+
+def _eps2_5d(what, eps2, lat):
+    _eps2_like(what, eps2, lat)
+    if eps2.dim() != 5:
+        raise VdxError(f"{what}: eps2 must be (2,C,T,H,W): the statistics are per channel")
+
+
+def cfg_mimic_stats(eps2, guidance, mimic, ws=None, stages: int = 7):
+    """The statistics pass of the dynamically thresholded step (include/vdx.h `vdx_cfg_mimic_stats_f16`): three launches (the
+    sums, the histogram, the select) that leave every channel's (mg, ref_lo, ref_hi, s) in the workspace -> the workspace, the
+    per-stream one unless `ws` is given: valid until the next statistics pass on this stream.  `mimic`: `mimic_factors`' triple
+    for this sample's channel size.  `stages`: the launches to run, 1 | 2 | 4 (tests and the benchmark)."""
+    _eps2_5d("cfg_mimic_stats", eps2, None)
+    ws, wp, shape = _mimic_ws("cfg_mimic_stats", eps2.shape, eps2, ws)
+    ms, k, f = mimic
+    _launch("vdx_cfg_mimic_stats_f16", _p(eps2, "eps2"), *shape, float(guidance), float(ms), int(k), float(f), wp, int(stages))
+    return ws
+
+
+def cfg_mimic_ddim_step(eps2, lat, guidance, coeffs, ws, out=None):
+    """`cfg_ddim_step` with the guided noise thresholded per channel by the scalars `cfg_mimic_stats` of the same eps2 left in
+    `ws` (`vdx_cfg_mimic_ddim_step_f16`)."""
+    _eps2_5d("cfg_mimic_ddim_step", eps2, lat)
+    if out is None:
+        out = torch.empty_like(lat)
+    _, wp, shape = _mimic_ws("cfg_mimic_ddim_step", lat.shape, lat, ws)
+    s1, sa, sp, s1p = (float(c) for c in coeffs)
+    _launch("vdx_cfg_mimic_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), wp, float(guidance), s1, sa, sp, s1p, *shape)
+    return out
+
+
+def cfg_mimic_dpm_step(eps2, lat, guidance, coeffs, ws, x0_prev=None, x0_out=None, out=None):
+    """`cfg_dpm_step` with the thresholded guided noise (`vdx_cfg_mimic_dpm_step_f16`) -> (lat', x0)."""
+    _eps2_5d("cfg_mimic_dpm_step", eps2, lat)
+    x0_out, out, c = _dpm_args("cfg_mimic_dpm_step", lat, x0_prev, x0_out, out, coeffs)
+    _, wp, shape = _mimic_ws("cfg_mimic_dpm_step", lat.shape, lat, ws)
+    _launch("vdx_cfg_mimic_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
+            _p(out, "out"), wp, float(guidance), *c, *shape)
+    return out, x0_out
+
+
+def cofuse_cfg_mimic_stats(z, windows, table, wn, guidance, mimic, ws=None, stages: int = 7):
+    """The statistics pass of the thresholded co-denoising step (`vdx_cofuse_cfg_mimic_stats_f16`): `cfg_mimic_stats` of the noise
+    fused from the windows as `cofuse_cfg_ddim_step` fuses it, over the whole clip.  z gives the shape only."""
+    head, tail = _cofuse_args("cofuse_cfg_mimic_stats", z, windows, table, wn)
+    ws, wp, _ = _mimic_ws("cofuse_cfg_mimic_stats", z.shape, z, ws)
+    ms, k, f = mimic
+    _launch("vdx_cofuse_cfg_mimic_stats_f16", *head[1:], float(guidance), float(ms), int(k), float(f), wp, int(stages), *tail)
+    return ws
+
+
+def cofuse_cfg_mimic_ddim_step(z, windows, table, wn, guidance, coeffs, ws, out=None):
+    """`cofuse_cfg_ddim_step` with the thresholded guided noise (`vdx_cofuse_cfg_mimic_ddim_step_f16`)."""
+    return _co_ddim_step("vdx_cofuse_cfg_mimic_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out, mimic_ws=ws)
+
+
+def cofuse_cfg_mimic_dpm_step(z, windows, table, wn, guidance, coeffs, ws, x0_prev=None, x0_out=None, out=None):
+    """`cofuse_cfg_dpm_step` with the thresholded guided noise (`vdx_cofuse_cfg_mimic_dpm_step_f16`) -> (z', x0)."""
+    return _co_dpm_step("vdx_cofuse_cfg_mimic_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
+                        mimic_ws=ws)
 
 
 # --------------------------------------------------------------------------------------------

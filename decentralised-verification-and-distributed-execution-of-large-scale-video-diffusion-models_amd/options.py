@@ -108,6 +108,29 @@ def check_guidance_rescale(cfg) -> float:
     return float(phi)
 
 
+def check_cfg_mimic(cfg) -> Optional[dict]:
+    """`cfg.cfg_mimic` / `cfg.cfg_mimic_percentile` as {"scale", "percentile"} (None when off); `ValueError` before any work for a
+    scale that is not a finite number > 0, a percentile outside (0, 1] or given without a scale, `guidance_scale <= 1` (there is
+    no high scale to tame), and together with `guidance_rescale` (both rewrite the guided noise, and no order is defined) or with
+    `tile`, `loop` or `context_stride` > 1 (the statistics pass has no tiled, ring or strided form, as the rescale's has none).
+    The option's refusals live here, as the regions' do in their check: `RULES` lists the co-denoising family only."""
+    ms, q = getattr(cfg, "cfg_mimic", None), getattr(cfg, "cfg_mimic_percentile", 1.0)
+    if ms is None:
+        if q != 1.0:
+            raise ValueError(f"cfg_mimic_percentile {q!r} needs cfg_mimic")
+        return None
+    ops.mimic_factors(ms, q, 1)
+    if not cfg.guidance_scale > 1:
+        raise ValueError(f"cfg_mimic {ms!r} needs guidance_scale > 1, got {cfg.guidance_scale!r}")
+    if cfg.guidance_rescale != 0:
+        raise ValueError("cfg_mimic and guidance_rescale exclude each other: both rewrite the guided noise, and no order is defined")
+    for on, name, form in ((cfg.tile is not None, "tile", "tiled"), (cfg.loop, "loop", "ring"),
+                           (cfg.context_stride != 1, "context_stride", "strided")):
+        if on:
+            raise ValueError(f"cfg_mimic and {name} exclude each other: the thresholding's statistics pass has no {form} form yet")
+    return {"scale": float(ms), "percentile": float(q)}
+
+
 def check_tome(cfg) -> Optional[dict]:
     """`cfg.tome` / `cfg.tome_seed` as {"ratio", "sx", "sy", "seed", "max_downsample"} (None when off); `ValueError` before any work
     for a ratio `enable_tome` refuses, or a seed without a ratio."""
@@ -321,6 +344,7 @@ class JobOptions:
     lora_found: Optional[tuple] = None                              # what `read_lora` found in them (`run_job` fills it in): the record
     prompt_syntax: str = "plain"                                    # "plain" | "a1111" (vdx/prompt.py)
     prompt_found: Optional[dict] = None                             # the chunked texts' record (`run_job` fills it in once they are encoded)
+    cfg_mimic: Optional[dict] = None                                # dynamic thresholding: {"scale", "percentile"} (csrc/dynthresh.hip)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -350,6 +374,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         regions = check_regions(cfg)
         lora = check_lora(cfg)
         syntax = check_prompt_syntax(cfg, job_texts(cfg, travel, regions))
+        mimic = check_cfg_mimic(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -361,11 +386,13 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         regions = check_regions(cfg)
         lora = check_lora(cfg)
         syntax = check_prompt_syntax(cfg)
+        mimic = check_cfg_mimic(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
-                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax)
+                      guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
+                      cfg_mimic=mimic)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -388,6 +415,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(region_record(opts))
     out.update(lora_record(opts))
     out.update(prompt_record(opts))
+    out.update(mimic_record(opts))
     return out
 
 
@@ -437,6 +465,16 @@ def prompt_record(src) -> dict:
     if src.prompt_found is None:
         return {}
     return {"prompt_syntax": dict(src.prompt_found)}
+
+
+def mimic_record(src) -> dict:
+    """`{"cfg_mimic": {"scale", "percentile"}}` beside `record_options`' entries, only when the option is set (else {}): from the
+    resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"cfg_mimic": src["cfg_mimic"]} if "cfg_mimic" in src else {}
+    if src.cfg_mimic is None:
+        return {}
+    return {"cfg_mimic": dict(src.cfg_mimic)}
 
 
 def record_options(res: dict) -> dict:

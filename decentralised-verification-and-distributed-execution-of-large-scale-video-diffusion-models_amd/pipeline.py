@@ -36,8 +36,8 @@ from . import ops
 from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
-from .options import JobOptions, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, job_texts, lora_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
+from .options import JobOptions, check_cfg_mimic, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
+from .options import info_options, job_texts, lora_record, mimic_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -140,6 +140,13 @@ class DiffuserConfig:
     # of a job at the same length); the UNet's cross-attentions then see up to 308 rows.  A text of at most 75 tokens without
     # emphasis gives the same job bit for bit.  "plain" = one 77-position sequence, the rest truncated, every token alike, as always
     prompt_syntax: str = "plain"
+    # dynamic thresholding of the guided noise (vdx/scheduler.py, csrc/dynthresh.hip; the A1111 / ComfyUI "Dynamic Thresholding (CFG
+    # Scale Fix)" with its mimic scale, restated and unpinned): at every step each channel of the guided noise, less its mean, is
+    # clamped at the `cfg_mimic_percentile` quantile of its magnitude and squeezed into the range the same prediction has at the
+    # scale `cfg_mimic`, so a high `guidance_scale` keeps its direction without saturating.  No extra UNet call.  Needs
+    # `guidance_scale` > 1; not with `guidance_rescale`, `tile`, `loop` or `context_stride` > 1.  None = off, as always
+    cfg_mimic: Optional[float] = None
+    cfg_mimic_percentile: float = 1.0
 
     @property
     def use_fsdp(self):
@@ -295,6 +302,9 @@ class DistributedVideoDiffuser:
         check_tome(cfg)
         phi = check_guidance_rescale(cfg)
         self._rescale_kw = {"guidance_rescale": phi} if phi != 0 else {}     # off: the step is called as it always was
+        mimic = check_cfg_mimic(cfg)
+        if mimic is not None:                   # never with rescale (`check_cfg_mimic`): the step's one set of extra keywords
+            self._rescale_kw = {"cfg_mimic": mimic["scale"], "cfg_mimic_percentile": mimic["percentile"]}
         if check_free_init(cfg) > 1 and init_latents is not None:
             raise ValueError("free_init_iters > 1 and init_latents exclude each other: FreeInit re-initialises a start from pure noise")
         self.free_init_starts: List[torch.Tensor] = []             # the start latents of iterations 1.. of the last call
@@ -670,6 +680,11 @@ def build_arg_parser():
                    help="text of the unconditional branch of classifier-free guidance (default: the empty prompt)")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="CFG rescale phi in [0, 1] (Lin et al. 2023): 0, the default, is off; needs --guidance_scale > 1")
+    p.add_argument("--cfg_mimic", type=float, default=None, metavar="M",
+                   help="dynamic thresholding of the guided noise towards the mimic scale M, per channel and step (default: off; needs "
+                        "--guidance_scale > 1; not with --guidance_rescale, --tile, --loop or --context_stride > 1)")
+    p.add_argument("--cfg_mimic_percentile", type=float, default=1.0, metavar="Q",
+                   help="with --cfg_mimic: clamp each channel at this quantile of its magnitude, in (0, 1] (default 1.0: its maximum)")
     p.add_argument("--prompt_at", nargs=2, action="append", default=None, metavar=("FRAME", "TEXT"),
                    help="prompt travel: TEXT is the prompt at frame FRAME, frames between two such keys blend them (repeatable; "
                         "--prompt is the key at frame 0 unless one names it; default: off)")
@@ -947,7 +962,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "strength": cfg.strength if cfg.init_video is not None else None, "steps_run": info["steps_run"], "encode_s": encode_s,
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
-            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **lora_record(info),
+            **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
             **prompt_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
@@ -986,7 +1001,7 @@ def main(argv=None) -> int:
         row = metrics.result_row(res, mode=cfg.mode, num_frames=cfg.num_frames, elapsed_s=time.time() - t0)
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
-        source = {**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res),
+        source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
                   **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
@@ -1014,7 +1029,7 @@ def main(argv=None) -> int:
             # likewise after the row; always the generated frames, whatever --score_from_file and --interpolate do to the file
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
-            rec.update({**record_options(res), **travel_record(res), **region_record(res), **lora_record(res), **prompt_record(res),
+            rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
                         **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():

@@ -64,6 +64,17 @@ class _SchedulerBase:
             st = self.rescale_stats = torch.zeros(8, dtype=torch.float16, device=device)
         return ops.rescale_factors(guidance_rescale), st
 
+    def _mimic(self, cfg_mimic, percentile, sample):
+        """Dynamic thresholding (csrc/dynthresh.hip): `ops.mimic_factors` of the sample's channel size, kept per (scale, percentile,
+        size): the float64 rank is formed once."""
+        if sample.dim() != 5:
+            raise ValueError("cfg_mimic needs a (1,C,T,H,W) sample: the statistics are per channel")
+        key = (cfg_mimic, percentile, sample.shape[2] * sample.shape[3] * sample.shape[4])
+        if self._mimic_factors is None or self._mimic_factors[0] != key:
+            self._mimic_factors = (key, ops.mimic_factors(*key))
+        return self._mimic_factors[1]
+
+    _mimic_factors = None
     _dpm = None         # False / True: which of an `ops` step's two forms, (DDIM, DPM-Solver++), this scheduler launches
 
     def _begin(self, timestep, sample):
@@ -71,11 +82,21 @@ class _SchedulerBase:
         once the kernel was enqueued).  It changes nothing that a launch which raises would have to undo."""
         raise NotImplementedError
 
-    def _fused_step(self, steps, head, timestep, sample, guidance_scale, guidance_rescale=0.0, rescaled=None):
+    def _fused_step(self, steps, head, timestep, sample, guidance_scale, guidance_rescale=0.0, rescaled=None, cfg_mimic=None,
+                    cfg_mimic_percentile=1.0, mimicked=None):
         """`steps[self._dpm](*head, ...)`, `steps` = the (DDIM, DPM-Solver++) pair of an `ops` step.  With `guidance_rescale` != 0
-        `rescaled` = (the statistics op, its leading arguments, the pair of rescaled steps): two launches and no host read."""
+        `rescaled` = (the statistics op, its leading arguments, the pair of rescaled steps): two launches and no host read.  With
+        `cfg_mimic` (csrc/dynthresh.hip) `mimicked` is the same triple of the thresholded steps: four launches and no host read,
+        the statistics in `ops`' per-stream workspace."""
+        if cfg_mimic is not None and guidance_rescale != 0.0:
+            raise ValueError("cfg_mimic and guidance_rescale exclude each other: both rewrite the guided noise, and no order is defined")
         coeffs, history, commit = self._begin(timestep, sample)
-        if guidance_rescale == 0.0:
+        if cfg_mimic is not None:
+            stats_op, stats_head, steps = mimicked
+            factors = self._mimic(cfg_mimic, cfg_mimic_percentile, sample)
+            ws = stats_op(*stats_head, guidance_scale, factors)
+            res = steps[self._dpm](*head, guidance_scale, coeffs, ws, **history)
+        elif guidance_rescale == 0.0:
             res = steps[self._dpm](*head, guidance_scale, coeffs, **history)
         else:
             stats_op, stats_head, steps = rescaled
@@ -85,24 +106,33 @@ class _SchedulerBase:
         commit()
         return res[0] if self._dpm else res                       # the DPM-Solver++ ops return (the new latent, x0)
 
-    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+    def step_cfg(self, noise2, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0, cfg_mimic=None,
+                 cfg_mimic_percentile: float = 1.0):
         """Fused `u + gs*(c-u)` + step (fsdp_chunked_coherent.py:141-142) in one kernel (`vdx_cfg_ddim_step_f16` /
         `vdx_cfg_dpm_step_f16`).  `guidance_rescale` != 0 (Lin et al. 2023, diffusers' `rescale_noise_cfg`; csrc/rescale.hip): the
         guided noise is rescaled towards the standard deviation of the conditional one over this sample, in two launches (the
-        statistics, then the step) and without a host read."""
-        if self._dpm or guidance_rescale != 0.0:                  # the plain DDIM op refuses a non-contiguous sample itself
+        statistics, then the step) and without a host read.  `cfg_mimic` (a mimic scale; dynamic thresholding, csrc/dynthresh.hip):
+        every channel of the guided noise, less its mean, is clamped at the `cfg_mimic_percentile` quantile of its magnitude and
+        squeezed into the range the same prediction has at the mimic scale, in four launches and without a host read.  Not both."""
+        if self._dpm or guidance_rescale != 0.0 or cfg_mimic is not None:   # the plain DDIM op refuses a non-contiguous sample itself
             sample = sample.contiguous()
         return self._fused_step((ops.cfg_ddim_step, ops.cfg_dpm_step), (noise2, sample), timestep, sample, guidance_scale,
-                                guidance_rescale, (ops.cfg_rescale_stats, (noise2,), (ops.cfg_rescale_ddim_step, ops.cfg_rescale_dpm_step)))
+                                guidance_rescale, (ops.cfg_rescale_stats, (noise2,), (ops.cfg_rescale_ddim_step, ops.cfg_rescale_dpm_step)),
+                                cfg_mimic, cfg_mimic_percentile,
+                                (ops.cfg_mimic_stats, (noise2,), (ops.cfg_mimic_ddim_step, ops.cfg_mimic_dpm_step)))
 
-    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0):
+    def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0,
+                         cfg_mimic=None, cfg_mimic_percentile: float = 1.0):
         """Co-denoising (vdx/codenoise.py): `step_cfg` of the whole clip's latent `sample` on the noise fused from the
         windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step` / `ops.cofuse_cfg_dpm_step`), one
-        kernel; with `guidance_rescale` != 0 two, the statistics being those of the fused noise over the whole clip."""
+        kernel; with `guidance_rescale` != 0 two, with `cfg_mimic` four, the statistics being those of the fused noise over the
+        whole clip."""
         head = (sample.contiguous(), windows, table, wn)
         return self._fused_step((ops.cofuse_cfg_ddim_step, ops.cofuse_cfg_dpm_step), head, timestep, head[0], guidance_scale,
                                 guidance_rescale, (ops.cofuse_cfg_rescale_stats, head,
-                                                   (ops.cofuse_cfg_rescale_ddim_step, ops.cofuse_cfg_rescale_dpm_step)))
+                                                   (ops.cofuse_cfg_rescale_ddim_step, ops.cofuse_cfg_rescale_dpm_step)),
+                                cfg_mimic, cfg_mimic_percentile,
+                                (ops.cofuse_cfg_mimic_stats, head, (ops.cofuse_cfg_mimic_ddim_step, ops.cofuse_cfg_mimic_dpm_step)))
 
     def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
         """Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`): `step_cfg_windows` with every time window's block holding

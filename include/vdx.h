@@ -467,6 +467,46 @@ int vdx_cofuse_cfg_rescale_dpm_step_f16(const void* z, const void* windows, size
                                         void* x0_out, void* lat_out, const double* partials, void* stats_out, float guidance,
                                         float phi, float phi1, float c_s0, float c_inv_a0, float c_x, float c_d0, float c_d1,
                                         float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
+/* Classifier-free guidance with dynamic thresholding towards a mimic scale (the "Dynamic Thresholding (CFG Scale Fix)" of the A1111 /
+ * ComfyUI world; no reference counterpart and no external pin, opt-in: `cfg_mimic` of vdx/scheduler.py, csrc/dynthresh.hip, restated
+ * in tests/dynthresh_ref.py).  The sample is (C, T, HW), M = T*HW elements per channel, M below 2^32.  With g the combine above at
+ * `guidance` and l the same combine at `mimic`, per channel: mg = fp16(sum g / M), ml = fp16(sum l / M) (fp64 sums in a fixed order,
+ * one division, one rounding); d = fp16(g - mg), e = fp16(l - ml); ref_lo = max |e| as the integer bits & 0x7fff; ref_hi = the
+ * linear interpolation fp16(lo + f*(hi - lo)) (fp32, each operation rounded; lo's bits when f == 0) between the order statistics
+ * lo = a[k], hi = a[min(k+1, M-1)] of the channel's bits(d) & 0x7fff in ascending integer order; s = whichever of ref_lo, ref_hi
+ * has the larger bit pattern; g' = fp16(fp16(fp16(clamp(d, -s, s) / s) * ref_lo) + mg) takes g's place in the step.  No other clamp:
+ * a constant channel (s = 0), NaN and infinity give what the lines give, in their channel only.  k in [0, M-1] and f in [0, 1) are
+ * the host's floor and fraction of q*(M-1) in float64; `mimic` is finite and > 0; all refused otherwise.
+ * ws: `vdx_cfg_mimic_ws_bytes(C, T, HW)` bytes (0 for a shape the entries refuse), 16-byte aligned, apart from every other buffer;
+ * it may hold anything on entry.  Its layout, every part at a multiple of 16 bytes:
+ *   scal fp16 [C][4] = (mg, ref_lo, ref_hi, s) | maxbits uint32 [C] | partials double [C][64][2] | hist uint32 [C][32768]
+ * The statistics entry is three launches: 1 the sums (rows [sum g, sum l] per channel, their number a function of the shapes
+ * alone and <= 64; it also zeroes hist and maxbits), 2 the histogram and the maximum (integer atomics only), 4 the select, which
+ * writes scal.  `stages` is the set of launches to run: 7 for a step; tests and the benchmark run them one at a time.  The step
+ * entries read scal.  Everything else as for the step of the same name without "mimic".                                          */
+size_t vdx_cfg_mimic_ws_bytes(int C, int T, int HW);
+int vdx_cfg_mimic_stats_f16(const void* eps2, int C, int T, int HW, float guidance, float mimic, size_t k, float f, void* ws,
+                            int stages, vdx_stream_t stream);
+int vdx_cfg_mimic_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, const void* ws, float guidance,
+                                float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float sqrt_one_minus_aprev, int C, int T,
+                                int HW, vdx_stream_t stream);
+int vdx_cfg_mimic_dpm_step_f16(const void* eps2, const void* lat, const void* x0_prev, void* x0_out, void* lat_out, const void* ws,
+                               float guidance, float c_s0, float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, int C,
+                               int T, int HW, vdx_stream_t stream);
+/* The same for co-denoising: U and Cc fused from the windows exactly as in vdx_cofuse_cfg_ddim_step_f16 (in launches 1 and 2 and
+ * in the step), the statistics over the whole clip; the rows per channel are min(T, 64).                                         */
+size_t vdx_cofuse_cfg_mimic_ws_bytes(int C, int T, int HW);
+int vdx_cofuse_cfg_mimic_stats_f16(const void* windows, size_t windows_elems, const int64_t* win_off, const int* win_start,
+                                   const int* win_len, int K, const float* wn, float guidance, float mimic, size_t k, float f,
+                                   void* ws, int stages, int C, int T, int HW, vdx_stream_t stream);
+int vdx_cofuse_cfg_mimic_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                       const int* win_start, const int* win_len, int K, const float* wn, void* lat_out,
+                                       const void* ws, float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                                       float sqrt_one_minus_aprev, int C, int T, int HW, vdx_stream_t stream);
+int vdx_cofuse_cfg_mimic_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                      const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                      void* x0_out, void* lat_out, const void* ws, float guidance, float c_s0, float c_inv_a0,
+                                      float c_x, float c_d0, float c_d1, float c_inv_r0, int C, int T, int HW, vdx_stream_t stream);
 /* Masked video-to-video (keep frames or regions of --init_video, generate the rest; no reference counterpart, opt-in:
  * vdx/inpaint.py, csrc/inpaint.hip).  Masks are uint8, 1 = regenerate, 0 = keep; every entry point is a SELECT of bits (no
  * arithmetic on the mask: no 0*inf, -0 keeps its sign, NaN / inf stay in their element).  tests/inpaint_ref.py states it.

@@ -247,6 +247,10 @@ SIGNATURES = {
     "vdx_gif_lzw_offsets": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "vdx_gif_lzw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vdx_gif_pack": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    # the portable seeded noise generator (no reference counterpart; vdx/noise.py, csrc/noise.hip)
+    "vdx_noise_f16": (_i, [_sz, _sz, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _f, _vp, _vp]),
+    "vdx_noise_f32": (_i, [_sz, _sz, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
+    "vdx_noise_form": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
 }
 
 _lib = None

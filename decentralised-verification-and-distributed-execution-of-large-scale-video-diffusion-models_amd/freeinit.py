@@ -84,10 +84,10 @@ def freq_mix(z_T: torch.Tensor, eta: torch.Tensor, filt: torch.Tensor) -> torch.
     return ops.freeinit_mix(z_T.contiguous(), eta.contiguous(), filt.to(z_T.device).contiguous())
 
 
-def reinit(z0: torch.Tensor, base_noise: torch.Tensor, scheduler, iteration: int, filt: torch.Tensor, noise_device=None):
+def reinit(z0: torch.Tensor, base_noise: torch.Tensor, scheduler, iteration: int, filt: torch.Tensor, noise_device=None, seed=None):
     """One whole re-initialisation: the blended latent `z0` (any float dtype, (B, C, T, h, w)) of iteration `iteration - 1` and
     the job's base noise (fp16, the same shape) -> the fp16 start latent of iteration `iteration` >= 1 (0 is the seed of the
-    base noise itself).  `noise_device` as in `pipeline.seeded_noise`."""
+    base noise itself).  `noise_device` and `seed` (the portable generator's, None: torch's stream) as in `pipeline.seeded_noise`."""
     from .pipeline import iteration_noise
     if isinstance(iteration, bool) or not isinstance(iteration, int) or iteration < 1:
         raise ValueError(f"free_init: reinit starts iteration 1 or later, got {iteration!r}")
@@ -95,5 +95,5 @@ def reinit(z0: torch.Tensor, base_noise: torch.Tensor, scheduler, iteration: int
         raise VdxError(f"free_init: latent {tuple(z0.shape)} and base noise {tuple(base_noise.shape)} differ in shape")
     dev = base_noise.device
     z_T = scheduler.add_noise(z0.to(dev, torch.float16).contiguous(), base_noise, scheduler.config.num_train_timesteps - 1)
-    eta = iteration_noise(tuple(z0.shape), iteration, dev, noise_device)
+    eta = iteration_noise(tuple(z0.shape), iteration, dev, noise_device, **({"seed": seed} if seed is not None else {}))
     return freq_mix(z_T, eta, filt)

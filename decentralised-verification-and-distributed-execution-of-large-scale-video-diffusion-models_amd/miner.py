@@ -23,6 +23,25 @@ def leaf_hash(t: int, z: torch.Tensor, eps: torch.Tensor) -> bytes:
     return hashlib.sha256(int(t).to_bytes(2, "big") + z.cpu().numpy().tobytes() + eps.cpu().numpy().tobytes()).digest()
 
 
+def seeded_latent(seed: int, shape, device, frames=None) -> torch.Tensor:
+    """The start latent `denoise_with_trace` takes, from the validator's 64-bit seed (`proof.py:11-15`) alone: the base stream of
+    the portable generator "philox4x32-10/v1" (vdx/noise.py) over the logical (1, C, T, h, w) `shape`, fp16, unscaled (the
+    miner's DDIM has init_noise_sigma 1).  `frames` = (t0, t1): only the frames [t0, t1) of it, (1, C, t1 - t0, h, w), with the
+    bits the whole latent has there; a validator's frame-0 spot check regenerates `frames=(0, 1)` without the clip."""
+    from . import noise, ops
+    shape = tuple(shape)
+    if len(shape) != 5 or shape[0] != 1:
+        raise VdxError(f"seeded_latent: shape must be (1, C, T, h, w), got {shape}")
+    box = None
+    if frames is not None:
+        if (not isinstance(frames, (tuple, list)) or len(frames) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in frames)
+                or not 0 <= frames[0] < frames[1] <= shape[2]):
+            raise ValueError(f"seeded_latent: frames must be (t0, t1) with 0 <= t0 < t1 <= {shape[2]}, got {frames!r}")
+        t0, t1 = frames
+        box = ((0, 0, t0, 0, 0), (1, shape[1], t1 - t0, shape[3], shape[4]))
+    return ops.philox_normal(shape, noise.check_seed(seed), noise.STREAM_BASE, box=box, device=device)
+
+
 @torch.no_grad()
 def denoise_with_trace(unet, scheduler, z: torch.Tensor, encoder_hidden_states: torch.Tensor, num_steps: int) -> Dict:
     """miner.py:516-586.  z (1,4,T,h,w) fp16 initial noise on the GPU; encoder_hidden_states (1,77,D) fp16.

@@ -2472,3 +2472,81 @@ def gif_pack(workspace, T: int, H: int, W: int, strip_rows: int, out) -> torch.T
         _launch("vdx_gif_pack", _gif_u8(workspace, need, "gif_pack", "workspace"), T, H, W, strip_rows, _gif_u8(out, 1, "gif_pack", "out"),
                 out.numel())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# the portable seeded noise generator "philox4x32-10/v1" (no reference counterpart; include/vdx.h "Portable seeded noise";
+# csrc/noise.hip; vdx/noise.py holds the streams' names and the job's `normal`; tests/noise_ref.py is the definition)
+NOISE_MAX_DIMS = 5
+
+
+def _noise_int(what: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v < hi:
+        raise ValueError(f"{what} must be an integer in [{lo}, {hi}), got {v!r}")
+    return v
+
+
+def philox_box(shape, box=None):
+    """(shape, start, extent) as tuples of ints of one length, checked on the host: 1..5 axes of size >= 1, fewer than 2^63
+    elements, `box` = (start, extent) within the shape with extents >= 1 (None: the whole tensor); `ValueError` otherwise."""
+    shape = tuple(shape)
+    if not 1 <= len(shape) <= NOISE_MAX_DIMS:
+        raise ValueError(f"philox_normal: the logical shape has 1 to {NOISE_MAX_DIMS} axes, got {shape!r}")
+    total = 1
+    for d, n in enumerate(shape):
+        total *= _noise_int(f"philox_normal: shape[{d}]", n, 1, 2 ** 63)
+    if total >= 2 ** 63:
+        raise ValueError(f"philox_normal: the logical tensor {shape} must have fewer than 2^63 elements")
+    if box is None:
+        return shape, (0,) * len(shape), shape
+    if not isinstance(box, (tuple, list)) or len(box) != 2 or any(not isinstance(v, (tuple, list)) or len(v) != len(shape) for v in box):
+        raise ValueError(f"philox_normal: box must be (start, extent), each of {len(shape)} integers, got {box!r}")
+    start, extent = tuple(box[0]), tuple(box[1])
+    for d, n in enumerate(shape):
+        _noise_int(f"philox_normal: extent[{d}]", extent[d], 1, n + 1)
+        _noise_int(f"philox_normal: start[{d}] (extent {extent[d]} of {n})", start[d], 0, n - extent[d] + 1)
+    return shape, start, extent
+
+
+def _noise_arrays(shape, start, extent):
+    arr = C.c_size_t * len(shape)
+    return len(shape), arr(*shape), arr(*start), arr(*extent)
+
+
+def philox_form(shape, box=None) -> bool:
+    """True when that box takes the kernel's fast form (a lane per Philox block), False for the general one (`vdx_noise_form`)."""
+    rc = _lib.load().vdx_noise_form(*_noise_arrays(*philox_box(shape, box)))
+    if rc < 0:
+        _lib.check(rc, "vdx_noise_form")
+    return bool(rc)
+
+
+def philox_normal(shape, seed: int, stream: int = 0, *, box=None, sigma: float = 1.0, dtype=torch.float16, device, out=None):
+    """N(0, 1) of the generator "philox4x32-10/v1" (csrc/noise.hip): element i of stream `stream` under `seed`, both in [0, 2^64),
+    is a pure function of (seed, stream, i), i the C-order index in the LOGICAL tensor `shape`.  `box` = (start, extent): only that
+    box of it, with the bits the whole tensor has there.  -> a new contiguous tensor of the box's shape on `device` (or `out`, of
+    that shape and dtype): fp32(n) for `dtype` float32, fp16(fp32(fp16(n)) * fp32(sigma)) for float16 (`sigma` goes with float16
+    only).  `ValueError` / `VdxError` before any launch for arguments outside these."""
+    import math
+    shape, start, extent = philox_box(shape, box)
+    seed, stream = _noise_int("philox_normal: seed", seed, 0, 2 ** 64), _noise_int("philox_normal: stream", stream, 0, 2 ** 64)
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"philox_normal: dtype must be torch.float16 or torch.float32, got {dtype}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or abs(sigma) > 3.4028234663852886e38:
+        raise ValueError(f"philox_normal: sigma must be a finite number (fp32), got {sigma!r}")
+    if dtype == torch.float32 and sigma != 1.0:
+        raise ValueError("philox_normal: sigma goes with float16 (the start latent's scale); float32 output is N(0, 1) itself")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise VdxError(f"philox_normal: expected a GPU device (the generator has no host form in the package), got {device}")
+    if out is None:
+        out = torch.empty(extent, dtype=dtype, device=device)
+    elif not out.is_cuda or tuple(out.shape) != extent or out.dtype != dtype or not out.is_contiguous():
+        raise VdxError(f"philox_normal: out must be a contiguous {dtype} GPU tensor of shape {extent}")
+    nd, sh, st, ex = _noise_arrays(shape, start, extent)
+    with torch.cuda.device(out.device):
+        if dtype == torch.float16:
+            _launch("vdx_noise_f16", seed, stream, nd, sh, st, ex, float(sigma), _p(out, "out"))
+        else:
+            _launch("vdx_noise_f32", seed, stream, nd, sh, st, ex, _p(out, "out", torch.float32))
+    return out

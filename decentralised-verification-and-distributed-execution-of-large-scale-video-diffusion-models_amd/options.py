@@ -131,6 +131,35 @@ def check_cfg_mimic(cfg) -> Optional[dict]:
     return {"scale": float(ms), "percentile": float(q)}
 
 
+def check_noise(cfg) -> Optional[dict]:
+    """`cfg.noise` / `cfg.seed` as {"generator", "seed"} (None for "torch", the reference's stream, as always); `ValueError` before
+    any work for a generator that is neither "torch" nor "philox", a seed that is no integer in [0, 2^64), a seed with "torch" (a
+    chosen seed gets the portable generator; the torch stream stays what the reference draws: its seeds are fixed), and under
+    "philox" a `noise_device` other than the job's device (the generator has no host form in the package).  "philox" without a
+    seed is seed 0.  The front end's `--seed N` alone selects "philox" (`pipeline.config_from_args`)."""
+    from . import noise as _noise
+    gen, seed = getattr(cfg, "noise", "torch"), getattr(cfg, "seed", None)
+    if gen not in _noise.GENERATORS:
+        raise ValueError(f"noise must be one of {_noise.GENERATORS}, got {gen!r}")
+    if seed is not None:
+        _noise.check_seed(seed)
+    if gen == "torch":
+        if seed is not None:
+            raise ValueError(f"seed {seed!r} needs noise=\"philox\" (--seed alone selects it): the torch stream's seeds are the "
+                             "reference's and stay fixed")
+        return None
+    if cfg.noise_device is not None:
+        import torch
+        try:
+            nd, dev = torch.device(cfg.noise_device), torch.device(cfg.device)
+        except (RuntimeError, TypeError):
+            raise ValueError(f"noise_device {cfg.noise_device!r} is no device") from None
+        if nd.type != dev.type or (nd.index is not None and dev.index is not None and nd.index != dev.index):
+            raise ValueError(f"noise=\"philox\" draws on the job's device {cfg.device!r}, noise_device is {cfg.noise_device!r}: the "
+                             "generator has no host form in the package, and its bits do not depend on the device")
+    return _noise.record(0 if seed is None else seed)
+
+
 def check_tome(cfg) -> Optional[dict]:
     """`cfg.tome` / `cfg.tome_seed` as {"ratio", "sx", "sy", "seed", "max_downsample"} (None when off); `ValueError` before any work
     for a ratio `enable_tome` refuses, or a seed without a ratio."""
@@ -345,6 +374,7 @@ class JobOptions:
     prompt_syntax: str = "plain"                                    # "plain" | "a1111" (vdx/prompt.py)
     prompt_found: Optional[dict] = None                             # the chunked texts' record (`run_job` fills it in once they are encoded)
     cfg_mimic: Optional[dict] = None                                # dynamic thresholding: {"scale", "percentile"} (csrc/dynthresh.hip)
+    noise: Optional[dict] = None                                    # the portable generator: {"generator", "seed"} (vdx/noise.py); None: torch's stream
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -375,6 +405,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         lora = check_lora(cfg)
         syntax = check_prompt_syntax(cfg, job_texts(cfg, travel, regions))
         mimic = check_cfg_mimic(cfg)
+        noise = check_noise(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -387,12 +418,13 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         lora = check_lora(cfg)
         syntax = check_prompt_syntax(cfg)
         mimic = check_cfg_mimic(cfg)
+        noise = check_noise(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
-                      cfg_mimic=mimic)
+                      cfg_mimic=mimic, noise=noise)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -416,6 +448,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(lora_record(opts))
     out.update(prompt_record(opts))
     out.update(mimic_record(opts))
+    out.update(noise_record(opts))
     return out
 
 
@@ -475,6 +508,16 @@ def mimic_record(src) -> dict:
     if src.cfg_mimic is None:
         return {}
     return {"cfg_mimic": dict(src.cfg_mimic)}
+
+
+def noise_record(src) -> dict:
+    """`{"noise": {"generator": "philox4x32-10/v1", "seed"}}` beside `record_options`' entries, only when the portable generator is
+    selected (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"noise": src["noise"]} if "noise" in src else {}
+    if src.noise is None:
+        return {}
+    return {"noise": dict(src.noise)}
 
 
 def record_options(res: dict) -> dict:

@@ -32,12 +32,13 @@ from typing import List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import noise as _noise
 from . import ops
 from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
-from .options import JobOptions, check_cfg_mimic, check_free_init, check_freeu, check_guidance_rescale, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, job_texts, lora_record, mimic_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
+from .options import JobOptions, check_cfg_mimic, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
+from .options import info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -147,6 +148,13 @@ class DiffuserConfig:
     # `guidance_scale` > 1; not with `guidance_rescale`, `tile`, `loop` or `context_stride` > 1.  None = off, as always
     cfg_mimic: Optional[float] = None
     cfg_mimic_percentile: float = 1.0
+    # the noise generator (vdx/noise.py, csrc/noise.hip; Philox4x32-10 + Box-Muller, restated in tests/noise_ref.py and unpinned):
+    # "philox" draws the start latent, FreeInit's fresh noise and the video-to-video posterior sample from the portable generator
+    # "philox4x32-10/v1" under `seed` (an integer in [0, 2^64), None = 0): the same bits on every device, rank and torch build, and any
+    # box of them can be regenerated from the seed alone.  A seed needs "philox" (`--seed N` alone selects it).  "torch", None = the
+    # reference's `torch.manual_seed(0)` stream on the device, as always
+    seed: Optional[int] = None
+    noise: str = "torch"
 
     @property
     def use_fsdp(self):
@@ -190,9 +198,12 @@ def _noise_device(device, noise_device=None) -> torch.device:
     return torch.device(device if noise_device is None else noise_device)
 
 
-def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
+def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16, seed: Optional[int] = None):
     """`torch.manual_seed(0); randn(...) * init_noise_sigma` (:180-182).  RNG streams are
-    device-specific, so parity runs pass noise_device="cpu" (SURVEY.md §8 a2)."""
+    device-specific, so parity runs pass noise_device="cpu" (SURVEY.md §8 a2).  `seed` (the portable generator, vdx/noise.py):
+    its base stream under that seed instead, times sigma, on `device`: no torch generator is touched."""
+    if seed is not None:
+        return _noise.normal(shape, device, seed=seed, stream=_noise.STREAM_BASE, sigma=sigma, dtype=dtype)
     nd = _noise_device(device, noise_device)
     torch.manual_seed(0)
     base = torch.randn(*shape, device=nd, dtype=dtype)
@@ -200,9 +211,12 @@ def seeded_noise(shape, sigma, device, noise_device=None, dtype=torch.float16):
     return base.to(device)
 
 
-def iteration_noise(shape, iteration: int, device, noise_device=None):
+def iteration_noise(shape, iteration: int, device, noise_device=None, seed: Optional[int] = None):
     """FreeInit's fresh noise of iteration `iteration` >= 1: fp32 N(0, 1) from a generator of its own seeded with the iteration
-    number (seed 0 is `seeded_noise`'s), generated on `noise_device` like the base noise; the global generator is left alone."""
+    number (seed 0 is `seeded_noise`'s), generated on `noise_device` like the base noise; the global generator is left alone.
+    `seed` (the portable generator): stream `iteration` under that seed instead."""
+    if seed is not None:
+        return _noise.normal(shape, device, seed=seed, stream=_noise.stream_of_iteration(int(iteration)), dtype=torch.float32)
     nd = _noise_device(device, noise_device)
     g = torch.Generator(device=nd).manual_seed(int(iteration))
     return torch.randn(*shape, generator=g, device=nd, dtype=torch.float32).to(device)
@@ -298,6 +312,9 @@ class DistributedVideoDiffuser:
         `region.RegionPlan` of the clip.  Every UNet call then gains `regions=(region_embs, plan, its window)` (`region_kw`).
         None: off."""
         self.cfg = cfg
+        check_noise(cfg)
+        self._seed = _noise.generator_of(cfg)                         # the portable generator's seed; None: torch's stream, as always
+        self._seed_kw = {"seed": self._seed} if self._seed is not None else {}
         check_freeu(cfg)
         check_tome(cfg)
         phi = check_guidance_rescale(cfg)
@@ -345,14 +362,14 @@ class DistributedVideoDiffuser:
             if tuple(init_latents.shape) != shape:
                 raise ValueError(f"init_latents {tuple(init_latents.shape)} != {shape}")
             self.timesteps = vid2vid_timesteps(scheduler, cfg.steps, cfg.strength)
-            base = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+            base = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device, **self._seed_kw)
             self._x0, self._base = init_latents.to(cfg.device, torch.float16).contiguous(), base
             self._start = scheduler.add_noise(self._x0, base, self.timesteps[0])
             if cfg.use_ctx:                                           # the frame-mean of the whole clip's start latent
                 self.ctx = self._start.mean(dim=2, keepdim=True).contiguous()
         elif cfg.use_ctx:                                             # reference :105-127
             if self.rank == 0:
-                full = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+                full = seeded_noise(shape, scheduler.init_noise_sigma, cfg.device, cfg.noise_device, **self._seed_kw)
                 ctx = full.mean(dim=2, keepdim=True)
             else:
                 ctx = torch.empty(shape[:2] + (1,) + shape[3:], device=cfg.device, dtype=torch.float16)
@@ -531,7 +548,7 @@ class DistributedVideoDiffuser:
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
         if self._start is None:
-            base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device)
+            base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device, **self._seed_kw)
         else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
             base = self._start
         T = cfg.num_frames
@@ -571,7 +588,7 @@ class DistributedVideoDiffuser:
                     rec["denoise_s"].append(spent["denoise_s"])
                 if it + 1 < iters:
                     t0 = time.time()
-                    start = freeinit.reinit(out, base, self.scheduler, it + 1, filt, cfg.noise_device)
+                    start = freeinit.reinit(out, base, self.scheduler, it + 1, filt, cfg.noise_device, **self._seed_kw)
                     if cfg.use_ctx:
                         self.ctx = start.mean(dim=2, keepdim=True).contiguous()
                     self._sync()
@@ -623,6 +640,12 @@ def build_arg_parser():
     p.add_argument("--out_csv", default="results.csv")
     p.add_argument("--exchange", choices=["allgather", "halo"], default="allgather")
     p.add_argument("--noise_device", default=None)
+    p.add_argument("--seed", type=int, default=None, metavar="N",
+                   help="draw the job's noise from the portable generator philox4x32-10/v1 under seed N in [0, 2^64): the same start "
+                        "latent on every device and rank (default: the reference's torch stream, seed 0)")
+    p.add_argument("--noise", choices=list(_noise.GENERATORS), default=None,
+                   help="the noise generator: torch (the reference's device-dependent stream, the default) or philox (the portable one; "
+                        "--seed N selects it, alone it means seed 0)")
     p.add_argument("--out_video", default="out.mp4")
     p.add_argument("--clip_json", default=None, help="write the CLIP quality score of the decoded frames here (rank 0)")
     p.add_argument("--clip_model", default=None, help="local CLIP ViT-B/32 directory (transformers layout) for --clip_json")
@@ -710,6 +733,8 @@ def config_from_args(a) -> DiffuserConfig:
     """The parsed flags as a `DiffuserConfig`: every field that has a flag takes that flag's value."""
     flag_of = {f.name: FLAG_OF_FIELD.get(f.name, f.name) for f in fields(DiffuserConfig)}
     cfg = DiffuserConfig(**{name: getattr(a, flag) for name, flag in flag_of.items() if flag is not None})
+    if cfg.noise is None:                       # --seed N alone selects the portable generator; --noise torch --seed N is refused
+        cfg.noise = "philox" if cfg.seed is not None else "torch"
     if cfg.freeu is not None:
         cfg.freeu = tuple(cfg.freeu)
     if cfg.tile is not None:
@@ -826,7 +851,10 @@ def encode_init_video(cfg: DiffuserConfig, vae, dev, return_frames: bool = False
     if frames.shape[1:3] != (cfg.height, cfg.width):
         frames = ops.resize_u8(frames, cfg.height, cfg.width)
     noise = None
-    if cfg.posterior == "sample":
+    if cfg.posterior == "sample" and _noise.generator_of(cfg) is not None:       # the portable generator's posterior stream
+        noise = _noise.normal((cfg.num_frames, 4, cfg.height // 8, cfg.width // 8), dev, seed=_noise.generator_of(cfg),
+                              stream=_noise.STREAM_POSTERIOR)
+    elif cfg.posterior == "sample":
         nd = _noise_device(dev, cfg.noise_device)
         g = torch.Generator(device=nd).manual_seed(1)
         noise = torch.randn((cfg.num_frames, 4, cfg.height // 8, cfg.width // 8), generator=g, device=nd,
@@ -963,7 +991,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1002,7 +1030,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **gif_record(res)}
+                  **noise_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1030,7 +1058,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **gif_record(res)})
+                        **noise_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -1088,6 +1088,25 @@ int vdx_gif_lzw(const void* idx, int T, int H, int W, int strip_rows, void* work
  * 00 terminator), frame f at the sum of stage 5's lengths[0 .. f); out_bytes: the size of `out`, past which nothing is stored. */
 int vdx_gif_pack(const void* workspace, int T, int H, int W, int strip_rows, void* out, size_t out_bytes, vdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Portable seeded noise "philox4x32-10/v1" (no reference counterpart: fsdp_chunked_coherent.py:180-182 is torch's stream, which
+ * depends on the device and the torch build) (csrc/noise.hip; vdx/noise.py; tests/noise_ref.py is the definition).
+ * Element i of stream `stream` under `seed` is a pure function of (seed, stream, i), i the C-order linear index in the LOGICAL
+ * tensor `shape` (ndim 1..5 axes, fewer than 2^63 elements): Philox4x32-10 with key (seed lo, seed hi) and counter (q lo, q hi,
+ * stream lo, stream hi), q = i >> 2; Box-Muller in fp64 on the block's word pairs with the file's own ln, sin and cos (stated
+ * sequences of fp64 + - * / sqrt: the same bits on every device).  out: the box [start, start + extent) of the logical tensor,
+ * contiguous, of the box's shape, 16-byte aligned: fp32(n), or fp16(fp32(fp16(n)) * sigma).  The same bits for the whole tensor or
+ * any box of it; no atomics, no state.  Refused: a box that leaves the shape, an extent < 1, 2^63 elements or more, a sigma
+ * that is not finite.  seed and stream are 64-bit values passed as size_t.
+ * ---------------------------------------------------------------------------------------- */
+int vdx_noise_f16(size_t seed, size_t stream, int ndim, const size_t* shape, const size_t* start, const size_t* extent, float sigma,
+                  void* out, vdx_stream_t stream_handle);
+int vdx_noise_f32(size_t seed, size_t stream, int ndim, const size_t* shape, const size_t* start, const size_t* extent, void* out,
+                  vdx_stream_t stream_handle);
+/* 1 when that box takes the fast form (a lane per Philox block, 8- or 16-byte stores), 0 for the general one (a lane per
+ * output), -1 for a box the entries refuse.  The bits do not depend on the form.                                            */
+int vdx_noise_form(int ndim, const size_t* shape, const size_t* start, const size_t* extent);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,16 @@
-// cofuse_common.h — what the co-fused whole-clip steps share: the window table, the fp32 fuse of the windows' noise, the vector
-// accesses, the ONE line-per-block step kernel with its tail, dispatch and launcher, and the host checks.  codenoise.hip (the plain
-// co-denoising steps, flat and ring), rescale.hip (the same steps with CFG rescale and their statistics pass) and cotile.hip (the
-// row-per-block tiled steps) all go through these, so the variants cannot drift apart.  A variant is a guidance policy (what turns
-// the fused u, c into the guided noise), the RING flag, the table type (`costride_tab`: a frame stride per row), or a block map of
-// its own that ends in `cofuse_tail`.
+// cofuse_common.h — what the co-fused whole-clip steps share on top of step_common.h: the window table, the fp32 fuse of the windows'
+// noise (as a function and as the statistics passes' noise source), the ONE line-per-block step kernel with its launcher, and the
+// host checks.  codenoise.hip (the plain co-denoising steps, flat and ring), rescale.hip and dynthresh.hip (the same steps with CFG
+// rescale / dynamic thresholding and their statistics passes) and cotile.hip (the row-per-block tiled steps) all go through these,
+// so the variants cannot drift apart.  A variant is a guidance policy (what turns the fused u, c into the guided noise), the RING
+// flag, the table type (`costride_tab`: a frame stride per row), or a block map of its own that ends in `cofuse_tail`.
 #pragma once
 #include <cstdint>
 #include <type_traits>
 
 #include "vdx_common.h"
 #include "step_chains.h"   // rn16
+#include "step_common.h"   // the vector accesses, the policies, the tail, the dispatch, the aliasing check
 
 #define COFUSE_MAX_WINDOWS 64
 
@@ -26,33 +27,6 @@ struct costride_tab : cofuse_tab {
     int d[COFUSE_MAX_WINDOWS];             // frame stride, >= 1
 };
 template <class Tab> constexpr bool co_strided = std::is_same<Tab, costride_tab>::value;
-
-template <int E> struct halves;
-template <> struct halves<8> { typedef f16x8 type; };
-template <> struct halves<4> { typedef f16x4 type; };
-template <> struct halves<1> { typedef f16 type; };
-
-template <int E>
-__device__ __forceinline__ void load_halves(const f16* p, f16 (&v)[E]) {
-    if constexpr (E == 1) {
-        v[0] = p[0];
-    } else {
-        const typename halves<E>::type h = *(const typename halves<E>::type*)p;
-#pragma unroll
-        for (int j = 0; j < E; ++j) v[j] = h[j];
-    }
-}
-template <int E>
-__device__ __forceinline__ void store_halves(f16* p, const f16 (&v)[E]) {
-    if constexpr (E == 1) {
-        p[0] = v[0];
-    } else {
-        typename halves<E>::type h;
-#pragma unroll
-        for (int j = 0; j < E; ++j) h[j] = v[j];
-        *(typename halves<E>::type*)p = h;
-    }
-}
 
 // x = fp16(x + fp16(weight * ctx)) on E elements: the ctx term of every UNet-input kernel, with `cfg_input_kernel`'s two roundings
 template <int E>
@@ -73,15 +47,14 @@ __device__ __forceinline__ float fuse_term(float acc, float w, float x, bool fir
     return first ? prod : __fadd_rn(acc, prod);
 }
 
-// U, Cc of the E elements at (c, t, p) fused over the windows that hold frame t, k ascending, then rounded to fp16 (returned as
-// the floats the chains take).  t is uniform over a block, so the window loop, the table reads and the weights are too.
+// U, Cc of the E elements at (c, t, p) fused over the windows that hold frame t, k ascending, then rounded to fp16.  t is uniform over a block, so the window loop, the table reads and the weights are too.
 // RING (the vdx_coloop_* steps): window k holds the frames (s_k + f) mod T, f in [0, L_k), with 0 <= s_k < T and L_k <= T, so the one
 // wrap is a compare and an add; the default leaves the plain instantiations as they were.
 // A `costride_tab` (the vdx_costride_* steps): window k holds frame t as its frame q / d_k where q = t - s_k >= 0, q % d_k == 0 and
 // q / d_k < L_k: one unsigned division per window, on block-uniform integers.
 template <int E, bool RING = false, class Tab = cofuse_tab>
 __device__ __forceinline__ void cofuse_uc(const f16* win, const Tab& tab, int K, const float* wn, int C, int T, int HW, int c,
-                                          int t, int p, float (&uf)[E], float (&cf)[E]) {
+                                          int t, int p, f16 (&uf)[E], f16 (&cf)[E]) {
     float U[E], Cc[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) U[j] = Cc[j] = 0.f;
@@ -115,68 +88,51 @@ __device__ __forceinline__ void cofuse_uc(const f16* win, const Tab& tab, int K,
     }
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        uf[j] = (float)rn16(U[j]);
-        cf[j] = (float)rn16(Cc[j]);
+        uf[j] = rn16(U[j]);
+        cf[j] = rn16(Cc[j]);
     }
 }
 
-
-// ---- the step itself ---------------------------------------------------------------------------------------------------------------
-// A guidance policy turns the fused (u, c) of one element into the new latent (and x0).  `prologue()` is called by all 256 lanes of
-// a block before any of them leaves and gives one scalar per block; `elem<MODE>` is the chain of step_chains.h.  MODE 0: DDIM;
-// 1: DPM-Solver++ first order; 2: second order.  This one is plain classifier-free guidance: no state, no LDS, no prologue.
-struct cfg_guidance {
-    __device__ __forceinline__ float prologue() const { return 0.f; }
-    template <int MODE>
-    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, float, const ddim_coef& kd, const dpm_coef& kp, f16& x0,
-                                         f16& o) const {
-        if (MODE == 0) o = cfg_ddim_elem(u, c, x, kd);
-        else dpm_elem<true, MODE == 2>(u, c, x, x0p, kp, x0, o);
+// The co-fused noise source of the statistics passes (step_common.h `direct_source` is the one-buffer one): a channel is `lines`
+// consecutive (c, t) lines of the clip (T of them: a latent channel; C * T: the whole clip as one).  Block x of nx of channel ch
+// takes the channel's lines x, x + nx, ...; a lane the elements p = (lane + 256 j) E of each.
+template <int E>
+struct cofuse_source {
+    static constexpr int width = E;
+    const f16* win;
+    cofuse_tab tab;
+    int K;
+    const float* wn;
+    int C, T, HW;
+    unsigned lines;
+    template <class F>
+    __device__ __forceinline__ void each(unsigned ch, unsigned x, unsigned nx, F&& f) const {
+        for (unsigned l = x; l < lines; l += nx) {
+            const unsigned line = ch * lines + l;
+            const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
+            for (int p = (int)threadIdx.x * E; p < HW; p += 256 * E) {
+                f16 uf[E], cf[E];
+                cofuse_uc<E>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);
+                f((size_t)line * HW + p, uf, cf);
+            }
+        }
     }
 };
 
-// the tail of every co-fused step kernel: a lane's E elements at i, from their fused (u, c) to the stores
-template <int MODE, int E, class G>
-__device__ __forceinline__ void cofuse_tail(const f16* z, const f16* x0_prev, f16* x0_out, f16* out, size_t i, const float (&uf)[E],
-                                            const float (&cf)[E], const G& g, float r, const ddim_coef& kd, const dpm_coef& kp) {
-    f16 x[E], xp[E];
-    load_halves<E>(z + i, x);
-    if (MODE == 2) load_halves<E>(x0_prev + i, xp);
-    f16 o[E], x0[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) g.template elem<MODE>(uf[j], cf[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, r, kd, kp, x0[j], o[j]);
-    if (MODE != 0) store_halves<E>(x0_out + i, x0);
-    store_halves<E>(out + i, o);
-}
-
+// ---- the step itself ---------------------------------------------------------------------------------------------------------------
 // Block map: a block works on ONE (c, t) line of h*w elements (tiles of 256 lanes x E elements): see codenoise.hip.
 template <int MODE, int E, bool RING, class G, class Tab = cofuse_tab>
 __global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f16* win, Tab tab, int K, const float* wn,
                                                           const f16* x0_prev, f16* x0_out, f16* out, ddim_coef kd, dpm_coef kp, G g,
                                                           int C, int T, int HW, unsigned tiles_per_line) {
-    const float r = g.prologue();                                 // all 256 lanes, before any of them leaves
     const unsigned line = blockIdx.x / tiles_per_line, tile = blockIdx.x - line * tiles_per_line;
     const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
+    const typename G::state st = g.prologue(c);                   // all 256 lanes, before any of them leaves
     const int p = (int)((tile * 256u + threadIdx.x) * (unsigned)E);
     if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
-    float uf[E], cf[E];
+    f16 uf[E], cf[E];
     cofuse_uc<E, RING, Tab>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);   // uniform over the block: t is
-    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, r, kd, kp);
-}
-
-// go(MODE, E) as integral constants, for the one rule of the mode and an access width of 8, 4 or 1 halves
-template <class F>
-static inline void step_dispatch(int mode, const void* x0_prev, int e, F&& go) {
-    const auto width = [&](auto m) {
-        if (e == 8) go(m, std::integral_constant<int, 8>{});
-        else if (e == 4) go(m, std::integral_constant<int, 4>{});
-        else go(m, std::integral_constant<int, 1>{});
-    };
-    switch (mode == 0 ? 0 : x0_prev ? 2 : 1) {
-    case 0: width(std::integral_constant<int, 0>{}); break;
-    case 1: width(std::integral_constant<int, 1>{}); break;
-    default: width(std::integral_constant<int, 2>{}); break;
-    }
+    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, st, kd, kp);
 }
 
 // the launch of a line-per-block step whose arguments `cofuse_check` has passed (it gave `tab` and `e`)
@@ -197,17 +153,6 @@ static int cofuse_launch(const char* what, int mode, const void* z, const void* 
 }
 
 // ---- the host checks ---------------------------------------------------------------------------------------------------------------
-static inline bool co_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-// the widest access (8, 4 or 1 halves, at most `e`) that still divides v
-static inline void co_narrow(int& e, long long v) {
-    if (e == 8 && v % 8) e = v % 4 ? 1 : 4;
-    if (e == 4 && v % 4) e = 1;
-}
-
 // The time-window table of a step: every row (off, s, L) against T and the buffer, `e` narrowed to what every offset allows, and
 // every frame in some window.  `ring`: a row means the frames (s + f) mod T, so 0 <= s < T and 1 <= L <= T replace s + L <= T, and
 // a frame is held under that rule.  `need(k, L, elems)` gives the elements window k occupies from its offset (it may refuse the row).
@@ -247,27 +192,6 @@ static inline int cofuse_windows(const char* what, bool ring, size_t windows_ele
         }
         VDX_CHECK(hit, "%s: frame %d is in no window", what, t);
     }
-    return 0;
-}
-
-struct co_buf {
-    const void* p;
-    size_t bytes;
-};
-
-// What a step's outputs (nb bytes each) may share: lat_out may be z itself; otherwise no output touches z, another output, x0_prev or
-// one of `inputs`.  `x0_z` / `x0_in` end the message of an x0_out that overlaps z or lat_out / one of `inputs`.
-template <size_t N>
-static inline int cofuse_alias(const char* what, int mode, const void* z, const void* x0_prev, const void* x0_out, const void* lat_out,
-                               size_t nb, const co_buf (&inputs)[N], const char* x0_z, const char* x0_in) {
-    VDX_CHECK(lat_out == z || !co_overlap(lat_out, nb, z, nb), "%s: lat_out overlaps z without being z", what);
-    for (const co_buf& in : inputs) VDX_CHECK(!co_overlap(lat_out, nb, in.p, in.bytes), "%s: lat_out overlaps an input", what);
-    if (mode == 0) return 0;
-    VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-    VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, z, nb), "%s: x0_out overlaps %s", what, x0_z);
-    for (const co_buf& in : inputs) VDX_CHECK(!co_overlap(x0_out, nb, in.p, in.bytes), "%s: x0_out overlaps %s", what, x0_in);
-    VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-              "%s: x0_prev overlaps an output", what);
     return 0;
 }
 

@@ -52,7 +52,9 @@ __global__ __launch_bounds__(256) void cotile_kernel(const f16* z, const f16* wi
     const int y = (int)(row - ct * (unsigned)g.H);
     const int c = (int)(ct / (unsigned)g.T), t = (int)(ct - (unsigned)c * (unsigned)g.T);
     const int x = (int)((seg * blockDim.x + threadIdx.x) * (unsigned)E);
-    if (x >= g.W) return;                                         // W is a multiple of E: a lane's E elements are all inside
+    const cfg_guidance guide{};
+    const cfg_guidance::state st = guide.prologue(c);             // all lanes, before any of them leaves
+    if (x >= g.W) return;                                        // W is a multiple of E: a lane's E elements are all inside
     float U[E], Cc[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) U[j] = Cc[j] = 0.f;
@@ -86,13 +88,13 @@ __global__ __launch_bounds__(256) void cotile_kernel(const f16* z, const f16* wi
             }
         }
     }
-    float uf[E], cf[E];
+    f16 uf[E], cf[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        uf[j] = (float)rn16(U[j]);
-        cf[j] = (float)rn16(Cc[j]);
+        uf[j] = rn16(U[j]);
+        cf[j] = rn16(Cc[j]);
     }
-    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)row * g.W + x, uf, cf, cfg_guidance{}, 0.f, kd, kp);
+    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)row * g.W + x, uf, cf, guide, st, kd, kp);
 }
 
 // every band of `n0` inside [0, N), and every cell of [0, N) in some band

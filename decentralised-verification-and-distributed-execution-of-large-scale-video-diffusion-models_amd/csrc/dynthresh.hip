@@ -84,20 +84,6 @@ __device__ __forceinline__ void mimic_bins(float u, float c, float gs, float ms,
     eb = abs_bits(rn16(__fsub_rn((float)l, ml)));
 }
 
-// the block's 256 lanes' sums -> row[2]: a shuffle tree inside each wave, then the four waves in ascending order
-__device__ __forceinline__ void block_row2(double (&a)[2], double* row) {
-    __shared__ double w[4][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) a[q] += __shfl_down(a[q], off, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) w[threadIdx.x >> 6][q] = a[q];
-    __syncthreads();
-    if (threadIdx.x < 2) row[threadIdx.x] = ((w[0][threadIdx.x] + w[1][threadIdx.x]) + w[2][threadIdx.x]) + w[3][threadIdx.x];
-}
-
 // the sums launch's second duty: block x of `nx` of channel ch zeroes its share of the channel's bins, block 0 the max word
 __device__ __forceinline__ void mimic_zero(const mimic_ws& w, unsigned ch, unsigned x, unsigned nx) {
     uint32_t* h = w.hist + (size_t)ch * MIMIC_BINS;
@@ -154,43 +140,36 @@ __device__ __forceinline__ void max_fold(uint32_t* word, uint32_t mx) {
     if ((threadIdx.x & 63) == 0) atomicMax(word, mx);
 }
 
-// ---- one sample in one buffer: eps2 = [u; c], C channels of M elements each, E halves per access (M is a multiple of E) --------
-// grid (rows, C): block x of channel y takes the vectors x * 256 + lane + j * rows * 256
-template <int E>
-__global__ __launch_bounds__(256) void mimic_sums_kernel(const f16* eps, float gs, float ms, mimic_ws w, size_t M, size_t n) {
+// ---- launches 1 and 2, over either noise source ------------------------------------------------------------------------------------
+// grid (blocks, C): block x of channel y adds what the source hands it, in the source's order.  One buffer (`direct_source`, eps2 =
+// [u; c], channels of M elements): the vectors x * 256 + lane + j * blocks * 256; the sums launch has min(vectors / 256, 64) blocks.
+// Co-fused (`cofuse_source`, T lines a channel): the (y, t) lines t = x, x + blocks, ...; the sums launch has min(T, 64) blocks.
+// Either way a block's partial depends on the shapes (and the table) alone.
+template <class Src>
+__global__ __launch_bounds__(256) void mimic_sums_kernel(Src src, float gs, float ms, mimic_ws w) {
     const unsigned ch = blockIdx.y;
     mimic_zero(w, ch, blockIdx.x, gridDim.x);
     double a[2] = {0.0, 0.0};
-    const f16* up = eps + (size_t)ch * M;
-    const size_t nv = M / E, stride = (size_t)gridDim.x * 256;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
-        f16 u[E], c[E];
-        load_halves<E>(up + v * E, u);
-        load_halves<E>(up + n + v * E, c);
+    src.each(ch, blockIdx.x, gridDim.x, [&](size_t, const f16 (&uf)[Src::width], const f16 (&cf)[Src::width]) {
 #pragma unroll
-        for (int j = 0; j < E; ++j) sum_acc(a, (float)u[j], (float)c[j], gs, ms);
-    }
-    block_row2(a, w.partials + ((size_t)ch * MIMIC_MAX_ROWS + blockIdx.x) * 2);
+        for (int j = 0; j < Src::width; ++j) sum_acc(a, (float)uf[j], (float)cf[j], gs, ms);
+    });
+    block_row(a, w.partials + ((size_t)ch * MIMIC_MAX_ROWS + blockIdx.x) * 2);
 }
 
-template <int E>
-__global__ __launch_bounds__(256) void mimic_hist_kernel(const f16* eps, float gs, float ms, mimic_ws w, int nrows, size_t M, size_t n) {
+template <class Src>
+__global__ __launch_bounds__(256) void mimic_hist_kernel(Src src, float gs, float ms, mimic_ws w, int nrows, double m) {
     const unsigned ch = blockIdx.y;
     float mg, ml;
-    channel_means(w.partials + (size_t)ch * MIMIC_MAX_ROWS * 2, nrows, (double)M, mg, ml);
+    channel_means(w.partials + (size_t)ch * MIMIC_MAX_ROWS * 2, nrows, m, mg, ml);
     uint32_t* h = w.hist + (size_t)ch * MIMIC_BINS;
     uint32_t mx = 0;
-    const f16* up = eps + (size_t)ch * M;
-    const size_t nv = M / E, stride = (size_t)gridDim.x * 256;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
-        f16 u[E], c[E];
-        load_halves<E>(up + v * E, u);
-        load_halves<E>(up + n + v * E, c);
-        uint32_t db[E], eb[E];
+    src.each(ch, blockIdx.x, gridDim.x, [&](size_t, const f16 (&uf)[Src::width], const f16 (&cf)[Src::width]) {
+        uint32_t db[Src::width], eb[Src::width];
 #pragma unroll
-        for (int j = 0; j < E; ++j) mimic_bins((float)u[j], (float)c[j], gs, ms, mg, ml, db[j], eb[j]);
-        hist_add<E>(h, db, eb, mx);
-    }
+        for (int j = 0; j < Src::width; ++j) mimic_bins((float)uf[j], (float)cf[j], gs, ms, mg, ml, db[j], eb[j]);
+        hist_add<Src::width>(h, db, eb, mx);
+    });
     max_fold(w.maxbits + ch, mx);
 }
 
@@ -250,71 +229,36 @@ __global__ __launch_bounds__(256) void mimic_select_kernel(mimic_ws w, int nrows
     }
 }
 
-// g -> d -> g' -> the sampler's tail.  MODE 0: DDIM; 1: DPM-Solver++ first order; 2: second order
-template <int MODE>
-__device__ __forceinline__ void mimic_step_elem(float u, float c, float x, float x0p, float mg, float ref_lo, float s,
-                                                const ddim_coef& kd, const dpm_coef& kp, f16& x0_out, f16& out) {
-    const f16 g = cfg_combine(u, c, MODE == 0 ? kd.gs : kp.gs);
-    const f16 d = rn16(__fsub_rn((float)g, mg));
-    const f16 g2 = cfg_mimic_elem(d, s, ref_lo, mg);
-    if (MODE == 0) out = ddim_tail(g2, x, kd);
-    else dpm_tail<MODE == 2>(g2, x, x0p, kp, x0_out, out);
-}
-
-template <int MODE, int E>
-__global__ __launch_bounds__(256) void mimic_step_kernel(const f16* eps, const f16* lat, const f16* x0_prev, f16* x0_out, f16* out,
-                                                         ddim_coef kd, dpm_coef kp, const f16* scal, size_t M, size_t n) {
-    const unsigned ch = blockIdx.y;
-    const f16* sc = scal + (size_t)ch * 4;
-    const float mg = (float)sc[0], ref_lo = (float)sc[1], s = (float)sc[3];
-    const size_t base = (size_t)ch * M, nv = M / E, stride = (size_t)gridDim.x * 256;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
-        const size_t i = base + v * E;
-        f16 u[E], c[E], x[E], xp[E], o[E], x0[E];
-        load_halves<E>(eps + i, u);
-        load_halves<E>(eps + n + i, c);
-        load_halves<E>(lat + i, x);
-        if (MODE == 2) load_halves<E>(x0_prev + i, xp);
-#pragma unroll
-        for (int j = 0; j < E; ++j)
-            mimic_step_elem<MODE>((float)u[j], (float)c[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, mg, ref_lo, s, kd, kp, x0[j], o[j]);
-        if (MODE != 0) store_halves<E>(x0_out + i, x0);
-        store_halves<E>(out + i, o);
-    }
-}
-
-// the guidance policy of the co-fused step (cofuse_common.h `cofuse_step_kernel`): a block owns one (c, t) line, so `prologue`
-// hands the block's channel (as the bits of its float) to `elem`, which reads that channel's scalars: uniform loads
+// the guidance policy of every thresholded step (step_common.h `direct_step_kernel`, cofuse_common.h `cofuse_step_kernel`): the
+// block's channel's scalars are its state (uniform loads, once per block), then g -> d -> g' -> the sampler's tail
 struct mimic_guidance {
     const f16* scal;
-    unsigned tiles_per_line, T;
-    __device__ __forceinline__ float prologue() const { return __uint_as_float(blockIdx.x / tiles_per_line / T); }
+    struct state {
+        float mg, ref_lo, s;
+    };
+    static constexpr bool uses_c = true;
+    __device__ __forceinline__ state prologue(int channel) const {
+        const f16* sc = scal + (size_t)channel * 4;
+        const auto uniform = [](f16 h) {                          // the same for every lane: kept in a scalar register
+            return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint((float)h)));
+        };
+        return {uniform(sc[0]), uniform(sc[1]), uniform(sc[3])};
+    }
     template <int MODE>
-    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, float r, const ddim_coef& kd, const dpm_coef& kp, f16& x0,
-                                         f16& o) const {
-        const f16* sc = scal + (size_t)__float_as_uint(r) * 4;
-        mimic_step_elem<MODE>(u, c, x, x0p, (float)sc[0], (float)sc[1], (float)sc[3], kd, kp, x0, o);
+    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, const state& st, const ddim_coef& kd, const dpm_coef& kp,
+                                         f16& x0, f16& o) const {
+        const f16 g = cfg_combine(u, c, MODE == 0 ? kd.gs : kp.gs);
+        const f16 d = rn16(__fsub_rn((float)g, st.mg));
+        const f16 g2 = cfg_mimic_elem(d, st.s, st.ref_lo, st.mg);
+        if (MODE == 0) o = ddim_tail(g2, x, kd);
+        else dpm_tail<MODE == 2>(g2, x, x0p, kp, x0, o);
     }
 };
 
 static inline int mimic_width(size_t M) { return M % 8 == 0 ? 8 : M % 4 == 0 ? 4 : 1; }
 
-// rows of `partials` per channel = blocks per channel of the sums launch: a function of M alone
-static inline int mimic_rows(size_t M) {
-    const size_t nv = M / mimic_width(M), want = (nv + 255) / 256;
-    return (int)(want < MIMIC_MAX_ROWS ? want : MIMIC_MAX_ROWS);
-}
-
 static inline bool mimic_shape_ok(int C, int T, int HW) {
     return C > 0 && C <= 65535 && T > 0 && HW > 0 && (size_t)T * HW < ((size_t)1 << 32) && (size_t)C * T * HW <= ((size_t)1 << 40);
-}
-
-// what every statistics entry checks of its scalars: the scale, and the rank (k, f) against M
-static int mimic_check_rank(const char* what, float mimic, size_t k, float f, size_t M) {
-    VDX_CHECK(std::isfinite(mimic) && mimic > 0.f, "%s: mimic scale %g must be finite and > 0", what, (double)mimic);
-    VDX_CHECK(k <= M - 1, "%s: rank k = %zu must lie in [0, M - 1], M = %zu", what, k, M);
-    VDX_CHECK(f >= 0.f && f < 1.f, "%s: the rank's fraction f = %g must lie in [0, 1)", what, (double)f);
-    return 0;
 }
 
 extern "C" size_t vdx_cfg_mimic_ws_bytes(int C, int T, int HW) {
@@ -322,35 +266,33 @@ extern "C" size_t vdx_cfg_mimic_ws_bytes(int C, int T, int HW) {
     return mimic_shape_ok(C, T, HW) ? mimic_layout(nullptr, C, w) : 0;
 }
 
+extern "C" size_t vdx_cofuse_cfg_mimic_ws_bytes(int C, int T, int HW) { return vdx_cfg_mimic_ws_bytes(C, T, HW); }
+
+// The statistics pass of both entries, whose checks of their noise have passed: the scalars and the workspace, then the launches.
+// `src(E)` makes the noise source of access width E; `rows` / `hblocks`: the blocks a channel gets in the sums / histogram launch.
 // `stages`: bit 0 the sums, bit 1 the histogram, bit 2 the select; 7 is the statistics pass, anything else is for tests and the
-// benchmark, which run one launch at a time on what the launches before it left in the workspace
-extern "C" int vdx_cfg_mimic_stats_f16(const void* eps2, int C, int T, int HW, float guidance, float mimic, size_t k, float f, void* ws,
-                                       int stages, vdx_stream_t stream) {
-    const char* what = "vdx_cfg_mimic_stats_f16";
-    VDX_CHECK(eps2 && ws, "%s: null pointer", what);
+// benchmark, which run one launch at a time on what the launches before it left in the workspace.
+template <class MakeSrc, size_t N>
+static int mimic_stats_launch(const char* what, int e, MakeSrc&& src, const co_buf (&inputs)[N], float guidance, float mimic, size_t k,
+                              float f, void* ws, int stages, int rows, size_t hblocks, int C, int T, int HW, vdx_stream_t stream) {
     VDX_CHECK(mimic_shape_ok(C, T, HW), "%s: bad shape C=%d T=%d HW=%d (a channel holds fewer than 2^32 elements)", what, C, T, HW);
     VDX_CHECK(stages >= 1 && stages <= 7, "%s: stages %d is not a set of launches 1 | 2 | 4", what, stages);
-    const size_t M = (size_t)T * HW, n = (size_t)C * M;
-    if (int rc = mimic_check_rank(what, mimic, k, f, M)) return rc;
-    VDX_CHECK(((uintptr_t)eps2 & 15) == 0 && ((uintptr_t)ws & 15) == 0, "%s: pointer not 16-byte aligned", what);
+    const size_t M = (size_t)T * HW;
+    VDX_CHECK(std::isfinite(mimic) && mimic > 0.f, "%s: mimic scale %g must be finite and > 0", what, (double)mimic);
+    VDX_CHECK(k <= M - 1, "%s: rank k = %zu must lie in [0, M - 1], M = %zu", what, k, M);
+    VDX_CHECK(f >= 0.f && f < 1.f, "%s: the rank's fraction f = %g must lie in [0, 1)", what, (double)f);
+    VDX_CHECK(ws, "%s: null pointer", what);
+    VDX_CHECK(((uintptr_t)ws & 15) == 0, "%s: the workspace must be a 16-byte aligned pointer", what);
     mimic_ws w;
     const size_t wb = mimic_layout(ws, C, w);
-    VDX_CHECK(!co_overlap(ws, wb, eps2, 2 * n * sizeof(f16)), "%s: the workspace overlaps eps2", what);
-    const int e = mimic_width(M), rows = mimic_rows(M);
-    const size_t nv = M / e, want = (nv + 255) / 256;
+    for (const co_buf& in : inputs) VDX_CHECK(!co_overlap(ws, wb, in.p, in.bytes), "%s: the workspace overlaps an input", what);
     const hipStream_t s = (hipStream_t)stream;
-    const f16* ep = (const f16*)eps2;
-    const dim3 block(256), sgrid((unsigned)rows, (unsigned)C), hgrid((unsigned)(want < 1024 ? want : 1024), (unsigned)C);
-    if (stages & 1) {
-        if (e == 8) hipLaunchKernelGGL(mimic_sums_kernel<8>, sgrid, block, 0, s, ep, guidance, mimic, w, M, n);
-        else if (e == 4) hipLaunchKernelGGL(mimic_sums_kernel<4>, sgrid, block, 0, s, ep, guidance, mimic, w, M, n);
-        else hipLaunchKernelGGL(mimic_sums_kernel<1>, sgrid, block, 0, s, ep, guidance, mimic, w, M, n);
-    }
-    if (stages & 2) {
-        if (e == 8) hipLaunchKernelGGL(mimic_hist_kernel<8>, hgrid, block, 0, s, ep, guidance, mimic, w, rows, M, n);
-        else if (e == 4) hipLaunchKernelGGL(mimic_hist_kernel<4>, hgrid, block, 0, s, ep, guidance, mimic, w, rows, M, n);
-        else hipLaunchKernelGGL(mimic_hist_kernel<1>, hgrid, block, 0, s, ep, guidance, mimic, w, rows, M, n);
-    }
+    const dim3 block(256), sgrid((unsigned)rows, (unsigned)C), hgrid((unsigned)(hblocks < 1024 ? hblocks : 1024), (unsigned)C);
+    width_dispatch(e, [&](auto ee) {
+        auto sr = src(ee);
+        if (stages & 1) hipLaunchKernelGGL(mimic_sums_kernel<decltype(sr)>, sgrid, block, 0, s, sr, guidance, mimic, w);
+        if (stages & 2) hipLaunchKernelGGL(mimic_hist_kernel<decltype(sr)>, hgrid, block, 0, s, sr, guidance, mimic, w, rows, (double)M);
+    });
     if (stages & 4) {
         const size_t k2 = k + 1 < M ? k + 1 : M - 1;
         hipLaunchKernelGGL(mimic_select_kernel, dim3((unsigned)C), block, 0, s, w, rows, (double)M, (uint32_t)k, (uint32_t)k2, f);
@@ -358,38 +300,32 @@ extern "C" int vdx_cfg_mimic_stats_f16(const void* eps2, int C, int T, int HW, f
     return vdx_launch_status(what);
 }
 
+// ---- one sample in one buffer: eps2 = [u; c], C channels of M = T HW elements each, E halves per access (M is a multiple of E) --
+extern "C" int vdx_cfg_mimic_stats_f16(const void* eps2, int C, int T, int HW, float guidance, float mimic, size_t k, float f, void* ws,
+                                       int stages, vdx_stream_t stream) {
+    const char* what = "vdx_cfg_mimic_stats_f16";
+    VDX_CHECK(eps2, "%s: null pointer", what);
+    VDX_CHECK(((uintptr_t)eps2 & 15) == 0, "%s: pointer not 16-byte aligned", what);
+    const size_t M = (size_t)T * HW, n = (size_t)C * M;
+    const int e = mimic_width(M);
+    const size_t want = (M / e + 255) / 256;                      // rows of `partials` per channel: a function of M alone, <= 64
+    const co_buf inputs[] = {{eps2, 2 * n * sizeof(f16)}};
+    const auto src = [&](auto ee) { return direct_source<decltype(ee)::value>{(const f16*)eps2, M, n}; };
+    return mimic_stats_launch(what, e, src, inputs, guidance, mimic, k, f, ws, stages, (int)(want < MIMIC_MAX_ROWS ? want : MIMIC_MAX_ROWS),
+                              want, C, T, HW, stream);
+}
+
 static int mimic_step_launch(const char* what, int mode, const void* eps2, const void* lat, const void* x0_prev, void* x0_out,
                              void* lat_out, const void* ws, ddim_coef kd, dpm_coef kp, int C, int T, int HW, vdx_stream_t stream) {
-    VDX_CHECK(eps2 && lat && lat_out && ws && (mode == 0 || x0_out), "%s: bad arguments", what);
+    VDX_CHECK(ws, "%s: bad arguments", what);
     VDX_CHECK(mimic_shape_ok(C, T, HW), "%s: bad shape C=%d T=%d HW=%d (a channel holds fewer than 2^32 elements)", what, C, T, HW);
-    const size_t M = (size_t)T * HW, n = (size_t)C * M, nb = n * sizeof(f16);
-    for (const void* p : {eps2, lat, x0_prev, (const void*)x0_out, (const void*)lat_out, ws})
-        VDX_CHECK(((uintptr_t)p & 15) == 0, "%s: pointer not 16-byte aligned", what);
+    const size_t M = (size_t)T * HW, nb = (size_t)C * M * sizeof(f16);
     mimic_ws w;
-    const size_t wb = mimic_layout((void*)ws, C, w);
-    // a lane reads its elements before it writes them, and writes nobody else's: lat_out == lat is fine, nothing else may share
-    VDX_CHECK(lat_out == lat || !co_overlap(lat_out, nb, lat, nb), "%s: lat_out overlaps lat without being lat", what);
-    VDX_CHECK(!co_overlap(lat_out, nb, eps2, 2 * nb) && !co_overlap(lat_out, nb, ws, wb), "%s: lat_out overlaps an input", what);
-    VDX_CHECK(!co_overlap(ws, wb, eps2, 2 * nb) && !co_overlap(ws, wb, lat, nb) && (!x0_prev || !co_overlap(ws, wb, x0_prev, nb)),
-              "%s: the workspace overlaps another buffer", what);
-    if (mode != 0) {
-        VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-        VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, lat, nb) && !co_overlap(x0_out, nb, eps2, 2 * nb) &&
-                      !co_overlap(x0_out, nb, ws, wb),
-                  "%s: x0_out overlaps an input or lat_out", what);
-        VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-                  "%s: x0_prev overlaps an output", what);
-    }
-    const int e = mimic_width(M);
-    const size_t nv = M / e, want = (nv + 255) / 256;
-    const dim3 grid((unsigned)(want < 1024 ? want : 1024), (unsigned)C), block(256);
-    const hipStream_t s = (hipStream_t)stream;
-    const f16 *ep = (const f16*)eps2, *x = (const f16*)lat, *p = (const f16*)x0_prev, *sc = w.scal;
-    f16 *z = (f16*)x0_out, *o = (f16*)lat_out;
-    step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
-        hipLaunchKernelGGL((mimic_step_kernel<decltype(m)::value, decltype(ee)::value>), grid, block, 0, s, ep, x, p, z, o, kd, kp, sc, M, n);
-    });
-    return vdx_launch_status(what);
+    const co_buf extra[] = {{ws, mimic_layout((void*)ws, C, w)}}, read[] = {{eps2, 2 * nb}, {lat, nb}, {x0_prev, nb}};
+    for (const co_buf& in : read)
+        VDX_CHECK(!in.p || !co_overlap(ws, extra[0].bytes, in.p, in.bytes), "%s: the workspace overlaps another buffer", what);
+    return direct_launch(what, mode, false, eps2, lat, x0_prev, x0_out, lat_out, extra, kd, kp, mimic_guidance{w.scal}, (unsigned)C, M, 1024,
+                         stream);
 }
 
 extern "C" int vdx_cfg_mimic_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, const void* ws, float guidance,
@@ -407,50 +343,6 @@ extern "C" int vdx_cfg_mimic_dpm_step_f16(const void* eps2, const void* lat, con
 }
 
 // ---- co-denoising: the sample is the whole clip, its noise fused from the windows' outputs ------------------------------------
-// grid (rows, C): block x of channel y takes the (y, t) lines t = x, x + rows, ...; a lane the elements p = (lane + 256 j) E of
-// each.  rows = min(T, 64) for the sums: the partial of a block depends on the shapes and the table alone.
-template <int E>
-__global__ __launch_bounds__(256) void cofuse_mimic_sums_kernel(const f16* win, cofuse_tab tab, int K, const float* wn, float gs, float ms,
-                                                                mimic_ws w, int C, int T, int HW) {
-    const unsigned ch = blockIdx.y;
-    mimic_zero(w, ch, blockIdx.x, gridDim.x);
-    double a[2] = {0.0, 0.0};
-    for (int t = (int)blockIdx.x; t < T; t += (int)gridDim.x) {
-        for (int p = (int)threadIdx.x * E; p < HW; p += 256 * E) {
-            float uf[E], cf[E];
-            cofuse_uc<E>(win, tab, K, wn, C, T, HW, (int)ch, t, p, uf, cf);
-#pragma unroll
-            for (int j = 0; j < E; ++j) sum_acc(a, uf[j], cf[j], gs, ms);
-        }
-    }
-    block_row2(a, w.partials + ((size_t)ch * MIMIC_MAX_ROWS + blockIdx.x) * 2);
-}
-
-template <int E>
-__global__ __launch_bounds__(256) void cofuse_mimic_hist_kernel(const f16* win, cofuse_tab tab, int K, const float* wn, float gs, float ms,
-                                                                mimic_ws w, int nrows, int C, int T, int HW) {
-    const unsigned ch = blockIdx.y;
-    float mg, ml;
-    channel_means(w.partials + (size_t)ch * MIMIC_MAX_ROWS * 2, nrows, (double)((size_t)T * HW), mg, ml);
-    uint32_t* h = w.hist + (size_t)ch * MIMIC_BINS;
-    uint32_t mx = 0;
-    for (int t = (int)blockIdx.x; t < T; t += (int)gridDim.x) {
-        for (int p = (int)threadIdx.x * E; p < HW; p += 256 * E) {
-            float uf[E], cf[E];
-            cofuse_uc<E>(win, tab, K, wn, C, T, HW, (int)ch, t, p, uf, cf);
-            uint32_t db[E], eb[E];
-#pragma unroll
-            for (int j = 0; j < E; ++j) mimic_bins(uf[j], cf[j], gs, ms, mg, ml, db[j], eb[j]);
-            hist_add<E>(h, db, eb, mx);
-        }
-    }
-    max_fold(w.maxbits + ch, mx);
-}
-
-static inline int cofuse_mimic_rows(int T) { return T < MIMIC_MAX_ROWS ? T : MIMIC_MAX_ROWS; }
-
-extern "C" size_t vdx_cofuse_cfg_mimic_ws_bytes(int C, int T, int HW) { return vdx_cfg_mimic_ws_bytes(C, T, HW); }
-
 extern "C" int vdx_cofuse_cfg_mimic_stats_f16(const void* windows, size_t windows_elems, const int64_t* win_off, const int* win_start,
                                               const int* win_len, int K, const float* wn, float guidance, float mimic, size_t k, float f,
                                               void* ws, int stages, int C, int T, int HW, vdx_stream_t stream) {
@@ -460,34 +352,10 @@ extern "C" int vdx_cofuse_cfg_mimic_stats_f16(const void* windows, size_t window
     if (int rc = cofuse_check(what, 0, false, nullptr, windows, windows_elems, win_off, win_start, win_len, K, wn, nullptr, nullptr,
                               nullptr, C, T, HW, tab, e))
         return rc;
-    VDX_CHECK(mimic_shape_ok(C, T, HW), "%s: bad shape C=%d T=%d HW=%d (a channel holds fewer than 2^32 elements)", what, C, T, HW);
-    VDX_CHECK(stages >= 1 && stages <= 7, "%s: stages %d is not a set of launches 1 | 2 | 4", what, stages);
-    const size_t M = (size_t)T * HW;
-    if (int rc = mimic_check_rank(what, mimic, k, f, M)) return rc;
-    VDX_CHECK(ws && ((uintptr_t)ws & 15) == 0, "%s: the workspace must be a 16-byte aligned pointer", what);
-    mimic_ws w;
-    const size_t wb = mimic_layout(ws, C, w);
-    VDX_CHECK(!co_overlap(ws, wb, windows, windows_elems * sizeof(f16)) && !co_overlap(ws, wb, wn, (size_t)K * T * sizeof(float)),
-              "%s: the workspace overlaps an input", what);
-    const int rows = cofuse_mimic_rows(T);
-    const dim3 block(256), sgrid((unsigned)rows, (unsigned)C), hgrid((unsigned)(T < 1024 ? T : 1024), (unsigned)C);
-    const hipStream_t st = (hipStream_t)stream;
-    const f16* ww = (const f16*)windows;
-    if (stages & 1) {
-        if (e == 8) hipLaunchKernelGGL(cofuse_mimic_sums_kernel<8>, sgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, C, T, HW);
-        else if (e == 4) hipLaunchKernelGGL(cofuse_mimic_sums_kernel<4>, sgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, C, T, HW);
-        else hipLaunchKernelGGL(cofuse_mimic_sums_kernel<1>, sgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, C, T, HW);
-    }
-    if (stages & 2) {
-        if (e == 8) hipLaunchKernelGGL(cofuse_mimic_hist_kernel<8>, hgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, rows, C, T, HW);
-        else if (e == 4) hipLaunchKernelGGL(cofuse_mimic_hist_kernel<4>, hgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, rows, C, T, HW);
-        else hipLaunchKernelGGL(cofuse_mimic_hist_kernel<1>, hgrid, block, 0, st, ww, tab, K, wn, guidance, mimic, w, rows, C, T, HW);
-    }
-    if (stages & 4) {
-        const size_t k2 = k + 1 < M ? k + 1 : M - 1;
-        hipLaunchKernelGGL(mimic_select_kernel, dim3((unsigned)C), block, 0, st, w, rows, (double)M, (uint32_t)k, (uint32_t)k2, f);
-    }
-    return vdx_launch_status(what);
+    const co_buf inputs[] = {{windows, windows_elems * sizeof(f16)}, {wn, (size_t)K * T * sizeof(float)}};
+    const auto src = [&](auto ee) { return cofuse_source<decltype(ee)::value>{(const f16*)windows, tab, K, wn, C, T, HW, (unsigned)T}; };
+    return mimic_stats_launch(what, e, src, inputs, guidance, mimic, k, f, ws, stages, T < MIMIC_MAX_ROWS ? T : MIMIC_MAX_ROWS, (size_t)T, C,
+                              T, HW, stream);
 }
 
 static int cofuse_mimic_launch(const char* what, int mode, const void* z, const void* windows, size_t windows_elems,
@@ -509,10 +377,8 @@ static int cofuse_mimic_launch(const char* what, int mode, const void* z, const 
     VDX_CHECK(!co_overlap(ws, wb, z, nb) && !co_overlap(ws, wb, windows, windows_elems * sizeof(f16)) &&
                   !co_overlap(ws, wb, wn, (size_t)K * T * sizeof(float)) && (!x0_prev || !co_overlap(ws, wb, x0_prev, nb)),
               "%s: the workspace overlaps an input", what);
-    const size_t per_tile = 256 * (size_t)e;                      // `cofuse_launch`'s block map: the policy finds its channel by it
-    const unsigned tiles_per_line = (unsigned)(((size_t)HW + per_tile - 1) / per_tile);
-    return cofuse_launch<false>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp,
-                                mimic_guidance{w.scal, tiles_per_line, (unsigned)T}, C, T, HW, stream);
+    return cofuse_launch<false>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp, mimic_guidance{w.scal}, C, T, HW,
+                                stream);
 }
 
 extern "C" int vdx_cofuse_cfg_mimic_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,

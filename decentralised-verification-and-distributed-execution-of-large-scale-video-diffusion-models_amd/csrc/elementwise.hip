@@ -1,13 +1,13 @@
 // elementwise.hip — layout edges of the UNet (conv_in / output permute), SiLU, and the
-// orchestration ops the reference owns: ctx injection (fsdp_chunked_coherent.py:133-137),
-// CFG combine + DDIM step (:141-142), linear-ramp blend (:204-217).
+// orchestration ops the reference owns: ctx injection (fsdp_chunked_coherent.py:133-137) and the
+// linear-ramp blend (:204-217); the CFG combine + DDIM step (:141-142) is dpm.hip's.
 // The orchestration kernels round to fp16 after every tensor op, in the order torch evaluates
 // the reference's expressions ON A GPU (the reference's tensors live on `cuda`): a 0-d fp32
 // coefficient stays fp32 on either side of `*`, and `/ cpu_scalar` is `* (1/scalar)`.  ctx
 // injection and blend are bit-exact against the CPU oracle; for the DDIM step torch-CPU differs
 // from torch-GPU in exactly those two rules (oracle/ddim_ref.py `step_gpu_rules` restates them).
 #include "vdx_common.h"
-#include "step_chains.h"   // rn16 and the CFG + DDIM chain, shared with codenoise.hip
+#include "step_chains.h"   // rn16
 
 // ---- conv_in gather: (B,Cin,F,H,W) latent -> im2col rows [B*F*H*W][Kpad], K = (ky*3+kx)*Cin + ci
 // (zero padded to Kpad, a multiple of 64) so conv_in runs on the MFMA GEMM like every other conv.
@@ -144,52 +144,6 @@ extern "C" int vdx_cfg_input_f16(const void* lat, const void* ctx, float weight,
     hipLaunchKernelGGL(cfg_input_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)lat,
                        (const f16*)ctx, weight, (f16*)x2, C, F, HW);
     return vdx_launch_status("vdx_cfg_input_f16");
-}
-
-// ---- fsdp_chunked_coherent.py:141-142 -------------------------------------------------------
-//   u, c = noise.chunk(2);  lat = sched.step(u + gs*(c-u), t, lat).prev_sample     (DDIM, eta 0)
-// DDIMScheduler.step with fp32 0-d coefficients and fp16 tensors: every tensor op rounds to fp16.
-__global__ void cfg_ddim_kernel(const f16* eps2, const f16* lat, f16* out, float gs, float s1, float sa,
-                                float sp, float s1p, size_t n) {
-    const ddim_coef k = {gs, s1, sa, sp, s1p};
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        out[i] = cfg_ddim_elem((float)eps2[i], (float)eps2[n + i], (float)lat[i], k);   // step_chains.h
-    }
-}
-extern "C" int vdx_cfg_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, float guidance,
-                                     float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
-                                     float sqrt_one_minus_aprev, size_t n, vdx_stream_t stream) {
-    VDX_CHECK(eps2 && lat && lat_out && n > 0, "cfg_ddim_step: bad arguments");
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(cfg_ddim_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)eps2,
-                       (const f16*)lat, (f16*)lat_out, guidance, sqrt_one_minus_at, 1.0f / sqrt_at, sqrt_aprev,
-                       sqrt_one_minus_aprev, n);
-    return vdx_launch_status("vdx_cfg_ddim_step_f16");
-}
-
-// DDIMScheduler.step alone (the reference's `sched.step(eps, t, lat).prev_sample`, :142), same
-// rounding chain; used when the CFG combine was done by the caller (unchanged reference script).
-__global__ void ddim_kernel(const f16* eps, const f16* lat, f16* out, float s1, float sa, float sp, float s1p,
-                            size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float g = (float)eps[i], x = (float)lat[i];
-        const f16 a1 = rn16(__fmul_rn(s1, g));
-        const f16 a2 = rn16(__fsub_rn(x, (float)a1));
-        const f16 x0 = rn16(__fmul_rn((float)a2, sa));
-        const f16 d = rn16(__fmul_rn(s1p, g));
-        const f16 b1 = rn16(__fmul_rn(sp, (float)x0));
-        out[i] = rn16(__fadd_rn((float)b1, (float)d));
-    }
-}
-extern "C" int vdx_ddim_step_f16(const void* eps, const void* lat, void* lat_out, float sqrt_one_minus_at,
-                                 float sqrt_at, float sqrt_aprev, float sqrt_one_minus_aprev, size_t n,
-                                 vdx_stream_t stream) {
-    VDX_CHECK(eps && lat && lat_out && n > 0, "ddim_step: bad arguments");
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(ddim_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)eps,
-                       (const f16*)lat, (f16*)lat_out, sqrt_one_minus_at, 1.0f / sqrt_at, sqrt_aprev,
-                       sqrt_one_minus_aprev, n);
-    return vdx_launch_status("vdx_ddim_step_f16");
 }
 
 // ---- fsdp_chunked_coherent.py:204-217 -------------------------------------------------------

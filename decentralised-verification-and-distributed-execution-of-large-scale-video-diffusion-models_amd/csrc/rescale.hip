@@ -49,22 +49,9 @@ __device__ __forceinline__ void stat_acc(double (&a)[4], float u, float c, float
     a[3] += (double)__fmul_rn(g, g);
 }
 
-// the block's 256 lanes' sums -> row[4]: a shuffle tree inside each wave, then the four waves in ascending order
-__device__ __forceinline__ void block_row(double (&a)[4], double* row) {
-    __shared__ double w[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) a[q] += __shfl_down(a[q], off, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[threadIdx.x >> 6][q] = a[q];
-    __syncthreads();
-    if (threadIdx.x < 4) row[threadIdx.x] = ((w[0][threadIdx.x] + w[1][threadIdx.x]) + w[2][threadIdx.x]) + w[3][threadIdx.x];
-}
-
 // every block of a step kernel: the rows through LDS, added in ascending order (lane q adds column q), then sd_c, sd_g and r.
-// Called by all 256 lanes before any of them leaves.
+// Called by all 256 lanes before any of them leaves.  Block 0 of a grid whose y is 1 (the rescaled steps have ONE channel, the sample)
+// also leaves the three scalars in `stats_out`.
 __device__ __forceinline__ float rescale_ratio(const rescale_args& ra) {
     __shared__ double rowbuf[RESCALE_MAX_ROWS][4];
     __shared__ double s[4];
@@ -87,7 +74,7 @@ __device__ __forceinline__ float rescale_ratio(const rescale_args& ra) {
         const f16 sd_g = (f16)sqrt((ra.n * s[3] - s[2] * s[2]) / den);
         const f16 r = rn16(__fdiv_rn((float)sd_c, (float)sd_g));
         ratio = (float)r;
-        if (ra.stats_out && blockIdx.x == 0) {
+        if (ra.stats_out && blockIdx.x == 0 && blockIdx.y == 0) {
             ra.stats_out[0] = sd_c;
             ra.stats_out[1] = sd_g;
             ra.stats_out[2] = r;
@@ -97,68 +84,49 @@ __device__ __forceinline__ float rescale_ratio(const rescale_args& ra) {
     return ratio;
 }
 
-// g -> g' -> the sampler's tail.  MODE 0: DDIM; 1: DPM-Solver++ first order; 2: second order
-template <int MODE>
-__device__ __forceinline__ void rescale_step_elem(float u, float c, float x, float x0p, float r, const rescale_args& ra,
-                                                  const ddim_coef& kd, const dpm_coef& kp, f16& x0_out, f16& out) {
-    const f16 g = cfg_combine(u, c, MODE == 0 ? kd.gs : kp.gs);
-    const f16 g2 = cfg_rescale_elem(g, r, ra.phi, ra.phi1);
-    if (MODE == 0) out = ddim_tail(g2, x, kd);
-    else dpm_tail<MODE == 2>(g2, x, x0p, kp, x0_out, out);
-}
-
-// the guidance policy of the co-fused step (cofuse_common.h `cofuse_step_kernel`): the block's r, then g' in g's place
+// the guidance policy of every rescaled step (step_common.h `direct_step_kernel`, cofuse_common.h `cofuse_step_kernel`): the block's
+// r is its state, then g -> g' -> the sampler's tail
 struct rescale_guidance {
     rescale_args ra;
-    __device__ __forceinline__ float prologue() const { return rescale_ratio(ra); }
+    typedef float state;
+    static constexpr bool uses_c = true;
+    __device__ __forceinline__ state prologue(int) const { return rescale_ratio(ra); }
     template <int MODE>
-    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, float r, const ddim_coef& kd, const dpm_coef& kp, f16& x0,
-                                         f16& o) const {
-        rescale_step_elem<MODE>(u, c, x, x0p, r, ra, kd, kp, x0, o);
+    __device__ __forceinline__ void elem(float u, float c, float x, float x0p, const state& r, const ddim_coef& kd, const dpm_coef& kp,
+                                         f16& x0, f16& o) const {
+        const f16 g = cfg_combine(u, c, MODE == 0 ? kd.gs : kp.gs);
+        const f16 g2 = cfg_rescale_elem(g, r, ra.phi, ra.phi1);
+        if (MODE == 0) o = ddim_tail(g2, x, kd);
+        else dpm_tail<MODE == 2>(g2, x, x0p, kp, x0, o);
     }
 };
 
-// ---- one sample in one buffer: eps2 = [u; c], n elements each, E halves per access (n is a multiple of E) ---------------------
-template <int E>
-__global__ __launch_bounds__(256) void rescale_stats_kernel(const f16* eps, float gs, double* partials, size_t n) {
+// ---- the statistics pass, over either noise source ---------------------------------------------------------------------------------
+// The sample is ONE channel of the source: block b adds what the source hands it, in the source's order, into row b.  One buffer
+// (`direct_source`): rows = the blocks of n / E vectors, at most 256.  Co-fused (`cofuse_source`, the clip as C T lines): rows =
+// min(C T, 256).  Either way a block's partial depends on the shapes (and the table) alone.
+template <class Src>
+__global__ __launch_bounds__(256) void rescale_stats_kernel(Src src, float gs, double* partials) {
     double a[4] = {0.0, 0.0, 0.0, 0.0};
-    const size_t nv = n / E, stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride) {
-        f16 u[E], c[E];
-        load_halves<E>(eps + v * E, u);
-        load_halves<E>(eps + n + v * E, c);
+    src.each(0, blockIdx.x, gridDim.x, [&](size_t, const f16 (&uf)[Src::width], const f16 (&cf)[Src::width]) {
 #pragma unroll
-        for (int j = 0; j < E; ++j) stat_acc(a, (float)u[j], (float)c[j], gs);
-    }
+        for (int j = 0; j < Src::width; ++j) stat_acc(a, (float)uf[j], (float)cf[j], gs);
+    });
     block_row(a, partials + (size_t)blockIdx.x * 4);
 }
 
-template <int MODE, int E>
-__global__ __launch_bounds__(256) void rescale_step_kernel(const f16* eps, const f16* lat, const f16* x0_prev, f16* x0_out, f16* out,
-                                                           ddim_coef kd, dpm_coef kp, rescale_args ra, size_t n) {
-    const float r = rescale_ratio(ra);
-    const size_t nv = n / E, stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += stride) {
-        const size_t i = v * E;
-        f16 u[E], c[E], x[E], xp[E], o[E], x0[E];
-        load_halves<E>(eps + i, u);
-        load_halves<E>(eps + n + i, c);
-        load_halves<E>(lat + i, x);
-        if (MODE == 2) load_halves<E>(x0_prev + i, xp);
-#pragma unroll
-        for (int j = 0; j < E; ++j)
-            rescale_step_elem<MODE>((float)u[j], (float)c[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, r, ra, kd, kp, x0[j], o[j]);
-        if (MODE != 0) store_halves<E>(x0_out + i, x0);
-        store_halves<E>(out + i, o);
-    }
-}
-
-static inline int rescale_width(size_t n) { return n % 8 == 0 ? 8 : n % 4 == 0 ? 4 : 1; }
-
-// rows of `partials` = blocks of the statistics launch: a function of n alone
-static inline int rescale_rows(size_t n) {
-    const size_t nv = n / rescale_width(n), want = (nv + 255) / 256;
-    return (int)(want < RESCALE_MAX_ROWS ? want : RESCALE_MAX_ROWS);
+// the launch of both statistics entries, whose own checks have passed: `src(E)` makes the noise source of access width E
+template <class MakeSrc, size_t N>
+static int rescale_stats_launch(const char* what, int e, int rows, MakeSrc&& src, float guidance, double* partials,
+                                const co_buf (&inputs)[N], vdx_stream_t stream) {
+    VDX_CHECK(partials && ((uintptr_t)partials & 15) == 0, "%s: partials must be a 16-byte aligned pointer", what);
+    for (const co_buf& in : inputs)
+        VDX_CHECK(!co_overlap(partials, (size_t)rows * 4 * sizeof(double), in.p, in.bytes), "%s: partials overlap an input", what);
+    width_dispatch(e, [&](auto ee) {
+        auto s = src(ee);
+        hipLaunchKernelGGL(rescale_stats_kernel<decltype(s)>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, s, guidance, partials);
+    });
+    return vdx_launch_status(what);
 }
 
 static inline int rescale_check_phi(const char* what, float phi, float phi1) {
@@ -167,64 +135,48 @@ static inline int rescale_check_phi(const char* what, float phi, float phi1) {
     return 0;
 }
 
+// stats_out is written (by one block): it may touch none of `bufs` (a null one is skipped)
+template <size_t N>
+static inline int rescale_stats_out_free(const char* what, const void* stats_out, const co_buf (&bufs)[N]) {
+    if (stats_out)
+        for (const co_buf& b : bufs)
+            VDX_CHECK(!b.p || !co_overlap(stats_out, 3 * sizeof(f16), b.p, b.bytes), "%s: stats_out overlaps another buffer", what);
+    return 0;
+}
+
+// ---- one sample in one buffer: eps2 = [u; c], n elements each, E halves per access (n is a multiple of E) ---------------------
+static inline int rescale_width(size_t n) { return n % 8 == 0 ? 8 : n % 4 == 0 ? 4 : 1; }
+
+// rows of `partials` = blocks of the statistics launch: a function of n alone
+static inline int rescale_rows(size_t n) {
+    const size_t nv = n / rescale_width(n), want = (nv + 255) / 256;
+    return (int)(want < RESCALE_MAX_ROWS ? want : RESCALE_MAX_ROWS);
+}
+
 extern "C" int vdx_cfg_rescale_rows(size_t n) { return n > 0 && n <= ((size_t)1 << 40) ? rescale_rows(n) : 0; }
 
 extern "C" int vdx_cfg_rescale_stats_f16(const void* eps2, size_t n, float guidance, double* partials, vdx_stream_t stream) {
     const char* what = "vdx_cfg_rescale_stats_f16";
-    VDX_CHECK(eps2 && partials && n > 0, "%s: bad arguments", what);
+    VDX_CHECK(eps2 && n > 0, "%s: bad arguments", what);
     VDX_CHECK(n <= ((size_t)1 << 40), "%s: n too large", what);
-    VDX_CHECK(((uintptr_t)eps2 & 15) == 0 && ((uintptr_t)partials & 15) == 0, "%s: pointer not 16-byte aligned", what);
-    const int rows = rescale_rows(n);
-    VDX_CHECK(!co_overlap(partials, (size_t)rows * 4 * sizeof(double), eps2, 2 * n * sizeof(f16)), "%s: partials overlap eps2", what);
-    const dim3 grid((unsigned)rows), block(256);
-    const hipStream_t s = (hipStream_t)stream;
-    const f16* e = (const f16*)eps2;
-    switch (rescale_width(n)) {
-    case 8: hipLaunchKernelGGL(rescale_stats_kernel<8>, grid, block, 0, s, e, guidance, partials, n); break;
-    case 4: hipLaunchKernelGGL(rescale_stats_kernel<4>, grid, block, 0, s, e, guidance, partials, n); break;
-    default: hipLaunchKernelGGL(rescale_stats_kernel<1>, grid, block, 0, s, e, guidance, partials, n); break;
-    }
-    return vdx_launch_status(what);
+    VDX_CHECK(((uintptr_t)eps2 & 15) == 0, "%s: pointer not 16-byte aligned", what);
+    const co_buf inputs[] = {{eps2, 2 * n * sizeof(f16)}};
+    const auto src = [&](auto ee) { return direct_source<decltype(ee)::value>{(const f16*)eps2, n, n}; };
+    return rescale_stats_launch(what, rescale_width(n), rescale_rows(n), src, guidance, partials, inputs, stream);
 }
 
 static int rescale_step_launch(const char* what, int mode, const void* eps2, const void* lat, const void* x0_prev, void* x0_out,
                                void* lat_out, const double* partials, void* stats_out, float phi, float phi1, ddim_coef kd,
                                dpm_coef kp, size_t n, vdx_stream_t stream) {
-    VDX_CHECK(eps2 && lat && lat_out && partials && n > 0 && (mode == 0 || x0_out), "%s: bad arguments", what);
+    VDX_CHECK(partials && n > 0, "%s: bad arguments", what);
     VDX_CHECK(n <= ((size_t)1 << 40), "%s: n too large", what);
     if (int rc = rescale_check_phi(what, phi, phi1)) return rc;
-    const size_t nb = n * sizeof(f16);
-    for (const void* p : {eps2, lat, x0_prev, (const void*)x0_out, (const void*)lat_out, (const void*)partials, (const void*)stats_out})
-        VDX_CHECK(((uintptr_t)p & 15) == 0, "%s: pointer not 16-byte aligned", what);
     const int rows = rescale_rows(n);
-    const size_t pb = (size_t)rows * 4 * sizeof(double), sb = 3 * sizeof(f16);
-    // a lane reads its elements before it writes them, and writes nobody else's: lat_out == lat is fine, nothing else may share
-    VDX_CHECK(lat_out == lat || !co_overlap(lat_out, nb, lat, nb), "%s: lat_out overlaps lat without being lat", what);
-    VDX_CHECK(!co_overlap(lat_out, nb, eps2, 2 * nb) && !co_overlap(lat_out, nb, partials, pb), "%s: lat_out overlaps an input", what);
-    if (stats_out)
-        VDX_CHECK(!co_overlap(stats_out, sb, eps2, 2 * nb) && !co_overlap(stats_out, sb, lat, nb) && !co_overlap(stats_out, sb, lat_out, nb) &&
-                      !co_overlap(stats_out, sb, partials, pb) && (!x0_prev || !co_overlap(stats_out, sb, x0_prev, nb)) &&
-                      (!x0_out || !co_overlap(stats_out, sb, x0_out, nb)),
-                  "%s: stats_out overlaps another buffer", what);
-    if (mode != 0) {
-        VDX_CHECK(!x0_prev || x0_out != x0_prev, "%s: x0_out must not be x0_prev (ping-pong two history buffers)", what);
-        VDX_CHECK(!co_overlap(x0_out, nb, lat_out, nb) && !co_overlap(x0_out, nb, lat, nb) && !co_overlap(x0_out, nb, eps2, 2 * nb) &&
-                      !co_overlap(x0_out, nb, partials, pb),
-                  "%s: x0_out overlaps an input or lat_out", what);
-        VDX_CHECK(!x0_prev || (!co_overlap(x0_prev, nb, x0_out, nb) && !co_overlap(x0_prev, nb, lat_out, nb)),
-                  "%s: x0_prev overlaps an output", what);
-    }
-    const int e = rescale_width(n);
-    const size_t nv = n / e, want = (nv + 255) / 256;
-    const dim3 grid((unsigned)(want < 4096 ? want : 4096)), block(256);
-    const hipStream_t s = (hipStream_t)stream;
+    const size_t nb = n * sizeof(f16), pb = (size_t)rows * 4 * sizeof(double);
+    const co_buf extra[] = {{partials, pb}, {stats_out, 3 * sizeof(f16)}}, read[] = {{eps2, 2 * nb}, {lat, nb}, {partials, pb}, {x0_prev, nb}};
+    if (int rc = rescale_stats_out_free(what, stats_out, read)) return rc;
     const rescale_args ra = {partials, (f16*)stats_out, rows, (double)n, phi, phi1};
-    const f16 *ep = (const f16*)eps2, *x = (const f16*)lat, *p = (const f16*)x0_prev;
-    f16 *z = (f16*)x0_out, *o = (f16*)lat_out;
-    step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
-        hipLaunchKernelGGL((rescale_step_kernel<decltype(m)::value, decltype(ee)::value>), grid, block, 0, s, ep, x, p, z, o, kd, kp, ra, n);
-    });
-    return vdx_launch_status(what);
+    return direct_launch(what, mode, false, eps2, lat, x0_prev, x0_out, lat_out, extra, kd, kp, rescale_guidance{ra}, 1, n, 4096, stream);
 }
 
 extern "C" int vdx_cfg_rescale_ddim_step_f16(const void* eps2, const void* lat, void* lat_out, const double* partials, void* stats_out,
@@ -245,25 +197,6 @@ extern "C" int vdx_cfg_rescale_dpm_step_f16(const void* eps2, const void* lat, c
 }
 
 // ---- co-denoising: the sample is the whole clip, its noise fused from the windows' outputs ------------------------------------
-// Statistics: block b takes the (c, t) lines b, b + rows, ...; a lane the elements p = (lane + 256 j) E of each.  rows = min(C T,
-// 256): the partial of a block depends on the shapes and the table alone.
-template <int E>
-__global__ __launch_bounds__(256) void cofuse_stats_kernel(const f16* win, cofuse_tab tab, int K, const float* wn, float gs,
-                                                           double* partials, int C, int T, int HW) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    const unsigned lines = (unsigned)C * (unsigned)T;
-    for (unsigned line = blockIdx.x; line < lines; line += gridDim.x) {
-        const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
-        for (int p = (int)threadIdx.x * E; p < HW; p += 256 * E) {
-            float uf[E], cf[E];
-            cofuse_uc<E>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);
-#pragma unroll
-            for (int j = 0; j < E; ++j) stat_acc(a, uf[j], cf[j], gs);
-        }
-    }
-    block_row(a, partials + (size_t)blockIdx.x * 4);
-}
-
 static inline int cofuse_rescale_rows(int C, int T) {
     const size_t lines = (size_t)C * T;
     return (int)(lines < RESCALE_MAX_ROWS ? lines : RESCALE_MAX_ROWS);
@@ -282,18 +215,11 @@ extern "C" int vdx_cofuse_cfg_rescale_stats_f16(const void* windows, size_t wind
     if (int rc = cofuse_check(what, 0, false, nullptr, windows, windows_elems, win_off, win_start, win_len, K, wn, nullptr, nullptr,
                               nullptr, C, T, HW, tab, e))
         return rc;
-    VDX_CHECK(partials && ((uintptr_t)partials & 15) == 0, "%s: partials must be a 16-byte aligned pointer", what);
-    const int rows = cofuse_rescale_rows(C, T);
-    const size_t pb = (size_t)rows * 4 * sizeof(double);
-    VDX_CHECK(!co_overlap(partials, pb, windows, windows_elems * sizeof(f16)) && !co_overlap(partials, pb, wn, (size_t)K * T * sizeof(float)),
-              "%s: partials overlap an input", what);
-    const dim3 grid((unsigned)rows), block(256);
-    const hipStream_t st = (hipStream_t)stream;
-    const f16* ww = (const f16*)windows;
-    if (e == 8) hipLaunchKernelGGL(cofuse_stats_kernel<8>, grid, block, 0, st, ww, tab, K, wn, guidance, partials, C, T, HW);
-    else if (e == 4) hipLaunchKernelGGL(cofuse_stats_kernel<4>, grid, block, 0, st, ww, tab, K, wn, guidance, partials, C, T, HW);
-    else hipLaunchKernelGGL(cofuse_stats_kernel<1>, grid, block, 0, st, ww, tab, K, wn, guidance, partials, C, T, HW);
-    return vdx_launch_status(what);
+    const co_buf inputs[] = {{windows, windows_elems * sizeof(f16)}, {wn, (size_t)K * T * sizeof(float)}};
+    const auto src = [&](auto ee) {
+        return cofuse_source<decltype(ee)::value>{(const f16*)windows, tab, K, wn, C, T, HW, (unsigned)C * (unsigned)T};
+    };
+    return rescale_stats_launch(what, e, cofuse_rescale_rows(C, T), src, guidance, partials, inputs, stream);
 }
 
 static int cofuse_rescale_launch(const char* what, int mode, const void* z, const void* windows, size_t windows_elems,
@@ -309,15 +235,12 @@ static int cofuse_rescale_launch(const char* what, int mode, const void* z, cons
     VDX_CHECK(partials && ((uintptr_t)partials & 15) == 0 && ((uintptr_t)stats_out & 15) == 0,
               "%s: partials must be a 16-byte aligned pointer, stats_out one or null", what);
     const int rows = cofuse_rescale_rows(C, T);
-    const size_t nb = (size_t)C * T * HW * sizeof(f16), pb = (size_t)rows * 4 * sizeof(double), sb = 3 * sizeof(f16);
-    const size_t wb = windows_elems * sizeof(f16);
+    const size_t nb = (size_t)C * T * HW * sizeof(f16), pb = (size_t)rows * 4 * sizeof(double);
     VDX_CHECK(!co_overlap(partials, pb, lat_out, nb) && (!x0_out || !co_overlap(partials, pb, x0_out, nb)),
               "%s: partials overlap an output", what);
-    if (stats_out)
-        VDX_CHECK(!co_overlap(stats_out, sb, z, nb) && !co_overlap(stats_out, sb, lat_out, nb) && !co_overlap(stats_out, sb, windows, wb) &&
-                      !co_overlap(stats_out, sb, wn, (size_t)K * T * sizeof(float)) && !co_overlap(stats_out, sb, partials, pb) &&
-                      (!x0_prev || !co_overlap(stats_out, sb, x0_prev, nb)) && (!x0_out || !co_overlap(stats_out, sb, x0_out, nb)),
-                  "%s: stats_out overlaps another buffer", what);
+    const co_buf all[] = {{z, nb}, {lat_out, nb}, {windows, windows_elems * sizeof(f16)}, {wn, (size_t)K * T * sizeof(float)},
+                          {partials, pb}, {x0_prev, nb}, {x0_out, nb}};
+    if (int rc = rescale_stats_out_free(what, stats_out, all)) return rc;
     const rescale_args ra = {partials, (f16*)stats_out, rows, (double)((size_t)C * T * HW), phi, phi1};
     return cofuse_launch<false>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp, rescale_guidance{ra}, C, T, HW,
                                 stream);

@@ -1,7 +1,6 @@
-// step_chains.h — the per-element rounding chains of the fused CFG + sampler steps, written once: elementwise.hip
-// (`vdx_cfg_ddim_step_f16`), dpm.hip (`vdx_cfg_dpm_step_f16`, `vdx_dpm_step_f16`) and codenoise.hip (the co-denoising steps,
-// which feed the same chains a fused noise) and rescale.hip (the CFG-rescale steps: the same combine, `cfg_rescale_elem`,
-// the same tails) all call these, so they cannot drift apart; likewise `add_noise`'s chain for
+// step_chains.h — the per-element rounding chains of the fused CFG + sampler steps, written once: the guidance policies of
+// step_common.h (the plain steps of dpm.hip and codenoise.hip), rescale.hip (`cfg_rescale_elem` between the combine and the tails)
+// and dynthresh.hip (`cfg_mimic_elem` likewise) all call these, so they cannot drift apart; likewise `add_noise`'s chain for
 // vid2vid.hip and inpaint.hip (the masked step re-noises the kept cells with exactly video-to-video's start).  Every function is
 // __forceinline__: a kernel that calls one compiles to the instructions it had when the chain was written in its loop.
 #pragma once

@@ -804,33 +804,8 @@ def is_cfg_duplicate(x) -> bool:
         return False
 
 
-def cfg_ddim_step(eps2, lat, guidance, coeffs, out=None):
-    """fsdp_chunked_coherent.py:141-142.  coeffs = (sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev))."""
-    if eps2.shape[0] != 2 or tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1:
-        raise VdxError("cfg_ddim_step: eps2 must be (2,...) matching lat (1,...)")
-    if not (eps2.is_contiguous() and lat.is_contiguous()):
-        raise VdxError("cfg_ddim_step: tensors must be contiguous")
-    if out is None:
-        out = torch.empty_like(lat)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cfg_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), float(guidance), s1, sa, sp, s1p,
-            lat.numel())
-    return out
-
-
-def ddim_step(eps, lat, coeffs, out=None):
-    """`scheduler.step(eps, t, lat).prev_sample` (fsdp_chunked_coherent.py:142) without the CFG combine."""
-    if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
-        raise VdxError("ddim_step: eps and lat must be contiguous and of equal shape")
-    if out is None:
-        out = torch.empty_like(lat)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_ddim_step_f16", _p(eps, "eps"), _p(lat, "lat"), _p(out, "out"), s1, sa, sp, s1p, lat.numel())
-    return out
-
-
 def _dpm_args(what, lat, x0_prev, x0_out, out, coeffs):
-    """Shared checks of the two DPM-Solver++ steps -> (x0_out, out, the six fp32 coefficients)."""
+    """Shared checks of the DPM-Solver++ steps -> (x0_out, out, the six fp32 coefficients)."""
     for name, t in (("x0_prev", x0_prev), ("x0_out", x0_out), ("out", out)):
         if t is not None and (tuple(t.shape) != tuple(lat.shape) or not t.is_contiguous()):
             raise VdxError(f"{what}: {name} must be contiguous and shaped like lat")
@@ -846,28 +821,65 @@ def _dpm_args(what, lat, x0_prev, x0_out, out, coeffs):
     return x0_out, out, c
 
 
+def _eps2_like(what, eps2, lat):
+    if eps2.dim() < 1 or eps2.shape[0] != 2 or (lat is not None and (tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1)):
+        raise VdxError(f"{what}: eps2 must be (2,...) matching lat (1,...)")
+    if not (eps2.is_contiguous() and (lat is None or lat.is_contiguous())):
+        raise VdxError(f"{what}: tensors must be contiguous")
+
+
+def _one_step(symbol, eps, lat, guidance, coeffs, history, out, rescaled=None, mimic=None):
+    """Every one-buffer sampler step (csrc/step_common.h `direct_launch`), launched as `symbol`(eps, lat, history, out, buffers,
+    scalars, coefficients, size) and named in errors as the wrapper, `symbol` without `vdx_` and `_f16`.  `guidance` None: the
+    sampler alone on an eps shaped like lat, else eps = [u; c].  `history` None: the DDIM form -> out; else (x0_prev, x0_out), the
+    DPM-Solver++ form through `_dpm_args` -> (out, x0).  `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out);
+    `mimic`: the thresholded variants' (workspace,).  One call below the public wrapper and no closure: launch-bound."""
+    what = symbol[4:-4]
+    if guidance is None:
+        if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
+            raise VdxError(f"{what}: eps and lat must be contiguous and of equal shape")
+    else:
+        (_eps2_like if mimic is None else _eps2_5d)(what, eps, lat)
+    if history is None:
+        if out is None:
+            out = torch.empty_like(lat)
+        hist = ()
+        s1, sa, sp, s1p = (float(c) for c in coeffs)
+        c = (s1, sa, sp, s1p)
+    else:
+        x0_out, out, c = _dpm_args(what, lat, history[0], history[1], out, coeffs)
+        hist = (_p(history[0], "x0_prev"), _p(x0_out, "x0_out"))
+    bufs, scal, size = (), () if guidance is None else (float(guidance),), (lat.numel(),)
+    if rescaled is not None:
+        _, pp, sp_ = _rescale_buffers(what, cfg_rescale_rows(lat.numel()), lat, rescaled[1], rescaled[2])
+        bufs, scal = (pp, sp_), scal + tuple(float(v) for v in rescaled[0])
+    elif mimic is not None:
+        _, wp, size = _mimic_ws(what, lat.shape, lat, mimic[0])
+        bufs = (wp,)
+    _launch(symbol, _p(eps, "eps" if guidance is None else "eps2"), _p(lat, "lat"), *hist, _p(out, "out"), *bufs, *scal, *c, *size)
+    return out if history is None else (out, x0_out)
+
+
+def cfg_ddim_step(eps2, lat, guidance, coeffs, out=None):
+    """fsdp_chunked_coherent.py:141-142.  coeffs = (sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev))."""
+    return _one_step("vdx_cfg_ddim_step_f16", eps2, lat, guidance, coeffs, None, out)
+
+
+def ddim_step(eps, lat, coeffs, out=None):
+    """`scheduler.step(eps, t, lat).prev_sample` (fsdp_chunked_coherent.py:142) without the CFG combine."""
+    return _one_step("vdx_ddim_step_f16", eps, lat, None, coeffs, None, out)
+
+
 def cfg_dpm_step(eps2, lat, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """`u + gs*(c-u)` + one DPM-Solver++ step (vdx/scheduler.py `DPMSolverMultistepScheduler.step_cfg`) in one kernel ->
     (lat', x0).  coeffs = (s0, 1/a0, st/s0, -at*(exp(-h)-1), half of that, 1/r0); `x0_prev=None`: the first-order form.
     `out` may be `lat`; `x0_out` may not be `x0_prev`."""
-    if eps2.shape[0] != 2 or tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1:
-        raise VdxError("cfg_dpm_step: eps2 must be (2,...) matching lat (1,...)")
-    if not (eps2.is_contiguous() and lat.is_contiguous()):
-        raise VdxError("cfg_dpm_step: tensors must be contiguous")
-    x0_out, out, c = _dpm_args("cfg_dpm_step", lat, x0_prev, x0_out, out, coeffs)
-    _launch("vdx_cfg_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
-            _p(out, "out"), float(guidance), *c, lat.numel())
-    return out, x0_out
+    return _one_step("vdx_cfg_dpm_step_f16", eps2, lat, guidance, coeffs, (x0_prev, x0_out), out)
 
 
 def dpm_step(eps, lat, coeffs, x0_prev=None, x0_out=None, out=None):
     """`scheduler.step(eps, t, lat)` of the DPM-Solver++ scheduler without the CFG combine -> (lat', x0)."""
-    if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
-        raise VdxError("dpm_step: eps and lat must be contiguous and of equal shape")
-    x0_out, out, c = _dpm_args("dpm_step", lat, x0_prev, x0_out, out, coeffs)
-    _launch("vdx_dpm_step_f16", _p(eps, "eps"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
-            _p(out, "out"), *c, lat.numel())
-    return out, x0_out
+    return _one_step("vdx_dpm_step_f16", eps, lat, None, coeffs, (x0_prev, x0_out), out)
 
 
 def blend_accumulate(full, weight, chunk, w, s, e):
@@ -1148,13 +1160,6 @@ def _rescale_buffers(what, rows: int, like, partials, stats_out):
     return partials, _p(partials, "partials", torch.float64), _p(stats_out, "stats_out")
 
 
-def _eps2_like(what, eps2, lat):
-    if eps2.dim() < 1 or eps2.shape[0] != 2 or (lat is not None and (tuple(eps2.shape[1:]) != tuple(lat.shape[1:]) or lat.shape[0] != 1)):
-        raise VdxError(f"{what}: eps2 must be (2,...) matching lat (1,...)")
-    if not (eps2.is_contiguous() and (lat is None or lat.is_contiguous())):
-        raise VdxError(f"{what}: tensors must be contiguous")
-
-
 def cfg_rescale_rows(n: int) -> int:
     """Rows the statistics pass writes for a sample of n elements (`vdx_cfg_rescale_rows`): a function of n alone, <= 256."""
     return int(_lib.load().vdx_cfg_rescale_rows(int(n)))
@@ -1179,26 +1184,13 @@ def cfg_rescale_stats(eps2, guidance, partials=None):
 def cfg_rescale_ddim_step(eps2, lat, guidance, rescale, coeffs, partials, out=None, stats_out=None):
     """`cfg_ddim_step` with the guided noise rescaled by `rescale` (`rescale_factors`' pair) from `cfg_rescale_stats`' rows of
     the same eps2 (`vdx_cfg_rescale_ddim_step_f16`).  `stats_out`: 3 halves that receive [sd_c, sd_g, r], or None."""
-    _eps2_like("cfg_rescale_ddim_step", eps2, lat)
-    if out is None:
-        out = torch.empty_like(lat)
-    _, pp, sp_ = _rescale_buffers("cfg_rescale_ddim_step", cfg_rescale_rows(lat.numel()), lat, partials, stats_out)
-    phi, phi1 = (float(v) for v in rescale)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cfg_rescale_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), pp, sp_, float(guidance), phi, phi1,
-            s1, sa, sp, s1p, lat.numel())
-    return out
+    return _one_step("vdx_cfg_rescale_ddim_step_f16", eps2, lat, guidance, coeffs, None, out, rescaled=(rescale, partials, stats_out))
 
 
 def cfg_rescale_dpm_step(eps2, lat, guidance, rescale, coeffs, partials, x0_prev=None, x0_out=None, out=None, stats_out=None):
     """`cfg_dpm_step` with the rescaled guided noise (`vdx_cfg_rescale_dpm_step_f16`) -> (lat', x0)."""
-    _eps2_like("cfg_rescale_dpm_step", eps2, lat)
-    x0_out, out, c = _dpm_args("cfg_rescale_dpm_step", lat, x0_prev, x0_out, out, coeffs)
-    _, pp, sp_ = _rescale_buffers("cfg_rescale_dpm_step", cfg_rescale_rows(lat.numel()), lat, partials, stats_out)
-    phi, phi1 = (float(v) for v in rescale)
-    _launch("vdx_cfg_rescale_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
-            _p(out, "out"), pp, sp_, float(guidance), phi, phi1, *c, lat.numel())
-    return out, x0_out
+    return _one_step("vdx_cfg_rescale_dpm_step_f16", eps2, lat, guidance, coeffs, (x0_prev, x0_out), out,
+                     rescaled=(rescale, partials, stats_out))
 
 
 def cofuse_cfg_rescale_stats(z, windows, table, wn, guidance, partials=None):
@@ -1306,23 +1298,12 @@ def cfg_mimic_stats(eps2, guidance, mimic, ws=None, stages: int = 7):
 def cfg_mimic_ddim_step(eps2, lat, guidance, coeffs, ws, out=None):
     """`cfg_ddim_step` with the guided noise thresholded per channel by the scalars `cfg_mimic_stats` of the same eps2 left in
     `ws` (`vdx_cfg_mimic_ddim_step_f16`)."""
-    _eps2_5d("cfg_mimic_ddim_step", eps2, lat)
-    if out is None:
-        out = torch.empty_like(lat)
-    _, wp, shape = _mimic_ws("cfg_mimic_ddim_step", lat.shape, lat, ws)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch("vdx_cfg_mimic_ddim_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(out, "out"), wp, float(guidance), s1, sa, sp, s1p, *shape)
-    return out
+    return _one_step("vdx_cfg_mimic_ddim_step_f16", eps2, lat, guidance, coeffs, None, out, mimic=(ws,))
 
 
 def cfg_mimic_dpm_step(eps2, lat, guidance, coeffs, ws, x0_prev=None, x0_out=None, out=None):
     """`cfg_dpm_step` with the thresholded guided noise (`vdx_cfg_mimic_dpm_step_f16`) -> (lat', x0)."""
-    _eps2_5d("cfg_mimic_dpm_step", eps2, lat)
-    x0_out, out, c = _dpm_args("cfg_mimic_dpm_step", lat, x0_prev, x0_out, out, coeffs)
-    _, wp, shape = _mimic_ws("cfg_mimic_dpm_step", lat.shape, lat, ws)
-    _launch("vdx_cfg_mimic_dpm_step_f16", _p(eps2, "eps2"), _p(lat, "lat"), _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"),
-            _p(out, "out"), wp, float(guidance), *c, *shape)
-    return out, x0_out
+    return _one_step("vdx_cfg_mimic_dpm_step_f16", eps2, lat, guidance, coeffs, (x0_prev, x0_out), out, mimic=(ws,))
 
 
 def cofuse_cfg_mimic_stats(z, windows, table, wn, guidance, mimic, ws=None, stages: int = 7):

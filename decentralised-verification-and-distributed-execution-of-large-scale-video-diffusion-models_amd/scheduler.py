@@ -21,6 +21,21 @@ import torch
 
 from . import ops
 
+# The fused steps: (noise source, guidance) -> (the statistics op or None, the step's (DDIM, DPM-Solver++) pair), as the names of
+# `ops` functions, looked up at the call.  The sources: "one" buffer eps2 = [u; c], else the whole clip's noise fused from "windows",
+# "tiles", "ring" windows or "strided" ones.  A missing key is a combination that has no kernel.
+_STEPS = {
+    ("one", "plain"): (None, ("cfg_ddim_step", "cfg_dpm_step")),
+    ("one", "rescale"): ("cfg_rescale_stats", ("cfg_rescale_ddim_step", "cfg_rescale_dpm_step")),
+    ("one", "mimic"): ("cfg_mimic_stats", ("cfg_mimic_ddim_step", "cfg_mimic_dpm_step")),
+    ("windows", "plain"): (None, ("cofuse_cfg_ddim_step", "cofuse_cfg_dpm_step")),
+    ("windows", "rescale"): ("cofuse_cfg_rescale_stats", ("cofuse_cfg_rescale_ddim_step", "cofuse_cfg_rescale_dpm_step")),
+    ("windows", "mimic"): ("cofuse_cfg_mimic_stats", ("cofuse_cfg_mimic_ddim_step", "cofuse_cfg_mimic_dpm_step")),
+    ("tiles", "plain"): (None, ("cotile_cfg_ddim_step", "cotile_cfg_dpm_step")),
+    ("ring", "plain"): (None, ("coloop_cfg_ddim_step", "coloop_cfg_dpm_step")),
+    ("strided", "plain"): (None, ("costride_cfg_ddim_step", "costride_cfg_dpm_step")),
+}
+
 
 class _SchedulerBase:
     """What the schedulers share: the call-surface constants, the sync-free timestep lookup, `add_noise`, and a `reset()`
@@ -82,27 +97,26 @@ class _SchedulerBase:
         once the kernel was enqueued).  It changes nothing that a launch which raises would have to undo."""
         raise NotImplementedError
 
-    def _fused_step(self, steps, head, timestep, sample, guidance_scale, guidance_rescale=0.0, rescaled=None, cfg_mimic=None,
-                    cfg_mimic_percentile=1.0, mimicked=None):
-        """`steps[self._dpm](*head, ...)`, `steps` = the (DDIM, DPM-Solver++) pair of an `ops` step.  With `guidance_rescale` != 0
-        `rescaled` = (the statistics op, its leading arguments, the pair of rescaled steps): two launches and no host read.  With
-        `cfg_mimic` (csrc/dynthresh.hip) `mimicked` is the same triple of the thresholded steps: four launches and no host read,
-        the statistics in `ops`' per-stream workspace."""
+    def _fused_step(self, source, head, timestep, sample, guidance_scale, guidance_rescale=0.0, cfg_mimic=None, cfg_mimic_percentile=1.0):
+        """One fused step of `_STEPS[source, guide]` on `head`, the ops' leading arguments (the noise, then the latent).  Plain: one
+        launch.  `guidance_rescale` != 0 (csrc/rescale.hip): the statistics op, then the rescaled step, two launches.  `cfg_mimic`
+        (csrc/dynthresh.hip): four launches, the statistics in `ops`' per-stream workspace.  Never a host read."""
         if cfg_mimic is not None and guidance_rescale != 0.0:
             raise ValueError("cfg_mimic and guidance_rescale exclude each other: both rewrite the guided noise, and no order is defined")
+        guide = "mimic" if cfg_mimic is not None else "rescale" if guidance_rescale != 0.0 else "plain"
+        stats_name, step_names = _STEPS[source, guide]
+        step, stats_op = getattr(ops, step_names[self._dpm]), stats_name and getattr(ops, stats_name)
         coeffs, history, commit = self._begin(timestep, sample)
-        if cfg_mimic is not None:
-            stats_op, stats_head, steps = mimicked
-            factors = self._mimic(cfg_mimic, cfg_mimic_percentile, sample)
-            ws = stats_op(*stats_head, guidance_scale, factors)
-            res = steps[self._dpm](*head, guidance_scale, coeffs, ws, **history)
-        elif guidance_rescale == 0.0:
-            res = steps[self._dpm](*head, guidance_scale, coeffs, **history)
-        else:
-            stats_op, stats_head, steps = rescaled
+        noise = head[:1] if source == "one" else head             # what the statistics read: eps2, or (z for its shape, the windows ...)
+        if guide == "mimic":
+            ws = stats_op(*noise, guidance_scale, self._mimic(cfg_mimic, cfg_mimic_percentile, sample))
+            res = step(*head, guidance_scale, coeffs, ws, **history)
+        elif guide == "rescale":
             rescale, stats = self._rescale(guidance_rescale, sample.device)
-            part = stats_op(*stats_head, guidance_scale)
-            res = steps[self._dpm](*head, guidance_scale, rescale, coeffs, part, stats_out=stats, **history)
+            part = stats_op(*noise, guidance_scale)
+            res = step(*head, guidance_scale, rescale, coeffs, part, stats_out=stats, **history)
+        else:
+            res = step(*head, guidance_scale, coeffs, **history)
         commit()
         return res[0] if self._dpm else res                       # the DPM-Solver++ ops return (the new latent, x0)
 
@@ -116,10 +130,7 @@ class _SchedulerBase:
         squeezed into the range the same prediction has at the mimic scale, in four launches and without a host read.  Not both."""
         if self._dpm or guidance_rescale != 0.0 or cfg_mimic is not None:   # the plain DDIM op refuses a non-contiguous sample itself
             sample = sample.contiguous()
-        return self._fused_step((ops.cfg_ddim_step, ops.cfg_dpm_step), (noise2, sample), timestep, sample, guidance_scale,
-                                guidance_rescale, (ops.cfg_rescale_stats, (noise2,), (ops.cfg_rescale_ddim_step, ops.cfg_rescale_dpm_step)),
-                                cfg_mimic, cfg_mimic_percentile,
-                                (ops.cfg_mimic_stats, (noise2,), (ops.cfg_mimic_ddim_step, ops.cfg_mimic_dpm_step)))
+        return self._fused_step("one", (noise2, sample), timestep, sample, guidance_scale, guidance_rescale, cfg_mimic, cfg_mimic_percentile)
 
     def step_cfg_windows(self, windows, table, wn, timestep, sample, guidance_scale: float, guidance_rescale: float = 0.0,
                          cfg_mimic=None, cfg_mimic_percentile: float = 1.0):
@@ -127,33 +138,30 @@ class _SchedulerBase:
         windows' raw UNet outputs in `windows` (`table`, `wn`: `ops.cofuse_cfg_ddim_step` / `ops.cofuse_cfg_dpm_step`), one
         kernel; with `guidance_rescale` != 0 two, with `cfg_mimic` four, the statistics being those of the fused noise over the
         whole clip."""
-        head = (sample.contiguous(), windows, table, wn)
-        return self._fused_step((ops.cofuse_cfg_ddim_step, ops.cofuse_cfg_dpm_step), head, timestep, head[0], guidance_scale,
-                                guidance_rescale, (ops.cofuse_cfg_rescale_stats, head,
-                                                   (ops.cofuse_cfg_rescale_ddim_step, ops.cofuse_cfg_rescale_dpm_step)),
-                                cfg_mimic, cfg_mimic_percentile,
-                                (ops.cofuse_cfg_mimic_stats, head, (ops.cofuse_cfg_mimic_ddim_step, ops.cofuse_cfg_mimic_dpm_step)))
+        sample = sample.contiguous()
+        return self._fused_step("windows", (sample, windows, table, wn), timestep, sample, guidance_scale, guidance_rescale, cfg_mimic,
+                                cfg_mimic_percentile)
 
     def step_cfg_tiles(self, windows, table, wn, tiles, timestep, sample, guidance_scale: float):
         """Spatially tiled co-denoising (vdx/codenoise.py `tile_plan`): `step_cfg_windows` with every time window's block holding
         its row x column tiles' outputs (`tiles`: an `ops.TileGrid`; `ops.cotile_cfg_ddim_step` / `ops.cotile_cfg_dpm_step`), one
         kernel.  There is no `guidance_rescale` form: its statistics pass has no tiled fuse."""
-        head = (sample.contiguous(), windows, table, wn, tiles)
-        return self._fused_step((ops.cotile_cfg_ddim_step, ops.cotile_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+        sample = sample.contiguous()
+        return self._fused_step("tiles", (sample, windows, table, wn, tiles), timestep, sample, guidance_scale)
 
     def step_cfg_loop(self, windows, table, wn, timestep, sample, guidance_scale: float):
         """Seamless looping (vdx/codenoise.py `loop_plan`): `step_cfg_windows` with every window on a ring, a `table` row
         (offset, s, L) meaning the frames (s + f) mod T (`ops.coloop_cfg_ddim_step` / `ops.coloop_cfg_dpm_step`), one kernel.
         No `guidance_rescale` form."""
-        head = (sample.contiguous(), windows, table, wn)
-        return self._fused_step((ops.coloop_cfg_ddim_step, ops.coloop_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+        sample = sample.contiguous()
+        return self._fused_step("ring", (sample, windows, table, wn), timestep, sample, guidance_scale)
 
     def step_cfg_strided(self, windows, table, wn, timestep, sample, guidance_scale: float):
         """Strided context windows (vdx/codenoise.py `stride_plan`): `step_cfg_windows` with a `table` row (offset, s, L, d)
         meaning the frames s + f * d (`ops.costride_cfg_ddim_step` / `ops.costride_cfg_dpm_step`), one kernel.
         No `guidance_rescale` form."""
-        head = (sample.contiguous(), windows, table, wn)
-        return self._fused_step((ops.costride_cfg_ddim_step, ops.costride_cfg_dpm_step), head, timestep, head[0], guidance_scale)
+        sample = sample.contiguous()
+        return self._fused_step("strided", (sample, windows, table, wn), timestep, sample, guidance_scale)
 
     def add_noise(self, original_samples, noise, timesteps):
         """diffusers `DDIMScheduler.add_noise` for one timestep: alphas_cumprod is cast to the sample dtype (fp16) FIRST,

@@ -105,6 +105,26 @@ def test_step_bit_exact_sizes(gpu, n):
         _check_one(ops, eps2, lat, prev, R.scalars(sig, i, second), second, f"n {n} i {i}")
 
 
+@pytest.mark.parametrize("n", [2048, 2052, 2051])
+def test_step_bit_exact_at_every_access_width(gpu, n):
+    """n a multiple of 8, of 4 only, and odd (16-, 8- and 2-byte accesses), both orders, both entries; at 2048 also in place."""
+    ops, _ = _ops()
+    sig = R.sigmas(10)
+    eps2, lat, prev = _inputs(n, n, gpu)
+    for i, second in ((0, False), (5, True)):
+        k = R.scalars(sig, i, second)
+        want, want_x0 = _check_one(ops, eps2, lat, prev, k, second, f"n {n} i {i}")
+        if n == 2048:
+            p = prev if second else None
+            x = lat.clone()
+            got, got_x0 = ops.cfg_dpm_step(eps2, x, GS, _coeffs(k), x0_prev=p, out=x)
+            assert got is x
+            _same(got, want, "in place cfg"), _same(got_x0, want_x0, "in place cfg x0")
+            x = lat.clone()
+            got, got_x0 = ops.dpm_step(R.cfg_combine(eps2, GS), x, _coeffs(k), x0_prev=p, out=x)
+            _same(got, want, "in place"), _same(got_x0, want_x0, "in place x0")
+
+
 def test_last_step_returns_the_bits_of_x0(gpu):
     ops, _ = _ops()
     for steps in (1, 2, 10, 25):

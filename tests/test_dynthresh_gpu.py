@@ -16,6 +16,7 @@ import torch
 import codenoise_ref as CR
 import dpm_ref
 import dynthresh_ref as D
+import stats_order_ref as O
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -174,7 +175,12 @@ def _flat(ops, gpu, eps2, x, gs):
     return stats, (ddim, dpm)
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=str)
+# (C, T, HW) = (3, 2, 24), (3, 2, 20), (3, 1, 7): M a multiple of 8, of 4 only, and odd, so a channel boundary falls inside what a
+# wider access would span
+WIDTHS = [(3, 2, 4, 6), (3, 2, 4, 5), (3, 1, 1, 7)]
+
+
+@pytest.mark.parametrize("shape", SHAPES + WIDTHS, ids=str)
 def test_every_stage_from_the_stage_before(gpu, shape):
     ops, _ = _ops()
     eps2, x, prev = _case(shape)
@@ -328,6 +334,65 @@ def test_cofused_stages_and_end_to_end_on_the_fused_noise(gpu, C, T, h, w, table
     _same(ops.cofuse_cfg_mimic_ddim_step(zg, bg, rows, wg, GS, DDIM, ws), D.ddim_step(eps2, z, GS, MS, 0.995, DDIM), "cofuse end to end")
 
 
+def _workspace_in_the_stated_order(ops, ws, eps2, order, rows, q, what):
+    """`scal`, `partials`, `hist` and `maxbits` of a finished statistics pass against the host: the partial rows bit for bit
+    (tests/stats_order_ref.py: `order(x, nx)` is the source's block map), and everything after them from those rows."""
+    C, M = eps2.shape[1], eps2[0, 0].numel()
+    v = ops.mimic_ws_views(ws, C)
+    g, l = D.combines(eps2, GS, MS)
+    want = np.stack([O.rows(np.stack([g[ch].double().numpy(), l[ch].double().numpy()], axis=1), order, rows) for ch in range(C)])
+    assert O.same_bits(v["partials"][:, :rows].cpu().numpy(), want), f"{what}: partials"
+    means = D.means_of(_kernel_sums({"partials": torch.from_numpy(want)}, C, rows), M)
+    hist, maxbits = D.histogram(eps2, GS, MS, means)
+    assert torch.equal(v["hist"].cpu().long(), hist), f"{what}: hist"
+    assert torch.equal(v["maxbits"].cpu().long(), maxbits), f"{what}: maxbits"
+    _same_scal(_u16(v["scal"]), D.select(eps2, GS, MS, q, means), f"{what}: scal")
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 2052), (2, 3, 4, 5)], ids=str)
+def test_workspace_bit_for_bit_in_the_stated_order(gpu, shape):
+    ops, _ = _ops()
+    eps2 = _case(shape)[0]
+    M = shape[1] * shape[2] * shape[3]
+    ws = ops.cfg_mimic_stats(eps2.to(gpu), GS, ops.mimic_factors(MS, 0.995, M))
+    _workspace_in_the_stated_order(ops, ws, eps2, lambda x, k: O.direct_order(M, O.width(M), x, k), _rows(M), 0.995, str(shape))
+
+
+def test_cofused_workspace_bit_for_bit_in_the_stated_order(gpu):
+    """(C, T, HW) = (2, 3, 20), two windows that overlap in frame 1: a channel's T lines, block x the lines x, x + rows, ..."""
+    ops, _ = _ops()
+    C, T, h, w, table = 2, 3, 4, 5, [(0, 2), (1, 2)]
+    wins, packed, rows, wn = _windows(C, T, h, w, table, 5)
+    eps2 = CR.fuse(wins, table, wn, (1, C, T, h, w))
+    z = torch.zeros(1, C, T, h, w, dtype=torch.float16, device=gpu)
+    ws = ops.cofuse_cfg_mimic_stats(z, packed.to(gpu), rows, wn.to(gpu), GS, ops.mimic_factors(MS, 0.995, T * h * w))
+    _workspace_in_the_stated_order(ops, ws, eps2, lambda x, k: O.line_order(T, h * w, O.width(h * w), x, k), min(T, 64), 0.995, "cofuse")
+
+
+def test_thresholded_step_past_the_block_cap_equals_its_halves_and_runs_in_place(gpu):
+    """C = 1, M = 1024 * 256 * 8 + 8 * 300 as two frames: a lane of the 1024-block grid takes a second trip.  The same entry on
+    each frame alone, given the same workspace (the step reads the channel's scalars only), gives the same bits; then the
+    DPM-Solver++ entry, second order, with `out` being `lat`."""
+    ops, _ = _ops()
+    M = 1024 * 256 * 8 + 8 * 300
+    h = M // 2
+    assert h % 8 == 0
+    g = torch.Generator(device=gpu).manual_seed(13)
+    noise = torch.randn(2, 1, 2, 1, h, generator=g, device=gpu).half()
+    lat, prev = (torch.randn(1, 1, 2, 1, h, generator=g, device=gpu).half() for _ in range(2))
+    ws = ops.cfg_mimic_stats(noise, GS, ops.mimic_factors(MS, 0.995, M)).clone()
+    got = ops.cfg_mimic_ddim_step(noise, lat, GS, DDIM, ws)
+    assert bool(torch.isfinite(got.float()).all())
+    for t in (0, 1):
+        half = ops.cfg_mimic_ddim_step(noise[:, :, t:t + 1].contiguous(), lat[:, :, t:t + 1].contiguous(), GS, DDIM, ws)
+        assert torch.equal(got[:, :, t:t + 1], half)
+    c = _dpm_coeffs(dpm_ref.scalars(dpm_ref.sigmas(10), 4, True))
+    new, x0 = ops.cfg_mimic_dpm_step(noise, lat, GS, c, ws, x0_prev=prev)
+    y = lat.clone()
+    same, x0_again = ops.cfg_mimic_dpm_step(noise, y, GS, c, ws, x0_prev=prev, out=y)
+    assert same is y and torch.equal(y, new) and torch.equal(x0_again, x0)
+
+
 @pytest.mark.parametrize("shape", [(4, 3, 5, 7), (3, 2, 2, 6), (4, 4, 48, 48)], ids=str)
 def test_one_window_is_the_flat_step(gpu, shape):
     ops, _ = _ops()
@@ -376,6 +441,9 @@ def test_bad_arguments_are_refused_before_a_launch(gpu):
         assert lib.vdx_cfg_mimic_ddim_step_f16(*args, *tail) != 0, args
     assert lib.vdx_cfg_mimic_dpm_step_f16(pe, px, None, None, po, pw, GS, 1, 1, 1, 1, 0, 0, 4, 2, 12, stream) != 0
     assert lib.vdx_cfg_mimic_dpm_step_f16(pe, px, None, po, po, pw, GS, 1, 1, 1, 1, 0, 0, 4, 2, 12, stream) != 0
+    prev = torch.zeros_like(xg)                           # the history may be neither its predecessor nor the latent
+    assert lib.vdx_cfg_mimic_dpm_step_f16(pe, px, prev.data_ptr(), prev.data_ptr(), po, pw, GS, 1, 1, 1, 1, 0, 0, 4, 2, 12, stream) != 0
+    assert lib.vdx_cfg_mimic_dpm_step_f16(pe, px, prev.data_ptr(), px, po, pw, GS, 1, 1, 1, 1, 0, 0, 4, 2, 12, stream) != 0
     with pytest.raises(VdxError, match="bytes"):
         ops.cfg_mimic_ddim_step(e, xg, GS, DDIM, ws[:64])
     with pytest.raises(VdxError):

@@ -1046,6 +1046,95 @@ def test_cfg_ddim_step_bit_exact(gpu, steps):
         lat = want
 
 
+DDIM_COEFFS = (0.9493, 0.3143, 0.4206, 0.9073)      # any four fp32 coefficients, where no reference is evaluated
+
+
+def _ddim_case(n, gpu):
+    """Seeded (2, n) noise and (1, n) latent -> (noise, guided noise, latent) on the GPU, the step `test_cfg_ddim_step_bit_exact`
+    pins (oracle/ddim_ref.py `step_gpu_rules`, evaluated on the CPU) and its coefficients."""
+    from oracle.ddim_ref import DDIMSchedulerRef
+    s = DDIMSchedulerRef()
+    s.set_timesteps(10)
+    t = s.timesteps[3]
+    g = torch.Generator().manual_seed(n)
+    noise, lat = torch.randn(2, n, generator=g).half(), torch.randn(1, n, generator=g).half()
+    u, c = noise.chunk(2)
+    guided = u + 7.5 * (c - u)
+    return noise.to(gpu), guided.to(gpu), lat.to(gpu), s.step_gpu_rules(guided, t, lat).prev_sample.to(gpu), s.coefficients(int(t))
+
+
+@pytest.mark.parametrize("n", [2048, 2052, 2051])
+def test_ddim_steps_at_every_access_width(gpu, n):
+    """n a multiple of 8, of 4 only, and odd: the one-buffer step kernel's 16-, 8- and 2-byte accesses; then `out` being `lat`."""
+    ops, _ = _ops()
+    noise, guided, lat, want, coeffs = _ddim_case(n, gpu)
+    assert want.dtype == torch.float16
+    assert torch.equal(ops.cfg_ddim_step(noise, lat, 7.5, coeffs), want)
+    assert torch.equal(ops.ddim_step(guided, lat, coeffs), want)
+    x = lat.clone()
+    assert ops.cfg_ddim_step(noise, x, 7.5, coeffs, out=x) is x and torch.equal(x, want)
+    x = lat.clone()
+    assert ops.ddim_step(guided, x, coeffs, out=x) is x and torch.equal(x, want)
+
+
+@pytest.mark.parametrize("n,off", [(2051, 1), (2048, 1), (2048, 4)])
+def test_ddim_entries_take_tensors_off_a_16_byte_boundary(gpu, n, off):
+    """The two DDIM entries of the library take any fp16 pointers (`ops` itself asks for 16-byte ones): `lat` and `eps` that start
+    2 bytes into an allocation, n odd, are accepted and give the bits of the aligned call; so are, at an n that would allow 16-byte
+    accesses, pointers 2 and 8 bytes off, which narrow the access to 2 and 8 bytes."""
+    ops, _ = _ops()
+    from vdx import _lib
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    noise, guided, lat, want, coeffs = _ddim_case(n, gpu)
+    off_lat = torch.zeros(n + 8, dtype=torch.float16, device=gpu)[off:off + n]
+    off_eps = torch.zeros(2 * n + 8, dtype=torch.float16, device=gpu)[off:off + 2 * n]
+    assert off_lat.data_ptr() % 16 == 2 * off and off_eps.data_ptr() % 16 == 2 * off
+    off_lat.copy_(lat.view(-1)), off_eps.copy_(noise.view(-1))
+    out = torch.zeros(1, n, dtype=torch.float16, device=gpu)
+    _lib.check(lib.vdx_cfg_ddim_step_f16(off_eps.data_ptr(), off_lat.data_ptr(), out.data_ptr(), 7.5, *coeffs, n, stream),
+               "vdx_cfg_ddim_step_f16")
+    assert torch.equal(out, want)
+    off_eps[:n].copy_(guided.view(-1))
+    out.zero_()
+    _lib.check(lib.vdx_ddim_step_f16(off_eps.data_ptr(), off_lat.data_ptr(), out.data_ptr(), *coeffs, n, stream), "vdx_ddim_step_f16")
+    assert torch.equal(out, want)
+    off_out = torch.zeros(n + 8, dtype=torch.float16, device=gpu)[off:off + n]     # and an output off the boundary, the rest on it
+    _lib.check(lib.vdx_ddim_step_f16(guided.data_ptr(), lat.data_ptr(), off_out.data_ptr(), *coeffs, n, stream), "vdx_ddim_step_f16")
+    assert torch.equal(off_out.view(1, n), want)
+
+
+def test_ddim_entries_refuse_an_output_that_half_overlaps_the_latent(gpu):
+    ops, _ = _ops()
+    from vdx._lib import VdxError
+    n = 2048
+    buf = torch.zeros(2 * n, dtype=torch.float16, device=gpu)
+    lat, out = buf[:n].view(1, n), buf[n // 2:n // 2 + n].view(1, n)
+    noise = torch.zeros(2, n, dtype=torch.float16, device=gpu)
+    with pytest.raises(VdxError):
+        ops.cfg_ddim_step(noise, lat, 7.5, DDIM_COEFFS, out=out)
+    with pytest.raises(VdxError):
+        ops.ddim_step(noise[:1], lat, DDIM_COEFFS, out=out)
+    with pytest.raises(VdxError):                       # ... or the noise
+        ops.cfg_ddim_step(noise, lat, 7.5, DDIM_COEFFS, out=noise[1:])
+    assert torch.equal(ops.cfg_ddim_step(noise, lat, 7.5, DDIM_COEFFS, out=lat), torch.zeros_like(lat))
+
+
+def test_plain_step_past_the_block_cap_equals_its_halves(gpu):
+    """n = 4096 * 256 * 8 + 8 * 300: a lane of the capped grid takes a second trip.  The same entry on the two halves of the buffers
+    gives the same bits (an element's result depends on nothing but its own inputs)."""
+    ops, _ = _ops()
+    n = 4096 * 256 * 8 + 8 * 300
+    h = n // 2
+    assert h % 8 == 0
+    g = torch.Generator(device=gpu).manual_seed(11)
+    noise = torch.randn(2, n, generator=g, device=gpu).half()
+    lat = torch.randn(1, n, generator=g, device=gpu).half()
+    got = ops.cfg_ddim_step(noise, lat, 7.5, DDIM_COEFFS)
+    for sl in (slice(0, h), slice(h, n)):
+        part = ops.cfg_ddim_step(noise[:, sl].contiguous(), lat[:, sl].contiguous(), 7.5, DDIM_COEFFS)
+        assert torch.equal(got[:, sl], part)
+
+
 @pytest.mark.parametrize("hin,win,hout,wout", [(5, 8, 9, 15), (9, 15, 18, 30), (3, 3, 5, 6), (4, 4, 8, 8), (7, 2, 7, 3)])
 def test_conv3x3_upsample_to_size(gpu, hin, win, hout, wout):
     """conv3x3 over a source nearest-upsampled to an explicit size (vdx_gemm_args.upsample = 2) against

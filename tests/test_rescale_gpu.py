@@ -14,6 +14,7 @@ import torch
 import codenoise_ref as CR
 import dpm_ref
 import rescale_ref as R
+import stats_order_ref as O
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,9 +86,12 @@ def test_partial_sums(gpu, shape):
     assert torch.equal(again.view(torch.int64), part.view(torch.int64))
 
 
-@pytest.mark.parametrize("shape", SHAPES + [HEADLINE], ids=str)
+WIDTHS = [(2048,), (2052,), (2051,)]                               # n a multiple of 8, of 4 only, and odd: every access width
+
+
+@pytest.mark.parametrize("shape", SHAPES + [HEADLINE] + WIDTHS, ids=str)
 def test_steps_given_the_kernels_own_r(gpu, shape):
-    ops, _ = _ops()
+    ops, VdxError = _ops()
     eps2, x, prev = _case(shape)
     e, xg, pg = eps2.to(gpu), x.to(gpu), prev.to(gpu)
     gs, phi = 7.5, 0.7
@@ -110,6 +114,13 @@ def test_steps_given_the_kernels_own_r(gpu, shape):
     # in place on the latent, as the plain steps allow
     y = xg.clone()
     assert ops.cfg_rescale_ddim_step(e, y, gs, fac, DDIM, part, out=y) is y and torch.equal(y, got)
+    y = xg.clone()
+    assert ops.cfg_rescale_dpm_step(e, y, gs, fac, coeffs, part, x0_prev=pg, out=y)[0] is y and torch.equal(y, new)
+    # the history may be neither its predecessor nor the latent
+    with pytest.raises(VdxError):
+        ops.cfg_rescale_dpm_step(e, xg, gs, fac, coeffs, part, x0_prev=pg, x0_out=pg)
+    with pytest.raises(VdxError):
+        ops.cfg_rescale_dpm_step(e, xg, gs, fac, coeffs, part, x0_prev=pg, x0_out=xg)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
@@ -194,6 +205,59 @@ def test_cofused_steps_match_the_restatement_on_the_fused_noise(gpu, C, T, h, w,
         want, want0 = R.dpm_step(eps2, z, prev if second else None, gs, phi, k)
         _same_bits(new, want, f"cofuse dpm order {1 + second}")
         _same_bits(x0, want0, f"cofuse dpm order {1 + second}: history")
+
+
+def _rescale_terms(eps2, gs):
+    """float64 (n, 4): c, c*c, g, g*g per element, in memory order (the products are exact in fp32, so in float64 too)."""
+    c = eps2[1].reshape(-1).double().numpy()
+    g = dpm_ref.cfg_combine(eps2, gs).reshape(-1).double().numpy()
+    return np.stack([c, c * c, g, g * g], axis=1)
+
+
+@pytest.mark.parametrize("shape", [(2052,), (2, 3, 4, 5)], ids=str)
+def test_partial_rows_bit_for_bit_in_the_stated_order(gpu, shape):
+    """Every row of `cfg_rescale_stats` against tests/stats_order_ref.py: per lane in stride order, shuffle tree, waves ascending."""
+    ops, _ = _ops()
+    eps2 = _case(shape)[0]
+    n = eps2.numel() // 2
+    E, nx = O.width(n), ops.cfg_rescale_rows(n)
+    want = O.rows(_rescale_terms(eps2, 7.5), lambda x, k: O.direct_order(n, E, x, k), nx)
+    assert O.same_bits(ops.cfg_rescale_stats(eps2.to(gpu), 7.5).cpu().numpy(), want)
+
+
+def test_cofused_partial_rows_bit_for_bit_in_the_stated_order(gpu):
+    """(C, T, HW) = (2, 3, 20), two windows that overlap in frame 1: the clip as C T lines, block b the lines b, b + rows, ..."""
+    ops, _ = _ops()
+    C, T, h, w, table = 2, 3, 4, 5, [(0, 2), (1, 2)]
+    wins, packed, rows, wn = _windows(C, T, h, w, table, 5)
+    eps2 = CR.fuse(wins, table, wn, (1, C, T, h, w))
+    z = torch.zeros(1, C, T, h, w, dtype=torch.float16, device=gpu)
+    got = ops.cofuse_cfg_rescale_stats(z, packed.to(gpu), rows, wn.to(gpu), 7.5).cpu().numpy()
+    want = O.rows(_rescale_terms(eps2, 7.5), lambda x, k: O.line_order(C * T, h * w, O.width(h * w), x, k), min(C * T, 256))
+    assert O.same_bits(got, want)
+
+
+def test_rescaled_step_past_the_block_cap_equals_its_halves(gpu):
+    """n = 4096 * 256 * 8 + 8 * 300: a lane of the capped grid takes a second trip behind a prologue that uses LDS.  The same entry
+    on the two halves of the buffers, given the same statistics buffer, gives the same bits: the buffer holds S1 = 0 and
+    S2c = 4 S2g, so sd_c = 2 sd_g in fp16 and r = 2 whatever N is."""
+    ops, _ = _ops()
+    n = 4096 * 256 * 8 + 8 * 300
+    h = n // 2
+    assert h % 8 == 0 and ops.cfg_rescale_rows(n) == ops.cfg_rescale_rows(h) == 256
+    g = torch.Generator(device=gpu).manual_seed(12)
+    noise = torch.randn(2, n, generator=g, device=gpu).half()
+    lat = torch.randn(1, n, generator=g, device=gpu).half()
+    part = torch.zeros(256, 4, dtype=torch.float64, device=gpu)
+    part[0, 1], part[0, 3] = 4.0 * n, 1.0 * n
+    st = torch.zeros(8, dtype=torch.float16, device=gpu)
+    fac = ops.rescale_factors(0.7)
+    got = ops.cfg_rescale_ddim_step(noise, lat, 7.5, fac, DDIM, part, stats_out=st)
+    assert float(st[2]) == 2.0
+    for sl in (slice(0, h), slice(h, n)):
+        st.zero_()
+        half = ops.cfg_rescale_ddim_step(noise[:, sl].contiguous(), lat[:, sl].contiguous(), 7.5, fac, DDIM, part, stats_out=st)
+        assert float(st[2]) == 2.0 and torch.equal(got[:, sl], half)
 
 
 @pytest.mark.parametrize("shape", [(4, 3, 5, 7), (4, 2, 4, 6), (4, 16, 18, 32)], ids=str)

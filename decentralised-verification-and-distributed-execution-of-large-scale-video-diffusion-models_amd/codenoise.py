@@ -32,12 +32,16 @@ frame's fused noise (`stride_plan`, `stride_table` below; `check_stride` in vdx/
 tests/test_costride_gpu.py against tests/costride_ref.py, the stride itself by permuting the clip; NOT pinned and not claimed:
 no external implementation is pinned (the schedule is restated), and there is no quality claim on real Zeroscope weights, whose
 temporal layers were trained on consecutive frames and see faster motion in a strided window.
+
+Whatever the plan, a window is ONE row here, `Window(s, L, d, ring)`: the frames `s + f * d`, f in [0, L), mod T on a ring
+(`plan_windows`, `rank_windows`).  `_fuse_table` is the one builder of the normalised weights, behind `window_table`, `loop_table`
+and `stride_table`, and `co_denoise_round` the one per-step loop: it reads its input op and its scheduler step from `_KINDS` once.
 """
 from __future__ import annotations
 
 import time
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -57,40 +61,94 @@ def fuse_weights(length: int, overlap: int) -> List[float]:
     return [min(j + 1, length - j, overlap + 1) / (overlap + 1) for j in range(length)]
 
 
+class Window(NamedTuple):
+    """One window, whatever plan it came from: the `L` frames `s + f * d`, f in [0, L), taken mod T when `ring`.  It is what
+    `DistributedVideoDiffuser.window_text` and `region_kw` take, in their order."""
+    s: int
+    L: int
+    d: int = 1
+    ring: bool = False
+
+
+def plan_windows(plan, ring: bool = False) -> List[Window]:
+    """Every window of a plan in plan order: a `ChunkPlan`'s ranges (`ring`: a `loop_plan`'s) or a `StridePlan`'s windows."""
+    if isinstance(plan, StridePlan):
+        return [Window(s, L, d) for s, L, d in plan.windows]
+    return [Window(s, e - s, 1, ring) for s, e in plan.ranges]
+
+
+def rank_windows(plan, rank: int, ring: bool = False) -> Tuple[List[Window], int, int]:
+    """(this rank's windows, `chunk`, `per_rank`) of any plan: window i belongs to rank `i % world`; `chunk`, the longest window,
+    sizes a slot of the packed buffer, and every rank has `per_rank` of them."""
+    return plan_windows(plan, ring)[rank::plan.world], plan.chunk, plan.per_rank
+
+
+@dataclass(frozen=True)
+class StrideTable:
+    """`fused`: (index in the plan, s, L, d) of the windows that enter the fuse, in plan order; `wn`: fp32 (K, T), the normalised
+    weights, zero outside a window."""
+    fused: Tuple[Tuple[int, int, int, int], ...]
+    wn: torch.Tensor
+
+    def rows(self, world: int, per_rank: int, slot_elems: int) -> List[Tuple[int, int, int, int]]:
+        """(element offset, first frame, length, stride) per fused window in the packed buffer `[world][per_rank][slot]`: window i
+        of the plan sits at rank i % world, slot i // world."""
+        return [(((i % world) * per_rank + i // world) * slot_elems, s, L, d) for i, s, L, d in self.fused]
+
+
 @dataclass(frozen=True)
 class WindowTable:
-    """`fused`: (index in the plan, s, e) of the windows that enter the fuse, in plan order; `wn`: fp32 (K, T), the normalised
-    weights, zero outside a window."""
+    """A `StrideTable` of stride 1 as flat and ring plans are read: `fused` rows (index in the plan, s, e), e = s + L (past T where
+    a ring window wraps), and `rows()` without the stride column."""
     fused: Tuple[Tuple[int, int, int], ...]
     wn: torch.Tensor
 
     def rows(self, world: int, per_rank: int, slot_elems: int) -> List[Tuple[int, int, int]]:
-        """(element offset, first frame, length) per fused window in the packed buffer `[world][per_rank][slot]`: window i of
-        the plan sits at rank i % world, slot i // world."""
         return [(((i % world) * per_rank + i // world) * slot_elems, s, e - s) for i, s, e in self.fused]
 
 
-def window_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
-    """The plan's windows in plan order.  A range that repeats an earlier one (the planner's repeated tail window) is still
-    DENOISED by its rank, so that all ranks make the same number of UNet calls and the sharded parameters' gathers stay in
-    lockstep, but it is left out of the fuse.  `wn[k][t] = w_k[t - s_k] / sum over the fused windows that hold t`, in float64,
-    then rounded to fp32: exactly 1.0 where one window covers a frame.  A frame in no window is a `ValueError`."""
-    seen, fused = set(), []
-    for i, (s, e) in enumerate(chunk_plan.ranges):
-        if not 0 <= s < e <= T:
-            raise ValueError(f"window_table: window {i} = [{s}, {e}) leaves the {T} frames")
-        if (s, e) not in seen:
-            seen.add((s, e))
-            fused.append((i, s, e))
+def _fuse_table(windows: List[Window], T: int, overlap: int, name: str) -> StrideTable:
+    """The one builder of fuse tables: `windows` in plan order, window i at index i.  A window that repeats an earlier one (the
+    planner's repeated tail, a strided plan's padding) is still DENOISED by its rank, so that all ranks make the same number of
+    UNet calls and the sharded parameters' gathers stay in lockstep, but it is left out of the fuse; a ring plan has no such
+    window, and every ring window given enters the fuse.  Raw weights `fuse_weights(L, overlap)[f]` at frame `s + f * d` (mod T on
+    a ring), normalised in float64 PER STRIDE over the fused windows of that stride that hold the frame (every frame must be in
+    one), times `1 / strides` in float64 where there is more than one stride, rounded to fp32 once: exactly 1.0 where one window
+    covers a frame, and every stride has the same share of every frame's noise.  `ValueError`, under `name`: a window that
+    leaves the T frames, more than `ops.COFUSE_MAX_WINDOWS` fused windows, a frame in no window."""
+    fused = []                                                    # (index in the plan, s, L, d)
+    for i, w in enumerate(windows):
+        s, L, d, ring = w
+        if not (d >= 1 and L >= 1 and 0 <= s < T and (L - 1) * d + (0 if ring else s) < T):   # a ring window may pass T, not lap itself
+            raise ValueError(f"{name}: window {i} = " + (f"[{s}, {s + L})" if d == 1 else f"({s}, {L}, {d})")
+                             + (f" is no ring window of {T} frames" if ring else f" leaves the {T} frames"))
+        if ring or w not in windows[:i]:                          # a ring plan repeats none: what `loop_table` is given, it fuses
+            fused.append((i, s, L, d))
     if len(fused) > ops.COFUSE_MAX_WINDOWS:
-        raise ValueError(f"window_table: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
+        raise ValueError(f"{name}: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
     raw = np.zeros((len(fused), T), dtype=np.float64)
-    for k, (_, s, e) in enumerate(fused):
-        raw[k, s:e] = fuse_weights(e - s, chunk_plan.overlap)
-    total = raw.sum(axis=0)
-    if (total <= 0).any():
-        raise ValueError(f"window_table: frame {int(np.argmin(total > 0))} is in no window")
-    return WindowTable(tuple(fused), torch.from_numpy((raw / total).astype(np.float32)))
+    for k, (_, s, L, d) in enumerate(fused):
+        raw[k, (s + d * np.arange(L)) % T] = fuse_weights(L, overlap)     # only a ring window reaches T
+    strides = sorted({w[3] for w in fused}) or [1]
+    wn = np.zeros_like(raw)
+    for d in strides:
+        level = np.array([w[3] == d for w in fused], dtype=bool)
+        total = raw[level].sum(axis=0)
+        if (total <= 0).any():
+            raise ValueError(f"{name}: frame {int(np.argmin(total > 0))} is in no window" + (f" of stride {d}" if strides != [1] else ""))
+        wn[level] = raw[level] / total
+    if len(strides) > 1:
+        wn = wn * (1.0 / len(strides))
+    return StrideTable(tuple(fused), torch.from_numpy(wn.astype(np.float32)))
+
+
+def _flat_table(tab: StrideTable) -> WindowTable:
+    return WindowTable(tuple((i, s, s + L) for i, s, L, _ in tab.fused), tab.wn)
+
+
+def window_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
+    """`_fuse_table` of the plan's windows `[s, e)`; `rows()`: (offset, first frame, length)."""
+    return _flat_table(_fuse_table(plan_windows(chunk_plan), T, chunk_plan.overlap, "window_table"))
 
 
 # ---- ring windows (seamless looping; csrc/codenoise.hip, its RING flag) -----------------------------------------------------------------------------
@@ -131,23 +189,9 @@ def loop_plan_of(cfg, world: int) -> ChunkPlan:
 
 
 def loop_table(chunk_plan: ChunkPlan, T: int) -> WindowTable:
-    """`window_table` for a ring plan: `wn[k][t] = fuse_weights(size, ov)[(t - s_k) mod T]` where that index is `< size`, else 0,
-    normalised over the windows that hold `t` in float64, then rounded to fp32 once: exactly 1.0 where one window holds the
-    frame.  Every window enters the fuse (a ring plan repeats none); `rows()` is unchanged: (offset, first frame, length)."""
-    fused = []
-    for i, (s, e) in enumerate(chunk_plan.ranges):
-        if not (0 <= s < T and 1 <= e - s <= T):
-            raise ValueError(f"loop_table: window {i} = [{s}, {e}) is no ring window of {T} frames")
-        fused.append((i, s, e))
-    if len(fused) > ops.COFUSE_MAX_WINDOWS:
-        raise ValueError(f"loop_table: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
-    raw = np.zeros((len(fused), T), dtype=np.float64)
-    for k, (_, s, e) in enumerate(fused):
-        raw[k, (s + np.arange(e - s)) % T] = fuse_weights(e - s, chunk_plan.overlap)
-    total = raw.sum(axis=0)
-    if (total <= 0).any():
-        raise ValueError(f"loop_table: frame {int(np.argmin(total > 0))} is in no window")
-    return WindowTable(tuple(fused), torch.from_numpy((raw / total).astype(np.float32)))
+    """`window_table` for a ring plan: a range `(s, e)` means the frames `(s + f) mod T`, `0 <= s < T`, `1 <= e - s <= T` (a ring
+    plan repeats no window, so every one enters the fuse); `rows()` is unchanged: (offset, first frame, length)."""
+    return _flat_table(_fuse_table(plan_windows(chunk_plan, True), T, chunk_plan.overlap, "loop_table"))
 
 
 # ---- strided context windows (AnimateDiff-Evolved's `context_stride`; csrc/codenoise.hip, its `costride_tab`) -----------------------
@@ -213,47 +257,10 @@ def stride_plan_of(cfg, world: int) -> StridePlan:
     return stride_plan(cfg.num_frames, world, cfg.chunk_size, cfg.overlap, cfg.overlap_rule, cfg.context_stride, cfg.no_chunking)
 
 
-@dataclass(frozen=True)
-class StrideTable:
-    """`fused`: (index in the plan, s, L, d) of the windows that enter the fuse, in plan order; `wn`: fp32 (K, T), the normalised
-    weights, zero outside a window."""
-    fused: Tuple[Tuple[int, int, int, int], ...]
-    wn: torch.Tensor
-
-    def rows(self, world: int, per_rank: int, slot_elems: int) -> List[Tuple[int, int, int, int]]:
-        """(element offset, first frame, length, stride) per fused window in the packed buffer `[world][per_rank][slot]`."""
-        return [(((i % world) * per_rank + i // world) * slot_elems, s, L, d) for i, s, L, d in self.fused]
-
-
 def stride_table(sp: StridePlan, T: int) -> StrideTable:
-    """`window_table` for a strided plan.  A window that repeats an earlier one (the planner's repeated tail, the padding) is
-    denoised but left out of the fuse.  Raw weights `fuse_weights(L, ov)[f]` at frame `s + f * d`, normalised in float64 PER
-    LEVEL over the fused windows of that stride that hold the frame (every frame must be in one, else `ValueError`), times
-    `1 / levels` in float64 (levels = the number of distinct strides), rounded to fp32 once: every level has the share 1/levels of
-    every frame's noise.  With one level that is `window_table`'s table, bit for bit."""
-    seen, fused = set(), []
-    for i, (s, L, d) in enumerate(sp.windows):
-        if not (d >= 1 and L >= 1 and 0 <= s and s + (L - 1) * d < T):
-            raise ValueError(f"stride_table: window {i} = ({s}, {L}, {d}) leaves the {T} frames")
-        if (s, L, d) not in seen:
-            seen.add((s, L, d))
-            fused.append((i, s, L, d))
-    if len(fused) > ops.COFUSE_MAX_WINDOWS:
-        raise ValueError(f"stride_table: {len(fused)} windows, the fused step takes {ops.COFUSE_MAX_WINDOWS}")
-    strides = sorted({d for _, _, _, d in fused})
-    raw = np.zeros((len(fused), T), dtype=np.float64)
-    for k, (_, s, L, d) in enumerate(fused):
-        raw[k, s + d * np.arange(L)] = fuse_weights(L, sp.overlap)
-    wn = np.zeros_like(raw)
-    for d in strides:
-        level = np.array([w[3] == d for w in fused])
-        total = raw[level].sum(axis=0)
-        if (total <= 0).any():
-            raise ValueError(f"stride_table: frame {int(np.argmin(total > 0))} is in no window of stride {d}")
-        wn[level] = raw[level] / total
-    if len(strides) > 1:
-        wn = wn * (1.0 / len(strides))
-    return StrideTable(tuple(fused), torch.from_numpy(wn.astype(np.float32)))
+    """`_fuse_table` of a strided plan's windows `(s, L, d)`: every level has the share `1 / levels` of every frame's noise.  With
+    one level that is `window_table`'s table, bit for bit."""
+    return _fuse_table(plan_windows(sp), T, sp.overlap, "stride_table")
 
 
 # ---- spatial tiles (MultiDiffusion's original form; csrc/cotile.hip) ------------------------------------------------------------
@@ -327,53 +334,48 @@ def tile_plan(h: int, w: int, th: int, tw: int, oy: int, ox: int) -> TilePlan:
     return TilePlan(th, tw, oy, ox, tuple(ys), tuple(xs), axis_weights(h, th, oy, ys), axis_weights(w, tw, ox, xs))
 
 
+# kind of round -> (`ops`' input op, the range it takes of a `Window`, the scheduler's step method, the name in a table's errors)
+_KINDS = {"flat": ("cfg_input_window", lambda w: (w.s, w.s + w.L), "step_cfg_windows", "window_table"),
+          "tiles": ("cfg_input_tile", lambda w: (w.s, w.s + w.L), "step_cfg_tiles", "window_table"),
+          "ring": ("cfg_input_loop", lambda w: (w.s, w.L), "step_cfg_loop", "loop_table"),
+          "strided": ("cfg_input_stride", lambda w: (w.s, w.L, w.d), "step_cfg_strided", "stride_table")}
+
+
 def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[TilePlan] = None, strided: Optional[StridePlan] = None):
     """One co-denoised sampling round of `d` (a `DistributedVideoDiffuser`) from the whole clip's start latent -> (z.float(),
-    the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  Per step: this rank's windows go
-    through `ops.cfg_input_window` -> UNet into one packed buffer `[per_rank][2][C][cp.chunk][h][w]` (a window shorter than the
-    chunk fills the front of its slot; the rest is never read); with more than one rank, one `all_gather_into_tensor` of that
-    buffer; then every rank runs the fused step on its own copy of z (identical bits on every rank: no broadcast; with
-    `guidance_rescale` the step's statistic is taken over that same gathered buffer, so every rank gets the same r).  There is no
-    final blend, so the zeroed first and last frame of the reference's ramp blend does not occur.
-    `tiles` (a `TilePlan`, spatially tiled co-denoising): every window of this rank is run once per tile, through
-    `ops.cfg_input_tile` on the tile's crop of z (and of the whole frame's ctx), into `tiles.count` consecutive slots of the
-    packed buffer `[per_rank][ny nx][2][C][cp.chunk][th][tw]`; the step is `step_cfg_tiles`; the record gains `"tile"`.  The
-    ranks' shares, the repeated tail window and the one gather per step are as without it.
-    `cfg.loop` (ring windows; `cp` is then a `loop_plan`): the table is `loop_table`'s, a window's input comes from
-    `ops.cfg_input_loop` (frames `(s + f) mod T`), the step is `step_cfg_loop`, and the record gains `"loop"`: the windows as
-    [first frame, length]; everything else, the packed buffer and the mask step on the whole clip included, is as without it.
-    `strided` (a `StridePlan` of more than one level; `cp` is its level 0): the windows, their ranks and the slot (sized by the
-    longest window) are the strided plan's, the table is `stride_table`'s, a window's input comes from `ops.cfg_input_stride`
-    (frames `s + f * d`), the step is `step_cfg_strided`, and the record gains `"context_stride"`: the levels, their strides and
-    the fused windows as [s, L, d]; still one gather per step, and the mask step on the whole clip as without it.
-    `d.travel` (prompt travel, vdx/travel.py): every window is called with its own text, `d.window_text` of its (s, L, d, ring),
-    built once; every tile of a window shares the window's text; nothing else changes.
-    `d.regions` (regional prompts, vdx/region.py): every window's UNet call gains `d.region_kw` of its (s, L, d, ring)."""
+    the round's seconds and bytes under `info`'s names, the `info["co_denoise"]` record).  The plan is `strided` (a `StridePlan`
+    of more than one level) where given, else `cp`, a `loop_plan` with `cfg.loop`; a window is its `Window` (s, L, d, ring)
+    throughout, and `_KINDS` names the input op, the scheduler's method and the `_fuse_table` name of the four kinds.  Per step:
+    this rank's windows go through the input op -> UNet into one packed buffer `[per_rank][2][C][chunk][h][w]` (a window shorter
+    than the chunk, the plan's longest, fills the front of its slot; the rest is never read); with more than one rank, one
+    `all_gather_into_tensor` of that buffer; then every rank runs the fused step on its own copy of z (identical bits on every
+    rank: no broadcast; with `guidance_rescale` the step's statistic is taken over that same gathered buffer, so every rank gets
+    the same r), and the mask step on the whole clip.  There is no final blend, so the zeroed first and last frame of the
+    reference's ramp blend does not occur.
+    `tiles` (a `TilePlan`): every window is run once per tile, on the tile's crop of z (and of the whole frame's ctx), into
+    `tiles.count` consecutive slots of the packed buffer `[per_rank][ny nx][2][C][chunk][th][tw]`.
+    The record gains `"tile"`, `"loop"` (the fused windows as [s, L]) and `"context_stride"` (the levels, their strides and the
+    fused windows as [s, L, d]) with their options.
+    `d.travel` (prompt travel, vdx/travel.py): every window is called with its own text, `d.window_text` of it, built once; every
+    tile of a window shares it.  `d.regions` (regional prompts, vdx/region.py): a window's UNet call gains `d.region_kw` of it."""
     from .pipeline import emu_gather_delay_s
     cfg, sched = d.cfg, d.scheduler
     _, C, T, H, W = start.shape
-    loop = bool(cfg.loop)
-    if strided is not None:
-        cp = strided                                              # the same names: chunk, per_rank, for_rank
-        table = stride_table(strided, T)
-    else:
-        table = loop_table(cp, T) if loop else window_table(cp, T)
-    per, world, rank = cp.per_rank, d.world, d.rank
+    loop, plan, world = bool(cfg.loop), cp if strided is None else strided, d.world
+    kind = "strided" if strided is not None else "ring" if loop else "flat" if tiles is None else "tiles"
+    input_name, takes, step_name, table_name = _KINDS[kind]      # the window's UNet input and the step, decided once per round
+    table = _fuse_table(plan_windows(plan, loop), T, plan.overlap, table_name)
+    spans, chunk, per = rank_windows(plan, d.rank, loop)
     boxes = [()] if tiles is None else tiles.boxes                # (): the whole frame, as always
     nt = len(boxes)
     area = H * W if tiles is None else tiles.th * tiles.tw
-    slot = 2 * C * cp.chunk * area
+    slot = 2 * C * chunk * area
     rows = table.rows(world, per, nt * slot)
     wn = table.wn.to(start.device)
-    grid = None if tiles is None else tiles.grid(slot, start.device)
-    mine = cp.for_rank(rank)
-    if strided is not None:                                       # (s, L, d) -> the (s, e) the byte counts below read: e - s = L
-        mine, spans_strided = [(s, s + L) for s, L, _ in mine], mine
-    emb = torch.cat([d.uncond_emb, d.cond_emb], dim=0) if d.travel is None else None
     local = torch.zeros((per, nt * slot), dtype=torch.float16, device=start.device)
     packed = torch.zeros((world, per, nt * slot), dtype=torch.float16, device=start.device) if world > 1 else local
-    payload_step = sum((e - s) * C * 2 for s, e in mine)          # the reference's formula (:194), per exchange
-    actual_step = sum(2 * C * (e - s) * area * nt * 2 for s, e in mine)
+    payload_step = sum(w.L * C * 2 for w in spans)                # the reference's formula (:194), per exchange
+    actual_step = sum(2 * C * w.L * area * nt * 2 for w in spans)
     bytes_step = (world - 1) * per * nt * slot * 2
     z = start.clone()
     reset = getattr(sched, "reset", None)
@@ -381,40 +383,16 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
         reset()
     spent = {"denoise_s": 0.0, "emu_gather_delay_s": 0.0, "net_gather_s": 0.0, "network_bytes": 0, "payload_bytes": 0,
              "payload_bytes_actual": 0}
-    # the window's UNet input and the step, decided once per round: the op with the range it takes, the method with its leading arguments
-    if strided is not None:
-        input_op, spans = ops.cfg_input_stride, spans_strided
-        step, head, step_kw = sched.step_cfg_strided, (packed, rows, wn), {}
-    elif loop:
-        input_op, spans = ops.cfg_input_loop, [(s, e - s) for s, e in mine]
-        step, head, step_kw = sched.step_cfg_loop, (packed, rows, wn), {}
-    elif tiles is None:
-        input_op, spans = ops.cfg_input_window, mine
-        step, head, step_kw = sched.step_cfg_windows, (packed, rows, wn), d._rescale_kw
-    else:
-        input_op, spans = ops.cfg_input_tile, mine
-        step, head, step_kw = sched.step_cfg_tiles, (packed, rows, wn, grid), {}
+    input_op, ranges = getattr(ops, input_name), [takes(w) for w in spans]     # the op with the range it takes of a window
+    step, head = getattr(sched, step_name), (packed, rows, wn) if tiles is None else (packed, rows, wn, tiles.grid(slot, start.device))
+    step_kw = d._rescale_kw if kind == "flat" else {}             # the other kinds have no rescaled or thresholded form
     # prompt travel: every window has its own text (every tile of a window shares it), built once; else the one text of the job
-    if d.travel is None:
-        texts = [emb] * len(spans)
-    elif strided is not None:
-        texts = [d.window_text(s, L, dd) for s, L, dd in spans]
-    elif loop:
-        texts = [d.window_text(s, L, 1, True) for s, L in spans]
-    else:
-        texts = [d.window_text(s, e - s) for s, e in spans]
+    texts = [torch.cat([d.uncond_emb, d.cond_emb], dim=0)] * len(spans) if d.travel is None else [d.window_text(*w) for w in spans]
     # regional prompts: every window's UNet call gains the plan and the window's place in the clip ({} when off; never with tiles)
-    if getattr(d, "regions", None) is None:
-        region_kws = [{}] * len(spans)
-    elif strided is not None:
-        region_kws = [d.region_kw(s, L, dd) for s, L, dd in spans]
-    elif loop:
-        region_kws = [d.region_kw(s, L, 1, True) for s, L in spans]
-    else:
-        region_kws = [d.region_kw(s, e - s) for s, e in spans]
+    region_kws = [{}] * len(spans) if getattr(d, "regions", None) is None else [d.region_kw(*w) for w in spans]
     t_round = time.time()
     for i, t in enumerate(d.schedule):
-        for j, span in enumerate(spans):
+        for j, span in enumerate(ranges):
             for k, box in enumerate(boxes):
                 noise = d.unet(input_op(z, d.ctx, cfg.context_weight, *span, *box), t, encoder_hidden_states=texts[j], **region_kws[j]).sample
                 local[j, k * slot:k * slot + noise.numel()].copy_(noise.reshape(-1))
@@ -443,8 +421,7 @@ def co_denoise_round(d, start: torch.Tensor, cp: ChunkPlan, tiles: Optional[Tile
     if tiles is not None:
         rec["tile"] = tiles.record(len(table.fused))
     if loop:
-        rec["loop"] = {"windows": [[s, e - s] for _, s, e in table.fused]}
+        rec["loop"] = {"windows": [[s, L] for _, s, L, _ in table.fused]}
     if strided is not None:
-        rec["context_stride"] = {"levels": strided.levels, "strides": strided.strides,
-                                 "windows": [[s, L, dd] for _, s, L, dd in table.fused]}
+        rec["context_stride"] = {"levels": strided.levels, "strides": strided.strides, "windows": [list(w[1:]) for w in table.fused]}
     return z.float(), spent, rec

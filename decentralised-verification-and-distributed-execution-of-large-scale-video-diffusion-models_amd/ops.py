@@ -938,7 +938,8 @@ COFUSE_MAX_WINDOWS = 64
 def _cofuse_args(what, z, windows, table, wn, strided=False):
     """Shared checks of the two fused co-denoising steps -> the launch's leading arguments.  `table`: [(element offset into
     `windows`, first frame, length)] per window, host integers; the library checks every row against T and the buffer.
-    `strided`: a row has a fourth entry, the frame stride, which travels as a fourth host array after the lengths."""
+    `strided`: a row has a fourth entry, the frame stride, which travels as a fourth host array after the lengths; the other
+    launches have no place for one and refuse a row whose fourth entry is not 1."""
     if z.dim() != 5 or z.shape[0] != 1 or not z.is_contiguous():
         raise VdxError(f"{what}: z must be contiguous (1,C,T,H,W)")
     if not windows.is_contiguous():
@@ -952,60 +953,56 @@ def _cofuse_args(what, z, windows, table, wn, strided=False):
     off = (C.c_int64 * K)(*(int(r[0]) for r in table))
     st = (C.c_int32 * K)(*(int(r[1]) for r in table))
     ln = (C.c_int32 * K)(*(int(r[2]) for r in table))
-    sd = ((C.c_int32 * K)(*(int(r[3]) for r in table)),) if strided else ()
+    sd = ()
+    if strided:
+        sd = ((C.c_int32 * K)(*(int(r[3]) for r in table)),)
+    else:
+        for r in table:                                            # a plain loop: no generator's frame on a launch-bound path
+            if len(r) > 3 and r[3] != 1:
+                raise VdxError(f"{what}: a window row has a frame stride other than 1, which only the strided steps take")
     return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, *sd, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
 
 
-def _co_ddim_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, out, rescaled=None, strided=False, mimic_ws=None):
-    """The DDIM form of every whole-clip fused step, launched as `symbol`(head, out, extras, tail) and named in errors as the
-    wrapper, `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head (`strided`: with its fourth column), else
-    `_cotile_args`'; `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out); `mimic_ws`: the thresholded variants'
-    statistics workspace.  One call below the public wrapper and no closure: launch-bound."""
+def _co_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, history, out, rescaled=None, strided=False, mimic_ws=None):
+    """Every whole-clip fused step, launched as `symbol`(head, history, out, extras, tail) and named in errors as the wrapper,
+    `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head (`strided`: with its fourth column), else
+    `_cotile_args`'.  `history` None: the DDIM form -> out; else (x0_prev, x0_out), the DPM-Solver++ form through `_dpm_args` ->
+    (out, x0), as in `_one_step`.  `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out); `mimic_ws`: the
+    thresholded variants' statistics workspace.  One call below the public wrapper and no closure: launch-bound."""
     what = symbol[4:-4]
     head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
-    if out is None:
-        out = torch.empty_like(z)
-    elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
-        raise VdxError(f"{what}: out must be contiguous and shaped like z")
+    if history is None:
+        if out is None:
+            out = torch.empty_like(z)
+        elif tuple(out.shape) != tuple(z.shape) or not out.is_contiguous():
+            raise VdxError(f"{what}: out must be contiguous and shaped like z")
+        hist = ()
+        s1, sa, sp, s1p = (float(v) for v in coeffs)
+        c = (s1, sa, sp, s1p)
+    else:
+        x0_out, out, c = _dpm_args(what, z, history[0], history[1], out, coeffs)
+        hist = (_p(history[0], "x0_prev"), _p(x0_out, "x0_out"))
     bufs = phis = ()
     if rescaled is not None:
         _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
         bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
     elif mimic_ws is not None:
         bufs = (_mimic_ws(what, z.shape, z, mimic_ws)[1],)
-    s1, sa, sp, s1p = (float(c) for c in coeffs)
-    _launch(symbol, *head, _p(out, "out"), *bufs, float(guidance), *phis, s1, sa, sp, s1p, *tail)
-    return out
-
-
-def _co_dpm_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out, rescaled=None, strided=False,
-                 mimic_ws=None):
-    """The DPM-Solver++ form of the same, through `_dpm_args` -> (z', x0)."""
-    what = symbol[4:-4]
-    head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
-    x0_out, out, c = _dpm_args(what, z, x0_prev, x0_out, out, coeffs)
-    bufs = phis = ()
-    if rescaled is not None:
-        _, pp, sp_ = _rescale_buffers(what, cofuse_cfg_rescale_rows(tail[0], tail[1]), z, rescaled[1], rescaled[2])
-        bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
-    elif mimic_ws is not None:
-        bufs = (_mimic_ws(what, z.shape, z, mimic_ws)[1],)
-    _launch(symbol, *head, _p(x0_prev, "x0_prev"), _p(x0_out, "x0_out"), _p(out, "out"), *bufs, float(guidance), *phis,
-            *c, *tail)
-    return out, x0_out
+    _launch(symbol, *head, *hist, _p(out, "out"), *bufs, float(guidance), *phis, *c, *tail)
+    return out if history is None else (out, x0_out)
 
 
 def cofuse_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
     """One co-denoising DDIM step of the whole clip (include/vdx.h `vdx_cofuse_cfg_ddim_step_f16`): the windows' raw UNet
     outputs, each a contiguous (2,C,L_k,H,W) block at its `table` offset inside `windows`, are averaged per frame with `wn`
     and fed to `cfg_ddim_step`'s chain.  coeffs as for `cfg_ddim_step`; `out` may be `z`."""
-    return _co_ddim_step("vdx_cofuse_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out)
+    return _co_step("vdx_cofuse_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out)
 
 
 def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cofuse_cfg_dpm_step_f16`) -> (z', x0), both of the whole
     clip's shape.  coeffs, `x0_prev`, `x0_out` and `out` as for `cfg_dpm_step`."""
-    return _co_dpm_step("vdx_cofuse_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out)
+    return _co_step("vdx_cofuse_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1026,12 +1023,12 @@ def cfg_input_loop(z, ctx, weight, s: int, L: int, out=None):
 def coloop_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
     """`cofuse_cfg_ddim_step` over ring windows (include/vdx.h `vdx_coloop_cfg_ddim_step_f16`): a `table` row (offset, s, L)
     means the frames `(s + f) mod T`; the fuse, the chain, `coeffs` and `out` (which may be `z`) are the same."""
-    return _co_ddim_step("vdx_coloop_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out)
+    return _co_step("vdx_coloop_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out)
 
 
 def coloop_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """`cofuse_cfg_dpm_step` over ring windows (`vdx_coloop_cfg_dpm_step_f16`) -> (z', x0)."""
-    return _co_dpm_step("vdx_coloop_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out)
+    return _co_step("vdx_coloop_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1053,13 +1050,12 @@ def cfg_input_stride(z, ctx, weight, s: int, L: int, d: int, out=None):
 def costride_cfg_ddim_step(z, windows, table, wn, guidance, coeffs, out=None):
     """`cofuse_cfg_ddim_step` over strided windows (include/vdx.h `vdx_costride_cfg_ddim_step_f16`): a `table` row
     (offset, s, L, d) means the frames `s + f * d`; the fuse, the chain, `coeffs` and `out` (which may be `z`) are the same."""
-    return _co_ddim_step("vdx_costride_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out, strided=True)
+    return _co_step("vdx_costride_cfg_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out, strided=True)
 
 
 def costride_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """`cofuse_cfg_dpm_step` over strided windows (`vdx_costride_cfg_dpm_step_f16`) -> (z', x0)."""
-    return _co_dpm_step("vdx_costride_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
-                        strided=True)
+    return _co_step("vdx_costride_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out, strided=True)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1120,12 +1116,12 @@ def cotile_cfg_ddim_step(z, windows, table, wn, tiles: TileGrid, guidance, coeff
     `cofuse_cfg_ddim_step`, each time window's block now holding the `len(ys) * len(xs)` tiles' (2,C,L_k,th,tw) outputs at
     `tiles.stride` from one another; the noise is averaged per cell with `wn[kt][t] * wyn[ky][y] * wxn[kx][x]` and fed to
     `cfg_ddim_step`'s chain.  `out` may be `z`."""
-    return _co_ddim_step("vdx_cotile_cfg_ddim_step_f16", z, windows, table, wn, tiles, guidance, coeffs, out)
+    return _co_step("vdx_cotile_cfg_ddim_step_f16", z, windows, table, wn, tiles, guidance, coeffs, None, out)
 
 
 def cotile_cfg_dpm_step(z, windows, table, wn, tiles: TileGrid, guidance, coeffs, x0_prev=None, x0_out=None, out=None):
     """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cotile_cfg_dpm_step_f16`) -> (z', x0)."""
-    return _co_dpm_step("vdx_cotile_cfg_dpm_step_f16", z, windows, table, wn, tiles, guidance, coeffs, x0_prev, x0_out, out)
+    return _co_step("vdx_cotile_cfg_dpm_step_f16", z, windows, table, wn, tiles, guidance, coeffs, (x0_prev, x0_out), out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1205,15 +1201,15 @@ def cofuse_cfg_rescale_stats(z, windows, table, wn, guidance, partials=None):
 
 def cofuse_cfg_rescale_ddim_step(z, windows, table, wn, guidance, rescale, coeffs, partials, out=None, stats_out=None):
     """`cofuse_cfg_ddim_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_ddim_step_f16`)."""
-    return _co_ddim_step("vdx_cofuse_cfg_rescale_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out,
-                         (rescale, partials, stats_out))
+    return _co_step("vdx_cofuse_cfg_rescale_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out,
+                    (rescale, partials, stats_out))
 
 
 def cofuse_cfg_rescale_dpm_step(z, windows, table, wn, guidance, rescale, coeffs, partials, x0_prev=None, x0_out=None, out=None,
                                 stats_out=None):
     """`cofuse_cfg_dpm_step` with the rescaled guided noise (`vdx_cofuse_cfg_rescale_dpm_step_f16`) -> (z', x0)."""
-    return _co_dpm_step("vdx_cofuse_cfg_rescale_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
-                        (rescale, partials, stats_out))
+    return _co_step("vdx_cofuse_cfg_rescale_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out,
+                    (rescale, partials, stats_out))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1318,13 +1314,13 @@ def cofuse_cfg_mimic_stats(z, windows, table, wn, guidance, mimic, ws=None, stag
 
 def cofuse_cfg_mimic_ddim_step(z, windows, table, wn, guidance, coeffs, ws, out=None):
     """`cofuse_cfg_ddim_step` with the thresholded guided noise (`vdx_cofuse_cfg_mimic_ddim_step_f16`)."""
-    return _co_ddim_step("vdx_cofuse_cfg_mimic_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, out, mimic_ws=ws)
+    return _co_step("vdx_cofuse_cfg_mimic_ddim_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out, mimic_ws=ws)
 
 
 def cofuse_cfg_mimic_dpm_step(z, windows, table, wn, guidance, coeffs, ws, x0_prev=None, x0_out=None, out=None):
     """`cofuse_cfg_dpm_step` with the thresholded guided noise (`vdx_cofuse_cfg_mimic_dpm_step_f16`) -> (z', x0)."""
-    return _co_dpm_step("vdx_cofuse_cfg_mimic_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, x0_prev, x0_out, out,
-                        mimic_ws=ws)
+    return _co_step("vdx_cofuse_cfg_mimic_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out,
+                    mimic_ws=ws)
 
 
 # --------------------------------------------------------------------------------------------

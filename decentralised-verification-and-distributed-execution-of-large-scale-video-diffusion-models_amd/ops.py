@@ -424,6 +424,13 @@ def clip_band_span(y_bounds, band: int) -> int:
     return max(int(y_bounds[min(b + band, out) - 1].sum() - y_bounds[b, 0]) for b in range(0, out, band))
 
 
+def pillow_resizes_vertically_first(in_h: int, in_w: int, out_h: int) -> bool:
+    """`Image.resize` runs the vertical pass first, as a resize of its own, on an image more than 100 times taller than wide
+    whose height shrinks (PIL/Image.py); every other image gets the horizontal pass first.  The intermediate image is uint8
+    either way, so the two orders differ in the low bit of many pixels."""
+    return in_h > 100 * in_w and out_h < in_h
+
+
 _CLIP_TABLES: dict = {}   # (in_size, device) -> (bounds, coeffs) int32 device tensors, host-computed once per size
 
 
@@ -441,6 +448,10 @@ def clip_preprocess(frames, out=None, return_u8=False):
     fp16 [F*49][3072] of Resize((224, 224)) + ToTensor + Normalize(ImageNet).  `return_u8`: also the resized uint8
     (F, 224, 224, 3) image -> (rows, u8)."""
     F, H, W = check_u8_frames(frames, "clip_preprocess")
+    if pillow_resizes_vertically_first(H, W, CLIP_IMAGE):
+        # the kernel's order is horizontal, then vertical: hand it the vertical pass's (F, 224, W, 3) image, which its own
+        # vertical pass (224 -> 224: weights 2^22, 0) leaves as it is
+        frames, H = resize_u8(frames, CLIP_IMAGE, W, "bilinear"), CLIP_IMAGE
     dev = frames.device
     xb, xk, _ = _clip_table(W, dev)
     yb, yk, yb_host = _clip_table(H, dev)
@@ -1484,7 +1495,8 @@ def _resize_table(in_size: int, out_size: int, filter: str, device):
 def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     """uint8 RGB (F, Hi, Wi, 3) on the GPU -> (F, height, width, 3): `PIL.Image.resize((width, height))` bit for bit
     (default filter BICUBIC; 22-bit weights, horizontal pass then vertical, uint8 intermediate).  As in Pillow, a pass whose
-    size does not change is skipped (both unchanged: a copy)."""
+    size does not change is skipped (both unchanged: a copy), and a frame more than 100 times taller than wide whose height
+    shrinks gets the vertical pass first (`pillow_resizes_vertically_first`)."""
     F, Hi, Wi = check_u8_frames(frames, "resize_u8")
     if height <= 0 or width <= 0:
         raise VdxError(f"resize_u8: target {height}x{width}")
@@ -1493,6 +1505,11 @@ def resize_u8(frames, height: int, width: int, filter: str = "bicubic"):
     if Hi == height and Wi == width:
         return out.copy_(frames)
     src = frames
+    if Wi != width and pillow_resizes_vertically_first(Hi, Wi, height):
+        src = torch.empty((F, height, Wi, 3), dtype=torch.uint8, device=dev)
+        b, k = _resize_table(Hi, height, filter, dev)
+        _launch("vdx_resample_v_u8", *_u8_args(frames), F, Hi, Wi, b.data_ptr(), k.data_ptr(), k.shape[1], height, *_u8_args(src))
+        Hi = height
     if Wi != width:
         mid = out if Hi == height else torch.empty((F, Hi, width, 3), dtype=torch.uint8, device=dev)
         b, k = _resize_table(Wi, width, filter, dev)

@@ -3,50 +3,20 @@ libvdx_hip.so against the REAL dependencies: Pillow for Resize((224, 224)) and `
 (ViT-B/32 shapes, seeded weights) in fp32 on the CPU for the towers and the score."""
 import csv
 
-import numpy as np
 import pytest
 import torch
+
+from clip_stage_ref import frames_like_video, pil_resize, reference_pixels, unfold_patches
 
 pytestmark = pytest.mark.gpu
 transformers = pytest.importorskip("transformers")
 Image = pytest.importorskip("PIL.Image")
 
 SIZES = [(576, 1024), (320, 576), (72, 128), (100, 150), (224, 224)]
-MEAN = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1)
-STD = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
 
 
 def rel_l2(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-def frames_like_video(F, H, W, seed):
-    """Smooth colour fields + noise: natural-image-like statistics, every frame different."""
-    g = np.random.default_rng(seed)
-    yy, xx = np.meshgrid(np.linspace(0, 1, H), np.linspace(0, 1, W), indexing="ij")
-    out = []
-    for f in range(F):
-        a, b, c = g.uniform(0, 6.3, 3)
-        base = np.stack([np.sin(3 * xx + a + 0.2 * f), np.cos(4 * yy + b), np.sin(2 * (xx + yy) + c)], -1)
-        img = 127.5 + 90 * base + g.normal(0, 20, (H, W, 3))
-        out.append(np.clip(img, 0, 255).astype(np.uint8))
-    return np.stack(out)
-
-
-def pil_resize(frames):
-    return np.stack([np.asarray(Image.fromarray(f).resize((224, 224), Image.BILINEAR)) for f in frames])
-
-
-def reference_pixels(frames):
-    """The reference's transform (scoring.py:81-85) on torch-CPU: fp32 (F, 3, 224, 224)."""
-    u8 = torch.from_numpy(pil_resize(frames)).permute(0, 3, 1, 2)
-    return (u8.float() / 255 - MEAN) / STD
-
-
-def unfold_patches(px):
-    """(F, 3, 224, 224) -> the patch-GEMM rows [F*49][3072]: row f*49 + py*7 + px, column c*1024 + ky*32 + kx."""
-    F = px.shape[0]
-    return px.view(F, 3, 7, 32, 7, 32).permute(0, 2, 4, 1, 3, 5).reshape(F * 49, 3072)
 
 
 @pytest.fixture(scope="module")

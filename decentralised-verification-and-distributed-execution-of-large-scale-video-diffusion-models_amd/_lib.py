@@ -251,6 +251,16 @@ SIGNATURES = {
     "vdx_noise_f16": (_i, [_sz, _sz, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _f, _vp, _vp]),
     "vdx_noise_f32": (_i, [_sz, _sz, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _vp, _vp]),
     "vdx_noise_form": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    # stochastic sampling: the one-buffer and co-fused steps with the generator's draw inside (no reference counterpart;
+    # vdx/scheduler.py, csrc/dpm.hip, csrc/codenoise.hip, csrc/step_noise.h)
+    "vdx_cfg_ddim_eta_step_f16": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _sz, _sz, _i, _i, _i, _i, _i, _vp]),
+    "vdx_ddim_eta_step_f16": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _sz, _sz, _i, _i, _i, _i, _i, _vp]),
+    "vdx_cfg_sde_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _sz, _i, _i, _i, _i, _i, _vp]),
+    "vdx_sde_dpm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _sz, _sz, _i, _i, _i, _i, _i, _vp]),
+    "vdx_cofuse_cfg_ddim_eta_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _sz, _sz, _i, _i, _i,
+                                              _vp]),
+    "vdx_cofuse_cfg_sde_dpm_step_f16": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _sz,
+                                             _sz, _i, _i, _i, _vp]),
 }
 
 _lib = None

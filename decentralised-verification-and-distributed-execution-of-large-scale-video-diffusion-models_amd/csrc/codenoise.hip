@@ -46,6 +46,7 @@
 #include "vdx_common.h"
 #include "step_chains.h"
 #include "cofuse_common.h"   // the window table, the fuse, the step kernel and its launcher, the host checks
+#include "step_noise.h"      // the stochastic steps' noise policy
 
 template <bool RING, class Tab = cofuse_tab>
 static int cofuse_plain(const char* what, int mode, const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
@@ -58,6 +59,42 @@ static int cofuse_plain(const char* what, int mode, const void* z, const void* w
                               C, T, HW, tab, e, RING, win_stride))
         return rc;
     return cofuse_launch<RING>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp, cfg_guidance{}, C, T, HW, stream);
+}
+
+// the stochastic forms of the flat steps (dpm.hip states the coefficients): `cofuse_plain<false>` with the "philox" noise policy
+// of step_noise.h.  The sample is the clip, so an element's index is its logical one.
+static int cofuse_noise(const char* what, int mode, const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                        const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev, void* x0_out,
+                        void* lat_out, ddim_coef kd, dpm_coef kp, float c_n, size_t seed, size_t noise_stream, int C, int T, int HW,
+                        vdx_stream_t stream) {
+    cofuse_tab tab;
+    int e;
+    if (int rc = cofuse_check(what, mode, true, z, windows, windows_elems, win_off, win_start, win_len, K, wn, x0_prev, x0_out, lat_out,
+                              C, T, HW, tab, e))
+        return rc;
+    philox_noise nz;
+    if (int rc = philox_noise_of(what, seed, noise_stream, c_n, C, T, HW, 0, T, nz)) return rc;
+    return cofuse_launch<false>(what, mode, z, windows, tab, e, K, wn, x0_prev, x0_out, lat_out, kd, kp, cfg_guidance{}, C, T, HW, stream,
+                                nz);
+}
+
+extern "C" int vdx_cofuse_cfg_ddim_eta_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                                const int* win_start, const int* win_len, int K, const float* wn, void* lat_out,
+                                                float guidance, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float dir_coef,
+                                                float c_n, size_t seed, size_t noise_stream, int C, int T, int HW, vdx_stream_t stream) {
+    const ddim_coef kd = {guidance, sqrt_one_minus_at, 1.0f / sqrt_at, sqrt_aprev, dir_coef};
+    return cofuse_noise("vdx_cofuse_cfg_ddim_eta_step_f16", 0, z, windows, windows_elems, win_off, win_start, win_len, K, wn, nullptr,
+                        nullptr, lat_out, kd, dpm_coef{}, c_n, seed, noise_stream, C, T, HW, stream);
+}
+
+extern "C" int vdx_cofuse_cfg_sde_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                               const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                               void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x,
+                                               float c_d0, float c_d1, float c_inv_r0, float c_n, size_t seed, size_t noise_stream, int C,
+                                               int T, int HW, vdx_stream_t stream) {
+    const dpm_coef kp = {guidance, c_s0, c_inv_a0, c_x, c_d0, c_d1, c_inv_r0};
+    return cofuse_noise("vdx_cofuse_cfg_sde_dpm_step_f16", 1, z, windows, windows_elems, win_off, win_start, win_len, K, wn, x0_prev,
+                        x0_out, lat_out, ddim_coef{}, kp, c_n, seed, noise_stream, C, T, HW, stream);
 }
 
 extern "C" int vdx_cofuse_cfg_ddim_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,

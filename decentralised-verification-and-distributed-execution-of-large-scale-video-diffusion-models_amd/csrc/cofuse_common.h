@@ -121,10 +121,10 @@ struct cofuse_source {
 
 // ---- the step itself ---------------------------------------------------------------------------------------------------------------
 // Block map: a block works on ONE (c, t) line of h*w elements (tiles of 256 lanes x E elements): see codenoise.hip.
-template <int MODE, int E, bool RING, class G, class Tab = cofuse_tab>
+template <int MODE, int E, bool RING, class G, class Tab = cofuse_tab, class Z = no_noise>
 __global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f16* win, Tab tab, int K, const float* wn,
                                                           const f16* x0_prev, f16* x0_out, f16* out, ddim_coef kd, dpm_coef kp, G g,
-                                                          int C, int T, int HW, unsigned tiles_per_line) {
+                                                          int C, int T, int HW, unsigned tiles_per_line, Z nz) {
     const unsigned line = blockIdx.x / tiles_per_line, tile = blockIdx.x - line * tiles_per_line;
     const int c = (int)(line / (unsigned)T), t = (int)(line - (unsigned)c * (unsigned)T);
     const typename G::state st = g.prologue(c);                   // all 256 lanes, before any of them leaves
@@ -132,22 +132,23 @@ __global__ __launch_bounds__(256) void cofuse_step_kernel(const f16* z, const f1
     if (p >= HW) return;                                          // HW is a multiple of E: a lane's E elements are all inside
     f16 uf[E], cf[E];
     cofuse_uc<E, RING, Tab>(win, tab, K, wn, C, T, HW, c, t, p, uf, cf);   // uniform over the block: t is
-    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, st, kd, kp);
+    cofuse_tail<MODE, E>(z, x0_prev, x0_out, out, (size_t)line * HW + p, uf, cf, g, st, kd, kp, nz);
 }
 
-// the launch of a line-per-block step whose arguments `cofuse_check` has passed (it gave `tab` and `e`)
-template <bool RING, class G, class Tab>
+// the launch of a line-per-block step whose arguments `cofuse_check` has passed (it gave `tab` and `e`).  `nz`: the noise policy of
+// a stochastic step; the sample is the clip, so an element's index is its logical one and E stays (a lane's i is a multiple of E)
+template <bool RING, class G, class Tab, class Z = no_noise>
 static int cofuse_launch(const char* what, int mode, const void* z, const void* windows, const Tab& tab, int e, int K,
                          const float* wn, const void* x0_prev, void* x0_out, void* lat_out, ddim_coef kd, dpm_coef kp, G g, int C, int T,
-                         int HW, vdx_stream_t stream) {
+                         int HW, vdx_stream_t stream, Z nz = Z{}) {
     const size_t per_tile = 256 * (size_t)e;
     const size_t tiles_per_line = ((size_t)HW + per_tile - 1) / per_tile;
     const size_t blocks = tiles_per_line * C * T;
     VDX_CHECK(blocks <= 0x7fffffffull, "%s: %zu blocks exceed the grid", what, blocks);
     step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
-        hipLaunchKernelGGL((cofuse_step_kernel<decltype(m)::value, decltype(ee)::value, RING, G, Tab>), dim3((unsigned)blocks), dim3(256), 0,
+        hipLaunchKernelGGL((cofuse_step_kernel<decltype(m)::value, decltype(ee)::value, RING, G, Tab, Z>), dim3((unsigned)blocks), dim3(256), 0,
                            (hipStream_t)stream, (const f16*)z, (const f16*)windows, tab, K, wn, (const f16*)x0_prev, (f16*)x0_out,
-                           (f16*)lat_out, kd, kp, g, C, T, HW, (unsigned)tiles_per_line);
+                           (f16*)lat_out, kd, kp, g, C, T, HW, (unsigned)tiles_per_line, nz);
     });
     return vdx_launch_status(what);
 }

@@ -96,3 +96,10 @@ template <bool CFG, bool O2>
 __device__ __forceinline__ void dpm_elem(float u, float c, float x, float x0p, const dpm_coef& k, f16& x0_out, f16& out) {
     dpm_tail<O2>(CFG ? cfg_combine(u, c, k.gs) : (f16)u, x, x0p, k, x0_out, out);
 }
+
+// ---- the stochastic samplers' one extra link (DDIM with eta > 0; SDE-DPM-Solver++): after the tail, out = out + c_n * w ---------
+//   w: the step's N(0, 1) draw for this element (fp16), c_n: the host's fp32 scalar (DDIM: eta's std; SDE: st * sqrt(1 - exp(-2h)))
+__device__ __forceinline__ f16 noise_term(f16 out, f16 w, float c_n) {
+    const f16 n1 = rn16(__fmul_rn(c_n, (float)w));        // c_n * w
+    return rn16(__fadd_rn((float)out, (float)n1));
+}

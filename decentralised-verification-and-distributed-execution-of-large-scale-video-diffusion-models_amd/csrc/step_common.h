@@ -70,17 +70,32 @@ struct cfg_guidance {
     }
 };
 
+// ---- noise policies ----------------------------------------------------------------------------------------------------------------
+// What a stochastic sampler adds after the tail: `draws` false, nothing (every deterministic step: the policy is empty, no argument
+// is read and no branch taken); true (step_noise.h `philox_noise`): `draw<E>(i, w)` gives the N(0, 1) of the lane's E elements at
+// i, `c_n` their factor, and the tail ends in step_chains.h's `noise_term`.  `narrow(e)`: what the host takes off the access width.
+struct no_noise {
+    static constexpr bool draws = false;
+    void narrow(int&) const {}
+};
+
 // the tail of every step kernel: a lane's E elements at i, from their (u, c) to the stores
-template <int MODE, int E, class G>
+template <int MODE, int E, class G, class Z = no_noise>
 __device__ __forceinline__ void cofuse_tail(const f16* z, const f16* x0_prev, f16* x0_out, f16* out, size_t i, const f16 (&uf)[E],
                                             const f16 (&cf)[E], const G& g, const typename G::state& st, const ddim_coef& kd,
-                                            const dpm_coef& kp) {
+                                            const dpm_coef& kp, const Z& nz = Z{}) {
     f16 x[E], xp[E];
     load_halves<E>(z + i, x);
     if (MODE == 2) load_halves<E>(x0_prev + i, xp);
     f16 o[E], x0[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) g.template elem<MODE>((float)uf[j], (float)cf[j], (float)x[j], MODE == 2 ? (float)xp[j] : 0.f, st, kd, kp, x0[j], o[j]);
+    if constexpr (Z::draws) {
+        f16 w[E];
+        nz.template draw<E>(i, w);
+#pragma unroll
+        for (int j = 0; j < E; ++j) o[j] = noise_term(o[j], w[j], nz.c_n);
+    }
     if (MODE != 0) store_halves<E>(x0_out + i, x0);
     store_halves<E>(out + i, o);
 }
@@ -123,12 +138,12 @@ __device__ __forceinline__ void block_row(double (&a)[Q], double* row) {
 
 // THE one-buffer step kernel.  grid (x, nchan): block (x, y) takes the vectors of the elements [y * M, (y + 1) * M).  Every element is
 // read and written by one lane only, so `out` may be `lat`, and the result does not depend on the grid.
-template <int MODE, int E, class G>
+template <int MODE, int E, class G, class Z = no_noise>
 __global__ __launch_bounds__(256) void direct_step_kernel(direct_source<E, G::uses_c> src, const f16* lat, const f16* x0_prev, f16* x0_out,
-                                                          f16* out, ddim_coef kd, dpm_coef kp, G g) {
+                                                          f16* out, ddim_coef kd, dpm_coef kp, G g, Z nz) {
     const typename G::state st = g.prologue((int)blockIdx.y);     // all 256 lanes, before any of them leaves
     src.each(blockIdx.y, blockIdx.x, gridDim.x, [&](size_t i, const f16 (&uf)[E], const f16 (&cf)[E]) {
-        cofuse_tail<MODE, E>(lat, x0_prev, x0_out, out, i, uf, cf, g, st, kd, kp);
+        cofuse_tail<MODE, E>(lat, x0_prev, x0_out, out, i, uf, cf, g, st, kd, kp, nz);
     });
 }
 
@@ -189,11 +204,11 @@ static inline int cofuse_alias(const char* what, int mode, const void* z, const 
 // history), otherwise DPM-Solver++.  `extra`: the policy's buffers, which join eps as inputs of the aliasing check.  E is the widest
 // of 8, 4, 1 that divides M (and so n, where the conditional half starts); `lenient` (the two DDIM entries, which take any fp16
 // tensor): the widest that the pointers' alignment allows as well, else every pointer must be 16-byte aligned.  `cap`: the blocks a
-// channel gets at most; beyond it a lane strides.
-template <class G, size_t N>
+// channel gets at most; beyond it a lane strides.  `nz`: the noise policy (a stochastic step; it narrows E to what its map allows).
+template <class G, size_t N, class Z = no_noise>
 static int direct_launch(const char* what, int mode, bool lenient, const void* eps, const void* lat, const void* x0_prev, void* x0_out,
                          void* lat_out, const co_buf (&extra)[N], ddim_coef kd, dpm_coef kp, G g, unsigned nchan, size_t M, unsigned cap,
-                         vdx_stream_t stream) {
+                         vdx_stream_t stream, Z nz = Z{}) {
     const size_t n = (size_t)nchan * M, nb = n * sizeof(f16);
     VDX_CHECK(eps && lat && lat_out && n > 0 && (mode == 0 || x0_out), "%s: bad arguments", what);
     VDX_CHECK(n <= ((size_t)1 << 40), "%s: n too large", what);
@@ -206,14 +221,15 @@ static int direct_launch(const char* what, int mode, bool lenient, const void* e
         if (lenient) co_narrow(e, (long long)((uintptr_t)p / sizeof(f16)));
         else VDX_CHECK(((uintptr_t)p & 15) == 0, "%s: pointer not 16-byte aligned", what);
     }
+    nz.narrow(e);
     if (int rc = cofuse_alias(what, mode, lat, x0_prev, x0_out, lat_out, nb, inputs, "an input or lat_out", "an input or lat_out")) return rc;
     const size_t want = (M / e + 255) / 256;
     const dim3 grid((unsigned)(want < cap ? want : cap), nchan), block(256);
     step_dispatch(mode, x0_prev, e, [&](auto m, auto ee) {
         constexpr int E = decltype(ee)::value;
-        hipLaunchKernelGGL((direct_step_kernel<decltype(m)::value, E, G>), grid, block, 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((direct_step_kernel<decltype(m)::value, E, G, Z>), grid, block, 0, (hipStream_t)stream,
                            direct_source<E, G::uses_c>{(const f16*)eps, M, n}, (const f16*)lat, (const f16*)x0_prev, (f16*)x0_out,
-                           (f16*)lat_out, kd, kp, g);
+                           (f16*)lat_out, kd, kp, g, nz);
     });
     return vdx_launch_status(what);
 }

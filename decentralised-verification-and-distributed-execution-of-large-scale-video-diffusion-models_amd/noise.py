@@ -10,7 +10,8 @@ Streams of one seed, 64-bit:
     STREAM_BASE        0          the base noise (the start latent, `add_noise`'s and the masked job's re-noising)
     1 .. 2^32 - 1                 FreeInit's fresh noise of iteration k (`stream_of_iteration`)
     STREAM_POSTERIOR   2^32       the video-to-video posterior sample
-    STREAM_SAMPLER     2^33 ...   reserved for per-step sampler noise (no sampler here draws any yet)
+    STREAM_SAMPLER     2^33 ...   per-step sampler noise, drawn by the stochastic samplers (`DiffuserConfig.eta`: DDIM with eta > 0,
+                                  SDE-DPM-Solver++; vdx/scheduler.py `seed_noise`): 2^33 + round 2^16 + i (`stream_of_step`)
 """
 from __future__ import annotations
 
@@ -26,6 +27,8 @@ STREAM_BASE = 0
 STREAM_ITERATION_MAX = 2 ** 32 - 1
 STREAM_POSTERIOR = 2 ** 32
 STREAM_SAMPLER = 2 ** 33
+STREAM_STEP_MAX = 2 ** 16 - 1          # a step's index in its schedule
+STREAM_ROUND_MAX = 2 ** 30 - 1         # a sampling round (the FreeInit iteration less one)
 
 
 def check_seed(seed) -> int:
@@ -42,6 +45,16 @@ def stream_of_iteration(iteration: int) -> int:
     if isinstance(iteration, bool) or not isinstance(iteration, int) or not 1 <= iteration <= STREAM_ITERATION_MAX:
         raise ValueError(f"FreeInit iteration must be an integer in [1, {STREAM_ITERATION_MAX}], got {iteration!r}")
     return iteration
+
+
+def stream_of_step(round: int, i: int) -> int:
+    """The stream a stochastic sampler draws step `i` of sampling round `round` from: STREAM_SAMPLER + round 2^16 + i.  `i`: the
+    timestep's index in the scheduler's FULL schedule (a video-to-video run starts at its first timestep's index, not at 0);
+    `round`: the FreeInit iteration less one, 0 without FreeInit."""
+    for name, v, hi in (("round", round, STREAM_ROUND_MAX), ("step index", i, STREAM_STEP_MAX)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= hi:
+            raise ValueError(f"sampler noise: the {name} must be an integer in [0, {hi}], got {v!r}")
+    return STREAM_SAMPLER + round * 2 ** 16 + i
 
 
 def generator_of(cfg) -> Optional[int]:

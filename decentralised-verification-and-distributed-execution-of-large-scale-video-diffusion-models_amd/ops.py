@@ -839,12 +839,39 @@ def _eps2_like(what, eps2, lat):
         raise VdxError(f"{what}: tensors must be contiguous")
 
 
-def _one_step(symbol, eps, lat, guidance, coeffs, history, out, rescaled=None, mimic=None):
+def _step_noise(what, lat, noise, frames=None):
+    """The stochastic steps' trailing arguments (c_n, seed, stream, C, T, HW, s, L) from `noise` = (c_n, seed, stream) and the
+    sample's place in the clip: `frames` = (s, T), the sample (1,C,L,H,W) being the frames [s, s + L) of a clip of T; None: the
+    sample is the logical tensor itself (of any shape)."""
+    import math
+    c_n, seed, stream = noise
+    c_n = float(c_n)
+    if not math.isfinite(c_n):
+        raise VdxError(f"{what}: c_n must be finite, got {c_n!r}")
+    seed, stream = _noise_int(f"{what}: seed", seed, 0, 2 ** 64), _noise_int(f"{what}: stream", stream, 0, 2 ** 64)
+    if frames is None:
+        if lat.dim() == 5 and lat.shape[0] == 1:
+            _, Cc, L, H, W = lat.shape
+            return c_n, seed, stream, Cc, L, H * W, 0, L
+        if lat.numel() >= 2 ** 31:
+            raise VdxError(f"{what}: a sample that is not (1,C,T,H,W) must have fewer than 2^31 elements")
+        return c_n, seed, stream, 1, 1, lat.numel(), 0, 1
+    if lat.dim() != 5 or lat.shape[0] != 1:
+        raise VdxError(f"{what}: with frames the sample must be (1,C,L,H,W)")
+    _, Cc, L, H, W = lat.shape
+    s, T = (_noise_int(f"{what}: frames[{k}]", v, 0, 2 ** 31) for k, v in enumerate(frames))
+    if s + L > T:
+        raise VdxError(f"{what}: the frames [{s}, {s} + {L}) leave the clip of {T} frames")
+    return c_n, seed, stream, Cc, T, H * W, s, L
+
+
+def _one_step(symbol, eps, lat, guidance, coeffs, history, out, rescaled=None, mimic=None, noise=None):
     """Every one-buffer sampler step (csrc/step_common.h `direct_launch`), launched as `symbol`(eps, lat, history, out, buffers,
     scalars, coefficients, size) and named in errors as the wrapper, `symbol` without `vdx_` and `_f16`.  `guidance` None: the
     sampler alone on an eps shaped like lat, else eps = [u; c].  `history` None: the DDIM form -> out; else (x0_prev, x0_out), the
     DPM-Solver++ form through `_dpm_args` -> (out, x0).  `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out);
-    `mimic`: the thresholded variants' (workspace,).  One call below the public wrapper and no closure: launch-bound."""
+    `mimic`: the thresholded variants' (workspace,).  `noise`: the stochastic variants' `_step_noise` arguments, which stand where
+    the size stands.  One call below the public wrapper and no closure: launch-bound."""
     what = symbol[4:-4]
     if guidance is None:
         if tuple(eps.shape) != tuple(lat.shape) or not (eps.is_contiguous() and lat.is_contiguous()):
@@ -867,6 +894,8 @@ def _one_step(symbol, eps, lat, guidance, coeffs, history, out, rescaled=None, m
     elif mimic is not None:
         _, wp, size = _mimic_ws(what, lat.shape, lat, mimic[0])
         bufs = (wp,)
+    elif noise is not None:
+        size = noise
     _launch(symbol, _p(eps, "eps" if guidance is None else "eps2"), _p(lat, "lat"), *hist, _p(out, "out"), *bufs, *scal, *c, *size)
     return out if history is None else (out, x0_out)
 
@@ -891,6 +920,32 @@ def cfg_dpm_step(eps2, lat, guidance, coeffs, x0_prev=None, x0_out=None, out=Non
 def dpm_step(eps, lat, coeffs, x0_prev=None, x0_out=None, out=None):
     """`scheduler.step(eps, t, lat)` of the DPM-Solver++ scheduler without the CFG combine -> (lat', x0)."""
     return _one_step("vdx_dpm_step_f16", eps, lat, None, coeffs, (x0_prev, x0_out), out)
+
+
+# the stochastic forms (include/vdx.h "Stochastic sampling"; csrc/step_noise.h; tests/sde_ref.py): `noise` = (c_n, seed, stream), the
+# draw being `philox_normal`'s for the whole clip at the sample's place in it (`frames` = (s, T); None: the sample is the clip)
+def cfg_ddim_eta_step(eps2, lat, guidance, coeffs, noise, frames=None, out=None):
+    """`cfg_ddim_step` with eta > 0: coeffs = (sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-std^2)), then + c_n * w."""
+    return _one_step("vdx_cfg_ddim_eta_step_f16", eps2, lat, guidance, coeffs, None, out,
+                     noise=_step_noise("cfg_ddim_eta_step", lat, noise, frames))
+
+
+def ddim_eta_step(eps, lat, coeffs, noise, frames=None, out=None):
+    """`ddim_step` with eta > 0 (`DDIMScheduler.step(eta=)`), without the CFG combine."""
+    return _one_step("vdx_ddim_eta_step_f16", eps, lat, None, coeffs, None, out, noise=_step_noise("ddim_eta_step", lat, noise, frames))
+
+
+def cfg_sde_dpm_step(eps2, lat, guidance, coeffs, noise, frames=None, x0_prev=None, x0_out=None, out=None):
+    """`cfg_dpm_step` of SDE-DPM-Solver++: coeffs = (s0, 1/a0, (st/s0)*exp(-h), at*(1-exp(-2h)), half of that, 1/r0), then
+    + c_n * w -> (lat', x0)."""
+    return _one_step("vdx_cfg_sde_dpm_step_f16", eps2, lat, guidance, coeffs, (x0_prev, x0_out), out,
+                     noise=_step_noise("cfg_sde_dpm_step", lat, noise, frames))
+
+
+def sde_dpm_step(eps, lat, coeffs, noise, frames=None, x0_prev=None, x0_out=None, out=None):
+    """`dpm_step` of SDE-DPM-Solver++, without the CFG combine -> (lat', x0)."""
+    return _one_step("vdx_sde_dpm_step_f16", eps, lat, None, coeffs, (x0_prev, x0_out), out,
+                     noise=_step_noise("sde_dpm_step", lat, noise, frames))
 
 
 def blend_accumulate(full, weight, chunk, w, s, e):
@@ -974,12 +1029,14 @@ def _cofuse_args(what, z, windows, table, wn, strided=False):
     return (_p(z, "z"), _p(windows, "windows"), windows.numel(), off, st, ln, *sd, K, _p(wn, "wn", torch.float32)), (Cc, T, H * W)
 
 
-def _co_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, history, out, rescaled=None, strided=False, mimic_ws=None):
+def _co_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, history, out, rescaled=None, strided=False, mimic_ws=None,
+             noise=None):
     """Every whole-clip fused step, launched as `symbol`(head, history, out, extras, tail) and named in errors as the wrapper,
     `symbol` without `vdx_` and `_f16`: `tiles` None for `_cofuse_args`' head (`strided`: with its fourth column), else
     `_cotile_args`'.  `history` None: the DDIM form -> out; else (x0_prev, x0_out), the DPM-Solver++ form through `_dpm_args` ->
     (out, x0), as in `_one_step`.  `rescaled`: the rescale variants' ((phi, 1 - phi), partials, stats_out); `mimic_ws`: the
-    thresholded variants' statistics workspace.  One call below the public wrapper and no closure: launch-bound."""
+    thresholded variants' statistics workspace; `noise`: the stochastic variants' (c_n, seed, stream), after the coefficients.  One
+    call below the public wrapper and no closure: launch-bound."""
     what = symbol[4:-4]
     head, tail = _cofuse_args(what, z, windows, table, wn, strided) if tiles is None else _cotile_args(what, z, windows, table, wn, tiles)
     if history is None:
@@ -999,6 +1056,8 @@ def _co_step(symbol, z, windows, table, wn, tiles, guidance, coeffs, history, ou
         bufs, phis = (pp, sp_), tuple(float(v) for v in rescaled[0])
     elif mimic_ws is not None:
         bufs = (_mimic_ws(what, z.shape, z, mimic_ws)[1],)
+    elif noise is not None:
+        c = c + _step_noise(what, z, noise)[:3]
     _launch(symbol, *head, *hist, _p(out, "out"), *bufs, float(guidance), *phis, *c, *tail)
     return out if history is None else (out, x0_out)
 
@@ -1014,6 +1073,18 @@ def cofuse_cfg_dpm_step(z, windows, table, wn, guidance, coeffs, x0_prev=None, x
     """The same fused noise into `cfg_dpm_step`'s chain (`vdx_cofuse_cfg_dpm_step_f16`) -> (z', x0), both of the whole
     clip's shape.  coeffs, `x0_prev`, `x0_out` and `out` as for `cfg_dpm_step`."""
     return _co_step("vdx_cofuse_cfg_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out)
+
+
+def cofuse_cfg_ddim_eta_step(z, windows, table, wn, guidance, coeffs, noise, out=None):
+    """`cofuse_cfg_ddim_step` with eta > 0 (`vdx_cofuse_cfg_ddim_eta_step_f16`): coeffs and `noise` as for `cfg_ddim_eta_step`; the
+    sample is the clip."""
+    return _co_step("vdx_cofuse_cfg_ddim_eta_step_f16", z, windows, table, wn, None, guidance, coeffs, None, out, noise=noise)
+
+
+def cofuse_cfg_sde_dpm_step(z, windows, table, wn, guidance, coeffs, noise, x0_prev=None, x0_out=None, out=None):
+    """`cofuse_cfg_dpm_step` of SDE-DPM-Solver++ (`vdx_cofuse_cfg_sde_dpm_step_f16`) -> (z', x0); coeffs and `noise` as for
+    `cfg_sde_dpm_step`."""
+    return _co_step("vdx_cofuse_cfg_sde_dpm_step_f16", z, windows, table, wn, None, guidance, coeffs, (x0_prev, x0_out), out, noise=noise)
 
 
 # --------------------------------------------------------------------------------------------

@@ -160,6 +160,41 @@ def check_noise(cfg) -> Optional[dict]:
     return _noise.record(0 if seed is None else seed)
 
 
+SDE_SCHEDULER = "dpmpp_2m_sde"
+
+
+def check_eta(cfg) -> Optional[dict]:
+    """`cfg.eta` / `cfg.scheduler` as {"eta", "algorithm"} (None for a deterministic job, as always); `ValueError` before any work
+    unless eta is a finite number in [0, 1]; with the scheduler "dpmpp_2m_sde" (SDE-DPM-Solver++, which has no partial form) unless
+    it is 0 or 1, and it is recorded as 1; with "dpmpp_2m" unless it is 0.  A stochastic job (DDIM with eta > 0, "dpmpp_2m_sde")
+    draws every step's noise from the portable generator, so it needs `noise="philox"` (`--seed`): the torch stream has no
+    per-step form (its draw depends on the device, the rank and the chunk).  Refused with `guidance_rescale`, `cfg_mimic`, `tile`,
+    `loop` and `context_stride` > 1, whose steps have no noise form yet."""
+    import math
+    eta, sched = getattr(cfg, "eta", 0.0), getattr(cfg, "scheduler", "ddim")
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not math.isfinite(eta) or not 0 <= eta <= 1:
+        raise ValueError(f"eta must be a finite number in [0, 1], got {eta!r}")
+    if sched == SDE_SCHEDULER:
+        if eta not in (0, 1):
+            raise ValueError(f"scheduler {SDE_SCHEDULER!r} has no partial form: eta must be 0 or 1 (it runs as 1), got {eta!r}")
+        rec = {"eta": 1.0, "algorithm": "sde-dpmsolver++"}
+    elif eta == 0:
+        return None
+    elif sched != "ddim":
+        raise ValueError(f"eta {eta!r} goes with scheduler \"ddim\" or {SDE_SCHEDULER!r}: {sched!r} is deterministic")
+    else:
+        rec = {"eta": float(eta), "algorithm": "ddim"}
+    if getattr(cfg, "noise", "torch") != "philox":
+        raise ValueError("a stochastic sampler (eta > 0, dpmpp_2m_sde) needs noise=\"philox\" (--seed N selects it): the torch stream "
+                         "has no per-step form, its draw depends on the device, the rank and the chunk")
+    for on, name, form in ((cfg.guidance_rescale != 0, "guidance_rescale", "rescaled"), (cfg.cfg_mimic is not None, "cfg_mimic", "thresholded"),
+                           (cfg.tile is not None, "tile", "tiled"), (cfg.loop, "loop", "ring"),
+                           (cfg.context_stride != 1, "context_stride", "strided")):
+        if on:
+            raise ValueError(f"eta and {name} exclude each other: the stochastic step has no {form} noise form yet")
+    return rec
+
+
 def check_tome(cfg) -> Optional[dict]:
     """`cfg.tome` / `cfg.tome_seed` as {"ratio", "sx", "sy", "seed", "max_downsample"} (None when off); `ValueError` before any work
     for a ratio `enable_tome` refuses, or a seed without a ratio."""
@@ -375,6 +410,7 @@ class JobOptions:
     prompt_found: Optional[dict] = None                             # the chunked texts' record (`run_job` fills it in once they are encoded)
     cfg_mimic: Optional[dict] = None                                # dynamic thresholding: {"scale", "percentile"} (csrc/dynthresh.hip)
     noise: Optional[dict] = None                                    # the portable generator: {"generator", "seed"} (vdx/noise.py); None: torch's stream
+    sampler_noise: Optional[dict] = None                            # a stochastic sampler: {"eta", "algorithm"} (vdx/scheduler.py); None: deterministic
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -406,6 +442,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         syntax = check_prompt_syntax(cfg, job_texts(cfg, travel, regions))
         mimic = check_cfg_mimic(cfg)
         noise = check_noise(cfg)
+        sde = check_eta(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -419,12 +456,13 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         syntax = check_prompt_syntax(cfg)
         mimic = check_cfg_mimic(cfg)
         noise = check_noise(cfg)
+        sde = check_eta(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
-                      cfg_mimic=mimic, noise=noise)
+                      cfg_mimic=mimic, noise=noise, sampler_noise=sde)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -449,6 +487,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(prompt_record(opts))
     out.update(mimic_record(opts))
     out.update(noise_record(opts))
+    out.update(sampler_noise_record(opts))
     return out
 
 
@@ -518,6 +557,16 @@ def noise_record(src) -> dict:
     if src.noise is None:
         return {}
     return {"noise": dict(src.noise)}
+
+
+def sampler_noise_record(src) -> dict:
+    """`{"sampler_noise": {"eta", "algorithm"}}` beside `record_options`' entries, only when the job's sampler is stochastic (else
+    {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"sampler_noise": src["sampler_noise"]} if "sampler_noise" in src else {}
+    if src.sampler_noise is None:
+        return {}
+    return {"sampler_noise": dict(src.sampler_noise)}
 
 
 def record_options(res: dict) -> dict:

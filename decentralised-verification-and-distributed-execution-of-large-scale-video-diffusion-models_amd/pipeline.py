@@ -37,8 +37,8 @@ from . import ops
 from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
-from .options import JobOptions, check_cfg_mimic, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, travel_record, world_size
+from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
+from .options import info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -71,7 +71,7 @@ class DiffuserConfig:
     strength: float = 0.6
     posterior: str = "sample"              # "sample" | "mode" of the encoder's diagonal Gaussian
     gpu_flow: bool = False                 # flow_err (and MD-VQS' TC) from the HIP Farneback kernels instead of the host path
-    scheduler: str = "ddim"                # "ddim" | "dpmpp_2m" (DPM-Solver++ 2M, vdx/scheduler.py): the sampler `run_job` uses
+    scheduler: str = "ddim"                # "ddim" | "dpmpp_2m" (DPM-Solver++ 2M) | "dpmpp_2m_sde" (its SDE form; see `eta`): the sampler `run_job` uses
     interpolate: int = 1                   # N > 1: write (F-1) N + 1 motion-interpolated frames at fps N (vdx/interp.py); 1 = as always
     # FreeInit (vdx/freeinit.py; diffusers' enable_free_init, unpinned): sample, noise the blend back to t = 999 with the same
     # base noise, keep its low frequencies, take the high ones from fresh noise, sample again.  1 = one sampling pass, as always
@@ -155,6 +155,13 @@ class DiffuserConfig:
     # reference's `torch.manual_seed(0)` stream on the device, as always
     seed: Optional[int] = None
     noise: str = "torch"
+    # stochastic sampling (vdx/scheduler.py, csrc/step_noise.h; diffusers' `DDIMScheduler.step(eta=)` and
+    # `algorithm_type="sde-dpmsolver++"` / A1111's "DPM++ 2M SDE", restated in tests/sde_ref.py and unpinned): with "ddim", eta in
+    # (0, 1] adds eta times the DDPM posterior's noise at every step; the scheduler "dpmpp_2m_sde" is SDE-DPM-Solver++ 2M (eta 0 or
+    # 1 there, run and recorded as 1).  Every step's noise is drawn inside the step kernel from the portable generator, at the
+    # element's place in the whole clip, so overlapping windows and any number of ranks draw the same noise: needs `noise`
+    # "philox" (`--seed`).  Not with `guidance_rescale`, `cfg_mimic`, `tile`, `loop` or `context_stride` > 1.  0 = deterministic, as always
+    eta: float = 0.0
 
     @property
     def use_fsdp(self):
@@ -222,17 +229,25 @@ def iteration_noise(shape, iteration: int, device, noise_device=None, seed: Opti
     return torch.randn(*shape, generator=g, device=nd, dtype=torch.float32).to(device)
 
 
-SCHEDULERS = ("ddim", "dpmpp_2m")
+SCHEDULERS = ("ddim", "dpmpp_2m", "dpmpp_2m_sde")
 
 
 def make_scheduler(name: str, base):
     """The sampler `name` of `DiffuserConfig.scheduler` / `--scheduler`: "ddim" is `base` itself (the pipeline's scheduler,
-    untouched); "dpmpp_2m" is `DPMSolverMultistepScheduler.from_config(base.config)`, as Zeroscope's published recipe builds it."""
+    untouched); "dpmpp_2m" is `DPMSolverMultistepScheduler.from_config(base.config)`, as Zeroscope's published recipe builds it;
+    "dpmpp_2m_sde" the same with `algorithm_type="sde-dpmsolver++"`."""
     if name == "ddim":
         return base
+    if name == "dpmpp_2m_sde":
+        from .scheduler import DPMSolverMultistepScheduler
+        if isinstance(base, DPMSolverMultistepScheduler) and base.stochastic:
+            return base
+        return DPMSolverMultistepScheduler.from_config(base.config, algorithm_type="sde-dpmsolver++")
     if name == "dpmpp_2m":
         from .scheduler import DPMSolverMultistepScheduler
-        return base if isinstance(base, DPMSolverMultistepScheduler) else DPMSolverMultistepScheduler.from_config(base.config)
+        if isinstance(base, DPMSolverMultistepScheduler):
+            return base if not base.stochastic else DPMSolverMultistepScheduler.from_config(base.config, algorithm_type="dpmsolver++")
+        return DPMSolverMultistepScheduler.from_config(base.config)
     raise ValueError(f"unknown scheduler {name!r}: expected one of {SCHEDULERS}")
 
 
@@ -315,6 +330,17 @@ class DistributedVideoDiffuser:
         check_noise(cfg)
         self._seed = _noise.generator_of(cfg)                         # the portable generator's seed; None: torch's stream, as always
         self._seed_kw = {"seed": self._seed} if self._seed is not None else {}
+        self._sde = check_eta(cfg)                                    # a stochastic sampler's {"eta", "algorithm"}; None: deterministic, as always
+        if self._sde is not None:
+            if self._sde["algorithm"] == "ddim":
+                if not hasattr(scheduler, "eta") or getattr(scheduler, "_dpm", False):
+                    raise ValueError("eta > 0 with scheduler \"ddim\" needs a DDIMScheduler")
+                scheduler.eta = self._sde["eta"]
+            elif not getattr(scheduler, "stochastic", False):
+                raise ValueError("scheduler \"dpmpp_2m_sde\" needs an SDEDPMSolverMultistepScheduler")
+            scheduler.seed_noise(self._seed, 0)
+        elif getattr(scheduler, "eta", 0.0) != 0.0:
+            scheduler.eta = 0.0                                       # the pipeline's own scheduler, after a stochastic job
         check_freeu(cfg)
         check_tome(cfg)
         phi = check_guidance_rescale(cfg)
@@ -417,13 +443,19 @@ class DistributedVideoDiffuser:
 
     def denoise(self, lat: torch.Tensor, s: Optional[int] = None, text: Optional[torch.Tensor] = None, window=None) -> torch.Tensor:
         """Reference `_denoise` (:129-143) for one chunk.  `s` (masked video-to-video only, with a `latent_mask`): the chunk's
-        first frame in the clip; None: the masked path is off.  `text` (prompt travel): the chunk's `window_text`.  `window`
+        first frame in the clip; None: the masked path is off; a stochastic sampler needs it too (the chunk draws the clip's noise at
+        its frames).  `text` (prompt travel): the chunk's `window_text`.  `window`
         (regional prompts; required with them): the chunk's (s, L) in the clip."""
         if self.regions is not None and window is None:
             raise ValueError("denoise: with regions the chunk's window (s, L) in the clip must be given: the masks are per clip frame")
         region_kw = self.region_kw(*window) if window is not None else {}
         masked = s is not None and self.latent_mask is not None
         cfg, sched = self.cfg, self.scheduler
+        step_kw = self._rescale_kw
+        if self._sde is not None:
+            if s is None:
+                raise ValueError("denoise: a stochastic sampler needs the chunk's first frame s in the clip")
+            step_kw = {"frames": (int(s), cfg.num_frames)}            # never with rescale or mimic (`check_eta`)
         emb = torch.cat([self.uncond_emb, self.cond_emb], dim=0) if text is None else text
         lat = lat.contiguous()
         reset = getattr(sched, "reset", None)
@@ -432,7 +464,7 @@ class DistributedVideoDiffuser:
         for i, t in enumerate(self.schedule):
             x = ops.cfg_input(lat, self.ctx, cfg.context_weight)
             noise = self.unet(x, t, encoder_hidden_states=emb, **region_kw).sample
-            lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale, **self._rescale_kw)
+            lat = sched.step_cfg(noise, t, lat, cfg.guidance_scale, **step_kw)
             if masked:
                 self._mask_step(lat, i, s)
         return lat
@@ -488,7 +520,7 @@ class DistributedVideoDiffuser:
             return out, spent
         _, C, T, H, W = start.shape
         t0 = time.time()
-        masked = self.latent_mask is not None
+        masked = self.latent_mask is not None or self._sde is not None        # who needs the chunk's first frame: `denoise` tells them apart
         if self.regions is not None:        # regional prompts: every window with its place in the clip
             mine = [self.denoise(start[:, :, s:e].clone(), s if masked else None, None, (s, e - s)) for s, e in cp.for_rank(self.rank)]
         elif self.travel is None:           # the call as it always was
@@ -513,7 +545,7 @@ class DistributedVideoDiffuser:
             net_gather_s = time.time() - t0
             received = (self.world - 1) * cp.per_rank * C * cp.chunk * H * W * 2
             out = self.blend(chunks, start, cp.overlap)
-            if masked:              # the ramp blend zeroes the clip's first and last frame and re-weights overlaps: kept cells again
+            if self.latent_mask is not None:              # the ramp blend zeroes the clip's first and last frame and re-weights overlaps: kept cells again
                 ops.mask_paste_f32(out, self._x0, self.latent_mask)
         else:
             hp = HaloPlan(cp, T)
@@ -581,6 +613,8 @@ class DistributedVideoDiffuser:
             info["tome"] = tome
         try:
             for it in range(iters):
+                if self._sde is not None:                              # every round draws streams of its own
+                    self.scheduler.seed_noise(self._seed, it)
                 out, spent = self._round(start, cp, exchange, comm, co_recs, tiles, opts.stride_plan)
                 for k, v in spent.items():
                     info[k] += v
@@ -667,7 +701,11 @@ def build_arg_parser():
     p.add_argument("--strength", type=float, default=0.6, help="video-to-video: fraction of the schedule run (0, 1]")
     p.add_argument("--posterior", choices=["sample", "mode"], default="sample", help="video-to-video: encoder posterior")
     p.add_argument("--scheduler", choices=list(SCHEDULERS), default="ddim",
-                   help="sampler: ddim (the reference's, default) or dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality)")
+                   help="sampler: ddim (the reference's, default), dpmpp_2m (DPM-Solver++ 2M: fewer --steps for the same quality) or "
+                        "dpmpp_2m_sde (its stochastic form, SDE-DPM-Solver++ 2M; needs --seed)")
+    p.add_argument("--eta", type=float, default=0.0, metavar="E",
+                   help="stochastic sampling: with ddim, E in (0, 1] adds E times the posterior's noise at every step (needs --seed; "
+                        "0, the default: deterministic); dpmpp_2m_sde runs as 1")
     p.add_argument("--interpolate", type=int, default=1,
                    help="write N - 1 motion-interpolated frames between every two generated ones, at fps * N (1: none, the default)")
     p.add_argument("--free_init", type=int, default=1,
@@ -991,7 +1029,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1030,7 +1068,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1058,7 +1096,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

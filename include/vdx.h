@@ -1103,6 +1103,44 @@ int vdx_noise_f16(size_t seed, size_t stream, int ndim, const size_t* shape, con
                   void* out, vdx_stream_t stream_handle);
 int vdx_noise_f32(size_t seed, size_t stream, int ndim, const size_t* shape, const size_t* start, const size_t* extent, void* out,
                   vdx_stream_t stream_handle);
+/* Stochastic sampling: DDIM with eta > 0 (diffusers `DDIMScheduler.step(eta=)`) and SDE-DPM-Solver++ 2M (diffusers
+ * `algorithm_type="sde-dpmsolver++"`, A1111's "DPM++ 2M SDE"); restated and unpinned; no reference counterpart, opt-in:
+ * vdx/scheduler.py, `DiffuserConfig.eta`; csrc/dpm.hip, csrc/codenoise.hip, csrc/step_noise.h; restated in tests/sde_ref.py.
+ * Each entry is its deterministic sibling (the same kernel, chain, alignment and overlap rules: lat_out may be lat / z) run with
+ * other host coefficients, followed inside the same kernel by one more link:
+ *     lat' = fp16(lat' + fp16(c_n * w))
+ * w: what vdx_noise_f16 holds, with sigma 1, under `seed` and `noise_stream` for the LOGICAL tensor (1,C,T,h,w) of the whole clip
+ * at the element's place in the clip.  The one-buffer entries take a sample (1,C,L,h,w) that is the frames [s, s + L) of the clip
+ * (eps / eps2 shaped alike): two samples that share frames add the same noise to them.  The co-fused entries' sample is the clip.
+ *   DDIM, eta in (0, 1]:  std = eta * sqrt(((1-a_prev)/(1-a_t)) * (1 - a_t/a_prev));  dir_coef = sqrt(1 - a_prev - std^2) stands
+ *                         where the deterministic entry takes sqrt(1 - a_prev);  c_n = std
+ *   SDE-DPM-Solver++:     c_x = (st/s0)*exp(-h),  c_d0 = at*(1 - exp(-2h)),  c_d1 = 0.5*c_d0,  c_n = st*sqrt(1 - exp(-2h));
+ *                         x0_prev == NULL: first order.  (The last step, sigma 0, has c_n = 0: callers run the deterministic entry.)
+ * 16-byte accesses where L*HW, (T-L)*HW and s*HW are multiples of 8 (a lane then computes two Philox blocks), 8-byte for
+ * multiples of 4, else element-wise; the bits do not depend on the width.  One launch; no atomics, no state, no noise buffer.
+ * Refused: a c_n that is not finite, frames [s, s + L) that leave [0, T), a clip of 2^63 elements or more, and whatever the
+ * deterministic sibling refuses.  seed and noise_stream are 64-bit values passed as size_t.                                      */
+int vdx_cfg_ddim_eta_step_f16(const void* eps2, const void* lat, void* lat_out, float guidance, float sqrt_one_minus_at,
+                              float sqrt_at, float sqrt_aprev, float dir_coef, float c_n, size_t seed, size_t noise_stream, int C,
+                              int T, int HW, int s, int L, vdx_stream_t stream);
+int vdx_ddim_eta_step_f16(const void* eps, const void* lat, void* lat_out, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                          float dir_coef, float c_n, size_t seed, size_t noise_stream, int C, int T, int HW, int s, int L,
+                          vdx_stream_t stream);
+int vdx_cfg_sde_dpm_step_f16(const void* eps2, const void* lat, const void* x0_prev, void* x0_out, void* lat_out, float guidance,
+                             float c_s0, float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, float c_n, size_t seed,
+                             size_t noise_stream, int C, int T, int HW, int s, int L, vdx_stream_t stream);
+int vdx_sde_dpm_step_f16(const void* eps, const void* lat, const void* x0_prev, void* x0_out, void* lat_out, float c_s0,
+                         float c_inv_a0, float c_x, float c_d0, float c_d1, float c_inv_r0, float c_n, size_t seed,
+                         size_t noise_stream, int C, int T, int HW, int s, int L, vdx_stream_t stream);
+int vdx_cofuse_cfg_ddim_eta_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                     const int* win_start, const int* win_len, int K, const float* wn, void* lat_out, float guidance,
+                                     float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float dir_coef, float c_n, size_t seed,
+                                     size_t noise_stream, int C, int T, int HW, vdx_stream_t stream);
+int vdx_cofuse_cfg_sde_dpm_step_f16(const void* z, const void* windows, size_t windows_elems, const int64_t* win_off,
+                                    const int* win_start, const int* win_len, int K, const float* wn, const void* x0_prev,
+                                    void* x0_out, void* lat_out, float guidance, float c_s0, float c_inv_a0, float c_x, float c_d0,
+                                    float c_d1, float c_inv_r0, float c_n, size_t seed, size_t noise_stream, int C, int T, int HW,
+                                    vdx_stream_t stream);
 /* 1 when that box takes the fast form (a lane per Philox block, 8- or 16-byte stores), 0 for the general one (a lane per
  * output), -1 for a box the entries refuse.  The bits do not depend on the form.                                            */
 int vdx_noise_form(int ndim, const size_t* shape, const size_t* start, const size_t* extent);

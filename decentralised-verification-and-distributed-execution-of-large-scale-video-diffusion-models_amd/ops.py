@@ -269,11 +269,15 @@ def _gemm_name(g: GemmArgs) -> str:
 
 
 def gemm_kernel_name(M: int, N: int, K: int, mode: int, geglu: bool, variant: int = 0, single_source: bool = True,
-                     residual: bool = False, whole: bool = True, wset: bool = False) -> str:
+                     residual: bool = False, whole: bool = True, wset: bool = False, conv=None, tconv=None,
+                     pad_mode: int = 0, ksplit: int = 0, rows=None, wset_rows: int = 0) -> str:
     """Name of the instantiation vdx_gemm_f16 launches (as rocprofv3 prints it) for M rows (`whole`: the call covers
     the whole product — the weights-stationary kernels take no row ranges).  Host-only (no GPU): a call of this shape
     with placeholder pointers, which the library tests for null and never reads, and the smallest geometry its
-    validation accepts (one M x 1 picture, one one-frame clip), which the choice does not depend on."""
+    validation accepts (one M x 1 picture, one one-frame clip), which the choice does not depend on.
+    A call can also be spelled out as `gemm` takes it: `conv` = (n_img, h_in, w_in, h_out, w_out, stride, upsample) with
+    `pad_mode`, `tconv` = (frames, hw), a pinned `ksplit`, `rows` = (row_begin, row_end) of the M rows, `wset_rows`; the
+    library then validates that geometry and a call it refuses raises VdxError as `gemm` would."""
     g = GemmArgs()
     g.a = g.w = g.out = 1 << 20
     g.M, g.N, g.K, g.mode, g.ldo = M, N, K, mode, N
@@ -281,14 +285,22 @@ def gemm_kernel_name(M: int, N: int, K: int, mode: int, geglu: bool, variant: in
     g.epilogue = (EPI_GEGLU if geglu else 0) | ((variant & 15) << 8)
     if mode == CONV3X3:
         g.h_in, g.w_in, g.h_out, g.w_out, g.stride = M, 1, M, 1, 1
+        if conv is not None:
+            _, g.h_in, g.w_in, g.h_out, g.w_out, g.stride, ups = conv
+            g.upsample = int(ups)
+        g.pad_mode = int(pad_mode)
     elif mode == TCONV3:
-        g.frames, g.hw = 1, M
+        g.frames, g.hw = tconv if tconv is not None else (1, M)
     elif not single_source:             # a second source: 64 channels of the concat
         g.a2, g.c2, g.lda2, g.c1 = 1 << 20, 64, 64, K - 64
     if residual:
         g.residual, g.ldr = 1 << 20, N
-    if wset:
-        g.wset_rows, g.wset_bias = M, 1 << 20
+    if wset or wset_rows:
+        g.wset_rows, g.wset_bias = wset_rows or M, 1 << 20
+    if ksplit:
+        g.ksplit = ksplit
+    if rows is not None:
+        g.row_begin, g.row_end = rows
     if not whole:                       # rows [0, M) of a longer product
         g.row_end = M
         g.M = 2 * M

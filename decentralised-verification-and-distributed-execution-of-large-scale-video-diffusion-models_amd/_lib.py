@@ -209,6 +209,10 @@ SIGNATURES = {
     # FreeU's skip filter and backbone scale (no reference counterpart; unet3d.py enable_freeu, csrc/freeu.hip)
     "vdx_freeu_filter_f16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
     "vdx_freeu_scale_f16": (_i, [_vp, _i, _sz, _i, _f, _vp]),
+    # FreeNoise: window-fused temporal attention and the start noise's frame gather (no reference counterpart; unet3d.py
+    # enable_free_noise, vdx/freenoise.py, csrc/freenoise.hip)
+    "vdx_temporal_attn_windows_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "vdx_frame_gather_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     # token merging around the spatial self-attention (no reference counterpart; unet3d.py enable_tome, vdx/tome.py, csrc/tome.hip)
     "vdx_tome_match_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp]),
     "vdx_tome_select_lds": (_sz, [_i, _i]),

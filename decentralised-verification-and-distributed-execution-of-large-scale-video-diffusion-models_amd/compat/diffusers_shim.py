@@ -270,6 +270,18 @@ class DiffusionPipeline:
     def disable_tome(self):
         self.unet.disable_tome()
 
+    def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid", noise_type="shuffle_context"):
+        """diffusers' pipeline-level `enable_free_noise(context_length, context_stride, weighting_scheme, noise_type)`: the UNet's
+        switch (vdx/unet3d.py `enable_free_noise`).  This pipeline object samples nothing itself: the start noise is
+        rescheduled where it is drawn, in the job (`--free_noise`, vdx/freenoise.py `reschedule_index`), which restates
+        "shuffle_context"; any other `noise_type` is refused."""
+        if noise_type != "shuffle_context":
+            raise ValueError(f"enable_free_noise: noise_type must be \"shuffle_context\", got {noise_type!r}")
+        self.unet.enable_free_noise(context_length=context_length, context_stride=context_stride, weighting_scheme=weighting_scheme)
+
+    def disable_free_noise(self):
+        self.unet.disable_free_noise()
+
     # ------------------------------------------------------------------------------------------
     # LoRA adapters (diffusers' LoraLoaderMixin surface, unpinned; vdx/lora.py, csrc/lora.hip).  Adapters here are always fused:
     # a change of the active set re-obtains the component's base state dict from where `from_pretrained` got it, merges the

@@ -691,6 +691,51 @@ def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
     return out
 
 
+def temporal_attn_windows(qkv, wn, *, B, F, HW, heads, scale, L, S, out=None):
+    """FreeNoise's window-fused temporal attention (include/vdx.h `vdx_temporal_attn_windows_f16`, csrc/freenoise.hip):
+    `temporal_attn` restricted to sliding windows of L frames at stride S, the windows' outputs averaged per frame with the
+    weights `wn`, fp32 [n][L] on the device (`freenoise.window_weights`).  The library refuses what lies outside
+    2 <= L <= 32, 1 <= S <= L, L < F <= 128."""
+    r, c, ld = _rows(qkv, "qkv")
+    inner = heads * 64
+    M = B * F * HW
+    if r < M or c < 3 * inner:
+        raise VdxError("temporal_attn_windows: qkv too small")
+    L, S = int(L), int(S)
+    if 1 <= S <= L < F:                     # else the library's refusal: there is no window count to hold the table to
+        n = -(-(F - L) // S) + 1
+        if not torch.is_tensor(wn) or wn.device != qkv.device or not wn.is_contiguous() or tuple(wn.shape) != (n, L):
+            raise VdxError(f"temporal_attn_windows: wn must be a contiguous fp32 ({n}, {L}) tensor on {qkv.device}")
+    out, ldo = _out(out, M, inner, qkv, "temporal_attn_windows")
+    if out.data_ptr() == qkv.data_ptr():
+        raise VdxError("temporal_attn_windows: out may not alias qkv")
+    _launch("vdx_temporal_attn_windows_f16", _p(qkv, "qkv"), ld, _p(out, "out"), ldo, B, F, HW, heads, float(scale), L, S,
+            _p(wn, "wn", torch.float32))
+    return out
+
+
+def frame_gather(src, idx, out=None):
+    """FreeNoise's noise rescheduling (include/vdx.h `vdx_frame_gather_f16`): out[:, :, t] = src[:, :, idx[t]] for a contiguous
+    fp16 latent (1, C, T, h, w).  `idx`: T integers (a tensor on any device, or a sequence), every one checked here, on the
+    host, to lie in [0, T).  `out` may not overlap `src`."""
+    if src.dim() != 5 or src.shape[0] != 1 or not src.is_contiguous():
+        raise VdxError(f"frame_gather: expected a contiguous (1, C, T, h, w) latent, got {tuple(src.shape)}")
+    _, Cc, T, h, w = src.shape
+    host = torch.as_tensor(idx).detach().cpu()
+    if host.dim() != 1 or host.numel() != T or host.dtype.is_floating_point or host.dtype == torch.bool:
+        raise VdxError(f"frame_gather: idx must be {T} integers, got {host.dtype} {tuple(host.shape)}")
+    if T and (int(host.min()) < 0 or int(host.max()) >= T):
+        raise VdxError(f"frame_gather: idx must lie in [0, {T}), got [{int(host.min())}, {int(host.max())}]")
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.shape != src.shape or not out.is_contiguous():
+        raise VdxError(f"frame_gather: out must be a contiguous {tuple(src.shape)} tensor, got {tuple(out.shape)}")
+    dev_idx = host.to(torch.int32).to(src.device)
+    with torch.cuda.device(src.device):
+        _launch("vdx_frame_gather_f16", _p(src, "src"), _p(out, "out"), dev_idx.data_ptr(), Cc, T, h * w)
+    return out
+
+
 def temporal_attn_block2_supported(inner: int, F: int) -> bool:
     return bool(_lib.load().vdx_temporal_attn_block2_supported(inner, F))
 

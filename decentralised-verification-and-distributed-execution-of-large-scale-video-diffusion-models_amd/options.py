@@ -206,6 +206,50 @@ def check_tome(cfg) -> Optional[dict]:
     return check_params(cfg.tome, seed=cfg.tome_seed)
 
 
+def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
+    """`cfg.free_noise` / `cfg.free_noise_weighting` as {"context_length", "context_stride", "weighting", "windows"} (None when
+    off), `windows` being the windows of one chunk of the plan; `ValueError` before any work for values outside the kernel's
+    domain (`freenoise.check_params`), a weighting without the option, a plan whose chunk is no longer than the context
+    length (there is nothing to window) or longer than the kernel's 128 frames, and together with `init_video`, `mask` /
+    `keep_frames` (the start is a clip: there is no noise to reschedule), `free_init_iters` > 1 (its fresh noise has no
+    rescheduled form yet) or `co_denoise` (and so its whole family).  The option's refusals live here, as `cfg_mimic`'s do:
+    `RULES` lists the co-denoising family only.  Both exchanges and every mode whose chunk exceeds the context length are
+    served.  `world` None: the initialised group's, else 1."""
+    fn, weighting = getattr(cfg, "free_noise", None), getattr(cfg, "free_noise_weighting", "pyramid")
+    if fn is None:
+        if weighting != "pyramid":
+            raise ValueError(f"free_noise_weighting {weighting!r} needs free_noise")
+        return None
+    from .freenoise import MAX_FRAMES, check_params, window_starts
+    from .planner import plan
+    if not isinstance(fn, (tuple, list)) or len(fn) != 2:
+        raise ValueError(f"free_noise must be two integers (context_length, context_stride), got {fn!r}")
+    rec = check_params(fn[0], fn[1], weighting)
+    L = rec["context_length"]
+    try:
+        cp = plan(cfg.num_frames, world_size() if world is None else world, cfg.chunk_size, cfg.overlap, cfg.no_chunking, cfg.overlap_rule)
+    except PlannerError as err:
+        raise ValueError(f"free_noise: {err}") from None
+    chunk = min(cp.chunk, cfg.num_frames)
+    if chunk <= L:
+        raise ValueError(f"free_noise: the plan's chunk of {chunk} frames is no longer than context_length {L}: there is nothing to "
+                         "window; use --mode fsdp (the whole clip in one UNet call) or a larger --chunk_size")
+    if chunk > MAX_FRAMES:
+        raise ValueError(f"free_noise: the plan's chunk of {chunk} frames exceeds the {MAX_FRAMES} the windowed attention takes; use a "
+                         "smaller --chunk_size")
+    if cfg.init_video is not None:
+        raise ValueError("free_noise and init_video exclude each other: the start is a clip, there is no noise to reschedule")
+    if getattr(cfg, "mask", None) is not None or getattr(cfg, "keep_frames", None) is not None:
+        raise ValueError("free_noise and mask / keep_frames exclude each other: the start is a clip, there is no noise to reschedule")
+    if cfg.free_init_iters > 1:
+        raise ValueError("free_noise and free_init_iters > 1 exclude each other: FreeInit's fresh noise has no rescheduled form yet")
+    if cfg.co_denoise:
+        raise ValueError("free_noise and co_denoise exclude each other: co-denoising fuses whole-UNet windows, FreeNoise runs the UNet "
+                         "once over the clip")
+    rec["windows"] = len(window_starts(chunk, L, rec["context_stride"]))
+    return rec
+
+
 def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
     """`cfg.co_denoise`; `ValueError` before any work when it is asked for together with the halo exchange: every rank holds the
     whole latent at every step anyway, there are no owned segments to return."""
@@ -411,6 +455,7 @@ class JobOptions:
     cfg_mimic: Optional[dict] = None                                # dynamic thresholding: {"scale", "percentile"} (csrc/dynthresh.hip)
     noise: Optional[dict] = None                                    # the portable generator: {"generator", "seed"} (vdx/noise.py); None: torch's stream
     sampler_noise: Optional[dict] = None                            # a stochastic sampler: {"eta", "algorithm"} (vdx/scheduler.py); None: deterministic
+    free_noise: Optional[dict] = None                               # FreeNoise: {"context_length", "context_stride", "weighting", "windows"} (vdx/freenoise.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -443,6 +488,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         mimic = check_cfg_mimic(cfg)
         noise = check_noise(cfg)
         sde = check_eta(cfg)
+        free_noise = check_free_noise(cfg, exchange, world)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -457,12 +503,13 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         mimic = check_cfg_mimic(cfg)
         noise = check_noise(cfg)
         sde = check_eta(cfg)
+        free_noise = check_free_noise(cfg, exchange, world)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
-                      cfg_mimic=mimic, noise=noise, sampler_noise=sde)
+                      cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -488,6 +535,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(mimic_record(opts))
     out.update(noise_record(opts))
     out.update(sampler_noise_record(opts))
+    out.update(free_noise_record(opts))
     return out
 
 
@@ -567,6 +615,16 @@ def sampler_noise_record(src) -> dict:
     if src.sampler_noise is None:
         return {}
     return {"sampler_noise": dict(src.sampler_noise)}
+
+
+def free_noise_record(src) -> dict:
+    """`{"free_noise": {"context_length", "context_stride", "weighting", "windows"}}` beside `record_options`' entries, only when
+    the option is set (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"free_noise": src["free_noise"]} if "free_noise" in src else {}
+    if src.free_noise is None:
+        return {}
+    return {"free_noise": dict(src.free_noise)}
 
 
 def record_options(res: dict) -> dict:

@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import free_noise_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -162,6 +162,15 @@ class DiffuserConfig:
     # element's place in the whole clip, so overlapping windows and any number of ranks draw the same noise: needs `noise`
     # "philox" (`--seed`).  Not with `guidance_rescale`, `cfg_mimic`, `tile`, `loop` or `context_stride` > 1.  0 = deterministic, as always
     eta: float = 0.0
+    # FreeNoise (vdx/freenoise.py, csrc/freenoise.hip; Qiu et al. 2024 / diffusers' `enable_free_noise(context_length,
+    # context_stride, weighting_scheme, noise_type="shuffle_context")`, restated in tests/freenoise_ref.py and unpinned): (L, S).
+    # The UNet runs ONCE over every chunk longer than L frames; only its temporal attentions are restricted to sliding windows of
+    # L frames at stride S, a frame's output being the weighted mean of its windows' ("pyramid" | "flat"), and the start noise of
+    # the frames past the first window is a seeded shuffled repeat of the first window's.  2 <= L <= 32, 1 <= S <= L, the plan's
+    # chunk in (L, 128] (`--mode fsdp` or a large `--chunk_size`).  Not with `init_video`, `mask` / `keep_frames`,
+    # `free_init_iters` > 1 or `co_denoise`.  None = full attention over the chunk's frames, as always
+    free_noise: Optional[Tuple[int, int]] = None
+    free_noise_weighting: str = "pyramid"
 
     @property
     def use_fsdp(self):
@@ -575,12 +584,16 @@ class DistributedVideoDiffuser:
         opts = options or resolve(cfg, exchange, self.world)
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
-        iters, freeu, tome = opts.free_init_iters, opts.freeu, opts.tome
+        iters, freeu, tome, free_noise = opts.free_init_iters, opts.freeu, opts.tome, opts.free_noise
         tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
         if self._start is None:
             base = seeded_noise(self.latent_shape, self.scheduler.init_noise_sigma, cfg.device, cfg.noise_device, **self._seed_kw)
+            if free_noise is not None:      # FreeNoise: the frames past the first window repeat its noise, shuffled (never with a clip's start)
+                from .freenoise import reschedule_index
+                base = ops.frame_gather(base, reschedule_index(cfg.num_frames, free_noise["context_length"], free_noise["context_stride"],
+                                                               self._seed or 0))
         else:                       # video-to-video: the constructor noised the encoded clip with this same seeded noise
             base = self._start
         T = cfg.num_frames
@@ -611,6 +624,12 @@ class DistributedVideoDiffuser:
             tome0 = self.unet.tome
             self.unet.enable_tome(**tome)
             info["tome"] = tome
+        if free_noise is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            free_noise0 = self.unet.free_noise
+            self.unet.enable_free_noise(free_noise["context_length"], free_noise["context_stride"], free_noise["weighting"])
+            if cfg.use_ctx:                 # the context mean is the rescheduled start's, on every rank (the index is the seed's alone)
+                self.ctx = base.mean(dim=2, keepdim=True).contiguous()
         try:
             for it in range(iters):
                 if self._sde is not None:                              # every round draws streams of its own
@@ -636,6 +655,11 @@ class DistributedVideoDiffuser:
                 self.unet.enable_freeu(**freeu0) if freeu0 is not None else self.unet.disable_freeu()
             if tome is not None:
                 self.unet.enable_tome(**tome0) if tome0 is not None else self.unet.disable_tome()
+            if free_noise is not None:
+                if free_noise0 is not None:
+                    self.unet.enable_free_noise(free_noise0["context_length"], free_noise0["context_stride"], free_noise0["weighting"])
+                else:
+                    self.unet.disable_free_noise()
         if iters > 1:
             self.free_init_starts = starts
             info["free_init"] = rec
@@ -719,6 +743,12 @@ def build_arg_parser():
     p.add_argument("--tome", type=float, default=None, metavar="RATIO",
                    help="token merging around the level-0 spatial self-attentions: share of the tokens merged away, in (0, 0.75] (default: off)")
     p.add_argument("--tome_seed", type=int, default=None, help="token merging: draw the cells' destination offsets once from this seed")
+    p.add_argument("--free_noise", type=int, nargs=2, default=None, metavar=("L", "S"),
+                   help="FreeNoise: one UNet call per chunk longer than L frames, its temporal attentions in sliding windows of L frames "
+                        "at stride S, the start noise rescheduled (2 <= L <= 32, 1 <= S <= L; needs a chunk in (L, 128]: --mode fsdp or a "
+                        "large --chunk_size; default: off)")
+    p.add_argument("--free_noise_weighting", choices=["pyramid", "flat"], default="pyramid",
+                   help="with --free_noise: a window's weight in a frame, min(j + 1, L - j) (pyramid, the default) or 1 (flat)")
     p.add_argument("--co_denoise", action="store_true",
                    help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
     p.add_argument("--tile", type=int, nargs=2, default=None, metavar=("TH", "TW"),
@@ -775,6 +805,8 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.noise = "philox" if cfg.seed is not None else "torch"
     if cfg.freeu is not None:
         cfg.freeu = tuple(cfg.freeu)
+    if cfg.free_noise is not None:
+        cfg.free_noise = tuple(cfg.free_noise)
     if cfg.tile is not None:
         cfg.tile = tuple(cfg.tile)
     if cfg.tile_overlap is not None:
@@ -1029,7 +1061,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1068,7 +1100,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1096,7 +1128,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

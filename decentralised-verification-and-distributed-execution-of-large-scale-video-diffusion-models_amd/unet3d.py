@@ -106,6 +106,8 @@ class UNet3DConditionModel(nn.Module):
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
         self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
         self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
+        self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
+        self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
 
     # ------------------------------------------------------------------------------------------
     # FreeU (Si et al. 2023; diffusers' enable_freeu / disable_freeu, unpinned; csrc/freeu.hip)
@@ -176,6 +178,47 @@ class UNet3DConditionModel(nn.Module):
             part = partition(hh, ww, tm["ratio"], tm["sx"], tm["sy"], tm["seed"])
             plan = self._tome_tables[key] = (part.src_idx.to(device), part.dst_idx.to(device), part.r)
         return plan if plan[2] > 0 and plan[1].numel() > 0 else None
+
+    # ------------------------------------------------------------------------------------------
+    # FreeNoise (Qiu et al. 2024; diffusers' enable_free_noise, unpinned; vdx/freenoise.py, csrc/freenoise.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid"):
+        """diffusers' `enable_free_noise(context_length, context_stride, weighting_scheme)` for the temporal transformers: from
+        the next forward on, whenever a forward has F > context_length frames, both attentions of every temporal transformer
+        attend inside sliding windows of `context_length` frames at stride `context_stride` (the last window moved back to end
+        with the clip) and a frame's output is the weighted mean of its windows' (`ops.temporal_attn_windows`; "pyramid":
+        min(j + 1, L - j), "flat": 1).  Those forwards take the unfused temporal path at every level, K7 blobs or not.  A
+        forward with F <= context_length is one window: it runs as without the switch, launch for launch.  Convolutions,
+        spatial layers, FreeU and token merging are untouched.  Refused with `ValueError`, the state left as it was: what
+        `freenoise.check_params` refuses (2 <= context_length <= 32, 1 <= context_stride <= context_length)."""
+        from .freenoise import check_params
+        self._free_noise = check_params(context_length, context_stride, weighting_scheme)
+        return self
+
+    def disable_free_noise(self):
+        """diffusers' `disable_free_noise()`: the forward is again the one without FreeNoise, launch for launch."""
+        self._free_noise = None
+        self._free_noise_tables = {}
+        return self
+
+    @property
+    def free_noise(self) -> Optional[Dict[str, object]]:
+        """{"context_length", "context_stride", "weighting"} while FreeNoise is enabled, else None."""
+        return dict(self._free_noise) if self._free_noise is not None else None
+
+    def _free_noise_plan(self, F, device):
+        """(L, S, the weight table on `device`) for a forward of F frames, or None where the windows do not apply: disabled, or
+        one window holds the whole sequence."""
+        fn = self._free_noise
+        if fn is None or F <= fn["context_length"]:
+            return None
+        L, S, weighting = fn["context_length"], fn["context_stride"], fn["weighting"]
+        key = (F, L, S, weighting, str(device))
+        wn = self._free_noise_tables.get(key)
+        if wn is None:
+            from .freenoise import window_weights
+            wn = self._free_noise_tables[key] = window_weights(F, L, S, weighting).to(device).contiguous()
+        return L, S, wn
 
     # ------------------------------------------------------------------------------------------
     # weights
@@ -777,6 +820,9 @@ class UNet3DConditionModel(nn.Module):
         t = self._norm_proj_in(p, x, B, F * S, M, part=part)
         fused = self.fuse_temporal_attention and f"{b}.attn1.k7_qkv" in W and ops.temporal_attn_block_supported(t.shape[1], F)
         fused2 = self.fuse_temporal_attention and f"{b}.attn1.k7b" in W and ops.temporal_attn_block2_supported(t.shape[1], F)
+        windows = self._free_noise_plan(F, t.device)      # FreeNoise: (L, S, wn) when on and F > L; the fused kernels have no windowed form
+        if windows is not None:
+            fused = fused2 = False
         for a, nm in (("attn1", "norm1"), ("attn2", "norm2")):
             if fused2:     # K7, second design (inner 320)
                 t = ops.temporal_attn_block2(t, W[f"{b}.{a}.k7b"], B=B, F=F, HW=S)
@@ -788,7 +834,10 @@ class UNet3DConditionModel(nn.Module):
             ln = ops.layernorm(t, W[f"{b}.{nm}.weight"], W[f"{b}.{nm}.bias"], M=M)
             qkv = ops.gemm(ln, W[f"{b}.{a}.to_qkv.weight"], M=M)
             del ln
-            o = ops.temporal_attn(qkv, B=B, F=F, HW=S, heads=heads, scale=scale)
+            if windows is None:
+                o = ops.temporal_attn(qkv, B=B, F=F, HW=S, heads=heads, scale=scale)
+            else:
+                o = ops.temporal_attn_windows(qkv, windows[2], B=B, F=F, HW=S, heads=heads, scale=scale, L=windows[0], S=windows[1])
             del qkv
             t = ops.gemm(o, W[f"{b}.{a}.to_out.0.weight"], M=M, bias=W[f"{b}.{a}.to_out.0.bias"], residual=t)
             del o

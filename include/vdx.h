@@ -849,6 +849,27 @@ int vdx_freeu_filter_f16(const void* x, int ldx, const double* tw_h, const doubl
 int vdx_freeu_scale_f16(void* x, int ld, size_t rows, int C, float b, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FreeNoise (Qiu et al., "FreeNoise: Tuning-Free Longer Video Diffusion via Noise Rescheduling", ICLR 2024; diffusers'
+ * enable_free_noise(context_length, context_stride, weighting_scheme, noise_type), restated and unpinned; nothing in the
+ * reference: it makes a long clip from whole-UNet windows only; UNet3DConditionModel.enable_free_noise, the job's
+ * --free_noise, vdx/freenoise.py, csrc/freenoise.hip).  tests/freenoise_ref.py states both definitions.
+ * ------------------------------------------------------------------------------------------ */
+/* Window-fused temporal attention.  qkv, out, ldqkv, ldo, B, F, HW, heads, scale: as for vdx_temporal_attn_f16.  Windows
+ * i = 0 .. n-1 of L frames, n = ceil((F - L) / S) + 1, window i at s_i = min(i S, F - L) (stride S, the last one moved back to
+ * end with the clip).  Per (b, pixel, head):  O_i = softmax(scale Q_i K_i^T) V_i over window i's frames only, and
+ *   out[t] = fp16( sum_{i : s_i <= t < s_i + L} wn[i][t - s_i] O_i[t - s_i] )
+ * summed in fp32 over ascending i, every product and add rounded on its own, one rounding to fp16.  wn: fp32 [n][L] on the
+ * device, the per-frame normalised window weights (freenoise.window_weights).  Every q, k, v element is read from HBM once;
+ * no atomics: the same bits on every run and for any B and HW; NaN and inf stay inside their (pixel, head).
+ * 2 <= L <= 32, 1 <= S <= L, L < F <= 128, qkv 16-byte aligned.  One launch.                                                 */
+int vdx_temporal_attn_windows_f16(const void* qkv, int ldqkv, void* out, int ldo, int B, int F, int HW, int heads, float scale,
+                                  int L, int S, const float* wn, vdx_stream_t stream);
+/* The start noise's rescheduling: dst[c][t] = src[c][idx[t]] on a contiguous fp16 latent (1, C, T, h, w), HW = h w.  idx: int32
+ * [T] on the device, every entry in [0, T) (checked by the caller, on the host).  dst must not overlap src.  16-byte accesses
+ * where HW % 8 == 0 and both pointers are 16-byte aligned, 2-byte ones otherwise.  One launch.                               */
+int vdx_frame_gather_f16(const void* src, void* dst, const int32_t* idx, int C, int T, int HW, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Token merging (Bolya & Hoffman, "Token Merging for Stable Diffusion", CVPRW 2023; the tomesd package's
  * bipartite_soft_matching_random2d, unpinned) around a spatial self-attention, on rows [n_img][S][C] fp16 (nothing in the
  * reference; UNet3DConditionModel.enable_tome, the job's --tome, vdx/tome.py, csrc/tome.hip).  tests/tome_ref.py states the

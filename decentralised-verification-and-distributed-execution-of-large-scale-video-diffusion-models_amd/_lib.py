@@ -143,6 +143,8 @@ SIGNATURES = {
     "vdx_flow_remap_absdiff_u8": (_i, [_vp, _sz, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     # motion-compensated frame interpolation (no reference counterpart; vdx/interp.py, csrc/interp.hip)
     "vdx_interp_frames_u8": (_i, [_vp, _sz, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    # motion-compensated temporal filtering (no reference counterpart; vdx/deflicker.py, csrc/deflicker.hip)
+    "vdx_deflicker_u8": (_i, [_vp, _sz, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
     # full-reference clip comparison: SSE / SSIM / MS-SSIM (no reference counterpart; vdx/compare.py, csrc/compare.hip)
     "vdx_compare_tiles": (_i, [_i, _i]),
     "vdx_compare_ssim_scale_u8": (_i, [_vp, _sz, _i, _vp, _sz, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp, _vp]),

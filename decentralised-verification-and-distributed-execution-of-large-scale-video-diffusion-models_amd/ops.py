@@ -1927,6 +1927,33 @@ def interp_frames(frames, fab, fba, factor: int, out=None):
 
 
 # --------------------------------------------------------------------------------------------
+# Motion-compensated temporal filtering (no reference counterpart; include/vdx.h "temporal filtering"; csrc/deflicker.hip).
+# vdx/deflicker.py computes the flows and runs the passes.
+def deflicker_frames(frames, fab, fba, strength: float, sigma: float, loop: bool = False, out=None):
+    """One pass of the temporal filter: uint8 RGB frames (F, H, W, 3), F >= 1, and their flows fab (frame i -> i+1) and fba
+    (frame i+1 -> i), fp32 (F-1, H, W, 2) or with `loop` (F, H, W, 2), the last entry being the pair (F-1, 0), all on the GPU
+    -> uint8 (F, H, W, 3): every frame blended with its neighbours warped onto it, each weighted by its 3x3 patch distance
+    (tests/deflicker_ref.py states it).  `out` must not share memory with `frames`.  One launch (vdx_deflicker_u8)."""
+    F, H, W = check_u8_frames(frames, "deflicker_frames")
+    for name, v, ok in (("strength", strength, lambda v: 0 < v <= 1), ("sigma", sigma, lambda v: 0 < v < float("inf"))):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+            raise VdxError(f"deflicker_frames: {name} {v!r} is outside " + ("(0, 1]" if name == "strength" else "(0, inf)"))
+    n_flows = F if loop else F - 1
+    for name, fl in (("fab", fab), ("fba", fba)):
+        if fl.device != frames.device:
+            raise VdxError(f"deflicker_frames: {name} is on {fl.device}, the frames on {frames.device}")
+        _f32(fl, (n_flows, H, W, 2), "deflicker_frames", name)
+    if out is None:
+        out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=frames.device)
+    elif (not out.is_cuda or out.device != frames.device or out.dtype != torch.uint8 or tuple(out.shape) != (F, H, W, 3)
+          or not out.is_contiguous()):
+        raise VdxError(f"deflicker_frames: out must be contiguous uint8 {(F, H, W, 3)} on the frames' device")
+    _launch("vdx_deflicker_u8", *_u8_args(frames), fab.data_ptr() or None, fba.data_ptr() or None, F, H, W, int(bool(loop)),
+            float(strength), float(sigma), out.data_ptr(), out.stride(0))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Full-reference clip comparison: SSE / SSIM / MS-SSIM (no reference counterpart; include/vdx.h "comparison"; csrc/compare.hip).
 # vdx/compare.py drives these and turns the means into the metrics; planes between the scales are packed fp32 [n][H][W].
 COMPARE_TAPS, COMPARE_SCALES = 11, 5

@@ -250,6 +250,28 @@ def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = No
     return rec
 
 
+def check_deflicker(cfg) -> Optional[dict]:
+    """`cfg.deflicker` / `cfg.deflicker_passes` as {"strength", "sigma", "passes"} (None when off); `ValueError` before any work
+    unless `deflicker` is two numbers (strength in (0, 1], sigma finite and > 0, in grey levels), the passes are an integer in
+    1..4 (and 1 without the option), and the frame is of a size the flow takes (`flow.level_plan`).  The filter runs on the
+    decoded frames, after the sampler: it goes with every other option, so `RULES` has no row for it."""
+    df, passes = getattr(cfg, "deflicker", None), getattr(cfg, "deflicker_passes", 1)
+    if df is None:
+        if passes != 1:
+            raise ValueError(f"deflicker_passes {passes!r} needs deflicker")
+        return None
+    from ._lib import VdxError
+    from .deflicker import check_params, check_size
+    if not isinstance(df, (tuple, list)) or len(df) != 2:
+        raise ValueError(f"deflicker must be two numbers (strength, sigma), got {df!r}")
+    try:
+        rec = check_params(df[0], df[1], passes)
+        check_size(cfg.height, cfg.width)
+    except VdxError as err:
+        raise ValueError(str(err)) from None
+    return rec
+
+
 def check_co_denoise(cfg, exchange: str = "allgather") -> bool:
     """`cfg.co_denoise`; `ValueError` before any work when it is asked for together with the halo exchange: every rank holds the
     whole latent at every step anyway, there are no owned segments to return."""
@@ -456,6 +478,7 @@ class JobOptions:
     noise: Optional[dict] = None                                    # the portable generator: {"generator", "seed"} (vdx/noise.py); None: torch's stream
     sampler_noise: Optional[dict] = None                            # a stochastic sampler: {"eta", "algorithm"} (vdx/scheduler.py); None: deterministic
     free_noise: Optional[dict] = None                               # FreeNoise: {"context_length", "context_stride", "weighting", "windows"} (vdx/freenoise.py)
+    deflicker: Optional[dict] = None                                # temporal filter of the written frames: {"strength", "sigma", "passes"} (vdx/deflicker.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -489,6 +512,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         noise = check_noise(cfg)
         sde = check_eta(cfg)
         free_noise = check_free_noise(cfg, exchange, world)
+        deflicker = check_deflicker(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -504,12 +528,13 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         noise = check_noise(cfg)
         sde = check_eta(cfg)
         free_noise = check_free_noise(cfg, exchange, world)
+        deflicker = check_deflicker(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
-                      cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise)
+                      cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -536,6 +561,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(noise_record(opts))
     out.update(sampler_noise_record(opts))
     out.update(free_noise_record(opts))
+    out.update(deflicker_record(opts))
     return out
 
 
@@ -625,6 +651,16 @@ def free_noise_record(src) -> dict:
     if src.free_noise is None:
         return {}
     return {"free_noise": dict(src.free_noise)}
+
+
+def deflicker_record(src) -> dict:
+    """`{"deflicker": {"strength", "sigma", "passes"}}` beside `record_options`' entries, only when the option is set (else {}):
+    from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"deflicker": src["deflicker"]} if "deflicker" in src else {}
+    if src.deflicker is None:
+        return {}
+    return {"deflicker": dict(src.deflicker)}
 
 
 def record_options(res: dict) -> dict:

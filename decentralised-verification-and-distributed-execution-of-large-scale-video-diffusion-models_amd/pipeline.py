@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import free_noise_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import deflicker_record, free_noise_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -171,6 +171,14 @@ class DiffuserConfig:
     # `free_init_iters` > 1 or `co_denoise`.  None = full attention over the chunk's frames, as always
     free_noise: Optional[Tuple[int, int]] = None
     free_noise_weighting: str = "pyramid"
+    # motion-compensated temporal filtering of the written frames (vdx/deflicker.py, csrc/deflicker.hip; the project's own
+    # definition, restated in tests/deflicker_ref.py and unpinned): (strength, sigma).  Rank 0 blends every generated frame with
+    # its two neighbours warped onto it along the Farneback flows, at weight strength in (0, 1] times 1 / (1 + d / sigma^2), d the
+    # mean squared difference over the pixel's 3x3 patch (sigma in grey levels), `deflicker_passes` times (1..4), before
+    # `interpolate`; with `loop` the last and the first frame are neighbours.  The numbers and the scores stay those of the
+    # generated frames, as under `interpolate`.  Goes with every other option.  None = the frames are written as decoded, as always
+    deflicker: Optional[Tuple[float, float]] = None
+    deflicker_passes: int = 1
 
     @property
     def use_fsdp(self):
@@ -732,6 +740,13 @@ def build_arg_parser():
                         "0, the default: deterministic); dpmpp_2m_sde runs as 1")
     p.add_argument("--interpolate", type=int, default=1,
                    help="write N - 1 motion-interpolated frames between every two generated ones, at fps * N (1: none, the default)")
+    p.add_argument("--deflicker", type=float, default=None, metavar="STRENGTH",
+                   help="filter the written frames along their motion: each frame is blended with its two flow-warped neighbours at "
+                        "weight STRENGTH in (0, 1], before --interpolate (vdx/deflicker.py; default: off)")
+    p.add_argument("--deflicker_sigma", type=float, default=10.0, metavar="S",
+                   help="with --deflicker: a neighbour's weight falls to 1/2 where its 3x3 patch differs by S grey levels rms (default 10)")
+    p.add_argument("--deflicker_passes", type=int, default=1, metavar="N",
+                   help="with --deflicker: N passes in 1..4, each over the one before with the same flows (default 1)")
     p.add_argument("--free_init", type=int, default=1,
                    help="FreeInit: N sampling passes, the start of each re-initialised from the one before (1: none, the default)")
     p.add_argument("--free_init_method", choices=["butterworth", "gaussian", "ideal"], default="butterworth")
@@ -807,6 +822,8 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.freeu = tuple(cfg.freeu)
     if cfg.free_noise is not None:
         cfg.free_noise = tuple(cfg.free_noise)
+    if cfg.deflicker is not None:               # the flag is STRENGTH alone; the field is the pair
+        cfg.deflicker = (cfg.deflicker, a.deflicker_sigma)
     if cfg.tile is not None:
         cfg.tile = tuple(cfg.tile)
     if cfg.tile_overlap is not None:
@@ -1028,13 +1045,18 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
     frames_written = gif_info = None
     if d.rank == 0 and (out_video or out_gif):
         to_write, fps = frames, cfg.fps
+        if opts.deflicker is not None:
+            # like the interpolation below: after the metrics above and on a clip of its own, so `frames` (what the numbers and the
+            # scores are about) stays the generated clip; what is written is the filtered one, then interpolated
+            from .deflicker import filter_frames
+            to_write = filter_frames(frames, device=dev, **opts.deflicker, **({"loop": True} if loop else {}))
         if factor > 1:
             # after the metrics above, which are numbers about the generated frames; `frames` itself (what --clip_json and
             # --mdvqs_json score) stays as it is
             from .interp import interpolate_frames
-            to_write, fps = interpolate_frames(frames, factor, device=dev, **({"loop": True} if loop else {})), cfg.fps * factor
+            to_write, fps = interpolate_frames(to_write, factor, device=dev, **({"loop": True} if loop else {})), cfg.fps * factor
         if out_video:
-            host = factor > 1 and not gpu_video_write
+            host = (factor > 1 or opts.deflicker is not None) and not gpu_video_write
             metrics.write_video(list(to_write.cpu().numpy()) if host else to_write, out_video, fps, restart_rows=video_restart_rows,
                                 device=dev if gpu_video_write else None)
             frames_written = len(to_write)
@@ -1061,7 +1083,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1100,7 +1122,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1128,7 +1150,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -776,6 +776,24 @@ int vdx_interp_frames_u8(const void* frames, size_t frame_pitch, int row_pitch, 
                          int W, int N, void* out, size_t out_frame_pitch, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Motion-compensated temporal filtering (no reference counterpart: the reference writes the decoded frames as they are; the
+ * job's --deflicker, vdx/deflicker.py, csrc/deflicker.hip).  tests/deflicker_ref.py states the definition.
+ * ------------------------------------------------------------------------------------------ */
+/* frames: uint8 RGB [F] (pitches in bytes); fab / fba: fp32 [F-1+loop][H][W][2], the Farneback flows frame i -> i+1 and
+ * i+1 -> i (with `loop` entry F-1 is the pair (F-1, 0)); 8-byte aligned, NULL only for F == 1 without loop.  out: uint8 [F]
+ * frames of packed rows, out_frame_pitch >= 3*W*H bytes apart, overlapping no byte of `frames` (refused).  One pass, per frame
+ * t, neighbour n in (t-1, t+1) in that order (mod F with `loop`, else only those inside the clip) and pixel q:
+ *   Wn(q) = bilinear sample of frame n at q + f(q) clamped to the frame, f = fba[t-1] towards t-1 and fab[t] towards t+1;
+ *   en(q) = the sum over R, G, B of (I(q) - Wn(q))^2; dn(p) = (the sum of en over the 3x3 patch around p, row-major, border
+ *   replicate) / 27; wn = 1 / (1 + dn / (sigma*sigma)), 0 for a neighbour that does not exist;
+ *   out(p) = (I(p) + strength*(w- * W-(p) + w+ * W+(p))) / (1 + strength*(w- + w+)), then floor(out + 0.5) clamped to 0..255.
+ * fp32 without contraction; every gather index is clamped as an integer after the float was clamped (NaN -> 0, +inf -> the far
+ * edge), so no flow value reads outside the frames.  One launch, no atomics: the same bytes on every run and for any F; frame t
+ * depends on frames t-1, t, t+1 alone.  0 < strength <= 1, sigma finite and > 0, 1 <= F <= 65535.                          */
+int vdx_deflicker_u8(const void* frames, size_t frame_pitch, int row_pitch, const float* fab, const float* fba, int F, int H, int W,
+                     int loop, float strength, float sigma, void* out, size_t out_frame_pitch, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Full-reference comparison of two uint8 RGB clips of one shape: SSE (PSNR), SSIM, MS-SSIM (nothing in the reference: it never
  * holds two clips; vdx/compare.py, csrc/compare.hip).  tests/compare_ref.py states the definition: every R, G, B plane on its
  * own, the 11-tap Gaussian window (sigma 1.5) as a valid correlation, C1 = (0.01*255)^2, C2 = (0.03*255)^2, a 2x2 mean between

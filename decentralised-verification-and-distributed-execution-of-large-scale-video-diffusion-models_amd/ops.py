@@ -130,25 +130,49 @@ def groupnorm_linear_supported(C: int, N: int, rows_per_sample: int) -> bool:
     return C in (320, 640) and N % 32 == 0 and rows_per_sample % 64 == 0
 
 
-def groupnorm_linear(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sample, eps, partition_samples=0, out=None):
-    """Linear(GroupNorm(x)) without the normalised tensor (`norm` -> `proj_in` of the transformer blocks): the statistics
-    pass, then one weight matrix + fp32 bias per sample (`vdx_groupnorm_fold_linear_f16`), then the weights-stationary GEMM
-    on the raw rows with `wset_rows = rows_per_sample`."""
+def _gn_workspace(device, need: int, workspace):
+    """The statistics workspace of one GroupNorm launch: `workspace` (uint8, on the GPU, >= `need` bytes) or the pool's."""
+    if workspace is None:
+        return _scratch(_GN_WS, device, need, torch.uint8, 1 << 20)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise VdxError(f"groupnorm: workspace must be contiguous uint8 of at least {need} bytes")
+    _p(workspace, "workspace", torch.uint8)
+    return workspace
+
+
+def groupnorm_fold(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sample, eps, partition_samples=0, workspace=None):
+    """GroupNorm folded into the Linear that follows it (`vdx_groupnorm_fold_linear_f16`): the statistics pass, then one
+    weight matrix fp16 [n_samples * N][C] = fp16(w * scale) and one fp32 bias [n_samples][N] per sample
+    -> (w_s, b_s), what the weights-stationary GEMM takes as `w` and `wset_bias`."""
     r, Cc, ldx = _rows(x, "x")
-    M = n_samples * rows_per_sample
     N, K = w.shape
-    if r < M or K != Cc or gamma.numel() != Cc or beta.numel() != Cc:
-        raise VdxError(f"groupnorm_linear: x [{r}][{Cc}], w [{N}][{K}], gamma {gamma.numel()}: shapes do not match")
-    if not groupnorm_linear_supported(Cc, N, rows_per_sample) or not w.is_contiguous():
-        raise VdxError(f"groupnorm_linear: C={Cc}, N={N}, rows_per_sample={rows_per_sample} not supported")
+    if r < n_samples * rows_per_sample or K != Cc or gamma.numel() != Cc or beta.numel() != Cc:
+        raise VdxError(f"groupnorm_fold: x [{r}][{Cc}], w [{N}][{K}], gamma {gamma.numel()}: shapes do not match")
+    if not w.is_contiguous():
+        raise VdxError("groupnorm_fold: w must be contiguous [N][C]")
     need = _lib.load().vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
-    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
+    ws = _gn_workspace(x.device, need, workspace)
     w_s = torch.empty((n_samples * N, K), dtype=torch.float16, device=x.device)
     b_s = torch.empty((n_samples, N), dtype=torch.float32, device=x.device)
     _launch("vdx_groupnorm_fold_linear_f16", _p(x, "x"), Cc, ldx, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups,
             n_samples, rows_per_sample, ws.data_ptr(), partition_samples, _p(w, "w"), _p(bias, "bias"), N, w_s.data_ptr(),
             b_s.data_ptr())
-    return gemm(x, w_s, M=M, wset_rows=rows_per_sample, wset_bias=b_s, out=out)
+    return w_s, b_s
+
+
+def groupnorm_linear(x, gamma, beta, w, bias, *, groups, n_samples, rows_per_sample, eps, partition_samples=0, out=None):
+    """Linear(GroupNorm(x)) without the normalised tensor (`norm` -> `proj_in` of the transformer blocks): the statistics
+    pass, then one weight matrix + fp32 bias per sample (`groupnorm_fold`), then the weights-stationary GEMM on the raw
+    rows with `wset_rows = rows_per_sample`."""
+    r, Cc, _ = _rows(x, "x")
+    N, K = w.shape
+    if r < n_samples * rows_per_sample or K != Cc or gamma.numel() != Cc or beta.numel() != Cc:
+        raise VdxError(f"groupnorm_linear: x [{r}][{Cc}], w [{N}][{K}], gamma {gamma.numel()}: shapes do not match")
+    if not groupnorm_linear_supported(Cc, N, rows_per_sample) or not w.is_contiguous():
+        raise VdxError(f"groupnorm_linear: C={Cc}, N={N}, rows_per_sample={rows_per_sample} not supported")
+    w_s, b_s = groupnorm_fold(x, gamma, beta, w, bias, groups=groups, n_samples=n_samples, rows_per_sample=rows_per_sample,
+                              eps=eps, partition_samples=partition_samples)
+    return gemm(x, w_s, M=n_samples * rows_per_sample, wset_rows=rows_per_sample, wset_bias=b_s, out=out)
 
 
 def gemm(a, w, *, M, mode=PLAIN, a2=None, bias=None, bias2=None, rows_per_bias2=0, residual=None,
@@ -541,6 +565,39 @@ def groupnorm(x, gamma, beta, *, groups, n_samples, rows_per_sample, eps, silu_a
     return out
 
 
+def groupnorm_stats(x, gamma, beta, *, groups, n_samples, rows_per_sample, eps, x2=None, partition_samples=0, workspace=None):
+    """The statistics pass alone (`vdx_groupnorm_stats_f16`: partial + finalize, no apply pass) -> (scale_shift, partial):
+    fp32 views into the workspace (the pool's unless one is given), [n_samples][C][2] (scale, shift) per (sample, channel)
+    — what K1 / K3 read — and [n_samples][nslabs][G][3] (n, mean, M2) per (sample, row slab, group).  The views stay
+    valid until the next GroupNorm launch on this stream."""
+    r, c1, ldx = _rows(x, "x")
+    M = n_samples * rows_per_sample
+    c2 = ldx2 = 0
+    if x2 is not None:
+        r2, c2, ldx2 = _rows(x2, "x2")
+        if r2 < M:
+            raise VdxError(f"groupnorm_stats: x2 has {r2} rows, need {M}")
+    Cc = c1 + c2
+    if r < M or gamma.numel() != Cc or beta.numel() != Cc:
+        raise VdxError(f"groupnorm_stats: x [{r}][{c1}] (+{c2}), gamma {gamma.numel()}, M = {M}: shapes do not match")
+    need = _lib.load().vdx_groupnorm_workspace_part(n_samples, rows_per_sample, Cc, groups, partition_samples)
+    ws = _gn_workspace(x.device, need, workspace)
+    off = C.c_size_t(0)
+    _launch("vdx_groupnorm_stats_f16", _p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"), _p(beta, "beta"),
+            float(eps), groups, n_samples, rows_per_sample, ws.data_ptr(), partition_samples, C.byref(off))
+    # the table starts behind the slab triples, rounded up to 4 floats.  The slab count is the library's: its workspace
+    # size for no channels and 4 groups is n_samples * nslabs * 12 floats with nothing rounded (the partition depends on
+    # neither C nor G), and the offset this launch returned must be the one that count gives
+    unit = 3 * n_samples * groups
+    nslabs = _lib.load().vdx_groupnorm_workspace_part(n_samples, rows_per_sample, 0, 4, partition_samples) // (48 * n_samples)
+    if round_up(unit * nslabs, 4) * 4 != off.value or off.value + n_samples * Cc * 8 != need:
+        raise VdxError(f"groupnorm_stats: table offset {off.value} does not match the workspace size {need}")
+    f32 = ws.view(torch.float32)
+    partial = f32[:unit * nslabs].view(n_samples, nslabs, groups, 3)
+    scale_shift = f32[off.value // 4:off.value // 4 + n_samples * Cc * 2].view(n_samples, Cc, 2)
+    return scale_shift, partial
+
+
 def conv3x3_gn_preferred(c1: int, c2: int, N: int, n_img: int, h: int, w: int) -> bool:
     """K1 supported AND expected to be faster than the apply pass + conv GEMM (level 0 of the XL UNet)."""
     return bool(_lib.load().vdx_conv3x3_gn_preferred(c1, c2, N, n_img, h, w))
@@ -575,13 +632,10 @@ def conv3x3_gn(x, gamma, beta, w, *, x2=None, bias=None, bias2=None, rows_per_bi
     ldb2 = _covers(bias2, M, N, "conv3x3_gn", "bias2", rows_per_bias2)
     ldr = _covers(residual, M, N, "conv3x3_gn", "residual")
     out, ldo = _out(out, M, N, x, "conv3x3_gn")
-    need = _lib.load().vdx_groupnorm_workspace_part(n_img, S, Cc, groups, partition_samples)
-    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
-    off = C.c_size_t(0)
-    _launch("vdx_groupnorm_stats_f16", _p(x, "x"), c1, ldx, _p(x2, "x2"), c2, ldx2, _p(gamma, "gamma"), _p(beta, "beta"),
-            float(eps), groups, n_img, S, ws.data_ptr(), partition_samples, C.byref(off))
+    ab, _ = groupnorm_stats(x, gamma, beta, groups=groups, n_samples=n_img, rows_per_sample=S, eps=eps, x2=x2,
+                            partition_samples=partition_samples)
     with _timed("conv3x3_gn_kernel", 2.0 * M * N * K, (M, N, K)):
-        _launch("vdx_conv3x3_gn_f16", _p(x, "x"), ldx, _p(x2, "x2"), ldx2, c1, c2, ws.data_ptr() + off.value, _p(w, "w"),
+        _launch("vdx_conv3x3_gn_f16", _p(x, "x"), ldx, _p(x2, "x2"), ldx2, c1, c2, ab.data_ptr(), _p(w, "w"),
                 _p(bias, "bias"), _p(bias2, "bias2"), rows_per_bias2, ldb2, _p(residual, "residual"), ldr, _p(out, "out"), ldo,
                 n_img, h, wd, N)
     return out
@@ -613,13 +667,10 @@ def tconv_gn(x, gamma, beta, w, *, bias=None, residual=None, groups, B, F, S, ep
         raise VdxError(f"tconv_gn: bias has {bias.numel()} elements, N={N}")
     ldr = _covers(residual, M, N, "tconv_gn", "residual")
     out, ldo = _out(out, M, N, x, "tconv_gn")
-    need = _lib.load().vdx_groupnorm_workspace_part(B, F * S, Cc, groups, partition_samples)
-    ws = _scratch(_GN_WS, x.device, need, torch.uint8, 1 << 20)
-    off = C.c_size_t(0)
-    _launch("vdx_groupnorm_stats_f16", _p(x, "x"), Cc, ldx, None, 0, 0, _p(gamma, "gamma"), _p(beta, "beta"), float(eps), groups, B,
-            F * S, ws.data_ptr(), partition_samples, C.byref(off))
+    ab, _ = groupnorm_stats(x, gamma, beta, groups=groups, n_samples=B, rows_per_sample=F * S, eps=eps,
+                            partition_samples=partition_samples)
     with _timed(f"tconv_gn_kernel<{16 if F % 16 == 0 else 12 if F % 12 == 0 else 8}>", 2.0 * M * N * K, (M, N, K)):
-        _launch("vdx_tconv_gn_f16", _p(x, "x"), ldx, ws.data_ptr() + off.value, _p(w, "w"), _p(bias, "bias"),
+        _launch("vdx_tconv_gn_f16", _p(x, "x"), ldx, ab.data_ptr(), _p(w, "w"), _p(bias, "bias"),
                 _p(residual, "residual"), ldr, _p(out, "out"), ldo, B, F, S, Cc, N)
     return out
 

@@ -270,6 +270,13 @@ class DiffusionPipeline:
     def disable_tome(self):
         self.unet.disable_tome()
 
+    def enable_hypertile(self, ny, nx, max_downsample=1):
+        """HyperTile as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_hypertile`)."""
+        self.unet.enable_hypertile(ny, nx, max_downsample=max_downsample)
+
+    def disable_hypertile(self):
+        self.unet.disable_hypertile()
+
     def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid", noise_type="shuffle_context"):
         """diffusers' pipeline-level `enable_free_noise(context_length, context_stride, weighting_scheme, noise_type)`: the UNet's
         switch (vdx/unet3d.py `enable_free_noise`).  This pipeline object samples nothing itself: the start noise is

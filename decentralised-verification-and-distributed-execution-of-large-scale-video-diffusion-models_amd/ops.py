@@ -731,6 +731,26 @@ def flash_attn(q, k, vt, *, n_seq, sq, skv, skv_pad, heads, seq_per_kv, scale, o
     return out
 
 
+def flash_attn_win(q, k, v, *, n_img, hh, ww, ny, nx, heads, scale, out=None):
+    """HyperTile's windowed self-attention (include/vdx.h `vdx_flash_attn_win_f16`, csrc/flash_win.hip): q, k, v rows
+    [n_img*hh*ww][>= heads*64] as `flash_attn(..., v_rows=True)` takes them; every image's hh x ww tokens are split into an
+    ny x nx grid of windows and each token attends inside its window.  The rows are read and written where they lie.  The
+    library refuses a grid that does not divide the tokens, and 1 x 1 (that is `flash_attn`)."""
+    n_img, hh, ww, ny, nx, heads = int(n_img), int(hh), int(ww), int(ny), int(nx), int(heads)
+    M, inner = n_img * hh * ww, heads * 64
+    ptrs = []
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        r, c, ld = _rows(t, name)
+        if r < M or c < inner:
+            raise VdxError(f"flash_attn_win: {name} too small")
+        ptrs += [_p(t, name), ld]
+    out, ldo = _out(out, M, inner, q, "flash_attn_win")
+    T = (hh // max(ny, 1)) * (ww // max(nx, 1))
+    with _timed(f"flash_attn_win_kernel<{2 if T >= 512 else 1}>", 4.0 * n_img * ny * nx * heads * T * T * 64, (M, T, inner)):
+        _launch("vdx_flash_attn_win_f16", *ptrs, _p(out, "out"), ldo, n_img, hh, ww, ny, nx, heads, float(scale))
+    return out
+
+
 def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
     r, c, ld = _rows(qkv, "qkv")
     inner = heads * 64

@@ -206,6 +206,28 @@ def check_tome(cfg) -> Optional[dict]:
     return check_params(cfg.tome, seed=cfg.tome_seed)
 
 
+def check_hypertile(cfg) -> Optional[dict]:
+    """`cfg.hypertile` / `cfg.hypertile_max_downsample` as {"grid", "max_downsample", "levels"} (None when off); `ValueError` before
+    any work unless `hypertile` is two integers >= 1 and the max_downsample one of 1, 2, 4, 8, for a grid that does not divide
+    the UNet's frame (the tile where `tile` is on) or cuts it into windows under 8 latent cells a side, and together with `tome`
+    (merged rows have no 2-D grid).  The option's refusals live here: `RULES` lists the co-denoising family only."""
+    ht, md = getattr(cfg, "hypertile", None), getattr(cfg, "hypertile_max_downsample", 1)
+    if ht is None:
+        if md != 1:
+            raise ValueError(f"hypertile_max_downsample {md!r} needs hypertile")
+        return None
+    if not isinstance(ht, (tuple, list)) or len(ht) != 2:
+        raise ValueError(f"hypertile must be two integers (ny, nx), got {ht!r}")
+    from .hypertile import check_frame, check_params, levels
+    params = check_params(ht[0], ht[1], md)
+    if cfg.tome is not None:
+        raise ValueError("hypertile and tome exclude each other: merged rows have no 2-D grid to cut into windows")
+    tile = getattr(cfg, "tile", None)          # the UNet's frame is a tile where tiling is on, else the whole latent frame
+    hh, ww = (int(tile[0]) // 8, int(tile[1]) // 8) if tile is not None else (cfg.height // 8, cfg.width // 8)
+    check_frame(hh, ww, params)
+    return {"grid": list(params["grid"]), "max_downsample": md, "levels": levels(params, hh, ww)}
+
+
 def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
     """`cfg.free_noise` / `cfg.free_noise_weighting` as {"context_length", "context_stride", "weighting", "windows"} (None when
     off), `windows` being the windows of one chunk of the plan; `ValueError` before any work for values outside the kernel's
@@ -479,6 +501,7 @@ class JobOptions:
     sampler_noise: Optional[dict] = None                            # a stochastic sampler: {"eta", "algorithm"} (vdx/scheduler.py); None: deterministic
     free_noise: Optional[dict] = None                               # FreeNoise: {"context_length", "context_stride", "weighting", "windows"} (vdx/freenoise.py)
     deflicker: Optional[dict] = None                                # temporal filter of the written frames: {"strength", "sigma", "passes"} (vdx/deflicker.py)
+    hypertile: Optional[dict] = None                                # HyperTile: {"grid", "max_downsample", "levels"} (vdx/hypertile.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -513,6 +536,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         sde = check_eta(cfg)
         free_noise = check_free_noise(cfg, exchange, world)
         deflicker = check_deflicker(cfg)
+        hypertile = check_hypertile(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -529,12 +553,14 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         sde = check_eta(cfg)
         free_noise = check_free_noise(cfg, exchange, world)
         deflicker = check_deflicker(cfg)
+        hypertile = check_hypertile(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
-                      cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker)
+                      cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker,
+                      hypertile=hypertile)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -562,6 +588,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(sampler_noise_record(opts))
     out.update(free_noise_record(opts))
     out.update(deflicker_record(opts))
+    out.update(hypertile_record(opts))
     return out
 
 
@@ -661,6 +688,16 @@ def deflicker_record(src) -> dict:
     if src.deflicker is None:
         return {}
     return {"deflicker": dict(src.deflicker)}
+
+
+def hypertile_record(src) -> dict:
+    """`{"hypertile": {"grid", "max_downsample", "levels"}}` beside `record_options`' entries, only when the option is set (else
+    {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"hypertile": src["hypertile"]} if "hypertile" in src else {}
+    if src.hypertile is None:
+        return {}
+    return {"hypertile": dict(src.hypertile)}
 
 
 def record_options(res: dict) -> dict:

@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import deflicker_record, free_noise_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import deflicker_record, free_noise_record, hypertile_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -179,6 +179,11 @@ class DiffuserConfig:
     # generated frames, as under `interpolate`.  Goes with every other option.  None = the frames are written as decoded, as always
     deflicker: Optional[Tuple[float, float]] = None
     deflicker_passes: int = 1
+    # HyperTile (vdx/hypertile.py, csrc/flash_win.hip; tfernd 2023, unpinned): (ny, nx).  The spatial self-attentions of the levels
+    # with downsample factor d <= `hypertile_max_downsample` attend inside the windows of a (max(1, ny // d), max(1, nx // d))
+    # grid of each frame (the tile with `tile`); the grid is fixed, where the published method redraws it per call.  Not with `tome`.
+    hypertile: Optional[Tuple[int, int]] = None
+    hypertile_max_downsample: int = 1
 
     @property
     def use_fsdp(self):
@@ -593,6 +598,7 @@ class DistributedVideoDiffuser:
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         iters, freeu, tome, free_noise = opts.free_init_iters, opts.freeu, opts.tome, opts.free_noise
+        hypertile = opts.hypertile
         tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
@@ -632,6 +638,10 @@ class DistributedVideoDiffuser:
             tome0 = self.unet.tome
             self.unet.enable_tome(**tome)
             info["tome"] = tome
+        if hypertile is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            hypertile0 = self.unet.hypertile
+            self.unet.enable_hypertile(*hypertile["grid"], max_downsample=hypertile["max_downsample"])
         if free_noise is not None:
             # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
             free_noise0 = self.unet.free_noise
@@ -663,6 +673,11 @@ class DistributedVideoDiffuser:
                 self.unet.enable_freeu(**freeu0) if freeu0 is not None else self.unet.disable_freeu()
             if tome is not None:
                 self.unet.enable_tome(**tome0) if tome0 is not None else self.unet.disable_tome()
+            if hypertile is not None:
+                if hypertile0 is not None:
+                    self.unet.enable_hypertile(*hypertile0["grid"], max_downsample=hypertile0["max_downsample"])
+                else:
+                    self.unet.disable_hypertile()
             if free_noise is not None:
                 if free_noise0 is not None:
                     self.unet.enable_free_noise(free_noise0["context_length"], free_noise0["context_stride"], free_noise0["weighting"])
@@ -757,6 +772,11 @@ def build_arg_parser():
                    help="FreeU in the UNet's up blocks 0 and 1: backbone factors B1 B2 (> 0), skip filter scales S1 S2 (default: off)")
     p.add_argument("--tome", type=float, default=None, metavar="RATIO",
                    help="token merging around the level-0 spatial self-attentions: share of the tokens merged away, in (0, 0.75] (default: off)")
+    p.add_argument("--hypertile", type=int, nargs=2, default=None, metavar=("NY", "NX"),
+                   help="HyperTile: the spatial self-attention of a frame runs inside the windows of an NY x NX grid (windows of at least "
+                        "8 latent cells a side; not with --tome; default: off)")
+    p.add_argument("--hypertile_max_downsample", type=int, default=1, metavar="D",
+                   help="with --hypertile: the levels with downsample factor up to D (1, 2, 4 or 8) take the grid (NY // d, NX // d) (default 1: level 0)")
     p.add_argument("--tome_seed", type=int, default=None, help="token merging: draw the cells' destination offsets once from this seed")
     p.add_argument("--free_noise", type=int, nargs=2, default=None, metavar=("L", "S"),
                    help="FreeNoise: one UNet call per chunk longer than L frames, its temporal attentions in sliding windows of L frames "
@@ -822,6 +842,8 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.freeu = tuple(cfg.freeu)
     if cfg.free_noise is not None:
         cfg.free_noise = tuple(cfg.free_noise)
+    if cfg.hypertile is not None:
+        cfg.hypertile = tuple(cfg.hypertile)
     if cfg.deflicker is not None:               # the flag is STRENGTH alone; the field is the pair
         cfg.deflicker = (cfg.deflicker, a.deflicker_sigma)
     if cfg.tile is not None:
@@ -1083,7 +1105,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1122,7 +1144,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1150,7 +1172,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

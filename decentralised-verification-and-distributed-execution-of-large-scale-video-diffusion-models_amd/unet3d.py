@@ -106,6 +106,7 @@ class UNet3DConditionModel(nn.Module):
         self._freeu: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None    # ((b1, s1), (b2, s2)) of enable_freeu; None: off
         self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
         self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
+        self._hypertile: Optional[Dict[str, object]] = None    # enable_hypertile's record {"grid": (ny, nx), "max_downsample"}; None: off
         self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
         self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
 
@@ -150,7 +151,10 @@ class UNet3DConditionModel(nn.Module):
         ratio that is not finite or outside (0, 1 - 1 / (sx sy)], sx or sy below 1 or sx sy < 2, a max_downsample outside
         {1, 2, 4, 8}."""
         from .tome import check_params
-        self._tome = check_params(ratio, sx=sx, sy=sy, seed=seed, max_downsample=max_downsample)
+        params = check_params(ratio, sx=sx, sy=sy, seed=seed, max_downsample=max_downsample)
+        if self._hypertile is not None:
+            raise ValueError("enable_tome: HyperTile is enabled and merged rows have no 2-D grid to cut into windows; disable_hypertile() first")
+        self._tome = params
         self._tome_tables = {}
         return self
 
@@ -178,6 +182,43 @@ class UNet3DConditionModel(nn.Module):
             part = partition(hh, ww, tm["ratio"], tm["sx"], tm["sy"], tm["seed"])
             plan = self._tome_tables[key] = (part.src_idx.to(device), part.dst_idx.to(device), part.r)
         return plan if plan[2] > 0 and plan[1].numel() > 0 else None
+
+    # ------------------------------------------------------------------------------------------
+    # HyperTile (tfernd 2023, unpinned; vdx/hypertile.py, csrc/flash_win.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_hypertile(self, ny, nx, max_downsample=1):
+        """From the next forward on, the spatial self-attentions (`attn1`) of the levels whose downsample factor d is at most
+        `max_downsample` attend inside the windows of a (max(1, ny // d), max(1, nx // d)) grid of each frame — a tile keeps its
+        size in pixels — through `ops.flash_attn_win`, which reads and writes the rows where they lie: no launch is added and
+        LayerNorm, the q|k|v projection and `to_out` + residual run on all rows as before.  A level whose grid is 1 x 1 or does
+        not divide its tokens runs the plain attention; a level-0 grid that does not divide raises `ValueError` in the forward.
+        Cross-attention, feed-forward, temporal transformers and the VAE are untouched.  The grid is fixed (the published
+        method redraws the tile count per call).  Refused with `ValueError`, the state left as it was: counts that are no
+        integers >= 1, a max_downsample outside {1, 2, 4, 8}, token merging enabled (merged rows have no 2-D grid)."""
+        from .hypertile import check_params
+        params = check_params(ny, nx, max_downsample)
+        if self._tome is not None:
+            raise ValueError("enable_hypertile: token merging is enabled and merged rows have no 2-D grid to cut into windows; disable_tome() first")
+        self._hypertile = params
+        return self
+
+    def disable_hypertile(self):
+        """The forward is again the one without HyperTile, launch for launch."""
+        self._hypertile = None
+        return self
+
+    @property
+    def hypertile(self) -> Optional[Dict[str, object]]:
+        """{"grid": (ny, nx), "max_downsample"} while HyperTile is enabled, else None."""
+        return dict(self._hypertile) if self._hypertile is not None else None
+
+    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None):
+        """The self-attention core on one q|k|v projection's rows: inside the windows of the grid `win`, or plain (None)."""
+        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if win is not None:
+            return ops.flash_attn_win(q, k, v, n_img=n_img, hh=hh, ww=ww, ny=win[0], nx=win[1], heads=heads, scale=scale, out=out)
+        S = hh * ww
+        return ops.flash_attn(q, k, v, n_seq=n_img, sq=S, skv=S, skv_pad=S, heads=heads, seq_per_kv=1, scale=scale, out=out, v_rows=True)
 
     # ------------------------------------------------------------------------------------------
     # FreeNoise (Qiu et al. 2024; diffusers' enable_free_noise, unpinned; vdx/freenoise.py, csrc/freenoise.hip)
@@ -626,7 +667,7 @@ class UNet3DConditionModel(nn.Module):
 
     def _self_attention(self, b, t, n_img, hh, ww, down=1):
         """`t + attn1(norm1(t))` of transformer block b on the rows t [n_img * hh * ww][C]; `down`: the level's downsample
-        factor (token merging applies up to `enable_tome`'s max_downsample)."""
+        factor (token merging and HyperTile apply up to their max_downsample)."""
         W = self.W
         S = hh * ww
         M = n_img * S
@@ -639,6 +680,10 @@ class UNet3DConditionModel(nn.Module):
         ln = ops.layernorm(t, W[b + ".norm1.weight"], W[b + ".norm1.bias"], M=M)
         wqkv = W[b + ".attn1.to_qkv.weight"]
         tome = self._tome_plan(hh, ww, down, t.device) if self._tome is not None else None
+        win = None                              # HyperTile: the level's window grid, None where the plain attention runs
+        if self._hypertile is not None:
+            from .hypertile import window_grid
+            win = window_grid(self._hypertile, hh, ww, down)
         if tome is not None:
             # token merging: the block's input t is the metric; the attention runs on S - r rows per image (the single q|k|v
             # path, whatever the memory-lean switches say) and every token reads its merged row back under the residual
@@ -666,11 +711,10 @@ class UNet3DConditionModel(nn.Module):
             hm, hn = M // 2, n_img // 2
             for r0 in (0, hm):
                 qkv = ops.gemm(ln[r0:r0 + hm], wqkv, M=hm)
-                ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_seq=hn, sq=S, skv=S, skv_pad=S, heads=heads,
-                               seq_per_kv=1, scale=scale, out=o[r0:r0 + hm], v_rows=True)
+                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm])
                 del qkv
             del ln
-        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0:
+        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None:
             # the round-2 form, kept for same-process A/B timing (tools/step_ab.py): q|k GEMM + V^T by the swapped GEMM
             qk = ops.gemm(ln, wqkv[:2 * C], M=M)
             vt = ops.gemm(wqkv[2 * C:], ln, M=C)
@@ -680,8 +724,7 @@ class UNet3DConditionModel(nn.Module):
         else:
             qkv = ops.gemm(ln, wqkv, M=M)
             del ln
-            o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_seq=n_img, sq=S, skv=S, skv_pad=S, heads=heads,
-                               seq_per_kv=1, scale=scale, v_rows=True)
+            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win)
             del qkv
         if tome is None:
             t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)

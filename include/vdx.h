@@ -236,6 +236,18 @@ int vdx_flash_attn_f16(const void* q, int ldq, const void* k, int ldk, const voi
 int vdx_flash_attn_rows_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                             void* out, int ldo, int n_seq, int sq, int skv, int skv_pad, int heads,
                             int seq_per_kv, float scale, int causal, vdx_stream_t stream);
+/* HyperTile (tfernd 2023): the spatial self-attention computed inside the windows of an ny x nx grid of every image, on the
+ * rows where they lie.  q, k, v, out: the row matrices of vdx_flash_attn_rows_f16 over n_img images of hh x ww tokens
+ * ([n_img*hh*ww][ld], head h at columns h*64.., V as rows; the three inputs may be the column blocks of one q|k|v
+ * projection).  With th = hh / ny, tw = ww / nx, T = th tw, token i of window (n, wy, wx) is row
+ *   n hh ww + (wy th + i / tw) ww + wx tw + i % tw,
+ * and per (window, head) out = softmax(q k^T scale) v over the window's T tokens, written to the same rows of out.  fp16 in
+ * and out, head dimension 64, fp32 accumulation; the score range is vdx_flash_attn_f16's.  Refused: a null pointer, a leading
+ * dimension that is no multiple of 8, hh % ny or ww % nx != 0, ny == nx == 1 (that grid is vdx_flash_attn_rows_f16 with
+ * sq = hh ww), more than 2^30 rows or 2^20 tokens per window, a grid of 2^31 blocks or more.  out may not overlap q, k or v. */
+int vdx_flash_attn_win_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
+                           void* out, int ldo, int n_img, int hh, int ww, int ny, int nx,
+                           int heads, float scale, vdx_stream_t stream);
 
 /* K8 — the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
  * erf GELU, both in Transformer2DModel and TransformerTemporalModel) as ONE kernel: LayerNorm -> [val | gate] projection ->

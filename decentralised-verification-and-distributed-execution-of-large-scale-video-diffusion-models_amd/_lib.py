@@ -81,6 +81,8 @@ SIGNATURES = {
     "vdx_flash_attn_rows_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     # HyperTile: the same attention inside the windows of an ny x nx grid of each image, rows read and written in place (csrc/flash_win.hip)
     "vdx_flash_attn_win_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    # cross-frame attention: keys / values from R reference frames of the sample, named by a device table [F][R] (csrc/flash_frames.hip)
+    "vdx_flash_attn_frames_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
     "vdx_timestep_embedding_f16": (_i, [_vp, _vp, _i, _i, _vp]),
     "vdx_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
     "vdx_temporal_attn_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),

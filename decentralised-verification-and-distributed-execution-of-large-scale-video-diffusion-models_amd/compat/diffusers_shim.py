@@ -277,6 +277,13 @@ class DiffusionPipeline:
     def disable_hypertile(self):
         self.unet.disable_hypertile()
 
+    def enable_cross_frame(self, mode="sparse_causal", max_downsample=8):
+        """Cross-frame attention as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_cross_frame`)."""
+        self.unet.enable_cross_frame(mode, max_downsample=max_downsample)
+
+    def disable_cross_frame(self):
+        self.unet.disable_cross_frame()
+
     def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid", noise_type="shuffle_context"):
         """diffusers' pipeline-level `enable_free_noise(context_length, context_stride, weighting_scheme, noise_type)`: the UNet's
         switch (vdx/unet3d.py `enable_free_noise`).  This pipeline object samples nothing itself: the start noise is

@@ -1,5 +1,5 @@
-// flash_common.h — the parts of the flash attention tile that flash.hip and flash_win.hip share: the softmax
-// state (lazy monotone offset, four max / sum chains) and the transposed V read.
+// flash_common.h — the parts of the flash attention tile that flash.hip, flash_win.hip and flash_frames.hip share: the softmax
+// state (lazy monotone offset, four max / sum chains), the transposed V read and the per-lane-row store.
 // profiles/r04_flash.md has the measurements behind each; flash.hip's header comment the layout they assume.
 #pragma once
 #include "attn_common.h"
@@ -142,4 +142,40 @@ __device__ __forceinline__ f16x8 fl_read_vtr(const char* vb) {      // keys 16kk
     pr.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ltr_t)vb);
     pr.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ltr_t)(vb + 512));
     return __builtin_bit_cast(f16x8, pr);
+}
+
+// epilogue of the kernels whose query rows are given per lane (flash_win.hip, flash_frames.hip): O[query][d], lane = query;
+// pair lanes (l, l^32) to emit 16-byte stores (flash.hip fl_store with the row given per lane); rows with ok false are not stored
+template <int QB>
+__device__ __forceinline__ void fl_store_rows(const FlSoft<QB>& st, const f32x16 (&o_acc)[QB][2], int h, f16* const (&dst)[QB], const bool (&ok)[QB]) {
+#pragma unroll
+    for (int qb = 0; qb < QB; ++qb) {
+        const float inv = 1.0f / st.row_sum(qb);
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+#pragma unroll
+            for (int g = 0; g < 4; g += 2) {
+                // register group g holds d = 32*db + 8*g + 4*h + (0..3)
+                f16x4 mine[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) mine[u][j] = (f16)(o_acc[qb][db][4 * (g + u) + j] * inv);
+                const f16x4 send = h ? mine[0] : mine[1];
+                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                u32x2 sb = __builtin_bit_cast(u32x2, send), rb;
+                rb[0] = __shfl_xor(sb[0], 32, 64);
+                rb[1] = __shfl_xor(sb[1], 32, 64);
+                const f16x4 recv = __builtin_bit_cast(f16x4, rb);
+                f16x8 o;
+                const f16x4 lo = h ? recv : mine[0], hi = h ? mine[1] : recv;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    o[j] = lo[j];
+                    o[4 + j] = hi[j];
+                }
+                if (ok[qb]) *(f16x8*)(dst[qb] + 32 * db + 8 * (g + h)) = o;
+            }
+        }
+    }
 }

@@ -43,41 +43,6 @@ __device__ __forceinline__ void fl_win_split(const FlWinP& p, int i, int& y, int
     x = i - y * p.tw;
 }
 
-// epilogue: O[query][d], lane = query; pair lanes (l, l^32) to emit 16-byte stores (flash.hip fl_store with the row given per lane)
-template <int QB>
-__device__ __forceinline__ void fl_win_store(const FlSoft<QB>& st, const f32x16 (&o_acc)[QB][2], int h, f16* const (&dst)[QB], const bool (&ok)[QB]) {
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        const float inv = 1.0f / st.row_sum(qb);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-#pragma unroll
-            for (int g = 0; g < 4; g += 2) {
-                // register group g holds d = 32*db + 8*g + 4*h + (0..3)
-                f16x4 mine[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) mine[u][j] = (f16)(o_acc[qb][db][4 * (g + u) + j] * inv);
-                const f16x4 send = h ? mine[0] : mine[1];
-                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                u32x2 sb = __builtin_bit_cast(u32x2, send), rb;
-                rb[0] = __shfl_xor(sb[0], 32, 64);
-                rb[1] = __shfl_xor(sb[1], 32, 64);
-                const f16x4 recv = __builtin_bit_cast(f16x4, rb);
-                f16x8 o;
-                const f16x4 lo = h ? recv : mine[0], hi = h ? mine[1] : recv;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[j] = lo[j];
-                    o[4 + j] = hi[j];
-                }
-                if (ok[qb]) *(f16x8*)(dst[qb] + 32 * db + 8 * (g + h)) = o;
-            }
-        }
-    }
-}
-
 template <int QB>
 __global__ __launch_bounds__(256) void flash_attn_win_kernel(const FlWinP p) {
     // LDS: 2 stages x { K tile [64 key][64 d] (chunk c of row r at c ^ ((r >> 1) & 7)), V tile [64 key][64 d] (chunk c of
@@ -224,7 +189,7 @@ __global__ __launch_bounds__(256) void flash_attn_win_kernel(const FlWinP p) {
             dst[qb] = p.out + (size_t)qrow[qb] * p.ldo + head * 64;
             ok[qb] = q0 + qb * 32 + r32 < p.T;                       // query rows past T are not stored
         }
-        fl_win_store<QB>(st, o_acc, h, dst, ok);
+        fl_store_rows<QB>(st, o_acc, h, dst, ok);
     }
 }
 

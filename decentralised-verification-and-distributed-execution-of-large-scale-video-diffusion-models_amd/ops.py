@@ -751,6 +751,29 @@ def flash_attn_win(q, k, v, *, n_img, hh, ww, ny, nx, heads, scale, out=None):
     return out
 
 
+def flash_attn_frames(q, k, v, *, n_samples, F, S, heads, refs, scale, out=None):
+    """Cross-frame attention (include/vdx.h `vdx_flash_attn_frames_f16`, csrc/flash_frames.hip): q, k, v rows
+    [n_samples*F*S][>= heads*64] as `flash_attn(..., v_rows=True)` takes them, the F frames of a sample being consecutive
+    images of S tokens; frame f attends to the R S keys of the frames refs[f][0..R-1] of its own sample, read where they lie.
+    `refs`: a contiguous int32 [F][R] on the device, as `crossframe.ref_table` builds and checks it on the host (the kernel
+    clamps what it reads, it cannot refuse).  The library refuses R outside 1..4 and an `out` that overlaps an input."""
+    n_samples, F, S, heads = int(n_samples), int(F), int(S), int(heads)
+    M, inner = n_samples * F * S, heads * 64
+    if refs.dim() != 2 or refs.shape[0] != F or not refs.is_contiguous() or refs.device != q.device:
+        raise VdxError(f"flash_attn_frames: refs must be a contiguous int32 [F = {F}][R] on q's device, got {tuple(refs.shape)} on {refs.device}")
+    R = refs.shape[1]
+    ptrs = []
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        r, c, ld = _rows(t, name)
+        if r < M or c < inner:
+            raise VdxError(f"flash_attn_frames: {name} too small")
+        ptrs += [_p(t, name), ld]
+    out, ldo = _out(out, M, inner, q, "flash_attn_frames")
+    with _timed(f"flash_attn_frames_kernel<{2 if S >= 512 else 1}>", 4.0 * n_samples * F * heads * S * R * S * 64, (M, R * S, inner)):
+        _launch("vdx_flash_attn_frames_f16", *ptrs, _p(out, "out"), ldo, n_samples, F, S, heads, _p(refs, "refs", torch.int32), R, float(scale))
+    return out
+
+
 def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
     r, c, ld = _rows(qkv, "qkv")
     inner = heads * 64

@@ -228,6 +228,28 @@ def check_hypertile(cfg) -> Optional[dict]:
     return {"grid": list(params["grid"]), "max_downsample": md, "levels": levels(params, hh, ww)}
 
 
+def check_cross_frame(cfg) -> Optional[dict]:
+    """`cfg.cross_frame` / `cfg.cross_frame_max_downsample` as {"mode", "refs_per_frame", "max_downsample"} (None when off);
+    `ValueError` before any work for what `crossframe.check_params` refuses (an unknown mode, a malformed table, a
+    max_downsample outside 1, 2, 4, 8) and together with `tome` or `hypertile` (both change the rows a frame's keys are read
+    from).  A table's rows are checked against the frame count of each UNet call when it runs.  The option's refusals live
+    here: `RULES` lists the co-denoising family only."""
+    mode, md = getattr(cfg, "cross_frame", None), getattr(cfg, "cross_frame_max_downsample", 8)
+    if mode is None:
+        if md != 8:
+            raise ValueError(f"cross_frame_max_downsample {md!r} needs cross_frame")
+        return None
+    from .crossframe import check_params
+    params = check_params(mode, md)
+    if cfg.tome is not None:
+        raise ValueError("cross_frame and tome exclude each other: merged rows differ from frame to frame")
+    if getattr(cfg, "hypertile", None) is not None:
+        raise ValueError("cross_frame and hypertile exclude each other: the cross-frame keys are whole frames")
+    if not isinstance(params["mode"], str):
+        params["mode"] = [list(row) for row in params["mode"]]
+    return params
+
+
 def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
     """`cfg.free_noise` / `cfg.free_noise_weighting` as {"context_length", "context_stride", "weighting", "windows"} (None when
     off), `windows` being the windows of one chunk of the plan; `ValueError` before any work for values outside the kernel's
@@ -502,6 +524,7 @@ class JobOptions:
     free_noise: Optional[dict] = None                               # FreeNoise: {"context_length", "context_stride", "weighting", "windows"} (vdx/freenoise.py)
     deflicker: Optional[dict] = None                                # temporal filter of the written frames: {"strength", "sigma", "passes"} (vdx/deflicker.py)
     hypertile: Optional[dict] = None                                # HyperTile: {"grid", "max_downsample", "levels"} (vdx/hypertile.py)
+    cross_frame: Optional[dict] = None                              # cross-frame attention: {"mode", "refs_per_frame", "max_downsample"} (vdx/crossframe.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -537,6 +560,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         free_noise = check_free_noise(cfg, exchange, world)
         deflicker = check_deflicker(cfg)
         hypertile = check_hypertile(cfg)
+        cross_frame = check_cross_frame(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -554,13 +578,14 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         free_noise = check_free_noise(cfg, exchange, world)
         deflicker = check_deflicker(cfg)
         hypertile = check_hypertile(cfg)
+        cross_frame = check_cross_frame(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
                       cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker,
-                      hypertile=hypertile)
+                      hypertile=hypertile, cross_frame=cross_frame)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -589,6 +614,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(free_noise_record(opts))
     out.update(deflicker_record(opts))
     out.update(hypertile_record(opts))
+    out.update(cross_frame_record(opts))
     return out
 
 
@@ -698,6 +724,16 @@ def hypertile_record(src) -> dict:
     if src.hypertile is None:
         return {}
     return {"hypertile": dict(src.hypertile)}
+
+
+def cross_frame_record(src) -> dict:
+    """`{"cross_frame": {"mode", "refs_per_frame", "max_downsample"}}` beside `record_options`' entries, only when the option is
+    set (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"cross_frame": src["cross_frame"]} if "cross_frame" in src else {}
+    if src.cross_frame is None:
+        return {}
+    return {"cross_frame": dict(src.cross_frame)}
 
 
 def record_options(res: dict) -> dict:

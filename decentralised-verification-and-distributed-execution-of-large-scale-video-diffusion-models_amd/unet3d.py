@@ -107,6 +107,8 @@ class UNet3DConditionModel(nn.Module):
         self._tome: Optional[Dict[str, object]] = None    # enable_tome's record {"ratio", "sx", "sy", "seed", "max_downsample"}; None: off
         self._tome_tables: Dict[tuple, tuple] = {}        # (hh, ww, device) -> (src_idx, dst_idx, r) of that token grid
         self._hypertile: Optional[Dict[str, object]] = None    # enable_hypertile's record {"grid": (ny, nx), "max_downsample"}; None: off
+        self._cross_frame: Optional[Dict[str, object]] = None  # enable_cross_frame's record {"mode", "refs_per_frame", "max_downsample"}; None: off
+        self._cross_frame_tables: Dict[tuple, torch.Tensor] = {}  # (F, device) -> the reference table int32 [F][R] on the device
         self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
         self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
 
@@ -154,6 +156,8 @@ class UNet3DConditionModel(nn.Module):
         params = check_params(ratio, sx=sx, sy=sy, seed=seed, max_downsample=max_downsample)
         if self._hypertile is not None:
             raise ValueError("enable_tome: HyperTile is enabled and merged rows have no 2-D grid to cut into windows; disable_hypertile() first")
+        if self._cross_frame is not None:
+            raise ValueError("enable_tome: cross-frame attention is enabled and merged rows differ from frame to frame; disable_cross_frame() first")
         self._tome = params
         self._tome_tables = {}
         return self
@@ -199,6 +203,8 @@ class UNet3DConditionModel(nn.Module):
         params = check_params(ny, nx, max_downsample)
         if self._tome is not None:
             raise ValueError("enable_hypertile: token merging is enabled and merged rows have no 2-D grid to cut into windows; disable_tome() first")
+        if self._cross_frame is not None:
+            raise ValueError("enable_hypertile: cross-frame attention is enabled and its keys are whole frames; disable_cross_frame() first")
         self._hypertile = params
         return self
 
@@ -212,13 +218,65 @@ class UNet3DConditionModel(nn.Module):
         """{"grid": (ny, nx), "max_downsample"} while HyperTile is enabled, else None."""
         return dict(self._hypertile) if self._hypertile is not None else None
 
-    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None):
-        """The self-attention core on one q|k|v projection's rows: inside the windows of the grid `win`, or plain (None)."""
+    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None, frames=None):
+        """The self-attention core on one q|k|v projection's rows: inside the windows of the grid `win`, against the reference
+        frames of `frames` = (F, the device table), or plain (both None)."""
         q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if frames is not None:
+            return ops.flash_attn_frames(q, k, v, n_samples=n_img // frames[0], F=frames[0], S=hh * ww, heads=heads, refs=frames[1],
+                                         scale=scale, out=out)
         if win is not None:
             return ops.flash_attn_win(q, k, v, n_img=n_img, hh=hh, ww=ww, ny=win[0], nx=win[1], heads=heads, scale=scale, out=out)
         S = hh * ww
         return ops.flash_attn(q, k, v, n_seq=n_img, sq=S, skv=S, skv_pad=S, heads=heads, seq_per_kv=1, scale=scale, out=out, v_rows=True)
+
+    # ------------------------------------------------------------------------------------------
+    # Cross-frame attention (Text2Video-Zero, Tune-A-Video, extended attention; unpinned; vdx/crossframe.py, csrc/flash_frames.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_cross_frame(self, mode="sparse_causal", max_downsample=8):
+        """From the next forward on, the spatial self-attentions (`attn1`) of the levels whose downsample factor is at most
+        `max_downsample` take their keys and values from reference frames of the same sample, frame f from the frames of row f of
+        `crossframe.ref_table(mode, F)`: "first" (frame 0), "sparse_causal" (frame 0 || f - 1), "self_first" (f || 0),
+        "self_prev" (f || f - 1) or a table of F rows.  `ops.flash_attn_frames` reads the reference frames' rows of the one
+        q|k|v projection where they lie: the plain attention's launch is swapped, none is added, and LayerNorm, the projection
+        and `to_out` + residual run as before.  F is the forward's frame count and frame 0 its first frame (a window's, in a
+        windowed job); a forward with F = 1 runs the plain attention.  Cross-attention, feed-forward, temporal transformers and
+        the VAE are untouched.  Refused with `ValueError`, the state left as it was: what `crossframe.check_params` refuses,
+        token merging or HyperTile enabled; a table that does not fit the forward's F raises in the forward."""
+        from .crossframe import check_params
+        params = check_params(mode, max_downsample)
+        if self._tome is not None or self._hypertile is not None:
+            which = "token merging" if self._tome is not None else "HyperTile"
+            raise ValueError(f"enable_cross_frame: {which} is enabled and changes the rows a frame's keys are read from; disable it first")
+        self._cross_frame = params
+        self._cross_frame_tables = {}
+        return self
+
+    def disable_cross_frame(self):
+        """The forward is again the one without cross-frame attention, launch for launch."""
+        self._cross_frame = None
+        self._cross_frame_tables = {}
+        return self
+
+    @property
+    def cross_frame(self) -> Optional[Dict[str, object]]:
+        """{"mode", "refs_per_frame", "max_downsample"} while cross-frame attention is enabled, else None."""
+        return dict(self._cross_frame) if self._cross_frame is not None else None
+
+    def _cross_frame_plan(self, F, n_img, down, device):
+        """(F, the reference table on `device`) for a self-attention over n_img images that are samples of F frames at a level
+        with downsample factor `down`, or None where the plain attention runs: disabled, F unknown or 1, above max_downsample."""
+        cf = self._cross_frame
+        if cf is None or F is None or F <= 1 or down > cf["max_downsample"]:
+            return None
+        if n_img % F:
+            raise ValueError(f"cross_frame: {n_img} images are no whole samples of {F} frames")
+        key = (F, str(device))
+        refs = self._cross_frame_tables.get(key)
+        if refs is None:
+            from .crossframe import ref_table
+            refs = self._cross_frame_tables[key] = ref_table(cf["mode"], F).to(device).contiguous()
+        return F, refs
 
     # ------------------------------------------------------------------------------------------
     # FreeNoise (Qiu et al. 2024; diffusers' enable_free_noise, unpinned; vdx/freenoise.py, csrc/freenoise.hip)
@@ -665,9 +723,10 @@ class UNet3DConditionModel(nn.Module):
             return 1 << (nlev - 1 - int(rest.split(".")[0]))
         return 1 << (nlev - 1)
 
-    def _self_attention(self, b, t, n_img, hh, ww, down=1):
+    def _self_attention(self, b, t, n_img, hh, ww, down=1, F=None):
         """`t + attn1(norm1(t))` of transformer block b on the rows t [n_img * hh * ww][C]; `down`: the level's downsample
-        factor (token merging and HyperTile apply up to their max_downsample)."""
+        factor (token merging, HyperTile and cross-frame attention apply up to their max_downsample); `F`: the frames per
+        sample, the images being samples of F consecutive frames (cross-frame attention needs it; None: unknown, plain)."""
         W = self.W
         S = hh * ww
         M = n_img * S
@@ -684,6 +743,7 @@ class UNet3DConditionModel(nn.Module):
         if self._hypertile is not None:
             from .hypertile import window_grid
             win = window_grid(self._hypertile, hh, ww, down)
+        frames = self._cross_frame_plan(F, n_img, down, t.device)      # cross-frame attention: (F, table), None where plain
         if tome is not None:
             # token merging: the block's input t is the metric; the attention runs on S - r rows per image (the single q|k|v
             # path, whatever the memory-lean switches say) and every token reads its merged row back under the residual
@@ -702,7 +762,8 @@ class UNet3DConditionModel(nn.Module):
             del o
             t = ops.tome_unmerge_add(am, slot, t, src_idx, dst_idx, n_img=n_img, S=S, r=r)
             del am, slot
-        elif self.ff_block_bytes and self.lean_attn and n_img % 2 == 0 and M * C * 2 > (128 << 20):
+        elif (self.ff_block_bytes and self.lean_attn and n_img % 2 == 0 and M * C * 2 > (128 << 20)
+              and (frames is None or (n_img // 2) % frames[0] == 0)):      # cross-frame: the cut lies between two samples
             # memory-lean mode: images are independent in the self-attention, so the projection and the attention run
             # over the images in two halves and only half of [rows][3C] is alive at a time.
             # (level 0 only: 0.6 ms per step on a 16-frame window for 45 MB of its peak — measured 4.33 against 4.374 GB
@@ -711,10 +772,10 @@ class UNet3DConditionModel(nn.Module):
             hm, hn = M // 2, n_img // 2
             for r0 in (0, hm):
                 qkv = ops.gemm(ln[r0:r0 + hm], wqkv, M=hm)
-                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm])
+                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm], frames=frames)
                 del qkv
             del ln
-        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None:
+        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None and frames is None:
             # the round-2 form, kept for same-process A/B timing (tools/step_ab.py): q|k GEMM + V^T by the swapped GEMM
             qk = ops.gemm(ln, wqkv[:2 * C], M=M)
             vt = ops.gemm(wqkv[2 * C:], ln, M=C)
@@ -724,7 +785,7 @@ class UNet3DConditionModel(nn.Module):
         else:
             qkv = ops.gemm(ln, wqkv, M=M)
             del ln
-            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win)
+            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win, frames=frames)
             del qkv
         if tome is None:
             t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)
@@ -747,7 +808,7 @@ class UNet3DConditionModel(nn.Module):
         scale = 64 ** -0.5
         b = p + ".transformer_blocks.0"
         t = self._norm_proj_in(p, x, n_img, S, M, part=2 * n_img if dup else 0)
-        t = self._self_attention(b, t, n_img, hh, ww, self._level_down_of(p))
+        t = self._self_attention(b, t, n_img, hh, ww, self._level_down_of(p), F=F)
         # --- cross-attention over the (padded) text tokens; all F frames of a sample share K/V — or, with per-frame text
         # (`encoder_hidden_states` (B, F, N, D): prompt travel), every frame has its own item: nb = B F, `fpi` = F items per sample
         pad = self._text_pad

@@ -248,6 +248,21 @@ int vdx_flash_attn_rows_f16(const void* q, int ldq, const void* k, int ldk, cons
 int vdx_flash_attn_win_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                            void* out, int ldo, int n_img, int hh, int ww, int ny, int nx,
                            int heads, float scale, vdx_stream_t stream);
+/* Cross-frame attention (Text2Video-Zero's first-frame, Tune-A-Video's sparse-causal, "extended" attention): the spatial
+ * self-attention of every frame with its keys and values taken from R reference frames of the same sample, read where they
+ * lie.  q, k, v, out: the row matrices of vdx_flash_attn_rows_f16 over n_samples * F images of S tokens ([n_samples*F*S][ld],
+ * head h at columns h*64.., V as rows; the three inputs may be the column blocks of one q|k|v projection).  refs: device
+ * int32 [F][R], entries in 0 .. F-1 (the caller checks them; the kernel clamps).  Key j (0 <= j < R S) of query image (b, f)
+ * is row
+ *   (b F + refs[f][j / S]) S + j % S,
+ * and out = softmax(q k^T scale) v over those R S keys, written to the query's own row.  Duplicate references are legal
+ * (each copy counts as its own keys).  fp16 in and out, head dimension 64, fp32 accumulation, no atomics, the same bits
+ * on every run and for any n_samples; the score range is vdx_flash_attn_f16's.  Refused: a null pointer, a leading dimension
+ * that is no multiple of 8 or below heads*64, R outside 1..4, F, S, heads or n_samples < 1, R S > 2^20, more than 2^30 rows,
+ * a grid of 2^31 blocks or more, out's byte range meeting that of q, k or v. */
+int vdx_flash_attn_frames_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
+                              void* out, int ldo, int n_samples, int F, int S, int heads,
+                              const int* refs, int R, float scale, vdx_stream_t stream);
 
 /* K8 — the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
  * erf GELU, both in Transformer2DModel and TransformerTemporalModel) as ONE kernel: LayerNorm -> [val | gate] projection ->

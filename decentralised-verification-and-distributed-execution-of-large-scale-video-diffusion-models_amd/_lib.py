@@ -83,6 +83,8 @@ SIGNATURES = {
     "vdx_flash_attn_win_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
     # cross-frame attention: keys / values from R reference frames of the sample, named by a device table [F][R] (csrc/flash_frames.hip)
     "vdx_flash_attn_frames_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
+    # token downsampling: all queries of an image against every s-th row and column of its token grid, read in place (csrc/flash_kvdown.hip)
+    "vdx_flash_attn_kvdown_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "vdx_timestep_embedding_f16": (_i, [_vp, _vp, _i, _i, _vp]),
     "vdx_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
     "vdx_temporal_attn_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),

@@ -284,6 +284,13 @@ class DiffusionPipeline:
     def disable_cross_frame(self):
         self.unet.disable_cross_frame()
 
+    def enable_kv_downsample(self, factor=2, max_downsample=1):
+        """Token downsampling of the keys (ToDo) as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_kv_downsample`)."""
+        self.unet.enable_kv_downsample(factor, max_downsample=max_downsample)
+
+    def disable_kv_downsample(self):
+        self.unet.disable_kv_downsample()
+
     def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid", noise_type="shuffle_context"):
         """diffusers' pipeline-level `enable_free_noise(context_length, context_stride, weighting_scheme, noise_type)`: the UNet's
         switch (vdx/unet3d.py `enable_free_noise`).  This pipeline object samples nothing itself: the start noise is

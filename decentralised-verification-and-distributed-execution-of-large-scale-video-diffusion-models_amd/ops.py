@@ -774,6 +774,27 @@ def flash_attn_frames(q, k, v, *, n_samples, F, S, heads, refs, scale, out=None)
     return out
 
 
+def flash_attn_kvdown(q, k, v, *, n_img, hh, ww, s, heads, scale, out=None):
+    """Token downsampling of the keys (include/vdx.h `vdx_flash_attn_kvdown_f16`, csrc/flash_kvdown.hip): q, k, v rows
+    [n_img*hh*ww][>= heads*64] as `flash_attn(..., v_rows=True)` takes them; all hh ww queries of an image attend to the
+    (hh // s) (ww // s) keys at every s-th row and column of its token grid (`kvdown.key_rows`), read where they lie, and the
+    result goes to the queries' own rows.  The library refuses s < 2 (that is `flash_attn`) and a factor that leaves no key."""
+    n_img, hh, ww, s, heads = int(n_img), int(hh), int(ww), int(s), int(heads)
+    M, inner = n_img * hh * ww, heads * 64
+    ptrs = []
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        r, c, ld = _rows(t, name)
+        if r < M or c < inner:
+            raise VdxError(f"flash_attn_kvdown: {name} too small")
+        ptrs += [_p(t, name), ld]
+    out, ldo = _out(out, M, inner, q, "flash_attn_kvdown")
+    S, Tk = hh * ww, (hh // max(s, 1)) * (ww // max(s, 1))
+    two = S >= 512 and Tk >= 256                        # flash_attn's rule
+    with _timed(f"flash_attn_kvdown_kernel<{2 if two else 1}>", 4.0 * n_img * heads * S * Tk * 64, (M, Tk, inner)):
+        _launch("vdx_flash_attn_kvdown_f16", *ptrs, _p(out, "out"), ldo, n_img, hh, ww, s, heads, float(scale))
+    return out
+
+
 def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
     r, c, ld = _rows(qkv, "qkv")
     inner = heads * 64

@@ -250,6 +250,27 @@ def check_cross_frame(cfg) -> Optional[dict]:
     return params
 
 
+def check_kv_downsample(cfg) -> Optional[dict]:
+    """`cfg.kv_downsample` / `cfg.kv_downsample_max_downsample` as {"factor", "max_downsample", "levels"} (None when off);
+    `ValueError` before any work unless the factor is an integer 2..8 and the max_downsample one of 1, 2, 4, 8, for a UNet frame
+    (the tile where `tile` is on) whose key grid has under 4 cells a side, and together with `tome`, `hypertile` or `cross_frame`
+    (each changes which rows are keys).  The option's refusals live here: `RULES` lists the co-denoising family only."""
+    s, md = getattr(cfg, "kv_downsample", None), getattr(cfg, "kv_downsample_max_downsample", 1)
+    if s is None:
+        if md != 1:
+            raise ValueError(f"kv_downsample_max_downsample {md!r} needs kv_downsample")
+        return None
+    from .kvdown import check_frame, check_params, levels
+    params = check_params(s, md)
+    for other in ("tome", "hypertile", "cross_frame"):
+        if getattr(cfg, other, None) is not None:
+            raise ValueError(f"kv_downsample and {other} exclude each other: both change which rows are a query's keys")
+    tile = getattr(cfg, "tile", None)          # the UNet's frame is a tile where tiling is on, else the whole latent frame
+    hh, ww = (int(tile[0]) // 8, int(tile[1]) // 8) if tile is not None else (cfg.height // 8, cfg.width // 8)
+    check_frame(hh, ww, params)
+    return {"factor": s, "max_downsample": md, "levels": levels(params, hh, ww)}
+
+
 def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
     """`cfg.free_noise` / `cfg.free_noise_weighting` as {"context_length", "context_stride", "weighting", "windows"} (None when
     off), `windows` being the windows of one chunk of the plan; `ValueError` before any work for values outside the kernel's
@@ -525,6 +546,7 @@ class JobOptions:
     deflicker: Optional[dict] = None                                # temporal filter of the written frames: {"strength", "sigma", "passes"} (vdx/deflicker.py)
     hypertile: Optional[dict] = None                                # HyperTile: {"grid", "max_downsample", "levels"} (vdx/hypertile.py)
     cross_frame: Optional[dict] = None                              # cross-frame attention: {"mode", "refs_per_frame", "max_downsample"} (vdx/crossframe.py)
+    kv_downsample: Optional[dict] = None                            # key downsampling: {"factor", "max_downsample", "levels"} (vdx/kvdown.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -561,6 +583,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         deflicker = check_deflicker(cfg)
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
+        kv_downsample = check_kv_downsample(cfg)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -579,13 +602,14 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         deflicker = check_deflicker(cfg)
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
+        kv_downsample = check_kv_downsample(cfg)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
                       cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker,
-                      hypertile=hypertile, cross_frame=cross_frame)
+                      hypertile=hypertile, cross_frame=cross_frame, kv_downsample=kv_downsample)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -615,6 +639,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(deflicker_record(opts))
     out.update(hypertile_record(opts))
     out.update(cross_frame_record(opts))
+    out.update(kv_downsample_record(opts))
     return out
 
 
@@ -734,6 +759,16 @@ def cross_frame_record(src) -> dict:
     if src.cross_frame is None:
         return {}
     return {"cross_frame": dict(src.cross_frame)}
+
+
+def kv_downsample_record(src) -> dict:
+    """`{"kv_downsample": {"factor", "max_downsample", "levels"}}` beside `record_options`' entries, only when the option is set
+    (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"kv_downsample": src["kv_downsample"]} if "kv_downsample" in src else {}
+    if src.kv_downsample is None:
+        return {}
+    return {"kv_downsample": dict(src.kv_downsample)}
 
 
 def record_options(res: dict) -> dict:

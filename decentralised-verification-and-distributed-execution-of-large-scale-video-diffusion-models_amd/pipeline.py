@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import cross_frame_record, deflicker_record, free_noise_record, hypertile_record, info_options, job_texts, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import cross_frame_record, deflicker_record, free_noise_record, hypertile_record, info_options, job_texts, kv_downsample_record, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -190,6 +190,12 @@ class DiffuserConfig:
     # same UNet call (a window's first frame is its frame 0).  Not with `tome` or `hypertile`.
     cross_frame: Optional[object] = None
     cross_frame_max_downsample: int = 8
+    # Token downsampling of the keys (vdx/kvdown.py, csrc/flash_kvdown.hip; ToDo, Smith et al. 2024, unpinned): the factor, 2..8.
+    # The spatial self-attentions of the levels with downsample factor d <= `kv_downsample_max_downsample` keep every query and
+    # take their keys and values from every max(1, factor // d)-th row and column of the frame (the tile with `tile`).  Not
+    # with `tome`, `hypertile` or `cross_frame`.
+    kv_downsample: Optional[int] = None
+    kv_downsample_max_downsample: int = 1
 
     @property
     def use_fsdp(self):
@@ -604,7 +610,7 @@ class DistributedVideoDiffuser:
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         iters, freeu, tome, free_noise = opts.free_init_iters, opts.freeu, opts.tome, opts.free_noise
-        hypertile, cross_frame = opts.hypertile, opts.cross_frame
+        hypertile, cross_frame, kv_downsample = opts.hypertile, opts.cross_frame, opts.kv_downsample
         tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
@@ -652,6 +658,10 @@ class DistributedVideoDiffuser:
             # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
             cross_frame0 = self.unet.cross_frame
             self.unet.enable_cross_frame(cross_frame["mode"], max_downsample=cross_frame["max_downsample"])
+        if kv_downsample is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            kv_downsample0 = self.unet.kv_downsample
+            self.unet.enable_kv_downsample(kv_downsample["factor"], max_downsample=kv_downsample["max_downsample"])
         if free_noise is not None:
             # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
             free_noise0 = self.unet.free_noise
@@ -693,6 +703,8 @@ class DistributedVideoDiffuser:
                     self.unet.enable_cross_frame(cross_frame0["mode"], max_downsample=cross_frame0["max_downsample"])
                 else:
                     self.unet.disable_cross_frame()
+            if kv_downsample is not None:
+                self.unet.enable_kv_downsample(**kv_downsample0) if kv_downsample0 is not None else self.unet.disable_kv_downsample()
             if free_noise is not None:
                 if free_noise0 is not None:
                     self.unet.enable_free_noise(free_noise0["context_length"], free_noise0["context_stride"], free_noise0["weighting"])
@@ -798,6 +810,11 @@ def build_arg_parser():
                         "(self_prev) of the same UNet call (not with --tome or --hypertile; default: off)")
     p.add_argument("--cross_frame_max_downsample", type=int, default=8, metavar="D",
                    help="with --cross_frame: the levels with downsample factor up to D (1, 2, 4 or 8) attend across frames (default 8: all)")
+    p.add_argument("--kv_downsample", type=int, default=None, metavar="S",
+                   help="token downsampling (ToDo): the spatial self-attention of a frame keeps every query and takes its keys and values "
+                        "from every S-th row and column of the frame, S in 2..8 (not with --tome, --hypertile or --cross_frame; default: off)")
+    p.add_argument("--kv_downsample_max_downsample", type=int, default=1, metavar="D",
+                   help="with --kv_downsample: the levels with downsample factor up to D (1, 2, 4 or 8) take the factor S // d (default 1: level 0)")
     p.add_argument("--tome_seed", type=int, default=None, help="token merging: draw the cells' destination offsets once from this seed")
     p.add_argument("--free_noise", type=int, nargs=2, default=None, metavar=("L", "S"),
                    help="FreeNoise: one UNet call per chunk longer than L frames, its temporal attentions in sliding windows of L frames "
@@ -1126,7 +1143,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **kv_downsample_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1165,7 +1182,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1193,7 +1210,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -109,6 +109,7 @@ class UNet3DConditionModel(nn.Module):
         self._hypertile: Optional[Dict[str, object]] = None    # enable_hypertile's record {"grid": (ny, nx), "max_downsample"}; None: off
         self._cross_frame: Optional[Dict[str, object]] = None  # enable_cross_frame's record {"mode", "refs_per_frame", "max_downsample"}; None: off
         self._cross_frame_tables: Dict[tuple, torch.Tensor] = {}  # (F, device) -> the reference table int32 [F][R] on the device
+        self._kv_downsample: Optional[Dict[str, object]] = None  # enable_kv_downsample's record {"factor", "max_downsample"}; None: off
         self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
         self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
 
@@ -158,6 +159,8 @@ class UNet3DConditionModel(nn.Module):
             raise ValueError("enable_tome: HyperTile is enabled and merged rows have no 2-D grid to cut into windows; disable_hypertile() first")
         if self._cross_frame is not None:
             raise ValueError("enable_tome: cross-frame attention is enabled and merged rows differ from frame to frame; disable_cross_frame() first")
+        if self._kv_downsample is not None:
+            raise ValueError("enable_tome: key downsampling is enabled and merged rows have no 2-D grid to downsample; disable_kv_downsample() first")
         self._tome = params
         self._tome_tables = {}
         return self
@@ -205,6 +208,8 @@ class UNet3DConditionModel(nn.Module):
             raise ValueError("enable_hypertile: token merging is enabled and merged rows have no 2-D grid to cut into windows; disable_tome() first")
         if self._cross_frame is not None:
             raise ValueError("enable_hypertile: cross-frame attention is enabled and its keys are whole frames; disable_cross_frame() first")
+        if self._kv_downsample is not None:
+            raise ValueError("enable_hypertile: key downsampling is enabled and its keys span the whole frame; disable_kv_downsample() first")
         self._hypertile = params
         return self
 
@@ -218,10 +223,12 @@ class UNet3DConditionModel(nn.Module):
         """{"grid": (ny, nx), "max_downsample"} while HyperTile is enabled, else None."""
         return dict(self._hypertile) if self._hypertile is not None else None
 
-    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None, frames=None):
+    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None, frames=None, kvd=None):
         """The self-attention core on one q|k|v projection's rows: inside the windows of the grid `win`, against the reference
-        frames of `frames` = (F, the device table), or plain (both None)."""
+        frames of `frames` = (F, the device table), against the keys of every `kvd`-th row and column, or plain (all None)."""
         q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if kvd is not None:
+            return ops.flash_attn_kvdown(q, k, v, n_img=n_img, hh=hh, ww=ww, s=kvd, heads=heads, scale=scale, out=out)
         if frames is not None:
             return ops.flash_attn_frames(q, k, v, n_samples=n_img // frames[0], F=frames[0], S=hh * ww, heads=heads, refs=frames[1],
                                          scale=scale, out=out)
@@ -245,8 +252,8 @@ class UNet3DConditionModel(nn.Module):
         token merging or HyperTile enabled; a table that does not fit the forward's F raises in the forward."""
         from .crossframe import check_params
         params = check_params(mode, max_downsample)
-        if self._tome is not None or self._hypertile is not None:
-            which = "token merging" if self._tome is not None else "HyperTile"
+        if self._tome is not None or self._hypertile is not None or self._kv_downsample is not None:
+            which = "token merging" if self._tome is not None else "HyperTile" if self._hypertile is not None else "key downsampling"
             raise ValueError(f"enable_cross_frame: {which} is enabled and changes the rows a frame's keys are read from; disable it first")
         self._cross_frame = params
         self._cross_frame_tables = {}
@@ -277,6 +284,46 @@ class UNet3DConditionModel(nn.Module):
             from .crossframe import ref_table
             refs = self._cross_frame_tables[key] = ref_table(cf["mode"], F).to(device).contiguous()
         return F, refs
+
+    # ------------------------------------------------------------------------------------------
+    # Token downsampling of the keys (ToDo, Smith et al. 2024; unpinned; vdx/kvdown.py, csrc/flash_kvdown.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_kv_downsample(self, factor=2, max_downsample=1):
+        """From the next forward on, the spatial self-attentions (`attn1`) of the levels whose downsample factor d is at most
+        `max_downsample` keep all their queries and take their keys and values from every s-th row and column of the frame's
+        token grid, s = max(1, factor // d) — the key pitch stays fixed in pixels: nearest-neighbour downsampling of the hidden
+        state in front of the key and value projections.  `ops.flash_attn_kvdown` reads those rows of the one q|k|v projection
+        where they lie: the plain attention's launch is swapped, none is added, and LayerNorm, the projection (still of all
+        rows) and `to_out` + residual run as before.  A level with s = 1, or too small to keep a key, runs the plain attention.
+        Cross-attention, feed-forward, temporal transformers and the VAE are untouched.  Refused with `ValueError`, the state
+        left as it was: a factor that is no integer 2..8, a max_downsample outside {1, 2, 4, 8}, token merging, HyperTile or
+        cross-frame attention enabled (each changes which rows are keys)."""
+        from .kvdown import check_params
+        params = check_params(factor, max_downsample)
+        for on, which in ((self._tome, "token merging"), (self._hypertile, "HyperTile"), (self._cross_frame, "cross-frame attention")):
+            if on is not None:
+                raise ValueError(f"enable_kv_downsample: {which} is enabled and changes which rows are keys; disable it first")
+        self._kv_downsample = params
+        return self
+
+    def disable_kv_downsample(self):
+        """The forward is again the one without key downsampling, launch for launch."""
+        self._kv_downsample = None
+        return self
+
+    @property
+    def kv_downsample(self) -> Optional[Dict[str, object]]:
+        """{"factor", "max_downsample"} while key downsampling is enabled, else None."""
+        return dict(self._kv_downsample) if self._kv_downsample is not None else None
+
+    def _kv_downsample_factor(self, hh, ww, down):
+        """The factor `ops.flash_attn_kvdown` runs with on an (hh, ww) token grid at a level with downsample factor `down`, or
+        None where the plain attention runs: disabled, factor 1, above max_downsample, no key left."""
+        if self._kv_downsample is None:
+            return None
+        from .kvdown import level_factor
+        s = level_factor(self._kv_downsample, down)
+        return s if s > 1 and hh // s >= 1 and ww // s >= 1 else None
 
     # ------------------------------------------------------------------------------------------
     # FreeNoise (Qiu et al. 2024; diffusers' enable_free_noise, unpinned; vdx/freenoise.py, csrc/freenoise.hip)
@@ -725,7 +772,7 @@ class UNet3DConditionModel(nn.Module):
 
     def _self_attention(self, b, t, n_img, hh, ww, down=1, F=None):
         """`t + attn1(norm1(t))` of transformer block b on the rows t [n_img * hh * ww][C]; `down`: the level's downsample
-        factor (token merging, HyperTile and cross-frame attention apply up to their max_downsample); `F`: the frames per
+        factor (token merging, HyperTile, cross-frame attention and key downsampling apply up to their max_downsample); `F`: the frames per
         sample, the images being samples of F consecutive frames (cross-frame attention needs it; None: unknown, plain)."""
         W = self.W
         S = hh * ww
@@ -744,6 +791,7 @@ class UNet3DConditionModel(nn.Module):
             from .hypertile import window_grid
             win = window_grid(self._hypertile, hh, ww, down)
         frames = self._cross_frame_plan(F, n_img, down, t.device)      # cross-frame attention: (F, table), None where plain
+        kvd = self._kv_downsample_factor(hh, ww, down)                 # key downsampling: the level's factor, None where plain
         if tome is not None:
             # token merging: the block's input t is the metric; the attention runs on S - r rows per image (the single q|k|v
             # path, whatever the memory-lean switches say) and every token reads its merged row back under the residual
@@ -772,10 +820,10 @@ class UNet3DConditionModel(nn.Module):
             hm, hn = M // 2, n_img // 2
             for r0 in (0, hm):
                 qkv = ops.gemm(ln[r0:r0 + hm], wqkv, M=hm)
-                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm], frames=frames)
+                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm], frames=frames, kvd=kvd)
                 del qkv
             del ln
-        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None and frames is None:
+        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None and frames is None and kvd is None:
             # the round-2 form, kept for same-process A/B timing (tools/step_ab.py): q|k GEMM + V^T by the swapped GEMM
             qk = ops.gemm(ln, wqkv[:2 * C], M=M)
             vt = ops.gemm(wqkv[2 * C:], ln, M=C)
@@ -785,7 +833,7 @@ class UNet3DConditionModel(nn.Module):
         else:
             qkv = ops.gemm(ln, wqkv, M=M)
             del ln
-            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win, frames=frames)
+            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win, frames=frames, kvd=kvd)
             del qkv
         if tome is None:
             t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)

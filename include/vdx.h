@@ -263,6 +263,22 @@ int vdx_flash_attn_win_f16(const void* q, int ldq, const void* k, int ldk, const
 int vdx_flash_attn_frames_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                               void* out, int ldo, int n_samples, int F, int S, int heads,
                               const int* refs, int R, float scale, vdx_stream_t stream);
+/* Token downsampling of the keys (ToDo, Smith et al. 2024): the spatial self-attention of every image with all hh ww queries
+ * and the keys and values of every s-th row and column of the token grid, read where they lie.  q, k, v, out: the row matrices
+ * of vdx_flash_attn_rows_f16 over n_img images of hh x ww tokens ([n_img*hh*ww][ld], head h at columns h*64.., V as rows; the
+ * three inputs may be the column blocks of one q|k|v projection).  With kh = hh / s, kw = ww / s (floors), Tk = kh kw, key j
+ * (0 <= j < Tk) of image n is row
+ *   n hh ww + (j / kw) s ww + (j % kw) s
+ * (nearest-neighbour downsampling by s; rows and columns from kh s and kw s on are never keys, and no other row of k or v is
+ * read), and per (image, head) out = softmax(q k^T scale) v over those Tk keys for all hh ww queries, written to the queries'
+ * own rows.  fp16 in and out, head dimension 64, fp32 accumulation, no atomics, the same bits on every run, for any n_img, and
+ * as vdx_flash_attn_rows_f16 gives on the gathered keys; the score range is vdx_flash_attn_f16's.  Refused: a null pointer,
+ * n_img, hh, ww or heads < 1, a leading dimension that is no multiple of 8 or below heads*64, s < 2 (that is
+ * vdx_flash_attn_rows_f16), hh / s or ww / s < 1, more than 2^30 rows or 2^20 keys per image, a grid of 2^31 blocks or more,
+ * out's byte range meeting that of k or v. */
+int vdx_flash_attn_kvdown_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
+                              void* out, int ldo, int n_img, int hh, int ww, int s,
+                              int heads, float scale, vdx_stream_t stream);
 
 /* K8 — the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
  * erf GELU, both in Transformer2DModel and TransformerTemporalModel) as ONE kernel: LayerNorm -> [val | gate] projection ->

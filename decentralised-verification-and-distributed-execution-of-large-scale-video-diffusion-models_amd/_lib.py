@@ -221,6 +221,9 @@ SIGNATURES = {
     # enable_free_noise, vdx/freenoise.py, csrc/freenoise.hip)
     "vdx_temporal_attn_windows_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
     "vdx_frame_gather_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    # FreeLong: spectrally blended temporal attention (no reference counterpart; unet3d.py enable_free_long, vdx/freelong.py,
+    # csrc/freelong.hip)
+    "vdx_temporal_attn_blend_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     # token merging around the spatial self-attention (no reference counterpart; unet3d.py enable_tome, vdx/tome.py, csrc/tome.hip)
     "vdx_tome_match_f16": (_i, [C.POINTER(TomeArgs), _vp, _i, _vp]),
     "vdx_tome_select_lds": (_sz, [_i, _i]),

@@ -291,6 +291,13 @@ class DiffusionPipeline:
     def disable_kv_downsample(self):
         self.unet.disable_kv_downsample()
 
+    def enable_free_long(self, window=24, d_t=0.25, method="gaussian", order=4):
+        """FreeLong's spectrally blended temporal attention as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_free_long`)."""
+        self.unet.enable_free_long(window, d_t, method, order)
+
+    def disable_free_long(self):
+        self.unet.disable_free_long()
+
     def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid", noise_type="shuffle_context"):
         """diffusers' pipeline-level `enable_free_noise(context_length, context_stride, weighting_scheme, noise_type)`: the UNet's
         switch (vdx/unet3d.py `enable_free_noise`).  This pipeline object samples nothing itself: the start noise is

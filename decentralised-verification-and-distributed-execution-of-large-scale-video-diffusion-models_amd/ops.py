@@ -829,6 +829,27 @@ def temporal_attn_windows(qkv, wn, *, B, F, HW, heads, scale, L, S, out=None):
     return out
 
 
+def temporal_attn_blend(qkv, lp, *, B, F, HW, heads, scale, radius, out=None):
+    """FreeLong's spectrally blended temporal attention (include/vdx.h `vdx_temporal_attn_blend_f16`, csrc/freelong.hip):
+    `temporal_attn` over all F frames and inside the band |t - j| <= radius from one set of scores, the global result's
+    difference from the local one taken through `lp`, a contiguous fp16 (F, F) matrix on qkv's device
+    (`freelong.blend_matrix`), along the frame axis.  The library refuses what lies outside 2 <= F <= 128, radius >= 1."""
+    r, c, ld = _rows(qkv, "qkv")
+    inner = heads * 64
+    M = B * F * HW
+    if r < M or c < 3 * inner:
+        raise VdxError("temporal_attn_blend: qkv too small")
+    if (not torch.is_tensor(lp) or lp.dtype != torch.float16 or lp.device != qkv.device or not lp.is_contiguous()
+            or tuple(lp.shape) != (F, F)):
+        raise VdxError(f"temporal_attn_blend: lp must be a contiguous fp16 ({F}, {F}) tensor on {qkv.device}")
+    out, ldo = _out(out, M, inner, qkv, "temporal_attn_blend")
+    if out.data_ptr() == qkv.data_ptr():
+        raise VdxError("temporal_attn_blend: out may not alias qkv")
+    _launch("vdx_temporal_attn_blend_f16", _p(qkv, "qkv"), ld, _p(out, "out"), ldo, B, F, HW, heads, float(scale), int(radius),
+            lp.data_ptr())
+    return out
+
+
 def frame_gather(src, idx, out=None):
     """FreeNoise's noise rescheduling (include/vdx.h `vdx_frame_gather_f16`): out[:, :, t] = src[:, :, idx[t]] for a contiguous
     fp16 latent (1, C, T, h, w).  `idx`: T integers (a tensor on any device, or a sequence), every one checked here, on the

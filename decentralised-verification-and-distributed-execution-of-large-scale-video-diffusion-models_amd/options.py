@@ -315,6 +315,42 @@ def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = No
     return rec
 
 
+def check_free_long(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
+    """`cfg.free_long` / `cfg.free_long_method` as {"window", "d_t", "method"} (None when off); `ValueError` before any work for
+    values `freelong.check_params` refuses, a method without the option, a plan whose chunk is no longer than the window
+    (every frame's band would hold the whole chunk: there is nothing to blend) or longer than the kernel's 128 frames, and
+    together with `free_noise` (one of the two decides what a temporal attention sees) or `co_denoise` (and so its whole
+    family: it fuses whole-UNet windows, FreeLong runs the UNet once over the chunk).  The option's refusals live here, as
+    `free_noise`'s do: `RULES` lists the co-denoising family only.  `world` None: the initialised group's, else 1."""
+    fl, method = getattr(cfg, "free_long", None), getattr(cfg, "free_long_method", "gaussian")
+    if fl is None:
+        if method != "gaussian":
+            raise ValueError(f"free_long_method {method!r} needs free_long")
+        return None
+    from .freelong import MAX_FRAMES, check_params
+    from .planner import plan
+    if not isinstance(fl, (tuple, list)) or len(fl) != 2:
+        raise ValueError(f"free_long must be two numbers (window, d_t), got {fl!r}")
+    rec = check_params(fl[0], fl[1], method)
+    if getattr(cfg, "free_noise", None) is not None:
+        raise ValueError("free_long and free_noise exclude each other: each decides what a temporal attention sees")
+    if cfg.co_denoise:
+        raise ValueError("free_long and co_denoise exclude each other: co-denoising fuses whole-UNet windows, FreeLong runs the UNet "
+                         "once over the chunk")
+    try:
+        cp = plan(cfg.num_frames, world_size() if world is None else world, cfg.chunk_size, cfg.overlap, cfg.no_chunking, cfg.overlap_rule)
+    except PlannerError as err:
+        raise ValueError(f"free_long: {err}") from None
+    chunk = min(cp.chunk, cfg.num_frames)
+    if chunk <= rec["window"]:
+        raise ValueError(f"free_long: the plan's chunk of {chunk} frames is no longer than the window of {rec['window']}: there is "
+                         "nothing to blend; use --mode fsdp (the whole clip in one UNet call) or a larger --chunk_size")
+    if chunk > MAX_FRAMES:
+        raise ValueError(f"free_long: the plan's chunk of {chunk} frames exceeds the {MAX_FRAMES} the blended attention takes; use a "
+                         "smaller --chunk_size")
+    return {"window": rec["window"], "d_t": rec["d_t"], "method": rec["method"]}
+
+
 def check_deflicker(cfg) -> Optional[dict]:
     """`cfg.deflicker` / `cfg.deflicker_passes` as {"strength", "sigma", "passes"} (None when off); `ValueError` before any work
     unless `deflicker` is two numbers (strength in (0, 1], sigma finite and > 0, in grey levels), the passes are an integer in
@@ -547,6 +583,7 @@ class JobOptions:
     hypertile: Optional[dict] = None                                # HyperTile: {"grid", "max_downsample", "levels"} (vdx/hypertile.py)
     cross_frame: Optional[dict] = None                              # cross-frame attention: {"mode", "refs_per_frame", "max_downsample"} (vdx/crossframe.py)
     kv_downsample: Optional[dict] = None                            # key downsampling: {"factor", "max_downsample", "levels"} (vdx/kvdown.py)
+    free_long: Optional[dict] = None                                # FreeLong: {"window", "d_t", "method"} (vdx/freelong.py)
 
 
 def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, job: bool = False) -> JobOptions:
@@ -584,6 +621,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
         kv_downsample = check_kv_downsample(cfg)
+        free_long = check_free_long(cfg, exchange, world)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
         levels, sp = _stride(cfg, exchange, world)
@@ -603,13 +641,14 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
         kv_downsample = check_kv_downsample(cfg)
+        free_long = check_free_long(cfg, exchange, world)
     if phi != 0:
         guidance["guidance_rescale"] = phi
     return JobOptions(exchange=exchange, world=world, free_init_iters=iters, freeu=freeu, tome=tome, co_denoise=co, tile=tile,
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
                       cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker,
-                      hypertile=hypertile, cross_frame=cross_frame, kv_downsample=kv_downsample)
+                      hypertile=hypertile, cross_frame=cross_frame, kv_downsample=kv_downsample, free_long=free_long)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -640,6 +679,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(hypertile_record(opts))
     out.update(cross_frame_record(opts))
     out.update(kv_downsample_record(opts))
+    out.update(free_long_record(opts))
     return out
 
 
@@ -769,6 +809,16 @@ def kv_downsample_record(src) -> dict:
     if src.kv_downsample is None:
         return {}
     return {"kv_downsample": dict(src.kv_downsample)}
+
+
+def free_long_record(src) -> dict:
+    """`{"free_long": {"window", "d_t", "method"}}` beside `record_options`' entries, only when the option is set (else {}): from
+    the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"free_long": src["free_long"]} if "free_long" in src else {}
+    if src.free_long is None:
+        return {}
+    return {"free_long": dict(src.free_long)}
 
 
 def record_options(res: dict) -> dict:

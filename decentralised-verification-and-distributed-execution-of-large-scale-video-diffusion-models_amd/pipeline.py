@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import cross_frame_record, deflicker_record, free_noise_record, hypertile_record, info_options, job_texts, kv_downsample_record, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import cross_frame_record, deflicker_record, free_long_record, free_noise_record, hypertile_record, info_options, job_texts, kv_downsample_record, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -196,6 +196,14 @@ class DiffuserConfig:
     # with `tome`, `hypertile` or `cross_frame`.
     kv_downsample: Optional[int] = None
     kv_downsample_max_downsample: int = 1
+    # FreeLong (vdx/freelong.py, csrc/freelong.hip; Lu et al. 2024, restated in tests/freelong_ref.py and unpinned): (window, d_t).
+    # The UNet runs ONCE over every chunk longer than `window` frames; each of its temporal attentions is taken over all the
+    # chunk's frames and inside the band |t - j| <= window // 2 from one set of scores, and keeps the temporal frequencies the
+    # low-pass filter (`free_long_method`: "gaussian" | "butterworth" | "ideal", stop frequency d_t; only the temporal factor of
+    # the paper's 3-D filter) passes from the former and the rest from the latter.  The plan's chunk in (window, 128]
+    # (`--mode fsdp` or a large `--chunk_size`).  Not with `free_noise` or `co_denoise`.  None = full attention, as always
+    free_long: Optional[Tuple[int, float]] = None
+    free_long_method: str = "gaussian"
 
     @property
     def use_fsdp(self):
@@ -610,7 +618,7 @@ class DistributedVideoDiffuser:
         if self.latent_mask is not None and exchange == "halo":
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         iters, freeu, tome, free_noise = opts.free_init_iters, opts.freeu, opts.tome, opts.free_noise
-        hypertile, cross_frame, kv_downsample = opts.hypertile, opts.cross_frame, opts.kv_downsample
+        hypertile, cross_frame, kv_downsample, free_long = opts.hypertile, opts.cross_frame, opts.kv_downsample, opts.free_long
         tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
@@ -668,6 +676,10 @@ class DistributedVideoDiffuser:
             self.unet.enable_free_noise(free_noise["context_length"], free_noise["context_stride"], free_noise["weighting"])
             if cfg.use_ctx:                 # the context mean is the rescheduled start's, on every rank (the index is the seed's alone)
                 self.ctx = base.mean(dim=2, keepdim=True).contiguous()
+        if free_long is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            free_long0 = self.unet.free_long
+            self.unet.enable_free_long(free_long["window"], free_long["d_t"], free_long["method"])
         try:
             for it in range(iters):
                 if self._sde is not None:                              # every round draws streams of its own
@@ -710,6 +722,8 @@ class DistributedVideoDiffuser:
                     self.unet.enable_free_noise(free_noise0["context_length"], free_noise0["context_stride"], free_noise0["weighting"])
                 else:
                     self.unet.disable_free_noise()
+            if free_long is not None:
+                self.unet.enable_free_long(**free_long0) if free_long0 is not None else self.unet.disable_free_long()
         if iters > 1:
             self.free_init_starts = starts
             info["free_init"] = rec
@@ -822,6 +836,13 @@ def build_arg_parser():
                         "large --chunk_size; default: off)")
     p.add_argument("--free_noise_weighting", choices=["pyramid", "flat"], default="pyramid",
                    help="with --free_noise: a window's weight in a frame, min(j + 1, L - j) (pyramid, the default) or 1 (flat)")
+    p.add_argument("--free_long", type=float, nargs=2, default=None, metavar=("WINDOW", "D_T"),
+                   help="FreeLong: one UNet call per chunk longer than WINDOW frames, each temporal attention taken over all its frames "
+                        "and inside the band of WINDOW frames around each frame, the temporal frequencies below the stop frequency D_T "
+                        "from the former, the rest from the latter (only the temporal factor of the paper's 3-D filter is built; needs "
+                        "a chunk in (WINDOW, 128]: --mode fsdp or a large --chunk_size; not with --free_noise or --co_denoise; default: off)")
+    p.add_argument("--free_long_method", choices=["gaussian", "butterworth", "ideal"], default="gaussian",
+                   help="with --free_long: the low-pass filter along time (default: gaussian)")
     p.add_argument("--co_denoise", action="store_true",
                    help="temporal co-denoising: one latent for the whole clip, window predictions averaged at every step (default: off)")
     p.add_argument("--tile", type=int, nargs=2, default=None, metavar=("TH", "TW"),
@@ -880,6 +901,9 @@ def config_from_args(a) -> DiffuserConfig:
         cfg.freeu = tuple(cfg.freeu)
     if cfg.free_noise is not None:
         cfg.free_noise = tuple(cfg.free_noise)
+    if cfg.free_long is not None:               # WINDOW is an integer (a fraction stays a float, and is refused), D_T a float
+        w, d_t = cfg.free_long
+        cfg.free_long = (int(w) if w == int(w) else w, d_t)
     if cfg.hypertile is not None:
         cfg.hypertile = tuple(cfg.hypertile)
     if cfg.deflicker is not None:               # the flag is STRENGTH alone; the field is the pair
@@ -1143,7 +1167,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **kv_downsample_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **kv_downsample_record(info), **free_long_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1182,7 +1206,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1210,7 +1234,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

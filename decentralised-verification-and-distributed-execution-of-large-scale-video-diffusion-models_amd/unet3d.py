@@ -112,6 +112,8 @@ class UNet3DConditionModel(nn.Module):
         self._kv_downsample: Optional[Dict[str, object]] = None  # enable_kv_downsample's record {"factor", "max_downsample"}; None: off
         self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
         self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
+        self._free_long: Optional[Dict[str, object]] = None     # enable_free_long's record {"window", "d_t", "method", "order"}; None: off
+        self._free_long_tables: Dict[tuple, torch.Tensor] = {}   # (F, device) -> the blend matrix Lp fp16 [F][F]
 
     # ------------------------------------------------------------------------------------------
     # FreeU (Si et al. 2023; diffusers' enable_freeu / disable_freeu, unpinned; csrc/freeu.hip)
@@ -338,6 +340,8 @@ class UNet3DConditionModel(nn.Module):
         spatial layers, FreeU and token merging are untouched.  Refused with `ValueError`, the state left as it was: what
         `freenoise.check_params` refuses (2 <= context_length <= 32, 1 <= context_stride <= context_length)."""
         from .freenoise import check_params
+        if self._free_long is not None:
+            raise ValueError("enable_free_noise: FreeLong is enabled; disable_free_long() first")
         self._free_noise = check_params(context_length, context_stride, weighting_scheme)
         return self
 
@@ -365,6 +369,51 @@ class UNet3DConditionModel(nn.Module):
             from .freenoise import window_weights
             wn = self._free_noise_tables[key] = window_weights(F, L, S, weighting).to(device).contiguous()
         return L, S, wn
+
+    # ------------------------------------------------------------------------------------------
+    # FreeLong (Lu et al. 2024, restated and unpinned; vdx/freelong.py, csrc/freelong.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_free_long(self, window=24, d_t=0.25, method="gaussian", order=4):
+        """FreeLong's SpectralBlend temporal attention: from the next forward on, whenever a forward has F > window frames,
+        both attentions of every temporal transformer are taken globally over all F frames and locally inside the band
+        |t - j| <= window // 2 from one set of scores, and the result keeps the temporal frequencies the low-pass filter
+        (`method`, stop frequency `d_t`, `order` for "butterworth": the temporal factor of vdx/freeinit.py's filters) passes
+        from the global one and the rest from the local one (`ops.temporal_attn_blend`).  Only the temporal factor of the
+        paper's three-dimensional filter is built.  Those forwards take the unfused temporal path at every level, K7 blobs or
+        not, and F <= 128.  A forward with F <= window runs as without the switch, launch for launch.  Convolutions and
+        spatial layers are untouched.  Refused with `ValueError`, the state left as it was: what `freelong.check_params`
+        refuses, and enabling it while FreeNoise is on (one of the two decides what a temporal attention sees)."""
+        from .freelong import check_params
+        if self._free_noise is not None:
+            raise ValueError("enable_free_long: FreeNoise is enabled; disable_free_noise() first")
+        self._free_long = check_params(window, d_t, method, order)
+        self._free_long_tables = {}
+        return self
+
+    def disable_free_long(self):
+        """The forward is again the one without FreeLong, launch for launch."""
+        self._free_long = None
+        self._free_long_tables = {}
+        return self
+
+    @property
+    def free_long(self) -> Optional[Dict[str, object]]:
+        """{"window", "d_t", "method", "order"} while FreeLong is enabled, else None."""
+        return dict(self._free_long) if self._free_long is not None else None
+
+    def _free_long_plan(self, F, device):
+        """(radius, Lp fp16 (F, F) on `device`) for a forward of F frames, or None where the blend does not apply: disabled,
+        or the band of one window holds the whole sequence."""
+        fl = self._free_long
+        if fl is None or F <= fl["window"]:
+            return None
+        key = (F, str(device))
+        lp = self._free_long_tables.get(key)
+        if lp is None:
+            from .freelong import blend_matrix
+            lp = self._free_long_tables[key] = blend_matrix(F, fl["method"], fl["d_t"], fl["order"]).to(torch.float16).to(device).contiguous()
+        from .freelong import radius_of
+        return radius_of(fl["window"]), lp
 
     # ------------------------------------------------------------------------------------------
     # weights
@@ -973,7 +1022,8 @@ class UNet3DConditionModel(nn.Module):
         fused = self.fuse_temporal_attention and f"{b}.attn1.k7_qkv" in W and ops.temporal_attn_block_supported(t.shape[1], F)
         fused2 = self.fuse_temporal_attention and f"{b}.attn1.k7b" in W and ops.temporal_attn_block2_supported(t.shape[1], F)
         windows = self._free_noise_plan(F, t.device)      # FreeNoise: (L, S, wn) when on and F > L; the fused kernels have no windowed form
-        if windows is not None:
+        blend = self._free_long_plan(F, t.device)         # FreeLong: (radius, Lp) when on and F > window; never together with FreeNoise
+        if windows is not None or blend is not None:
             fused = fused2 = False
         for a, nm in (("attn1", "norm1"), ("attn2", "norm2")):
             if fused2:     # K7, second design (inner 320)
@@ -986,7 +1036,9 @@ class UNet3DConditionModel(nn.Module):
             ln = ops.layernorm(t, W[f"{b}.{nm}.weight"], W[f"{b}.{nm}.bias"], M=M)
             qkv = ops.gemm(ln, W[f"{b}.{a}.to_qkv.weight"], M=M)
             del ln
-            if windows is None:
+            if blend is not None:
+                o = ops.temporal_attn_blend(qkv, blend[1], B=B, F=F, HW=S, heads=heads, scale=scale, radius=blend[0])
+            elif windows is None:
                 o = ops.temporal_attn(qkv, B=B, F=F, HW=S, heads=heads, scale=scale)
             else:
                 o = ops.temporal_attn_windows(qkv, windows[2], B=B, F=F, HW=S, heads=heads, scale=scale, L=windows[0], S=windows[1])

@@ -931,6 +931,29 @@ int vdx_temporal_attn_windows_f16(const void* qkv, int ldqkv, void* out, int ldo
 int vdx_frame_gather_f16(const void* src, void* dst, const int32_t* idx, int C, int T, int HW, vdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FreeLong (Lu et al., "FreeLong: Training-Free Long Video Generation with SpectralBlend Temporal Attention", NeurIPS 2024,
+ * restated and unpinned; nothing in the reference; UNet3DConditionModel.enable_free_long, the job's --free_long,
+ * vdx/freelong.py, csrc/freelong.hip).  tests/freelong_ref.py states the definition.
+ * ------------------------------------------------------------------------------------------ */
+/* Spectrally blended temporal attention.  qkv, out, ldqkv, ldo, B, F, HW, heads, scale: as for vdx_temporal_attn_f16.  Per
+ * (b, pixel, head), with q, k, v its F x 64 blocks, a band radius r and lp, an fp16 [F][F] row-major matrix on the device
+ * (freelong.blend_matrix: the temporal low-pass filter as a real circulant; any matrix is taken):
+ *   S   = scale Q K^T
+ *   Zg  = softmax(S) V                       over all F keys
+ *   Zl  = softmax(S + M) V                   M[t][j] = 0 where |t - j| <= r, else -inf
+ *   out[t] = fp16( Zl[t] + sum_j lp[t][j] fp16(Zg[j] - Zl[j]) )
+ * Rounding points: scores in fp32; each softmax under its own row maximum (the local one under the band's), P = exp2(..) <= 1
+ * rounded to fp16 unnormalised, its row sum taken in fp32 from the unrounded values, Zg and Zl = (P V) / sum in fp32;
+ * D = Zg - Zl rounded to fp16 once; lp is fp16 as given; the sum over j in fp32 on the matrix unit in ascending j; Zl stays fp32
+ * until the one final rounding.  lp = 0 gives the local attention alone, lp = I vdx_temporal_attn_f16's result to rounding,
+ * r >= F - 1 the same whatever lp is.  No atomics: the same bits on every run and for any B and HW; NaN and inf stay inside
+ * their (pixel, head).  2 <= F <= 128, r >= 1, head dimension 64, qkv 16-byte aligned, out not overlapping qkv (refused).
+ * 16-byte reads of lp where F % 8 == 0 and lp is 16-byte aligned, 8-byte stores where ldo % 4 == 0 and out is 8-byte aligned,
+ * 2-byte ones otherwise.  One launch.                                                                                        */
+int vdx_temporal_attn_blend_f16(const void* qkv, int ldqkv, void* out, int ldo, int B, int F, int HW, int heads, float scale,
+                                int r, const void* lp, vdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Token merging (Bolya & Hoffman, "Token Merging for Stable Diffusion", CVPRW 2023; the tomesd package's
  * bipartite_soft_matching_random2d, unpinned) around a spatial self-attention, on rows [n_img][S][C] fp16 (nothing in the
  * reference; UNet3DConditionModel.enable_tome, the job's --tome, vdx/tome.py, csrc/tome.hip).  tests/tome_ref.py states the

@@ -85,6 +85,10 @@ SIGNATURES = {
     "vdx_flash_attn_frames_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
     # token downsampling: all queries of an image against every s-th row and column of its token grid, read in place (csrc/flash_kvdown.hip)
     "vdx_flash_attn_kvdown_f16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    # INT8 score product: the pre-pass that packs q^, k^ and their block scales, and the attention that reads them (csrc/flash_i8.hip)
+    "vdx_attn_quant_i8_workspace": (_sz, [_i, _i, _i]),
+    "vdx_attn_quant_i8": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "vdx_flash_attn_i8_f16": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "vdx_timestep_embedding_f16": (_i, [_vp, _vp, _i, _i, _vp]),
     "vdx_gelu_f16": (_i, [_vp, _vp, _sz, _vp]),
     "vdx_temporal_attn_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),

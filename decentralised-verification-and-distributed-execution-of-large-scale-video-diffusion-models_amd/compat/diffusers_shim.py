@@ -291,6 +291,13 @@ class DiffusionPipeline:
     def disable_kv_downsample(self):
         self.unet.disable_kv_downsample()
 
+    def enable_quant_attn(self, max_downsample=1):
+        """The int8 score product (SageAttention) as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_quant_attn`)."""
+        self.unet.enable_quant_attn(max_downsample)
+
+    def disable_quant_attn(self):
+        self.unet.disable_quant_attn()
+
     def enable_free_long(self, window=24, d_t=0.25, method="gaussian", order=4):
         """FreeLong's spectrally blended temporal attention as a pipeline method: the UNet's switch (vdx/unet3d.py `enable_free_long`)."""
         self.unet.enable_free_long(window, d_t, method, order)

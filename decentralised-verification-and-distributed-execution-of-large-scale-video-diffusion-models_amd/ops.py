@@ -795,6 +795,63 @@ def flash_attn_kvdown(q, k, v, *, n_img, hh, ww, s, heads, scale, out=None):
     return out
 
 
+def attn_quant_i8_workspace(n_img, S, heads, device):
+    """A uint8 workspace of `vdx_attn_quant_i8_workspace` bytes on `device` for `attn_quant_i8` / `flash_attn_i8`."""
+    nbytes = _lib.load().vdx_attn_quant_i8_workspace(int(n_img), int(S), int(heads))
+    if nbytes == 0:
+        raise VdxError(f"attn_quant_i8: the library refuses n_img={n_img}, S={S}, heads={heads}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _quant_i8_views(ws, n_img, S, heads):
+    """(q8, k8, dq, dk) of a workspace: int8 [n_img][heads][S_pad][64] twice, fp32 [n_img][heads][S_pad / 64] twice (the
+    layout of include/vdx.h `vdx_attn_quant_i8`)."""
+    nb = (S + 63) // 64
+    a, b = n_img * heads * nb * 64 * 64, round_up(n_img * heads * nb * 4, 16)
+    i8 = [ws[o:o + a].view(torch.int8).view(n_img, heads, nb * 64, 64) for o in (0, a)]
+    f32 = [ws[o:o + n_img * heads * nb * 4].view(torch.float32).view(n_img, heads, nb) for o in (2 * a, 2 * a + b)]
+    return (*i8, *f32)
+
+
+def attn_quant_i8(q, k, *, n_img, S, heads, scale, workspace=None):
+    """The INT8 attention's pre-pass (include/vdx.h `vdx_attn_quant_i8`, csrc/flash_i8.hip): q, k rows [n_img*S][>= heads*64]
+    as `flash_attn(..., v_rows=True)` takes them -> (q8, k8, dq, dk), views of the workspace: the keys minus their per-image
+    mean and the queries times scale*log2(e), as int8 with one fp32 scale per block of 64 tokens."""
+    n_img, S, heads = int(n_img), int(S), int(heads)
+    M, inner = n_img * S, heads * 64
+    ptrs = []
+    for t, name in ((q, "q"), (k, "k")):
+        r, c, ld = _rows(t, name)
+        if r < M or c < inner:
+            raise VdxError(f"attn_quant_i8: {name} too small")
+        ptrs += [_p(t, name), ld]
+    if workspace is None:
+        workspace = attn_quant_i8_workspace(n_img, S, heads, q.device)
+    with _timed("attn_quant_i8_kernel", 0.0, (M, inner)):
+        _launch("vdx_attn_quant_i8", *ptrs, n_img, S, heads, float(scale), _p(workspace, "workspace", torch.uint8), workspace.numel())
+    return _quant_i8_views(workspace, n_img, S, heads)
+
+
+def flash_attn_i8(q, k, v, *, n_img, S, heads, scale, out=None, workspace=None):
+    """Spatial self-attention with the INT8 score product (include/vdx.h `vdx_flash_attn_i8_f16`): the pre-pass
+    `attn_quant_i8` on q and k, then per (image, head) softmax of the int32 scores times their block scales, P.V in fp16 as
+    `flash_attn` has it.  q, k, v rows [n_img*S][>= heads*64] (the column blocks of one q|k|v projection); `workspace`: a
+    reusable `attn_quant_i8_workspace`."""
+    n_img, S, heads = int(n_img), int(S), int(heads)
+    M, inner = n_img * S, heads * 64
+    r, c, ldv = _rows(v, "v")
+    if r < M or c < inner:
+        raise VdxError("flash_attn_i8: v too small")
+    if workspace is None:
+        workspace = attn_quant_i8_workspace(n_img, S, heads, q.device)
+    attn_quant_i8(q, k, n_img=n_img, S=S, heads=heads, scale=scale, workspace=workspace)
+    out, ldo = _out(out, M, inner, q, "flash_attn_i8")
+    with _timed(f"flash_attn_i8_kernel<{2 if S >= 512 else 1}>", 4.0 * n_img * heads * S * S * 64, (M, S, inner)):
+        _launch("vdx_flash_attn_i8_f16", _p(workspace, "workspace", torch.uint8), workspace.numel(), _p(v, "v"), ldv, _p(out, "out"), ldo,
+                n_img, S, heads)
+    return out
+
+
 def temporal_attn(qkv, *, B, F, HW, heads, scale, out=None):
     r, c, ld = _rows(qkv, "qkv")
     inner = heads * 64

@@ -271,6 +271,28 @@ def check_kv_downsample(cfg) -> Optional[dict]:
     return {"factor": s, "max_downsample": md, "levels": levels(params, hh, ww)}
 
 
+def check_quant_attn(cfg) -> Optional[dict]:
+    """`cfg.quant_attn` / `cfg.quant_attn_max_downsample` as {"mode", "max_downsample", "levels"} (None when off); `ValueError`
+    before any work unless quant_attn is a bool and the max_downsample one of 1, 2, 4, 8, and together with `tome`, `hypertile`,
+    `cross_frame` or `kv_downsample` (each owns the attention's data path).  The option's refusals live here: `RULES` lists the
+    co-denoising family only."""
+    on, md = getattr(cfg, "quant_attn", False), getattr(cfg, "quant_attn_max_downsample", 1)
+    if not isinstance(on, bool):
+        raise ValueError(f"quant_attn must be True or False, got {on!r}")
+    if not on:
+        if md != 1:
+            raise ValueError(f"quant_attn_max_downsample {md!r} needs quant_attn")
+        return None
+    from .quantattn import check_params, levels
+    params = check_params(md)
+    for other in ("tome", "hypertile", "cross_frame", "kv_downsample"):
+        if getattr(cfg, other, None) is not None:
+            raise ValueError(f"quant_attn and {other} exclude each other: each owns the self-attention's data path")
+    tile = getattr(cfg, "tile", None)          # the UNet's frame is a tile where tiling is on, else the whole latent frame
+    hh, ww = (int(tile[0]) // 8, int(tile[1]) // 8) if tile is not None else (cfg.height // 8, cfg.width // 8)
+    return {**params, "levels": levels(params, hh, ww)}
+
+
 def check_free_noise(cfg, exchange: str = "allgather", world: Optional[int] = None) -> Optional[dict]:
     """`cfg.free_noise` / `cfg.free_noise_weighting` as {"context_length", "context_stride", "weighting", "windows"} (None when
     off), `windows` being the windows of one chunk of the plan; `ValueError` before any work for values outside the kernel's
@@ -583,6 +605,7 @@ class JobOptions:
     hypertile: Optional[dict] = None                                # HyperTile: {"grid", "max_downsample", "levels"} (vdx/hypertile.py)
     cross_frame: Optional[dict] = None                              # cross-frame attention: {"mode", "refs_per_frame", "max_downsample"} (vdx/crossframe.py)
     kv_downsample: Optional[dict] = None                            # key downsampling: {"factor", "max_downsample", "levels"} (vdx/kvdown.py)
+    quant_attn: Optional[dict] = None                               # int8 score product: {"mode", "max_downsample", "levels"} (vdx/quantattn.py)
     free_long: Optional[dict] = None                                # FreeLong: {"window", "d_t", "method"} (vdx/freelong.py)
 
 
@@ -621,6 +644,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
         kv_downsample = check_kv_downsample(cfg)
+        quant_attn = check_quant_attn(cfg)
         free_long = check_free_long(cfg, exchange, world)
     else:
         co, tile, loop = check_co_denoise(cfg, exchange), check_tile(cfg, exchange), check_loop(cfg, exchange, world)
@@ -641,6 +665,7 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
         hypertile = check_hypertile(cfg)
         cross_frame = check_cross_frame(cfg)
         kv_downsample = check_kv_downsample(cfg)
+        quant_attn = check_quant_attn(cfg)
         free_long = check_free_long(cfg, exchange, world)
     if phi != 0:
         guidance["guidance_rescale"] = phi
@@ -648,7 +673,8 @@ def resolve(cfg, exchange: str = "allgather", world: Optional[int] = None, *, jo
                       loop=loop, context_stride=levels, stride_plan=sp, interpolate=factor, pixel_mask=pixel_mask,
                       guidance_rescale=phi, guidance=guidance, prompt_travel=travel, regions=regions, lora=lora, prompt_syntax=syntax,
                       cfg_mimic=mimic, noise=noise, sampler_noise=sde, free_noise=free_noise, deflicker=deflicker,
-                      hypertile=hypertile, cross_frame=cross_frame, kv_downsample=kv_downsample, free_long=free_long)
+                      hypertile=hypertile, cross_frame=cross_frame, kv_downsample=kv_downsample, free_long=free_long,
+                      quant_attn=quant_attn)
 
 
 # ---- the options' entries in `info`, the result dict and the JSON records -----------------------------------------------------
@@ -679,6 +705,7 @@ def info_options(opts: JobOptions, rounds) -> dict:
     out.update(hypertile_record(opts))
     out.update(cross_frame_record(opts))
     out.update(kv_downsample_record(opts))
+    out.update(quant_attn_record(opts))
     out.update(free_long_record(opts))
     return out
 
@@ -819,6 +846,16 @@ def free_long_record(src) -> dict:
     if src.free_long is None:
         return {}
     return {"free_long": dict(src.free_long)}
+
+
+def quant_attn_record(src) -> dict:
+    """`{"quant_attn": {"mode", "max_downsample", "levels"}}` beside `record_options`' entries, only when the option is set
+    (else {}): from the resolved options, or copied from a dict (`info`, the result) that holds the entry."""
+    if isinstance(src, dict):
+        return {"quant_attn": src["quant_attn"]} if "quant_attn" in src else {}
+    if src.quant_attn is None:
+        return {}
+    return {"quant_attn": dict(src.quant_attn)}
 
 
 def record_options(res: dict) -> dict:

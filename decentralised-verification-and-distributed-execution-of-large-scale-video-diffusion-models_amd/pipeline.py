@@ -38,7 +38,7 @@ from .codenoise import co_denoise_round, loop_plan_of, tile_plan
 from .inpaint import known_coefficients, mask_record
 from .halo import HaloPlan, blend_owned, exchange_halos, ramp_weights
 from .options import JobOptions, check_cfg_mimic, check_eta, check_free_init, check_freeu, check_guidance_rescale, check_noise, check_tome  # the checks' home is vdx/options.py
-from .options import cross_frame_record, deflicker_record, free_long_record, free_noise_record, hypertile_record, info_options, job_texts, kv_downsample_record, lora_record, mimic_record, noise_record, prompt_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
+from .options import cross_frame_record, deflicker_record, free_long_record, free_noise_record, hypertile_record, info_options, job_texts, kv_downsample_record, lora_record, mimic_record, noise_record, prompt_record, quant_attn_record, record_options, region_record, resolve, sampler_noise_record, travel_record, world_size
 from .planner import ChunkPlan, plan
 
 
@@ -196,6 +196,11 @@ class DiffuserConfig:
     # with `tome`, `hypertile` or `cross_frame`.
     kv_downsample: Optional[int] = None
     kv_downsample_max_downsample: int = 1
+    # INT8 score product (vdx/quantattn.py, csrc/flash_i8.hip; SageAttention, Zhang et al. 2025, unpinned): the plain spatial
+    # self-attentions of the levels with downsample factor d <= `quant_attn_max_downsample` compute Q.K^T in int8 on mean-smoothed
+    # keys with one scale per 64 tokens; softmax and P.V stay fp16.  Not with `tome`, `hypertile`, `cross_frame` or `kv_downsample`.
+    quant_attn: bool = False
+    quant_attn_max_downsample: int = 1
     # FreeLong (vdx/freelong.py, csrc/freelong.hip; Lu et al. 2024, restated in tests/freelong_ref.py and unpinned): (window, d_t).
     # The UNet runs ONCE over every chunk longer than `window` frames; each of its temporal attentions is taken over all the
     # chunk's frames and inside the band |t - j| <= window // 2 from one set of scores, and keeps the temporal frequencies the
@@ -619,6 +624,7 @@ class DistributedVideoDiffuser:
             raise ValueError("latent_mask needs exchange=\"allgather\": the paste after the blend needs the whole latent on every rank")
         iters, freeu, tome, free_noise = opts.free_init_iters, opts.freeu, opts.tome, opts.free_noise
         hypertile, cross_frame, kv_downsample, free_long = opts.hypertile, opts.cross_frame, opts.kv_downsample, opts.free_long
+        quant_attn = opts.quant_attn
         tiles = tile_plan(cfg.height // 8, cfg.width // 8, *opts.tile) if opts.tile is not None else None
         co_recs = [] if opts.co_denoise else None                      # co_denoise: the rounds' records
         cp = self.plan()
@@ -666,6 +672,10 @@ class DistributedVideoDiffuser:
             # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
             cross_frame0 = self.unet.cross_frame
             self.unet.enable_cross_frame(cross_frame["mode"], max_downsample=cross_frame["max_downsample"])
+        if quant_attn is not None:
+            # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
+            quant_attn0 = self.unet.quant_attn
+            self.unet.enable_quant_attn(quant_attn["max_downsample"])
         if kv_downsample is not None:
             # like FreeU: enabled for the length of the call, the UNet handed back in the state it came in
             kv_downsample0 = self.unet.kv_downsample
@@ -715,6 +725,8 @@ class DistributedVideoDiffuser:
                     self.unet.enable_cross_frame(cross_frame0["mode"], max_downsample=cross_frame0["max_downsample"])
                 else:
                     self.unet.disable_cross_frame()
+            if quant_attn is not None:
+                self.unet.enable_quant_attn(quant_attn0["max_downsample"]) if quant_attn0 is not None else self.unet.disable_quant_attn()
             if kv_downsample is not None:
                 self.unet.enable_kv_downsample(**kv_downsample0) if kv_downsample0 is not None else self.unet.disable_kv_downsample()
             if free_noise is not None:
@@ -827,6 +839,11 @@ def build_arg_parser():
     p.add_argument("--kv_downsample", type=int, default=None, metavar="S",
                    help="token downsampling (ToDo): the spatial self-attention of a frame keeps every query and takes its keys and values "
                         "from every S-th row and column of the frame, S in 2..8 (not with --tome, --hypertile or --cross_frame; default: off)")
+    p.add_argument("--quant_attn", action="store_true",
+                   help="int8 score product (SageAttention): the plain spatial self-attentions compute Q.K^T in int8 on mean-smoothed keys, "
+                        "softmax and P.V stay fp16 (not with --tome, --hypertile, --cross_frame or --kv_downsample; default: off)")
+    p.add_argument("--quant_attn_max_downsample", type=int, default=1, metavar="D",
+                   help="with --quant_attn: the levels with downsample factor up to D (1, 2, 4 or 8) take the int8 path (default 1: level 0)")
     p.add_argument("--kv_downsample_max_downsample", type=int, default=1, metavar="D",
                    help="with --kv_downsample: the levels with downsample factor up to D (1, 2, 4 or 8) take the factor S // d (default 1: level 0)")
     p.add_argument("--tome_seed", type=int, default=None, help="token merging: draw the cells' destination offsets once from this seed")
@@ -1167,7 +1184,7 @@ def run_job(cfg: DiffuserConfig, exchange: str = "allgather", out_video: Optiona
             "scheduler": cfg.scheduler, "interpolate": factor, "frames_written": frames_written,
             **({"free_init": info["free_init"]} if "free_init" in info else {}),
             **record_options({**info, **mask, **opts.guidance}), **travel_record(info), **region_record(info), **mimic_record(info), **lora_record(info),
-            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **kv_downsample_record(info), **free_long_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
+            **prompt_record(info), **noise_record(info), **sampler_noise_record(info), **free_noise_record(info), **deflicker_record(info), **hypertile_record(info), **cross_frame_record(info), **kv_downsample_record(info), **free_long_record(info), **quant_attn_record(info), **({"gif": {k: gif_info[k] for k in GIF_RECORD_KEYS}} if gif_info else {})}
 
 
 GIF_RECORD_KEYS = ("frames", "colors", "bytes", "delay_cs", "dither", "strip_rows")
@@ -1206,7 +1223,7 @@ def main(argv=None) -> int:
         metrics.append_csv(cfg.out_csv, row)
         print(f"Metrics appended ->  {cfg.out_csv}")
         source = {**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **gif_record(res)}
+                  **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **quant_attn_record(res), **gif_record(res)}
         scored = cfg.prompt
         if "prompt_syntax" in res:
             # the scores know no weights and CLIP ViT-B/32 truncates at its own 77 tokens: they are taken against --prompt with the
@@ -1234,7 +1251,7 @@ def main(argv=None) -> int:
             from . import compare
             rec = compare_record(generated, a.compare_to, clip_inputs["ranges"], clip_inputs["device"])
             rec.update({**record_options(res), **travel_record(res), **region_record(res), **mimic_record(res), **lora_record(res), **prompt_record(res),
-                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **gif_record(res)})
+                        **noise_record(res), **sampler_noise_record(res), **free_noise_record(res), **deflicker_record(res), **hypertile_record(res), **cross_frame_record(res), **kv_downsample_record(res), **free_long_record(res), **quant_attn_record(res), **gif_record(res)})
             write_record(a.compare_json, rec, compare.dumps)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -110,6 +110,8 @@ class UNet3DConditionModel(nn.Module):
         self._cross_frame: Optional[Dict[str, object]] = None  # enable_cross_frame's record {"mode", "refs_per_frame", "max_downsample"}; None: off
         self._cross_frame_tables: Dict[tuple, torch.Tensor] = {}  # (F, device) -> the reference table int32 [F][R] on the device
         self._kv_downsample: Optional[Dict[str, object]] = None  # enable_kv_downsample's record {"factor", "max_downsample"}; None: off
+        self._quant_attn: Optional[Dict[str, object]] = None    # enable_quant_attn's record {"mode", "max_downsample"}; None: off
+        self._quant_attn_ws: Dict[tuple, torch.Tensor] = {}     # (n_img, S, heads, device) -> the int8 workspace of that forward shape
         self._free_noise: Optional[Dict[str, object]] = None    # enable_free_noise's record {"context_length", "context_stride", "weighting"}; None: off
         self._free_noise_tables: Dict[tuple, torch.Tensor] = {}  # (F, L, S, weighting, device) -> the windows' weight table fp32 [n][L]
         self._free_long: Optional[Dict[str, object]] = None     # enable_free_long's record {"window", "d_t", "method", "order"}; None: off
@@ -163,6 +165,8 @@ class UNet3DConditionModel(nn.Module):
             raise ValueError("enable_tome: cross-frame attention is enabled and merged rows differ from frame to frame; disable_cross_frame() first")
         if self._kv_downsample is not None:
             raise ValueError("enable_tome: key downsampling is enabled and merged rows have no 2-D grid to downsample; disable_kv_downsample() first")
+        if self._quant_attn is not None:
+            raise ValueError("enable_tome: the int8 attention is enabled and owns the attention's data path; disable_quant_attn() first")
         self._tome = params
         self._tome_tables = {}
         return self
@@ -212,6 +216,8 @@ class UNet3DConditionModel(nn.Module):
             raise ValueError("enable_hypertile: cross-frame attention is enabled and its keys are whole frames; disable_cross_frame() first")
         if self._kv_downsample is not None:
             raise ValueError("enable_hypertile: key downsampling is enabled and its keys span the whole frame; disable_kv_downsample() first")
+        if self._quant_attn is not None:
+            raise ValueError("enable_hypertile: the int8 attention is enabled and owns the attention's data path; disable_quant_attn() first")
         self._hypertile = params
         return self
 
@@ -225,10 +231,17 @@ class UNet3DConditionModel(nn.Module):
         """{"grid": (ny, nx), "max_downsample"} while HyperTile is enabled, else None."""
         return dict(self._hypertile) if self._hypertile is not None else None
 
-    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None, frames=None, kvd=None):
+    def _attn1(self, qkv, C, n_img, hh, ww, heads, scale, win, out=None, frames=None, kvd=None, i8=False):
         """The self-attention core on one q|k|v projection's rows: inside the windows of the grid `win`, against the reference
-        frames of `frames` = (F, the device table), against the keys of every `kvd`-th row and column, or plain (all None)."""
+        frames of `frames` = (F, the device table), against the keys of every `kvd`-th row and column, with the int8 score
+        product (`i8`), or plain (all None / False)."""
         q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if i8:
+            key = (n_img, hh * ww, heads, str(qkv.device))
+            ws = self._quant_attn_ws.get(key)
+            if ws is None:
+                ws = self._quant_attn_ws[key] = ops.attn_quant_i8_workspace(n_img, hh * ww, heads, qkv.device)
+            return ops.flash_attn_i8(q, k, v, n_img=n_img, S=hh * ww, heads=heads, scale=scale, out=out, workspace=ws)
         if kvd is not None:
             return ops.flash_attn_kvdown(q, k, v, n_img=n_img, hh=hh, ww=ww, s=kvd, heads=heads, scale=scale, out=out)
         if frames is not None:
@@ -254,8 +267,9 @@ class UNet3DConditionModel(nn.Module):
         token merging or HyperTile enabled; a table that does not fit the forward's F raises in the forward."""
         from .crossframe import check_params
         params = check_params(mode, max_downsample)
-        if self._tome is not None or self._hypertile is not None or self._kv_downsample is not None:
-            which = "token merging" if self._tome is not None else "HyperTile" if self._hypertile is not None else "key downsampling"
+        if self._tome is not None or self._hypertile is not None or self._kv_downsample is not None or self._quant_attn is not None:
+            which = ("token merging" if self._tome is not None else "HyperTile" if self._hypertile is not None
+                     else "key downsampling" if self._kv_downsample is not None else "the int8 attention")
             raise ValueError(f"enable_cross_frame: {which} is enabled and changes the rows a frame's keys are read from; disable it first")
         self._cross_frame = params
         self._cross_frame_tables = {}
@@ -302,7 +316,8 @@ class UNet3DConditionModel(nn.Module):
         cross-frame attention enabled (each changes which rows are keys)."""
         from .kvdown import check_params
         params = check_params(factor, max_downsample)
-        for on, which in ((self._tome, "token merging"), (self._hypertile, "HyperTile"), (self._cross_frame, "cross-frame attention")):
+        for on, which in ((self._tome, "token merging"), (self._hypertile, "HyperTile"), (self._cross_frame, "cross-frame attention"),
+                          (self._quant_attn, "the int8 attention")):
             if on is not None:
                 raise ValueError(f"enable_kv_downsample: {which} is enabled and changes which rows are keys; disable it first")
         self._kv_downsample = params
@@ -326,6 +341,37 @@ class UNet3DConditionModel(nn.Module):
         from .kvdown import level_factor
         s = level_factor(self._kv_downsample, down)
         return s if s > 1 and hh // s >= 1 and ww // s >= 1 else None
+
+    # ------------------------------------------------------------------------------------------
+    # INT8 score product (SageAttention, Zhang et al. 2025; unpinned; vdx/quantattn.py, csrc/flash_i8.hip)
+    # ------------------------------------------------------------------------------------------
+    def enable_quant_attn(self, max_downsample=1):
+        """From the next forward on, the plain spatial self-attentions (`attn1`) of the levels whose downsample factor is at most
+        `max_downsample` compute Q.K^T in int8: `ops.flash_attn_i8` quantises the q and k columns of the one q|k|v projection
+        (keys minus their per-image mean, one scale per 64 tokens) into a workspace held per forward shape and runs the
+        attention from it; softmax and P.V are the fp16 kernel's.  Two launches are added per attention; LayerNorm, the
+        projection and `to_out` + residual run as before.  Cross-attention, feed-forward, temporal transformers, the VAE and
+        CLIP are untouched.  Refused with `ValueError`, the state left as it was: a max_downsample outside {1, 2, 4, 8}, token
+        merging, HyperTile, cross-frame attention or key downsampling enabled (each owns the attention's data path)."""
+        from .quantattn import check_params
+        params = check_params(max_downsample)
+        for on, which in ((self._tome, "token merging"), (self._hypertile, "HyperTile"), (self._cross_frame, "cross-frame attention"),
+                          (self._kv_downsample, "key downsampling")):
+            if on is not None:
+                raise ValueError(f"enable_quant_attn: {which} is enabled and owns the attention's data path; disable it first")
+        self._quant_attn = params
+        return self
+
+    def disable_quant_attn(self):
+        """The forward is again the one without the int8 attention, launch for launch; the workspaces are dropped."""
+        self._quant_attn = None
+        self._quant_attn_ws = {}
+        return self
+
+    @property
+    def quant_attn(self) -> Optional[Dict[str, object]]:
+        """{"mode", "max_downsample"} while the int8 attention is enabled, else None."""
+        return dict(self._quant_attn) if self._quant_attn is not None else None
 
     # ------------------------------------------------------------------------------------------
     # FreeNoise (Qiu et al. 2024; diffusers' enable_free_noise, unpinned; vdx/freenoise.py, csrc/freenoise.hip)
@@ -821,7 +867,7 @@ class UNet3DConditionModel(nn.Module):
 
     def _self_attention(self, b, t, n_img, hh, ww, down=1, F=None):
         """`t + attn1(norm1(t))` of transformer block b on the rows t [n_img * hh * ww][C]; `down`: the level's downsample
-        factor (token merging, HyperTile, cross-frame attention and key downsampling apply up to their max_downsample); `F`: the frames per
+        factor (token merging, HyperTile, cross-frame attention, key downsampling and the int8 attention apply up to their max_downsample); `F`: the frames per
         sample, the images being samples of F consecutive frames (cross-frame attention needs it; None: unknown, plain)."""
         W = self.W
         S = hh * ww
@@ -841,6 +887,7 @@ class UNet3DConditionModel(nn.Module):
             win = window_grid(self._hypertile, hh, ww, down)
         frames = self._cross_frame_plan(F, n_img, down, t.device)      # cross-frame attention: (F, table), None where plain
         kvd = self._kv_downsample_factor(hh, ww, down)                 # key downsampling: the level's factor, None where plain
+        i8 = self._quant_attn is not None and down <= self._quant_attn["max_downsample"]   # the int8 score product
         if tome is not None:
             # token merging: the block's input t is the metric; the attention runs on S - r rows per image (the single q|k|v
             # path, whatever the memory-lean switches say) and every token reads its merged row back under the residual
@@ -869,10 +916,10 @@ class UNet3DConditionModel(nn.Module):
             hm, hn = M // 2, n_img // 2
             for r0 in (0, hm):
                 qkv = ops.gemm(ln[r0:r0 + hm], wqkv, M=hm)
-                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm], frames=frames, kvd=kvd)
+                self._attn1(qkv, C, hn, hh, ww, heads, scale, win, out=o[r0:r0 + hm], frames=frames, kvd=kvd, i8=i8)
                 del qkv
             del ln
-        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None and frames is None and kvd is None:
+        elif not self.spatial_v_rows and S % 8 == 0 and M % 64 == 0 and win is None and frames is None and kvd is None and not i8:
             # the round-2 form, kept for same-process A/B timing (tools/step_ab.py): q|k GEMM + V^T by the swapped GEMM
             qk = ops.gemm(ln, wqkv[:2 * C], M=M)
             vt = ops.gemm(wqkv[2 * C:], ln, M=C)
@@ -882,7 +929,7 @@ class UNet3DConditionModel(nn.Module):
         else:
             qkv = ops.gemm(ln, wqkv, M=M)
             del ln
-            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win, frames=frames, kvd=kvd)
+            o = self._attn1(qkv, C, n_img, hh, ww, heads, scale, win, frames=frames, kvd=kvd, i8=i8)
             del qkv
         if tome is None:
             t = ops.gemm(o, W[b + ".attn1.to_out.0.weight"], M=M, bias=W[b + ".attn1.to_out.0.bias"], residual=t)

@@ -279,8 +279,32 @@ int vdx_flash_attn_frames_f16(const void* q, int ldq, const void* k, int ldk, co
 int vdx_flash_attn_kvdown_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                               void* out, int ldo, int n_img, int hh, int ww, int s,
                               int heads, float scale, vdx_stream_t stream);
+/* INT8 score product for the spatial self-attention (SageAttention, Zhang et al., ICLR 2025, restated): a pre-pass that
+ * quantises q and k into a packed workspace, and the attention kernel that reads it.  Per image and head, with Q, K, V the
+ * S x 64 blocks of the row matrices of vdx_flash_attn_rows_f16 ([n_img*S][ld], head h at columns h*64.., V as rows):
+ *   kbar = mean over the image's S keys of K, per channel, in fp32, in a fixed order (rows g, g + 32, ... ascending into 32
+ *          partial sums, those added in ascending g, one IEEE division by S);   K' = K - kbar  (softmax does not see it);
+ *   Q'   = Q (scale log2 e) in fp32, the factor rounded to fp32 once;
+ *   a block is 64 consecutive tokens of one image and head (the last may be short); amax = max |x| over its values;
+ *   delta = amax / 127 in fp32, 1 for an all-zero block;   x^ = clamp(rint(x / delta), -127, 127) as int8 (IEEE division,
+ *   round-half-even);   S^ = Q^ K^^T in exact int32;   s = fp32(S^) (delta_Q delta_K), which carries scale log2 e;
+ *   out = softmax_2(s) V with the online base-2 softmax, P in fp16, fp32 row sums, P.V on fp16 MFMAs and one final rounding
+ *   exactly as vdx_flash_attn_rows_f16 has them.
+ * Workspace (vdx_attn_quant_i8_workspace bytes, 16-byte aligned; 0: the sizes are refused), in this order, with
+ * S_pad = ceil(S / 64) 64:  q8 int8 [n_img][heads][S_pad][64], k8 the same (tail rows zero), dq fp32 [n_img][heads][S_pad/64]
+ * padded to 16 bytes, dk the same, then the key means fp32 [n_img][heads][64].
+ * No atomics, the same bits on every run and for any n_img.  A NaN or inf in q or k makes its block's delta NaN and with it
+ * the output rows of its own (image, head) that meet the block; no other (image, head) sees it.
+ * Refused (both): a null pointer, n_img, S or heads < 1, a leading dimension that is no multiple of 8 or below heads*64 (head
+ * dimension 64 only), a pointer that is not 16-byte aligned, S above 2^24, 2^31 rows or blocks or more, a workspace below the
+ * size; vdx_attn_quant_i8: a workspace that meets q or k; vdx_flash_attn_i8_f16: out meeting v or the workspace. */
+size_t vdx_attn_quant_i8_workspace(int n_img, int S, int heads);
+int vdx_attn_quant_i8(const void* q, int ldq, const void* k, int ldk, int n_img, int S, int heads, float scale,
+                      void* workspace, size_t workspace_bytes, vdx_stream_t stream);
+int vdx_flash_attn_i8_f16(const void* workspace, size_t workspace_bytes, const void* v, int ldv, void* out, int ldo,
+                          int n_img, int S, int heads, vdx_stream_t stream);
 
-/* K8 — the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
+/* K8— the feed-forward sub-block of BasicTransformerBlock (`t = t + ff(norm3(t))`, GEGLU with the
  * erf GELU, both in Transformer2DModel and TransformerTemporalModel) as ONE kernel: LayerNorm -> [val | gate] projection ->
  * val * gelu(gate) -> output projection (+bias) + residual; the [rows][4*inner] intermediate never leaves the CU
  * (csrc/ff_fused.hip).  Built for inner 320 (level 0).  Its GELU is a polynomial in clamp(gate, -4.5, 4.5): within
